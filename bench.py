@@ -11,6 +11,9 @@ One step = one engine forward over `--pairs` image pairs per rank. At N > 1 rank
 pairwise predictions (dust3r_amd/parallel.py), issued asynchronously so that it overlaps the next step's compute.
 
 Usage: python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c5]   (N > 1: launched by torch.distributed.run, one rank per GPU)
+  --dump-outputs DIR: after the timed steps, what the last step returned (c2: the four forward result tensors; c3 / c5: those of the job's pairs,
+                 c5 also the aligned scene's poses, focals, principal points and depth maps) as DIR/<name>.npy in float32, at most 64 MB in all: a fixed,
+                 seeded sample of the pairs (and views) when there are more. Inputs and weights are seeded, so two builds can be compared file for file.
   --workload c2 (default): BASELINE configs[1], the configuration the metric is quoted on -- what the paragraph above describes.
   --workload c3: configs[2], 20 synthetic views -> make_pairs('complete', symmetrize=False) = 190 pairs, contiguous shards of
                  ceil(190 / N) pairs per rank, every distinct image of a shard encoded once, ONE all-gather per step; a step = the
@@ -148,6 +151,38 @@ def emit(result):
             return [clean(v) for v in o]
         return o
     print(json.dumps(clean(result), allow_nan=False), flush=True)
+
+
+DUMP_BUDGET = 63_000_000        # --dump-outputs: bytes of array data over all files (64 MB with the .npy headers)
+
+
+def dump_sample(n, item_bytes, budget):
+    """--dump-outputs: which of `n` items of `item_bytes` each to write so that they fit in `budget` bytes -- every item when they all fit,
+    else a fixed, seeded sample (sorted indices), the same on every run."""
+    k = min(n, max(1, budget // item_bytes))
+    if k == n:
+        return list(range(n))
+    return sorted(torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].tolist())
+
+
+def pred_arrays(pred1, pred2):
+    """The four result tensors of a forward (what inference() hands its caller), keyed by their --dump-outputs file name."""
+    return {'pred1_pts3d': pred1['pts3d'], 'pred1_conf': pred1['conf'], 'pred2_pts3d_in_other_view': pred2['pts3d_in_other_view'], 'pred2_conf': pred2['conf']}
+
+
+def dump_outputs(out_dir, arrays, sample):
+    """--dump-outputs: every tensor of `arrays` (file name -> tensor) as out_dir/<name>.npy, float64 kept, everything else as float32.
+    Returns the block the JSON line carries: the files with their shapes, the bytes written and which items `sample` says were kept."""
+    import numpy as np
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: (a if a.dtype == np.float64 else a.astype(np.float32)) for k, a in host.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_BUDGET, f'--dump-outputs: {total} bytes exceed the budget of {DUMP_BUDGET}'
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    log(f'[bench] dumped {len(host)} arrays ({total / 1e6:.1f} MB) to {out_dir}: sample {sample}')
+    return dict(dir=out_dir, bytes=total, files={k + '.npy': list(a.shape) for k, a in host.items()}, sample=sample)
 
 
 def build_model(precision, device):
@@ -603,6 +638,23 @@ def run_sharded(args, model, world, rank, device, one_device, backend):
                                        'scene of the same shape (100 views, the same 600 edges, 512x384) whose values are substituted INTO the handed-over payload tensor: gathered payload -> index_select(plan.source) -> '
                                        'values substituted -> unpack_predictions -> global_aligner, i.e. stage B consumes the tensors stage A hands over; random-init weights do not produce a scene'),
                       pairs_per_s_end_to_end=P / sec, forward_gflop_executed_per_job=gflop, **common)
+    # --dump-outputs: what the last timed job handed over (sampled pairs of the gathered predictions; c5: the aligned scene too), before any other model call
+    if args.dump_outputs:
+        from dust3r_amd.parallel import unpack_predictions
+        STAGE[0] = f'{args.workload}: dump outputs'
+        pick = dump_sample(P, H * W * 8 * 4, DUMP_BUDGET * 3 // 4 if c5 else DUMP_BUDGET)
+        rows = torch.tensor(pick, device=device)
+        arrays = pred_arrays(*unpack_predictions(last[0].index_select(0, keep[rows] if world > 1 else rows)))
+        sample = {'pairs': pick, 'of_pairs': P, 'how': 'all pairs' if len(pick) == P else 'seeded sample of pairs (torch.randperm, seed 0)'}
+        if c5:
+            scene = last[1]
+            arrays.update(scene_im_poses=scene.get_im_poses(), scene_focals=scene.get_focals(), scene_principal_points=scene.get_principal_points())
+            views = dump_sample(n_views, H * W * 4, DUMP_BUDGET - sum(a.numel() * 4 for a in arrays.values()))
+            depth = scene.get_depthmaps()
+            arrays['scene_depthmaps'] = torch.stack([depth[i] for i in views])
+            sample.update(depthmap_views=views, of_views=n_views)
+        result['dump_outputs'] = dump_outputs(args.dump_outputs, arrays, sample)
+        del arrays
     # parity of the job's own outputs: sampled pairs of the gathered payload vs one-pair-per-call runs (bit-equality)
     if not args.no_parity:
         allp = last[0].index_select(0, keep) if world > 1 else last[0]
@@ -634,9 +686,10 @@ def run_sharded(args, model, world, rank, device, one_device, backend):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` with no torchrun around it (WORLD_SIZE unset): re-exec this command under torch.distributed.run, one rank
-    per GPU of this node, rendezvous on 127.0.0.1 -- the same launch line the driver uses for N > 1. Does not return."""
+    """`python bench.py --gpus N` with no torchrun around it (WORLD_SIZE unset): run this command under torch.distributed.run, one rank
+    per GPU of this node, rendezvous on 127.0.0.1 -- the same launch line the driver uses for N > 1 -- as a child process, and exit with its status."""
     import socket
+    import subprocess
     n_dev = torch.cuda.device_count()
     if os.environ.get('D3R_BENCH_ONE_DEVICE') != '1' and n_dev < args.gpus:
         log(f'[bench] --gpus {args.gpus} but this node exposes {n_dev} GPU(s): one rank per GPU is the contract (D3R_BENCH_ONE_DEVICE=1 + D3R_BENCH_BACKEND=gloo '
@@ -653,7 +706,7 @@ def self_launch(args):
     log('[bench] WORLD_SIZE unset: launching ' + ' '.join(cmd))
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execvpe(sys.executable, cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def rank_table(world, rank, device, units):
@@ -688,7 +741,11 @@ def main():
     ap.add_argument('--no-aligner-380', action='store_true', help='skip the second aligner scene (the demo\'s symmetrised graph, 380 edges): under rocprofv3 its launches would be averaged into the same kernel symbol as the BASELINE scene\'s')
     ap.add_argument('--no-fast', '--no-accurate', dest='no_fast', action='store_true', help='skip the fast_mode block (fp16f8 / bf16 / fp16 throughput + their measured error)')
     ap.add_argument('--single-stream', action='store_true', help='keep decoder side 2 / head 2 on the main stream (serialised kernels: use under rocprofv3 so that per-kernel durations are not inflated by overlap)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last one returned as DIR/<name>.npy (float32; at most 64 MB in all: '
+                                                          'a fixed, seeded sample of the pairs when the batch is larger) and list the files in the JSON line')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         self_launch(args)                     # bare `python bench.py --gpus N`: becomes N ranks under torch.distributed.run
@@ -825,6 +882,21 @@ def main():
         if telemetry:
             result['sclk_mhz_mean'], result['power_w_mean'] = telemetry['sclk_mhz_mean'], telemetry['power_w_mean']
         log(f'[bench] {value:.2f} pairs/s on {world} GPU(s), {dt / args.steps * 1e3:.1f} ms/step; telemetry {telemetry}')
+
+    # ---- --dump-outputs: what the last timed step returned (with the all-gather: the gathered predictions of every rank), before any other model call ----
+    if rank == 0 and args.dump_outputs and last is not None:
+        STAGE[0] = 'c2: dump outputs'
+        n = world * B if do_gather else B
+        pick = dump_sample(n, H * W * 8 * 4, DUMP_BUDGET)
+        rows = torch.tensor(pick, device=device)
+        if do_gather:
+            from dust3r_amd.parallel import unpack_predictions
+            arrays = pred_arrays(*unpack_predictions(gather_out[(args.steps - 1) & 1].index_select(0, rows)))
+        else:
+            arrays = {k: v.index_select(0, rows) for k, v in pred_arrays(*last).items()}
+        result['dump_outputs'] = dump_outputs(args.dump_outputs, arrays, {'pairs': pick, 'of_pairs': n,
+                                                                          'how': 'all pairs' if len(pick) == n else 'seeded sample of pairs (torch.randperm, seed 0)'})
+        del arrays
 
     # ---- parity of the timed configuration itself: the last timed step's outputs vs one-pair-per-call runs -----------
     if rank == 0 and not args.no_parity and last is not None:

@@ -223,6 +223,99 @@ def load_images_golden():
     return dict(kind='load_images', cases=out, unpinned='torchvision ToTensor / Normalize restated in oracle/shims/torchvision')
 
 
+MAKE_PAIRS_CASES = [('complete', True), ('complete', False), ('swin-3', True), ('swin-2-noncyclic', False), ('logwin-3', True), ('oneref-2', True)]
+LOAD_IMAGES_SWEEP = [(1280, 960), (960, 1280), (800, 800), (1023, 577), (400, 300), (513, 512), (511, 512), (2000, 500), (64, 48)]
+
+
+def _tensor_sha256(t):
+    import hashlib
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def reference_pins_golden():
+    """What the unmodified reference returns for the pins of tests/test_oracle_pins.py and tests/test_host_cpu.py that compare the oracle / the host
+    logic with reference functions: forward of the tiny DPT model, state-dict layout of the release configs, Weiszfeld focal, clean_pointcloud,
+    align_multiple_poses, make_pairs, load_images over a sweep of source sizes (as sha256 of the fp32 output: bit-for-bit), and the names
+    dust3r/demo.py imports from the modules the integration aliases replace."""
+    import ast
+    import tempfile
+    import PIL.Image
+    from dust3r.cloud_opt.base_opt import clean_pointcloud
+    from dust3r.cloud_opt.init_im_poses import align_multiple_poses
+    from dust3r.post_process import estimate_focal_knowing_depth
+    from dust3r.utils.image import load_images
+    from dust3r_amd.synthetic import synthetic_photo
+    from oracle.roma_ref import unitquat_to_rotmat
+    pins = dict(kind='reference_pins', unpinned=UNPINNED)
+    # forward: tiny DPT model, weight seed 0, two 48x32 pairs of view seed 9
+    m = ref_model('tiny_dpt')
+    v1, v2 = synthetic_views(2, 48, 32, seed=9)
+    with torch.no_grad():
+        r1, r2 = m(copy.deepcopy(v1), copy.deepcopy(v2))
+    pins['forward'] = dict(config='tiny_dpt', weight_seed=0, B=2, H=48, W=32, view_seed=9, keys=sorted(m.state_dict()),
+                           pts3d=r1['pts3d'].clone(), conf2=r2['conf'].clone())
+    pins['state_dict_shapes'] = {cfg: {k: tuple(v.shape) for k, v in ref_model(cfg).state_dict().items()} for cfg in ('tiny_dpt', 'tiny_linear')}
+    # post_process.estimate_focal_knowing_depth (weiszfeld) on two edges of a noisy synthetic scene
+    out, _, gt = synthetic_scene(4, 32, 48, seed=3, symmetrize=True, noise=0.02)
+    pins['focal'] = dict(n_views=4, H=32, W=48, seed=3, noise=0.02, edges=[0, 5],
+                         values=[float(estimate_focal_knowing_depth(out['pred1']['pts3d'][e][None], torch.tensor((48 / 2, 32 / 2))[None], focal_mode='weiszfeld'))
+                                 for e in (0, 5)])
+    # base_opt.clean_pointcloud: world clouds of 4 views with one of them pulled towards its camera (inputs stored with the output)
+    g = torch.Generator().manual_seed(0)
+    c2w = gt['cam2world']
+    w2c = torch.linalg.inv(c2w)
+    f = gt['focal']
+    K = torch.tensor([[f, 0, 24.0], [0, f, 16.0], [0, 0, 1]]).repeat(4, 1, 1)
+    depth = [gt['depth'][i] * (0.8 if i == 1 else 1.0) for i in range(4)]
+    vs, us = torch.meshgrid(torch.arange(32.), torch.arange(48.), indexing='ij')
+    pts = []
+    for i in range(4):
+        cam = torch.stack((depth[i] * (us - 24) / f, depth[i] * (vs - 16) / f, depth[i]), dim=-1)
+        pts.append(cam @ c2w[i, :3, :3].T + c2w[i, :3, 3])
+    confs = [1 + 3 * torch.rand((32, 48), generator=g) for _ in range(4)]
+    cleaned = clean_pointcloud([c.clone() for c in confs], K, w2c, depth, pts, tol=0.001, bad_conf=0)
+    pins['clean_pointcloud'] = dict(confs=confs, K=K, w2c=w2c, depth=depth, pts=pts, tol=0.001, bad_conf=0, out=[c.clone() for c in cleaned])
+    # init_im_poses.align_multiple_poses on 2 / 3 / 7 poses: dst = a similarity of src plus a little noise (fp64)
+    pins['align_pose_sets'] = {}
+    for n in (2, 3, 7):
+        g = torch.Generator().manual_seed(n)
+
+        def poses(k):
+            q = torch.randn((k, 4), generator=g, dtype=torch.float64)
+            P = torch.eye(4, dtype=torch.float64).repeat(k, 1, 1)
+            P[:, :3, :3] = unitquat_to_rotmat(q / q.norm(dim=-1, keepdim=True))
+            P[:, :3, 3] = torch.randn((k, 3), generator=g, dtype=torch.float64) * 2
+            return P
+        src = poses(n)
+        dst = poses(1)[0] @ src
+        dst[:, :3, 3] = 1.7 * dst[:, :3, 3] + 0.01 * torch.randn((n, 3), generator=g, dtype=torch.float64)
+        s, R, T = align_multiple_poses(src.clone(), dst.clone())
+        pins['align_pose_sets'][n] = dict(src=src, dst=dst, s=float(s), R=R.clone(), T=T.clone())
+    # image_pairs.make_pairs over 9 images
+    imgs = [dict(idx=i) for i in range(9)]
+    pins['make_pairs'] = {(graph, sym): [(a['idx'], b['idx']) for a, b in make_pairs(imgs, graph, None, sym)] for graph, sym in MAKE_PAIRS_CASES}
+    # utils/image.py::load_images over a sweep of source sizes at the release resolutions
+    runs = []
+    with tempfile.TemporaryDirectory() as d:
+        paths = []
+        for k, (W, H) in enumerate(LOAD_IMAGES_SWEEP):
+            paths.append(os.path.join(d, f'img{k}.png'))
+            PIL.Image.fromarray(synthetic_photo(W, H, seed=k)).save(paths[-1])
+        for size, sq in ((512, False), (512, True), (224, False)):
+            views = load_images(paths, size=size, square_ok=sq, verbose=False)
+            runs.append(dict(size=size, square_ok=sq, views=[dict(shape=tuple(v['img'].shape), sha256=_tensor_sha256(v['img']), true_shape=v['true_shape'].copy(),
+                                                                 idx=v['idx'], instance=v['instance']) for v in views]))
+    pins['load_images'] = dict(sources=LOAD_IMAGES_SWEEP, runs=runs)
+    # dust3r/demo.py: `from dust3r.<module> import <names>` statements
+    import dust3r
+    demo = os.path.join(os.path.dirname(dust3r.__file__), 'demo.py')
+    with open(demo) as fh:
+        tree = ast.parse(fh.read())
+    pins['demo_imports'] = [(node.module, [a.name for a in node.names]) for node in tree.body
+                            if isinstance(node, ast.ImportFrom) and node.module and node.module.startswith('dust3r.')]
+    return pins
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -237,6 +330,7 @@ if __name__ == '__main__':
         'mst_init_12v_swin.pt': lambda: mst_init_golden(12, 48, 64, seed=4, scene_graph='swin-2'),
         'pair_viewer.pt': lambda: pair_viewer_golden(64, 96, seed=5),
         'load_images.pt': lambda: load_images_golden(),
+        'reference_pins.pt': lambda: reference_pins_golden(),
     }
     if len(sys.argv) > 1:        # regenerate only the named fixtures (aligner_c4.pt takes ~20 min of CPU)
         jobs = {k: v for k, v in jobs.items() if k in sys.argv[1:]}

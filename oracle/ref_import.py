@@ -7,9 +7,9 @@ What is real and what is restated when the reference is imported this way:
   restated  `models.*`  <- oracle/croco_ref/models (croco submodule is an empty directory)
             `roma`      <- oracle/roma_ref.py       (not installed)
             `cv2`, `torchvision`, `trimesh` <- oracle/shims (not installed)
-/root/reference does not exist on the GPU box: nothing under tests -m gpu, smoke() or
-bench.py calls this module; it is used by oracle/make_golden.py and by `-m "not gpu"`
-tests that skip when the directory is missing.
+/root/reference does not exist on the GPU box: nothing under tests/, smoke() or bench.py
+calls this module; it is used by oracle/make_golden.py (the tests read what it recorded
+under tests/golden) and by the precision tools under tools/.
 """
 import os
 import sys

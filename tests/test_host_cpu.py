@@ -75,12 +75,9 @@ def test_make_pairs_matches_reference_semantics(graph, sym):
         assert len(base) == 3 * n and all((j - i) % n in (1, 2, 3) or (i - j) % n in (1, 2, 3) for i, j in base)
     if graph == 'oneref-2':
         assert base == [(2, j) for j in range(n) if j != 2]
-    from oracle.ref_import import reference_available
-    if reference_available():
-        from oracle.ref_import import import_reference
-        import_reference()
-        from dust3r.image_pairs import make_pairs as ref_make_pairs
-        assert pairs == [(a['idx'], b['idx']) for a, b in ref_make_pairs(imgs, graph, None, sym)]
+    # the unmodified reference's make_pairs on the same 9 images (tests/golden/reference_pins.pt, oracle/make_golden.py)
+    ref = torch.load(os.path.join(ROOT, 'tests', 'golden', 'reference_pins.pt'), weights_only=False)['make_pairs']
+    assert pairs == ref[(graph, sym)]
 
 
 def test_make_pairs_prefilter():
@@ -243,23 +240,21 @@ def test_load_images_matches_reference_golden(tmp_path):
 
 
 def test_load_images_equals_live_reference(tmp_path):
-    """Same comparison against the LIVE reference function over a sweep of source sizes at the release resolutions (512, 224); needs
-    /root/reference (build container only)."""
-    from oracle.ref_import import import_reference, reference_available
-    if not reference_available():
-        pytest.skip('/root/reference only exists in the build container')
-    import_reference()
-    from dust3r.utils.image import load_images as ref_load
+    """Same comparison against the reference function over a sweep of source sizes at the release resolutions (512, 224): what the unmodified
+    reference's load_images returned on the same pictures is recorded in tests/golden/reference_pins.pt (`load_images`: shape, sha256 of the fp32
+    tensor, true_shape, idx, instance per view), so equal digests mean bit-for-bit equal images."""
+    import hashlib
     from dust3r_amd.utils.image import fit_geometry, load_images
-    paths, k = [], 0
-    for (W, H) in [(1280, 960), (960, 1280), (800, 800), (1023, 577), (400, 300), (513, 512), (511, 512), (2000, 500), (64, 48)]:
-        paths.append(_write_case_png(tmp_path, k, W, H))
-        k += 1
-    for size, sq in ((512, False), (512, True), (224, False)):
-        ours, refs = load_images(paths, size=size, square_ok=sq, verbose=False), ref_load(paths, size=size, square_ok=sq, verbose=False)
+    g = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_pins.pt'), weights_only=False)['load_images']
+    paths = [_write_case_png(tmp_path, k, W, H) for k, (W, H) in enumerate(g['sources'])]
+    assert len(g['runs']) == 3
+    for run in g['runs']:
+        ours, refs = load_images(paths, size=run['size'], square_ok=run['square_ok'], verbose=False), run['views']
         assert len(ours) == len(refs)
         for a, b in zip(ours, refs):
-            assert torch.equal(a['img'], b['img']) and (a['true_shape'] == b['true_shape']).all() and a['idx'] == b['idx'] and a['instance'] == b['instance']
+            assert tuple(a['img'].shape) == b['shape'] and a['img'].dtype == torch.float32
+            assert hashlib.sha256(a['img'].contiguous().numpy().tobytes()).hexdigest() == b['sha256']
+            assert (a['true_shape'] == b['true_shape']).all() and a['idx'] == b['idx'] and a['instance'] == b['instance']
     # the geometry alone, exhaustively over small sizes, against what the reference's arithmetic gives (image.py:98-116)
     for W1 in range(30, 140, 7):
         for H1 in range(30, 140, 11):
@@ -600,3 +595,28 @@ def test_persistent_gemm_has_no_scratch():
     assert len(kernels) >= 5 and len(scratch) == len(kernels) == len(spills)
     assert all(v == 0 for v in scratch) and all(v == 0 for v in spills), list(zip(kernels, scratch, spills))
     assert all(v == 1 for v in occ)          # one wave per SIMD: the whole register file
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: the pairs it writes are the same on every run (all of them when they fit, else a seeded sample), the files stay within
+    64 MB at the benchmark's image size, and they hold the selected pairs' values as float32."""
+    import bench
+    pair_bytes = bench.H * bench.W * 8 * 4                  # pts3d + conf of both views, fp32
+    assert bench.dump_sample(6, pair_bytes, bench.DUMP_BUDGET) == list(range(6))
+    for n in (32, 190, 600):
+        pick = bench.dump_sample(n, pair_bytes, bench.DUMP_BUDGET)
+        assert pick == bench.dump_sample(n, pair_bytes, bench.DUMP_BUDGET) == sorted(set(pick)) and 0 <= pick[0] and pick[-1] < n
+        assert 1 <= len(pick) * pair_bytes <= bench.DUMP_BUDGET
+    B, H, W = 5, 8, 12
+    g = torch.Generator().manual_seed(0)
+    p1 = dict(pts3d=torch.randn((B, H, W, 3), generator=g), conf=torch.rand((B, H, W), generator=g))
+    p2 = dict(pts3d_in_other_view=torch.randn((B, H, W, 3), generator=g, dtype=torch.float64), conf=torch.rand((B, H, W), generator=g).half())
+    rows = torch.tensor([1, 3])
+    arrays = {k: v.index_select(0, rows) for k, v in bench.pred_arrays(p1, p2).items()}
+    blk = bench.dump_outputs(str(tmp_path / 'out'), arrays, {'pairs': [1, 3]})
+    assert set(blk['files']) == {'pred1_pts3d.npy', 'pred1_conf.npy', 'pred2_pts3d_in_other_view.npy', 'pred2_conf.npy'}
+    for name, t in arrays.items():
+        a = np.load(str(tmp_path / 'out' / (name + '.npy')))
+        assert a.dtype == (np.float64 if t.dtype == torch.float64 else np.float32) and list(a.shape) == blk['files'][name + '.npy']
+        assert np.array_equal(a, t.double().numpy() if a.dtype == np.float64 else t.float().numpy())
+    assert sum(os.path.getsize(str(tmp_path / 'out' / f)) for f in blk['files']) <= 64_000_000

@@ -1,7 +1,6 @@
-"""CPU tests (-m "not gpu"): the oracle restatements against (a) the golden vectors generated from the
-UNMODIFIED reference files (tests/golden, oracle/make_golden.py) and (b) the reference itself when
-/root/reference is present (build container)."""
-import copy
+"""CPU tests (-m "not gpu"): the oracle restatements against the golden vectors generated from the
+UNMODIFIED reference files (tests/golden, oracle/make_golden.py): outputs of seeded runs, and the reference functions'
+answers on stored inputs (tests/golden/reference_pins.pt)."""
 import os
 
 import pytest
@@ -10,7 +9,6 @@ import torch
 from dust3r_amd.synthetic import MODEL_CONFIGS, OUT_GAIN, synthetic_image_list, synthetic_scene, synthetic_state_dict, synthetic_views
 from oracle.aligner_ref import AlignerRef
 from oracle.dust3r_ref import build_ref_model
-from oracle.ref_import import reference_available
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -93,141 +91,93 @@ def test_aligner_oracle_against_reference_golden():
     assert float((al.focals().detach().flatten() / g['focals'].flatten() - 1).abs().max()) < 5e-3
 
 
-@pytest.mark.skipif(not reference_available(), reason='/root/reference only exists in the build container')
 def test_forward_oracle_equals_live_reference():
-    from oracle.ref_import import import_reference
-    import_reference()
-    from dust3r.model import AsymmetricCroCo3DStereo as RefModel
-    inf = float('inf')
-    cfg = 'tiny_dpt'
-    ref = RefModel(output_mode='pts3d', depth_mode=('exp', -inf, inf), conf_mode=('exp', 1, inf), landscape_only=False, **MODEL_CONFIGS[cfg]).eval()
-    ref.load_state_dict(synthetic_state_dict(ref.state_dict(), 0, OUT_GAIN[cfg]))
-    m = build_ref_model(cfg)
-    assert set(ref.state_dict().keys()) == set(m.state_dict().keys())
-    v1, v2 = synthetic_views(2, 48, 32, seed=9)
+    """The oracle against the unmodified reference model on the same weights and views (tests/golden/reference_pins.pt `forward`): the same module tree
+    (state-dict keys) and the same outputs. The ops and their order are the reference's, but a stored vector only matches bit for bit at the thread count
+    it was recorded with (measured: up to 4e-6 between thread counts on one host), hence the cross-BLAS bar of the other forward fixtures."""
+    g = _g('reference_pins.pt')['forward']
+    m = build_ref_model(g['config'], seed=g['weight_seed'])
+    assert sorted(m.state_dict().keys()) == g['keys']
+    v1, v2 = synthetic_views(g['B'], g['H'], g['W'], seed=g['view_seed'])
     with torch.no_grad():
-        a1, a2 = ref(copy.deepcopy(v1), copy.deepcopy(v2))
         b1, b2 = m(v1, v2)
-    assert torch.equal(a1['pts3d'], b1['pts3d']) and torch.equal(a2['conf'], b2['conf'])
+    for a, b in ((b1['pts3d'], g['pts3d']), (b2['conf'], g['conf2'])):
+        assert a.shape == b.shape
+        assert float((a - b).abs().max() / b.abs().max()) < 1e-5
 
 
-@pytest.mark.skipif(not reference_available(), reason='/root/reference only exists in the build container')
 def test_state_dict_keys_match_reference_for_release_configs():
-    """The engine's expected checkpoint keys/shapes == the reference model's own state_dict (restated croco underneath)."""
-    from oracle.ref_import import import_reference
-    import_reference()
-    from dust3r.model import AsymmetricCroCo3DStereo as RefModel
+    """The engine's expected checkpoint keys/shapes == the reference model's own state_dict (restated croco underneath), as recorded in
+    tests/golden/reference_pins.pt `state_dict_shapes`."""
     from dust3r_amd.model import expected_state
-    inf = float('inf')
+    shapes = _g('reference_pins.pt')['state_dict_shapes']
     for cfg in ('tiny_dpt', 'tiny_linear'):
-        ref = RefModel(output_mode='pts3d', depth_mode=('exp', -inf, inf), conf_mode=('exp', 1, inf), landscape_only=False, **MODEL_CONFIGS[cfg])
         c = MODEL_CONFIGS[cfg]
         spec = expected_state(dict(enc_embed_dim=c['enc_embed_dim'], enc_depth=c['enc_depth'], dec_embed_dim=c['dec_embed_dim'],
                                    dec_depth=c['dec_depth'], patch_size=16, head_type=c['head_type']))
-        sd = ref.state_dict()
+        sd = shapes[cfg]
         assert set(spec) == set(sd), (set(spec) ^ set(sd))
         for k, shape in spec.items():
-            assert tuple(sd[k].shape) == tuple(shape), k
+            assert tuple(sd[k]) == tuple(shape), k
 
 
-@pytest.mark.skipif(not reference_available(), reason='/root/reference only exists in the build container')
 def test_cloud_restatements_equal_live_reference():
-    """oracle/cloud_ref.py (Weiszfeld focal, clean_pointcloud) against the unmodified reference functions on the same inputs."""
-    from oracle.ref_import import import_reference
-    import_reference()
-    from dust3r.cloud_opt.base_opt import clean_pointcloud as ref_clean
-    from dust3r.post_process import estimate_focal_knowing_depth as ref_focal
+    """oracle/cloud_ref.py (Weiszfeld focal, clean_pointcloud) against what the unmodified reference functions returned on the same inputs
+    (tests/golden/reference_pins.pt `focal`, `clean_pointcloud`)."""
     from dust3r_amd.synthetic import synthetic_scene
     from oracle.cloud_ref import clean_pointcloud_ref, estimate_focal_weiszfeld
-    out, init, gt = synthetic_scene(4, 32, 48, seed=3, symmetrize=True, noise=0.02)
-    for e in (0, 5):
-        pts = out['pred1']['pts3d'][e]
-        f_ref = float(ref_focal(pts[None], torch.tensor((48 / 2, 32 / 2))[None], focal_mode='weiszfeld'))
-        assert abs(estimate_focal_weiszfeld(pts) / f_ref - 1) < 1e-5
+    pins = _g('reference_pins.pt')
+    fg = pins['focal']
+    out, init, gt = synthetic_scene(fg['n_views'], fg['H'], fg['W'], seed=fg['seed'], symmetrize=True, noise=fg['noise'])
+    for e, f_ref in zip(fg['edges'], fg['values']):
+        assert abs(estimate_focal_weiszfeld(out['pred1']['pts3d'][e]) / f_ref - 1) < 1e-5
     # clean_pointcloud: world clouds of 4 views with one of them pulled towards its camera
-    g = torch.Generator().manual_seed(0)
-    c2w = gt['cam2world']
-    w2c = torch.linalg.inv(c2w)
-    f = gt['focal']
-    K = torch.tensor([[f, 0, 24.0], [0, f, 16.0], [0, 0, 1]]).repeat(4, 1, 1)
-    depth = [gt['depth'][i] * (0.8 if i == 1 else 1.0) for i in range(4)]
-    vs, us = torch.meshgrid(torch.arange(32.), torch.arange(48.), indexing='ij')
-    pts = []
-    for i in range(4):
-        cam = torch.stack((depth[i] * (us - 24) / f, depth[i] * (vs - 16) / f, depth[i]), dim=-1)
-        pts.append(cam @ c2w[i, :3, :3].T + c2w[i, :3, 3])
-    confs = [1 + 3 * torch.rand((32, 48), generator=g) for _ in range(4)]
-    ref = ref_clean([c.clone() for c in confs], K, w2c, depth, pts, tol=0.001, bad_conf=0)
-    got = clean_pointcloud_ref([c.clone() for c in confs], K, w2c, depth, pts, tol=0.001, bad_conf=0)
-    changed = sum(int((r != c).sum()) for r, c in zip(ref, confs))
+    c = pins['clean_pointcloud']
+    confs = c['confs']
+    got = clean_pointcloud_ref([x.clone() for x in confs], c['K'], c['w2c'], c['depth'], c['pts'], tol=c['tol'], bad_conf=c['bad_conf'])
+    changed = sum(int((r != x).sum()) for r, x in zip(c['out'], confs))
     assert changed > 50
-    assert all(torch.equal(a, b) for a, b in zip(ref, got))
+    assert all(torch.equal(a, b) for a, b in zip(c['out'], got))
 
 
-@pytest.mark.skipif(not reference_available(), reason='/root/reference only exists in the build container')
 @pytest.mark.parametrize('n', [2, 3, 7])
 def test_align_pose_sets_equals_live_reference(n):
-    """dust3r_amd.cloud_opt.bootstrap.align_pose_sets (init='known_poses', PairViewer) against the unmodified
-    init_im_poses.align_multiple_poses: the epsilon of the "point down the optical axis" is the median of the CONDENSED pairwise
-    centre distances (geometry.py:364-366, scipy pdist) -- with 2 poses that is d / 100, not d / 200."""
-    from oracle.ref_import import import_reference
-    import_reference()
+    """dust3r_amd.cloud_opt.bootstrap.align_pose_sets (init='known_poses', PairViewer) against what the unmodified
+    init_im_poses.align_multiple_poses returned on the same poses (tests/golden/reference_pins.pt `align_pose_sets`): the epsilon of the "point down
+    the optical axis" is the median of the CONDENSED pairwise centre distances (geometry.py:364-366, scipy pdist) -- with 2 poses that is d / 100, not d / 200."""
     import numpy as np
-    from dust3r.cloud_opt.init_im_poses import align_multiple_poses
-    from dust3r_amd.cloud_opt.bootstrap import align_pose_sets
-    from oracle.roma_ref import unitquat_to_rotmat
-    g = torch.Generator().manual_seed(n)
-
-    def poses(k):
-        q = torch.randn((k, 4), generator=g, dtype=torch.float64)
-        P = torch.eye(4, dtype=torch.float64).repeat(k, 1, 1)
-        P[:, :3, :3] = unitquat_to_rotmat(q / q.norm(dim=-1, keepdim=True))
-        P[:, :3, 3] = torch.randn((k, 3), generator=g, dtype=torch.float64) * 2
-        return P
-    src = poses(n)
-    # dst = a similarity of src plus a little noise, so that the registration is well conditioned
-    S = poses(1)[0]
-    dst = S @ src
-    dst[:, :3, 3] = 1.7 * dst[:, :3, 3] + 0.01 * torch.randn((n, 3), generator=g, dtype=torch.float64)
-    s_ref, R_ref, T_ref = align_multiple_poses(src, dst)
-    from dust3r_amd.cloud_opt.bootstrap import split_similarity
-    s, R, t = split_similarity(align_pose_sets(src.numpy(), dst.numpy()))
-    assert abs(float(s) / float(s_ref) - 1) < 1e-9
-    assert np.abs(np.asarray(R) - R_ref.numpy()).max() < 1e-9 and np.abs(np.asarray(t).ravel() - T_ref.numpy().ravel()).max() < 1e-8
+    from dust3r_amd.cloud_opt.bootstrap import align_pose_sets, split_similarity
+    g = _g('reference_pins.pt')['align_pose_sets'][n]
+    s, R, t = split_similarity(align_pose_sets(g['src'].numpy(), g['dst'].numpy()))
+    assert abs(float(s) / g['s'] - 1) < 1e-9
+    assert np.abs(np.asarray(R) - g['R'].numpy()).max() < 1e-9 and np.abs(np.asarray(t).ravel() - g['T'].numpy().ravel()).max() < 1e-8
 
 
-@pytest.mark.skipif(not reference_available(), reason='/root/reference only exists in the build container')
 def test_reference_demo_binds_to_the_engine_through_the_integration_aliases():
-    """with `dust3r.<hot-path module>` aliased to `dust3r_amd.<module>`, the reference's OWN dust3r/demo.py
-    (imported unmodified; gradio / matplotlib / trimesh stubbed) resolves every function of its reconstruction body to the engine's."""
+    """with `dust3r.<hot-path module>` aliased to `dust3r_amd.<module>`, every name the reference's OWN dust3r/demo.py imports
+    from those modules (its `from dust3r.<module> import ...` statements, recorded in tests/golden/reference_pins.pt `demo_imports`) resolves to the
+    engine's. The import statements run in a fresh interpreter against the aliased module table."""
     import subprocess
     import sys
-    code = r'''
+    imports = _g('reference_pins.pt')['demo_imports']
+    aliased = ('model', 'inference', 'image_pairs', 'cloud_opt', 'utils.image', 'utils.device')
+    bound = [(mod, names) for mod, names in imports if mod[len('dust3r.'):] in aliased]
+    assert {n for _, names in bound for n in names} >= {'inference', 'make_pairs', 'load_images', 'global_aligner', 'GlobalAlignerMode'}
+    stmts = '\n'.join(f"from {mod} import {', '.join(names)}" for mod, names in bound)
+    code = r"""
 import sys, types
-sys.path.insert(0, %r); sys.path.insert(0, %r + '/oracle/shims')
+sys.path.insert(0, %r)
 import dust3r_amd, dust3r_amd.model, dust3r_amd.inference, dust3r_amd.image_pairs, dust3r_amd.cloud_opt, dust3r_amd.utils.image, dust3r_amd.utils.device
-for stub in ('gradio', 'matplotlib', 'matplotlib.pyplot', 'scipy.spatial.transform'):
-    if stub not in sys.modules:
-        try:
-            __import__(stub)
-        except Exception:
-            sys.modules[stub] = types.ModuleType(stub)
-sys.modules['matplotlib'].pyplot = sys.modules['matplotlib.pyplot']
-sys.path.insert(0, '/root/reference')
-sys.modules['dust3r.utils.path_to_croco'] = types.ModuleType('dust3r.utils.path_to_croco')
-import dust3r
-for name in ('model', 'inference', 'image_pairs', 'cloud_opt', 'utils.image', 'utils.device'):
+dust3r = types.ModuleType('dust3r')
+dust3r.__path__ = []
+sys.modules['dust3r'] = dust3r
+for name in %r:
     sys.modules['dust3r.' + name] = sys.modules['dust3r_amd.' + name]
-viz = types.ModuleType('dust3r.viz')
-for k in ('add_scene_cam', 'CAM_COLORS', 'OPENGL', 'pts3d_to_trimesh', 'cat_meshes'):
-    setattr(viz, k, None)
-sys.modules['dust3r.viz'] = viz
-import dust3r.demo as demo
+%s
 import dust3r_amd.inference as I, dust3r_amd.image_pairs as P, dust3r_amd.cloud_opt as Cl, dust3r_amd.utils.image as U
-assert demo.inference is I.inference and demo.make_pairs is P.make_pairs and demo.load_images is U.load_images
-assert demo.global_aligner is Cl.global_aligner and demo.GlobalAlignerMode is Cl.GlobalAlignerMode
-assert demo.get_reconstructed_scene.__module__ == 'dust3r.demo'
+assert inference is I.inference and make_pairs is P.make_pairs and load_images is U.load_images
+assert global_aligner is Cl.global_aligner and GlobalAlignerMode is Cl.GlobalAlignerMode
 print('aliases ok')
-''' % (ROOT, ROOT)
+""" % (ROOT, aliased, stmts)
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'aliases ok' in r.stdout, r.stderr[-2000:]
