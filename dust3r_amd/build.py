@@ -31,16 +31,12 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=True, probes=None):
-    """probes (default: the D3R_PROBES=1 environment switch, else off): compile with -DD3R_PROBES -- the ablation kernels and the probe-only environment
-    switches of csrc/common.hpp (probe_env). The default library reads the twelve documented switches only."""
+def build(force=False, verbose=True):
     hipcc = _hipcc()
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
-    if probes is None:
-        probes = os.environ.get('D3R_PROBES', '0') == '1'
-    flags = FLAGS + (['-DD3R_PROBES'] if probes else []) + os.environ.get('D3R_BUILD_DEFINES', '').split()      # development: e.g. -DD3R_GEMM_ONLY_DT=3
+    flags = FLAGS + os.environ.get('D3R_BUILD_DEFINES', '').split()      # development: e.g. -DD3R_GEMM_ONLY_DT=3
     stamp = os.path.join(CSRC, '.build_flags')
-    if not os.path.exists(stamp) or open(stamp).read() != ' '.join(flags):      # objects of the other flavour: rebuild everything
+    if not os.path.exists(stamp) or open(stamp).read() != ' '.join(flags):      # objects built with other flags: rebuild everything
         force = True
     objs, jobs = [], []
     for src in SOURCES:
@@ -57,7 +53,7 @@ def build(force=False, verbose=True, probes=None):
         if r.returncode != 0:
             raise RuntimeError(f'hipcc failed:\n{r.stdout}\n{r.stderr}')
         if '-Rpass-analysis=kernel-resource-usage' in cmd:      # the register / scratch report of the kernels of this file, kept next to the object (tests/test_host_cpu.py reads it)
-            with open(cmd[-1].replace('.o', '.resources.txt'), 'w') as f:
+            with open(os.path.splitext(cmd[-1])[0] + '.resources.txt', 'w') as f:
                 f.write('\n'.join(ln for ln in r.stderr.splitlines() if 'remark:' in ln))
         return r
 

@@ -31,9 +31,7 @@ struct AlignerView {
     const int* img_area;    // [n]
     const int* adj_off;     // [n+1]
     const int* adj_es;      // [2E] entries e*2+side, grouped by projecting image
-    const float* pred[2];   // PLANAR copies owned by the handle: [E][3][maxA] (x, y, z planes: unit-stride float4 loads)
-    const float* wgt[2];    // [E][maxA]
-    const float* inter;     // LAY == 1: [2][E][maxAp / 256][4][256] -- per (side, edge, 256-pixel wave chunk) the x, y, z and weight runs back to back (4 KiB)
+    const float* inter;     // [2][E][maxAp / 256][4][256] -- per (side, edge, 256-pixel wave chunk) the x, y, z and weight runs back to back (4 KiB)
     int maxAp;              // maxA rounded up to 256
     float* depth;           // [n][maxA] log-depth
     float* depth_m;
@@ -95,16 +93,13 @@ D3R_DEV float4 stream_ld4(const float* p) {
     return make_float4(v[0], v[1], v[2], v[3]);
 }
 #define D3R_STREAM_LD4(ptr) stream_ld4(ptr)
-// NWV = waves per workgroup (4: 1024-pixel chunks; 8: 2048-pixel chunks = 8 KiB contiguous per plane and edge side, half the partial records;
-// probe D3R_ALIGNER_NWV=8 at handle creation -- the partial sums are then grouped differently: same result to fp32 rounding, not bit for bit)
-// PROBE (measurement aid, results INVALID; D3R_ALIGNER_PROBE=1|2 at handle creation, tools/aligner_probe.py): 1 = the pred / weight stream is loaded and summed,
-// the per-edge residual math and wave reductions are skipped -- the speed at which this access pattern is delivered; 2 = math kept, wave reductions skipped
-// LAY (round 5): 0 = four separate streams per edge side (x, y, z planes of the handle's planar copy + the caller's weight rows), a wave reads four 1 KiB
-// runs megabytes apart; 1 = the handle's block-interleaved copy [side][edge][256-pixel chunk][x | y | z | w][256]: a wave reads ONE contiguous 4 KiB run,
-// a workgroup 16 KiB per edge side (D3R_ALIGNER_LAYOUT at handle creation; same loads, same arithmetic, bit-identical results)
-template <bool L2, int PF, int NWV = 4, int PROBE = 0, int LAY = 0>   // PF = prefetch distance of the pred / weight stream in edges (1 or 2)
-__global__ __launch_bounds__(NWV * 64) void aligner_main_kernel(AlignerView a) {
-    constexpr int NTH = NWV * 64, CHUNK_T = NTH * PPT;
+// Four waves per workgroup (1024-pixel chunks), one edge of the pred / weight stream in flight. The stream is the handle's block-interleaved copy
+// [side][edge][256-pixel chunk][x | y | z | w][256] (round 5): a wave reads ONE contiguous 4 KiB run per edge side, a workgroup 16 KiB (rounds 1-4 read
+// four separate streams per edge side -- x, y, z planes and the caller's weight rows -- a wave four 1 KiB runs megabytes apart).
+constexpr int ALIGNER_NWV = 4;
+template <bool L2>
+__global__ __launch_bounds__(ALIGNER_NWV * 64) void aligner_main_kernel(AlignerView a) {
+    constexpr int NWV = ALIGNER_NWV, NTH = NWV * 64, CHUNK_T = NTH * PPT;
     const int nchunk = a.nslot;
     const int img_l = blockIdx.x / nchunk, chunk = blockIdx.x - img_l * nchunk;
     const int img = a.img0 + img_l;
@@ -160,38 +155,23 @@ __global__ __launch_bounds__(NWV * 64) void aligner_main_kernel(AlignerView a) {
             sh_M[j][k] = a.d_edge[(es >> 1) * 12 + k];
         }
         __syncthreads();
-        float4 nq0, nq1, nq2, nww, mq0, mq1, mq2, mww;   // edge j + 1 (and, PF == 2, edge j + 2) in flight
-        const size_t ploff = (size_t)(pl >> 8) * 1024 + (pl & 255);     // LAY == 1: this lane's offset inside an edge side's interleaved block
+        float4 nq0, nq1, nq2, nww;   // edge j + 1 in flight
+        const size_t ploff = (size_t)(pl >> 8) * 1024 + (pl & 255);     // this lane's offset inside an edge side's interleaved block
         auto stream_edge = [&](int es, float4& d0, float4& d1, float4& d2, float4& dw) __attribute__((always_inline)) {
-            if constexpr (LAY == 1) {
-                const float* pp = a.inter + ((size_t)(es & 1) * a.E + (size_t)(es >> 1)) * 4 * (size_t)a.maxAp + ploff;
-                d0 = D3R_STREAM_LD4(pp);
-                d1 = D3R_STREAM_LD4(pp + 256);
-                d2 = D3R_STREAM_LD4(pp + 512);
-                dw = D3R_STREAM_LD4(pp + 768);
-            } else {
-                const float* pp = a.pred[es & 1] + (size_t)(es >> 1) * 3 * a.maxA + pl;
-                d0 = D3R_STREAM_LD4(pp);
-                d1 = D3R_STREAM_LD4(pp + a.maxA);
-                d2 = D3R_STREAM_LD4(pp + 2 * (size_t)a.maxA);
-                dw = D3R_STREAM_LD4(a.wgt[es & 1] + (size_t)(es >> 1) * a.maxA + pl);
-            }
+            const float* pp = a.inter + ((size_t)(es & 1) * a.E + (size_t)(es >> 1)) * 4 * (size_t)a.maxAp + ploff;
+            d0 = D3R_STREAM_LD4(pp);
+            d1 = D3R_STREAM_LD4(pp + 256);
+            d2 = D3R_STREAM_LD4(pp + 512);
+            dw = D3R_STREAM_LD4(pp + 768);
         };
         stream_edge(sh_es[0], nq0, nq1, nq2, nww);
-        if (PF == 2) stream_edge(sh_es[nb > 1 ? 1 : 0], mq0, mq1, mq2, mww);
         for (int j = 0; j < nb; ++j) {
             const int es = sh_es[j];
             const int side = es & 1;
             const float4 q0 = nq0, q1 = nq1, q2 = nq2, ww = nww;
             {   // unconditional (index clamped): a branch here would make the compiler wait for the loads at its join
-                const int jn = j + PF < nb ? j + PF : nb - 1;
-                const int es2 = sh_es[jn];
-                if (PF == 2) { nq0 = mq0; nq1 = mq1; nq2 = mq2; nww = mww; }
-                float4& d0 = PF == 2 ? mq0 : nq0;
-                float4& d1 = PF == 2 ? mq1 : nq1;
-                float4& d2 = PF == 2 ? mq2 : nq2;
-                float4& dw = PF == 2 ? mww : nww;
-                stream_edge(es2, d0, d1, d2, dw);
+                const int jn = j + 1 < nb ? j + 1 : nb - 1;
+                stream_edge(sh_es[jn], nq0, nq1, nq2, nww);
             }
             float M[12];
             {
@@ -207,20 +187,10 @@ __global__ __launch_bounds__(NWV * 64) void aligner_main_kernel(AlignerView a) {
                 const float pr[PPT][3] = {{q0.x, q1.x, q2.x}, {q0.y, q1.y, q2.y}, {q0.z, q1.z, q2.z}, {q0.w, q1.w, q2.w}};   // q0 = x, q1 = y, q2 = z planes
                 const float ia = active ? a.inv_area[side] : 0.f;   // zero weight: inactive lanes contribute nothing
                 const float wv[PPT] = {ww.x * ia, ww.y * ia, ww.z * ia, ww.w * ia};
-                if constexpr (PROBE == 1) {
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k) { loss += pr[k][0] + pr[k][1] + pr[k][2] + wv[k] + M[k]; g[k][0] += pr[k][0]; }
-                } else {
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) residual_accumulate(X[k], M, pr[k], wv[k], L2, loss, g[k], gm);
-                }
             }
             float red[13];
-            if constexpr (PROBE != 0) {
-#pragma unroll
-                for (int k = 0; k < 12; ++k) red[k] = gm[k];
-                red[12] = loss;
-            } else
             if (a.use_dpp) {
 #pragma unroll
                 for (int k = 0; k < 12; ++k) red[k] = gm[k];
@@ -244,7 +214,6 @@ __global__ __launch_bounds__(NWV * 64) void aligner_main_kernel(AlignerView a) {
         for (int i = threadIdx.x; i < nb * PW; i += NTH) {
             const int j = i / PW, v = i - j * PW;
             float t = (sh_part[0][j][v] + sh_part[1][j][v]) + (sh_part[2][j][v] + sh_part[3][j][v]);
-            if constexpr (NWV == 8) t += (sh_part[4][j][v] + sh_part[5][j][v]) + (sh_part[6][j][v] + sh_part[7][j][v]);
             a.part_edge[((size_t)sh_es[j] * a.nslot + slot) * PW + v] = t;
         }
     }
@@ -297,22 +266,11 @@ __global__ __launch_bounds__(NWV * 64) void aligner_main_kernel(AlignerView a) {
     if (threadIdx.x < PW) {
         const int v = threadIdx.x;
         float t = (sh_part[0][0][v] + sh_part[1][0][v]) + (sh_part[2][0][v] + sh_part[3][0][v]);
-        if constexpr (NWV == 8) t += (sh_part[4][0][v] + sh_part[5][0][v]) + (sh_part[6][0][v] + sh_part[7][0][v]);
         a.part_img[((size_t)img * a.nslot + slot) * PW + v] = t;
     }
 }
 
-// one-time re-layout at create: [E][maxA][3] (the reference's stacked pointmaps) -> [E][3][maxA]
-__global__ __launch_bounds__(256) void aligner_planarize_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n_pix_total, int maxA) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_pix_total; i += (size_t)gridDim.x * 256) {
-        const size_t e = i / maxA, p = i - e * maxA;
-        const float x = in[i * 3], y = in[i * 3 + 1], z = in[i * 3 + 2];
-        float* o = out + e * 3 * (size_t)maxA + p;
-        o[0] = x; o[maxA] = y; o[2 * (size_t)maxA] = z;
-    }
-}
-
-// one-time re-layout at create (LAY == 1): pred [E][maxA][3] + weights [E][maxA] of one side -> [E][maxAp / 256][x | y | z | w][256]
+// one-time re-layout at create: pred [E][maxA][3] + weights [E][maxA] of one side -> [E][maxAp / 256][x | y | z | w][256]
 __global__ __launch_bounds__(256) void aligner_interleave_kernel(const float* __restrict__ pred, const float* __restrict__ wgt, float* __restrict__ out, int E, int maxA,
                                                                  int maxAp) {
     const size_t total = (size_t)E * maxAp;
@@ -730,15 +688,10 @@ using namespace d3r;
 
 struct d3r_aligner {
     int n = 0, E = 0, maxA = 0, nslot = 0;
-    int nwv = 4;              // waves per workgroup of the main kernel (D3R_ALIGNER_NWV=8 at creation: 2048-pixel chunks)
-    int probe = 0;            // D3R_ALIGNER_PROBE at creation (measurement aid, results INVALID)
-    int layout = 0;           // D3R_ALIGNER_LAYOUT at creation: 1 = block-interleaved stream copy (aligner_main_kernel LAY)
-    float* inter = nullptr;   // [2][E][maxAp / 256][4][256]
+    float* inter = nullptr;   // [2][E][maxAp / 256][4][256]: block-interleaved copy of pred_i / w_i, pred_j / w_j (aligner_main_kernel)
     int maxAp = 0;
     std::vector<int> h_w, h_h, h_area;
     int *d_w = nullptr, *d_h = nullptr, *d_area = nullptr, *d_adj_off = nullptr, *d_adj_es = nullptr;
-    const float *pred[2] = {nullptr, nullptr}, *wgt[2] = {nullptr, nullptr};
-    float* planar = nullptr;  // [2][E][3][maxA] re-laid-out copies of pred_i / pred_j
     float *pw_poses = nullptr, *pw_adaptors = nullptr, *im_poses = nullptr, *im_depth = nullptr, *im_focals = nullptr, *im_pp = nullptr;
     float* state = nullptr;  // one arena: Adam moments, derived matrices, partials
     float *depth_m, *depth_v, *pw_m, *pw_v, *imp_m, *imp_v, *foc_m, *foc_v, *pp_m, *pp_v, *pa_m, *pa_v, *d_edge, *d_img, *part_edge, *part_img, *loss_hist, *g_scratch;
@@ -784,13 +737,10 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     d3r_aligner* a = new (std::nothrow) d3r_aligner();
     if (!a) return D3R_ERR_ALLOC;
     a->n = n_imgs; a->E = n_edges; a->maxA = max_area;
-    { const char* e = probe_env("D3R_ALIGNER_NWV"); a->nwv = (e && e[0] == '8') ? 8 : 4; }
-    { const char* e = probe_env("D3R_ALIGNER_PROBE"); a->probe = (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }
-    // default since round 5: the block-interleaved copy (same-process A/B, tools/aligner_probe.py, profiles/r05_k: 3998 -> 4085 it/s at 190 edges, 2142 -> 2161 at 380,
-    // bit-identical losses); D3R_ALIGNER_LAYOUT=0: the planar copy + the caller's weight rows (rounds 1-4)
-    { const char* e = probe_env("D3R_ALIGNER_LAYOUT"); a->layout = (!(e && e[0] == '0') && a->nwv == 4 && !a->probe) ? 1 : 0; }
+    // the block-interleaved stream copy (round 5; measured against the planar copy of rounds 1-4, profiles/r05_k: 3998 -> 4085 it/s at 190 edges,
+    // 2142 -> 2161 at 380, bit-identical losses)
     a->maxAp = (max_area + 255) / 256 * 256;
-    a->nslot = cdiv(max_area, a->nwv * 64 * PPT);
+    a->nslot = cdiv(max_area, ALIGNER_NWV * 64 * PPT);
     a->h_w.assign(img_w, img_w + n_imgs);
     a->h_h.assign(img_h, img_h + n_imgs);
     a->h_area.resize(n_imgs);
@@ -813,7 +763,6 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     }
     a->inv_area[0] = (float)(1.0 / ta[0]);
     a->inv_area[1] = (float)(1.0 / ta[1]);
-    a->wgt[0] = w_i; a->wgt[1] = w_j;   // (pred_i / pred_j are copied into a planar layout below)
     a->pw_poses = pw_poses; a->pw_adaptors = pw_adaptors; a->im_poses = im_poses; a->im_depth = im_depth;
     a->im_focals = im_focals; a->im_pp = im_pp;
     a->base_scale = base_scale; a->pw_break = pw_break; a->focal_break = focal_break;
@@ -833,10 +782,6 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     a->state_bytes = fl * sizeof(float) + dbl * sizeof(double) + 64;
     if (hipMalloc((void**)&a->state, a->state_bytes) != hipSuccess) { delete a; return D3R_ERR_ALLOC; }
     hipStream_t st = (hipStream_t)stream;   // the clear and the re-layout below are ordered on the caller's stream, like every later call
-    // D3R_ALIGNER_POISON=1 (stress harness, tools/c4_stress.py): every allocation of the handle is filled with 0xFF bytes (fp32 / fp64 NaN,
-    // int -1) before its real initialisation, so that any read of a byte the create path failed to initialise shows up as NaN / a fault
-    static const bool poison = [] { const char* e = probe_env("D3R_ALIGNER_POISON"); return e && e[0] == '1'; }();
-    if (poison && hipMemsetAsync(a->state, 0xFF, a->state_bytes, st) != hipSuccess) { (void)hipFree(a->state); delete a; return D3R_ERR_LAUNCH; }
     if (hipMemsetAsync(a->state, 0, a->state_bytes, st) != hipSuccess) { (void)hipFree(a->state); delete a; return D3R_ERR_LAUNCH; }
     float* b = a->state;
     a->depth_m = b + o_dm; a->depth_v = b + o_dv; a->pw_m = b + o_pwm; a->pw_v = b + o_pwv; a->imp_m = b + o_im;
@@ -848,31 +793,20 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     const size_t ib = (3 * (size_t)n_imgs + (n_imgs + 1) + 2 * (size_t)n_edges) * sizeof(int);
     if (hipMalloc((void**)&a->d_w, ib) != hipSuccess) { (void)hipFree(a->state); delete a; return D3R_ERR_ALLOC; }
     a->d_h = a->d_w + n_imgs; a->d_area = a->d_h + n_imgs; a->d_adj_off = a->d_area + n_imgs; a->d_adj_es = a->d_adj_off + n_imgs + 1;
-    if (poison) { (void)hipMemsetAsync(a->d_w, 0xFF, ib, st); (void)hipStreamSynchronize(st); }
     // blocking copies (pageable host vectors): complete in device memory when they return, whatever stream the caller works on
     (void)hipMemcpy(a->d_w, a->h_w.data(), n_imgs * sizeof(int), hipMemcpyHostToDevice);
     (void)hipMemcpy(a->d_h, a->h_h.data(), n_imgs * sizeof(int), hipMemcpyHostToDevice);
     (void)hipMemcpy(a->d_area, a->h_area.data(), n_imgs * sizeof(int), hipMemcpyHostToDevice);
     (void)hipMemcpy(a->d_adj_off, off.data(), (n_imgs + 1) * sizeof(int), hipMemcpyHostToDevice);
     (void)hipMemcpy(a->d_adj_es, es.data(), 2 * (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice);
-    if (a->layout != 1) {
-        const size_t npix = (size_t)n_edges * max_area;
-        if (hipMalloc((void**)&a->planar, 2 * npix * 3 * sizeof(float)) != hipSuccess) { (void)hipFree(a->state); (void)hipFree(a->d_w); delete a; return D3R_ERR_ALLOC; }
-        const int grid = (int)((npix + 255) / 256 < 65536 ? (npix + 255) / 256 : 65536);
-        if (poison) (void)hipMemsetAsync(a->planar, 0xFF, 2 * npix * 3 * sizeof(float), st);   // (layout 1: every float of the interleaved copy is written by its kernel, padding included)
-        hipLaunchKernelGGL(aligner_planarize_kernel, dim3(grid), dim3(256), 0, st, pred_i, a->planar, npix, max_area);
-        hipLaunchKernelGGL(aligner_planarize_kernel, dim3(grid), dim3(256), 0, st, pred_j, a->planar + npix * 3, npix, max_area);
-        if (hipGetLastError() != hipSuccess) { (void)hipFree(a->planar); (void)hipFree(a->state); (void)hipFree(a->d_w); delete a; return D3R_ERR_LAUNCH; }
-        a->pred[0] = a->planar; a->pred[1] = a->planar + npix * 3;
-    }
-    if (a->layout == 1) {
+    {
         const size_t per_side = (size_t)n_edges * 4 * a->maxAp;
-        if (hipMalloc((void**)&a->inter, 2 * per_side * sizeof(float)) != hipSuccess) { (void)hipFree(a->planar); (void)hipFree(a->state); (void)hipFree(a->d_w); delete a; return D3R_ERR_ALLOC; }
+        if (hipMalloc((void**)&a->inter, 2 * per_side * sizeof(float)) != hipSuccess) { (void)hipFree(a->state); (void)hipFree(a->d_w); delete a; return D3R_ERR_ALLOC; }
         const size_t total = (size_t)n_edges * a->maxAp;
         const int grid = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
         hipLaunchKernelGGL(aligner_interleave_kernel, dim3(grid), dim3(256), 0, st, pred_i, w_i, a->inter, n_edges, max_area, a->maxAp);
         hipLaunchKernelGGL(aligner_interleave_kernel, dim3(grid), dim3(256), 0, st, pred_j, w_j, a->inter + per_side, n_edges, max_area, a->maxAp);
-        if (hipGetLastError() != hipSuccess) { (void)hipFree(a->inter); (void)hipFree(a->planar); (void)hipFree(a->state); (void)hipFree(a->d_w); delete a; return D3R_ERR_LAUNCH; }
+        if (hipGetLastError() != hipSuccess) { (void)hipFree(a->inter); (void)hipFree(a->state); (void)hipFree(a->d_w); delete a; return D3R_ERR_LAUNCH; }
     }
     a->create_stream = st;
     if (hipEventCreateWithFlags(&a->ev_ready, hipEventDisableTiming) == hipSuccess) (void)hipEventRecord(a->ev_ready, st);
@@ -884,7 +818,6 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
 extern "C" int d3r_aligner_destroy(d3r_aligner* a) {
     if (!a) return D3R_OK;
     if (a->ev_ready) (void)hipEventDestroy(a->ev_ready);
-    (void)hipFree(a->planar);
     if (a->inter) (void)hipFree(a->inter);
     (void)hipFree(a->state);
     (void)hipFree(a->d_w);
@@ -935,42 +868,15 @@ static int aligner_pass(d3r_aligner* a, bool update, double lr, int hist_idx, fl
     AlignerView v;
     v.img0 = a->img0;
     v.n = a->n; v.E = a->E; v.maxA = a->maxA; v.nslot = a->nslot; v.img_w = a->d_w; v.img_area = a->d_area;
-    v.adj_off = a->d_adj_off; v.adj_es = a->d_adj_es; v.pred[0] = a->pred[0]; v.pred[1] = a->pred[1]; v.inter = a->inter; v.maxAp = a->maxAp;
-    v.wgt[0] = a->wgt[0]; v.wgt[1] = a->wgt[1]; v.depth = a->im_depth; v.depth_m = a->depth_m; v.depth_v = a->depth_v;
+    v.adj_off = a->d_adj_off; v.adj_es = a->d_adj_es; v.inter = a->inter; v.maxAp = a->maxAp;
+    v.depth = a->im_depth; v.depth_m = a->depth_m; v.depth_v = a->depth_v;
     v.depth_grad = g_depth; v.d_edge = a->d_edge; v.d_img = a->d_img; v.part_edge = a->part_edge; v.part_img = a->part_img;
     v.inv_area[0] = a->inv_area[0]; v.inv_area[1] = a->inv_area[1]; v.l2 = a->l2; v.update = update ? 1 : 0;
     v.use_dpp = a->use_dpp; v.adam = s.adam;
-    // D3R_ALIGNER_PF=2: two edges of the stream in flight per wave (probe; 16 more VGPRs, 3 instead of 4 waves per SIMD)
-    static const int pf = [] { const char* e = probe_env("D3R_ALIGNER_PF"); return (e && e[0] == '2') ? 2 : 1; }();
     const dim3 grid(imgc * a->nslot);
     if (imgc > 0) {
-    // default build: the block-interleaved layout only (a->layout == 1 whenever no probe switch is read); the planar / 512-thread / two-edges-in-flight /
-    // ablation instances are compiled in probe builds (-DD3R_PROBES)
-    bool launched = false;
-    if constexpr (kProbes) {
-        launched = true;
-        if (a->probe && !a->l2) {
-            if (a->probe == 1 && pf == 2) hipLaunchKernelGGL((aligner_main_kernel<false, 2, 4, 1>), grid, dim3(256), 0, st, v);
-            else if (a->probe == 1) hipLaunchKernelGGL((aligner_main_kernel<false, 1, 4, 1>), grid, dim3(256), 0, st, v);
-            else hipLaunchKernelGGL((aligner_main_kernel<false, 1, 4, 2>), grid, dim3(256), 0, st, v);
-        } else if (a->layout == 1) {
-            launched = false;
-        } else if (a->nwv == 8) {
-            if (a->l2) hipLaunchKernelGGL((aligner_main_kernel<true, 1, 8>), grid, dim3(512), 0, st, v);
-            else hipLaunchKernelGGL((aligner_main_kernel<false, 1, 8>), grid, dim3(512), 0, st, v);
-        } else if (a->l2) {
-            if (pf == 2) hipLaunchKernelGGL((aligner_main_kernel<true, 2>), grid, dim3(256), 0, st, v);
-            else hipLaunchKernelGGL((aligner_main_kernel<true, 1>), grid, dim3(256), 0, st, v);
-        } else {
-            if (pf == 2) hipLaunchKernelGGL((aligner_main_kernel<false, 2>), grid, dim3(256), 0, st, v);
-            else hipLaunchKernelGGL((aligner_main_kernel<false, 1>), grid, dim3(256), 0, st, v);
-        }
-    }
-    (void)pf;
-    if (!launched) {
-        if (a->l2) hipLaunchKernelGGL((aligner_main_kernel<true, 1, 4, 0, 1>), grid, dim3(256), 0, st, v);
-        else hipLaunchKernelGGL((aligner_main_kernel<false, 1, 4, 0, 1>), grid, dim3(256), 0, st, v);
-    }
+        if (a->l2) hipLaunchKernelGGL((aligner_main_kernel<true>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
+        else hipLaunchKernelGGL((aligner_main_kernel<false>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
     }
     // part_edge | part_img and red_edge | red_img are contiguous: one launch reduces the 2E + n entries
     hipLaunchKernelGGL(aligner_reduce_kernel, dim3(2 * a->E + a->n), dim3(256), 0, st, a->part_edge, a->red_edge, a->nslot);

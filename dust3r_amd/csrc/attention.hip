@@ -293,10 +293,6 @@ D3R_DEV float xor32_sum(float v) {
     return a + b;
 }
 
-// PROBE (measurement aid, results invalid when != 0; tools/gpu_probe.py attnparts): bit 0 drops the VALU slices (softmax, P split), bit 1 the
-// MFMAs, bit 2 the per-tile barrier, bit 3 the staging of the next tiles (global loads + LDS writes) -- what each part costs next to the others
-// NW = waves per workgroup (4: 128 queries, two workgroups per CU; 8: 256 queries, one per CU -- every K / V^T tile staged once per 256
-// queries instead of 128: half the L2 -> LDS traffic per query, but nothing covers a workgroup's prologue).
 // DMA (round 4): the K and V^T tiles go L2 -> LDS with global_load_lds_dwordx4 (1 KiB per wave instruction, no VGPR round trip, no ds_write:
 // the ablation of round 3 priced the register staging -- 8 buffer loads + 12 LDS writes per thread and tile -- at 30 % of the kernel). The LDS
 // image of a DMA is lane-linear (lane l's 16 bytes land at base + 16 l), so rows cannot be padded: they are 256 bytes and the bank spread comes
@@ -309,12 +305,11 @@ D3R_DEV float xor32_sum(float v) {
 // (it holds the SIMD's issue port twice as long, and the matrix pipe's next instruction waits behind it) -- 64 of them per tile and wave here.
 // Same values bit for bit (the packed forms are two independent IEEE operations). attention.hip is compiled with -fno-slp-vectorize so that
 // hipcc does not re-pack the scalar pairs (dust3r_amd/build.py).
-// LZ (round 5): LAZY running maximum. The maximum a query's exponents are taken against moves only when the tile's maximum exceeds it by more than 6 octaves
-// (p = exp2(s c - m c) then stays <= 64: far inside fp16's range for the hi / lo split, fp32 for the row sum), so that on most tiles NO query of the wave moves it,
-// alpha = 1 everywhere, and the 32 multiplications per lane that rescale the O accumulators are skipped behind one wave-uniform branch (with an eager maximum at
-// least one of a wave's 32 queries moves it on nearly every tile of a 768-key row). The result is the same softmax(QK^T)V up to fp32 rounding of differently scaled partial sums.
-template <int ODT, int PROBE = 0, int NW = 4, bool DMA = false, bool SC = false, bool LZ = false>
-__global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) {
+// The product launches two instances: DMA with the scalar slices, and register staging with the packed slices (D3R_ATTN_DMA=0).
+constexpr int ATTN_X3_NW = 4;      // waves per workgroup: 128 queries, two workgroups per CU
+template <int ODT, bool DMA, bool SC>
+__global__ __launch_bounds__(ATTN_X3_NW * 64, 2) void attention_x3_kernel(AttnParams p) {
+    constexpr int NW = ATTN_X3_NW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using TR = Traits<D3R_F16X3>;
     constexpr int ROWB = 256, KROW = DMA ? ROWB : ROWB + 16, VROW = DMA ? ROWB : ROWB + 8;
@@ -412,7 +407,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
 
     const int ntiles = (p.Nk + 63) / 64;
     const float c = p.scale * 1.44269504088896340736f;  // fold log2(e): p = exp2(s c - m c)
-    const float lz_thr = 6.0f / c;                        // LZ: six octaves, in score units
     const int koff = DMA ? l31 * KROW : l31 * KROW + hh * 32;   // this lane's K row (/ group inside a 32-key block: padded image)
     const int voff = DMA ? l31 * VROW : l31 * VROW + hh * 8;    // this lane's V^T row (/ 4-key slot: padded image)
     // swizzled images: byte offsets inside the 256-byte row. K: chunk 4 ks + 2 hh + lo; V^T: logical slot 2 g (+ 1: second 8-key group, + 8: lo plane)
@@ -463,7 +457,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
     auto tile_step = [&](auto has_next_c, int t, f32x16_t (&s_cur)[2], f32x16_t (&s_nxt)[2]) __attribute__((always_inline)) {
         constexpr bool HAS_NEXT = decltype(has_next_c)::value;
         if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of K_{t+1} / V_t (issued one tile ago) have landed
-        if constexpr (!(PROBE & 4)) __syncthreads();   // K_{t+1}, V_t are visible; every wave is done with K_t (ring slot t & 1) and V_{t-1} (slot (t + 1) & 1)
+        __syncthreads();   // K_{t+1}, V_t are visible; every wave is done with K_t (ring slot t & 1) and V_{t-1} (slot (t + 1) & 1)
         const char* kb = smem + ((t + 1) & 1) * KT + koff;
         uint4 kh = make_uint4(0, 0, 0, 0), kl = kh;
         if constexpr (HAS_NEXT) {       // the first K fragment of S_{t+1}: requested right behind the barrier, used ~60 instructions later
@@ -473,21 +467,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
         if constexpr (HAS_NEXT && DMA) {
             dma_k(min(t + 2, last) * 64, t & 1);       // K_{t+2} (at t = ntiles - 2 a second copy of the last tile: that slot is not read again)
             dma_v((t + 1) * 64, (t + 1) & 1);          // V_{t+1}
-        } else if constexpr (HAS_NEXT && !(PROBE & 8)) {
-            if constexpr (!(PROBE & 16)) {
-                lds_put_k(t & 1);            // K_{t+2} (at t = ntiles - 2 a second copy of the last tile: that slot is not read again)
-                lds_put_v((t + 1) & 1);      // V_{t+1}
-            } else {                         // probe: loads without the LDS writes (kept alive)
-#pragma unroll
-                for (int i = 0; i < NP; ++i) {
-                    const u32x4b_t kk = {kst[i].x, kst[i].y, kst[i].z, kst[i].w}, vv = {vst[i].x, vst[i].y, vst[i].z, vst[i].w};
-                    asm volatile("" :: "v"(kk), "v"(vv));
-                }
-            }
-            if constexpr (!(PROBE & 32)) {
-                gload_k(min(t + 3, last) * 64);
-                gload_v(min(t + 2, last) * 64);
-            }
+        } else if constexpr (HAS_NEXT) {
+            lds_put_k(t & 1);            // K_{t+2} (at t = ntiles - 2 a second copy of the last tile: that slot is not read again)
+            lds_put_v((t + 1) & 1);      // V_{t+1}
+            gload_k(min(t + 3, last) * 64);
+            gload_v(min(t + 2, last) * 64);
         } else if constexpr (!HAS_NEXT) {
             // keys beyond Nk: only the last tile of a ragged sequence has them (selects, no branch)
 #pragma unroll
@@ -499,7 +483,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
                 }
         }
         float mt = -1e30f, m_new = 0.f, alpha = 1.f, mcn = 0.f;
-        bool resc = true;                             // LZ: does any query of this wave move its maximum on this tile (wave-uniform)
         v2f_t ps2 = {0.f, 0.f}, aa = {0.f, 0.f};      // row sum; the pair of exponents in flight between two slices
         float ps0 = 0.f, ps1 = 0.f, aa0 = 0.f, aa1 = 0.f;   // SC: the same as four scalars (the pins below carry whichever set is live)
         u32x4_t pH[2], pL[2];                         // P operands of PV group g in set g & 1 (hi and lo halves)
@@ -546,12 +529,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
                 mt = fmaxf(fmaxf(mt, sv[r0 + 6]), sv[r0 + 7]);
             } else if (v == 4) {               // lanes l and l ^ 32 share a query
                 mt = xor32_max(mt);
-                if constexpr (LZ) {
-                    m_new = mt > m_run + lz_thr ? mt : m_run;
-                    resc = __builtin_amdgcn_ballot_w64(m_new != m_run) != 0ull;
-                } else {
                 m_new = fmaxf(m_run, mt);
-                }
                 alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
                 mcn = -m_new * c;
                 if constexpr (SC) {
@@ -587,7 +565,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
                     aa = __builtin_elementwise_fma(sv, c2, m2);
                     }
                 }
-                if (i == 16 && resc) {         // rescale O: first d-block (the PV MFMAs of this tile come after phase A)
+                if (i == 16) {                 // rescale O: first d-block (the PV MFMAs of this tile come after phase A)
                     if constexpr (SC) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) o[0][r] *= alpha;
@@ -602,8 +580,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
                     }
                 }
             } else if (v == 22) {              // second d-block
-                if (!resc) {
-                } else
                 if constexpr (SC) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) o[1][r] *= alpha;
@@ -636,22 +612,21 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
                     nh = *reinterpret_cast<const uint4*>(kfrag_ptr(kb, st + 1, 0));
                     nl = *reinterpret_cast<const uint4*>(kfrag_ptr(kb, st + 1, 1));
                 }
-                if constexpr (!(PROBE & 2)) s_nxt[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q8(kl), q8(qf[2 * ks]), st < 2 ? zero16 : s_nxt[rb], 0, 0, 0);
-                else if (st < 2) s_nxt[rb] = zero16;
+                s_nxt[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q8(kl), q8(qf[2 * ks]), st < 2 ? zero16 : s_nxt[rb], 0, 0, 0);
                 if (st == 0) { PIN_A1(); } else { PIN_A(); }
-                if constexpr (!(PROBE & 1)) valu_slice(3 * st);
-                if constexpr (!(PROBE & 2)) s_nxt[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q8(kh), q8(qf[2 * ks + 1]), s_nxt[rb], 0, 0, 0);
+                valu_slice(3 * st);
+                s_nxt[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q8(kh), q8(qf[2 * ks + 1]), s_nxt[rb], 0, 0, 0);
                 if (st == 0) { PIN_A1(); } else { PIN_A(); }
-                if constexpr (!(PROBE & 1)) valu_slice(3 * st + 1);
-                if constexpr (!(PROBE & 2)) s_nxt[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q8(kh), q8(qf[2 * ks]), s_nxt[rb], 0, 0, 0);
+                valu_slice(3 * st + 1);
+                s_nxt[rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q8(kh), q8(qf[2 * ks]), s_nxt[rb], 0, 0, 0);
                 if (st == 0) { PIN_A1(); } else { PIN_A(); }
-                if constexpr (!(PROBE & 1)) valu_slice(3 * st + 2);
+                valu_slice(3 * st + 2);
                 kh = nh; kl = nl;
             }
             PIN_A();
         } else {
 #pragma unroll
-            for (int v = 0; v < 24; ++v) if constexpr (!(PROBE & 1)) valu_slice(v);
+            for (int v = 0; v < 24; ++v) valu_slice(v);
         }
         // ---- phase B: O^T += V_t^T P_t^T, contraction over keys permuted identically on both operands ---------------------------
         // unit u = (group g = (rb, sh): 16 keys, d-block db): 3 MFMAs; the next unit's V^T fragments are read, and (over a group's two
@@ -683,13 +658,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
             const int nrb = (g + 1) >> 1, nsh = (g + 1) & 1;
             u32x4_t nvh = vh, nvl = vl;
             if (u + 1 < 8) vfrag(u + 1, nvh, nvl);
-            if constexpr (!(PROBE & 2)) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(vl), h8(pH[cs]), o[db], 0, 0, 0);
+            o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(vl), h8(pH[cs]), o[db], 0, 0, 0);
             PIN_B();
-            if constexpr (!(PROBE & 1)) if (g + 1 < 4) SPLIT2(s_cur[nrb][8 * nsh + 4 * db], s_cur[nrb][8 * nsh + 4 * db + 1], pH[ns], pL[ns], 2 * db)
-            if constexpr (!(PROBE & 2)) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(vh), h8(pL[cs]), o[db], 0, 0, 0);
+            if (g + 1 < 4) SPLIT2(s_cur[nrb][8 * nsh + 4 * db], s_cur[nrb][8 * nsh + 4 * db + 1], pH[ns], pL[ns], 2 * db)
+            o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(vh), h8(pL[cs]), o[db], 0, 0, 0);
             PIN_B();
-            if constexpr (!(PROBE & 1)) if (g + 1 < 4) SPLIT2(s_cur[nrb][8 * nsh + 4 * db + 2], s_cur[nrb][8 * nsh + 4 * db + 3], pH[ns], pL[ns], 2 * db + 1)
-            if constexpr (!(PROBE & 2)) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(vh), h8(pH[cs]), o[db], 0, 0, 0);
+            if (g + 1 < 4) SPLIT2(s_cur[nrb][8 * nsh + 4 * db + 2], s_cur[nrb][8 * nsh + 4 * db + 3], pH[ns], pL[ns], 2 * db + 1)
+            o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h8(vh), h8(pH[cs]), o[db], 0, 0, 0);
             PIN_B();
             vh = nvh; vl = nvl;
         }
@@ -750,58 +725,31 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(AttnParams p) 
     }
 }
 
-template <int ODT, int PROBE, int NW = 4, bool DMA = false, bool SC = false, bool LZ = false> static hipError_t launch_x3_v2p(const AttnParams& p, hipStream_t s) {
+template <int ODT, bool DMA, bool SC> static hipError_t launch_x3_v2p(const AttnParams& p, hipStream_t s) {
     constexpr int LDS = DMA ? 4 * 64 * 256 : 2 * 64 * (256 + 16) + 2 * 64 * (256 + 8);
+    constexpr int QPB = ATTN_X3_NW * 32;
     static std::atomic<unsigned long long> attr_done{0};
     int dev_id = 0;
     (void)hipGetDevice(&dev_id);
     const unsigned long long dev_bit = 1ull << (dev_id & 63);
     if (!(attr_done.load(std::memory_order_relaxed) & dev_bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x3_kernel<ODT, PROBE, NW, DMA, SC, LZ>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x3_kernel<ODT, DMA, SC>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         attr_done.fetch_or(dev_bit, std::memory_order_relaxed);
     }
-    const int grid = p.B * p.H * ((p.Nq + NW * 32 - 1) / (NW * 32));
-    hipLaunchKernelGGL((attention_x3_kernel<ODT, PROBE, NW, DMA, SC, LZ>), dim3(grid), dim3(NW * 64), LDS, s, p);
+    const int grid = p.B * p.H * ((p.Nq + QPB - 1) / QPB);
+    hipLaunchKernelGGL((attention_x3_kernel<ODT, DMA, SC>), dim3(grid), dim3(ATTN_X3_NW * 64), LDS, s, p);
     return hipGetLastError();
 }
 template <int ODT> static hipError_t launch_x3_v2(const AttnParams& p, hipStream_t s) {
-    if constexpr (kProbes && ODT == D3R_F16X3) {
-        if (const char* e = probe_env("D3R_ATTN_PROBE")) {      // ablation instances (results invalid), see the kernel
-            switch (atoi(e)) {
-                case 1: return launch_x3_v2p<ODT, 1>(p, s);
-                case 2: return launch_x3_v2p<ODT, 2>(p, s);
-                case 4: return launch_x3_v2p<ODT, 4>(p, s);
-                case 8: return launch_x3_v2p<ODT, 8>(p, s);
-                case 12: return launch_x3_v2p<ODT, 12>(p, s);
-                case 13: return launch_x3_v2p<ODT, 13>(p, s);
-                case 14: return launch_x3_v2p<ODT, 14>(p, s);
-                case 16: return launch_x3_v2p<ODT, 16>(p, s);
-                case 32: return launch_x3_v2p<ODT, 32>(p, s);
-                default: break;
-            }
-        }
-    }
-    if constexpr (kProbes) if (const char* e = probe_env("D3R_ATTN_NW")) {
-        if (e[0] == '8' && e[1] == 0) return launch_x3_v2p<ODT, 0, 8>(p, s);   // probe: 256 queries per workgroup (register staging, packed softmax: round 3's instance)
-        // probe '8d' / '8e': 256 queries per workgroup with DMA staging and the scalar softmax slices, everywhere / for launches of >= 2048 workgroups of 128 queries only
-        if (e[0] == '8' && (e[1] == 'd' || (e[1] == 'e' && (long)p.B * p.H * ((p.Nq + 127) / 128) >= 4096))) return launch_x3_v2p<ODT, 0, 8, true, true>(p, s);
-    }
     // K / V^T tiles by global_load_lds DMA into swizzled 256-byte rows (default since round 4; D3R_ATTN_DMA=0: staged through registers into padded
     // rows; read per launch). Measured (profiles/r04_b/attndma.log, ab_attn_dma.txt): 64 x 16 heads 512 -> 492 us, 32 x 12 heads equal, forward
     // 193.15 -> 193.5 pairs/s; bit-identical outputs (tests/test_kernels_gpu.py::test_attention_split_fp16_dma_staging_is_bit_identical).
+    // With DMA the softmax / split slices run on scalar fp32 VALU (round 5; bit-identical to the packed v_pk_* form). Measured in one process on one
+    // box (profiles/r05_b/ab_probe.log, three alternating repetitions of the 32-pair forward): attention 21.20 -> 20.72 ms per step, forward
+    // 171.29 -> 170.83 ms.
     const char* e_dma = getenv("D3R_ATTN_DMA");
-    // The softmax / split slices on scalar fp32 VALU (default since round 5; D3R_ATTN_SC=0: the packed v_pk_* form; bit-identical; read per launch).
-    // Measured in one process on one box (tools/ab_probe.py, profiles/r05_b/ab_probe.log, three alternating repetitions of the 32-pair forward):
-    // attention 21.20 -> 20.72 ms per step, forward 171.29 -> 170.83 ms.
-    const char* e_sc = probe_env("D3R_ATTN_SC");
-    const char* e_lz = probe_env("D3R_ATTN_LAZY");          // 1: lazy running maximum (round 5 probe; read per launch)
     const bool dma = e_dma ? e_dma[0] != '0' : true;
-    if constexpr (kProbes) {        // the lazy-maximum and DMA + packed-softmax instances: probe builds only (-DD3R_PROBES)
-        if (dma && !(e_sc && e_sc[0] == '0') && e_lz && e_lz[0] == '1') return launch_x3_v2p<ODT, 0, 4, true, true, true>(p, s);
-        if (dma && e_sc && e_sc[0] == '0') return launch_x3_v2p<ODT, 0, 4, true>(p, s);
-    }
-    (void)e_sc; (void)e_lz;
-    return dma ? launch_x3_v2p<ODT, 0, 4, true, true>(p, s) : launch_x3_v2p<ODT, 0>(p, s);
+    return dma ? launch_x3_v2p<ODT, true, true>(p, s) : launch_x3_v2p<ODT, false, false>(p, s);
 }
 
 template <int DT, int ODT = DT> static hipError_t launch_t(const AttnParams& p, hipStream_t s) {

@@ -38,7 +38,7 @@ extern "C" int d3r_linear_x3res(const void* act, const void* wgt, const float* b
     return rc_of(launch_gemm(D3R_F16X3, p, (hipStream_t)stream));
 }
 
-extern "C" int d3r_conv_k_slice_major(void) { return d3r::conv_k_slice_major() ? 1 : 0; }
+extern "C" int d3r_conv_k_slice_major(void) { return 1; }
 
 extern "C" int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bias, void* out, const void* res1, const void* res2, void* out_relu_copy,
                                int B, int Hin, int Win, int Cin, int Cout, int ksize, int stride, int pad, int relu, const void* zero_page, int dtype,
@@ -73,8 +73,8 @@ extern "C" int d3r_gemm_set_trace(void* buf, size_t capacity_blocks) {
     return D3R_OK;
 }
 
-// 1: this library was compiled with -DD3R_PROBES (ablation kernels and probe-only environment switches present), 0: the default build
-extern "C" int d3r_build_has_probes(void) { return kProbes ? 1 : 0; }
+// 0: there is one build flavour, without the ablation kernels of earlier rounds; kept for the C ABI
+extern "C" int d3r_build_has_probes(void) { return 0; }
 
 // Diagnostics, host only (no GPU, no launch): the tile configuration the heuristic of gemm.hip picks for an nn.Linear-shaped problem
 // (same `epilogue` codes as d3r_linear; with_residual: an fp32 residual is added). The dispatch table of DESIGN.md section 4.1 as a function.

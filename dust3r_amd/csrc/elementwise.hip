@@ -354,17 +354,16 @@ __global__ __launch_bounds__(256) void upsample2x_quad_kernel(const void* __rest
 
 template <int DT> static void launch_upsample_t(const void* in, void* out, void* out_relu, int B, int Hi, int Wi, int C, int cstride, int Ho, int Wo,
                                                 hipStream_t s) {
-    // non-temporal stores of the x2 maps: measured 13.41 -> 12.75 ms of "other" kernels per step, forward 218.7 -> 219.6 pairs/s
-    // (profiles/r02_f8/bench_upsample_nt.log); D3R_UPSAMPLE_NT=0: plain stores
-    static const bool nt = [] { const char* e = probe_env("D3R_UPSAMPLE_NT"); return e ? e[0] != '0' : true; }();
+    // split-fp16: non-temporal stores of the x2 maps. Measured 13.41 -> 12.75 ms of "other" kernels per step, forward 218.7 -> 219.6 pairs/s
+    // (profiles/r02_f8/bench_upsample_nt.log)
     const char* e_v1 = getenv("D3R_UPSAMPLE_V1");            // 1: the one-output-pixel-per-thread kernel (A/B, parity tests); read per launch
     if (!(e_v1 && e_v1[0] == '1') && C % 8 == 0 && cstride % 8 == 0) {
         const int blocks = B * ((Ho + 1) / 2);
-        if (DT == D3R_F16X3 && nt) hipLaunchKernelGGL((upsample2x_quad_kernel<DT, true>), dim3(blocks), dim3(256), 0, s, in, out, out_relu, Hi, Wi, C, cstride, Ho, Wo);
+        if (DT == D3R_F16X3) hipLaunchKernelGGL((upsample2x_quad_kernel<DT, true>), dim3(blocks), dim3(256), 0, s, in, out, out_relu, Hi, Wi, C, cstride, Ho, Wo);
         else hipLaunchKernelGGL((upsample2x_quad_kernel<DT, false>), dim3(blocks), dim3(256), 0, s, in, out, out_relu, Hi, Wi, C, cstride, Ho, Wo);
         return;
     }
-    if (DT == D3R_F16X3 && nt && C % 8 == 0 && cstride % 8 == 0)
+    if (DT == D3R_F16X3 && C % 8 == 0 && cstride % 8 == 0)
         hipLaunchKernelGGL((upsample2x_kernel<DT, 2, true>), dim3(B * Ho), dim3(256), 0, s, in, out, out_relu, Hi, Wi, C, cstride, Ho, Wo);
     else if (C % 8 == 0 && cstride % 8 == 0) hipLaunchKernelGGL((upsample2x_kernel<DT, 2>), dim3(B * Ho), dim3(256), 0, s, in, out, out_relu, Hi, Wi, C, cstride, Ho, Wo);
     else hipLaunchKernelGGL((upsample2x_kernel<DT, 1>), dim3(B * Ho), dim3(256), 0, s, in, out, out_relu, Hi, Wi, C, cstride, Ho, Wo);
@@ -506,17 +505,13 @@ template <int DT> __global__ __launch_bounds__(256) void pack_weight_kernel(Pack
         const size_t r = i / p.cols, c = i - r * p.cols;
         d = (r + p.row_off) * (size_t)p.dst_cols + c;
         if (p.kscale) v *= p.kscale[c];          // W diag(gamma): the LayerNorm in front of this nn.Linear is folded into it (kernels.hpp, GemmParams::ln_*)
-    } else if (p.kind == PACK_CONV) {            // [Cout][Cin][k][k] -> [co][(ky*k+kx)*cin_pad + ci]
+    } else if (p.kind == PACK_CONV) {            // [Cout][Cin][k][k] -> [co][(ci / KS) * (k*k*KS) + t * KS + ci % KS], KS = elements of one K step (gemm.hip conv_k_step)
         const int kk = p.ksize * p.ksize;
         const size_t co = i / ((size_t)p.cin * kk);
         const int rem = (int)(i - co * (size_t)p.cin * kk);
         const int ci = rem / kk, t = rem - ci * kk;
-        if (p.kslice_major) {                    // [co][(ci / KS) * (k*k*KS) + t * KS + ci % KS], KS = elements of one K step
-            constexpr int KS = 128 / Traits<DT>::EB;
-            d = co * (size_t)p.dst_cols + (size_t)(ci / KS) * ((size_t)kk * KS) + (size_t)t * KS + (ci % KS);
-        } else {
-            d = co * (size_t)p.dst_cols + (size_t)t * p.cin_pad + ci;
-        }
+        constexpr int KS = 128 / Traits<DT>::EB;
+        d = co * (size_t)p.dst_cols + (size_t)(ci / KS) * ((size_t)kk * KS) + (size_t)t * KS + (ci % KS);
     } else {                                     // PACK_CONVT: [Cin][Cout][k][k] -> [(ky*k+kx)*cout_pad + co][ci]
         const int kk = p.ksize * p.ksize;
         const size_t ci = i / ((size_t)p.cols * kk);

@@ -103,7 +103,6 @@ struct d3r_model {
                               // (GemmParams::ln_part_in; kernels.hpp ln_row_stats = ln_finalize_kernel's arithmetic with four adjacent lanes per row) instead of by an ln_finalize
                               // launch: bit-identical, one pair 10.32 -> 10.10 ms, two 15.27 -> 15.09, four and eight equal (profiles/r05_y/ln_inline3.log; the first version, 32
                               // lanes per row with five fp64 exchange levels in front of every tile, was SLOWER: r05_v). D3R_LN_INLINE_ROWS=n at creation; 0 = always launch.
-    int enc_split_max = 0;    // encoder of calls with <= this many images (two views): the two views as two concurrent chains on the two streams (D3R_ENC_SPLIT)
     bool ln_fold = false, fold_dirty = false;
     std::vector<Lin*> fold_lins;
     std::unordered_map<std::string, Slot> slots;
@@ -128,12 +127,6 @@ struct d3r_model {
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
     bool two_streams = true;
-    // Cross-attention K | V of a decoder block read the OTHER side's previous-layer output, not the side's own chain: with at most kv_ahead_rows rows per side (calls of
-    // a few pairs: a chain of launches that each fill a fraction of the chip) they run on a third / fourth stream beside the block's self attention, into their own K / V^T
-    // buffers, and the side's stream waits for them in front of the cross attention. Same kernels on the same rows: bit-identical. D3R_DEC_KV_AHEAD=rows (0 = off).
-    hipStream_t kvs[2] = {nullptr, nullptr};
-    hipEvent_t ev_kv_go[2] = {nullptr, nullptr}, ev_kv_done[2] = {nullptr, nullptr};
-    int kv_ahead_rows = 0;
     PostMode post;                          // depth_mode / conf_mode of the heads (d3r_model_set_postprocess; default = the released checkpoints')
     int out_pstride = 3, out_cstride = 1;   // output element strides between pixels (8, 8 while d3r_model_forward_packed runs)
     // ---- hipGraph replay of small-batch forwards (d3r_model_forward* with B <= graph_max_pairs) ------------------------------------
@@ -375,7 +368,7 @@ int pack_slot(d3r_model* m, Slot& s, const float* data, int ndim, const int64_t*
             break;
         case PK_CONV:
             if (ndim != 4 || shape[0] != s.rows || shape[1] != s.cin || shape[2] != s.ksize || shape[3] != s.ksize) return D3R_ERR_SHAPE;
-            pp.kind = PACK_CONV; pp.cin = s.cin; pp.cin_pad = s.cin_pad; pp.ksize = s.ksize; pp.kslice_major = conv_k_slice_major() ? 1 : 0;
+            pp.kind = PACK_CONV; pp.cin = s.cin; pp.cin_pad = s.cin_pad; pp.ksize = s.ksize;
             break;
         case PK_CONVT:
             if (ndim != 4 || shape[0] != s.rows || shape[1] != s.cols || shape[2] != s.ksize || shape[3] != s.ksize) return D3R_ERR_SHAPE;
@@ -444,16 +437,6 @@ void gemm_heads(Ctx& c, const void* act, int lda, const Lin& L, int M, int head_
     p.epi = EPI_HEADS; p.head_c = head_c;
     for (int i = 0; i < nreg; ++i) { p.head_kind[i] = kinds[i]; p.head_dst[i] = dsts[i]; }
     p.heads = heads; p.ntok = ntok; p.tok_w = tok_w; p.ldv = ldv; p.rope_table = c.m->rope_table;
-    if constexpr (kProbes) {    // measurement aids, results INVALID (tools/launch_table.py): what the V^T scatter / the RoPE of the attention projections' epilogue cost --
-        // D3R_PROBE_V_PLAIN=1 stores the V region row-major like K (the GEMM side of a design whose attention kernel transposes V with ds_read_b64_tr_b16),
-        // D3R_PROBE_QK_PLAIN=1 stores q / k without the rotation
-        const char* ev = probe_env("D3R_PROBE_V_PLAIN");
-        const char* eq = probe_env("D3R_PROBE_QK_PLAIN");
-        for (int i = 0; i < nreg; ++i) {
-            if (ev && ev[0] == '1' && p.head_kind[i] == HEAD_VT) p.head_kind[i] = HEAD_PLAIN;
-            if (eq && eq[0] == '1' && p.head_kind[i] == HEAD_ROPE) p.head_kind[i] = HEAD_PLAIN;
-        }
-    }
     c.mark(prf_kind((L.dt == D3R_F16F8 || L.dt == D3R_F16X2F8) ? PRF_GEMM_F8 : PRF_GEMM, gemm_pick_config(p, L.dt)), 2.0 * M * (double)L.N * L.K, M, L.N, L.K);
     c.chk(launch_gemm(L.dt, p, c.st));
 }
@@ -559,15 +542,7 @@ extern "C" int d3r_model_create(d3r_model** out, const d3r_model_config* cfg) {
     if (!m->side || hipEventCreateWithFlags(&m->ev_main, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&m->ev_side, hipEventDisableTiming) != hipSuccess) { d3r_model_destroy(m); return D3R_ERR_ALLOC; }
     if (const char* e = getenv("D3R_GRAPH_MAX_PAIRS")) m->graph_max_pairs = atoi(e) > 0 ? atoi(e) : 0;
-    if (const char* e = probe_env("D3R_ENC_SPLIT")) m->enc_split_max = atoi(e) > 0 ? atoi(e) : 0;
     if (const char* e = getenv("D3R_LN_INLINE_ROWS")) m->ln_inline_rows = atoi(e) > 0 ? atoi(e) : 0;
-    if (const char* e = probe_env("D3R_DEC_KV_AHEAD")) m->kv_ahead_rows = atoi(e) > 0 ? atoi(e) : 0;
-    if (m->kv_ahead_rows > 0)          // probe only: its two streams and four events exist when it is switched on
-        for (int s = 0; s < 2; ++s) {
-            m->kvs[s] = shared_stream(1 + s);
-            if (!m->kvs[s] || hipEventCreateWithFlags(&m->ev_kv_go[s], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&m->ev_kv_done[s], hipEventDisableTiming) != hipSuccess) { d3r_model_destroy(m); return D3R_ERR_ALLOC; }
-        }
     (void)hipDeviceSynchronize();
     *out = m;
     return D3R_OK;
@@ -581,11 +556,6 @@ extern "C" int d3r_model_destroy(d3r_model* m) {
     if (m->ev_main) (void)hipEventDestroy(m->ev_main);
     if (m->ev_side) (void)hipEventDestroy(m->ev_side);
     if (m->side) (void)hipStreamSynchronize(m->side);      // shared with the process' other engines (shared_stream): drained, never destroyed
-    for (int s = 0; s < 2; ++s) {
-        if (m->kvs[s]) (void)hipStreamSynchronize(m->kvs[s]);
-        if (m->ev_kv_go[s]) (void)hipEventDestroy(m->ev_kv_go[s]);
-        if (m->ev_kv_done[s]) (void)hipEventDestroy(m->ev_kv_done[s]);
-    }
     m->drop_graphs();
     if (m->cap) (void)hipStreamDestroy(m->cap);
     if (m->ws) (void)hipFree(m->ws);
@@ -895,10 +865,7 @@ size_t forward_impl(d3r_model* m, void* ws, size_t ws_cap, int phases, const flo
     float *e_part = nullptr, *e_rs = nullptr, *e_nm = nullptr, *l_part[2] = {nullptr, nullptr}, *l_rs[2] = {nullptr, nullptr}, *l_nm[2] = {nullptr, nullptr};
     float *s_part[2] = {nullptr, nullptr}, *s_rs[2] = {nullptr, nullptr}, *s_nm[2] = {nullptr, nullptr};
     void* fr[2] = {nullptr, nullptr};
-    void *ckb = nullptr, *cvtb = nullptr;      // cross-attention K / V^T of the two sides when they are projected ahead on their own streams (d3r_model::kvs)
     if (fold) {
-        ckb = ar.take((size_t)2 * Mmax * Cd * eb);
-        cvtb = ar.take((size_t)2 * B * Hd * 64 * ldv_max * eb);
         e_part = (float*)ar.take((size_t)Me * Ge * 8); e_rs = (float*)ar.take((size_t)Me * 4 + 16); e_nm = (float*)ar.take((size_t)Me * 4 + 16);
         for (int b = 0; b < 2; ++b) {
             fr[b] = ar.take((size_t)M2d * Cd * eb);
@@ -929,48 +896,36 @@ size_t forward_impl(d3r_model* m, void* ws, size_t ws_cap, int phases, const flo
             c.chk(hipStreamWaitEvent(S[1], m->ev_main, 0));
         };
         if (d0.ldv != d0.N || d1.ldv != d1.N) D3R_OTHER(hipMemsetAsync(vt, 0, (size_t)nvt * Hmax * 64 * ldv_max * eb, st));
-        const bool kva = two && fold && do_dec && m->kvs[0] && m->kvs[1] && Mmax <= m->kv_ahead_rows;
-        if (kva && (d0.ldv != d0.N || d1.ldv != d1.N)) D3R_OTHER(hipMemsetAsync(cvtb, 0, (size_t)2 * B * Hd * 64 * ldv_max * eb, st));
         if (do_enc) {
             // ---- encoder: all images of the call in one pass when the views share a size (model.py:142-151 concatenates the
             // two views), else view 1's images then view 2's (model.py:148-150) -----------------------------------------------
             const size_t pk = 3 * (size_t)ps * ps;
-            // Encoder work is a list of GROUPS of images of one size: one group (both views) when the views share a size, else one per view. Round 5: small calls
-            // (<= enc_split_max images, two views, two streams on) run the two views as two groups CONCURRENTLY, view 2 on the model's second stream with its
-            // own rows of every scratch buffer -- one pair per call is a dependent chain of kernels that each fill a fraction of the chip, and two
-            // independent chains fill it better (what the decoder's two sides already do). Same kernels on the same rows: bit-identical.
-            struct EncGroup { const float* im[2]; int n[2]; const SideDim* dd; size_t row0; int img0; hipStream_t s; bool off; };
+            // Encoder work is a list of GROUPS of images of one size: one group (both views) when the views share a size, else one per view, one after the
+            // other on the caller's stream, each in the scratch buffers from row 0.
+            struct EncGroup { const float* im[2]; int n[2]; const SideDim* dd; size_t row0; };
             EncGroup groups[2];
             int ngroups = 0;
-            const bool split = two && nimg1 > 0 && nimg > nimg1 && nimg <= m->enc_split_max;
-            if (same && !split) {
-                groups[ngroups++] = EncGroup{{img1, img2}, {nimg1, nimg - nimg1}, &D[0], 0, 0, st, false};
+            if (same) {
+                groups[ngroups++] = EncGroup{{img1, img2}, {nimg1, nimg - nimg1}, &D[0], 0};
             } else {
-                if (nimg1 > 0) groups[ngroups++] = EncGroup{{img1, nullptr}, {nimg1, 0}, &D[0], 0, 0, st, split};
-                if (nimg > nimg1) groups[ngroups++] = EncGroup{{img2, nullptr}, {nimg - nimg1, 0}, &D[same ? 0 : 1], (size_t)nimg1 * d0.N, nimg1, split ? S[1] : st, split};
-            }
-            if (split) {      // view 2's stream starts behind everything the caller's stream holds (the images, the v^T clear)
-                c.chk(hipEventRecord(m->ev_main, S[0]));
-                c.chk(hipStreamWaitEvent(S[1], m->ev_main, 0));
+                if (nimg1 > 0) groups[ngroups++] = EncGroup{{img1, nullptr}, {nimg1, 0}, &D[0], 0};
+                if (nimg > nimg1) groups[ngroups++] = EncGroup{{img2, nullptr}, {nimg - nimg1, 0}, &D[1], (size_t)nimg1 * d0.N};
             }
             // phase -1: patches + patch embedding; 0 .. depth - 1: block l; depth: enc_norm
             auto enc_phase = [&](const EncGroup& g, int phase) {
                 const SideDim& dd = *g.dd;
                 const int n_img = g.n[0] + g.n[1];
                 const int Mp = n_img * dd.N;
-                c.st = g.s;
-                // a group that runs next to another one works in its own rows of the scratch buffers (sequential groups reuse them from row 0, as before)
-                const size_t ro = g.off ? g.row0 : 0;
                 float* xp = x + g.row0 * Ce;
-                void* gxn = (char*)xn + ro * Ce * eb;
-                void* gq = (char*)q + ro * Ce * eb;
-                void* gk = (char*)k + ro * Ce * eb;
-                void* gvt = (char*)vt + (size_t)(g.off ? g.img0 : 0) * He * 64 * dd.ldv * eb;
-                void* gao = (char*)ao + ro * Ce * eb;
-                void* ghb = (char*)hb + ro * 4 * Ce * eb;        // hidden rows; the patches of the group start at the same place
-                float* gpart = fold ? e_part + ro * Ge * 2 : nullptr;
-                float* grs = fold ? e_rs + ro : nullptr;
-                float* gnm = fold ? e_nm + ro : nullptr;
+                void* gxn = xn;
+                void* gq = q;
+                void* gk = k;
+                void* gvt = vt;
+                void* gao = ao;
+                void* ghb = hb;        // hidden rows; the patches of the group start at the same place
+                float* gpart = fold ? e_part : nullptr;
+                float* grs = fold ? e_rs : nullptr;
+                float* gnm = fold ? e_nm : nullptr;
                 const bool inl = fold && Mp <= inline_rows;
                 const LnStats es{grs, gnm, inl ? gpart : nullptr};
                 if (phase < 0) {
@@ -1004,16 +959,8 @@ size_t forward_impl(d3r_model* m, void* ws, size_t ws_cap, int phases, const flo
                     else D3R_OTHER(launch_layernorm(m->dt, xp, m->enc_norm.g, m->enc_norm.b, dst, Mp, Ce, 1e-6f, c.st));
                 }
             };
-            if (split) {       // layer by layer, so that both streams have work queued from the start
-                for (int phase = -1; phase <= cf.enc_depth; ++phase)
-                    for (int gi = 0; gi < ngroups; ++gi) enc_phase(groups[gi], phase);
-                c.chk(hipEventRecord(m->ev_side, S[1]));           // the caller's stream continues behind view 2's encoder
-                c.chk(hipStreamWaitEvent(S[0], m->ev_side, 0));
-            } else {
-                for (int gi = 0; gi < ngroups; ++gi)
-                    for (int phase = -1; phase <= cf.enc_depth; ++phase) enc_phase(groups[gi], phase);
-            }
-            c.st = st;
+            for (int gi = 0; gi < ngroups; ++gi)
+                for (int phase = -1; phase <= cf.enc_depth; ++phase) enc_phase(groups[gi], phase);
             m->last_encn = encn; m->last_encn_elems = (size_t)Me * Ce;
         }
         if (do_dec) {
@@ -1055,22 +1002,6 @@ size_t forward_impl(d3r_model* m, void* ws, size_t ws_cap, int phases, const flo
                     const LnStats sx{l_rs[cur] + Roff[s], l_nm[cur] + Roff[s], inl_own ? l_part[cur] + (size_t)Roff[s] * Gd * 2 : nullptr},
                                   sy{l_rs[cur] + Roff[1 - s], l_nm[cur] + Roff[1 - s], inl_oth ? l_part[cur] + (size_t)Roff[1 - s] * Gd * 2 : nullptr},
                                   ss{s_rs[s], s_nm[s], inl_own ? s_part[s] : nullptr};
-                    void* xk = sk;
-                    void* xvt = svt;
-                    if (kva) {
-                        // S[s] stands behind the layer boundary here (the other side's rows and statistics are complete) and behind this side's previous cross attention
-                        // (the last reader of xk / xvt): the projection may start now, beside the self attention
-                        xk = (char*)ckb + (size_t)s * Mmax * Cd * eb;
-                        xvt = (char*)cvtb + (size_t)s * B * Hd * 64 * ldv_max * eb;
-                        c.chk(hipEventRecord(m->ev_kv_go[s], S[s]));
-                        c.chk(hipStreamWaitEvent(m->kvs[s], m->ev_kv_go[s], 0));
-                        c.st = m->kvs[s];
-                        const int kkv[2] = {HEAD_ROPE, HEAD_VT};
-                        void* dkv[2] = {xk, xvt};
-                        gemm_heads(c, frp[cur][1 - s], Cd, b.ckv, Ms[1 - s], Cd, 2, kkv, dkv, Hd, oth.N, oth.tw, oth.ldv, sy);
-                        c.chk(hipEventRecord(m->ev_kv_done[s], m->kvs[s]));
-                        c.st = S[s];
-                    }
                     self_attention(c, frp[cur][s], b.qkv, Ms[s], Cd, Hd, B, own.N, own.tw, own.ldv, sq, sk, svt, sao, sx);      // norm1 folded
                     // the residual stream is the typed rows themselves (GF_X3RES): layer input frp[cur][s] -> sxn (after self attention, then in place after
                     // cross attention) -> the next layer's input fr[cur ^ 1] (or a DPT hook buffer)
@@ -1080,14 +1011,11 @@ size_t forward_impl(d3r_model* m, void* ws, size_t ws_cap, int phases, const flo
                         const int kq[1] = {HEAD_ROPE};
                         void* dq[1] = {sq};
                         gemm_heads(c, sxn, Cd, b.cq, Ms[s], Cd, 1, kq, dq, Hd, own.N, own.tw, own.ldv, ss);                     // norm2 folded
-                        if (kva) c.chk(hipStreamWaitEvent(S[s], m->ev_kv_done[s], 0));
-                        else {
                         const int kkv[2] = {HEAD_ROPE, HEAD_VT};
                         void* dkv[2] = {sk, svt};
                         gemm_heads(c, frp[cur][1 - s], Cd, b.ckv, Ms[1 - s], Cd, 2, kkv, dkv, Hd, oth.N, oth.tw, oth.ldv, sy);  // norm_y folded: the other side's raw rows and statistics
-                        }
                         AttnParams a;
-                        a.q = sq; a.k = xk; a.vt = xvt; a.out = sao; a.B = B; a.H = Hd; a.Nq = own.N; a.Nk = oth.N; a.ldv = oth.ldv; a.scale = 0.125f;
+                        a.q = sq; a.k = sk; a.vt = svt; a.out = sao; a.B = B; a.H = Hd; a.Nq = own.N; a.Nk = oth.N; a.ldv = oth.ldv; a.scale = 0.125f;
                         a.out_dt = m->bdt;
                         c.mark(PRF_ATTN, 4.0 * B * Hd * (double)own.N * oth.N * 64, B * Hd, own.N, oth.N);
                         c.chk(launch_attention(m->dt, a, c.st));

@@ -49,11 +49,10 @@ template <int NWI_, int NWJ_, int FI_, int FJ_, int MINW_, int KTB_ = 128, int N
     static constexpr int PASS_ROWS = NW * RPI;               // rows staged by one global_load_lds per wave
     static constexpr int APASS = BM / PASS_ROWS, WPASS = BN / PASS_ROWS;
     static constexpr int STAGE_BYTES = (BM + BN) * KTB;
-    // PP == 3: asymmetric ring -- THREE slots for the activation rows (streamed from HBM: two K steps of lookahead) and TWO for the
-    // weight rows (L2 / MALL resident: one step), 3 x 32 + 2 x 32 KiB = all 160 KiB of a CU for the 256 x 256 tile
-    // PP == 6: TWO slots for the activation rows and ONE for the weight rows (read into registers at the top of every K step): 80 KiB
+    // PP: the K loop. 0 = the plain NSTAGE-deep ring; 4 = fp16 + fp8 rows with the DMA pieces interleaved with the MFMA rows;
+    // 6 = TWO slots for the activation rows and ONE for the weight rows (read into registers at the top of every K step): 80 KiB
     // for the 256 x 128 tile, so that two blocks share a CU
-    static constexpr int LDS = PP_ == 3 ? (3 * NWJ_ * FJ_ * 16 + 2 * NWI_ * FI_ * 16) * KTB_ : PP_ == 6 ? (2 * NWJ_ * FJ_ * 16 + NWI_ * FI_ * 16) * KTB_ : NSTAGE * STAGE_BYTES;
+    static constexpr int LDS = PP_ == 6 ? (2 * NWJ_ * FJ_ * 16 + NWI_ * FI_ * 16) * KTB_ : NSTAGE * STAGE_BYTES;
     static constexpr int LPS = APASS + WPASS;                // DMA instructions per lane per K step
     // bank swizzle of the lane-linear LDS image: slot = chunk ^ key(row). Checked against the ds_read_b128 service groups
     // of gfx950 ({0-3,12-15,20-27}, {4-11,16-19,28-31}, +32): a fragment read (lane -> row lane & 15, chunk group lane >> 4)
@@ -65,21 +64,10 @@ typedef GemmCfg<2, 4, 4, 4, 2> Cfg256x128;  // M 256 x N 128, 512 threads, 96 Ki
 typedef GemmCfg<2, 2, 4, 4, 2> Cfg128;      // 128 x 128, 256 threads, 64 KiB LDS, 2 blocks / CU
 typedef GemmCfg<1, 8, 8, 4, 2> Cfg512x128;  // M 512 x N 128, 512 threads, 160 KiB LDS (all of it): N <= 128 convolutions with the
                                             // 128 x 64 per-wave tile of Cfg256 (12 ds_read_b128 per 32 MFMAs instead of 8 per 16)
-typedef GemmCfg<2, 4, 8, 4, 2, 64, 4> Cfg256s4;   // 256 x 256, 8 waves, 64-byte K rows, FOUR LDS stages (128 KiB): three K steps of DMA in flight
-typedef GemmCfg<2, 4, 8, 4, 2, 64, 4, 1> Cfg256pp;   // 256 x 256, 64-byte K rows, 4-stage ring, PING-PONG schedule: waves 0-3 and 4-7 (one of each per
-                                                     // SIMD) run half a phase apart, so one group's 16-MFMA burst covers the other's ds_reads + DMA issue
-// split-fp16 (x3) software-pipelined K loop (PP = 2): same tiles, barrier moved into the tail of the MFMA stream (see the K loop)
-typedef GemmCfg<2, 4, 8, 4, 2, 128, 2, 2> Cfg256sw;
-typedef GemmCfg<2, 4, 4, 4, 2, 128, 2, 2> Cfg256x128sw;
-typedef GemmCfg<2, 2, 4, 4, 2, 128, 2, 2> Cfg128sw;
-typedef GemmCfg<1, 8, 8, 4, 2, 128, 2, 2> Cfg512x128sw;
 // fp16 + fp8 rows, DMA pieces interleaved with the MFMA rows (PP = 4; see the K loop)
 typedef GemmCfg<2, 4, 8, 4, 2, 128, 2, 4> Cfg256il;
 typedef GemmCfg<2, 4, 4, 4, 2, 128, 2, 4> Cfg256x128il;
-typedef GemmCfg<2, 2, 4, 4, 2, 128, 2, 4> Cfg128il;
 typedef GemmCfg<1, 8, 8, 4, 2, 128, 2, 4> Cfg512x128il;
-typedef GemmCfg<1, 4, 8, 4, 2, 64, 3, 5> Cfg256x128f8;   // fp16 + fp8 rows: M 256 x N 128 by four waves of 128 (n) x 64 (m), 64-byte K steps, 3 x 24 KiB: TWO blocks per CU
-typedef GemmCfg<2, 4, 8, 4, 2, 128, 2, 3> Cfg256a3;     // 256 x 256, asymmetric ring (A x 3, W x 2), 160 KiB LDS
 // split-fp16, TWO blocks per CU (round 3): M 256 x N 128 by four waves of 128 (n) x 64 (m) -- the per-wave tile of Cfg256, so the LDS read
 // traffic per MFMA is unchanged --, 128-byte K steps, activation rows double buffered, weight rows single buffered and held in REGISTERS
 // for the step (80 KiB). One block's epilogue and barrier bubbles run under the other block's MFMAs (see the K loop).
@@ -89,13 +77,10 @@ typedef GemmCfg<1, 4, 8, 4, 2, 128, 2, 6> Cfg256x128r;
 // With hipcc as the register allocator the 128 x 64 wave tile at two waves per SIMD is the largest that stays in registers.)
 // split-fp16, SMALL problems (round 3): 64 x 64 by four waves of 32 x 32 -- four times the waves of the 128 x 128 tile for the same
 // problem, so that the one-pair forward (M = 1536 token rows: 96 tiles of 128 x 128 on 256 CUs) fills the chip. Twice the LDS read
-// traffic per MFMA (8 ds_read_b128 per 12 MFMAs); 32 KiB of LDS, up to four blocks per CU. Same K order per output element as every
-// other shape: bit-identical results.
-typedef GemmCfg<2, 2, 2, 2, 4> Cfg64;
-// the same tile on a three- / four-slot ring (48 / 64 KiB): two / three K steps of DMA in flight -- a small problem has too few waves per CU
-// to hide the load latency of a one-step lookahead (measured: 1 us per K step of 0.1 us of MFMA work, profiles/r03_f). Default: three slots.
+// traffic per MFMA (8 ds_read_b128 per 12 MFMAs). Same K order per output element as every other shape: bit-identical results.
+// A three-slot ring (48 KiB): two K steps of DMA in flight -- a small problem has too few waves per CU to hide the load latency of a
+// one-step lookahead (measured: 1 us per K step of 0.1 us of MFMA work, profiles/r03_f).
 typedef GemmCfg<2, 2, 2, 2, 4, 128, 3> Cfg64s3;
-typedef GemmCfg<2, 2, 2, 2, 2, 128, 4> Cfg64s4;
 // M 96 x N 64 by four waves of 32 (n) x 48 (m) on the three-slot ring (60 KiB; round 6): the small tile is bound by what it pulls out of L2 per flop and by the blocks a
 // CU has to run one after the other -- 1536 x 1024 is 384 tiles of 64 x 64 (a CU in two runs two: 256 operand rows per K step) or exactly 256 of
 // 96 x 64 (one per CU: 160 rows). Tile configuration 11; same K order per output element: bit-identical.
@@ -105,10 +90,8 @@ typedef GemmCfg<2, 2, 2, 3, 4, 128, 3> Cfg96x64;
 typedef GemmCfg<2, 4, 4, 2, 4> Cfg128w8;
 // M 384 x N 192 by eight waves stacked along m, each 192 (n) x 48 (m) = 12 x 3 fragments (144 accumulators; 147 KiB of LDS): the decoder's 24576-row GEMMs with
 // N = 768 / 1536 / 2304 / 3072 are exactly 1 / 2 / 3 / 4 rounds of 256 CUs on it (128 x 128: 1152 tiles = 2.25 rounds of 512 slots). Round 4; tile configuration 9,
-// chosen by gemm_pick_config (D3R_GEMM_T384=0: never). Same K order per output element as every other shape: bit-identical results.
+// chosen by gemm_pick_config. Same K order per output element as every other shape: bit-identical results.
 typedef GemmCfg<1, 8, 12, 3, 2> Cfg384x192;
-typedef GemmCfg<1, 4, 8, 4, 2, 64, 3> Cfg256x128w4;  // M 256 x N 128, 4 waves of 128 (n) x 64 (m), 64-byte K rows: 48 KiB LDS, TWO
-                                                  // blocks per CU, three stages (72 KiB)
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -128,20 +111,15 @@ D3R_DEV void load_rope_rows(const float* table, int ntok, int tok_w, int M, int 
     d[0] = cy[0]; d[1] = cy[1]; d[2] = cx[0]; d[3] = cx[1];
 }
 
-// K step kt of an implicit-GEMM operand -> filter tap and first input channel. Tap-major (k = tap * Cin + c) re-reads a tile's
-// whole input neighbourhood once per tap: with 32 tiles in flight per XCD that is 8-10 MiB between two uses of a line, past the
-// 4 MiB L2 (measured: 6.6x the algorithmic fetch on the 3x3 128->128 head convolution). Slice-major walks the taps of ONE K step's
-// channel slice before moving on: the lines of a slice (128 bytes per pixel) are touched by all k x k taps back to back.
+// K step kt of an implicit-GEMM operand -> filter tap and first input channel. The K order is slice-major: the taps of ONE K step's
+// channel slice come before the next slice, so the lines of a slice (128 bytes per pixel) are touched by all k x k taps back to back.
+// (Tap-major, k = tap * Cin + c, re-read a tile's whole input neighbourhood once per tap: with 32 tiles in flight per XCD that is 8-10 MiB
+// between two uses of a line, past the 4 MiB L2 -- measured 6.6x the algorithmic fetch on the 3x3 128->128 head convolution.)
 D3R_DEV void conv_k_step(const GemmParams& p, int kel, int S, int& tap, int& c0) {   // kel: first K element of the step; S: elements per 128-byte slice
-    if (p.kslice_major) {
-        const int per = p.ksize * p.ksize * S;
-        const int sl = kel / per, rem = kel - sl * per;
-        tap = rem / S;
-        c0 = sl * S + (rem - tap * S);
-    } else {
-        tap = kel / p.Cin;
-        c0 = kel - tap * p.Cin;
-    }
+    const int per = p.ksize * p.ksize * S;
+    const int sl = kel / per, rem = kel - sl * per;
+    tap = rem / S;
+    c0 = sl * S + (rem - tap * S);
 }
 
 // the same for ONE 32-column half of a head (xhalf 0: the y position's rows, 1: x): what a 32-wide epilogue group needs
@@ -178,28 +156,16 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
         tr[6] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
         tr[7] = blockIdx.x;
     }
-    // ---- start stagger of the first round of resident blocks -----------------------------------------------------------
-    // All tiles of a launch take the same time, so the resident blocks run in lockstep: every CU is in its K loop (HBM idle), then
-    // every CU is in its epilogue (MFMA idle, 256 x 128-512 KiB hitting HBM at once: measured 22-28 us per round at 3-4.7 TB/s
-    // where one CU alone needs a few us). Delaying the FIRST-round blocks by up to one such burst spreads the epilogues of all later
-    // rounds over time (a block's successor on the same CU inherits its phase); the price is half a burst once per launch.
-    if (p.stagger_ticks > 0 && (int)blockIdx.x < p.first_round) {
-        const unsigned slot = p.stagger_mode ? ((blockIdx.x & 7u) * 4u) : ((blockIdx.x >> 3) & 31u);   // mode 1: by XCD; mode 0: across each XCD's blocks
-        const long long delay = ((long long)p.stagger_ticks * slot) >> 5;
-        const long long t0 = wall_clock64();
-        while (wall_clock64() - t0 < delay) __builtin_amdgcn_s_sleep(32);
-    }
     // ---- block -> tile: XCD-contiguous ids, then 8-wide column panels walked row by row ------------------
     const int tiles_n = (p.n_store + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
     int lid = xcd_remap(blockIdx.x, gridDim.x);
     int sk_slice = 0;
     if (p.splitk > 1) { sk_slice = lid % p.splitk; lid /= p.splitk; }      // a tile's K slices: consecutive ids = one XCD (the combine reads same-XCD slabs)
     const int sk_tile = lid;
-    const int PANEL = p.panel;
-    const int per_panel = PANEL * tiles_m;
+    const int per_panel = GEMM_PANEL * tiles_m;
     const int panel = lid / per_panel, rem_p = lid - panel * per_panel;
-    const int width = min(PANEL, tiles_n - panel * PANEL);
-    const int tm = rem_p / width, tn = panel * PANEL + (rem_p - tm * width);
+    const int width = min(GEMM_PANEL, tiles_n - panel * GEMM_PANEL);
+    const int tm = rem_p / width, tn = panel * GEMM_PANEL + (rem_p - tm * width);
     const int m0 = tm * BM, n0 = tn * BN;
     // V^T regions of the attention projections: with the wide epilogue (16-bit types, token count a multiple of 64) the
     // transposition happens in the LDS staging tile and any tile shape works; otherwise the MFMA operand roles are
@@ -265,9 +231,8 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
 
     const uint32_t wave_u = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
     const uint32_t lds0 = lds_addr(smem) + wave_u * 1024;   // wave-uniform: one 1 KiB DMA piece per wave and pass
-    constexpr bool A3 = CF::PP == 3;
     auto stage_a = [&](int kt, int buf) __attribute__((always_inline)) {   // activation rows of K step kt -> stage buf
-        const uint32_t sb = lds0 + (A3 ? buf * (BM * KTB) : buf * STAGE_BYTES);
+        const uint32_t sb = lds0 + buf * STAGE_BYTES;
         const size_t koff = (size_t)kt * KTB;
         if (p.amode == AMODE_LINEAR) {
 #pragma unroll
@@ -289,7 +254,7 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
         }
     };
     auto stage_w = [&](int kt, int buf) __attribute__((always_inline)) {   // weight rows of K step kt -> stage buf
-        const uint32_t sb = lds0 + (A3 ? 3 * (BM * KTB) + buf * (BN * KTB) : buf * STAGE_BYTES + BM * KTB);
+        const uint32_t sb = lds0 + buf * STAGE_BYTES + BM * KTB;
         const size_t koff = (size_t)kt * KTB;
 #pragma unroll
         for (int q = 0; q < CF::WPASS; ++q) glds16(wsrc[q] + koff, sb + q * (CF::NW * 1024));
@@ -309,7 +274,7 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
 
     if (p.trace && tid == 0) p.trace[(size_t)blockIdx.x * 8 + 1] = (unsigned long long)wall_clock64();
     __builtin_amdgcn_s_setprio(2);   // K loop: ahead of a co-resident block's epilogue in the SIMD's issue arbitration
-    static_assert(CF::NSTAGE >= 2 && CF::NSTAGE <= 4, "vmcnt ladder below covers up to 2 younger steps in flight");
+    static_assert(CF::NSTAGE >= 2 && CF::NSTAGE <= 3, "vmcnt ladder below covers up to 1 younger step in flight");
     f32x4_t acc[FI][FJ];
 #pragma unroll
     for (int a = 0; a < FI; ++a)
@@ -330,403 +295,7 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
 #pragma unroll
         for (int q = 0; q < CF::APASS; ++q) arow[q] += skip;
     }
-    if constexpr (CF::PP == 3) {
-        // ---- asymmetric ring: activations two K steps ahead, weights one ------------------------------------------------------
-        // Measured with the per-block trace (tools/gpu_probe.py gemmtrace): next to other blocks' epilogue traffic a K step of the
-        // two-stage loop takes 2.2-2.7 us against 1.8-1.9 us alone -- the activation rows come from HBM and one step of lookahead
-        // does not cover their latency under load. Issue order per step: W(kt+1), then A(kt+2); loads complete in order, so the
-        // wait at the top of step kt+1 leaves the APASS pieces of A(kt+2) in flight.
-        static_assert(KTB == 128 && CF::NSTAGE == 2, "asymmetric ring: 128-byte K rows");
-        constexpr int ASLOT = BM * KTB, WSLOT = BN * KTB, WBASE = 3 * ASLOT;
-        stage_a(0, 0);
-        stage_w(0, 0);
-        if (nk > 1) stage_a(1, 1);
-        int ab = 0, wb = 0;
-        for (int kt = 0; kt < nk; ++kt) {
-            if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CF::APASS) : "memory");
-            else d3r_wait_vm0();
-            __syncthreads();
-            if (kt + 1 < nk) stage_w(kt + 1, wb ^ 1);
-            if (kt + 2 < nk) stage_a(kt + 2, ab >= 1 ? ab - 1 : 2);     // (ab + 2) % 3
-            const char* abase = smem + ab * ASLOT;
-            const char* wbase = smem + WBASE + wb * WSLOT;
-            const char* pb = swap ? abase : wbase;
-            const char* qb = swap ? wbase : abase;
-            if constexpr (DT == D3R_F16X3) {
-                const int chi = (fgrp ^ fsw) * 16, clo = ((4 + fgrp) ^ fsw) * 16;
-                uint4 qf[FJ], ql[FJ];
-#pragma unroll
-                for (int f = 0; f < FJ; ++f) {
-                    const char* qr = qb + (q_row0 + f * 16) * KTB;
-                    qf[f] = *reinterpret_cast<const uint4*>(qr + chi);
-                    ql[f] = *reinterpret_cast<const uint4*>(qr + clo);
-                }
-#pragma unroll
-                for (int fi = 0; fi < FI; ++fi) {
-                    const char* pr = pb + (p_row0 + fi * 16) * KTB;
-                    const uint4 pf = *reinterpret_cast<const uint4*>(pr + chi), pl = *reinterpret_cast<const uint4*>(pr + clo);
-#pragma unroll
-                    for (int fj = 0; fj < FJ; ++fj) TR::mma16x3(acc[fi][fj], pf, pl, qf[fj], ql[fj]);
-                }
-            } else if constexpr (DT != D3R_F16F8 && DT != D3R_F16X2F8) {
-#pragma unroll
-                for (int ks = 0; ks < KTB / 64; ++ks) {
-                    const int coff = ((ks * 4 + fgrp) ^ fsw) * 16;
-                    uint4 pf[FI], qf[FJ];
-#pragma unroll
-                    for (int f = 0; f < FJ; ++f) qf[f] = *reinterpret_cast<const uint4*>(qb + (q_row0 + f * 16) * KTB + coff);
-#pragma unroll
-                    for (int f = 0; f < FI; ++f) pf[f] = *reinterpret_cast<const uint4*>(pb + (p_row0 + f * 16) * KTB + coff);
-#pragma unroll
-                    for (int fi = 0; fi < FI; ++fi)
-#pragma unroll
-                        for (int fj = 0; fj < FJ; ++fj) TR::mma16(acc[fi][fj], pf[fi], qf[fj]);
-                }
-            }
-            ab = ab == 2 ? 0 : ab + 1;
-            wb ^= 1;
-        }
-    } else if constexpr (DT == D3R_F16X3 && CF::PP == 4) {
-        // ---- split-fp16, nn.Linear operands, DMA pieces interleaved with the MFMA rows (round 4) ---------------------------------------------
-        // The plain loop opens every K step with [vmcnt(0) | s_barrier | LPS DMA issues | first fragment reads]: a burst during which neither wave of
-        // a SIMD has an MFMA to issue. Here the pieces of step kt + 1 go out one fragment row at a time behind the MFMAs of step kt (fragment reads
-        // one row ahead, rows pinned with sched_barrier), as in the fp16 + fp8 and 2.5-unit loops. DMA addressing: a wave-uniform 64-bit tile base
-        // (SGPRs) + ONE 32-bit offset per operand (the plain loop keeps one 64-bit address per staged row: 16 VGPRs). Same MFMA order per accumulator
-        // as the plain loop: bit-identical results.
-        static_assert(KTB == 128 && NS == 2, "split-fp16 rows: 128-byte K steps, two stages");
-        const bool edge = __builtin_amdgcn_readfirstlane(m0 + BM > p.M ? 1 : 0) != 0;
-        const char* const tile_a = reinterpret_cast<const char*>(p.act) + (size_t)__builtin_amdgcn_readfirstlane(m0) * p.lda * EB;
-        const char* const tile_w = reinterpret_cast<const char*>(p.wgt) + (size_t)__builtin_amdgcn_readfirstlane(n0) * p.K * EB;
-        const uint32_t a0 = (uint32_t)(((size_t)(min(m0 + lrow, p.M - 1) - m0) * p.lda) * EB + lchunk * 16);
-        const uint32_t w0 = (uint32_t)(((size_t)lrow * p.K) * EB + lchunk * 16);
-        const size_t stride_a = (size_t)CF::PASS_ROWS * p.lda * EB, stride_w = (size_t)CF::PASS_ROWS * p.K * EB;
-        auto piece3 = [&](int idx, int kt, int buf) __attribute__((always_inline)) {
-            const uint32_t sb = lds0 + buf * STAGE_BYTES;
-            if (idx < CF::APASS) {
-                const int q = idx;
-                const char* ab = tile_a + (size_t)kt * KTB;
-                if (!edge) {
-                    glds16_so(ab + q * stride_a, a0, sb + q * (CF::NW * 1024));
-                } else {
-                    const int m = min(m0 + q * CF::PASS_ROWS + lrow, p.M - 1);
-                    glds16_so(ab, (uint32_t)(((size_t)(m - m0) * p.lda) * EB + lchunk * 16), sb + q * (CF::NW * 1024));
-                }
-            } else {
-                const int q = idx - CF::APASS;
-                glds16_so(tile_w + (size_t)kt * KTB + q * stride_w, w0, sb + BM * KTB + q * (CF::NW * 1024));
-            }
-        };
-        constexpr int PPR = (LPS + FI - 1) / FI;
-#pragma unroll
-        for (int i = 0; i < LPS; ++i) piece3(i, 0, 0);
-        const int chi = (fgrp ^ fsw) * 16, clo = ((4 + fgrp) ^ fsw) * 16;   // LDS image: [hi0..hi3 | lo0..lo3]
-        int buf = 0;
-        for (int kt = 0; kt < nk; ++kt) {
-            d3r_wait_vm0();
-            __syncthreads();
-            const bool more = kt + 1 < nk;
-            const char* sb = smem + buf * STAGE_BYTES;
-            uint4 qf[FJ], ql[FJ];
-#pragma unroll
-            for (int f = 0; f < FJ; ++f) {
-                const char* qr = sb + q_off + (q_row0 + f * 16) * KTB;
-                qf[f] = *reinterpret_cast<const uint4*>(qr + chi);
-                ql[f] = *reinterpret_cast<const uint4*>(qr + clo);
-            }
-            const char* pr0 = sb + p_off + p_row0 * KTB;
-            uint4 cf = *reinterpret_cast<const uint4*>(pr0 + chi), cl = *reinterpret_cast<const uint4*>(pr0 + clo);
-#pragma unroll
-            for (int fi = 0; fi < FI; ++fi) {
-                uint4 nf = cf, nl = cl;
-                if (fi + 1 < FI) {
-                    const char* pr = sb + p_off + (p_row0 + (fi + 1) * 16) * KTB;
-                    nf = *reinterpret_cast<const uint4*>(pr + chi);
-                    nl = *reinterpret_cast<const uint4*>(pr + clo);
-                }
-#pragma unroll
-                for (int fj = 0; fj < FJ; ++fj) TR::mma16x3(acc[fi][fj], cf, cl, qf[fj], ql[fj]);
-                if (more) {
-#pragma unroll
-                    for (int i = fi * PPR; i < (fi + 1) * PPR && i < LPS; ++i) piece3(i, kt + 1, buf ^ 1);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                cf = nf; cl = nl;
-            }
-            buf ^= 1;
-        }
-    } else if constexpr (CF::PP == 2) {
-        // ---- split-fp16, software pipelined (2 stages, ONE barrier per K step, no bubble at the step boundary) ---------------
-        // The plain loop below opens every K step with [vmcnt(0) | s_barrier | 8 DMA issues | first ds_reads] during which none of
-        // the CU's 8 waves has an MFMA to issue: ~25 % of the step at 96 MFMAs per wave. Here the barrier of step kt sits in
-        // front of the LAST fragment row (TAIL = 1) of step kt (every ds_read of stage kt & 1 has been issued and waited for by
-        // then, so the stage is dead), and behind it, interleaved with those TAIL x FJ x 3 MFMAs: the DMA of step kt + 2 into
-        // the stage just freed, and the ds_reads of step kt + 1's q fragments and first p fragment (published by the same
-        // barrier: every wave waited for ITS DMA pieces of step kt + 1, issued a whole step earlier, before arriving). The next
-        // step's MFMAs then start from registers. Hazards: RAW on stage (kt+1)&1 = vmcnt(0) + barrier; WAR on stage kt&1 =
-        // lgkmcnt(0) + the same barrier.
-        static_assert(DT == D3R_F16X3 && KTB == 128 && NS == 2, "software-pipelined loop: split-fp16 rows, two stages");
-        constexpr int TAIL = 1, NSLOT = TAIL * FJ;
-        const int chi = (fgrp ^ fsw) * 16, clo = ((4 + fgrp) ^ fsw) * 16;   // LDS image: [hi0..hi3 | lo0..lo3]
-        int cky = 0, ckx = 0, cc0 = 0;           // implicit-GEMM operand: filter tap / first channel of the K step being staged
-        auto conv_step = [&](int kt) __attribute__((always_inline)) {
-            if (p.amode != AMODE_LINEAR) {
-                int tap;
-                conv_k_step(p, kt * KT, 128 / EB, tap, cc0);
-                cky = tap / p.ksize;
-                ckx = tap - cky * p.ksize;
-            }
-        };
-        auto dma_piece = [&](int idx, int kt, int buf) __attribute__((always_inline)) {   // idx: compile-time constant after unrolling
-            const uint32_t sb = lds0 + buf * STAGE_BYTES;
-            const size_t koff = (size_t)kt * KTB;
-            if (idx < CF::APASS) {
-                const int q = idx;
-                if (p.amode == AMODE_LINEAR) {
-                    glds16(reinterpret_cast<const char*>((size_t)arow[q]) + koff, sb + q * (CF::NW * 1024));
-                } else {
-                    const int pk = (int)(arow[q] >> 32), ibase = (int)(unsigned)arow[q];
-                    const int iy = (pk >> 16) + cky, ix = (int)(short)(pk & 0xFFFF) + ckx;
-                    const bool ok = (iy >= 0) && (iy < p.Hin) && (ix >= 0) && (ix < p.Win);
-                    const char* src = reinterpret_cast<const char*>(p.act) + ((size_t)(ibase + iy * p.Win + ix) * p.cstride + cc0) * EB + lchunk * 16;
-                    glds16(ok ? src : zsrc, sb + q * (CF::NW * 1024));
-                }
-            } else {
-                const int q = idx - CF::APASS;
-                glds16(wsrc[q] + koff, sb + BM * KTB + q * (CF::NW * 1024));
-            }
-        };
-        auto frag = [&](const char* sbase, int off, int row, int coff) __attribute__((always_inline)) {
-            return *reinterpret_cast<const uint4*>(sbase + off + row * KTB + coff);
-        };
-        // DMA pieces of one K step (LPS per wave) are spread over the MFMA stream instead of being issued in one burst (8 waves x
-        // 8 pieces of 1 KiB keep the CU's vector-memory issue path busy for ~1000 cycles during which no wave issues MFMAs):
-        // pieces [0, PT) of step kt + 2 go out in the tail of step kt (behind the barrier that frees their stage), pieces
-        // [PT, LPS) in the first MROWS - GUARD main rows of step kt + 1; the last GUARD rows carry none, so that the youngest
-        // piece has ~GUARD x 12 MFMAs of time to land before the barrier that publishes it.
-        constexpr int MROWS = FI - TAIL, GUARD = MROWS >= 5 ? 2 : 1, DROWS = MROWS - GUARD;
-        constexpr int PT = (LPS + DROWS) / (DROWS + 1);         // tail share: about one row's worth
-        stage(0, 0);
-        conv_step(1);
-        if (nk > 1) {
-#pragma unroll
-            for (int pc = 0; pc < PT; ++pc) dma_piece(pc, 1, 1);
-        }
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PT) : "memory");   // step 0 has landed (the PT younger pieces may still fly)
-        if (nk <= 1) d3r_wait_vm0();
-        __syncthreads();
-        // Fragments that cross the step boundary: the first q fragment and the first p fragment of the next step, read behind the
-        // barrier under the tail MFMAs. Two register sets with swapped roles in a loop unrolled by two: no moves on the back edge.
-        struct Head { uint4 qh, ql, ph, pl; };
-        Head ha, hb;
-        ha.qh = frag(smem, q_off, q_row0, chi); ha.ql = frag(smem, q_off, q_row0, clo);
-        ha.ph = frag(smem, p_off, p_row0, chi); ha.pl = frag(smem, p_off, p_row0, clo);
-        auto kstep = [&](int kt, const Head& cur, Head& nxt) __attribute__((always_inline)) {
-            const char* sb = smem + (kt & 1) * STAGE_BYTES;
-            const char* sn = smem + ((kt + 1) & 1) * STAGE_BYTES;
-            const bool more1 = kt + 1 < nk, more2 = kt + 2 < nk;
-            uint4 qh[FJ], ql[FJ];
-            qh[0] = cur.qh; ql[0] = cur.ql;
-#pragma unroll
-            for (int f = 1; f < FJ; ++f) { qh[f] = frag(sb, q_off, q_row0 + f * 16, chi); ql[f] = frag(sb, q_off, q_row0 + f * 16, clo); }
-            uint4 ch = cur.ph, cl = cur.pl;
-#pragma unroll
-            for (int fi = 0; fi < MROWS; ++fi) {
-                const uint4 nh = frag(sb, p_off, p_row0 + (fi + 1) * 16, chi), nl = frag(sb, p_off, p_row0 + (fi + 1) * 16, clo);
-                if (more1 && fi < DROWS) {     // the rest of step kt + 1's DMA (conv_step(kt + 1) was evaluated in the previous tail / the prologue)
-#pragma unroll
-                    for (int pc = PT; pc < LPS; ++pc)
-                        if ((pc - PT) * DROWS / (LPS - PT) == fi) dma_piece(pc, kt + 1, (kt + 1) & 1);
-                }
-#pragma unroll
-                for (int fj = 0; fj < FJ; ++fj) TR::mma16x3(acc[fi][fj], ch, cl, qh[fj], ql[fj]);
-                ch = nh; cl = nl;
-            }
-            if (more2) conv_step(kt + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            // the next step's first fragments (stale but in-bounds bytes after the last step: never used)
-            nxt.qh = frag(sn, q_off, q_row0, chi); nxt.ql = frag(sn, q_off, q_row0, clo);
-            nxt.ph = frag(sn, p_off, p_row0, chi); nxt.pl = frag(sn, p_off, p_row0, clo);
-            __builtin_amdgcn_sched_barrier(0);
-            // tail row, term-major over its FJ accumulators (dependent MFMAs FJ apart), with the first PT pieces of step kt + 2
-            constexpr int NMF = 3 * NSLOT;
-#pragma unroll
-            for (int term = 0; term < 3; ++term) {
-#pragma unroll
-                for (int fj = 0; fj < FJ; ++fj) {
-                    const int mf = term * FJ + fj;
-                    if (more2) {
-#pragma unroll
-                        for (int pc = 0; pc < PT; ++pc)
-                            if (pc * NMF / PT == mf) dma_piece(pc, kt + 2, kt & 1);
-                    }
-                    TR::mma16_term(term, acc[MROWS][fj], ch, cl, qh[fj], ql[fj]);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        int kt = 0;
-        for (; kt + 1 < nk; kt += 2) {
-            kstep(kt, ha, hb);
-            kstep(kt + 1, hb, ha);
-        }
-        if (kt < nk) kstep(kt, ha, hb);
-        d3r_wait_vm0();   // nothing of this block's DMA is in flight when the epilogue reuses the stages
-    } else if constexpr (CF::PP == 1) {
-        // ---- ping-pong schedule (non-swapped 16-bit / fp32 operands; KTB = 64: one MFMA k-step per K step) -----------------
-        // A K step is two phases, each [L: issue half of the DMA of step kt+2, ds_read this phase's fragments] | s_barrier |
-        // [C: 16 MFMAs] | s_barrier. Waves 4-7 run one barrier behind waves 0-3, so on every SIMD one wave is in C while its
-        // partner is in L. Data flow (ring of 4 stages, loads two steps ahead): every wave waits for ITS loads of step kt+1
-        // (counted vmcnt: the 4 loads of step kt+2 stay in flight) in the segment that ends at the barrier in front of the
-        // first read of step kt+1 -- C_b for the leading group, L_b for the trailing one; the stage written by step kt+2's
-        // DMA was last read in step kt-2, four phases back.
-        static_assert(CF::KTB == 64 && CF::NSTAGE == 4 && CF::NW == 8 && FI == 8 && FJ == 4, "ping-pong schedule is written for the 256x256 / 64-byte-row tile");
-        const bool trailing = wave_u >= 4;
-        stage(0, 0);
-        if (nk > 1) stage(1, 1);
-        if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-        else d3r_wait_vm0();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (trailing) __builtin_amdgcn_s_barrier();
-        for (int kt = 0; kt < nk; ++kt) {
-            const char* sb = smem + (kt & 3) * STAGE_BYTES;
-            const int coff = (fgrp ^ fsw) * 16;
-            const bool more = kt + 2 < nk;
-            auto wait_next = [&]() __attribute__((always_inline)) {   // this wave's loads of step kt+1 have landed
-                if (kt + 1 < nk) {
-                    if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-                    else d3r_wait_vm0();
-                }
-            };
-            uint4 qf[FJ], pf[4];
-            // ---- phase a: P fragments 0-3 x all Q fragments
-            if (more) stage_a(kt + 2, (kt + 2) & 3);
-#pragma unroll
-            for (int f = 0; f < FJ; ++f) qf[f] = *reinterpret_cast<const uint4*>(sb + q_off + (q_row0 + f * 16) * KTB + coff);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) pf[f] = *reinterpret_cast<const uint4*>(sb + p_off + (p_row0 + f * 16) * KTB + coff);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int fi = 0; fi < 4; ++fi)
-#pragma unroll
-                for (int fj = 0; fj < FJ; ++fj) TR::mma16(acc[fi][fj], pf[fi], qf[fj]);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            // ---- phase b: P fragments 4-7 x all Q fragments
-            if (more) stage_w(kt + 2, (kt + 2) & 3);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) pf[f] = *reinterpret_cast<const uint4*>(sb + p_off + (p_row0 + (4 + f) * 16) * KTB + coff);
-            if (trailing) wait_next();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int fi = 0; fi < 4; ++fi)
-#pragma unroll
-                for (int fj = 0; fj < FJ; ++fj) TR::mma16(acc[4 + fi][fj], pf[fi], qf[fj]);
-            __builtin_amdgcn_s_setprio(0);
-            if (!trailing) wait_next();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (!trailing) __builtin_amdgcn_s_barrier();
-    } else if constexpr (DT == D3R_F16F8 && KTB == 64) {
-        // ---- fp16 + fp8 rows, 64-byte K steps, three LDS slots of 24 KiB: a 256 (m) x 128 (n) tile by FOUR waves of 128 (n) x 64 (m) --------
-        // Why: one 8-wave 256 x 256 block per CU spends a quarter of a K = 1024 tile's life in its epilogue with the MFMA pipes idle (the
-        // same forward with the epilogues removed runs 282 instead of 213 pairs/s). This shape keeps the per-wave tile (the LDS read
-        // traffic per MFMA) and halves the block, so that TWO blocks are resident per CU (2 x 72 KiB of LDS, 256 VGPRs per wave at two
-        // waves per SIMD) and one block's K loop runs under the other's epilogue.
-        // A 256-byte super-group [hi fp16 x64 | a8 x64 | b8 x64] is four steps h0, h1, fa, fb; step s lives in slot s % 3 = (j + i) % 3
-        // for step i of super-group j. Per super-group three phases, each [wait | barrier | issue loads | math]:
-        //   B0: math on h0 (one 16x16x32 k-step, lane group g on chunk g);   loads issued: h1(j), fa(j)
-        //   B1: math on h1;                                                  loads issued: fb(j)      -> the slot h0(j) just left
-        //   B2: math on (fa, fb): ONE fp8 MFMA per fragment pair, a8 from fa's slot and b8 from fb's;   loads issued: h0(j + 1)
-        // A load goes out behind the barrier that follows the last read of its slot's previous tenant (three steps earlier); loads
-        // complete in order, so B1 waits with vmcnt(LPS) (fa's pieces may still fly) and B0 / B2 with vmcnt(0).
-        static_assert(NS == 3 && CF::NWI == 1, "fp16 + fp8 rows on 64-byte K steps: three slots, waves stacked along m");
-        const bool edge = __builtin_amdgcn_readfirstlane(m0 + BM > p.M ? 1 : 0) != 0;
-        // offsets are relative to the TILE's first row (its 64-bit address is wave-uniform: SGPRs), so they fit 32 bits whatever the operand size
-        const char* const tile_a = reinterpret_cast<const char*>(p.act) + (size_t)__builtin_amdgcn_readfirstlane(m0) * p.lda * EB;
-        const char* const tile_w = reinterpret_cast<const char*>(p.wgt) + (size_t)__builtin_amdgcn_readfirstlane(n0) * p.K * EB;
-        const uint32_t a0 = (uint32_t)(((size_t)(min(m0 + lrow, p.M - 1) - m0) * p.lda) * EB + lchunk * 16);
-        const uint32_t w0 = (uint32_t)(((size_t)lrow * p.K) * EB + lchunk * 16);
-        const size_t stride_a = (size_t)CF::PASS_ROWS * p.lda * EB, stride_w = (size_t)CF::PASS_ROWS * p.K * EB;
-        auto load_step = [&](int step, int slot) __attribute__((always_inline)) {   // 64-byte K step `step` of every row -> LDS slot
-            const uint32_t sb = lds0 + slot * STAGE_BYTES;
-            const char* ab = tile_a + (size_t)step * KTB;
-            const char* wb = tile_w + (size_t)step * KTB;
-#pragma unroll
-            for (int q = 0; q < CF::APASS; ++q) {
-                if (!edge) {
-                    glds16_so(ab + q * stride_a, a0, sb + q * (CF::NW * 1024));
-                } else {
-                    const int m = min(m0 + q * CF::PASS_ROWS + lrow, p.M - 1);
-                    glds16_so(ab, (uint32_t)(((size_t)(m - m0) * p.lda) * EB + lchunk * 16), sb + q * (CF::NW * 1024));
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < CF::WPASS; ++q) glds16_so(wb + q * stride_w, w0, sb + BM * KTB + q * (CF::NW * 1024));
-        };
-        const int coff = (fgrp ^ fsw) * 16;
-        auto math_hi = [&](int slot) __attribute__((always_inline)) {
-            const char* sb = smem + slot * STAGE_BYTES;
-            uint4 qf[FJ];
-#pragma unroll
-            for (int f = 0; f < FJ; ++f) qf[f] = *reinterpret_cast<const uint4*>(sb + q_off + (q_row0 + f * 16) * KTB + coff);
-#pragma unroll
-            for (int fi = 0; fi < FI; ++fi) {
-                const uint4 pf = *reinterpret_cast<const uint4*>(sb + p_off + (p_row0 + fi * 16) * KTB + coff);
-#pragma unroll
-                for (int fj = 0; fj < FJ; ++fj) TR::mma16_hi(acc[fi][fj], pf, qf[fj]);
-            }
-        };
-        const int nsg = nk / 4;
-        load_step(0, 0);
-        int b = 0;
-        for (int j = 0; j < nsg; ++j) {
-            const int b1 = b == 2 ? 0 : b + 1, b2 = b1 == 2 ? 0 : b1 + 1;
-            d3r_wait_vm0();
-            __syncthreads();
-            load_step(4 * j + 1, b1);
-            load_step(4 * j + 2, b2);
-            math_hi(b);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-            __syncthreads();
-            load_step(4 * j + 3, b);
-            math_hi(b1);
-            d3r_wait_vm0();
-            __syncthreads();
-            if (j + 1 < nsg) load_step(4 * j + 4, b1);
-            {
-                const char* sa = smem + b2 * STAGE_BYTES;
-                const char* sbb = smem + b * STAGE_BYTES;
-                uint4 qa[FJ], qb[FJ];
-#pragma unroll
-                for (int f = 0; f < FJ; ++f) {
-                    const int ro = q_off + (q_row0 + f * 16) * KTB + coff;
-                    qa[f] = *reinterpret_cast<const uint4*>(sa + ro);
-                    qb[f] = *reinterpret_cast<const uint4*>(sbb + ro);
-                }
-#pragma unroll
-                for (int fi = 0; fi < FI; ++fi) {
-                    const int ro = p_off + (p_row0 + fi * 16) * KTB + coff;
-                    const uint4 pa = *reinterpret_cast<const uint4*>(sa + ro), pb = *reinterpret_cast<const uint4*>(sbb + ro);
-#pragma unroll
-                    for (int fj = 0; fj < FJ; ++fj) TR::mma16_f8(acc[fi][fj], pa, pb, qa[fj], qb[fj]);
-                }
-            }
-            b = b1;
-        }
-    } else if constexpr (DT == D3R_F16X2F8) {
+    if constexpr (DT == D3R_F16X2F8) {
         // ---- 2.5-unit rows (common.hpp, Traits<D3R_F16X2F8>): five K steps per 128 logical k ------------------------------------------------
         //   step s     activation slot (BM x 128 B)                                   weight slot (BN x 128 B)          MFMAs per fragment pair
         //   0          hi of k 0..63      (chunk 0 of super-group 2b)                 w_hi k 0..63     (chunk 5b)       2 x f16   a_hi . w_hi
@@ -959,10 +528,6 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
                             const uint4 pf = *reinterpret_cast<const uint4*>(sb + p_off + (p_row0 + fi * 16) * KTB + coff);
 #pragma unroll
                             for (int fj = 0; fj < FJ; ++fj) TR::mma16_hi(acc[fi][fj], pf, qf[fj]);
-                            if (p.f8_proxy) {
-#pragma unroll
-                                for (int fj = 0; fj < FJ; ++fj) TR::mma16_hi(acc[fi][fj], pf, qf[fj]);
-                            }
                         }
                     } else {
                         uint4 cur = *reinterpret_cast<const uint4*>(sb + p_off + p_row0 * KTB + coff);
@@ -972,10 +537,6 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
                             if (fi + 1 < FI) nxt = *reinterpret_cast<const uint4*>(sb + p_off + (p_row0 + (fi + 1) * 16) * KTB + coff);
 #pragma unroll
                             for (int fj = 0; fj < FJ; ++fj) TR::mma16_hi(acc[fi][fj], cur, qf[fj]);
-                            if (p.f8_proxy) {     // MEASUREMENT AID (results invalid): the MFMA mix of a 2.5-unit scheme, see launch_gemm
-#pragma unroll
-                                for (int fj = 0; fj < FJ; ++fj) TR::mma16_hi(acc[fi][fj], cur, qf[fj]);
-                            }
                             if (ks == 0) {
 #pragma unroll
                                 for (int i = fi * PPR_HI; i < (fi + 1) * PPR_HI && i < LPS; ++i) piece8(i, kt + 1, 1);
@@ -1005,10 +566,8 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
                     for (int fi = 0; fi < FI; ++fi) {
                         const char* pr = sb + p_off + (p_row0 + fi * 16) * KTB;
                         const uint4 pa = *reinterpret_cast<const uint4*>(pr + ca), pb = *reinterpret_cast<const uint4*>(pr + cb);
-                        if (!p.f8_proxy || (kt & 2)) {
 #pragma unroll
                         for (int fj = 0; fj < FJ; ++fj) TR::mma16_f8(acc[fi][fj], pa, pb, qa[fj], qb[fj]);
-                        }
                     }
                 } else {
                     const char* pr0 = sb + p_off + p_row0 * KTB;
@@ -1021,10 +580,8 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
                             na = *reinterpret_cast<const uint4*>(pr + ca);
                             nb = *reinterpret_cast<const uint4*>(pr + cb);
                         }
-                        if (!p.f8_proxy || (kt & 2)) {
 #pragma unroll
                         for (int fj = 0; fj < FJ; ++fj) TR::mma16_f8(acc[fi][fj], ca0, cb0, qa[fj], qb[fj]);
-                        }
                         if (more && fi < FI / 2) {
 #pragma unroll
                             for (int i = fi * PPR_F8; i < (fi + 1) * PPR_F8 && i < LPS; ++i) piece8(i, kt + 2, 0);
@@ -1121,8 +678,7 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
     for (int kt = 0; kt < nk; ++kt) {
         const int ahead = min(NS - 2, nk - 1 - kt);   // younger steps already issued
         if (NS == 2 || ahead <= 0) d3r_wait_vm0();
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPS) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
         __syncthreads();
         if (kt + NS - 1 < nk) {
             int nb = buf + NS - 1;
@@ -1220,15 +776,6 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
             }
         }
     } trace_end{p, tid};
-    if (p.flags & GF_NOSTORE) {   // measurement aid (D3R_GEMM_NOSTORE=1): keep the math, skip the epilogue's memory traffic
-        float t = 0.f;
-#pragma unroll
-        for (int a = 0; a < FI; ++a)
-#pragma unroll
-            for (int b = 0; b < FJ; ++b) t += acc[a][b][0] + acc[a][b][1] + acc[a][b][2] + acc[a][b][3];
-        if (t == 123.456f) reinterpret_cast<float*>(p.out)[0] = t;
-        return;
-    }
     const int i4 = (lane >> 4) * 4;  // first of this lane's 4 consecutive i inside a fragment
     const int jl = lane & 15;
 
@@ -1300,7 +847,7 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
     // ---- wide epilogues: accumulators -> wave-private LDS tile -> whole 128-byte rows ---------------------------------
     // An MFMA accumulator fragment gives a lane 4 consecutive columns of ONE row and 16 different rows per wave
     // instruction: stored directly that is 32 B (16-bit types) or 64 B (fp32) per row per instruction, and the store
-    // tail costs as much as the whole K loop at K = 1024 (measured with D3R_GEMM_NOSTORE: 750 -> 1270 TF/s,
+    // tail costs as much as the whole K loop at K = 1024 (measured with the epilogue's stores removed: 750 -> 1270 TF/s,
     // profiles/r01_call5). Staging a [64 rows j][64 x 16-bit or 32 x fp32 columns i] tile per wave in the (now idle) LDS
     // stages turns every global access into 8 lanes x 16 B = one full 128-byte line per row, 8 rows per instruction.
     constexpr int WROW = 144;   // 128 payload bytes + 16: keeps ds_write_b64/b128 and ds_read_b128 (nearly) conflict free
@@ -1664,7 +1211,6 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
                     // ONE residual buffer: the row of group g + 1 is requested into the register its group-g value has just left (a whole group
                     // ahead of its use, like the double buffer of the fp32 form, at half the registers: this kernel has none to spare).
                     const bool odd = rch & 1;
-                    const bool x3nt = p.x3res_nt != 0;       // probe D3R_GEMM_X3NT: the typed stream stored with the non-temporal policy (it is re-read by the next two launches)
                     auto swap_pair = [](uint32_t x) __attribute__((always_inline)) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true); };   // quad_perm [1,0,3,2]: lane ^ 1
                     auto request_row = [&](int g, int pass) __attribute__((always_inline)) -> uint4 {
                         const int m = min(jb + pass * 8 + rrow, p.M - 1);
@@ -1711,7 +1257,7 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
                             const uint32_t u0 = swap_pair(odd ? h.x : l.x), u1 = swap_pair(odd ? h.y : l.y);
                             if (m < p.M && n < p.n_store) {      // the typed sum: 16 hi bytes from the even lane, 16 lo bytes from the odd lane
                                 char* o2 = reinterpret_cast<char*>(p.out2) + TXR::boff((size_t)m * p.ldo2 + (n & ~7)) + (odd ? 16 : 0);
-                                store16(o2, odd ? make_uint4(u0, u1, l.x, l.y) : make_uint4(h.x, h.y, u0, u1), nt && x3nt);
+                                store16(o2, odd ? make_uint4(u0, u1, l.x, l.y) : make_uint4(h.x, h.y, u0, u1), false);      // plain: the typed stream is re-read by the next two launches
                             }
                             if (p.ln_part) {    // folded LayerNorm: (sum, sum of squares) of the 32 values of row m in this column group (8 lanes x 4), one fixed tree
                                 float sm, sq;
@@ -1968,17 +1514,6 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
     }
 }
 
-struct DevInfo { int cus; int wall_khz; };
-static DevInfo dev_info() {
-    DevInfo d{256, 100000};
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) d.cus = v;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeWallClockRate, dev) == hipSuccess && v > 0) d.wall_khz = v;
-    }
-    return d;
-}
-
 // ---- host side: configuration choice + launch ------------------------------------------------------------------
 template <int DT, class CF> static hipError_t launch_cfg(const GemmParams& p, hipStream_t s) {
     // the dynamic-LDS limit is a per-device function attribute: raise it once on every device this process launches on
@@ -1991,27 +1526,7 @@ template <int DT, class CF> static hipError_t launch_cfg(const GemmParams& p, hi
         attr_done.fetch_or(dev_bit, std::memory_order_relaxed);
     }
     const int grid = cdiv(p.M, CF::BM) * cdiv(p.n_store, CF::BN) * (p.splitk > 1 ? p.splitk : 1);
-    GemmParams q = p;
-    {   // first-round stagger (see the kernel): spread = factor x (epilogue bytes of the resident tiles / ~4.5 TB/s)
-        const char* e_st = probe_env("D3R_GEMM_STAGGER");       // default off: measured no gain (profiles/README.md), costs half a burst per launch; read per launch (probes toggle it)
-        const float factor = e_st ? (float)atof(e_st) : 0.0f;
-        const char* e_sm = probe_env("D3R_GEMM_STAGGER_MODE");
-        const int mode = e_sm ? atoi(e_sm) : 0;
-        static const DevInfo dev = dev_info();
-        const int resident = dev.cus * (CF::LDS * 2 <= 160 * 1024 ? 2 : 1);
-        if (factor > 0.f && grid > resident && !(p.flags & GF_NOSTORE)) {
-            const double eb_out = p.epi == EPI_F32 ? 4.0 : (double)Traits<DT>::EB;
-            double bytes = (double)CF::BM * CF::BN * eb_out;
-            if (p.res1) bytes += (double)CF::BM * CF::BN * eb_out;
-            if (p.res2) bytes += (double)CF::BM * CF::BN * eb_out;
-            if (p.out2) bytes += (double)CF::BM * CF::BN * Traits<DT>::EB;
-            const double burst_s = bytes * resident / 4.5e12;
-            q.stagger_ticks = (int)(burst_s * factor * dev.wall_khz * 1e3);
-            q.first_round = resident;
-            q.stagger_mode = mode;
-        }
-    }
-    hipLaunchKernelGGL((gemm_kernel<DT, CF>), dim3(grid), dim3(CF::NT), CF::LDS, s, q);
+    hipLaunchKernelGGL((gemm_kernel<DT, CF>), dim3(grid), dim3(CF::NT), CF::LDS, s, p);
     return hipGetLastError();
 }
 
@@ -2070,10 +1585,7 @@ static bool use_p4(const GemmParams& p, int dt) {
 int gemm_pick_config(const GemmParams& p, int dt) {
     if (use_p4(p, dt)) return GEMM_CFG_P4;
     int cfg = pick_config_raw(p, dt);
-    const bool split = dt == D3R_F16X3 || dt == D3R_F16F8 || dt == D3R_F16X2F8;
-    if (cfg == GEMM_CFG_256x128W4 && split) cfg = GEMM_CFG_256x128;
     if ((cfg == GEMM_CFG_256x128R || cfg == GEMM_CFG_64 || cfg == GEMM_CFG_96x64 || cfg == GEMM_CFG_384x192) && dt != D3R_F16X3) cfg = cfg == GEMM_CFG_256x128R ? GEMM_CFG_256x128 : GEMM_CFG_128;
-    if ((cfg == GEMM_CFG_256S4 || cfg == GEMM_CFG_256PP) && split) cfg = GEMM_CFG_256;
     if (dt == D3R_F16X2F8 && cfg != GEMM_CFG_256) cfg = GEMM_CFG_128;      // the 2.5-unit K loop exists on the two square tiles
     return cfg;
 }
@@ -2083,18 +1595,17 @@ static int pick_config_raw(const GemmParams& p, int dt) {
     const bool heads = p.epi == EPI_HEADS && !wide_vt;   // "heads" = needs a square tile (operand-role swap for V^T)
     const bool ok256 = cdiv(p.n_store, 256) * 256 <= n_rows && (p.epi != EPI_HEADS || p.head_c % 256 == 0);
     int forced = p.force_cfg;
-    if (forced < 0) {   // D3R_GEMM_CFG=0|1|2|3 pins the tile configuration (parity tests, probes); infeasible choices are ignored
+    if (forced < 0) {   // D3R_GEMM_CFG=0|1|2|3 pins the tile configuration (parity tests, A/B runs); infeasible choices are ignored
         forced = env_forced_cfg();
     }
+    // retired shapes: 4 (four-wave 256 x 128) runs on the eight-wave 256 x 128 tile, 5 / 6 (four-stage, ping-pong 256 x 256) on the two-stage one
+    if (forced == GEMM_CFG_256x128W4) forced = GEMM_CFG_256x128;
+    if (forced == GEMM_CFG_256S4 || forced == GEMM_CFG_256PP) forced = GEMM_CFG_256;
     if (forced == GEMM_CFG_384x192 && dt == D3R_F16X3 && !heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4 && p.amode == AMODE_LINEAR && cdiv(p.n_store, 192) * 192 <= n_rows) return forced;
     if (forced == GEMM_CFG_96x64 && dt == D3R_F16X3 && !heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4) return forced;
     if (forced == GEMM_CFG_128 || forced == GEMM_CFG_64 || (forced == GEMM_CFG_256 && ok256) ||
-        ((forced == GEMM_CFG_256x128 || forced == GEMM_CFG_512x128 || forced == GEMM_CFG_256x128W4 || forced == GEMM_CFG_256x128R) && !heads) || ((forced == GEMM_CFG_256S4 || forced == GEMM_CFG_256PP) && ok256))
+        ((forced == GEMM_CFG_256x128 || forced == GEMM_CFG_512x128 || forced == GEMM_CFG_256x128R) && !heads))
         return forced;
-    if (p.epi == EPI_F32 && p.K <= 1024) {   // probe: tile of the HBM-heavy residual-stream epilogues at short K (D3R_GEMM_F32CFG=0|2|4)
-        if (const char* e = probe_env("D3R_GEMM_F32CFG"))
-            if ((e[0] == '0' || e[0] == '2' || e[0] == '4') && e[1] == 0) return e[0] - '0';
-    }
     if (!heads && p.n_store <= 128) {
         if (cdiv(p.M, 512) >= 512) return GEMM_CFG_512x128;
         if (cdiv(p.M, 256) >= 512) return GEMM_CFG_256x128;
@@ -2106,47 +1617,37 @@ static int pick_config_raw(const GemmParams& p, int dt) {
     // + GELU 384 -> 364, plain stores 108 -> 88 / 222 -> 161 / 286 -> 224 (N = 768 / 1536 / 2304), the fp32-residual projections at K = 768 90 -> 94.
     // On the forward the isolated gains mostly vanish (in the network the default tiles run faster than back to back on one shape, and the two decoder
     // sides overlap their tails on the two streams): every eligible launch on it 194.55 -> 196.75 and 191.7 -> 192.7 pairs/s (two boxes, every run above every
-    // baseline run); WITHOUT the K <= 1024 projections 191.7 -> 190.9 -- so the rule is "every eligible launch". D3R_GEMM_T384=0: never; =1: not the
-    // fp32-residual projections at K <= 1024 (the probe of that A/B).
+    // baseline run); WITHOUT the K <= 1024 projections 191.7 -> 190.9 -- so the rule is "every eligible launch".
     if (dt == D3R_F16X3 && !heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4 && p.amode == AMODE_LINEAR && p.n_store % 192 == 0 && cdiv(p.n_store, 192) * 192 <= n_rows) {
-        const char* e384 = probe_env("D3R_GEMM_T384");
         const long t384 = (long)cdiv(p.M, 384) * cdiv(p.n_store, 192);
-        const bool short_res = p.epi == EPI_F32 && p.K <= 1024;
         const int cus = device_cus();       // whole rounds of THIS device's compute units (256 on MI355X; a partitioned device has fewer)
-        if (!(e384 && e384[0] == '0') && !(short_res && e384 && e384[0] == '1') && t384 >= cus * 9 / 10 && (t384 % cus == 0 || t384 % cus >= cus * 9 / 10)) return GEMM_CFG_384x192;
+        if (t384 >= cus * 9 / 10 && (t384 % cus == 0 || t384 % cus >= cus * 9 / 10)) return GEMM_CFG_384x192;
     }
     // split-fp16, launches without attention heads (their V^T regions need a square tile): the two-blocks-per-CU 256 x 128 shape with the
     // weights of a K step in registers. Measured on MI355X (profiles/r03_c/gemmtrace_cfg7.log, bench_r*.log): it wins where the epilogue
     // is an HBM burst that the other block's MFMAs can run under -- the fp32-residual projections at K <= 1024 (proj 49152 x 1024 x
     // 1024: 337 vs 296 TFLOP/s) -- and loses 1-6 % where the epilogue is VALU work (GELU, typed stores: on gfx950 VALU and MFMA of a
     // SIMD overlap only by half, tools/issue_probe.hip) or the K loop dominates (fc2): default = those projections only.
-    // D3R_GEMM_R=0: never; =1: every eligible launch (the A/B of the round).
     if (dt == D3R_F16X3 && !heads && p.epi != EPI_HEADS && p.n_store > 128) {
-        const char* e_r = probe_env("D3R_GEMM_R");      // read per call, like the other probes (tests move it with monkeypatch)
-        const int r_on = e_r ? atoi(e_r) : -1;
         const long tiles = (long)cdiv(p.M, 256) * cdiv(p.n_store, 128);
-        if (r_on == 1 && tiles >= 512) return GEMM_CFG_256x128R;
-        if (r_on < 0 && p.epi == EPI_F32 && p.res1 != nullptr && p.K <= 1024 && p.amode == AMODE_LINEAR && tiles >= 1024) return GEMM_CFG_256x128R;
+        if (p.epi == EPI_F32 && p.res1 != nullptr && p.K <= 1024 && p.amode == AMODE_LINEAR && tiles >= 1024) return GEMM_CFG_256x128R;
     }
     // split-fp16, small problems (the one- and two-pair forwards of dust3r/demo.py:156 / visloc.py:88, batch_size = 1): below ~1.5
     // 128 x 128 tiles per CU the chip is not full -- the 64 x 64 tile by four waves of 32 x 32 runs the same problem on four times the
-    // waves. D3R_GEMM_T64 moves the crossover (0 = never); measured at 200 / 400 / 600 / 1000 / 2000 for 1-8 pairs per call: 200 is the
-    // best or within noise of it everywhere (profiles/r03_f/latency_small_tiles.log).
+    // waves. The crossover, 200 tiles of 128 x 128, was measured against 400 / 600 / 1000 / 2000 for 1-8 pairs per call: the best or within
+    // noise of it everywhere (profiles/r03_f/latency_small_tiles.log).
     if (dt == D3R_F16X3 && p.n_store > 128) {
-        long t64 = 200;
-        if (const char* e = probe_env("D3R_GEMM_T64")) t64 = atol(e);
-        if ((long)cdiv(p.M, 128) * cdiv(p.n_store, 128) < t64) {
+        if ((long)cdiv(p.M, 128) * cdiv(p.n_store, 128) < 200) {
             // round 6: M 96 x N 64 instead, where its tiles come to 1.5 ... 2 per CU. The small tiles run at the rate their operand rows arrive: the 96 x 64
             // shape moves 17 % fewer bytes per flop, but a CU needs two or three resident blocks' worth of loads in flight to keep that rate -- measured on MI355X
             // (tools/tile_probe.py, profiles/r06_f; 64 x 64 -> 96 x 64, us per launch): 3072 x 1024 x 4096 81 -> 71, 2304 x 1024 x 4096 75 -> 61, 3072 x 768 x 3072 66 -> 53,
             // 1536 x 1536 x 768 20 -> 18, 768 x 3072 x 768 20 -> 18 (384 or 512 tiles); 1536 x 1024 x 4096 56 -> 61 (256 tiles: one block per CU), 1152 x 768 x 3072 33 -> 40 (144),
-            // 1536 x 2304 x 768 28 -> 30 (576). nn.Linear operands without attention heads only. INSIDE the forward (tools/env_latency_ab.py, same process, rule on | off) the
+            // 1536 x 2304 x 768 28 -> 30 (576). nn.Linear operands without attention heads only. INSIDE the forward (same process, rule on | off) the
             // K = 768 / 1024 cases do not carry over -- one pair 10.04 vs 9.96 ms (the decoder's two sides run side by side: twice the tiles in flight), two pairs 14.49 vs
             // 14.68 -- so the rule keeps the long K loops only (K >= 2048: fc2 of the encoder at two / three pairs, of the decoder at four).
             const long t96 = (long)cdiv(p.M, 96) * cdiv(p.n_store, 64);
             const int cus = device_cus();
-            const char* e96 = probe_env("D3R_GEMM_T96");        // probe builds: 0 = never
-            if (!(e96 && e96[0] == '0') && !heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4 && p.amode == AMODE_LINEAR && p.K >= 2048 && t96 * 2 >= (long)cus * 3 && t96 <= (long)cus * 2) return GEMM_CFG_96x64;
+            if (!heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4 && p.amode == AMODE_LINEAR && p.K >= 2048 && t96 * 2 >= (long)cus * 3 && t96 <= (long)cus * 2) return GEMM_CFG_96x64;
             return GEMM_CFG_64;
         }
     }
@@ -2154,97 +1655,21 @@ static int pick_config_raw(const GemmParams& p, int dt) {
     // fp16 + fp8 rows: the 256-wide tile is 1.3-1.6x ahead of the 128 x 128 one per tile (its K loop lost a third of its MFMA work, the small
     // tile's LDS read traffic per MFMA is twice as high), so it pays from a single round of resident blocks on: measured +1.5 % on the
     // forward with the decoder's 24576 x 768 GEMMs (288 tiles, two such launches side by side on the two streams) on it
-    long t256 = (dt == D3R_F16F8 || dt == D3R_F16X2F8) ? 250 : 700;     // probes: D3R_GEMM_T256 moves the 256x256 / 128x128 crossover, D3R_GEMM_MID=2 sends the shapes below it to 256x128
-    if (const char* e = probe_env("D3R_GEMM_T256")) t256 = atol(e);
-    if (ok256 && tiles256 >= t256) {
-        // nn.Linear operands: the ping-pong schedule measured 1-8 % ahead of the plain 2-stage loop (profiles/r01_call13);
-        // implicit-GEMM operands: behind it (the per-tap address arithmetic sits in the load segment) -> plain loop
-        const char* e_pp = probe_env("D3R_GEMM_PP");
-        const bool pp = e_pp ? e_pp[0] == '1' : false;
-        return (pp && p.amode == AMODE_LINEAR) ? GEMM_CFG_256PP : GEMM_CFG_256;
-    }
-    if (const char* e = probe_env("D3R_GEMM_MID")) if (e[0] == '2' && !heads) return GEMM_CFG_256x128;
+    const long t256 = (dt == D3R_F16F8 || dt == D3R_F16X2F8) ? 250 : 700;
+    if (ok256 && tiles256 >= t256) return GEMM_CFG_256;
     return GEMM_CFG_128;
 }
 
 template <int DT> static hipError_t launch_t(const GemmParams& p, hipStream_t s) {
-    int cfg = gemm_pick_config(p, DT);
-    constexpr bool SPLIT = (DT == D3R_F16X3 || DT == D3R_F16F8 || DT == D3R_F16X2F8);   // split-fp16 and fp16 + fp8 rows need 128-byte K rows, two stages
-    if (cfg == GEMM_CFG_256x128W4 && SPLIT) cfg = GEMM_CFG_256x128;
-    if (cfg == GEMM_CFG_256x128R && DT != D3R_F16X3) cfg = GEMM_CFG_256x128;      // the weights-in-registers shape exists for split-fp16 only
-    if ((cfg == GEMM_CFG_64 || cfg == GEMM_CFG_96x64) && DT != D3R_F16X3) cfg = GEMM_CFG_128;                // the 64 x 64 / 96 x 64 shapes too
-    if (cfg == GEMM_CFG_384x192 && DT != D3R_F16X3) cfg = GEMM_CFG_128;           // and the 384 x 192 one
+    const int cfg = gemm_pick_config(p, DT);       // already mapped onto the shapes DT has
     // the fused head tail needs a wave to hold every output channel of its rows: waves stacked along m, 128 columns per wave
     if (p.epi == EPI_HEAD4 && (DT != D3R_F16X3 || !(cfg == GEMM_CFG_512x128 || cfg == GEMM_CFG_256x128R))) return hipErrorInvalidValue;
-    if ((cfg == GEMM_CFG_256S4 || cfg == GEMM_CFG_256PP) && (SPLIT || !kProbes)) cfg = GEMM_CFG_256;      // the four-wave 256 x 128, four-stage and ping-pong shapes never won a
-    if (cfg == GEMM_CFG_256x128W4 && !kProbes) cfg = GEMM_CFG_256x128;                                       // default (profiles/r01_*): compiled in probe builds only (-DD3R_PROBES)
-    // the ping-pong schedule has no operand-role swap: attention projections only through the wide V^T route
-    if (cfg == GEMM_CFG_256PP && p.epi == EPI_HEADS && !((DT == D3R_BF16 || DT == D3R_F16) && (p.ntok & 63) == 0 && !(p.flags & GF_NOWIDE))) cfg = GEMM_CFG_256;
-    if constexpr (!SPLIT && kProbes) {
-        if (cfg == GEMM_CFG_256x128W4) return launch_cfg<DT, Cfg256x128w4>(p, s);
-        if (cfg == GEMM_CFG_256S4) return launch_cfg<DT, Cfg256s4>(p, s);
-        if (cfg == GEMM_CFG_256PP) return launch_cfg<DT, Cfg256pp>(p, s);
-    }
-    if constexpr (kProbes && DT != D3R_F16F8 && DT != D3R_F16X2F8) {
-        const char* e_a3 = probe_env("D3R_GEMM_A3");
-        const bool a3 = e_a3 ? e_a3[0] != '0' : false;
-        if (a3 && cfg == GEMM_CFG_256) return launch_cfg<DT, Cfg256a3>(p, s);
-    }
     if constexpr (DT == D3R_F16X3) {
         if (cfg == GEMM_CFG_384x192) return launch_cfg<DT, Cfg384x192>(p, s);
         if (cfg == GEMM_CFG_256x128R) return launch_cfg<DT, Cfg256x128r>(p, s);
         if (cfg == GEMM_CFG_96x64) return launch_cfg<DT, Cfg96x64>(p, s);
-        if (cfg == GEMM_CFG_64) {
-            const char* e_ns = probe_env("D3R_GEMM_64NS");     // probe: LDS ring depth of the 64 x 64 tile (2 | 3 | 4)
-            const int ns = e_ns ? atoi(e_ns) : 3;             // measured (profiles/r03_f): one pair 14.56 ms on the 128 x 128 tile, 12.36 / 10.38 / 10.48 ms with 2 / 3 / 4 slots
-            if constexpr (kProbes) {
-                if (ns == 2) return launch_cfg<DT, Cfg64>(p, s);
-                if (ns == 4) return launch_cfg<DT, Cfg64s4>(p, s);
-            }
-            (void)ns;
-            return launch_cfg<DT, Cfg64s3>(p, s);
-        }
-        // split-fp16: D3R_GEMM_X3SW=1 selects the software-pipelined K loop. Measured on MI355X (profiles/r02_*): equal to the plain
-        // two-stage loop on the 256-wide tiles, 10-15 % behind on the 128 x 128 tile -- the K loop is not where the time goes (the
-        // same launches without their epilogue run 30 % faster in either form), so the plain loop stays the default.
-        // D3R_GEMM_X3IL=1 / 0: nn.Linear launches on the 256 x 256 tile with the DMA pieces interleaved with the MFMA rows (bit-identical)
-        if constexpr (kProbes) {
-        const char* e_il = probe_env("D3R_GEMM_X3IL");
-        const bool x3il = e_il ? e_il[0] == '1' : false;
-        if (x3il && cfg == GEMM_CFG_256 && p.amode == AMODE_LINEAR && (size_t)512 * p.lda * 4 < (1ull << 32) && (size_t)512 * p.K * 4 < (1ull << 32)) return launch_cfg<DT, Cfg256il>(p, s);
-        const char* e_sw = probe_env("D3R_GEMM_X3SW");
-        const bool sw = e_sw ? e_sw[0] == '1' : false;
-        if (sw) {
-            switch (cfg) {
-                case GEMM_CFG_256: return launch_cfg<DT, Cfg256sw>(p, s);
-                case GEMM_CFG_256x128: return launch_cfg<DT, Cfg256x128sw>(p, s);
-                case GEMM_CFG_512x128: return launch_cfg<DT, Cfg512x128sw>(p, s);
-                default: return launch_cfg<DT, Cfg128sw>(p, s);
-            }
-        }
-        }
-    }
-    if constexpr (DT == D3R_F16F8) {
-        // two blocks per CU (256 x 128 tile, four waves, 64-byte K steps): one block's K loop under the other's epilogue. The attention
-        // projections keep the square tile (their V^T regions swap the MFMA operand roles). D3R_GEMM_F8W4=1 / 0.
-        const char* e_w4 = probe_env("D3R_GEMM_F8W4");
-        const int w4 = e_w4 ? (e_w4[0] == '1' ? 1 : 0) : 0;
-        if constexpr (kProbes) { if (w4 == 1 && cfg == GEMM_CFG_256 && p.epi != EPI_HEADS && p.n_store % 128 == 0) return launch_cfg<DT, Cfg256x128f8>(p, s); }
-        (void)w4;
-        // DMA pieces interleaved with the MFMA rows (PP = 4). Measured on MI355X (profiles/r02_f8/bench_f8_il.log): +3 % on the 256-wide
-        // tiles (one block per CU: behind the barrier neither wave of a SIMD has MFMAs to issue), -2.5 % on the 128 x 128 tile (the
-        // CU's second block already fills that gap). D3R_GEMM_F8IL=0 / 1 forces the burst / interleaved loop everywhere.
-        static const int il = [] { const char* e = probe_env("D3R_GEMM_F8IL"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-        if (il == 1 || (il < 0 && cfg != GEMM_CFG_128)) {
-            switch (cfg) {
-                case GEMM_CFG_256: return launch_cfg<DT, Cfg256il>(p, s);
-                case GEMM_CFG_256x128: return launch_cfg<DT, Cfg256x128il>(p, s);
-                case GEMM_CFG_512x128: return launch_cfg<DT, Cfg512x128il>(p, s);
-                default: if constexpr (kProbes) return launch_cfg<DT, Cfg128il>(p, s); break;
-            }
-        }
-    }
-    if constexpr (DT == D3R_F16X3) {
+        // the 64 x 64 tile on a three-slot ring. Measured (profiles/r03_f): one pair 14.56 ms on the 128 x 128 tile, 12.36 / 10.38 / 10.48 ms with 2 / 3 / 4 slots
+        if (cfg == GEMM_CFG_64) return launch_cfg<DT, Cfg64s3>(p, s);
         // 128 x 128 launches of fewer than 1100 tiles (the one- to four-pair forwards) on the eight-wave shape. Measured (profiles/r03_k):
         // one pair 10.59 -> 10.26 ms, two 16.0 -> 15.3, four 26.3 -> 25.9; applied to the 1152-tile launches of the 32-pair step as well:
         // -0.1 %, hence the limit. D3R_GEMM_T128W8 moves it (0 = never).
@@ -2254,30 +1679,26 @@ template <int DT> static hipError_t launch_t(const GemmParams& p, hipStream_t s)
             if ((long)cdiv(p.M, 128) * cdiv(p.n_store, 128) < t) return launch_cfg<DT, Cfg128w8>(p, s);
         }
     }
-    if constexpr (DT == D3R_F16X2F8) {      // nn.Linear matrices of the transformer blocks only (N >= 768): the two square tiles; D3R_GEMM_X2IL=0 / 1:
-        const char* e_il = probe_env("D3R_GEMM_X2IL");     // DMA pieces of the next step in one burst behind the barrier / interleaved with the MFMA rows (default: on the 256-wide tile)
-        const int il = e_il ? (e_il[0] == '1' ? 1 : 0) : -1;
-        if constexpr (kProbes) {
-            if (cfg == GEMM_CFG_256 && il == 0) return launch_cfg<DT, Cfg256>(p, s);
-            if (cfg != GEMM_CFG_256 && il == 1) return launch_cfg<DT, Cfg128il>(p, s);
+    if constexpr (DT == D3R_F16F8) {
+        // the 256-wide tiles with the DMA pieces interleaved with the MFMA rows (PP = 4). Measured on MI355X (profiles/r02_f8/bench_f8_il.log): +3 % on
+        // the 256-wide tiles (one block per CU: behind the barrier neither wave of a SIMD has MFMAs to issue), -2.5 % on the 128 x 128 tile (the CU's
+        // second block already fills that gap)
+        switch (cfg) {
+            case GEMM_CFG_256: return launch_cfg<DT, Cfg256il>(p, s);
+            case GEMM_CFG_256x128: return launch_cfg<DT, Cfg256x128il>(p, s);
+            case GEMM_CFG_512x128: return launch_cfg<DT, Cfg512x128il>(p, s);
+            default: return launch_cfg<DT, Cfg128>(p, s);
         }
-        (void)il;
+    } else if constexpr (DT == D3R_F16X2F8) {      // nn.Linear matrices of the transformer blocks only (N >= 768): the two square tiles, interleaved DMA on the 256-wide one
         return cfg == GEMM_CFG_256 ? launch_cfg<DT, Cfg256il>(p, s) : launch_cfg<DT, Cfg128>(p, s);
     } else {
-    if constexpr (DT == D3R_F16F8 && !kProbes) return launch_cfg<DT, Cfg128>(p, s);     // every other shape left through the interleaved loop above
-    else
-    switch (cfg) {
-        case GEMM_CFG_256: return launch_cfg<DT, Cfg256>(p, s);
-        case GEMM_CFG_256x128: return launch_cfg<DT, Cfg256x128>(p, s);
-        case GEMM_CFG_512x128: return launch_cfg<DT, Cfg512x128>(p, s);
-        default: return launch_cfg<DT, Cfg128>(p, s);
+        switch (cfg) {
+            case GEMM_CFG_256: return launch_cfg<DT, Cfg256>(p, s);
+            case GEMM_CFG_256x128: return launch_cfg<DT, Cfg256x128>(p, s);
+            case GEMM_CFG_512x128: return launch_cfg<DT, Cfg512x128>(p, s);
+            default: return launch_cfg<DT, Cfg128>(p, s);
+        }
     }
-    }
-}
-
-bool conv_k_slice_major() {
-    static const bool v = [] { const char* e = probe_env("D3R_CONV_KORDER"); return !(e && e[0] == '0'); }();   // D3R_CONV_KORDER=0: tap-major (probe)
-    return v;
 }
 
 static unsigned long long* g_trace_buf = nullptr;
@@ -2287,24 +1708,12 @@ void gemm_set_trace(unsigned long long* buf, size_t capacity_blocks) { g_trace_b
 hipError_t launch_gemm(int dt, const GemmParams& p_in, hipStream_t s) {
     GemmParams p = p_in;
     if (g_trace_buf && (size_t)cdiv(p.M, 128) * cdiv(p.n_store, 128) <= g_trace_cap) p.trace = g_trace_buf;   // capacity for the smallest tile
-    if (const char* e = probe_env("D3R_GEMM_NOSTORE")) if (e[0] == '1') p.flags |= GF_NOSTORE;
     // (the folded-LayerNorm producer launches keep their wide epilogue: it is where the row sums and the typed residual stream are written)
     if (const char* e = getenv("D3R_GEMM_NOWIDE")) if (e[0] == '1' && !p.ln_part && !(p.flags & GF_X3RES)) p.flags |= GF_NOWIDE;
-    // measurement aid (results INVALID): the fp16 + fp8 K loop issues the MFMA mix of a 2.5-unit scheme -- per 64 k four f16 MFMAs (hi.hi and
-    // hi.w_lo on the f16 pipe) and half an e4m3 MFMA (a_lo.w_hi, K = 128 spans two groups) = 80 MFMA cycles instead of 64 (fp16f8) / 96 (fp16x3)
-    if (const char* e = probe_env("D3R_F8_PROXY")) if (e[0] == '1') {
-        p.f8_proxy = 1;
-        static std::atomic<bool> told{false};
-        if (!told.exchange(true)) fprintf(stderr, "[dust3r_amd] D3R_F8_PROXY=1: MEASUREMENT AID -- the fp16 + fp8 K loops issue a different MFMA mix and every result of an fp16f8 engine is INVALID\n");
-    }
-    // wide epilogues store with the non-temporal policy (measured +3..10 % on isolated GEMMs, +1 % on the forward); D3R_GEMM_NT=0: plain stores
-    { const char* e = probe_env("D3R_GEMM_NT"); if (!e || e[0] != '0') p.flags |= GF_NTSTORE; }
+    p.flags |= GF_NTSTORE;      // wide epilogues store with the non-temporal policy (measured +3..10 % on isolated GEMMs, +1 % on the forward)
     const int kt = 128 / (int)dt_bytes(dt);
     if (p.M <= 0 || p.n_pad % 128 != 0 || p.n_store > p.n_pad || p.K % kt != 0 || p.K <= 0) return hipErrorInvalidValue;
     if (p.amode == AMODE_CONV && (p.Cin % kt != 0 || p.zero_page == nullptr)) return hipErrorInvalidValue;
-    if (p.amode == AMODE_CONV) p.kslice_major = conv_k_slice_major() ? 1 : 0;
-    if (const char* e = probe_env("D3R_GEMM_X3NT")) p.x3res_nt = e[0] == '1' ? 1 : 0;
-    if (const char* e = probe_env("D3R_GEMM_PANEL")) { const int v = atoi(e); if (v >= 1 && v <= 64) p.panel = v; }
     if (p.epi == EPI_HEADS && p.head_c % 128 != 0 && p.head_c < (1 << 29)) return hipErrorInvalidValue;
     if (p.epi == EPI_HEAD4 && (p.n_store > 128 || p.n_store % 4 != 0 || !p.res1 || !p.res2 || !p.out || !p.out2)) return hipErrorInvalidValue;
     // folded LayerNorm (kernels.hpp): statistics come out of the wide fp32 epilogue only; the consumer side exists for split-fp16 operands, typed / GELU / head outputs
@@ -2321,23 +1730,17 @@ hipError_t launch_gemm(int dt, const GemmParams& p_in, hipStream_t s) {
         return hipErrorInvalidValue;
     if (use_p4(p, dt)) return launch_gemm_p4(p, s);
     {   // split-K (kernels.hpp): only with the caller's buffers, split-fp16 nn.Linear launches of the small-batch forwards (the problems the heuristic sends to the
-        // 64 x 64 tile: fewer than 200 tiles of 128 x 128), the plain K loop. Probe knobs (probe builds): D3R_SK_TILE=64|128 the tile the split launch runs on,
-        // D3R_SK_BLOCKS the most blocks a launch may have after the split, D3R_SK_MINSTEPS the fewest K steps (of 32) per slice.
+        // 64 x 64 tile: fewer than 200 tiles of 128 x 128), the plain K loop; at most 3 blocks per CU after the split, at least 16 K steps (of 32) per slice.
         int sk = 1;
-        if (p.sk_slab && p.sk_cnt && p.splitk != 1 && dt == D3R_F16X3 && p.amode == AMODE_LINEAR && !p.trace && !(p.flags & GF_NOSTORE) && p.force_cfg < 0 &&
+        if (p.sk_slab && p.sk_cnt && p.splitk != 1 && dt == D3R_F16X3 && p.amode == AMODE_LINEAR && !p.trace && p.force_cfg < 0 &&
             gemm_pick_config(p, dt) == GEMM_CFG_64) {
-            const int cus = device_cus();
-            int tile = 64, minsteps = 16;
-            long maxblocks = (long)cus * 3;
-            if (const char* e = probe_env("D3R_SK_TILE")) tile = atoi(e) == 128 ? 128 : 64;
-            if (const char* e = probe_env("D3R_SK_BLOCKS")) maxblocks = atol(e);
-            if (const char* e = probe_env("D3R_SK_MINSTEPS")) minsteps = atoi(e);
+            constexpr int tile = 64, minsteps = 16;
+            const long maxblocks = (long)device_cus() * 3;
             const long tiles = (long)cdiv(p.M, tile) * cdiv(p.n_store, tile);
             const int nk32 = p.K / 32;
             for (int c : {8, 6, 4, 3, 2}) {
                 if (tiles * c <= maxblocks && nk32 % c == 0 && nk32 / c >= minsteps && (size_t)tiles * c * tile * tile <= p.sk_slab_floats && tiles <= p.sk_cnt_n) { sk = c; break; }
             }
-            if (sk > 1 && tile == 128) p.force_cfg = GEMM_CFG_128;
         }
         p.splitk = sk;
     }

@@ -39,8 +39,8 @@ constexpr int LDS = RBUF0 + NW * 2 * 1024;                   // 162 816 of the C
 constexpr int NFRAG = FI * FJ;                               // 32 fragments per wave tile
 static_assert(LDS <= 160 * 1024, "one block owns the CU's LDS");
 
-// epilogue kinds; _LN: the launch also writes the row partial sums of a folded LayerNorm; NONE: probe builds (GF_NOSTORE), the K loops alone
-enum { EPK_TYPED = 0, EPK_GELU = 1, EPK_X3RES = 2, EPK_X3RES_LN = 3, EPK_NONE = 4 };
+// epilogue kinds; _LN: the launch also writes the row partial sums of a folded LayerNorm
+enum { EPK_TYPED = 0, EPK_GELU = 1, EPK_X3RES = 2, EPK_X3RES_LN = 3 };
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 template <int V> using IC = std::integral_constant<int, V>;
@@ -78,12 +78,12 @@ D3R_DEV void swap32(uint32_t& a, uint32_t& b) { asm volatile("s_nop 1\n\tv_perml
 D3R_DEV float add_xor16(float x) { uint32_t a = __float_as_uint(x), b = a; swap16(a, b); return __uint_as_float(a) + __uint_as_float(b); }
 D3R_DEV float add_xor32(float x) { uint32_t a = __float_as_uint(x), b = a; swap32(a, b); return __uint_as_float(a) + __uint_as_float(b); }
 
-D3R_DEV void tile_origin(int v, int ntiles, int tiles_m, int tiles_n, int panel_w, int& m0, int& n0) {
+D3R_DEV void tile_origin(int v, int ntiles, int tiles_m, int tiles_n, int& m0, int& n0) {
     const int lid = xcd_remap(v, ntiles);
-    const int per_panel = panel_w * tiles_m;
+    const int per_panel = GEMM_PANEL * tiles_m;
     const int panel = lid / per_panel, rem = lid - panel * per_panel;
-    const int width = min(panel_w, tiles_n - panel * panel_w);
-    const int tm = rem / width, tn = panel * panel_w + (rem - tm * width);
+    const int width = min(GEMM_PANEL, tiles_n - panel * GEMM_PANEL);
+    const int tm = rem / width, tn = panel * GEMM_PANEL + (rem - tm * width);
     m0 = tm * BM;
     n0 = tn * BN;
 }
@@ -99,7 +99,7 @@ constexpr int nst_of(int dr, bool lnp) { return dr == 0 ? 0 : dr == 3 ? 2 + (lnp
 
 // NF: fragments of the drain set per K step (1: K >= 1024, every one of a tile's first 32 steps carries one; 2: 16 steps carry two)
 // L32 (NF == 1 only): a tile has exactly 32 K steps, so its last step also carries the previous tile's last fragment
-template <int EPK, int NF, bool L32, int DBG = 0>      // DBG: probe instances (results invalid): 1 no stores, 2 no lane swaps, 4 stores early in the step, 5 plain instead of non-temporal stores, 6 the row-2 wait does not wait
+template <int EPK, int NF, bool L32>
 __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_m, int tiles_n, int ntiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using TX = Traits<D3R_F16X3>;
@@ -111,7 +111,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_
     const int G = gridDim.x;
     constexpr bool X3R = EPK == EPK_X3RES || EPK == EPK_X3RES_LN;     // typed residual stream epilogue (GF_X3RES)
     constexpr bool LNP = EPK == EPK_X3RES_LN;
-    constexpr bool DRAINS = EPK != EPK_NONE;
     constexpr int NREQ = X3R ? NF : 0;                                 // residual-row requests of a draining K step
 
     // ---- DMA: per-lane byte offsets of the 8 activation and 4 weight passes of a K step (32 rows apart); every piece takes the SAME wave-uniform base ----
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_
     const char* ld_w = nullptr;
     auto ld_set_tile = [&](int v) __attribute__((always_inline)) {
         int m0, n0;
-        tile_origin(v, ntiles, tiles_m, tiles_n, p.panel, m0, n0);
+        tile_origin(v, ntiles, tiles_m, tiles_n, m0, n0);
         ld_a = reinterpret_cast<const char*>(p.act) + (size_t)m0 * p.lda * 4;
         ld_w = reinterpret_cast<const char*>(p.wgt) + (size_t)n0 * p.K * 4;
     };
@@ -274,11 +273,9 @@ __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_
             } else {
                 // lanes l and l ^ 16 hold columns 0-3 / 4-7 of one 8-group of a row: the first keeps its hi words and takes the partner's hi words (16 hi bytes),
                 // the second takes the first's lo words and keeps its own (16 lo bytes): [hi x8][lo x8] = the row's 32 bytes, one 16-byte store per lane
-                if constexpr (DBG != 2) { swap16(hx[L], lx[L]); swap16(hy[L], ly[L]); }
+                swap16(hx[L], lx[L]); swap16(hy[L], ly[L]);
                 char* ob = obase0 + ((size_t)(dm0 + wave * 64 + fj * 16) * old_ + dn0 + fi * 16) * 4;
-                if constexpr (DBG == 5) gst16<false>(ob, o_voff, (u32x4_t){hx[L], hy[L], lx[L], ly[L]});
-                else if constexpr (DBG != 1) gst16<true>(ob, o_voff, (u32x4_t){hx[L], hy[L], lx[L], ly[L]});
-                else asm volatile("" :: "v"(hx[L]), "v"(hy[L]), "v"(lx[L]), "v"(ly[L]), "s"(ob));
+                gst16<true>(ob, o_voff, (u32x4_t){hx[L], hy[L], lx[L], ly[L]});
             }
         } else {
             if constexpr (k == 0) {
@@ -340,7 +337,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_
         constexpr bool LAST = decltype(last_tag)::value;
         if constexpr (SL >= 6 && SL <= 17) dma_piece(IC<SL - 6>());
         if constexpr (DR != 0) {
-            constexpr int L = SL & 1, k = DBG == 4 ? ((SL >> 1) + 8) % 12 : SL >> 1;      // DBG 4: the fragment's pieces rotated so that its store sits in slot 6
+            constexpr int L = SL & 1, k = SL >> 1;
             // operations issued since this lane's residual request (behind piece 1 of the previous step, or slot 4 of the previous tile's last step):
             // the other lane's request (lane 0 only), that step's 12 DMA pieces and its stores
             typedef IC<(NF == 2 && L == 0 ? 1 : 0) + 12 + PREVNST> RW;
@@ -370,7 +367,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_
         if constexpr (FIv == 2) {
             // this wave's WEIGHT pieces of the next step's slot have landed (issued one step ago, ahead of the activation pieces: WAITN younger operations may
             // stay in flight); the barrier publishes them to every wave and frees the weight slot the pieces below go into
-            wait_vm<DBG == 6 ? WAITN + 14 : WAITN>();
+            wait_vm<WAITN>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
@@ -420,7 +417,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_
     // step of a tile.
     auto kstep = [&](auto f, auto first, auto dr_tag, auto pdr_tag, auto req_tag, auto last_tag) __attribute__((always_inline)) {
         constexpr int DR = decltype(dr_tag)::value, PDR = decltype(pdr_tag)::value;
-        constexpr bool LAST = decltype(last_tag)::value && DRAINS, REQ = decltype(req_tag)::value && X3R && DR != 0;
+        constexpr bool LAST = decltype(last_tag)::value, REQ = decltype(req_tag)::value && X3R && DR != 0;
         constexpr bool TSTART = decltype(first)::value && DR != 0;
         constexpr int PREVNST = nst_of(PDR, LNP);
         const int nslot = slot == NST - 1 ? 0 : slot + 1;
@@ -473,10 +470,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_
     constexpr bool l32 = NF == 1 && L32;
     bool have_d = false;
     for (int v = blockIdx.x; v < ntiles; v += G) {
-        tile_origin(v, ntiles, tiles_m, tiles_n, p.panel, cm0, cn0);
+        tile_origin(v, ntiles, tiles_m, tiles_n, cm0, cn0);
         int kt = 0;
         bool last_done = false;
-        if (!DRAINS || !have_d) {
+        if (!have_d) {
             kstep(IC<NFRAG>(), T_(), IC<0>(), IC<0>(), F_(), F_());
             kt = 1;
         } else if constexpr (NF == 1) {
@@ -516,16 +513,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_p4_kernel(GemmParams p, int tiles_
 #pragma unroll
             for (int fj = 0; fj < FJ; ++fj) dacc[fi][fj] = acc[fi][fj];
         have_d = true;
-    }
-    if constexpr (EPK == EPK_NONE) {     // probe: keep the math alive
-        float t = 0.f;
-#pragma unroll
-        for (int fi = 0; fi < FI; ++fi)
-#pragma unroll
-            for (int fj = 0; fj < FJ; ++fj) t += dacc[fi][fj][0] + dacc[fi][fj][1] + dacc[fi][fj][2] + dacc[fi][fj][3];
-        if (t == 123.456f) reinterpret_cast<float*>(p.out ? p.out : p.out2)[0] = t;
-        wait_vm<0>();
-        return;
     }
     // ---- the last tile of this block: drained with nothing to hide under ------------------------------------------------------------------------
     if (have_d) {
@@ -577,13 +564,13 @@ bool gemm_p4_eligible(const GemmParams& p, int dt) {
     return false;
 }
 
-template <int EPK, int NF, bool L32 = false, int DBG = 0> static hipError_t launch_p4(const GemmParams& p, hipStream_t s) {
+template <int EPK, int NF, bool L32 = false> static hipError_t launch_p4(const GemmParams& p, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};
     int dev_id = 0;
     (void)hipGetDevice(&dev_id);
     const unsigned long long dev_bit = 1ull << (dev_id & 63);
     if (!(attr_done.load(std::memory_order_relaxed) & dev_bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(p4::gemm_p4_kernel<EPK, NF, L32, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, p4::LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(p4::gemm_p4_kernel<EPK, NF, L32>), hipFuncAttributeMaxDynamicSharedMemorySize, p4::LDS);
         attr_done.fetch_or(dev_bit, std::memory_order_relaxed);
     }
     static std::atomic<int> cus_cache[64];
@@ -595,29 +582,18 @@ template <int EPK, int NF, bool L32 = false, int DBG = 0> static hipError_t laun
     }
     const int tiles_m = p.M / p4::BM, tiles_n = p.n_store / p4::BN, ntiles = tiles_m * tiles_n;
     int grid = cus < ntiles ? cus : ntiles;
-    if (const char* e = probe_env("D3R_P4_GRID")) { const int g = atoi(e); if (g >= 8 && g < grid) grid = g; }      // probe: fewer resident blocks (more tiles per block)
     grid &= ~7;                          // XCD-contiguous tile ranges need the grid stride to keep a block on its XCD (v & 7 == blockIdx & 7)
     if (grid < 8) return hipErrorInvalidValue;
-    GemmParams q = p;
-    if (const char* e = probe_env("D3R_P4_PANEL")) { const int v = atoi(e); if (v >= 1 && v <= 64) q.panel = v; }      // probe: width in tiles of the column panels of the tile walk
-    hipLaunchKernelGGL((p4::gemm_p4_kernel<EPK, NF, L32, DBG>), dim3(grid), dim3(p4::NT), p4::LDS, s, q, tiles_m, tiles_n, ntiles);
+    hipLaunchKernelGGL((p4::gemm_p4_kernel<EPK, NF, L32>), dim3(grid), dim3(p4::NT), p4::LDS, s, p, tiles_m, tiles_n, ntiles);
     return hipGetLastError();
 }
 
 hipError_t launch_gemm_p4(const GemmParams& p, hipStream_t s) {
     // Two fragments per K step (16 draining steps) everywhere. The one-fragment form (NF = 1: 32 unrolled step bodies) measured SLOWER on MI355X
     // (typed store 408 vs 436 TFLOP/s, GELU 338 vs ~400 at K = 1024): ~100 KB of straight-line code per tile against a 64 KB instruction cache.
-    // It stays in the template (and in the probe below) but is not instantiated by default.
-    if (p.flags & GF_NOSTORE) return launch_p4<p4::EPK_NONE, 2>(p, s);       // probe: the K loops alone
+    // It stays in the template but is not instantiated.
     if (p.epi == EPI_F32) return p.ln_part ? launch_p4<p4::EPK_X3RES_LN, 2>(p, s) : launch_p4<p4::EPK_X3RES, 2>(p, s);
     if (p.epi == EPI_GELU) return launch_p4<p4::EPK_GELU, 2>(p, s);
-#ifdef D3R_PROBES
-    if (const char* e = probe_env("D3R_P4_DBG")) {       // probe instances (typed store, 32 K steps): results INVALID
-        if ((p.K >> 5) == 32 && e[0] == '0') return launch_p4<p4::EPK_TYPED, 1, true, 0>(p, s);
-        if ((p.K >> 5) == 32 && e[0] == '1') return launch_p4<p4::EPK_TYPED, 1, true, 1>(p, s);
-        if ((p.K >> 5) == 32 && e[0] == '6') return launch_p4<p4::EPK_TYPED, 1, true, 6>(p, s);
-    }
-#endif
     return launch_p4<p4::EPK_TYPED, 2>(p, s);
 }
 

@@ -12,7 +12,10 @@ enum { EPI_T = 0, EPI_F32 = 1, EPI_GELU = 2, EPI_HEADS = 3, EPI_CONVT = 4, EPI_H
 // pts / conf (dpt_head.py:63 + postprocess.py:10-58). Field reuse: out = pts (float*), ldo = its pixel stride, out2 = conf (float*),
 // ldo2 = its pixel stride, res1 = the 1x1 weights [4][n_store] fp32, res2 = its bias [4] fp32. Nothing of the C-channel map is stored.
 enum { HEAD_ROPE = 1, HEAD_VT = 2, HEAD_PLAIN = 3 };
-enum { GF_RELU = 1, GF_NOSTORE = 2, GF_NOWIDE = 4, GF_NTSTORE = 8, GF_X3RES = 16 };   // GF_X3RES (EPI_F32, split-fp16): res1 and the result live in split-fp16 rows only (out2); no fp32 row is stored   // GF_NTSTORE: wide epilogues store with the non-temporal policy (default; D3R_GEMM_NT=0 clears it)
+enum { GF_RELU = 1, GF_NOWIDE = 4, GF_NTSTORE = 8, GF_X3RES = 16 };   // GF_X3RES (EPI_F32, split-fp16): res1 and the result live in split-fp16 rows only (out2); no fp32 row is stored   // GF_NTSTORE: wide epilogues store with the non-temporal policy (set by launch_gemm)
+// tile map of both GEMM kernels: block ids walk column panels GEMM_PANEL tiles wide, row by row
+constexpr int GEMM_PANEL = 8;
+// 4 / 5 / 6 name retired shapes; pinned (D3R_GEMM_CFG, force_cfg) they run configurations 2 / 1 / 1
 enum { GEMM_CFG_128 = 0, GEMM_CFG_256 = 1, GEMM_CFG_256x128 = 2, GEMM_CFG_512x128 = 3, GEMM_CFG_256x128W4 = 4, GEMM_CFG_256S4 = 5, GEMM_CFG_256PP = 6, GEMM_CFG_256x128R = 7, GEMM_CFG_64 = 8, GEMM_CFG_384x192 = 9, GEMM_CFG_P4 = 10, GEMM_CFG_96x64 = 11 };
 
 struct GemmParams {
@@ -41,11 +44,6 @@ struct GemmParams {
     void* head_dst[3] = {nullptr, nullptr, nullptr};
     int heads = 0, ntok = 1, tok_w = 1, ldv = 0;
     const float* rope_table = nullptr;  // [max_pos][16] (cos, sin) pairs
-    // first-round start stagger (set by launch_gemm): blocks with blockIdx < first_round wait stagger_ticks * slot / 32 wall-clock
-    // ticks before they start, so that the epilogue bursts of the resident tiles do not all hit HBM at the same time
-    int stagger_ticks = 0, first_round = 0, stagger_mode = 0;
-    int panel = 8;               // tile map: width of the column panels in tiles (launch_gemm: D3R_GEMM_PANEL probe)
-    int kslice_major = 0;        // implicit-GEMM K order: 0 = (tap, channel), 1 = (channel slice of one K step, tap, channel in slice); set by launch_gemm
     // diagnostics (d3r_gemm_set_trace): 8 x uint64 per block -- wall-clock ticks at entry / K-loop start / K-loop end / epilogue
     // issued / stores drained, then HW_ID, XCC_ID, blockIdx
     unsigned long long* trace = nullptr;
@@ -64,12 +62,10 @@ struct GemmParams {
     // CONSUMER of a small problem: the partial sums [M][K / 32][2] of its input rows; the kernel's prologue then forms ln_rstd / ln_nmr of its tile's rows itself (and WRITES
     // them to those two arrays) with the arithmetic of ln_finalize_kernel, which is not launched
     const float* ln_part_in = nullptr; float ln_eps = 1e-6f, ln_inv_c = 0.f;
-    int x3res_nt = 0;            // GF_X3RES: typed-stream stores with the non-temporal policy (probe D3R_GEMM_X3NT=1; default plain: the rows are re-read at once)
     // ---- split-K for SMALL problems (round 6; split-fp16, nn.Linear operands, the plain K loop): `splitk` blocks share a tile, each over 1 / splitk of the K steps;
     // every block stores its fp32 partial tile in sk_slab ([tile][slice][wave][fragment][lane] float4), the block that draws the last ticket of sk_cnt[tile] adds the
     // slices up in slice order (deterministic whichever block is last) and runs the epilogue. Chosen by launch_gemm when the caller lends it the two buffers.
     int splitk = 1; float* sk_slab = nullptr; unsigned* sk_cnt = nullptr; size_t sk_slab_floats = 0; int sk_cnt_n = 0;
-    int f8_proxy = 0;            // MEASUREMENT AID (D3R_F8_PROXY=1, results INVALID): fp16 + fp8 K loop with the MFMA mix of a 2.5-unit scheme (4 f16 + 1/2 fp8 MFMA per 64 k)
 };
 void gemm_set_trace(unsigned long long* buf, size_t capacity_blocks);
 
@@ -129,10 +125,8 @@ struct PackParams {
     const float* src = nullptr; void* dst = nullptr;
     size_t numel = 0;
     int kind = PACK_MAT, cols = 0, row_off = 0, dst_cols = 0, cin = 0, cin_pad = 0, ksize = 1, cout_pad = 0;
-    int kslice_major = 0;        // PACK_CONV: K order of the packed rows (conv_k_slice_major())
     const float* kscale = nullptr;   // PACK_MAT: multiply column k of the source by kscale[k] before the conversion (LayerNorm gamma folded into the weights)
 };
-bool conv_k_slice_major();       // process-wide K order of implicit-GEMM operands (kernel and weight packing agree on it)
 hipError_t launch_pack_weight(int dt, const PackParams& p, hipStream_t s);
 hipError_t launch_pack_convt_bias(const float* src, float* dst, int cout, int cout_pad, int taps, hipStream_t s);
 

@@ -211,14 +211,11 @@ def layernorm_f8(x, gamma, beta, eps=1e-6):
 
 def pack_conv_weight(w, dtype=None):
     """torch (Cout, Cin, kh, kw) -> (round_up(Cout,256), kh*kw*Cin) in the K order d3r_conv2d_nhwc expects (include/dust3r_hip.h):
-    channel slices of one K step (128 bytes) outermost, then the taps, then the channels of the slice -- or (ky, kx, cin) when the
-    library runs with D3R_CONV_KORDER=0."""
+    channel slices of one K step (128 bytes) outermost, then the taps, then the channels of the slice."""
     Cout, Cin, kh, kw = w.shape
-    if lib.d3r_conv_k_slice_major():
-        S = 128 // torch.empty((), dtype=dtype or w.dtype).element_size()
-        assert Cin % S == 0, f'{Cin=} must be a multiple of {S}'
-        return pad_rows(w.reshape(Cout, Cin // S, S, kh * kw).permute(0, 1, 3, 2).reshape(Cout, -1))
-    return pad_rows(w.permute(0, 2, 3, 1).reshape(Cout, -1))
+    S = 128 // torch.empty((), dtype=dtype or w.dtype).element_size()
+    assert Cin % S == 0, f'{Cin=} must be a multiple of {S}'
+    return pad_rows(w.reshape(Cout, Cin // S, S, kh * kw).permute(0, 1, 3, 2).reshape(Cout, -1))
 
 
 _zero_pages = {}

@@ -86,9 +86,8 @@ int d3r_linear_x3res(const void* act, const void* wgt, const float* bias, void* 
 /* 2-D convolution, NHWC, as implicit GEMM: in [B][Hin][Win][Cin] dtype, wgt [round_up(Cout,256)][k*k*Cin] dtype;
  * out [B][Hout][Wout][Cout] dtype = [relu](conv + bias + res1 + res2)   (DPT head convs, dust3r/heads/dpt_head.py:34-65).
  * K order of a weight row: with S = 128 / sizeof(dtype) channels per K step (Cin % S == 0),
- *   d3r_conv_k_slice_major() == 1 (default): k = (cin / S) * (k*k*S) + (ky*k + kx) * S + cin % S   (all taps of one channel slice
- *                                            back to back: the slice's input lines are re-read from L2, not from HBM)
- *   == 0 (D3R_CONV_KORDER=0, probe)        : k = (ky*k + kx) * Cin + cin.
+ *   k = (cin / S) * (k*k*S) + (ky*k + kx) * S + cin % S   (all taps of one channel slice back to back: the slice's input lines are
+ *   re-read from L2, not from HBM); d3r_conv_k_slice_major() reports this order and always returns 1.
  * zero_page: >= 256 bytes of zeros. */
 int d3r_conv_k_slice_major(void);
 int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bias, void* out, const void* res1, const void* res2,
@@ -106,8 +105,8 @@ int d3r_upsample2x_nhwc(const void* in, void* out, int B, int Hi, int Wi, int C,
  * `buf` (device memory, 8 x uint64 per block: wall-clock ticks at block entry, K-loop start, K-loop end, epilogue issued, stores
  * drained; then HW_ID, XCC_ID, blockIdx). `capacity_blocks` bounds the launches that are traced; buf = NULL switches it off. */
 int d3r_gemm_set_trace(void* buf, size_t capacity_blocks);
-/* Diagnostics, host only: 1 when the library was built with -DD3R_PROBES (`D3R_PROBES=1 python -m dust3r_amd.build`): the ablation kernels and the
- * probe-only D3R_* environment switches of the tools/ probes are compiled in. The default build (0) reads the documented switches only. */
+/* Diagnostics, host only: always 0. There is one build, which reads the documented D3R_* switches only; the probe build
+ * flavour of earlier rounds is removed. Kept for the C ABI. */
 int d3r_build_has_probes(void);
 /* Diagnostics, host only (no device needed): the GEMM tile configuration the engine picks for an nn.Linear-shaped problem (epilogue codes of
  * d3r_linear; with_residual: an fp32 residual row is added). 0 = 128x128 (eight waves below 1100 tiles in split-fp16), 1 = 256x256,
@@ -240,14 +239,12 @@ int d3r_model_debug_read(d3r_model* m, int what, float* out_f32, size_t max_elem
  * Parameter tensors use the reference's own parameterisation and names (state_dict(trainable=True)):
  *   pw_poses [E][8] = quat XYZW, signed-log translation, log scale;  pw_adaptors [E][2] (frozen);
  *   im_poses [n][7];  im_depthmaps [n][max_area] log-depth;  im_focals [n] = focal_break*log(f);  im_pp [n][2] (frozen)
- * They live in caller-owned device memory and are updated IN PLACE; the handle borrows them and the weight
- * tensors until destroy. pred_* [E][max_area][3] and w_* [E][max_area] = conf_trf(conf) (zero in padding), fp32, are read ONCE at create:
+ * They live in caller-owned device memory and are updated IN PLACE; the handle borrows them until destroy. pred_* [E][max_area][3] and w_* [E][max_area] = conf_trf(conf) (zero in padding), fp32, are read ONCE at create:
  * the handle keeps its own block-interleaved copy [side][E][max_area / 256][x | y | z | w][256], so that a wave of the hot loop streams one
- * contiguous 4 KiB run per edge side (environment D3R_ALIGNER_LAYOUT=0 at creation: a planar [E][3][max_area] copy of pred_* and the caller's
- * w_* rows, which are then borrowed until destroy like the parameters). ei/ej/img_h/img_w are HOST arrays. Alignment: pw_poses, im_depthmaps, pred_*, w_* 16 bytes, pw_adaptors 8
- * (D3R_ERR_INVALID otherwise; any torch allocation satisfies it). create enqueues its one-off work (clearing the Adam state, the planar
- * copy of pred_*) on `stream` and does not synchronise the device: pred_* must be complete on that stream, and may be freed once it has
- * drained; run / loss_grad on the same stream need no further ordering, and on ANOTHER stream they first wait for an event the create
+ * contiguous 4 KiB run per edge side. ei/ej/img_h/img_w are HOST arrays. Alignment: pw_poses, im_depthmaps, pred_*, w_* 16 bytes, pw_adaptors 8
+ * (D3R_ERR_INVALID otherwise; any torch allocation satisfies it). create enqueues its one-off work (clearing the Adam state, the interleaved
+ * copy of pred_* / w_*) on `stream` and does not synchronise the device: pred_* and w_* must be complete on that stream, and may be freed once
+ * it has drained; run / loss_grad on the same stream need no further ordering, and on ANOTHER stream they first wait for an event the create
  * call recorded behind its work (no caller-side synchronisation either way).
  */
 typedef struct d3r_aligner d3r_aligner;

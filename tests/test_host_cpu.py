@@ -363,10 +363,9 @@ def test_fp16_fp8_row_layout_on_the_host():
 
 def test_gemm_tile_dispatch_table(monkeypatch):
     """The GEMM tile heuristic as a host function (d3r_gemm_tile_config, no device): the shapes of the BASELINE forward at 32 pairs per
-    step and at one pair per call land on the tile configurations DESIGN.md section 4.1 / 6 report, and the probe variables move them."""
+    step and at one pair per call land on the tile configurations DESIGN.md section 4.1 / 6 report, and D3R_GEMM_CFG pins them."""
     from dust3r_amd._lib import DTYPE_BF16, DTYPE_F16F8, DTYPE_F16X3, lib
-    for v in ('D3R_GEMM_CFG', 'D3R_GEMM_T64', 'D3R_GEMM_T256', 'D3R_GEMM_R', 'D3R_GEMM_MID', 'D3R_GEMM_F32CFG', 'D3R_GEMM_PP', 'D3R_GEMM_T384'):
-        monkeypatch.delenv(v, raising=False)
+    monkeypatch.delenv('D3R_GEMM_CFG', raising=False)
     PLAIN, F32, GELU = 0, 1, 2
     cfg = lambda dt, M, N, K, epi=PLAIN, res=0: lib.d3r_gemm_tile_config(dt, M, N, K, epi, res)   # noqa: E731
     x3 = DTYPE_F16X3
@@ -382,11 +381,6 @@ def test_gemm_tile_dispatch_table(monkeypatch):
     # round 4: the decoder's 24576-row GEMMs whose (M / 384) x (N / 192) tiles fill whole rounds of 256 CUs take the 384 x 192 tile (configuration 9)
     assert cfg(x3, 24576, 768, 3072, F32, 1) == 9 and cfg(x3, 24576, 3072, 768, GELU) == 9 and cfg(x3, 24576, 2304, 768) == 9 and cfg(x3, 24576, 768, 768, F32, 1) == 9
     assert cfg(DTYPE_BF16, 24576, 768, 3072, F32, 1) != 9 and cfg(x3, 24576 - 384 * 20, 768, 3072, F32, 1) != 9      # split-fp16 only; 176 tiles do not fill the chip
-    probes = bool(lib.d3r_build_has_probes())      # the probe-only switches move the table in probe builds only (D3R_PROBES=1 python -m dust3r_amd.build)
-    if probes:
-        monkeypatch.setenv('D3R_GEMM_T384', '0')
-        assert cfg(x3, 24576, 768, 3072, F32, 1) == 0 and cfg(x3, 24576, 3072, 768, GELU) == 1 and cfg(x3, 24576, 768, 768, F32, 1) == 0
-        monkeypatch.delenv('D3R_GEMM_T384')
     assert cfg(x3, 6291456, 128, 1152) == 3 and cfg(x3, 196608, 128, 1152) == 2 and cfg(x3, 1000, 96, 768) == 0   # N <= 128: the head's shapes
     # one pair per call = 1536 encoder rows / 768 decoder rows per side: small problems on the 64 x 64 tile, mid-size ones stay on 128 x 128
     assert cfg(x3, 1536, 1024, 4096, F32, 1) == 8 and cfg(x3, 1536, 1024, 1024, F32, 1) == 8 and cfg(x3, 768, 768, 768, F32, 1) == 8
@@ -400,10 +394,6 @@ def test_gemm_tile_dispatch_table(monkeypatch):
     # fp16 + fp8 rows go to the 256-wide tile from one round of resident blocks on
     assert cfg(DTYPE_F16F8, 24576, 768, 768, F32, 1) == 1
     monkeypatch.delenv('D3R_GEMM_PERSIST')
-    # probes
-    monkeypatch.setenv('D3R_GEMM_T64', '0')
-    assert cfg(x3, 768, 768, 768, F32, 1) == (0 if probes else 8)
-    monkeypatch.delenv('D3R_GEMM_T64')
     monkeypatch.setenv('D3R_GEMM_CFG', '2')
     assert cfg(x3, 49152, 4096, 1024, GELU) == 2
     assert lib.d3r_gemm_tile_config(x3, 0, 8, 8, 0, 0) < 0 or lib.d3r_gemm_tile_config(x3, 0, 8, 8, 0, 0) > 8     # invalid arguments: an error code, not a configuration
@@ -578,10 +568,11 @@ def test_from_pretrained_loads_a_local_hub_snapshot_directory(tmp_path, fmt):
         AsymmetricCroCo3DStereo.from_pretrained(str(tmp_path))
 
 
-def test_persistent_gemm_has_no_scratch():
+def test_persistent_gemm_instances_have_no_scratch():
     """gemm_p4.hip keeps TWO accumulator sets (256 registers) per wave at one wave per SIMD: it only works while hipcc keeps every accumulator in a register --
     one dynamically indexed access, one unrolled loop past the size cap, and the arrays move to scratch (90 instead of 400 TFLOP/s: DESIGN.md 4.1). The build
-    writes hipcc's resource report of the file next to its object (dust3r_amd/build.py): every kernel instance must show no scratch and no spilled VGPR."""
+    writes hipcc's resource report of the file next to its object (dust3r_amd/build.py): the file holds one instance per epilogue kind (typed store, GELU, typed
+    residual stream, the same with LayerNorm sums; two drain fragments per K step), and every one must show no scratch and no spilled VGPR."""
     from dust3r_amd.build import CSRC, build
     rep = os.path.join(CSRC, 'gemm_p4.resources.txt')
     if not os.path.exists(rep) or os.path.getmtime(rep) < os.path.getmtime(os.path.join(CSRC, 'gemm_p4.hip')):
@@ -592,7 +583,9 @@ def test_persistent_gemm_has_no_scratch():
     scratch = [int(x) for x in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', txt)]
     spills = [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', txt)]
     occ = [int(x) for x in re.findall(r'Occupancy \[waves/SIMD\]: (\d+)', txt)]
-    assert len(kernels) >= 5 and len(scratch) == len(kernels) == len(spills)
+    epk = sorted(int(m) for k in kernels for m in re.findall(r'gemm_p4_kernelILi(\d+)ELi2ELb0E', k))
+    assert epk == [0, 1, 2, 3] and len(kernels) == 4, kernels
+    assert len(scratch) == len(kernels) == len(spills)
     assert all(v == 0 for v in scratch) and all(v == 0 for v in spills), list(zip(kernels, scratch, spills))
     assert all(v == 1 for v in occ)          # one wave per SIMD: the whole register file
 

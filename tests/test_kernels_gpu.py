@@ -8,7 +8,6 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import probe_arms
 
 pytestmark = pytest.mark.gpu
 
@@ -66,22 +65,17 @@ def test_linear_epilogues(gpu, dtype, M, N, K):
     assert relerr(out, F.gelu(ref)) < OUT_TOL[dtype], 'gelu epilogue'
 
 
-@pytest.mark.parametrize('sw', probe_arms(['1', '0'], ['0']))
+@pytest.mark.parametrize('sw', ['0'])      # K loop: '0' = the plain loop, the only one the library has (the axis keeps the tests' IDs)
 @pytest.mark.parametrize('cfg', ['0', '0w8', '1', '2', '3', '7', '8', '9', '11'])
 @pytest.mark.parametrize('M,N,K', [(300, 192, 256), (1000, 3072, 1024), (77, 96, 768), (2100, 1032, 32), (515, 328, 64)])
 def test_linear_split_fp16(gpu, M, N, K, cfg, sw, monkeypatch):
     """The parity-grade precision mode (fp16x3: operands split into fp16 hi + lo, three MFMAs per product) at kernel level:
     every tile configuration ('7' = the two-blocks-per-CU 256 x 128 shape with a K step's weight fragments in registers, '8' = the
-    64 x 64 tile of the small-batch forwards), the
-    software-pipelined K loop and the plain two-stage loop, the LDS-staged wide epilogue and the direct stores; K = 32 / 64 are one- and two-step K loops (pipeline prologue / drain only). Reference =
+    64 x 64 tile of the small-batch forwards), the LDS-staged wide epilogue and the direct stores; K = 32 / 64 are one- and two-step K loops (pipeline prologue / drain only). Reference =
     fp32 matmul of the SAME fp32 operands: the split keeps 22 significand bits per operand, so the result is fp32-class."""
     from dust3r_amd import ops
-    from conftest import need_probes
-    if sw == '1':
-        need_probes('the software-pipelined K loop')
-    monkeypatch.setenv('D3R_GEMM_CFG', cfg[:-2] if cfg.endswith(('w8', 'w4')) else cfg)
+    monkeypatch.setenv('D3R_GEMM_CFG', cfg[:-2] if cfg.endswith('w8') else cfg)
     monkeypatch.setenv('D3R_GEMM_T128W8', '1000000' if cfg.endswith('w8') else '0')     # '0w8': the 128 x 128 tile by eight waves (small-batch forwards)
-    monkeypatch.setenv('D3R_GEMM_X3SW', sw)
     g = torch.Generator(device='cpu').manual_seed(M * 7 + N)
     a = torch.randn((M, K), generator=g).to(gpu)
     w = (torch.randn((N, K), generator=g) / math.sqrt(K)).to(gpu)
@@ -100,22 +94,16 @@ def test_linear_split_fp16(gpu, M, N, K, cfg, sw, monkeypatch):
         assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize('grid', probe_arms([None, '8'], [None]))
+@pytest.mark.parametrize('grid', [None])    # resident blocks: None = the default grid, the only one the library has (the axis keeps the tests' IDs)
 @pytest.mark.parametrize('M,N,K', [(2048, 256, 768), (4096, 384, 1024), (2048, 128, 1536), (6144, 256, 576), (16384, 1536, 768)])
 def test_persistent_gemm_is_bit_identical(gpu, M, N, K, grid, monkeypatch):
     """gemm_p4.hip (one block per CU walking its tiles, the epilogue of tile t drained under the K loop of tile t + 1) against the one-tile-per-block
     kernels on the same operands: typed store, GELU, and the typed residual stream with and without a residual and with its LayerNorm partial sums --
     BIT-identical (same MFMA order per element, same epilogue expressions, same summation tree), and within fp32-class error of the fp64 product.
-    K = 576 / 768: 18 / 24 K steps (the shortest loop the kernel takes); 1536: steps behind the draining ones; grid = 8: forty tiles per block (the
-    overlapped path; probe builds), default: one or two (first tile without a drain, last tile drained with nothing to hide under) -- and three per block on
-    the 16384 x 1536 problem (768 tiles on 256 resident blocks: first / overlapped / last tile, the steady state of the 32-pair step, in every build)."""
+    K = 576 / 768: 18 / 24 K steps (the shortest loop the kernel takes); 1536: steps behind the draining ones; one or two tiles per block (first tile
+    without a drain, last tile drained with nothing to hide under) -- and three per block on the 16384 x 1536 problem (768 tiles on 256 resident blocks:
+    first / overlapped / last tile, the steady state of the 32-pair step)."""
     from dust3r_amd import ops
-    from conftest import need_probes
-    if grid:
-        need_probes('D3R_P4_GRID')
-        if M > 8192:
-            pytest.skip('covered by the default grid')
-        monkeypatch.setenv('D3R_P4_GRID', grid)
     g = torch.Generator(device='cpu').manual_seed(M + 3 * N + K)
     a = torch.randn((M, K), generator=g).to(gpu)
     w = (torch.randn((N, K), generator=g) / math.sqrt(K)).to(gpu)
@@ -148,7 +136,7 @@ def test_persistent_gemm_dispatch_rule():
     assert cfg(24576, 768, 768, 0) != 10
 
 
-@pytest.mark.parametrize('cfg', probe_arms(['0', '1', '2', '3', '1w4'], ['0', '1', '2', '3']))
+@pytest.mark.parametrize('cfg', ['0', '1', '2', '3'])
 @pytest.mark.parametrize('M,N,K', [(300, 192, 256), (1000, 3072, 1024), (77, 128, 768), (2100, 1024, 64), (515, 320, 128)])
 def test_linear_fp16_fp8(gpu, M, N, K, cfg, monkeypatch):
     """The fp16 + fp8 operand mode at kernel level (hi.hi on the f16 MFMA, both cross terms on one K-concatenated e4m3 MFMA with an E8M0
@@ -158,12 +146,7 @@ def test_linear_fp16_fp8(gpu, M, N, K, cfg, monkeypatch):
     Activation-row outputs ('store' / 'gelu') are compared after decoding (hi + lo8 2^-11: one output rounding of 2^-15)."""
     from dust3r_amd import ops
     from oracle.f8_ref import f16f8_matmul
-    # '1w4': the two-blocks-per-CU shape of the 256-wide configuration (256 x 128 tile by four waves, 64-byte K steps, three LDS slots)
-    from conftest import need_probes
-    if cfg.endswith('w4'):
-        need_probes('the four-wave 256 x 128 fp16 + fp8 tile')
-    monkeypatch.setenv('D3R_GEMM_CFG', cfg[:-2] if cfg.endswith(('w8', 'w4')) else cfg)
-    monkeypatch.setenv('D3R_GEMM_F8W4', '1' if cfg.endswith('w4') else '0')
+    monkeypatch.setenv('D3R_GEMM_CFG', cfg)
     g = torch.Generator(device='cpu').manual_seed(M * 7 + N)
     a = torch.randn((M, K), generator=g).to(gpu)
     w = (torch.randn((N, K), generator=g) / math.sqrt(K)).to(gpu)
@@ -278,7 +261,7 @@ def test_conv2d_nhwc(gpu, dtype, B, H, W, Cin, Cout, k, stride, pad):
     assert relerr(out, (ref - b).clamp_min(0)) < OUT_TOL[dtype]
 
 
-@pytest.mark.parametrize('cfg', probe_arms(['0', '1', '2', '3', '4', '5', '6'], ['0', '1', '2', '3']))     # 4-6: probe-only tile shapes (W4, four-stage, ping-pong)
+@pytest.mark.parametrize('cfg', ['0', '1', '2', '3'])
 def test_gemm_tile_configurations(gpu, cfg, monkeypatch):
     """Every tile configuration of the GEMM template (128x128, 256x256, 256x128) on shapes with ragged M / N edges,
     K long enough to cycle both LDS stages many times, linear and implicit-GEMM convolution operands."""
@@ -343,7 +326,7 @@ def test_attention(gpu, dtype, B, H, Nq, Nk):
     assert relerr(out, ref) < tol
 
 
-@pytest.mark.parametrize('v1', probe_arms(['0', '1', 'dma', 'reg', 'pk', 'lz'], ['0', '1', 'dma', 'reg']))
+@pytest.mark.parametrize('v1', ['0', '1', 'dma', 'reg'])
 @pytest.mark.parametrize('B,H,Nq,Nk', [(2, 3, 196, 196), (1, 2, 768, 768), (2, 1, 6, 6), (1, 4, 130, 70), (1, 1, 768, 196), (1, 2, 40, 129), (1, 1, 300, 64), (1, 1, 64, 128)])
 def test_attention_split_fp16(gpu, v1, B, H, Nq, Nk, monkeypatch):
     """The split-fp16 attention of the default engine at kernel level, every kernel (D3R_ATTN_V1=1: the round-2 kernel; the
@@ -352,16 +335,9 @@ def test_attention_split_fp16(gpu, v1, B, H, Nq, Nk, monkeypatch):
     keep 22 significand bits and the probabilities are split too, so the result is fp32-class (3e-5 like the exact-fp32 kernel); 1 to 12
     key tiles, ragged last tiles, query blocks with idle lanes. A subprocess-free switch: the choice is read on every launch."""
     from dust3r_amd import ops
-    from conftest import need_probes
-    if v1 in ('pk', 'lz'):
-        need_probes('the packed-softmax / lazy-maximum attention instances')
     monkeypatch.setenv('D3R_ATTN_V1', '1' if v1 == '1' else '0')
     if v1 in ('dma', 'reg'):
         monkeypatch.setenv('D3R_ATTN_DMA', '1' if v1 == 'dma' else '0')
-    if v1 == 'pk':            # the softmax / split slices on packed fp32 VALU (rounds 3-4; round 5's default is the scalar form, DMA staging)
-        monkeypatch.setenv('D3R_ATTN_DMA', '1')
-        monkeypatch.setenv('D3R_ATTN_SC', '0')
-    monkeypatch.setenv('D3R_ATTN_LAZY', '1' if v1 == 'lz' else '0')     # lazy running maximum (round 5): the exponents' reference moves only by more than six octaves
     g = torch.Generator(device='cpu').manual_seed(Nq * 5 + Nk)
     q = (torch.randn((B, H, Nq, 64), generator=g) * 1.5).to(gpu)
     k = (torch.randn((B, H, Nk, 64), generator=g) * 1.5).to(gpu)
@@ -374,16 +350,12 @@ def test_attention_split_fp16(gpu, v1, B, H, Nq, Nk, monkeypatch):
     assert err < 3e-5
 
 
-@pytest.mark.parametrize('dma', probe_arms(['0', '1', 'lazy'], ['0', '1']))
+@pytest.mark.parametrize('dma', ['0', '1'])
 def test_attention_split_fp16_sharp_rows_and_late_maximum(gpu, dma, monkeypatch):
     """Running-maximum rescale of the pipelined kernel: one key dominating by a huge margin in a LATE tile (alpha = 0 there), and rows
     whose maximum moves in every tile."""
     from dust3r_amd import ops
-    from conftest import need_probes
-    if dma == 'lazy':
-        need_probes('the lazy-maximum attention instance')
-    monkeypatch.setenv('D3R_ATTN_DMA', '1' if dma == 'lazy' else dma)
-    monkeypatch.setenv('D3R_ATTN_LAZY', '1' if dma == 'lazy' else '0')     # head 1's maximum creeps up by 0.16 octaves per key: the lazy reference moves every ~38 keys only
+    monkeypatch.setenv('D3R_ATTN_DMA', dma)
     B, H, N = 1, 2, 320
     q = torch.zeros((B, H, N, 64), device=gpu)
     k = torch.zeros((B, H, N, 64), device=gpu)
@@ -407,11 +379,9 @@ def test_attention_split_fp16_dma_staging_is_bit_identical(gpu, monkeypatch):
         k = (torch.randn((B, H, Nk, 64), generator=g) * 1.5).to(gpu)
         v = torch.randn((B, H, Nk, 64), generator=g).to(gpu)
         outs = []
-        from conftest import probes_built
-        # register staging (packed softmax slices), [probe builds: DMA staging + packed slices,] DMA staging + scalar-VALU softmax slices (round 5, the default)
-        for dma, sc in ((('0', '0'), ('1', '0'), ('1', '1')) if probes_built() else (('0', '0'), ('1', '1'), ('1', '1'))):
+        # register staging (packed softmax slices), then DMA staging + scalar-VALU softmax slices (round 5, the default) twice
+        for dma in ('0', '1', '1'):
             monkeypatch.setenv('D3R_ATTN_DMA', dma)
-            monkeypatch.setenv('D3R_ATTN_SC', sc)
             outs.append(ops.attention_x3(q, k, v, scale=0.125).clone())
         assert torch.equal(outs[0], outs[1]), (B, H, Nq, Nk, float((outs[0] - outs[1]).abs().max()))
         assert torch.equal(outs[1], outs[2]), ('scalar VALU', B, H, Nq, Nk, float((outs[1] - outs[2]).abs().max()))

@@ -27,7 +27,7 @@ def timeit(fn, warm=3, reps=10):
 
 def gemm_probe():
     import os
-    print('== GEMM: ms and TFLOP/s per tile configuration (D3R_GEMM_CFG: 0 = 128x128, 1 = 256x256, 2 = 256x128, 3 = 512x128, 4 = 256x128 4-wave 2 blocks/CU, 5 = 256x256 4-stage, 6 = 256x256 ping-pong, auto = heuristic)')
+    print('== GEMM: ms and TFLOP/s per tile configuration (D3R_GEMM_CFG: 0 = 128x128, 1 = 256x256, 2 = 256x128, 3 = 512x128, auto = heuristic)')
     from dust3r_amd._lib import lib, ptr, current_stream, check
     shapes = [(49152, 3072, 1024), (49152, 1024, 1024), (49152, 4096, 1024), (49152, 1024, 4096), (24576, 2304, 768), (24576, 768, 768),
               (24576, 3072, 768), (24576, 768, 3072), (4096, 4096, 4096), (8192, 8192, 8192)]
@@ -43,7 +43,7 @@ def gemm_probe():
             def run():
                 check(lib.d3r_linear(ptr(a), ptr(w), ptr(b), ptr(out), None, M, N, K, 0, ops._dt(a), current_stream()))
             line = f'  M={M} N={N} K={K} {str(dt)[6:]:9s}'
-            for cfg in (('0', '1', '5', '6', None) if dt == torch.bfloat16 else (None,)):
+            for cfg in (('0', '1', None) if dt == torch.bfloat16 else (None,)):
                 if cfg is None:
                     os.environ.pop('D3R_GEMM_CFG', None)
                 else:
@@ -52,10 +52,6 @@ def gemm_probe():
                 line += f' | cfg {cfg or "auto"}: {ms:7.3f} ms {2 * M * N * K / ms / 1e9:7.1f} TF/s'
             os.environ.pop('D3R_GEMM_CFG', None)
             if dt == torch.bfloat16:
-                os.environ['D3R_GEMM_NOSTORE'] = '1'     # same launch without the epilogue's memory traffic
-                ms = timeit(run)
-                os.environ.pop('D3R_GEMM_NOSTORE', None)
-                line += f' | auto/no-store: {ms:7.3f} ms {2 * M * N * K / ms / 1e9:7.1f} TF/s'
                 os.environ['D3R_GEMM_NOWIDE'] = '1'      # A/B: direct fragment stores instead of the LDS-staged wide rows
                 ms = timeit(run)
                 os.environ.pop('D3R_GEMM_NOWIDE', None)
@@ -137,16 +133,10 @@ def gemmtrace_probe():
             traced('cfg 7: 256x128, weights in registers, 2 blocks / CU')
             os.environ.pop('D3R_GEMM_CFG')
         if os.environ.get('D3R_PROBE_EXTRA', '1') == '1':
-            os.environ['D3R_GEMM_NOSTORE'] = '1'
-            traced('same, epilogue skipped (D3R_GEMM_NOSTORE)')
-            os.environ.pop('D3R_GEMM_NOSTORE')
             a.zero_()
             traced('activation operand all zero (data-dependent MFMA power)')
             if not f8:
                 a.copy_(ops.pack_x3(torch.randn((M, K), device=dev)))
-            os.environ['D3R_GEMM_STAGGER'] = '1.0'
-            traced('first-round stagger 1.0')
-            os.environ.pop('D3R_GEMM_STAGGER')
         del a, w, out, buf
 
 
@@ -203,39 +193,6 @@ def attndma_probe():
             ms = timeit(lambda: check(lib.d3r_attention(ptr(qp), ptr(kp), ptr(vp), ptr(out), b, h, N, N, N, 0.125, _lib.DTYPE_F16X3, current_stream()), 'attention'), warm=3, reps=20)
             print(f'  D3R_ATTN_DMA={dma} B={b} H={h}: {ms * 1e3:8.1f} us  {4 * b * h * N * N * 64 / ms / 1e9:7.1f} TF/s', flush=True)
     os.environ.pop('D3R_ATTN_DMA')
-
-
-def attnparts_probe():
-    """The split-fp16 attention kernel with parts of its instruction stream removed (D3R_ATTN_PROBE bit mask: 1 no softmax / split VALU,
-    2 no MFMAs, 4 no per-tile barrier, 8 no staging of the next tiles; results invalid): what each part costs next to the others."""
-    import os
-    from dust3r_amd import _lib
-    from dust3r_amd._lib import lib
-    from dust3r_amd.ops import check, current_stream, pack_x3, ptr
-    B, H, N = 64, 16, 768
-    q, k = torch.randn((B, H, N, 64), device=dev), torch.randn((B, H, N, 64), device=dev)
-    vt = torch.randn((B, H, 64, N), device=dev)
-    qp, kp, vp = pack_x3(q), pack_x3(k), pack_x3(vt)
-    out = torch.empty((B, N, H * 64 * 2), dtype=torch.float16, device=dev)
-    fl = 4 * B * H * N * N * 64
-    print(f'== split-fp16 attention, B={B} H={H} N={N}: ablation (D3R_ATTN_PROBE)')
-    names = {0: 'full kernel', 1: 'no VALU', 2: 'no MFMA', 4: 'no barrier', 8: 'no staging', 12: 'no barrier, no staging', 13: 'MFMA + fragment reads only',
-             14: 'VALU only', 16: 'no LDS writes of the staging', 32: 'no global loads of the staging'}
-    for probe, name in names.items():
-        os.environ['D3R_ATTN_PROBE'] = str(probe)
-        ms = timeit(lambda: check(lib.d3r_attention(ptr(qp), ptr(kp), ptr(vp), ptr(out), B, H, N, N, N, 0.125, _lib.DTYPE_F16X3, current_stream()), 'attention'), warm=3, reps=20)
-        print(f'  probe {probe:2d} {name:28s} {ms * 1e3:8.1f} us  {fl / ms / 1e9:7.1f} TF/s-equivalent', flush=True)
-    os.environ.pop('D3R_ATTN_PROBE')
-    for nw in ('4', '8', '4', '8'):         # 128 vs 256 queries per workgroup
-        os.environ['D3R_ATTN_NW'] = nw
-        for (b, h) in ((64, 16), (32, 12)):
-            q, k = torch.randn((b, h, N, 64), device=dev) * 0.5, torch.randn((b, h, N, 64), device=dev) * 0.5
-            vt = torch.randn((b, h, 64, N), device=dev)
-            qp, kp, vp = pack_x3(q), pack_x3(k), pack_x3(vt)
-            out = torch.empty((b, N, h * 64 * 2), dtype=torch.float16, device=dev)
-            ms = timeit(lambda: check(lib.d3r_attention(ptr(qp), ptr(kp), ptr(vp), ptr(out), b, h, N, N, N, 0.125, _lib.DTYPE_F16X3, current_stream()), 'attention'), warm=3, reps=20)
-            print(f'  D3R_ATTN_NW={nw} B={b} H={h}: {ms * 1e3:8.1f} us  {4 * b * h * N * N * 64 / ms / 1e9:7.1f} TF/s', flush=True)
-    os.environ.pop('D3R_ATTN_NW')
 
 
 def forward_probe():
@@ -322,14 +279,13 @@ def aligner_probe():
 
 
 def tune_probe():
-    """A/B switches measured on the whole forward (B = 32, bf16, two-stream, as bench.py times it) and on isolated GEMMs with the
-    network's epilogues (bf16 out / fp32 residual stream): D3R_GEMM_NT=0 (plain instead of non-temporal epilogue stores),
-    D3R_GEMM_T256 (256x256 / 128x128 crossover, default 700 tiles)."""
+    """Isolated GEMMs with the network's epilogues (bf16 out / fp32 residual stream) per pinned tile, and the whole forward (B = 32, bf16,
+    as bench.py times it) on two streams and on one."""
     import os
     from dust3r_amd._lib import lib, ptr, current_stream, check
     from dust3r_amd.model import AsymmetricCroCo3DStereo
     from dust3r_amd.synthetic import MODEL_CONFIGS, OUT_GAIN, synthetic_state_dict, synthetic_views
-    print('== tune: isolated GEMMs (TF/s): bf16 store | fp32 out + fp32 residual (the residual-stream epilogue) | GELU; nt on / off')
+    print('== tune: isolated GEMMs (TF/s): bf16 store | fp32 out + fp32 residual (the residual-stream epilogue) | GELU')
     for (M, N, K) in ((49152, 1024, 1024), (49152, 1024, 4096), (24576, 768, 768), (24576, 768, 3072)):
         a = torch.randn((M, K), device=dev).to(torch.bfloat16)
         w = ops.pad_rows((torch.randn((N, K), device=dev) / math.sqrt(K)).to(torch.bfloat16))
@@ -340,7 +296,7 @@ def tune_probe():
         for name, epi, o, r in (('store', 0, out16, None), ('f32+res', 1, out32, out32), ('gelu', 2, out16, None)):
             def run():
                 check(lib.d3r_linear(ptr(a), ptr(w), ptr(b), ptr(o), ptr(r), M, N, K, epi, ops._dt(a), current_stream()))
-            for c in ((None, '0', '2', '4') if epi == 1 else (None,)):
+            for c in ((None, '0', '2') if epi == 1 else (None,)):
                 if c is None:
                     os.environ.pop('D3R_GEMM_CFG', None)
                 else:
@@ -355,15 +311,8 @@ def tune_probe():
     m.to(dev)
     v1, v2 = synthetic_views(32, 384, 512, seed=0, device=dev)
     print('== tune: forward B=32 bf16 (two streams)')
-    variants = [('default', {}), ('f32 epilogue K<=1024 on 128x128', {'D3R_GEMM_F32CFG': '0'}), ('f32 epilogue K<=1024 on 256x128', {'D3R_GEMM_F32CFG': '2'}),
-                ('f32 epilogue K<=1024 on 256x128 w4', {'D3R_GEMM_F32CFG': '4'}), ('T256=250', {'D3R_GEMM_T256': '250'}), ('default again', {})]
-    for name, env in variants:
-        for k, v in env.items():
-            os.environ[k] = v
-        ms = timeit(lambda: m(v1, v2), warm=2, reps=4)
-        for k in env:
-            os.environ.pop(k, None)
-        print(f'  {name:26s}: {ms:8.2f} ms/forward  {32 / ms * 1e3:7.2f} pairs/s')
+    ms = timeit(lambda: m(v1, v2), warm=2, reps=4)
+    print(f'  {"two streams":26s}: {ms:8.2f} ms/forward  {32 / ms * 1e3:7.2f} pairs/s')
     m.set_two_streams(False)
     ms = timeit(lambda: m(v1, v2), warm=2, reps=4)
     print(f'  {"single stream":26s}: {ms:8.2f} ms/forward  {32 / ms * 1e3:7.2f} pairs/s')
@@ -374,7 +323,7 @@ if __name__ == '__main__':
     print(torch.cuda.get_device_name(0))
     for w in which:
         try:
-            {'gemm': gemm_probe, 'gemmtrace': gemmtrace_probe, 'tune': tune_probe, 'cache': cache_probe, 'conv': conv_probe, 'attn': attn_probe, 'attnparts': attnparts_probe, 'attndma': attndma_probe, 'forward': forward_probe, 'aligner': aligner_probe}[w]()
+            {'gemm': gemm_probe, 'gemmtrace': gemmtrace_probe, 'tune': tune_probe, 'cache': cache_probe, 'conv': conv_probe, 'attn': attn_probe, 'attndma': attndma_probe, 'forward': forward_probe, 'aligner': aligner_probe}[w]()
         except Exception as e:  # keep going: this is a probe
             import traceback
             traceback.print_exc()

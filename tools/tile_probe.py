@@ -1,6 +1,5 @@
-"""On-GPU probe (not a test): split-fp16 GEMMs of the 32-pair step, per tile configuration, with and without their epilogue.
-What a tile shape's K loop delivers alone (D3R_GEMM_NOSTORE, probe builds only) against what the launch delivers with its epilogue is the
-room an overlapped epilogue has on that shape. Usage: python tools/tile_probe.py [cfgs, e.g. a,1,2,7,p]   (a = heuristic, p = persistent)"""
+"""On-GPU probe (not a test): split-fp16 GEMMs of the 32-pair step, per tile configuration; the persistent kernel's outputs are checked
+bit for bit against the one-tile-per-block kernels. Usage: python tools/tile_probe.py [cfgs, e.g. a,1,2,7,p]   (a = heuristic, p = persistent)"""
 import math
 import os
 import sys
@@ -39,8 +38,7 @@ if os.environ.get('D3R_PROBE_SHAPES'):
 
 def main():
     cfgs = (sys.argv[1].split(',') if len(sys.argv) > 1 else ['a', '1', '2', '7'])
-    nostore = os.environ.get('D3R_PROBE_NOSTORE', '1') == '1'
-    print('== split-fp16 GEMM: ms / TFLOP/s per tile configuration; "ns" = the same launch without its epilogue (probe builds)')
+    print('== split-fp16 GEMM: ms / TFLOP/s per tile configuration')
     for (M, N, K, epi, name) in SHAPES:
         a = ops.pack_x3(torch.randn((M, K), device=dev))
         w = ops.pad_rows(ops.pack_x3(torch.randn((N, K), device=dev) / math.sqrt(K)))
@@ -89,11 +87,6 @@ def main():
                         cell += f' DIFF {int(bad.sum())} of {bad.numel()} halves, max {float((o.float() - ref[0].float()).abs().max()):.3e}'
                         if op is not None:
                             cell += f', sums {int((op != ref[1]).sum())} differ'
-                if nostore:
-                    os.environ['D3R_GEMM_NOSTORE'] = '1'
-                    ms2 = timeit(run)
-                    os.environ.pop('D3R_GEMM_NOSTORE')
-                    cell += f' (ns {ms2:6.3f} {2 * M * N * K / ms2 / 1e9:6.1f})'
                 cells.append(cell)
             os.environ.pop('D3R_GEMM_CFG', None)
             os.environ.pop('D3R_GEMM_PERSIST', None)
