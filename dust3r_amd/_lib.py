@@ -75,6 +75,7 @@ def _load():
                                    i, i, i, i, i, vp]),
         'd3r_aligner_destroy': (i, [vp]),
         'd3r_aligner_set_option': (i, [vp, i, i]),
+        'd3r_aligner_set_trainable': (i, [vp, i, C.c_char_p]),
         'd3r_aligner_run': (i, [vp, i, i, i, f, f, i, fp, vp]),
         'd3r_aligner_loss_grad': (i, [vp, fp, fp, fp, fp, fp, fp, fp, vp]),
         'd3r_aligner_set_image_range': (i, [vp, i, i]),

@@ -14,7 +14,8 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-res
 # attention.hip: no SLP vectorisation -- its scalar-VALU softmax slices (attention_x3_kernel<..., SC = true>) must stay v_fma_f32 / v_add_f32
 # pairs; hipcc -O3 re-packs adjacent scalar fp32 operations into v_pk_* (an anti-lever beside MFMAs, MI355X_MICROARCH.md). The packed
 # variants of the same kernel use explicit 2-vectors and are not affected.
-EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'gemm_p4.hip': ['-fno-slp-vectorize', '-Rpass-analysis=kernel-resource-usage']}     # gemm_p4.hip: its drain's scalar GELU pieces sit between MFMAs too
+EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'gemm_p4.hip': ['-fno-slp-vectorize', '-Rpass-analysis=kernel-resource-usage'],     # gemm_p4.hip: its drain's scalar GELU pieces sit between MFMAs too
+               'aligner.hip': ['-Rpass-analysis=kernel-resource-usage']}      # aligner.hip: its report pins the registers / scratch of every aligner kernel (tests read it)
 
 
 def _hipcc():

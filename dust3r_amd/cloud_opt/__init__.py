@@ -5,6 +5,7 @@ from enum import Enum
 import torch
 
 from ..utils.device import upload_rows
+from .modular_optimizer import ModularPointCloudOptimizer
 from .optimizer import PointCloudOptimizer
 from .pair_viewer import PairViewer
 
@@ -15,15 +16,13 @@ class GlobalAlignerMode(Enum):
     PairViewer = "PairViewer"
 
 
-_SCENES = {GlobalAlignerMode.PointCloudOptimizer: PointCloudOptimizer, GlobalAlignerMode.PairViewer: PairViewer}
+_SCENES = {GlobalAlignerMode.PointCloudOptimizer: PointCloudOptimizer, GlobalAlignerMode.ModularPointCloudOptimizer: ModularPointCloudOptimizer,
+           GlobalAlignerMode.PairViewer: PairViewer}
 
 
 def global_aligner(dust3r_output, device, mode=GlobalAlignerMode.PointCloudOptimizer, **optim_kw):
     from ..utils.device import fit_host_threads_once
     fit_host_threads_once()
-    if mode == GlobalAlignerMode.ModularPointCloudOptimizer:
-        raise NotImplementedError('ModularPointCloudOptimizer (the slow per-edge variant, unused by the demo) is out of scope: '
-                                  'use GlobalAlignerMode.PointCloudOptimizer')
     if mode not in _SCENES:
         raise NotImplementedError(f'Unknown mode {mode}')
     inputs = [dust3r_output[k] for k in ('view1', 'view2', 'pred1', 'pred2')]

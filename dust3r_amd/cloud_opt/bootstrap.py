@@ -498,14 +498,33 @@ def bootstrap_from_spanning_tree(scene, niter_PnP=10, maps=None):
     _commit(scene, maps, plan.anchor, G, S, pw_job, focals, poses)
 
 
+def _image_group(scene, name):
+    """(values (n, ...), per-image trainable mask) of the image parameter group `name`: PointCloudOptimizer's one tensor (trainable as a
+    whole), or ModularPointCloudOptimizer's flat storage under its per-image parameters (each trainable on its own)."""
+    flat = getattr(scene, '_flat_' + name, None)
+    if flat is None:
+        t = getattr(scene, name)
+        return t.data, np.array([t.requires_grad] * scene.n_imgs)
+    return flat, np.array([p.requires_grad for p in getattr(scene, name)], dtype=bool)
+
+
+def _write_rows(dst, src, mask):
+    """dst[k] = src[k] for the trainable images k only (the reference's `_set_*` without force)."""
+    if mask.all():
+        dst.copy_(src)
+    elif mask.any():
+        idx = torch.from_numpy(np.nonzero(mask)[0]).to(dst.device)
+        dst[idx] = src[idx]
+
+
 def _commit(scene, maps, anchor, G, S, pw_job, focals, poses):
     """World clouds (anchor, G), pairwise registrations and per-image focals / poses -> the aligner's parameters
-    (init_im_poses.py:83-123)."""
+    (init_im_poses.py:83-123). Only trainable images are written (a preset pose / focal stays as it was)."""
     n, edges = scene.n_imgs, scene.edges
     has_poses = scene.has_im_poses
     poses = None if not has_poses else np.stack(poses)
     if has_poses:
-        known = np.array([not scene.im_poses.requires_grad] * n)
+        known = ~_image_group(scene, 'im_poses')[1]
         nkp = int(known.sum())
         if nkp == 1:
             raise NotImplementedError('Would be simpler to just align everything afterwards on the single known pose')
@@ -525,18 +544,22 @@ def _commit(scene, maps, anchor, G, S, pw_job, focals, poses):
     if not has_poses:
         return
     poses[:, :3, 3] *= s_factor
-    if scene.im_depthmaps.requires_grad:
+    depth, trainable = _image_group(scene, 'im_depthmaps')
+    if trainable.any():
         rows = [(np.linalg.inv(poses[k]) @ G[k])[2] for k in range(n)]
-        maps.anchor_depth([anchor[k] for k in range(n)], rows, scene.im_depthmaps.data)
-    if scene.im_poses.requires_grad:
-        scene.im_poses.data.copy_(torch.from_numpy(pose_params_batch(poses, False).astype(np.float32)).to(scene.im_poses.device))
-    if scene.im_focals.requires_grad:
-        vals = scene.im_focals.data.clone()
+        out = depth if trainable.all() else depth.clone()
+        maps.anchor_depth([anchor[k] for k in range(n)], rows, out)
+        _write_rows(depth, out, trainable)
+    im_poses, trainable = _image_group(scene, 'im_poses')
+    _write_rows(im_poses, torch.from_numpy(pose_params_batch(poses, False).astype(np.float32)).to(im_poses.device), trainable)
+    im_focals, trainable = _image_group(scene, 'im_focals')
+    if trainable.any():
+        vals = im_focals.clone()
         for k, f in enumerate(focals):
             if f is not None:
                 with np.errstate(divide='ignore', invalid='ignore'):     # a degenerate focal gives -inf / nan like the reference's np.log, not an exception
-                    vals[k] = scene.focal_break * float(np.log(np.float64(f)))
-        scene.im_focals.data.copy_(vals)
+                    vals[k] = scene.focal_break * float(np.log(np.float64(f)))      # fx and fy alike (fx_and_fy)
+        _write_rows(im_focals, vals, trainable)
     if scene.verbose:
         print(' init loss =', float(scene()))
 

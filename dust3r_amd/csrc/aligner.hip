@@ -38,12 +38,13 @@ struct AlignerView {
     float* depth_v;
     float* depth_grad;      // optional export (tests)
     const float* d_edge;    // derived [E][12]  M_e
-    const float* d_img;     // derived [n][16]  R(9) T(3) F ppx ppy -
+    const float* d_img;     // derived [n][16]  R(9) T(3) F ppx ppy Fy (Fy: the Modular scene only, 0 otherwise)
     float* part_edge;       // [2E][nslot][16]: gm(12) loss(1)
     float* part_img;        // [n][nslot][16]:  G = sum g (x) cam (9), sum g (3), sum g*exp(d) (3)
     float inv_area[2];
     int l2, update, use_dpp;
     AdamCoef adam;
+    int edge_mean;          // MODULAR: the per-edge-mean loss of BasePCOptimizer.forward (weight 1 / (E area(img))) instead of 1 / total side area
 };
 
 // ---- wave reduction: result valid in lane 63 -------------------------------------------------------
@@ -97,7 +98,10 @@ D3R_DEV float4 stream_ld4(const float* p) {
 // [side][edge][256-pixel chunk][x | y | z | w][256] (round 5): a wave reads ONE contiguous 4 KiB run per edge side, a workgroup 16 KiB (rounds 1-4 read
 // four separate streams per edge side -- x, y, z planes and the caller's weight rows -- a wave four 1 KiB runs megabytes apart).
 constexpr int ALIGNER_NWV = 4;
-template <bool L2>
+// MODULAR: the ModularPointCloudOptimizer scene (reference modular_optimizer.py): a y focal of its own (d_img slot 15) and, with edge_mean, the
+// per-edge-mean weighting of base_opt.py:246-273 -- both uniform per workgroup. A template parameter, not a per-pixel branch: this kernel is
+// VALU-bound, and the PointCloudOptimizer instantiations (MODULAR = false) compile to the code they always had.
+template <bool L2, bool MODULAR>
 __global__ __launch_bounds__(ALIGNER_NWV * 64) void aligner_main_kernel(AlignerView a) {
     constexpr int NWV = ALIGNER_NWV, NTH = NWV * 64, CHUNK_T = NTH * PPT;
     const int nchunk = a.nslot;
@@ -114,6 +118,9 @@ __global__ __launch_bounds__(ALIGNER_NWV * 64) void aligner_main_kernel(AlignerV
     for (int k = 0; k < 9; ++k) R[k] = di[k];
     const float T0 = di[9], T1 = di[10], T2 = di[11], F = di[12], ppx = di[13], ppy = di[14];
     const float invF = 1.0f / F;
+    const float invFy = MODULAR ? 1.0f / di[15] : invF;
+    // loss = (1/E) sum_e [mean over image i of w d + mean over image j]: every edge side projected onto `img` weighs 1 / (E area(img))
+    const float w_img = MODULAR ? (float)(1.0 / ((double)a.E * (double)area)) : 0.f;
 
     float X[PPT][3], cam[PPT][3], g[PPT][3], ed[PPT];
     float4 dlog = make_float4(0, 0, 0, 0);
@@ -126,7 +133,7 @@ __global__ __launch_bounds__(ALIGNER_NWV * 64) void aligner_main_kernel(AlignerV
         const int v = p < area ? p / W : 0, u = p < area ? p - v * W : 0;
         ed[k] = expf(dl[k]);
         cam[k][0] = ed[k] * ((float)u - ppx) * invF;
-        cam[k][1] = ed[k] * ((float)v - ppy) * invF;
+        cam[k][1] = ed[k] * ((float)v - ppy) * invFy;
         cam[k][2] = ed[k];
         X[k][0] = R[0] * cam[k][0] + R[1] * cam[k][1] + R[2] * cam[k][2] + T0;
         X[k][1] = R[3] * cam[k][0] + R[4] * cam[k][1] + R[5] * cam[k][2] + T1;
@@ -185,7 +192,7 @@ __global__ __launch_bounds__(ALIGNER_NWV * 64) void aligner_main_kernel(AlignerV
             for (int k = 0; k < 12; ++k) gm[k] = 0.f;
             {
                 const float pr[PPT][3] = {{q0.x, q1.x, q2.x}, {q0.y, q1.y, q2.y}, {q0.z, q1.z, q2.z}, {q0.w, q1.w, q2.w}};   // q0 = x, q1 = y, q2 = z planes
-                const float ia = active ? a.inv_area[side] : 0.f;   // zero weight: inactive lanes contribute nothing
+                const float ia = active ? ((MODULAR && a.edge_mean) ? w_img : a.inv_area[side]) : 0.f;   // zero weight: inactive lanes contribute nothing
                 const float wv[PPT] = {ww.x * ia, ww.y * ia, ww.z * ia, ww.w * ia};
 #pragma unroll
                 for (int k = 0; k < PPT; ++k) residual_accumulate(X[k], M, pr[k], wv[k], L2, loss, g[k], gm);
@@ -325,7 +332,74 @@ struct SmallView {
     float base_scale, pw_break, focal_break;
     int norm_pw_scale, opt_poses, opt_focals, opt_pp, opt_adapt, update;
     AdamCoef adam;
+    // the Modular scene (MOD kernels only): per-image trainability of poses / focals / principal points ([n] each, null: every image) and
+    // nfoc = 1 or 2 (fx_and_fy) focal parameters per image: im_focals, foc_m, foc_v, g_foc are [n][nfoc]
+    const unsigned char* tr_pose; const unsigned char* tr_foc; const unsigned char* tr_pp;
+    int nfoc;
 };
+
+// ---- the Modular scene's image step (reference modular_optimizer.py) ---------------------------------------------------------------
+// Q, fo (nfoc focal parameters; fo[1] = fo[0] when nfoc == 1), pp0 / pp1: the values the main pass took its gradients at, updated in place
+// (and stored) where trainable. A frozen entry is skipped whole -- no update, its moments stay zero -- which is torch.optim.Adam without that
+// parameter (`_no_grad` takes it out of the optimiser). Gradients are exported for every image.
+D3R_DEV void modular_image_step(const SmallView& s, int i, float (&Q)[7], float (&fo)[2], float& pp0, float& pp1, const double (&RI)[15]) {
+    float R[9];
+    quat_to_rotmat(Q, R);
+    double gQ[7], gf[2];
+    image_chain(Q, R, s.focal_break, RI, RI + 9, gQ, gf[0]);
+    if (s.nfoc == 2) focal_xy_grads(R, s.focal_break, RI, gf[0], gf[1]);
+    const bool tp = s.opt_poses && (!s.tr_pose || s.tr_pose[i]);
+    const bool tf = s.opt_focals && (!s.tr_foc || s.tr_foc[i]);
+    const bool tpp = s.opt_pp && (!s.tr_pp || s.tr_pp[i]);
+    if (s.g_imp)
+        for (int k = 0; k < 7; ++k) s.g_imp[i * 7 + k] = (float)gQ[k];
+    if (s.g_foc)
+        for (int k = 0; k < s.nfoc; ++k) s.g_foc[i * s.nfoc + k] = (float)gf[k];
+    if (s.g_pp || (s.update && tpp)) {
+        // pp = (W/2, H/2) + 10 im_pp: dL/d im_pp = -(10 / Fx) (R^T S)_0, -(10 / Fy) (R^T S)_1 at the focals the gradients were taken at
+        const double Fx = exp((double)fo[0] / (double)s.focal_break), Fy = exp((double)fo[1] / (double)s.focal_break);
+        const double gx = -(10.0 / Fx) * ((double)R[0] * RI[12] + (double)R[3] * RI[13] + (double)R[6] * RI[14]);
+        const double gy = -(10.0 / Fy) * ((double)R[1] * RI[12] + (double)R[4] * RI[13] + (double)R[7] * RI[14]);
+        if (s.g_pp) { s.g_pp[i * 2] = (float)gx; s.g_pp[i * 2 + 1] = (float)gy; }
+        if (s.update && tpp) {
+            pp0 = adam_update(pp0, (float)gx, s.pp_m[i * 2], s.pp_v[i * 2], s.adam);
+            pp1 = adam_update(pp1, (float)gy, s.pp_m[i * 2 + 1], s.pp_v[i * 2 + 1], s.adam);
+            s.im_pp[i * 2] = pp0; s.im_pp[i * 2 + 1] = pp1;
+        }
+    }
+    if (s.update && tp)
+        for (int k = 0; k < 7; ++k) {
+            Q[k] = adam_update(Q[k], (float)gQ[k], s.imp_m[i * 7 + k], s.imp_v[i * 7 + k], s.adam);
+            s.im_poses[i * 7 + k] = Q[k];
+        }
+    if (s.update && tf) {
+        for (int k = 0; k < s.nfoc; ++k) {
+            fo[k] = adam_update(fo[k], (float)gf[k], s.foc_m[i * s.nfoc + k], s.foc_v[i * s.nfoc + k], s.adam);
+            s.im_focals[i * s.nfoc + k] = fo[k];
+        }
+        if (s.nfoc == 1) fo[1] = fo[0];
+    }
+}
+
+// derived record of image i for the next main pass: R(9) T(3) Fx ppx ppy Fy
+D3R_DEV void modular_image_derived(const SmallView& s, int i, const float (&Q)[7], const float (&fo)[2], float pp0, float pp1) {
+    float D[16];
+    quat_to_rotmat(Q, D);
+    D[9] = signed_expm1f(Q[4]); D[10] = signed_expm1f(Q[5]); D[11] = signed_expm1f(Q[6]);
+    D[12] = expf(fo[0] / s.focal_break);
+    D[13] = 0.5f * (float)s.img_w[i] + 10.f * pp0;
+    D[14] = 0.5f * (float)s.img_h[i] + 10.f * pp1;
+    D[15] = expf(fo[1] / s.focal_break);
+    float4* dst = reinterpret_cast<float4*>(s.d_img + i * 16);
+    for (int k = 0; k < 4; ++k) dst[k] = make_float4(D[4 * k], D[4 * k + 1], D[4 * k + 2], D[4 * k + 3]);
+}
+
+D3R_DEV void modular_load_image(const SmallView& s, int i, float (&Q)[7], float (&fo)[2], float& pp0, float& pp1) {
+    for (int k = 0; k < 7; ++k) Q[k] = s.im_poses[i * 7 + k];
+    fo[0] = s.im_focals[i * s.nfoc];
+    fo[1] = s.im_focals[i * s.nfoc + s.nfoc - 1];
+    pp0 = s.im_pp[i * 2]; pp1 = s.im_pp[i * 2 + 1];
+}
 
 D3R_DEV float pw_scale_factor(const SmallView& s, double mean_p7) {
     return s.norm_pw_scale ? expf(logf(s.base_scale) - (float)mean_p7) : 1.0f;
@@ -343,6 +417,7 @@ D3R_DEV double block_sum_f64(double v, double* sh4) {
 
 // single workgroup; E and n are a few hundred at most per call site (E <= 600). Every sum over edges is
 // a block reduction (thread t owns edges t, t+256, ...): no thread-0 serial chains of dependent L2 loads.
+template <bool MOD>
 __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
     __shared__ double sh4[4];
     const int tid = threadIdx.x;
@@ -416,6 +491,14 @@ __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
         }
         // image poses / focals
         for (int i = tid; i < s.n; i += 256) {
+            if constexpr (MOD) {
+                float Q[7], fo[2], pp0, pp1;
+                double RI[15];
+                modular_load_image(s, i, Q, fo, pp0, pp1);
+                for (int k = 0; k < 15; ++k) RI[k] = s.red_img[(size_t)i * PW + k];
+                modular_image_step(s, i, Q, fo, pp0, pp1, RI);
+                continue;
+            }
             float* P = s.im_poses + i * 7;
             float R[9];
             quat_to_rotmat(P, R);
@@ -465,6 +548,12 @@ __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
         }
     }
     for (int i = tid; i < s.n; i += 256) {
+        if constexpr (MOD) {
+            float Q[7], fo[2], pp0, pp1;
+            modular_load_image(s, i, Q, fo, pp0, pp1);
+            modular_image_derived(s, i, Q, fo, pp0, pp1);
+            continue;
+        }
         const float* P = s.im_poses + i * 7;
         float* D = s.d_img + i * 16;
         quat_to_rotmat(P, D);
@@ -502,7 +591,7 @@ D3R_DEV void block_sum3_f64(double (&v)[3], double (*sh)[3]) {
     }
 }
 
-template <int NT>
+template <int NT, bool MOD>
 __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
     __shared__ double sh[NT / 64][3];
     const int tid = threadIdx.x;
@@ -539,6 +628,8 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
     for (int k = 0; k < 7; ++k) Q[k] = s.im_poses[i * 7 + k];
     foc = s.im_focals[i];
     pp0 = s.im_pp[i * 2]; pp1 = s.im_pp[i * 2 + 1];
+    float fo[2] = {foc, foc};   // MOD: x and y focal parameters
+    if constexpr (MOD) { fo[0] = s.im_focals[i * s.nfoc]; fo[1] = s.im_focals[i * s.nfoc + s.nfoc - 1]; }
     const int iw = s.img_w[i], ih = s.img_h[i];
     if (s.update) {
 #pragma unroll
@@ -604,7 +695,8 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
             }
         }
         // ---- images ------------------------------------------------------------------------------------------------------------
-        if (hi) {
+        if (MOD && hi) modular_image_step(s, i, Q, fo, pp0, pp1, RI);
+        if (!MOD && hi) {
             float R2[9];
             quat_to_rotmat(Q, R2);
             double gQ[7], gf;
@@ -652,7 +744,8 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
         for (int r = 0; r < 3; ++r)
             M[r] = make_float4(st * R[r * 3] * ad[0], st * R[r * 3 + 1] * ad[1], st * R[r * 3 + 2] * ad[2], st * signed_expm1f(P[4 + r]));
     }
-    if (hi) {
+    if (MOD && hi) modular_image_derived(s, i, Q, fo, pp0, pp1);
+    if (!MOD && hi) {
         float D[16];
         quat_to_rotmat(Q, D);
         D[9] = signed_expm1f(Q[4]); D[10] = signed_expm1f(Q[5]); D[11] = signed_expm1f(Q[6]);
@@ -666,12 +759,22 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
     }
 }
 
+template <bool MOD>
 static void launch_small(const SmallView& s, hipStream_t st, bool generic) {
     // generic (D3R_ALIGNER_OPT_GENERIC_SMALL) pins the strided-loop kernel, which takes any E, n: parity tests run both
     const int need = s.E > s.n ? s.E : s.n;
-    if (!generic && need <= 256) hipLaunchKernelGGL(aligner_small1_kernel<256>, dim3(1), dim3(256), 0, st, s);
-    else if (!generic && need <= 1024) hipLaunchKernelGGL(aligner_small1_kernel<1024>, dim3(1), dim3(1024), 0, st, s);
-    else hipLaunchKernelGGL(aligner_small_kernel, dim3(1), dim3(256), 0, st, s);
+    if (!generic && need <= 256) hipLaunchKernelGGL((aligner_small1_kernel<256, MOD>), dim3(1), dim3(256), 0, st, s);
+    else if constexpr (!MOD) {
+        if (!generic && need <= 1024) hipLaunchKernelGGL((aligner_small1_kernel<1024, MOD>), dim3(1), dim3(1024), 0, st, s);
+        else hipLaunchKernelGGL(aligner_small_kernel<MOD>, dim3(1), dim3(256), 0, st, s);
+    } else {
+        // the Modular scene above 256 edges / images takes the strided-loop kernel: at 1024 threads (128 VGPRs) the one-edge-per-thread form spills
+        hipLaunchKernelGGL(aligner_small_kernel<MOD>, dim3(1), dim3(256), 0, st, s);
+    }
+}
+static void launch_small(const SmallView& s, hipStream_t st, bool generic, bool modular) {
+    if (modular) launch_small<true>(s, st, generic);
+    else launch_small<false>(s, st, generic);
 }
 
 }  // namespace d3r
@@ -713,6 +816,12 @@ struct d3r_aligner {
     // stream first waits for this event (same stream: already ordered, no wait issued)
     hipStream_t create_stream = nullptr;
     hipEvent_t ev_ready = nullptr;
+    // the ModularPointCloudOptimizer scene: per-edge-mean loss (D3R_ALIGNER_OPT_EDGE_MEAN_LOSS), fx / fy (D3R_ALIGNER_OPT_FX_AND_FY: nfoc = 2)
+    // and per-image trainability (d3r_aligner_set_trainable: [3][n] bytes, poses | focals | principal points, allocated on first use).
+    // Any of them selects the MODULAR kernels; without them the PointCloudOptimizer kernels run exactly as before.
+    int edge_mean = 0, nfoc = 1;
+    unsigned char* d_train = nullptr;
+    bool modular() const { return edge_mean || nfoc == 2 || d_train != nullptr; }
 };
 
 // orders `st` behind the work d3r_aligner_create left in flight on its own stream
@@ -773,7 +882,7 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     size_t fl = 0;
     auto take = [&](size_t cnt) { size_t o = fl; fl += (cnt + 3) & ~(size_t)3; return o; };
     const size_t o_dm = take(nA), o_dv = take(nA), o_pwm = take((size_t)n_edges * 8), o_pwv = take((size_t)n_edges * 8),
-                 o_im = take((size_t)n_imgs * 7), o_iv = take((size_t)n_imgs * 7), o_fm = take(n_imgs), o_fv = take(n_imgs),
+                 o_im = take((size_t)n_imgs * 7), o_iv = take((size_t)n_imgs * 7), o_fm = take(2 * (size_t)n_imgs), o_fv = take(2 * (size_t)n_imgs),
                  o_pm = take((size_t)n_imgs * 2), o_pv = take((size_t)n_imgs * 2), o_am = take((size_t)n_edges * 2), o_av = take((size_t)n_edges * 2),
                  o_de = take((size_t)n_edges * 12), o_di = take((size_t)n_imgs * 16),
                  o_pe = take((size_t)2 * n_edges * a->nslot * PW), o_pi = take((size_t)n_imgs * a->nslot * PW),
@@ -819,6 +928,7 @@ extern "C" int d3r_aligner_destroy(d3r_aligner* a) {
     if (!a) return D3R_OK;
     if (a->ev_ready) (void)hipEventDestroy(a->ev_ready);
     if (a->inter) (void)hipFree(a->inter);
+    if (a->d_train) (void)hipFree(a->d_train);
     (void)hipFree(a->state);
     (void)hipFree(a->d_w);
     delete a;
@@ -848,17 +958,20 @@ static int aligner_pass(d3r_aligner* a, bool update, double lr, int hist_idx, fl
     s.base_scale = a->base_scale; s.pw_break = a->pw_break; s.focal_break = a->focal_break;
     s.norm_pw_scale = a->norm_pw_scale; s.opt_poses = a->opt_poses; s.opt_focals = a->opt_focals;
     s.update = 0; s.adam = adam_coef(lr, a->step + 1);
+    s.tr_pose = a->d_train; s.tr_foc = a->d_train ? a->d_train + a->n : nullptr; s.tr_pp = a->d_train ? a->d_train + 2 * a->n : nullptr;
+    s.nfoc = a->nfoc;
+    const bool modular = a->modular();
     if (phase == 2) {
         s.update = update ? 1 : 0;
         s.g_pw = g_pw; s.g_imp = g_imp; s.g_foc = g_foc; s.g_pp = g_pp; s.g_pa = g_pa;
-        launch_small(s, st, a->generic_small);
+        launch_small(s, st, a->generic_small, modular);
         if (update) a->step++;
         return hipGetLastError() == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH;
     }
     if (refresh_derived_first) {
         SmallView s0 = s;
         s0.loss_hist = nullptr;
-        launch_small(s0, st, a->generic_small);
+        launch_small(s0, st, a->generic_small, modular);
     }
     const int imgc = a->imgc < 0 ? a->n : a->imgc;
     if (a->part_clear_pending) {        // records of images outside the range must read as zero (they are never written here)
@@ -872,18 +985,23 @@ static int aligner_pass(d3r_aligner* a, bool update, double lr, int hist_idx, fl
     v.depth = a->im_depth; v.depth_m = a->depth_m; v.depth_v = a->depth_v;
     v.depth_grad = g_depth; v.d_edge = a->d_edge; v.d_img = a->d_img; v.part_edge = a->part_edge; v.part_img = a->part_img;
     v.inv_area[0] = a->inv_area[0]; v.inv_area[1] = a->inv_area[1]; v.l2 = a->l2; v.update = update ? 1 : 0;
-    v.use_dpp = a->use_dpp; v.adam = s.adam;
+    v.use_dpp = a->use_dpp; v.adam = s.adam; v.edge_mean = a->edge_mean;
     const dim3 grid(imgc * a->nslot);
     if (imgc > 0) {
-        if (a->l2) hipLaunchKernelGGL((aligner_main_kernel<true>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
-        else hipLaunchKernelGGL((aligner_main_kernel<false>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
+        if (modular) {
+            if (a->l2) hipLaunchKernelGGL((aligner_main_kernel<true, true>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
+            else hipLaunchKernelGGL((aligner_main_kernel<false, true>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
+        } else {
+            if (a->l2) hipLaunchKernelGGL((aligner_main_kernel<true, false>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
+            else hipLaunchKernelGGL((aligner_main_kernel<false, false>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
+        }
     }
     // part_edge | part_img and red_edge | red_img are contiguous: one launch reduces the 2E + n entries
     hipLaunchKernelGGL(aligner_reduce_kernel, dim3(2 * a->E + a->n), dim3(256), 0, st, a->part_edge, a->red_edge, a->nslot);
     if (phase == 1) return hipGetLastError() == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH;
     s.update = update ? 1 : 0;
     s.g_pw = g_pw; s.g_imp = g_imp; s.g_foc = g_foc; s.g_pp = g_pp; s.g_pa = g_pa;
-    launch_small(s, st, a->generic_small);
+    launch_small(s, st, a->generic_small, modular);
     if (update) a->step++;
     return hipGetLastError() == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH;
 }
@@ -895,6 +1013,8 @@ extern "C" int d3r_aligner_set_option(d3r_aligner* a, int option, int value) {
         case D3R_ALIGNER_OPT_OPTIMIZE_PP: a->opt_pp = value != 0; return D3R_OK;
         case D3R_ALIGNER_OPT_OPTIMIZE_ADAPTORS: a->opt_adapt = value != 0; return D3R_OK;
         case D3R_ALIGNER_OPT_GENERIC_SMALL: a->generic_small = value != 0; return D3R_OK;
+        case D3R_ALIGNER_OPT_EDGE_MEAN_LOSS: a->edge_mean = value != 0; return D3R_OK;
+        case D3R_ALIGNER_OPT_FX_AND_FY: a->nfoc = value != 0 ? 2 : 1; return D3R_OK;
         case D3R_ALIGNER_OPT_RESET_ADAM:
             // the moments are cleared on the stream of the NEXT d3r_aligner_run / loss_grad call (ordered against the iterations that
             // are still in flight there), not on the legacy NULL stream
@@ -903,6 +1023,22 @@ extern "C" int d3r_aligner_set_option(d3r_aligner* a, int option, int value) {
             return D3R_OK;
     }
     return D3R_ERR_INVALID;
+}
+
+// per-image trainability of the Modular scene (modular_optimizer.py `_no_grad`): mask_host [n] bytes, 0 = frozen, NULL = every image trainable
+extern "C" int d3r_aligner_set_trainable(d3r_aligner* a, int kind, const unsigned char* mask_host) {
+    if (!a || kind < D3R_ALIGNER_TRAIN_POSES || kind > D3R_ALIGNER_TRAIN_PP) return D3R_ERR_INVALID;
+    if (!a->d_train) {
+        if (hipMalloc((void**)&a->d_train, 3 * (size_t)a->n) != hipSuccess) { a->d_train = nullptr; return D3R_ERR_ALLOC; }
+        HIPCHK(hipMemset(a->d_train, 1, 3 * (size_t)a->n));
+    }
+    std::vector<unsigned char> m((size_t)a->n, 1);
+    if (mask_host)
+        for (int i = 0; i < a->n; ++i) m[i] = mask_host[i] ? 1 : 0;
+    // a setup call: iterations still in flight on any stream may read the masks, so they drain first
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(a->d_train + (size_t)kind * a->n, m.data(), a->n, hipMemcpyHostToDevice));
+    return D3R_OK;
 }
 
 // niter iterations of global_alignment_iter; lr follows the reference schedule evaluated at
@@ -943,7 +1079,7 @@ extern "C" int d3r_aligner_set_image_range(d3r_aligner* a, int first, int count)
 }
 
 extern "C" int d3r_aligner_step_begin(d3r_aligner* a, int k, int iter0, int niter_total, float lr_base, float lr_min, int schedule, void* stream) {
-    if (!a || k < 0 || k >= a->loss_cap || niter_total <= 0) return D3R_ERR_INVALID;
+    if (!a || k < 0 || k >= a->loss_cap || niter_total <= 0 || a->modular()) return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     aligner_wait_ready(a, st);
     if (a->reset_pending) {
@@ -954,7 +1090,7 @@ extern "C" int d3r_aligner_step_begin(d3r_aligner* a, int k, int iter0, int nite
 }
 
 extern "C" int d3r_aligner_step_end(d3r_aligner* a, int k, int iter0, int niter_total, float lr_base, float lr_min, int schedule, void* stream) {
-    if (!a || k < 0 || k >= a->loss_cap || niter_total <= 0) return D3R_ERR_INVALID;
+    if (!a || k < 0 || k >= a->loss_cap || niter_total <= 0 || a->modular()) return D3R_ERR_INVALID;
     return aligner_pass(a, true, sched_lr(k, iter0, niter_total, lr_base, lr_min, schedule), k, nullptr, nullptr, nullptr, nullptr, false, (hipStream_t)stream, nullptr, nullptr, 2);
 }
 

@@ -133,4 +133,16 @@ D3R_HD void image_chain(const float P[7], const float R[9], float focal_break, c
     g_focal = -tr / (double)focal_break;
 }
 
+// ModularPointCloudOptimizer(fx_and_fy=True) (reference modular_optimizer.py:30-34,107-113): cam = d ((u-ppx)/Fx, (v-ppy)/Fy, 1) with
+// Fx = exp(fx/fb), Fy = exp(fy/fb). The trace image_chain forms splits: dL/dfx = -(1/fb) (R^T G)_00, dL/dfy = -(1/fb) (R^T G)_11.
+D3R_HD void focal_xy_grads(const float R[9], float focal_break, const double GRi[9], double& g_fx, double& g_fy) {
+    double tx = 0.0, ty = 0.0;
+    for (int r = 0; r < 3; ++r) {
+        tx += (double)R[r * 3 + 0] * GRi[r * 3 + 0];
+        ty += (double)R[r * 3 + 1] * GRi[r * 3 + 1];
+    }
+    g_fx = -tx / (double)focal_break;
+    g_fy = -ty / (double)focal_break;
+}
+
 }  // namespace d3r

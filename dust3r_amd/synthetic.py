@@ -247,3 +247,27 @@ def synthetic_scene(n_views, H, W, seed=0, scene_graph='complete', symmetrize=Fa
     gt = dict(cam2world=c2w_t.cpu(), focal=f_gt, depth=depth.cpu(), world_scale=cworld, edges=edges,
               edge_scales=scales)
     return output, init_state, gt
+
+
+def synthetic_mixed_scene(shapes, seed=0):
+    """Pairwise output over images of DIFFERENT sizes (`shapes`: [(H, W)] per image; complete symmetrised graph), as `inference()`
+    returns it for such a set: the prediction tensors are per-edge lists. The pointmaps are random clouds in front of the camera
+    (depth 2 + N(0, .1)), not a consistent geometry: enough for loss / gradient parity, not for a converging alignment."""
+    g = torch.Generator(device='cpu').manual_seed(seed)
+    edges = scene_edges(len(shapes), 'complete', True)
+
+    def cloud(H, W):
+        vs, us = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing='ij')
+        d = 2 + 0.1 * torch.randn((H, W), generator=g)
+        f = 1.2 * W
+        return torch.stack((d * (us - W / 2) / f, d * (vs - H / 2) / f, d), dim=-1) + 0.05 * torch.randn((H, W, 3), generator=g)
+
+    pred_i, pred_j, conf_i, conf_j = [], [], [], []
+    for i, j in edges:
+        pred_i.append(cloud(*shapes[i]))
+        pred_j.append(cloud(*shapes[j]))
+        conf_i.append(1 + torch.exp(1 + 0.5 * torch.randn(shapes[i], generator=g)))
+        conf_j.append(1 + torch.exp(1 + 0.5 * torch.randn(shapes[j], generator=g)))
+    return dict(view1=dict(idx=[i for i, j in edges], instance=[str(i) for i, j in edges]),
+                view2=dict(idx=[j for i, j in edges], instance=[str(j) for i, j in edges]),
+                pred1=dict(pts3d=pred_i, conf=conf_i), pred2=dict(pts3d_in_other_view=pred_j, conf=conf_j), loss=None)

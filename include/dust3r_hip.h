@@ -256,6 +256,15 @@ typedef struct d3r_aligner d3r_aligner;
 #define D3R_ALIGNER_OPT_OPTIMIZE_ADAPTORS 4 /* 1: pw_adaptors are trainable (allow_pw_adaptors=True, base_opt.py:49,92) */
 #define D3R_ALIGNER_OPT_GENERIC_SMALL 5 /* 1: per-iteration pose / focal step by the strided-loop kernel (any E, n) instead of the
                                           one-edge-per-thread kernel used for E, n <= 1024 (tests compare the two) */
+/* The ModularPointCloudOptimizer scene (dust3r/cloud_opt/modular_optimizer.py; options set before the first run / loss_grad). Any of options 6, 7
+ * or a d3r_aligner_set_trainable call selects the Modular kernels; d3r_aligner_step_begin / step_end then return D3R_ERR_INVALID. */
+#define D3R_ALIGNER_OPT_EDGE_MEAN_LOSS 6 /* 1: BasePCOptimizer.forward's loss (base_opt.py:246-273): (1/E) sum_e [mean over image i + mean over
+                                           image j], i.e. an edge side projected onto image k weighs 1 / (E area_k), instead of 1 / total side area */
+#define D3R_ALIGNER_OPT_FX_AND_FY 7 /* 1: fx_and_fy=True (modular_optimizer.py:24,32-34): im_focals [n][2] = focal_brake * log (fx, fy); the
+                                      g_im_focals of d3r_aligner_loss_grad is then [n][2] too */
+#define D3R_ALIGNER_TRAIN_POSES 0
+#define D3R_ALIGNER_TRAIN_FOCALS 1
+#define D3R_ALIGNER_TRAIN_PP 2
 
 int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, const int* ei, const int* ej, const int* img_h, const int* img_w,
                        int max_area, const float* pred_i, const float* pred_j, const float* w_i, const float* w_j, float* pw_poses,
@@ -264,6 +273,12 @@ int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, const int* ei
                        int max_iters_per_run, void* stream);
 int d3r_aligner_destroy(d3r_aligner* a);
 int d3r_aligner_set_option(d3r_aligner* a, int option, int value);
+/* Per-image trainability of the Modular scene (modular_optimizer.py `_no_grad` on single entries of im_poses / im_focals / im_pp, set by
+ * preset_pose / preset_focal / preset_principal_point with a partial mask). kind: D3R_ALIGNER_TRAIN_*; mask_host: HOST bytes [n_imgs],
+ * 0 = frozen (no update, its Adam moments stay zero, as torch.optim.Adam without that parameter), NULL = every image trainable. The group's
+ * own switch (opt_im_poses / opt_im_focals of create, D3R_ALIGNER_OPT_OPTIMIZE_PP) still applies on top. Gradients are exported for frozen
+ * images too. A setup call: it waits for the device to drain. */
+int d3r_aligner_set_trainable(d3r_aligner* a, int kind, const unsigned char* mask_host);
 /* `niter` iterations of global_alignment_iter; iteration k uses lr = schedule((iter0 + k) / niter_total).
  * losses_out (device fp32 [niter], may be NULL) receives the loss evaluated BEFORE each step, as float(loss) does
  * at base_opt.py:366 -- but without the reference's per-iteration host synchronisation. */
