@@ -85,6 +85,9 @@ def _load():
         'd3r_aligner_read_losses': (i, [vp, i, fp, vp]),
         'd3r_nearest_neighbors': (i, [fp, i, fp, i, ip, vp]),
         'd3r_clean_pointcloud': (i, [i, fp, fp, fp, fp, fp, ip, ip, i, f, f, vp]),
+        'd3r_segment_sky_workspace_bytes': (C.c_size_t, [i, i]),
+        'd3r_segment_sky': (i, [i, vp, i, ip, ip, i, vp, vp, vp]),
+        'd3r_sky_color_mask': (i, [i, vp, i, ip, ip, i, vp, vp]),
         'd3r_row_means': (i, [fp, i, i, i, fp, vp]),
         'd3r_similarity_moments_workspace': (C.c_size_t, [i, i]),
         'd3r_similarity_moments': (i, [i, vp, vp, vp, ip, i, vp, vp, vp]),

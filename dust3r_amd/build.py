@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['gemm.hip', 'gemm_p4.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'engine.hip', 'capi.hip']
+SOURCES = ['gemm.hip', 'gemm_p4.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'sky.hip', 'engine.hip', 'capi.hip']
 HEADERS = ['common.hpp', 'kernels.hpp', 'aligner_math.hpp', os.path.join('..', '..', 'include', 'dust3r_hip.h')]
 LIB = os.path.join(CSRC, 'libdust3r_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-inline-asm']
@@ -15,7 +15,8 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-res
 # pairs; hipcc -O3 re-packs adjacent scalar fp32 operations into v_pk_* (an anti-lever beside MFMAs, MI355X_MICROARCH.md). The packed
 # variants of the same kernel use explicit 2-vectors and are not affected.
 EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'gemm_p4.hip': ['-fno-slp-vectorize', '-Rpass-analysis=kernel-resource-usage'],     # gemm_p4.hip: its drain's scalar GELU pieces sit between MFMAs too
-               'aligner.hip': ['-Rpass-analysis=kernel-resource-usage']}      # aligner.hip: its report pins the registers / scratch of every aligner kernel (tests read it)
+               'aligner.hip': ['-Rpass-analysis=kernel-resource-usage'],      # aligner.hip: its report pins the registers / scratch of every aligner kernel (tests read it)
+               'sky.hip': ['-Rpass-analysis=kernel-resource-usage']}          # sky.hip: its report shows the segmentation kernels use no scratch (tests read it)
 
 
 def _hipcc():

@@ -3,12 +3,14 @@
 
 Same constructor keywords, attributes (`edges, imshapes, imsizes, im_conf, pred_i, pred_j, conf_i,
 conf_j, pw_poses, pw_adaptors, min_conf_thr, conf_trf, is_symmetrized, n_imgs, n_edges,
-str_edges`), getters and `compute_global_alignment(init, niter_PnP, lr, niter, schedule, lr_min)`.
+str_edges`), getters, `compute_global_alignment(init, niter_PnP, lr, niter, schedule, lr_min)`, `clean_pointcloud()` and
+`mask_sky()`.
 What differs is WHERE the optimisation runs: the reference builds an autograd graph of ~25 kernels
 per iteration and steps torch.optim.Adam (base_opt.py:326-366); here `global_alignment_loop` hands
 the parameter tensors to the fused HIP aligner (csrc/aligner.hip, C ABI `d3r_aligner_*`), which
 updates them in place. There is no CPU execution path for the loop.
 """
+import copy
 import ctypes as C
 
 import numpy as np
@@ -281,8 +283,20 @@ class BasePCOptimizer(nn.Module):
             self.im_conf[i][:] = c
         return self
 
+    @torch.no_grad()
     def mask_sky(self):
-        raise NotImplementedError('sky segmentation (cv2) belongs to the visualisation layer, outside this engine')
+        """The reference's mask_sky (base_opt.py:290-295): a copy of the scene whose im_conf is zero on the sky of each image
+        (viz.segment_sky, all images in one GPU call). The scene itself is left untouched."""
+        if self.imgs is None:
+            raise ValueError('mask_sky needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
+        if self.device.type != 'cuda':
+            raise _lib.D3RError('mask_sky runs on the GPU (dust3r_amd has no CPU execution path)')
+        from ..viz import segment_sky_batch
+        skies = segment_sky_batch(self.imgs, self.device)
+        res = copy.deepcopy(self)
+        for conf, sky in zip(res.im_conf, skies):
+            conf[sky] = 0
+        return res
 
     def show(self, *a, **k):
         raise NotImplementedError('trimesh visualisation is outside this engine; export get_pts3d()/get_im_poses() instead')
@@ -295,6 +309,15 @@ class BasePCOptimizer(nn.Module):
         if getattr(self, '_engine', None) is not None:
             lib.d3r_aligner_destroy(self._engine)
             self._engine = None
+
+    def __deepcopy__(self, memo):
+        """Every tensor is copied (views of one storage stay views of one new storage); the copy has no engine and builds its own on first use:
+        the engine handle is a native pointer into this scene's tensors."""
+        res = type(self).__new__(type(self))
+        memo[id(self)] = res
+        for k, v in self.__dict__.items():
+            res.__dict__[k] = None if k in ('_engine', '_engine_sig') else copy.deepcopy(v, memo)
+        return res
 
     def __del__(self):
         try:

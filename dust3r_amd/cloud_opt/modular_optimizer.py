@@ -96,6 +96,11 @@ class ModularPointCloudOptimizer(BasePCOptimizer):
         self._bind_entries()
         return self
 
+    def __deepcopy__(self, memo):
+        res = super().__deepcopy__(memo)
+        res._bind_entries()           # nn.Parameter copies are clones: make the copy's per-image parameters views of ITS flat storage again
+        return res
+
     def state_dict(self, trainable=True):
         """The reference's keys: pw_poses, pw_adaptors, im_conf.<i>, im_depthmaps.<i> (H, W), im_poses.<i> (7,), im_focals.<i> (1,) | (2,), im_pp.<i> (2,)."""
         if not trainable:

@@ -108,6 +108,43 @@ def synthetic_photo(W, H, seed):
     return (np.clip(np.stack(chans, axis=-1), 0, 1) * 255).round().astype('uint8')
 
 
+# ------------------------------------------------------------------ sky segmentation pictures (tests/test_sky_*.py, tools/sky_speed.py)
+SKY_RGB, GROUND_RGB = (135, 206, 235), (40, 120, 40)
+
+
+def outdoor_scene(H, W, seed, horizon=0.45):
+    """Deterministic uint8 (H, W, 3) outdoor picture: a blue sky gradient with light and dark grey clouds above a ragged skyline of
+    buildings (dark, brick, sandstone, glass) and foliage. `horizon`: the skyline's mean height as a fraction of H from the top."""
+    rng = np.random.RandomState(seed)
+    y, x = np.mgrid[:H, :W].astype(np.float64)
+    t = y / H
+    img = np.stack([90 + 100 * t, 140 + 70 * t, 210 + 30 * t], axis=-1)
+    for _ in range(rng.randint(2, 6)):                                 # clouds: ellipses of light or dark grey
+        cy, cx = rng.uniform(0, horizon * H), rng.uniform(0, W)
+        ry, rx = rng.uniform(4, H / 8), rng.uniform(8, W / 4)
+        inside = ((y - cy) / ry) ** 2 + ((x - cx) / rx) ** 2 < 1
+        img[inside] = rng.choice([225, 200, 150, 120]) + rng.uniform(-5, 5, 3)
+    palette = np.array([(60, 55, 50), (150, 70, 50), (200, 180, 150), (70, 90, 110)], dtype=np.float64)
+    skyline, wall = np.zeros(W), np.zeros(W, dtype=int)
+    x0 = 0
+    while x0 < W:                                                      # buildings of random widths, heights and colours
+        w = rng.randint(max(2, W // 20), max(3, W // 5))
+        skyline[x0:x0 + w] = np.clip(horizon * H + rng.uniform(-0.3, 0.2) * H, 0, H)
+        wall[x0:x0 + w] = rng.randint(len(palette))
+        x0 += w
+    below = y >= skyline[None, :]
+    img[below] = palette[np.broadcast_to(wall[None, :], (H, W))[below]]
+    leaves = below & (y > H * (horizon + 0.25)) & (np.sin(x / 9.0 + rng.uniform(0, 6)) + np.cos(y / 7.0) > 0.6)
+    img[leaves] = (50, 110, 40)
+    img += rng.normal(0, 3, img.shape)
+    return np.clip(img, 0, 255).round().astype(np.uint8)
+
+
+def sky_mask_picture(mask):
+    """An RGB picture whose colour mask is exactly `mask`: sky blue where True, dark green elsewhere."""
+    return np.where(np.asarray(mask, bool)[..., None], np.uint8(SKY_RGB), np.uint8(GROUND_RGB)).astype(np.uint8)
+
+
 # (source W, H, size, square_ok): landscape / portrait / square (4:3 rule and square_ok) / odd sizes / enlargement (BICUBIC) / the 224 rule
 LOAD_IMAGES_CASES = [(640, 480, 160, False), (480, 640, 160, False), (500, 500, 160, False), (500, 500, 160, True), (333, 517, 128, False),
                      (100, 75, 160, False), (417, 300, 224, False), (300, 417, 224, False), (1001, 333, 192, False)]

@@ -314,6 +314,20 @@ int d3r_aligner_loss_grad(d3r_aligner* a, float* loss, float* g_pw_poses, float*
 int d3r_clean_pointcloud(int n_imgs, float* conf, const float* depth, const float* pts3d, const float* intrinsics, const float* world2cam,
                          const int* img_h_dev, const int* img_w_dev, int max_area, float tol, float bad_conf, void* stream);
 
+/* Sky segmentation (dust3r/viz.py:345-381 segment_sky, used by BasePCOptimizer.mask_sky, dust3r/cloud_opt/base_opt.py:290-295) of n
+ * images in one call. rgb [n][max_area][3] DEVICE, row-major H x W RGB per image: uint8 when rgb_is_u8, else fp32 in [0, 1] (converted
+ * like the reference: uint8(255 * clip(x, 0, 1)), fp32 product, truncated). img_h / img_w: DEVICE int arrays. Per image: OpenCV's 8-bit
+ * COLOR_BGR2HSV applied to the RGB data (R read as "b"), the colour rule (0 <= H <= 30 and V >= 100, or a bright grey), a binary opening
+ * with a 5x5 square (outside the image counts as 0), 8-connected components, and every component of area a with 2 a > a_max (the image's
+ * largest) kept. mask_out [n][max_area] DEVICE uint8 (0 / 1, 0 in the padding). workspace: d3r_segment_sky_workspace_bytes(n, max_area)
+ * bytes of DEVICE memory. Bit-exact and deterministic; no allocation, no synchronisation. */
+size_t d3r_segment_sky_workspace_bytes(int n_imgs, int max_area);
+int d3r_segment_sky(int n_imgs, const void* rgb, int rgb_is_u8, const int* img_h_dev, const int* img_w_dev, int max_area, uint8_t* mask_out,
+                    void* workspace, void* stream);
+/* the colour rule alone (no opening, no components), same arguments: mask_out[i][p] = 1 where pixel p of image i passes it */
+int d3r_sky_color_mask(int n_imgs, const void* rgb, int rgb_is_u8, const int* img_h_dev, const int* img_w_dev, int max_area, uint8_t* mask_out,
+                       void* stream);
+
 /* exhaustive 3-D nearest neighbour: idx_out[q] = argmin_r |query[q] - ref[r]|^2 (lowest index on ties); query [n_query][3],
  * ref [n_ref][3] DEVICE fp32, idx_out DEVICE int32. The building block of find_reciprocal_matches (dust3r/utils/geometry.py:345-361,
  * two SciPy KD-tree queries in the reference; caller: visloc.py:105). */
