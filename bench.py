@@ -4,13 +4,17 @@
 Metric (BASELINE.json): image-pairs/s of `AsymmetricCroCo3DStereo.forward`, DUSt3R_ViTLarge_BaseDecoder_512_dpt,
 synthetic 512x384 pairs (configs[1]: 32 pairs per GPU per step, inputs resident in HBM), at 1/2/4/8 GPUs; the
 second half of the metric, global_aligner iterations/s (configs[3]: 20 views, 190 edges, 300 cosine iterations),
-is reported in the same JSON line under "aligner".
+is reported in the same JSON line under "aligner" when the run is given --full.
 
 One step = one engine forward over `--pairs` image pairs per rank. At N > 1 ranks the pairs shard across ranks
 (weak scaling: fixed pairs per GPU) and every step ends with the path's ONE collective, the all-gather of the
 pairwise predictions (dust3r_amd/parallel.py), issued asynchronously so that it overlaps the next step's compute.
 
-Usage: python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c5]   (N > 1: launched by torch.distributed.run, one rank per GPU)
+Usage: python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c5] [--full]   (N > 1: launched by torch.distributed.run, one rank per GPU)
+  A plain run does only what the headline needs: it builds the engine, runs the warm-up and the timed steps, writes --dump-outputs and prints the line
+  (metric, value, unit, ms_per_step, dtype, the rank table and the clock / power telemetry of the timed steps).
+  --full: everything else as well, after the timed steps -- parity_check, roofline / kernels / launch_table, latency, fast_mode, the aligner,
+                 the CPU baselines and the DUST3R_CKPT checkpoint validation (before the engine is built); the --no-* switches below pick from them.
   --dump-outputs DIR: after the timed steps, what the last step returned (c2: the four forward result tensors; c3 / c5: those of the job's pairs,
                  c5 also the aligned scene's poses, focals, principal points and depth maps) as DIR/<name>.npy in float32, at most 64 MB in all: a fixed,
                  seeded sample of the pairs (and views) when there are more. Inputs and weights are seeded, so two builds can be compared file for file.
@@ -21,10 +25,10 @@ Usage: python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c5]   (N 
   --workload c5: configs[4], 100 views, make_pairs('swin-3', symmetrize=True) = 600 pairs: sharded forward + all-gather, then on rank 0
                  global_aligner(PointCloudOptimizer) + compute_global_alignment(init='mst', niter=300, cosine): wall clock per job,
                  next to a CPU figure EXTRAPOLATED by the BASELINE.md section 2 protocol (labelled as such).
-Every line carries a "parity_check" block: outputs of the timed 32-pair batch against one-pair-per-call runs of the same pairs
+With --full, every line carries a "parity_check" block: outputs of the timed 32-pair batch against one-pair-per-call runs of the same pairs
 (bit-equality; the one-pair call shape is what tests/ hold to the CPU oracle) and, at N = 1 with the CPU baseline on, the engine
 loaded with the CPU oracle's weights against the oracle's own output on the same pair (per-pixel relative error, bar 1e-3).
-Prints ONE JSON line on rank 0. Extra objects: "roofline" (dominant kernel, live HIP-event timing), "cpu_baseline"
+Prints ONE JSON line on rank 0. Extra objects of a --full run: "roofline" (dominant kernel, live HIP-event timing), "cpu_baseline"
 (the CPU oracle timed on this host's cores on a bounded sample, rank 0 at N=1 only), "aligner", "kernels", "fast_mode"
 (the opt-in modes fp16f8 / bf16 / fp16: throughput, their own dominant-kernel roofline block and their measured error against the headline
 engine. The headline precision is fp16x3, the engine default and the mode that meets the 1e-3 per-pixel bar on every plain weight seed tested; DESIGN.md section 2 for the outlier-weight figures).
@@ -733,6 +737,9 @@ def main():
     ap.add_argument('--precision', default=os.environ.get('DUST3R_AMD_PRECISION', 'fp16x3'),
                     help='engine precision of the HEADLINE: fp16x3 (default, the engine default: meets the 1e-3 per-pixel pointmap bar); fp16x2f8 / fp16f8 / bf16 / fp16 are opt-in modes reported under fast_mode')
     ap.add_argument('--workload', default='c2', choices=['c2', 'c3', 'c5'], help='c2 (default): BASELINE configs[1], 32 pairs per GPU per step; c3: configs[2], 20 views -> 190 pairs sharded; c5: configs[4], 100 views swin-3 -> 600 pairs, forward + global_aligner end to end')
+    ap.add_argument('--full', action='store_true', help='also run what the headline does not need: after the timed steps the parity checks, the profiled forward (roofline, '
+                                                        'kernels, launch_table), latency, the opt-in precisions, the aligner and the CPU baselines; before the engine is built '
+                                                        'the DUST3R_CKPT validation. The --no-* switches skip single parts of it')
     ap.add_argument('--no-parity', action='store_true', help='skip the parity_check block')
     ap.add_argument('--no-aligner', action='store_true')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -746,6 +753,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:           # a plain run: set-up, warm-up, timed steps, --dump-outputs and the line, nothing else
+        args.no_parity = args.no_aligner = args.no_aligner_380 = args.no_cpu_baseline = args.no_profile = args.no_latency = args.no_fast = True
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         self_launch(args)                     # bare `python bench.py --gpus N`: becomes N ranks under torch.distributed.run
@@ -788,12 +797,15 @@ def main():
     from dust3r_amd.parallel import all_gather_packed
     from dust3r_amd.synthetic import synthetic_views
     _lib.require_device()
-    # DUST3R_CKPT=<released checkpoint file>: the first thing a box with weights on it does is pin the croco / roma restatements of oracle/ against them
+    # DUST3R_CKPT=<released checkpoint file> with --full: the first thing a box with weights on it does is pin the croco / roma restatements of oracle/ against them
     # (tools/validate_checkpoint.py: key-for-key load into oracle and engine, per-pixel statistics of one pair per precision) -- BEFORE anything is timed, in its own
     # process; the verdict travels in the JSON line (`checkpoint_validation`). The timed workload itself stays BASELINE's: synthetic inputs, random-init weights.
     ckpt_validation = None
     if rank == 0 and os.environ.get('DUST3R_CKPT'):
-        ckpt_validation = validate_checkpoint_first(os.environ['DUST3R_CKPT'])
+        if args.full:
+            ckpt_validation = validate_checkpoint_first(os.environ['DUST3R_CKPT'])
+        else:
+            log('[bench] DUST3R_CKPT is set: its validation runs with --full only')
     model = build_model(args.precision, device)
     if args.single_stream:
         model.set_two_streams(False)

@@ -145,7 +145,7 @@ def test_validate_checkpoint_tool_on_a_synthetic_checkpoint(gpu, tmp_path):
 
 
 def test_validate_checkpoint_tool_on_a_synthetic_hub_snapshot(gpu, tmp_path):
-    """The same harness on a hub SNAPSHOT DIRECTORY (what PyTorchModelHubMixin.from_pretrained reads, dust3r/model.py:76-85; `DUST3R_CKPT=<dir> python bench.py` runs exactly
+    """The same harness on a hub SNAPSHOT DIRECTORY (what PyTorchModelHubMixin.from_pretrained reads, dust3r/model.py:76-85; `DUST3R_CKPT=<dir> python bench.py --full` runs exactly
     this first): config.json with lists / Infinity / ManyAR patch embed / freeze, model.safetensors with ONE name per shared tensor (the DPT head's layer_rn convolutions)
     and no dec_blocks2 keys. Oracle and engine both load it key for key and every precision passes the bar."""
     import json

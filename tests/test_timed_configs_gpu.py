@@ -349,7 +349,7 @@ def test_c5_alignment_consumes_the_sharded_handover_at_100_views(gpu):
 
 @pytest.mark.parametrize('workload', ['c2', 'c3', 'c5'])
 def test_bench_multi_rank_branches_on_one_device(gpu, workload, tmp_path):
-    """bench.py --gpus 2 for every workload, both ranks on this box's one GPU (D3R_BENCH_ONE_DEVICE=1, gloo moves the CUDA payload: RCCL
+    """bench.py --gpus 2 --full for every workload, both ranks on this box's one GPU (D3R_BENCH_ONE_DEVICE=1, gloo moves the CUDA payload: RCCL
     refuses two ranks on a device): the N > 1 code of the driver's scaling run -- shard bounds, per-rank encode-once, the all-gather,
     rank-0 alignment, max-over-ranks timing -- executes, prints ONE valid JSON line, and its own parity_check passes. A self-test of the
     code path, NOT a scaling measurement (the line says so in `data`); the artefact is kept under gpurun_out/ for profiles/."""
@@ -363,7 +363,7 @@ def test_bench_multi_rank_branches_on_one_device(gpu, workload, tmp_path):
         port = sk.getsockname()[1]
     env = dict(os.environ, D3R_BENCH_ONE_DEVICE='1', D3R_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     extra = ['--pairs', '4'] if workload == 'c2' else []
-    tail = ['--gpus', '2', '--steps', '1', '--warmup', '1', '--workload', workload, '--no-cpu-baseline', '--no-fast', '--no-profile', '--no-aligner'] + extra
+    tail = ['--gpus', '2', '--steps', '1', '--warmup', '1', '--workload', workload, '--full', '--no-cpu-baseline', '--no-fast', '--no-profile', '--no-aligner'] + extra
     if workload == 'c2':
         # the BARE command, as the driver writes its N = 1 line (no torchrun around it, WORLD_SIZE unset): bench.py launches its own ranks
         env.pop('WORLD_SIZE', None), env.pop('RANK', None), env.pop('LOCAL_RANK', None)
@@ -391,3 +391,28 @@ def test_bench_multi_rank_branches_on_one_device(gpu, workload, tmp_path):
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, f'bench_gpus2_selftest_{workload}.json'), 'w') as f:
         f.write(lines[0] + '\n')
+
+
+def test_bench_plain_run_prints_the_headline_only(gpu, tmp_path):
+    """bench.py without --full: the warm-up, the timed steps, --dump-outputs and ONE line with the headline fields; the parity checks, the profiled forward,
+    latency, the opt-in precisions, the aligner and the CPU baselines stay behind --full."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'DUST3R_CKPT', 'DUST3R_AMD_PRECISION'):
+        env.pop(k, None)
+    out = tmp_path / 'dump'
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '1', '--pairs', '2', '--dump-outputs', str(out)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['metric'] == 'image_pairs_per_sec_forward_512x384' and d['unit'] == 'pairs/s' and d['higher_is_better'] is True
+    assert d['value'] > 0 and d['ms_per_step'] > 0 and d['dtype'] == 'fp16x3' and d['steps'] == 1 and d['warmup'] == 1
+    assert sorted(d['dump_outputs']['files']) == ['pred1_conf.npy', 'pred1_pts3d.npy', 'pred2_conf.npy', 'pred2_pts3d_in_other_view.npy']
+    assert all((out / f).exists() for f in d['dump_outputs']['files'])
+    extras = ('parity_check', 'roofline', 'kernels', 'launch_table', 'latency', 'fast_mode', 'aligner', 'cpu_baseline', 'checkpoint_validation')
+    assert not [k for k in extras if k in d]
