@@ -32,6 +32,24 @@ class ModelConfig(C.Structure):
                 ('dpt_skip_relu_inplace', C.c_int)]
 
 
+class MatchJob(C.Structure):
+    """d3r_match_job (include/dust3r_hip.h)"""
+    _fields_ = [('pts_query', C.c_void_p), ('conf_query', C.c_void_p), ('pts_map', C.c_void_p), ('conf_map', C.c_void_p),
+                ('valid_map', C.c_void_p), ('n_query', C.c_int), ('n_map', C.c_int), ('conf_thr', C.c_float), ('reserved', C.c_int)]
+
+
+class PnpRansacJob(C.Structure):
+    """d3r_pnp_ransac_job (include/dust3r_hip.h)"""
+    _fields_ = [('pts2d', C.c_void_p), ('pts3d', C.c_void_p), ('inlier_mask', C.c_void_p), ('n', C.c_int), ('max_iters', C.c_int),
+                ('fx', C.c_float), ('fy', C.c_float), ('cx', C.c_float), ('cy', C.c_float), ('thr', C.c_float), ('confidence', C.c_float),
+                ('seed', C.c_ulonglong)]
+
+
+class PnpRansacParams(C.Structure):
+    """d3r_pnp_ransac_params (include/dust3r_hip.h)"""
+    _fields_ = [('max_iters', C.c_int), ('max_points', C.c_int)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
@@ -88,6 +106,13 @@ def _load():
         'd3r_segment_sky_workspace_bytes': (C.c_size_t, [i, i]),
         'd3r_segment_sky': (i, [i, vp, i, ip, ip, i, vp, vp, vp]),
         'd3r_sky_color_mask': (i, [i, vp, i, ip, ip, i, vp, vp]),
+        'd3r_match_pairs_workspace': (C.c_size_t, [i, i]),
+        'd3r_match_pairs': (i, [i, vp, i, vp, ip, ip, vp]),
+        'd3r_pnp_ransac_workspace': (C.c_size_t, [i, i]),
+        'd3r_pnp_ransac': (i, [i, vp, C.POINTER(PnpRansacParams), vp, fp, ip, ip, ip, vp]),
+        'd3r_selftest_p3p_host': (i, [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+        'd3r_selftest_p3p_roots_host': (i, [vp, vp, vp, vp]),
+        'd3r_selftest_ransac_iters_host': (i, [C.c_double, C.c_double, i, i]),
         'd3r_row_means': (i, [fp, i, i, i, fp, vp]),
         'd3r_similarity_moments_workspace': (C.c_size_t, [i, i]),
         'd3r_similarity_moments': (i, [i, vp, vp, vp, ip, i, vp, vp, vp]),

@@ -7,8 +7,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['gemm.hip', 'gemm_p4.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'sky.hip', 'engine.hip', 'capi.hip']
-HEADERS = ['common.hpp', 'kernels.hpp', 'aligner_math.hpp', os.path.join('..', '..', 'include', 'dust3r_hip.h')]
+SOURCES = ['gemm.hip', 'gemm_p4.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'sky.hip', 'visloc.hip', 'engine.hip', 'capi.hip']
+HEADERS = ['common.hpp', 'kernels.hpp', 'aligner_math.hpp', 'visloc_math.hpp', os.path.join('..', '..', 'include', 'dust3r_hip.h')]
 LIB = os.path.join(CSRC, 'libdust3r_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-inline-asm']
 # attention.hip: no SLP vectorisation -- its scalar-VALU softmax slices (attention_x3_kernel<..., SC = true>) must stay v_fma_f32 / v_add_f32
@@ -16,7 +16,8 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-res
 # variants of the same kernel use explicit 2-vectors and are not affected.
 EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'gemm_p4.hip': ['-fno-slp-vectorize', '-Rpass-analysis=kernel-resource-usage'],     # gemm_p4.hip: its drain's scalar GELU pieces sit between MFMAs too
                'aligner.hip': ['-Rpass-analysis=kernel-resource-usage'],      # aligner.hip: its report pins the registers / scratch of every aligner kernel (tests read it)
-               'sky.hip': ['-Rpass-analysis=kernel-resource-usage']}          # sky.hip: its report shows the segmentation kernels use no scratch (tests read it)
+               'sky.hip': ['-Rpass-analysis=kernel-resource-usage'],          # sky.hip: its report shows the segmentation kernels use no scratch (tests read it)
+               'visloc.hip': ['-Rpass-analysis=kernel-resource-usage']}       # visloc.hip: same for the matching / PnP-RANSAC kernels
 
 
 def _hipcc():

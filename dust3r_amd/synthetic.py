@@ -308,3 +308,39 @@ def synthetic_mixed_scene(shapes, seed=0):
     return dict(view1=dict(idx=[i for i, j in edges], instance=[str(i) for i, j in edges]),
                 view2=dict(idx=[j for i, j in edges], instance=[str(j) for i, j in edges]),
                 pred1=dict(pts3d=pred_i, conf=conf_i), pred2=dict(pts3d_in_other_view=pred_j, conf=conf_j), loss=None)
+
+
+PNP_K = np.array([[520.0, 0, 300.5], [0, 480.0, 210.25], [0, 0, 1.0]])      # fx != fy, off-centre principal point
+
+
+def pnp_problem(n, outliers, noise, seed, K=PNP_K, size=(640, 480)):
+    """A PnP problem for visual localization: n world points (fp32) in front of a random camera (world -> camera `w2c`, 4x4), their
+    pixels (fp32, N(0, noise) added) in an image of `size` (W, H) under K, and a fraction `outliers` of the pixels moved to random
+    places >= 20 px from their projection. Returns (uv, X, w2c, inlier mask)."""
+    rng = np.random.RandomState(seed)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    W, H = size
+    q = rng.normal(size=4)
+    q /= np.linalg.norm(q)
+    w, x, y, z = q
+    w2c = np.eye(4)
+    w2c[:3, :3] = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                            [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                            [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    w2c[:3, 3] = rng.normal(size=3)
+    uv_true = np.c_[rng.uniform(0, W, n), rng.uniform(0, H, n)]
+    depth = rng.uniform(2, 6, n)
+    Yc = np.c_[(uv_true[:, 0] - cx) / fx * depth, (uv_true[:, 1] - cy) / fy * depth, depth]
+    X = ((Yc - w2c[:3, 3]) @ w2c[:3, :3]).astype(np.float32)
+    Y = X.astype(np.float64) @ w2c[:3, :3].T + w2c[:3, 3]
+    uv = np.stack((fx * Y[:, 0] / Y[:, 2] + cx, fy * Y[:, 1] / Y[:, 2] + cy), axis=-1) + noise * rng.normal(size=(n, 2))
+    inl = np.ones(n, bool)
+    out_idx = rng.choice(n, int(round(outliers * n)), replace=False)
+    inl[out_idx] = False
+    for i in out_idx:
+        while True:
+            cand = np.array([rng.uniform(0, W), rng.uniform(0, H)])
+            if np.linalg.norm(cand - uv[i]) >= 20:
+                uv[i] = cand
+                break
+    return uv.astype(np.float32), X, w2c, inl

@@ -18,10 +18,30 @@ def xy_grid(W, H, device=None, origin=(0, 0), **arange_kw):
 def geotrf(Trf, pts, ncol=None, norm=False):
     """Points (..., d) through transforms of size (d+1)x(d+1) (affine part applied, homogeneous row ignored) or d x d.
     Trf is one matrix, or a batch (B, ., .) matching the leading dimension of pts (B, ..., d). `norm` divides by the last
-    coordinate (projection) and scales by it; `ncol` keeps the first columns. numpy in -> numpy out, torch in -> torch out."""
+    coordinate (projection) and scales by it -- for one (d+1)x(d+1) matrix, by the homogeneous coordinate of the full product, as the
+    reference does (also for a batch of them, except for torch pts (B, H, W, d), where the reference is affine too); `ncol` keeps
+    the first columns. numpy in -> numpy out, torch in -> torch out."""
     is_np = isinstance(Trf, np.ndarray)
     pts = np.asarray(pts) if is_np else torch.as_tensor(pts, dtype=Trf.dtype, device=Trf.device)
     d = pts.shape[-1]
+    einsum_path = not is_np and Trf.ndim == 3 and pts.ndim == 4
+    if norm and Trf.ndim in (2, 3) and Trf.shape[-1] == d + 1 and not einsum_path:
+        # homogeneous (d+1)x(d+1) matrices (a homography; visloc.py:116-117's to_orig): the full projective product divided by the
+        # homogeneous coordinate, as the reference does -- one matrix, or one per leading index of pts. The reference's torch
+        # einsum path (B matrices, pts (B, H, W, d)) is affine and divides by the last coordinate, as below. Elementwise, in a fixed
+        # order, so numpy and torch give the same bits.
+        def coef(i, k):                                  # Trf[i, k], or Trf[:, i, k] broadcast over pts (B, ..., d)
+            return Trf[:, i, k].reshape((-1,) + (1,) * (pts.ndim - 2)) if Trf.ndim == 3 else Trf[i, k]
+        rows = []
+        for i in range(d + 1):
+            acc = pts[..., 0] * coef(i, 0)
+            for k in range(1, d):
+                acc = acc + pts[..., k] * coef(i, k)
+            rows.append(acc + coef(i, d))
+        out = (np.stack if is_np else torch.stack)(rows[:d], -1) / rows[d][..., None]
+        if norm != 1:
+            out = out * norm
+        return out[..., :ncol] if ncol else out
     lin = Trf[..., :d, :d]
     shift = Trf[..., :d, d] if Trf.shape[-1] == d + 1 else None
     if Trf.ndim == 3:                                  # one transform per leading index of pts

@@ -333,6 +333,70 @@ int d3r_sky_color_mask(int n_imgs, const void* rgb, int rgb_is_u8, const int* im
  * two SciPy KD-tree queries in the reference; caller: visloc.py:105). */
 int d3r_nearest_neighbors(const float* query, int n_query, const float* ref, int n_ref, int* idx_out, void* stream);
 
+/* ---- visual localization (csrc/visloc.hip): the per-query loop of the reference's visloc.py:72-165, batched ------------------- */
+
+/* One (query, map view) pair of d3r_match_pairs. All pointers DEVICE. Query pixel p is used when conf_query[p] >= conf_thr, map pixel
+ * p when conf_map[p] >= conf_thr and (valid_map == NULL or valid_map[p] != 0) (visloc.py:90-91). Pointmaps are row-major [H][W][3]. */
+typedef struct {
+    const float* pts_query;     /* [n_query][3] */
+    const float* conf_query;    /* [n_query] */
+    const float* pts_map;       /* [n_map][3] */
+    const float* conf_map;      /* [n_map] */
+    const uint8_t* valid_map;   /* [n_map] or NULL */
+    int n_query, n_map;         /* H0 * W0, H1 * W1 (each <= max_pixels) */
+    float conf_thr;
+    int reserved;
+} d3r_match_job;
+
+/* Mutual nearest neighbours of n_pairs pairs in one launch sequence (no host synchronisation, pairs of any sizes): each side's used
+ * pixels are compacted in raster order, every point gets its exact fp32 nearest neighbour on the other side (d3r_nearest_neighbors'
+ * distance expression; ties to the lowest compacted index), and the mutual pairs are kept. out_counts [n_pairs] int32; out_pairs
+ * [n_pairs][max_pixels][2] int32 (query flat pixel, map flat pixel), the first out_counts[i] rows of pair i in ascending map order
+ * (find_reciprocal_matches' reciprocal_in_P2 order). A pair with an empty side gets 0. jobs: DEVICE array of n_pairs records;
+ * workspace: d3r_match_pairs_workspace(n_pairs, max_pixels) bytes of DEVICE memory (48 bytes per pair and pixel). At most 65535 pairs
+ * per call. */
+size_t d3r_match_pairs_workspace(int n_pairs, int max_pixels);
+int d3r_match_pairs(int n_pairs, const d3r_match_job* jobs, int max_pixels, void* workspace, int* out_counts, int* out_pairs, void* stream);
+
+/* One PnP-RANSAC problem of d3r_pnp_ransac: n correspondences, pixels pts2d [n][2] (undistorted) and world points pts3d [n][3], DEVICE
+ * fp32. Pinhole fx, fy, cx, cy; reprojection threshold thr in pixels; at most max_iters hypotheses, stopped early by OpenCV's
+ * RANSACUpdateNumIters at `confidence`; sampling keyed by `seed` and the hypothesis index only. inlier_mask: DEVICE uint8 [n] output
+ * (inliers of the returned pose), or NULL. */
+typedef struct {
+    const float* pts2d;
+    const float* pts3d;
+    uint8_t* inlier_mask;
+    int n, max_iters;
+    float fx, fy, cx, cy, thr, confidence;
+    unsigned long long seed;
+} d3r_pnp_ransac_job;
+
+/* HOST struct: max_iters >= every job's max_iters (rounds launched), max_points >= every job's n (grid and workspace size) */
+typedef struct {
+    int max_iters, max_points;
+} d3r_pnp_ransac_params;
+
+/* PnP-RANSAC of n_jobs independent problems in one call, everything on the device: per hypothesis a counter-based sample of 4 points,
+ * fp64 P3P on three with the fourth choosing the root, the inlier count (in front of the camera, squared pixel error <= thr^2);
+ * hypotheses in rounds with the per-job stopping rule kept in device memory; the best (largest support, then lowest index) polished by
+ * Levenberg-Marquardt on the reprojection error over its inliers (fp64 normal equations, 6x6 solve on the device), then its inliers
+ * recounted. out_poses [n_jobs][12] fp64 world -> camera [R | t] row-major; out_inliers [n_jobs]; out_status [n_jobs] 1 = success,
+ * 0 = failure (n <= 4, or no hypothesis supported by more than its 4 sample points). out_stats: NULL, or [n_jobs][2] int32 = (hypotheses
+ * drawn before the stopping rule ended the job, index of the best hypothesis or -1). Bit-identical for a job alone or in any batch.
+ * At most 65535 jobs per call.
+ * jobs: DEVICE array; workspace: d3r_pnp_ransac_workspace(n_jobs, params->max_points) bytes of DEVICE memory. */
+size_t d3r_pnp_ransac_workspace(int n_jobs, int max_points);
+int d3r_pnp_ransac(int n_jobs, const d3r_pnp_ransac_job* jobs, const d3r_pnp_ransac_params* params, void* workspace, double* out_poses,
+                   int* out_inliers, int* out_status, int* out_stats, void* stream);
+
+/* Host-only self tests of the shared visloc math (no GPU touched; all pointers HOST). d3r_selftest_p3p_host: P3P on 3 of 4 pixel /
+ * world correspondences, the 4th picking the root; pose_out [12] world -> camera; returns 1 when a pose was found.
+ * d3r_selftest_p3p_roots_host: every P3P solution for 3 unit bearings f [3][3] and world points X [3][3] (R_out [4][9], t_out [4][3]);
+ * returns their number. d3r_selftest_ransac_iters_host: the stopping rule. */
+int d3r_selftest_p3p_host(const double* uv, const double* X, double fx, double fy, double cx, double cy, double* pose_out);
+int d3r_selftest_p3p_roots_host(const double* f, const double* X, double* R_out, double* t_out);
+int d3r_selftest_ransac_iters_host(double confidence, double ep, int model_points, int max_iters);
+
 /* ---- scene bootstrap: the one-shot initialisation of the aligner (csrc/bootstrap.hip) -----------------------------------------
  * Replaces the per-edge / per-image host loops of dust3r/cloud_opt/init_im_poses.py:67-287 (roma.rigid_points_registration at
  * :220-223, estimate_focal -> post_process.py:40-56, fast_pnp -> cv2.solvePnPRansac at :247-287) and pair_viewer.py:30-76. All
