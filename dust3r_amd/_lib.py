@@ -106,6 +106,8 @@ def _load():
         'd3r_segment_sky_workspace_bytes': (C.c_size_t, [i, i]),
         'd3r_segment_sky': (i, [i, vp, i, ip, ip, i, vp, vp, vp]),
         'd3r_sky_color_mask': (i, [i, vp, i, ip, ip, i, vp, vp]),
+        'd3r_scene_mesh_workspace_bytes': (C.c_size_t, [i, i]),
+        'd3r_scene_mesh': (i, [i, vp, vp, vp, i, ip, ip, i, i, vp, vp, vp, vp, vp, vp, vp]),
         'd3r_match_pairs_workspace': (C.c_size_t, [i, i]),
         'd3r_match_pairs': (i, [i, vp, i, vp, ip, ip, vp]),
         'd3r_pnp_ransac_workspace': (C.c_size_t, [i, i]),

@@ -436,6 +436,25 @@ D3R_DEV int xcd_remap(int bid, int nwg) {
     return base + idx;
 }
 
+// exclusive prefix of `flag` over a 1024-thread workgroup (wave ballots, then the 16 wave counts through LDS); returns the position of
+// this thread, *total = the workgroup's count. wave_sums: 16 ints of LDS; every thread of the workgroup must call it.
+D3R_DEV int block_scan_1024(bool flag, int* wave_sums, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_sums[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int w = 0; w < 1024 / 64; ++w) {
+        const int s = wave_sums[w];
+        before += w < wave ? s : 0;
+        all += s;
+    }
+    __syncthreads();
+    *total = all;
+    return before + in_wave;
+}
+
 // ------------------------------------------------------------------------------ head epilogues
 // postprocess (dust3r/heads/postprocess.py:10-58). depth_mode (reg_dense_depth :23-47; the reference asserts the bounds away, :29-30):
 //   'exp'    pts = xyz / max(|xyz|, 1e-8) * expm1(|xyz|)      (the released checkpoints, model.py:61)

@@ -57,24 +57,6 @@ D3R_DEV int* ws_pix(char* base, int max_pixels, int side) { return (int*)(base +
 D3R_DEV int* ws_nn(char* base, int max_pixels, int side) { return ws_pix(base, max_pixels, side) + max_pixels; }
 D3R_DEV int* ws_count(char* base, int max_pixels) { return ws_pix(base, max_pixels, 2); }
 
-// exclusive prefix of `flag` over a 1024-thread workgroup; returns the position of this thread, *total = the workgroup's count
-D3R_DEV int block_scan_1024(bool flag, int* wave_sums, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_sums[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int w = 0; w < CNT / 64; ++w) {
-        const int s = wave_sums[w];
-        before += w < wave ? s : 0;
-        all += s;
-    }
-    __syncthreads();
-    *total = all;
-    return before + in_wave;
-}
-
 __global__ __launch_bounds__(CNT) void match_compact_kernel(const d3r_match_job* __restrict__ jobs, int max_pixels, void* workspace) {
     __shared__ int wave_sums[CNT / 64];
     const int side = blockIdx.x, pair = blockIdx.y;

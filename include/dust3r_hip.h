@@ -328,6 +328,27 @@ int d3r_segment_sky(int n_imgs, const void* rgb, int rgb_is_u8, const int* img_h
 int d3r_sky_color_mask(int n_imgs, const void* rgb, int rgb_is_u8, const int* img_h_dev, const int* img_w_dev, int max_area, uint8_t* mask_out,
                        void* stream);
 
+/* Geometry of the GLB export of a scene (dust3r/demo.py:66-107 _convert_scene_output_to_glb) for n views in one call. pts [n][max_area][3]
+ * DEVICE fp32, mask [n][max_area] DEVICE uint8 (nonzero = valid), rgb [n][max_area][3] DEVICE (uint8 when rgb_is_u8, else fp32 in [0, 1]),
+ * row-major H x W per view; img_h / img_w: DEVICE int arrays. The colour q of a pixel is its byte (uint8) or floor(255 c + 1/2) clamped to
+ * [0, 255] (fp32 product and sum; NaN -> 0).
+ * Mesh mode (as_pointcloud = 0): the faces of cat_meshes([pts3d_to_trimesh(img_i, pts_i, mask_i) ...]) (dust3r/viz.py:38-87): per view, every
+ *   valid upper triangle (p, p + 1, p + W) of quad p in raster order, the same reversed, every valid lower triangle (p + 1, p + W, p + W + 1),
+ *   the same reversed (a triangle is valid when its three pixels are); vertex indices offset by the h w vertices of every earlier view.
+ *   faces_out [sum 4 (h - 1)(w - 1)][3] DEVICE uint32 (the first sum counts_out rows written, views in order). colors_out [sum h w] RGBA8
+ *   per vertex: the per-channel integer mean (sum + k / 2) / k of the colours of the k valid faces that use it (an upper triangle takes the
+ *   colour of its top-left pixel, a lower one of its bottom-right pixel), the vertex's own q when k = 0; alpha 255. bounds_out [6] fp32:
+ *   component-wise min, max of pts over the vertices that a valid face uses. points_out is not used (may be NULL).
+ * Point-cloud mode (as_pointcloud = 1): points_out [sum h w][3] fp32 and colors_out [sum h w] RGBA8 (q, alpha 255) of every valid pixel, views
+ *   in order then raster order; bounds_out over those points. faces_out is not used (may be NULL).
+ * counts_out [n] DEVICE int64: faces (mesh) or points of each view. Bounds are (+inf, -inf) when nothing is emitted. The compaction is
+ * stable and atomic-free: the same bytes on every run. The caller keeps sum h w below 2^32 (uint32 indices). workspace:
+ * d3r_scene_mesh_workspace_bytes(n, max_area) bytes of DEVICE memory. At most 65535 views; no allocation, no synchronisation. */
+size_t d3r_scene_mesh_workspace_bytes(int n_views, int max_area);
+int d3r_scene_mesh(int n_views, const float* pts, const uint8_t* mask, const void* rgb, int rgb_is_u8, const int* img_h_dev, const int* img_w_dev,
+                   int max_area, int as_pointcloud, uint32_t* faces_out, float* points_out, uint32_t* colors_out, long long* counts_out,
+                   float* bounds_out, void* workspace, void* stream);
+
 /* exhaustive 3-D nearest neighbour: idx_out[q] = argmin_r |query[q] - ref[r]|^2 (lowest index on ties); query [n_query][3],
  * ref [n_ref][3] DEVICE fp32, idx_out DEVICE int32. The building block of find_reciprocal_matches (dust3r/utils/geometry.py:345-361,
  * two SciPy KD-tree queries in the reference; caller: visloc.py:105). */
