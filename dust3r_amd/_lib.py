@@ -108,6 +108,11 @@ def _load():
         'd3r_sky_color_mask': (i, [i, vp, i, ip, ip, i, vp, vp]),
         'd3r_scene_mesh_workspace_bytes': (C.c_size_t, [i, i]),
         'd3r_scene_mesh': (i, [i, vp, vp, vp, i, ip, ip, i, i, vp, vp, vp, vp, vp, vp, vp]),
+        'd3r_render_project': (i, [i, fp, i, fp, i, fp, f, ip, vp, vp]),
+        'd3r_render_clear': (i, [i, i, i, vp, vp]),
+        'd3r_render_points': (i, [i, fp, vp, C.c_uint32, i, fp, i, fp, f, i, i, i, vp, vp, vp]),
+        'd3r_render_triangles': (i, [i, vp, i, fp, C.c_uint32, i, fp, i, fp, f, i, i, vp, vp, vp]),
+        'd3r_render_resolve': (i, [i, fp, i, fp, f, i, i, vp, i, C.c_uint32, vp, i, C.c_uint32, vp, i, fp, vp, C.c_uint32, vp, fp, ip, vp]),
         'd3r_match_pairs_workspace': (C.c_size_t, [i, i]),
         'd3r_match_pairs': (i, [i, vp, i, vp, ip, ip, vp]),
         'd3r_pnp_ransac_workspace': (C.c_size_t, [i, i]),

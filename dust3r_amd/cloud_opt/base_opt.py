@@ -298,8 +298,73 @@ class BasePCOptimizer(nn.Module):
             conf[sky] = 0
         return res
 
-    def show(self, *a, **k):
-        raise NotImplementedError('trimesh visualisation is outside this engine; export get_pts3d()/get_im_poses() instead')
+    @torch.no_grad()
+    def show(self, show_pw_cams=False, show_pw_pts3d=False, cam_size=None, cam_colors=None, **kw):
+        """The reference's show() (base_opt.py:297-323) without a window: the masked cloud in the images' colours (a random colour per view
+        when the scene has no images), one glyph per camera in a random colour, on request the pairwise cameras and clouds; drawn on the GPU
+        by `viz.SceneViz.show(**kw)` (outfile=..., size=..., point_size=...). Returns the SceneViz; the picture is its `.image`. The colours are
+        drawn from numpy's global generator as in the reference, so two calls differ in them (the rasteriser itself is deterministic);
+        cam_colors (new): one (r, g, b) per image instead, for the same picture on every call."""
+        if self.device.type != 'cuda':
+            raise _lib.D3RError('show renders on the GPU (dust3r_amd has no CPU execution path)')
+        from ..viz import SceneViz, auto_cam_size
+        viz = SceneViz(self.device)
+        pts3d, masks = self.get_pts3d(), self.get_masks()
+        if cam_colors is None:
+            colors = [tuple(c) for c in np.random.randint(0, 256, size=(self.n_imgs, 3)).tolist()]
+        else:
+            colors = [tuple(int(v) for v in c) for c in cam_colors]
+            if len(colors) != self.n_imgs or any(len(c) != 3 for c in colors):
+                raise ValueError(f'show: cam_colors needs one (r, g, b) per image, {self.n_imgs} here')
+        if self.imgs is None:
+            for n in range(self.n_imgs):
+                viz.add_pointcloud(pts3d[n], colors[n], masks[n])
+        else:
+            viz.add_pointcloud(list(pts3d), list(self.imgs), list(masks))
+        im_poses = self.get_im_poses().detach().cpu().numpy()
+        if cam_size is None:
+            cam_size = auto_cam_size(im_poses)
+        viz.add_cameras(im_poses, self.get_focals().detach().cpu().numpy().reshape(-1), colors=colors, imsizes=self.imsizes, cam_size=cam_size)
+        if show_pw_cams:
+            pw_poses = self.get_pw_poses().detach()
+            viz.add_cameras(pw_poses.cpu().numpy(), imsizes=[self.imsizes[i] for i, j in self.edges], color=(192, 0, 192), cam_size=cam_size)
+            if show_pw_pts3d:
+                pts = [self.pred_i[edge_str(i, j)] @ pw_poses[e, :3, :3].T + pw_poses[e, :3, 3] for e, (i, j) in enumerate(self.edges)]
+                viz.add_pointcloud(pts, (128, 0, 128))
+        viz.show(**kw)
+        return viz
+
+    @torch.no_grad()
+    def render_views(self, point_size=1, as_mesh=False, return_depth=False):
+        """The fused scene re-drawn from every view's own camera, intrinsics and size -- does the cloud, seen from camera i, look like
+        picture i? All views of one size share one call of the rasteriser (one call in all when the sizes agree). The cloud is the masked
+        points (`get_masks()`), or with as_mesh the mesh of the GLB export. Returns a list of (H, W, 3) uint8 images, or with return_depth
+        a list of (image, depth (H, W) float32, inf where nothing was drawn)."""
+        if self.imgs is None:
+            raise ValueError('render_views needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
+        if self.device.type != 'cuda':
+            raise _lib.D3RError('render_views renders on the GPU (dust3r_amd has no CPU execution path)')
+        from ..viz import SceneViz, scene_mesh_batch
+        viz = SceneViz(self.device)
+        masks = self.get_masks()
+        if as_mesh:
+            pts3d = self.get_pts3d(raw=True)
+            geo = scene_mesh_batch(self.imgs, pts3d if isinstance(pts3d, torch.Tensor) else self.get_pts3d(), masks, self.device, to_host=False)
+            if len(geo['faces']):
+                viz.add_mesh(geo['positions'], geo['faces'], geo['colors'])
+        else:
+            viz.add_pointcloud(list(self.get_pts3d()), list(self.imgs), list(masks))
+        poses, K = self.get_im_poses().detach(), self.get_intrinsics().detach()
+        out = [None] * self.n_imgs
+        if viz.bounds() is None:
+            return [np.full((h, w, 3), 255, np.uint8) if not return_depth else (np.full((h, w, 3), 255, np.uint8), np.full((h, w), np.inf, np.float32))
+                    for h, w in self.imshapes]
+        for shape in sorted(set(map(tuple, self.imshapes))):
+            idx = [i for i, s in enumerate(self.imshapes) if tuple(s) == shape]
+            res = viz.render(poses[idx], K[idx], size=(shape[1], shape[0]), point_size=point_size, return_depth=return_depth)
+            for k, i in enumerate(idx):
+                out[i] = (res['rgb'][k], res['depth'][k]) if return_depth else res[k]
+        return out
 
     # ------------------------------------------------------------------ engine
     def _engine_signature(self):

@@ -6,7 +6,8 @@ binary:
   are the untransformed fp32 points;
 - the scene: a TRIANGLES primitive (indices, POSITION, COLOR_0 = the face colours averaged onto the vertices) or, with as_pointcloud, a
   POINTS primitive (POSITION, COLOR_0); left out when nothing is valid;
-- one wireframe per camera and, unless transparent_cams, its picture on a textured quad (PNG of np.uint8(255 * img))."""
+- one wireframe per camera and, unless transparent_cams, its picture on a textured quad (PNG of np.uint8(255 * img)).
+`render_turntable` (new; the reference has no headless output) draws the same scene into PNG frames on the GPU instead."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -15,7 +16,7 @@ import torch
 
 from .glb import ARRAY_BUFFER, FLOAT, POINTS, TRIANGLES, GlbBuilder
 from .utils.device import to_numpy, usable_cpus
-from .viz import CAM_COLORS, OPENGL, scene_camera_geometry, scene_mesh_batch
+from .viz import CAM_COLORS, OPENGL, SceneViz, auto_cam_size, scene_camera_geometry, scene_mesh_batch, turntable_poses
 
 
 def _device_of(*seqs):
@@ -135,3 +136,54 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
         msk = scene.get_masks()
     return _convert_scene_output_to_glb(outdir, rgbimg, pts3d, msk, focals, cams2world, as_pointcloud=as_pointcloud,
                                         transparent_cams=transparent_cams, cam_size=cam_size, silent=silent)
+
+
+def render_turntable(outdir, scene, n_frames=36, size=(1024, 768), as_pointcloud=True, min_conf_thr=3, mask_sky=False, clean_depth=False,
+                     point_size=2, focal=None, cam_size=None, transparent_cams=False, elevation_deg=20.0, background=(255, 255, 255), silent=True):
+    """n_frames pictures of a reconstructed scene from a circle round it, written as outdir/turntable_000.png ...; returns the file names.
+    The same pre-processing switches as get_3D_model_from_scene (clean_depth, mask_sky, min_conf_thr, as_pointcloud: the masked cloud or the
+    export's mesh) and the same camera glyphs (wire only; none with transparent_cams). The circle lies about the first camera's "down"
+    axis through the centre of the scene's bounds, raised by elevation_deg, at the distance where the bounds fit the frame
+    (viz.turntable_poses); focal defaults to 1.1 min(size). All frames are drawn in ONE call of the rasteriser; the PNGs are encoded on a
+    thread pool."""
+    if scene is None:
+        return None
+    if scene.imgs is None:
+        raise ValueError('render_turntable needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
+    if clean_depth:
+        scene = scene.clean_pointcloud()
+    if mask_sky:
+        scene = scene.mask_sky()
+    with torch.no_grad():
+        focals = scene.get_focals().cpu().numpy().reshape(-1)
+        cams2world = scene.get_im_poses().cpu().numpy()
+        scene.min_conf_thr = float(scene.conf_trf(torch.tensor(min_conf_thr)))
+        msk = scene.get_masks()
+        viz = SceneViz(scene.device)
+        if as_pointcloud:
+            viz.add_pointcloud(list(scene.get_pts3d()), list(scene.imgs), list(msk))
+        else:
+            pts3d = scene.get_pts3d(raw=True)
+            geo = scene_mesh_batch(scene.imgs, pts3d if isinstance(pts3d, torch.Tensor) else scene.get_pts3d(), msk, scene.device, to_host=False)
+            if len(geo['faces']):
+                viz.add_mesh(geo['positions'], geo['faces'], geo['colors'])
+        bounds = viz.bounds()
+        if bounds is None:
+            raise ValueError('render_turntable: no valid point in the scene (lower min_conf_thr)')
+        if not transparent_cams:
+            viz.add_cameras(cams2world, focals, imsizes=scene.imsizes, colors=[CAM_COLORS[i % len(CAM_COLORS)] for i in range(len(cams2world))],
+                            cam_size=auto_cam_size(cams2world) if cam_size is None else cam_size)
+        focal = 1.1 * min(size) if focal is None else float(focal)
+        poses = turntable_poses(bounds, n_frames, focal, size, down=cams2world[0][:3, 1], elevation_deg=elevation_deg)
+        frames = viz.render(poses, focal, size=size, point_size=point_size, background=background)
+    os.makedirs(outdir, exist_ok=True)
+    names = [os.path.join(outdir, f'turntable_{k:03d}.png') for k in range(n_frames)]
+
+    def write(k):
+        with open(names[k], 'wb') as f:
+            f.write(_png(frames[k]))
+    with ThreadPoolExecutor(max(1, min(usable_cpus(), n_frames))) as ex:
+        list(ex.map(write, range(n_frames)))
+    if not silent:
+        print('(wrote', n_frames, 'frames to', outdir, ')')
+    return names

@@ -3,8 +3,10 @@
   C ABI `d3r_segment_sky`) where the reference runs OpenCV and SciPy per image;
 - the geometry of the GLB export (`pts3d_to_trimesh` + `cat_meshes`, viz.py:38-87, or the masked point cloud): `scene_mesh_batch`, one call
   for all views (csrc/mesh.hip, C ABI `d3r_scene_mesh`), and the camera glyphs of `add_scene_cam` (viz.py:246-319) restated without trimesh
-  (`scene_camera_geometry`). dust3r_amd/glb.py writes the file, dust3r_amd/demo.py mirrors the demo's export functions.
-The viewers (SceneViz, show_*) are not mirrored."""
+  (`scene_camera_geometry`). dust3r_amd/glb.py writes the file, dust3r_amd/demo.py mirrors the demo's export functions;
+- `SceneViz` (viz.py:119-209) as a HEADLESS viewer: the same `add_pointcloud` / `add_camera` / `add_cameras`, and `render` / `show` that draw
+  the scene into images with the rasteriser of csrc/render.hip (`render_batch`, C ABI `d3r_render_*`) instead of opening a window.
+The interactive viewers (a window, show_raw_pointcloud*) are not mirrored."""
 import numpy as np
 import torch
 
@@ -68,7 +70,7 @@ def _tensor(x):
 
 
 @torch.no_grad()
-def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False):
+def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False, to_host=True):
     """The geometry of the demo's GLB export for all views in one GPU call (csrc/mesh.hip).
 
     imgs: H x W x 3 RGB images (numpy or tensors, all uint8 or all floating in [0, 1]; sizes may differ). pts3d: per view an (H, W, 3) map, or
@@ -81,7 +83,9 @@ def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False):
 
     Returns a dict of host arrays: positions (N, 3) float32, colors (N, 4) uint8 (RGBA), faces (F, 3) uint32 or None, counts (n,) int64 (faces
     or points per view), bounds = (min (3,), max (3,)) float32 of the positions a face uses (mesh) or of the points (NaN components are
-    skipped; +inf / -inf where no value is left), None when nothing is valid. The per-view counts are the one host synchronisation."""
+    skipped; +inf / -inf where no value is left), None when nothing is valid. The per-view counts are the one host synchronisation.
+    With to_host=False the large outputs stay on the device (what the renderer takes): positions (N, 3) float32, colors (N,) int32 packed
+    r | g << 8 | b << 16 | 255 << 24, faces (F, 3) int32 as torch tensors; counts and bounds as above."""
     from .utils.device import host_tensor
     _lib.require_device()
     device = torch.device(device)
@@ -137,6 +141,13 @@ def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False):
         counts = small[:n].numpy().copy()
         lo, hi = small[n:].view(torch.float32).numpy()[:3].copy(), small[n:].view(torch.float32).numpy()[3:].copy()
         total = int(counts.sum())
+        if not to_host:
+            if as_pointcloud:
+                dev_pos = points[:total]
+            else:
+                dev_pos = pts.view(n_vert, 3) if n * max_area == n_vert else torch.cat([pts[i, :a] for i, a in enumerate(areas)])
+            return dict(positions=dev_pos, colors=colors[:total] if as_pointcloud else colors, faces=None if as_pointcloud else faces[:total],
+                        counts=counts, bounds=(lo, hi) if total > 0 else None)
         if as_pointcloud:
             positions = host_tensor((total, 3), torch.float32)
             positions.copy_(points[:total])
@@ -215,3 +226,422 @@ def scene_camera_geometry(pose_c2w, focal, imsize, screen_width=0.03):
     image_vertices = _apply(transform, cone[[2, 1, 4, 3]])
     return dict(wire_vertices=verts, wire_faces=np.array(faces, dtype=np.int64), image_vertices=image_vertices,
                 image_faces=np.array([[0, 1, 2], [0, 2, 3], [2, 1, 0], [3, 2, 0]]), image_uv=np.float32([[0, 0], [1, 0], [1, 1], [0, 1]]))
+
+
+# ---- headless rendering --------------------------------------------------------------------------------------------------------------
+RENDER_GUARD = 8192          # px: the largest frame, and the guard band of the vertex stage (include/dust3r_hip.h d3r_render_*)
+ZQ_MAX = 0xFFFFFF
+
+
+def auto_cam_size(im_poses):
+    """The reference's rule (viz.py:115-116): a tenth of the median distance between the camera centres."""
+    c = np.asarray(im_poses, dtype=np.float64)[:, :3, 3]
+    return 0.1 * float(np.median(np.linalg.norm(c[:, None] - c[None], axis=-1)))
+
+
+def pack_rgba(color, n=None):
+    """Colours as the kernels take them, int32 r | g << 8 | b << 16 | 255 << 24: `color` is (..., 3) uint8, or floating in [0, 1] (converted
+    like the GLB export: floor(255 c + 1/2), clamped), numpy or tensor; a single colour is repeated `n` times when `n` is given."""
+    t = _tensor(color)
+    if t.is_floating_point():
+        t = (t.float() * 255 + 0.5).floor().clamp(0, 255)
+    t = t.reshape(-1, 3).to(torch.int32)
+    if ((t < 0) | (t > 255)).any():
+        raise ValueError('colours are 0 ... 255 (integers) or 0 ... 1 (floating)')
+    packed = t[:, 0] | (t[:, 1] << 8) | (t[:, 2] << 16) | torch.tensor(-16777216, dtype=torch.int32, device=t.device)
+    if n is not None and len(packed) == 1:
+        packed = packed.expand(n)
+    return packed.contiguous()
+
+
+def world_to_cam(cam2world):
+    """(F, 4, 4) or (4, 4) camera-to-world poses -> (F, 12) float32 rows [R | t] of their inverses, inverted in fp64 on the host."""
+    c2w = np.asarray(_to_numpy(cam2world), dtype=np.float64).reshape(-1, 4, 4)
+    return np.ascontiguousarray(np.linalg.inv(c2w)[:, :3, :].reshape(-1, 12).astype(np.float32))
+
+
+def _to_numpy(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def intrinsics_rows(focal_or_K, n_cams, size):
+    """(F, 4) float32 (fx, fy, cx, cy) from a focal (scalar or one per camera; principal point W/2, H/2 as everywhere in dust3r) or from
+    3 x 3 intrinsics (one or F)."""
+    W, H = size
+    a = np.asarray(_to_numpy(focal_or_K), dtype=np.float64)
+    if a.shape[-2:] == (3, 3):
+        K = np.broadcast_to(a.reshape(-1, 3, 3), (n_cams, 3, 3)) if a.size == 9 else a.reshape(-1, 3, 3)
+        rows = np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], axis=1)
+    else:
+        f = np.broadcast_to(a.reshape(-1), (n_cams,)) if a.size == 1 else a.reshape(-1)
+        rows = np.stack([f, f, np.full(len(f), W / 2), np.full(len(f), H / 2)], axis=1)
+    if rows.shape != (n_cams, 4) or not np.isfinite(rows).all() or (rows[:, :2] <= 0).any():
+        raise ValueError(f'intrinsics for {n_cams} cameras: got shape {a.shape} (positive finite focals needed)')
+    return np.ascontiguousarray(rows.astype(np.float32))
+
+
+def _dev(x, device, dtype):
+    return None if x is None else _tensor(x).to(device=device, dtype=dtype).contiguous()
+
+
+@torch.no_grad()
+def render_project(positions, w2c, intrinsics, near, device):
+    """The vertex stage alone (d3r_render_project): positions (N, 3), w2c (F, 12) or (F, 16) [R | t] rows, intrinsics (F, 4) -> device
+    tensors sxy (F, N, 2) int32 in 1/16 pixel and zq (F, N) int64 (0xFFFFFFFF = invalid)."""
+    _lib.require_device()
+    device = torch.device(device)
+    pos = _dev(positions, device, torch.float32).reshape(-1, 3)
+    cams = _dev(w2c, device, torch.float32)
+    intr = _dev(intrinsics, device, torch.float32)
+    F = cams.shape[0]
+    if cams.ndim != 2 or cams.shape[1] not in (12, 16) or tuple(intr.shape) != (F, 4) or len(pos) == 0:
+        raise ValueError(f'render_project: positions {tuple(pos.shape)}, w2c {tuple(cams.shape)}, intrinsics {tuple(intr.shape)}')
+    sxy = torch.empty((F, len(pos), 2), dtype=torch.int32, device=device)
+    zq = torch.empty((F, len(pos)), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        check(lib.d3r_render_project(len(pos), ptr(pos), F, ptr(cams), cams.shape[1], ptr(intr), float(near), ptr(sxy), ptr(zq), current_stream()),
+              'render_project')
+    return sxy, zq.to(torch.int64) & 0xFFFFFFFF
+
+
+@torch.no_grad()
+def render_batch(cam2world, intrinsics, size, device, points=None, point_colors=None, point_mask=None, vertices=None, faces=None,
+                 vertex_colors=None, point_size=1, background=(255, 255, 255), near=0.01, return_depth=False, return_ids=False,
+                 return_keys=False, to_host=True, stats=False):
+    """F images of one scene in one call of the rasteriser (csrc/render.hip; conventions in include/dust3r_hip.h, d3r_render_*).
+
+    cam2world: (F, 4, 4) camera-to-world poses (OpenCV axes); intrinsics: (F, 4) rows (fx, fy, cx, cy) (`intrinsics_rows`); size = (W, H).
+    points (N, 3) with point_colors (N,) packed (`pack_rgba`) and point_mask (N,) or None: drawn as point_size squares, ids 0 ... N - 1.
+    vertices (V, 3), faces (M, 3) indices, vertex_colors (V,) packed: drawn as triangles, ids N ... N + M - 1. Numpy inputs are uploaded,
+    device tensors are used where they are.
+
+    Returns a dict: rgb (F, H, W, 3) uint8, and on request depth (F, H, W) float32 (inf = background), ids (F, H, W) int32 (-1 =
+    background), keys (F, H, W) int64 (the raw frame buffer, (zq << 32) | id, -1 = empty), stats = (candidate samples, atomics issued).
+    Host arrays when to_host, else device tensors."""
+    W, H = int(size[0]), int(size[1])
+    if not (0 < W <= RENDER_GUARD and 0 < H <= RENDER_GUARD):
+        raise ValueError(f'render: size (W, H) = {size} must lie in 1 ... {RENDER_GUARD}')
+    if not 1 <= int(point_size) <= 16:
+        raise ValueError(f'render: point_size {point_size} must lie in 1 ... 16')
+    if not (near > 0 and np.isfinite(near)):
+        raise ValueError(f'render: near = {near} must be positive and finite')
+    _lib.require_device()
+    device = torch.device(device)
+    cams = torch.from_numpy(world_to_cam(cam2world)).to(device)
+    F = cams.shape[0]
+    intr = _dev(intrinsics, device, torch.float32)
+    if tuple(intr.shape) != (F, 4):
+        raise ValueError(f'render: {F} poses, intrinsics of shape {tuple(intr.shape)}')
+    n_pts = n_faces = n_vert = 0
+    pts = pcol = pmask = verts = fcs = vcol = None
+    if points is not None:
+        pts = _dev(points, device, torch.float32).reshape(-1, 3)
+        n_pts = len(pts)
+    if n_pts:
+        pcol = _dev(point_colors, device, torch.int32).reshape(-1)
+        pmask = None if point_mask is None else _dev(point_mask, device, torch.uint8).reshape(-1)
+        if len(pcol) != n_pts or (pmask is not None and len(pmask) != n_pts):
+            raise ValueError(f'render: {n_pts} points, {len(pcol)} colours, mask of {None if pmask is None else len(pmask)}')
+    if faces is not None and len(faces):
+        verts = _dev(vertices, device, torch.float32).reshape(-1, 3)
+        fcs = _tensor(faces)
+        fcs = (fcs.view(torch.int32) if fcs.dtype == torch.uint32 else fcs.to(torch.int32)).to(device).reshape(-1, 3).contiguous()
+        vcol = _dev(vertex_colors, device, torch.int32).reshape(-1)
+        n_faces, n_vert = len(fcs), len(verts)
+        if len(vcol) != n_vert or n_vert == 0:
+            raise ValueError(f'render: {n_vert} vertices, {len(vcol)} colours')
+    if n_pts + n_faces >= 2 ** 31:
+        raise ValueError(f'render: {n_pts} points + {n_faces} faces do not fit the 31-bit primitive id')
+    bg = int(pack_rgba(np.asarray(background, dtype=np.uint8))[0]) & 0xFFFFFFFF
+    fb = torch.empty((F, H, W), dtype=torch.int64, device=device)
+    rgb = torch.empty((F, H, W, 3), dtype=torch.uint8, device=device)
+    depth = torch.empty((F, H, W), dtype=torch.float32, device=device) if return_depth else None
+    ids = torch.empty((F, H, W), dtype=torch.int32, device=device) if return_ids else None
+    st = torch.zeros((2,), dtype=torch.int64, device=device) if stats else None
+    with torch.cuda.device(device):
+        stream = current_stream()
+        check(lib.d3r_render_clear(F, W, H, ptr(fb), stream), 'render_clear')
+        if n_pts:
+            check(lib.d3r_render_points(n_pts, ptr(pts), ptr(pmask), 0, F, ptr(cams), 12, ptr(intr), float(near), W, H, int(point_size), ptr(fb),
+                                        ptr(st), stream), 'render_points')
+        if n_faces:
+            check(lib.d3r_render_triangles(n_faces, ptr(fcs), n_vert, ptr(verts), n_pts, F, ptr(cams), 12, ptr(intr), float(near), W, H, ptr(fb),
+                                           ptr(st), stream), 'render_triangles')
+        check(lib.d3r_render_resolve(F, ptr(cams), 12, ptr(intr), float(near), W, H, ptr(fb), n_pts, 0, ptr(pcol), n_faces, n_pts, ptr(fcs), n_vert,
+                                     ptr(verts), ptr(vcol), bg, ptr(rgb), ptr(depth), ptr(ids), stream), 'render_resolve')
+    out = dict(rgb=rgb)
+    if return_depth:
+        out['depth'] = depth
+    if return_ids:
+        out['ids'] = ids
+    if return_keys:
+        out['keys'] = fb
+    if to_host:
+        from .utils.device import host_tensor              # huge pages for the large copies of a many-frame call
+        host = {k: host_tensor(v.shape, v.dtype) for k, v in out.items()}
+        for k, v in out.items():
+            host[k].copy_(v)
+        out = {k: v.numpy() for k, v in host.items()}
+    if stats:
+        out['stats'] = tuple(int(v) for v in st.cpu())
+    return out
+
+
+def look_at(eye, target, down=(0.0, 1.0, 0.0)):
+    """Camera-to-world pose (4 x 4, fp64, OpenCV axes: x right, y down, z forward) of a camera at `eye` looking at `target`, its y axis as
+    close to `down` as the viewing direction allows."""
+    eye, target = np.asarray(eye, dtype=np.float64), np.asarray(target, dtype=np.float64)
+    z = target - eye
+    if not np.linalg.norm(z) > 0:
+        raise ValueError('look_at: eye and target coincide')
+    z = z / np.linalg.norm(z)
+    d = np.asarray(down, dtype=np.float64)
+    x = np.cross(d, z)
+    if np.linalg.norm(x) < 1e-9:                          # looking along `down`: any perpendicular will do
+        x = np.cross(np.roll(d, 1) + np.array([0.3, 0.5, 0.7]), z)
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)
+    pose = np.eye(4)
+    pose[:3, 0], pose[:3, 1], pose[:3, 2], pose[:3, 3] = x, y, z, eye
+    return pose
+
+
+def fit_distance(radius, focal, size, margin=1.1):
+    """How far from the centre of a sphere of `radius` a camera of `focal` and size (W, H) stands so that the sphere fits the frame with
+    `margin`: radius margin / sin(half the smaller field of view)."""
+    half = np.arctan(min(size) / (2.0 * float(focal)))
+    return float(radius) * margin / np.sin(half)
+
+
+def default_viewpoint(cam2world0, bounds, focal, size):
+    """The viewpoint of `SceneViz.show()`: the first camera's orientation, looking at the centre of the bounds, pulled back ALONG ITS OWN
+    AXIS until the bounding sphere (centre = mid point of `bounds`, radius = half their diagonal) fits the frame (`fit_distance`). Without
+    a camera: looking along +z with y down. Returns the 4 x 4 camera-to-world pose (fp64)."""
+    lo, hi = np.asarray(bounds[0], dtype=np.float64), np.asarray(bounds[1], dtype=np.float64)
+    centre, radius = (lo + hi) / 2, max(float(np.linalg.norm(hi - lo)) / 2, 1e-6)
+    pose = np.eye(4) if cam2world0 is None else np.array(_to_numpy(cam2world0), dtype=np.float64).reshape(4, 4)
+    pose[:3, 3] = centre - fit_distance(radius, focal, size) * pose[:3, 2]
+    return pose
+
+
+def turntable_poses(bounds, n_frames, focal, size, down=(0.0, 1.0, 0.0), elevation_deg=20.0):
+    """n_frames camera-to-world poses (n, 4, 4) fp64 on a circle about the axis `down` through the centre of `bounds`, raised by
+    `elevation_deg` against `down`, at the distance where the bounding sphere fits the frame (`fit_distance`), each looking at the centre."""
+    if n_frames < 1:
+        raise ValueError(f'turntable_poses: n_frames = {n_frames}')
+    lo, hi = np.asarray(bounds[0], dtype=np.float64), np.asarray(bounds[1], dtype=np.float64)
+    centre, radius = (lo + hi) / 2, max(float(np.linalg.norm(hi - lo)) / 2, 1e-6)
+    d = np.asarray(down, dtype=np.float64)
+    d = d / np.linalg.norm(d)
+    a = np.cross(d, [1.0, 0.0, 0.0])
+    if np.linalg.norm(a) < 1e-6:
+        a = np.cross(d, [0.0, 0.0, 1.0])
+    a = a / np.linalg.norm(a)
+    b = np.cross(d, a)
+    dist, el = fit_distance(radius, focal, size), np.deg2rad(elevation_deg)
+    poses = []
+    for k in range(n_frames):
+        t = 2 * np.pi * k / n_frames
+        eye = centre + dist * (np.cos(el) * (np.cos(t) * a + np.sin(t) * b) - np.sin(el) * d)
+        poses.append(look_at(eye, centre, down=d))
+    return np.stack(poses)
+
+
+class SceneViz:
+    """The reference's SceneViz (viz.py:119-209) without a window: the same `add_pointcloud`, `add_camera`, `add_cameras`, and
+    `render(...)` / `show(outfile=None, ...)` that draw the scene into images on the GPU (`render_batch`). Geometry is kept as it is given
+    (device tensors stay on their device) and joined at the first render. Cameras are drawn as the wire glyph of `scene_camera_geometry`
+    in a flat colour; the textured image quad of the reference's glyph is out of scope, `image` / `images` only give the size."""
+
+    def __init__(self, device=None):
+        self.device = None if device is None else torch.device(device)
+        self._points, self._colors, self._masks = [], [], []
+        self._verts, self._faces, self._vcolors = [], [], []
+        self._n_vert = 0
+        self.cam_poses, self.cam_focals = [], []
+        self._joined = None
+        self.image = None            # the last picture of show()
+
+    # ---- geometry
+    def add_pointcloud(self, pts3d, color=(0, 0, 0), mask=None):
+        """pts3d: one (..., 3) map or a list of them; color: one (r, g, b) tuple for all, an image (same pixel count) or a list of images
+        (uint8, or floating in [0, 1]); mask: None, one boolean map or a list."""
+        if not isinstance(pts3d, (list, tuple)):
+            pts3d = [pts3d]
+            mask = None if mask is None else [mask]
+            color = color if isinstance(color, (tuple, list)) else [color]
+        elif isinstance(pts3d, tuple):
+            pts3d = list(pts3d)
+        flat = isinstance(color, tuple) or (isinstance(color, list) and len(color) == 3 and np.ndim(color[0]) == 0)
+        if flat and len(color) != 3:
+            raise ValueError(f'add_pointcloud: a colour is (r, g, b), got {color}')
+        if not flat and len(color) != len(pts3d):
+            raise ValueError(f'add_pointcloud: {len(pts3d)} pointmaps, {len(color)} colour images')
+        if mask is not None and len(mask) != len(pts3d):
+            raise ValueError(f'add_pointcloud: {len(pts3d)} pointmaps, {len(mask)} masks')
+        for k, p in enumerate(pts3d):
+            p = _tensor(p).reshape(-1, 3)
+            if self.device is None and p.is_cuda:
+                self.device = p.device
+            c = pack_rgba(np.asarray(color, dtype=np.uint8), len(p)) if flat else pack_rgba(color[k])
+            if len(c) != len(p):
+                raise ValueError(f'add_pointcloud: pointmap {k} has {len(p)} points, its colours {len(c)}')
+            m = None if mask is None or mask[k] is None else _tensor(mask[k]).reshape(-1)
+            if m is not None and len(m) != len(p):
+                raise ValueError(f'add_pointcloud: pointmap {k} has {len(p)} points, its mask {len(m)}')
+            self._points.append(p)
+            self._colors.append(c)
+            self._masks.append(m)
+        self._joined = None
+        return self
+
+    def add_mesh(self, vertices, faces, colors):
+        """Triangles: vertices (V, 3), faces (M, 3) indices, colors one (r, g, b), (V, 3) / (V, 4) per vertex, or (V,) int32 already packed
+        (`pack_rgba`; what `scene_mesh_batch(..., to_host=False)` gives). Tensors stay on their device. Vertices that no face uses (the
+        export's mesh keeps every pixel of every view, masked or not) are never drawn and do not count for `bounds()`."""
+        v = _tensor(vertices).reshape(-1, 3)
+        f = _tensor(faces)
+        f = (f.view(torch.int32) if f.dtype == torch.uint32 else f).reshape(-1, 3)
+        if len(f) and (int(f.min()) < 0 or int(f.max()) >= len(v)):
+            raise ValueError(f'add_mesh: face indices outside 0 ... {len(v) - 1}')
+        if self._n_vert + len(v) >= 2 ** 31:
+            raise ValueError('add_mesh: more than 2^31 vertices')
+        col = _tensor(colors)
+        if col.ndim == 1 and col.dtype == torch.int32 and len(col) == len(v):
+            c = col.contiguous()
+        else:
+            c = pack_rgba(col, len(v)) if col.numel() == 3 else pack_rgba(col.reshape(len(v), -1)[:, :3])
+        if self.device is None and v.is_cuda:
+            self.device = v.device
+        self._verts.append(v)
+        self._faces.append(f.to(torch.int32) + self._n_vert)
+        self._vcolors.append(c)
+        self._n_vert += len(v)
+        self._joined = None
+        return self
+
+    def add_camera(self, pose_c2w, focal=None, color=(0, 0, 0), image=None, imsize=None, cam_size=0.03):
+        pose = np.asarray(_to_numpy(pose_c2w), dtype=np.float64).reshape(4, 4)
+        focal = None if focal is None else _to_numpy(focal)
+        if isinstance(focal, np.ndarray) and focal.shape == (3, 3):
+            if imsize is None:
+                imsize = (2 * focal[0, 2], 2 * focal[1, 2])
+            focal = (focal[0, 0] * focal[1, 1]) ** 0.5
+        if imsize is None:
+            if image is None:
+                raise ValueError('add_camera: give imsize (W, H), an image, or 3 x 3 intrinsics')
+            imsize = tuple(image.shape[1::-1])
+        if focal is not None:
+            focal = float(np.asarray(focal).reshape(-1)[0])
+        cam = scene_camera_geometry(pose, focal, (float(imsize[0]), float(imsize[1])), screen_width=cam_size)
+        self.add_mesh(cam['wire_vertices'].astype(np.float32), cam['wire_faces'], np.asarray(color if color is not None else (0, 0, 0), dtype=np.uint8))
+        self.cam_poses.append(pose)
+        self.cam_focals.append(focal)
+        return self
+
+    def add_cameras(self, poses, focals=None, images=None, imsizes=None, colors=None, cam_size=0.03, color=None):
+        def get(arr, idx):
+            return None if arr is None else arr[idx]
+        for i, pose_c2w in enumerate(poses):
+            c = get(colors, i) if colors is not None else color
+            self.add_camera(pose_c2w, get(focals, i), image=get(images, i), color=(0, 0, 0) if c is None else c, imsize=get(imsizes, i),
+                            cam_size=cam_size)
+        return self
+
+    # ---- flat arrays
+    def _device(self):
+        if self.device is None:
+            _lib.require_device()
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        return self.device
+
+    def flat_arrays(self, device=None):
+        """Everything added so far as the flat tables of `render_batch`: dict(points (N, 3) fp32, point_colors (N,) int32, point_mask (N,)
+        uint8 or None, vertices (V, 3), faces (M, 3) int32, vertex_colors (V,)), on `device` (default: the scene's GPU)."""
+        device = torch.device(device) if device is not None else self._device()
+        out = dict(points=None, point_colors=None, point_mask=None, vertices=None, faces=None, vertex_colors=None)
+        if self._points:
+            out['points'] = torch.cat([p.to(device=device, dtype=torch.float32) for p in self._points])
+            out['point_colors'] = torch.cat([c.to(device) for c in self._colors])
+            if any(m is not None for m in self._masks):
+                out['point_mask'] = torch.cat([torch.ones(len(p), dtype=torch.uint8, device=device) if m is None else (m.to(device) != 0).to(torch.uint8)
+                                               for p, m in zip(self._points, self._masks)])
+        if self._verts:
+            out['vertices'] = torch.cat([v.to(device=device, dtype=torch.float32) for v in self._verts])
+            out['faces'] = torch.cat([f.to(device) for f in self._faces])
+            out['vertex_colors'] = torch.cat([c.to(device) for c in self._vcolors])
+        return out
+
+    def bounds(self):
+        """(min (3,), max (3,)) fp64 over what can be drawn: the finite unmasked points and the finite mesh vertices that a face uses (a
+        masked-out point or an unused vertex, however far away, moves neither the framing nor the default near plane); None for an empty scene."""
+        g = self._geometry()
+        sets = []
+        if g['points'] is not None:
+            p = g['points'] if g['point_mask'] is None else g['points'][g['point_mask'] != 0]
+            sets.append(p)
+        if g['vertices'] is not None:
+            used = torch.zeros(len(g['vertices']), dtype=torch.bool, device=g['vertices'].device)
+            used[g['faces'].reshape(-1).long()] = True
+            sets.append(g['vertices'][used])
+        sets = [p[torch.isfinite(p).all(dim=1)] for p in sets]
+        sets = [p for p in sets if len(p)]
+        if not sets:
+            return None
+        lo = torch.stack([p.min(dim=0).values for p in sets]).min(dim=0).values
+        hi = torch.stack([p.max(dim=0).values for p in sets]).max(dim=0).values
+        return lo.double().cpu().numpy(), hi.double().cpu().numpy()
+
+    def _geometry(self):
+        if self._joined is None:
+            self._joined = self.flat_arrays()
+        return self._joined
+
+    # ---- drawing
+    def render(self, cam2world, focal, size=(1024, 768), point_size=1, background=(255, 255, 255), near=None, return_depth=False,
+               return_ids=False, to_host=True):
+        """The scene seen from one camera-to-world pose (4, 4) or a stack of F poses (F, 4, 4), all frames in one call. `focal`: a focal in
+        pixels (principal point W/2, H/2; one value or one per pose) or 3 x 3 intrinsics K (one or F). size = (W, H). near: the near plane
+        (geometry not beyond it is not drawn; depth keeps 24 bits of near / Z); default 1 % of the diagonal of the scene's bounds.
+        Returns the image (H, W, 3) uint8 -- (F, H, W, 3) for a stack -- or, with return_depth / return_ids, the dict of `render_batch`."""
+        poses = _to_numpy(cam2world)
+        single = poses.ndim == 2
+        poses = poses.reshape(-1, 4, 4)
+        g = self._geometry()
+        if near is None:
+            near = self.default_near()
+        out = render_batch(poses, intrinsics_rows(focal, len(poses), size), size, self._device(), point_size=point_size, background=background,
+                           near=near, return_depth=return_depth, return_ids=return_ids, to_host=to_host, **g)
+        if single:
+            out = {k: v[0] for k, v in out.items()}
+        return out if (return_depth or return_ids) else out['rgb']
+
+    def default_near(self):
+        """The near plane `render` uses when none is given: 1 % of the diagonal of `bounds()` (0.01 for an empty or point-sized scene)."""
+        b = self.bounds()
+        near = 0.01 * float(np.linalg.norm(b[1] - b[0])) if b is not None else 0.01
+        return near if near > 0 else 0.01
+
+    def default_view(self, size=(1024, 768), focal=None):
+        """(pose, focal) of `show()`: the rule of `default_viewpoint` with the first camera added to the scene (its focal unless one is
+        given; 1.1 min(W, H) -- dust3r's default guess -- when it has none)."""
+        b = self.bounds()
+        if b is None:
+            raise ValueError('SceneViz: nothing to show (no finite point or vertex)')
+        if focal is None:
+            focal = self.cam_focals[0] if self.cam_focals and self.cam_focals[0] else 1.1 * min(size)
+        return default_viewpoint(self.cam_poses[0] if self.cam_poses else None, b, focal, size), float(focal)
+
+    def show(self, outfile=None, point_size=2, size=(1024, 768), focal=None, cam2world=None, **render_kw):
+        """Never opens a window: renders one image from `cam2world` (default: `default_view`), writes it as a PNG when `outfile` is given,
+        and returns it as an (H, W, 3) uint8 array, also kept as `self.image`. point_size = 2 is the reference's default."""
+        pose, f = self.default_view(size, focal) if cam2world is None else (cam2world, focal if focal is not None else 1.1 * min(size))
+        image = self.render(pose, f, size=size, point_size=point_size, **render_kw)
+        if isinstance(image, dict):
+            image = image['rgb']
+        if outfile is not None:
+            from .demo import _png
+            with open(outfile, 'wb') as fh:
+                fh.write(_png(np.asarray(image)))
+        self.image = image
+        return image

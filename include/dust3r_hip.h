@@ -349,6 +349,53 @@ int d3r_scene_mesh(int n_views, const float* pts, const uint8_t* mask, const voi
                    int max_area, int as_pointcloud, uint32_t* faces_out, float* points_out, uint32_t* colors_out, long long* counts_out,
                    float* bounds_out, void* workspace, void* stream);
 
+/* ---- headless rendering (csrc/render.hip): what scene.show(), scene.render_views() and demo.render_turntable draw with ------------ */
+
+/* A z-buffered software rasteriser for points and triangles, n_cams cameras in one call (the reference's show() opens a trimesh / pyglet
+ * window, dust3r/viz.py:119-209; this is its headless counterpart). All pointers DEVICE; no allocation, no synchronisation.
+ * Cameras: w2c [n_cams][w2c_stride] fp32, w2c_stride = 12 or 16: world -> camera [R | t], row-major 3 x 4 (a 4 x 4 matrix's first three
+ *   rows); intr [n_cams][4] fp32 = (fx, fy, cx, cy); near > 0. At most 65535 cameras.
+ * Vertex stage (fp32): X = R p + t, each row one fma chain fma(r0, px, fma(r1, py, fma(r2, pz, t))); x = fma(fx, X / Z, cx), y likewise;
+ *   sx = rint(16 x), sy = rint(16 y) (int32, 1/16 pixel); zq = 0xFFFFFF - rint((near / Z) 0xFFFFFF): 24 bits, linear in 1 / Z and so in
+ *   screen space, smaller = nearer; Z back from zq: near 0xFFFFFF / (0xFFFFFF - zq). A vertex is INVALID (zq = 0xFFFFFFFF, sx = sy = 0) when
+ *   a coordinate of p is not finite, when not Z > near, or when not |x|, |y| <= 8192 px (the guard band).
+ * Raster stage (integers only). Pixel (px, py) has its centre at image coordinates (px, py) (dust3r's convention: principal point W/2, H/2,
+ *   pixel (u, v) of a pointmap unprojects from exactly (u, v)) and covers [px - 1/2, px + 1/2). The frame buffer is one uint64 key per
+ *   pixel, [n_cams][H][W], (zq << 32) | primitive id, all ones = empty (d3r_render_clear), lowered with a 64-bit atomic minimum: the image
+ *   does not depend on the order of arrival, and at equal depth the lower id wins. W, H <= 8192. Bounds: |sx|, |sy| <= 2^17, so an edge
+ *   function and area2 stay below 2^37, area2 zq below 2^61 and the colour sums below 2^46: int64 throughout.
+ * d3r_render_points: point i (skipped when mask != NULL and mask[i] == 0, or invalid) covers the point_size x point_size pixels
+ *   base + (-floor((s - 1) / 2) ... +floor(s / 2)) in x and y, base = floor((sx + 8) / 16), floor((sy + 8) / 16), clipped to the frame, with
+ *   key (zq << 32) | (id_base + i). 1 <= point_size <= 16.
+ * d3r_render_triangles: face j = faces[j][3] (uint32 indices into positions [n_vert][3]; a face with an index >= n_vert or an invalid
+ *   vertex is dropped whole: there is NO near-plane clipping). Both windings are drawn (no culling), zero-area faces are skipped. The vertices
+ *   are ordered (v1 <-> v2 when needed) so that area2 = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) > 0; w0, w1, w2 = the edge functions of
+ *   (v1 -> v2), (v2 -> v0), (v0 -> v1) at the sample (16 px, 16 py), E(a -> b)(p) = (bx - ax)(py - ay) - (by - ay)(px - ax), w0 + w1 + w2 =
+ *   area2. TOP-LEFT fill rule: the sample is covered when every w_k > 0, or = 0 on an edge a -> b with by < ay, or by = ay and bx > ax; two
+ *   faces that share an edge cover every pixel exactly once. zq = (w0 zq0 + w1 zq1 + w2 zq2) / area2 (integer division), key
+ *   (zq << 32) | (id_base + j). A face whose clipped bounding box holds more than 64 samples is drawn by its whole wave (64 samples of a
+ *   row at a time), so no thread walks more than ceil(W / 64) H samples of one face.
+ * id_base + count <= 2^31 - 1. stats: NULL, or [2] uint64 that the call ADDS to: candidate samples, atomics issued (the others were
+ *   skipped by the load in front of the atomic: the stored key was already smaller); the counting build of the kernels is slower.
+ * d3r_render_resolve: per pixel, rgb_out [n_cams][H][W][3] uint8 = the background where the key is all ones; point_rgba[id - point_id_base]
+ *   (RGBA8 packed r | g << 8 | b << 16) for a point; for a face the colours vert_rgba of its three vertices interpolated per channel,
+ *   (w0 c0 + w1 c1 + w2 c2 + area2 / 2) / area2, with the weights recomputed at the pixel. The geometry and the cameras must be the ones
+ *   that were drawn. depth_out (or NULL) [n_cams][H][W] fp32: Z from zq, +inf for the background (and for zq = 0xFFFFFF: beyond
+ *   near 2^24); id_out (or NULL) int32: the primitive id, -1 for the background. */
+int d3r_render_project(int n_vert, const float* positions, int n_cams, const float* w2c, int w2c_stride, const float* intr, float near,
+                       int* sxy_out, uint32_t* zq_out, void* stream);      /* sxy_out [n_cams][n_vert][2] int32, zq_out [n_cams][n_vert] uint32 */
+int d3r_render_clear(int n_cams, int W, int H, unsigned long long* framebuffer, void* stream);
+int d3r_render_points(int n_points, const float* positions, const uint8_t* mask, uint32_t id_base, int n_cams, const float* w2c,
+                      int w2c_stride, const float* intr, float near, int W, int H, int point_size, unsigned long long* framebuffer,
+                      unsigned long long* stats, void* stream);
+int d3r_render_triangles(int n_faces, const uint32_t* faces, int n_vert, const float* positions, uint32_t id_base, int n_cams,
+                         const float* w2c, int w2c_stride, const float* intr, float near, int W, int H, unsigned long long* framebuffer,
+                         unsigned long long* stats, void* stream);
+int d3r_render_resolve(int n_cams, const float* w2c, int w2c_stride, const float* intr, float near, int W, int H,
+                       const unsigned long long* framebuffer, int n_points, uint32_t point_id_base, const uint32_t* point_rgba, int n_faces,
+                       uint32_t face_id_base, const uint32_t* faces, int n_vert, const float* vert_positions, const uint32_t* vert_rgba,
+                       uint32_t background_rgba, uint8_t* rgb_out, float* depth_out, int* id_out, void* stream);
+
 /* exhaustive 3-D nearest neighbour: idx_out[q] = argmin_r |query[q] - ref[r]|^2 (lowest index on ties); query [n_query][3],
  * ref [n_ref][3] DEVICE fp32, idx_out DEVICE int32. The building block of find_reciprocal_matches (dust3r/utils/geometry.py:345-361,
  * two SciPy KD-tree queries in the reference; caller: visloc.py:105). */
