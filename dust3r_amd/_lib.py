@@ -45,6 +45,12 @@ class PnpRansacJob(C.Structure):
                 ('seed', C.c_ulonglong)]
 
 
+class CriterionOpts(C.Structure):
+    """d3r_criterion_opts (include/dust3r_hip.h)"""
+    _fields_ = [('norm_mode', C.c_int), ('gt_scale', C.c_int), ('shift_inv', C.c_int), ('scale_inv', C.c_int), ('center_mode', C.c_int),
+                ('use_conf', C.c_int), ('has_dist_clip', C.c_int), ('stop_after', C.c_int), ('dist_clip', C.c_float), ('alpha', C.c_float)]
+
+
 class PnpRansacParams(C.Structure):
     """d3r_pnp_ransac_params (include/dust3r_hip.h)"""
     _fields_ = [('max_iters', C.c_int), ('max_points', C.c_int)]
@@ -131,6 +137,10 @@ def _load():
         'd3r_pnp_workspace': (C.c_size_t, [i]),
         'd3r_pnp_score': (i, [i, vp, fp, i, f, ip, vp]),
         'd3r_pnp_sums': (i, [i, vp, fp, f, vp, vp, vp]),
+        'd3r_pair_criterion_workspace_bytes': (C.c_size_t, [i, i]),
+        'd3r_pair_criterion': (i, [i, i, fp, fp, fp, vp, vp, fp, fp, fp, fp, C.POINTER(CriterionOpts), vp, fp, fp, vp, vp]),
+        'd3r_pair_criterion_passes': (i, [C.POINTER(CriterionOpts)]),
+        'd3r_masked_median': (i, [i, i, fp, fp, vp, vp, vp, vp, vp]),
         'd3r_selftest_aligner_math_host': (i, [i, i, ip, ip, i, i, fp, fp, fp, fp, fp, fp, fp, fp, f, f, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -1,9 +1,11 @@
-"""Inference driver -- mirror of the reference `dust3r/inference.py:26-78` (`inference`,
-`loss_of_one_batch` with criterion=None, `check_if_same_size`, `make_batch_symmetric`).
+"""Inference driver -- mirror of the reference `dust3r/inference.py:26-103` (`inference`, `loss_of_one_batch`,
+`check_if_same_size`, `make_batch_symmetric`, `get_pred_pts3d`).
 
-Same signature and same returned structure: dict(view1, view2, pred1, pred2, loss=None) with every
+Same signature and same returned structure: dict(view1, view2, pred1, pred2, loss) with every
 tensor on the CPU, concatenated over pairs (lists when image sizes are mixed). The model call goes
 to the HIP engine; pairs can additionally be sharded over ranks with `dust3r_amd.parallel`.
+`loss_of_one_batch` with a criterion of `dust3r_amd.losses` returns loss=(value, details) like the reference,
+evaluated on the device right behind the forward (no gradients: evaluation only).
 """
 import torch
 import tqdm
@@ -27,8 +29,29 @@ def make_batch_symmetric(batch):
     return _interleave_imgs(view1, view2), _interleave_imgs(view2, view1)
 
 
+def get_pred_pts3d(gt, pred, use_pose=False):
+    """The predicted points of one view (dust3r/inference.py:81-103): `pts3d` (in the view's own camera; through `camera_pose` of the
+    prediction when use_pose) or `pts3d_in_other_view` (already in the other camera). No shipped head predicts depth + pseudo_focal."""
+    if 'depth' in pred and 'pseudo_focal' in pred:
+        raise NotImplementedError('the depth + pseudo_focal prediction format is not produced by any head of this package')
+    if 'pts3d' in pred:
+        pts3d = pred['pts3d']
+    elif 'pts3d_in_other_view' in pred:
+        if use_pose is not True:
+            raise ValueError('pts3d_in_other_view is already transformed: use_pose must be True')
+        return pred['pts3d_in_other_view']
+    else:
+        raise KeyError('the prediction holds neither pts3d nor pts3d_in_other_view')
+    if use_pose:
+        camera_pose = pred.get('camera_pose')
+        if camera_pose is None:
+            raise ValueError('use_pose needs a camera_pose in the prediction')
+        from .utils.geometry import geotrf
+        pts3d = geotrf(camera_pose, pts3d)
+    return pts3d
+
+
 def loss_of_one_batch(batch, model, criterion, device, symmetrize_batch=False, use_amp=False, ret=None):
-    assert criterion is None, 'training losses are outside the scope of dust3r_amd (inference + alignment engine)'
     view1, view2 = batch
     ignore_keys = set(['depthmap', 'dataset', 'label', 'instance', 'idx', 'true_shape', 'rng'])
     for view in batch:
@@ -39,7 +62,9 @@ def loss_of_one_batch(batch, model, criterion, device, symmetrize_batch=False, u
     if symmetrize_batch:
         view1, view2 = make_batch_symmetric(batch)
     pred1, pred2 = model(view1, view2)      # use_amp is moot: the engine's precision is a model property
-    result = dict(view1=view1, view2=view2, pred1=pred1, pred2=pred2, loss=None)
+    # the criterion reads the predictions where the forward left them (dust3r_amd/losses.py); forward-only, no graph
+    loss = criterion(view1, view2, pred1, pred2) if criterion is not None else None
+    result = dict(view1=view1, view2=view2, pred1=pred1, pred2=pred2, loss=loss)
     return result[ret] if ret else result
 
 

@@ -94,3 +94,62 @@ def find_reciprocal_matches(P1, P2):
     if as_numpy:
         return reciprocal_in_P2.cpu().numpy(), nn2.cpu().numpy(), count
     return reciprocal_in_P2, nn2, count
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The joint statistics the regression criteria are built from (dust3r/utils/geometry.py:249-342), as thin callers of the fused
+# criterion kernels (dust3r_amd/csrc/losses.hip through dust3r_amd.losses.pair_criterion / masked_median). Results come back on the
+# device of the inputs.
+def _joint_stats(pts1, pts2, valid1, valid2, **kw):
+    from ..losses import pair_criterion
+    if pts1.ndim < 3 or pts1.shape[-1] != 3 or (pts2 is not None and (pts2.ndim < 3 or pts2.shape[-1] != 3)):
+        raise ValueError('points must be (B, ..., 3)')
+    if pts2 is not None and pts2.shape != pts1.shape:
+        raise ValueError('both views must share one shape')
+    eye = torch.eye(4).expand(pts1.shape[0], 4, 4)
+    stats, _, _ = pair_criterion(pts1, pts2, eye, valid1, valid2, pts1, pts2, **kw)
+    return stats
+
+
+def normalize_pointcloud(pts1, pts2, norm_mode='avg_dis', valid1=None, valid2=None, ret_factor=False):
+    """Both pointmaps divided by their JOINT norm factor: the mean over valid points of |p| ('avg_dis'), of log1p|p| ('avg_log1p',
+    and 'avg_warp-log1p', which first rescales every point to length log1p|p|), the median of |p| ('median_dis') or the squared mean
+    of sqrt|p| ('sqrt_dis'); the factor is clipped below at 1e-8."""
+    from ..losses import NORM_MODES, NORM_PR, STAGE_NORM
+    if not norm_mode or norm_mode not in NORM_MODES:
+        raise ValueError(f'bad norm_mode={norm_mode!r}')
+    stats = _joint_stats(pts1, pts2, valid1, valid2, norm_mode=norm_mode, gt_scale=True, stop_after=STAGE_NORM)
+    factor = stats[:, NORM_PR].float().to(pts1.device).reshape((-1,) + (1,) * (pts1.ndim - 1))
+
+    def apply(p, valid):
+        if norm_mode == 'avg_warp-log1p':      # an invalid point counts as the origin, as in the reference: its warp factor is 0
+            d = p.norm(dim=-1, keepdim=True)
+            if valid is not None:
+                d = d * torch.as_tensor(valid).to(p.device).reshape(d.shape)
+            p = p * (torch.log1p(d) / d.clip(min=1e-8))
+        return p / factor
+    res = apply(pts1, valid1) if pts2 is None else (apply(pts1, valid1), apply(pts2, valid2))
+    if ret_factor:
+        res = (res if isinstance(res, tuple) else (res,)) + (factor,)
+    return res
+
+
+def get_joint_pointcloud_depth(z1, z2, valid_mask1, valid_mask2=None, quantile=0.5):
+    """(B,) joint median (the lower one, as torch.nanmedian) of the valid depths of both views."""
+    if quantile != 0.5:
+        raise NotImplementedError('only the median (quantile=0.5) is selected on the GPU')
+    from ..losses import masked_median
+    return masked_median(z1, z2, valid_mask1, valid_mask2).to(z1.device)
+
+
+def get_joint_pointcloud_center_scale(pts1, pts2, valid_mask1=None, valid_mask2=None, z_only=False, center=True):
+    """(centre (B, 1, 1, 3), scale (B, 1, 1, 1)): the per-coordinate joint median of the valid points (x and y zeroed when z_only) and the
+    joint median distance to it (to the origin when center is False)."""
+    from ..losses import CENTER_FULL, CENTER_NONE, CENTER_PR, CENTER_Z_ONLY, SCALE_PR, STAGE_SCALE
+    # z_only zeroes the centre's x and y before the distances are taken; center=False keeps the centre out of them
+    stats = _joint_stats(pts1, pts2, valid_mask1, valid_mask2, norm_mode=None, scale_inv=True, stop_after=STAGE_SCALE,
+                         center_mode=CENTER_NONE if not center else (CENTER_Z_ONLY if z_only else CENTER_FULL))
+    ctr = stats[:, CENTER_PR:CENTER_PR + 3].float().to(pts1.device)
+    if z_only:
+        ctr[:, :2] = 0
+    return ctr[:, None, None, :], stats[:, SCALE_PR].float().to(pts1.device)[:, None, None, None]

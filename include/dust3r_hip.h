@@ -511,6 +511,73 @@ int d3r_selftest_aligner_math_host(int n_imgs, int n_edges, const int* ei, const
                                    float focal_break, double* loss, double* g_pw_poses, double* g_im_poses, double* g_im_depthmaps,
                                    double* g_im_focals);
 
+/* Forward-only evaluation of the reference's regression criteria for B pairs of N = H x W pixels in one call: Regr3D (dust3r/losses.py:158-194),
+ * ConfLoss (:220-238), Regr3D_ShiftInv / _ScaleInv / _ScaleShiftInv (:245-294), with normalize_pointcloud, get_joint_pointcloud_depth and
+ * get_joint_pointcloud_center_scale (dust3r/utils/geometry.py:249-342). There is no backward pass.
+ * All pointers DEVICE. gt_pts1 / gt_pts2 [B][N][3] fp32 world points of the two views (gt_pts2 NULL: one view only), inv_pose1 [B][16] the
+ * row-major INVERSE of view 1's camera_pose, valid1 / valid2 [B][N] uint8 (nonzero = valid), pr_pts1 / pr_pts2 [B][N][3] fp32 (pts3d and
+ * pts3d_in_other_view), conf1 / conf2 [B][N] fp32 (read when use_conf). Stages: (1) ground truth into camera 1's frame; dist_clip narrows the
+ * masks; joint normalisation of the prediction, and of the ground truth unless gt_scale; (2) shift_inv: z minus the joint median of z over
+ * the valid pixels of both views, per side; (3) scale_inv: centre = per-coordinate joint median (center_mode: z only / computed but not
+ * subtracted), scale = joint median of |p - centre|, the prediction's clipped to [1e-3, 1e3]; prediction *= gt / pred (gt_scale) or each side
+ * divided by its own; (4) l = |pred - gt| per valid pixel, and l conf - alpha log conf. A median is the element of rank (n - 1) / 2 of the n
+ * valid fp32 values (torch.nanmedian's lower median), NaN when n = 0 -- such a pair adds nothing to sums and counts.
+ * out [B][D3R_CRIT_NSTAT] fp64, indexed by D3R_CRIT_*: counts, every statistic used, and the SUMS over valid pixels, from which the caller
+ * composes any reduction (the reference's mean is over the valid pixels of the whole batch). map1 / map2 (optional) [B][N] fp32: l per pixel,
+ * 0 where invalid. stop_after ends the call behind a stage (the geometry helpers). workspace: d3r_pair_criterion_workspace_bytes(B, N).
+ * Deterministic: two calls give equal bits, and a pair's row does not depend on the other pairs of the call. Everything is enqueued on
+ * `stream`; no allocation, no synchronisation. Non-finite values at VALID pixels are outside the contract. */
+#define D3R_NORM_NONE 0
+#define D3R_NORM_AVG_DIS 1
+#define D3R_NORM_AVG_LOG1P 2
+#define D3R_NORM_AVG_WARP_LOG1P 3
+#define D3R_NORM_MEDIAN_DIS 4
+#define D3R_NORM_SQRT_DIS 5
+#define D3R_STAGE_ALL 0
+#define D3R_STAGE_NORM 1
+#define D3R_STAGE_SHIFT 2
+#define D3R_STAGE_SCALE 3
+#define D3R_CENTER_FULL 0
+#define D3R_CENTER_Z_ONLY 1
+#define D3R_CENTER_NONE 2
+#define D3R_CRIT_N1 0
+#define D3R_CRIT_N2 1
+#define D3R_CRIT_NORM_PR 2
+#define D3R_CRIT_NORM_GT 3
+#define D3R_CRIT_SHIFT_PR 4
+#define D3R_CRIT_SHIFT_GT 5
+#define D3R_CRIT_CENTER_PR 6 /* x, y, z */
+#define D3R_CRIT_CENTER_GT 9
+#define D3R_CRIT_SCALE_PR 12 /* as measured; the clip to [1e-3, 1e3] is applied where it is used */
+#define D3R_CRIT_SCALE_GT 13
+#define D3R_CRIT_SUM_L1 14
+#define D3R_CRIT_SUM_L2 15
+#define D3R_CRIT_SUM_CONF1 16
+#define D3R_CRIT_SUM_CONF2 17
+#define D3R_CRIT_NSTAT 24
+typedef struct {
+    int norm_mode;     /* D3R_NORM_* */
+    int gt_scale;      /* Regr3D(gt_scale=True): the ground truth keeps its scale */
+    int shift_inv, scale_inv;
+    int center_mode;   /* D3R_CENTER_* */
+    int use_conf;      /* ConfLoss */
+    int has_dist_clip;
+    int stop_after;    /* D3R_STAGE_* */
+    float dist_clip;
+    float alpha;
+} d3r_criterion_opts;
+size_t d3r_pair_criterion_workspace_bytes(int B, int N);
+int d3r_pair_criterion(int B, int N, const float* gt_pts1, const float* gt_pts2, const float* inv_pose1, const uint8_t* valid1,
+                       const uint8_t* valid2, const float* pr_pts1, const float* pr_pts2, const float* conf1, const float* conf2,
+                       const d3r_criterion_opts* opts, double* out, float* map1, float* map2, void* workspace, void* stream);
+/* streaming passes over the inputs that d3r_pair_criterion makes for these options */
+int d3r_pair_criterion_passes(const d3r_criterion_opts* opts);
+/* out[b] = lower median (rank (n - 1) / 2; NaN when n = 0) of the unmasked, non-NaN values of row b of vals1 [B][N] joined with row b of
+ * vals2 [B][N] (NULL: one array); mask1 / mask2 [B][N] uint8 or NULL (all valid). The same element torch.nanmedian returns. out [B] fp64
+ * DEVICE; workspace as for d3r_pair_criterion. */
+int d3r_masked_median(int B, int N, const float* vals1, const float* vals2, const uint8_t* mask1, const uint8_t* mask2, double* out,
+                      void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
