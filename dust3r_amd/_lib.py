@@ -51,6 +51,15 @@ class CriterionOpts(C.Structure):
                 ('use_conf', C.c_int), ('has_dist_clip', C.c_int), ('stop_after', C.c_int), ('dist_clip', C.c_float), ('alpha', C.c_float)]
 
 
+class ViewPlan(C.Structure):
+    """d3r_view_plan (include/dust3r_hip.h)"""
+    _fields_ = [('rgb', C.c_void_p), ('depth', C.c_void_p), ('kx', C.c_void_p), ('bx', C.c_void_p), ('ky', C.c_void_p), ('by', C.c_void_p),
+                ('tmp_off', C.c_longlong), ('src_w', C.c_int), ('src_h', C.c_int), ('crop_l', C.c_int), ('crop_t', C.c_int), ('crop_w', C.c_int),
+                ('crop_h', C.c_int), ('rs_w', C.c_int), ('rs_h', C.c_int), ('kxs', C.c_int), ('kys', C.c_int), ('off_x', C.c_int), ('off_y', C.c_int),
+                ('w', C.c_int), ('h', C.c_int), ('row0', C.c_int), ('nrows', C.c_int), ('transpose', C.c_int), ('fu', C.c_float), ('fv', C.c_float),
+                ('cu', C.c_float), ('cv', C.c_float), ('pose', C.c_float * 12)]
+
+
 class PnpRansacParams(C.Structure):
     """d3r_pnp_ransac_params (include/dust3r_hip.h)"""
     _fields_ = [('max_iters', C.c_int), ('max_points', C.c_int)]
@@ -141,6 +150,10 @@ def _load():
         'd3r_pair_criterion': (i, [i, i, fp, fp, fp, vp, vp, fp, fp, fp, fp, C.POINTER(CriterionOpts), vp, fp, fp, vp, vp]),
         'd3r_pair_criterion_passes': (i, [C.POINTER(CriterionOpts)]),
         'd3r_masked_median': (i, [i, i, fp, fp, vp, vp, vp, vp, vp]),
+        'd3r_view_plan_bytes': (i, []),
+        'd3r_prepare_views': (i, [i, C.POINTER(ViewPlan), vp, i, i, fp, vp, C.c_size_t, fp, fp, fp, vp, vp]),
+        'd3r_selftest_resample_host': (i, [vp, i, i, i, i, i, i, i, i, vp, vp, i, vp, vp, i, vp]),
+        'd3r_selftest_depth_host': (i, [C.POINTER(ViewPlan), i, i, fp, fp, vp]),
         'd3r_selftest_aligner_math_host': (i, [i, i, ip, ip, i, i, fp, fp, fp, fp, fp, fp, fp, fp, f, f, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

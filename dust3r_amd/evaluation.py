@@ -5,8 +5,9 @@
 `batches` is any iterable of collated (view1, view2) with the reference's keys (`img`, `pts3d`, `camera_pose`, `valid_mask`,
 `true_shape`). Every batch goes through `loss_of_one_batch` (forward on the engine, then the criterion on the device: the predictions never
 leave HBM); the table holds, for `loss` and every key of the criterion's details, `<key>_avg` = the mean of the per-batch values and
-`<key>_med` = their lower median -- what the reference's SmoothedValue reports with an unbounded window. Datasets and multi-rank
-evaluation are out of scope (ranks would add their per-pair sums and counts, see dust3r_amd/losses.py)."""
+`<key>_med` = their lower median -- what the reference's SmoothedValue reports with an unbounded window. `batches` can be a
+`dust3r_amd.datasets.get_data_loader(...)`: its batches are prepared on the GPU and arrive where the criterion reads them. Multi-rank
+evaluation is out of scope (ranks would add their per-pair sums and counts, see dust3r_amd/losses.py)."""
 import torch
 
 from .inference import loss_of_one_batch

@@ -578,6 +578,46 @@ int d3r_pair_criterion_passes(const d3r_criterion_opts* opts);
 int d3r_masked_median(int B, int N, const float* vals1, const float* vals2, const uint8_t* mask1, const uint8_t* mask2, double* out,
                       void* workspace, void* stream);
 
+/* ---- dataset views prepared per batch (csrc/views.hip, csrc/views_math.hpp) ------------------------------------------------------
+ * Replaces the per-view host pipeline of dust3r/datasets/base/base_stereo_view_dataset.py:63-181 (_crop_resize_if_necessary and the
+ * tail of __getitem__) with dust3r/datasets/utils/cropping.py: crop around the principal point, Pillow's Lanczos / bicubic resample, a
+ * nearest-neighbour resample of the depth map, the second crop, ImgNorm, depthmap_to_absolute_camera_coordinates, the validity mask
+ * and the portrait transpose. One call prepares the n views of a batch, whose sources differ in size; the outputs share one shape.
+ * A plan describes one view. The resampler is Pillow's, bit for bit: two separable passes with a uint8 intermediate; kx / ky are the
+ * 22-bit integer coefficient tables [rs_w][kxs] / [rs_h][kys] and bx / by the bounds tables [rs_w][2] / [rs_h][2] = {first source
+ * sample relative to the first crop, taps}, all int32, built on the host in fp64 (no transcendental is evaluated on the device).
+ * Only the window the second crop keeps is computed: columns off_x .. off_x + w, rows off_y .. off_y + h of the resampled picture, and
+ * of the horizontal pass only the crop rows row0 .. row0 + nrows those need, kept as [nrows][w][3] bytes at workspace + tmp_off.
+ * The depth map is one gather per output pixel (d3r::vw::nearest_index through both crops), followed by the back-projection. */
+typedef struct d3r_view_plan {
+    const uint8_t* rgb;   /* DEVICE [src_h][src_w][3], 4-byte aligned */
+    const float* depth;   /* DEVICE [src_h][src_w] */
+    const int32_t *kx, *bx, *ky, *by; /* DEVICE tables, see above */
+    long long tmp_off;    /* byte offset of this view's intermediate in the workspace */
+    int src_w, src_h;
+    int crop_l, crop_t, crop_w, crop_h; /* first crop */
+    int rs_w, rs_h;       /* size of the resampled first crop */
+    int kxs, kys;         /* row length of kx / ky */
+    int off_x, off_y;     /* second crop */
+    int w, h;             /* size of the view before the portrait transpose; out (H, W) = transpose ? (w, h) : (h, w) */
+    int row0, nrows;      /* crop rows kept by the horizontal pass */
+    int transpose;        /* 1: out[y][x] = view[x][y] */
+    float fu, fv, cu, cv; /* intrinsics of the view before the transpose */
+    float pose[12];       /* first three rows of cam2world */
+} d3r_view_plan;
+int d3r_view_plan_bytes(void);
+/* plans_host: the n plans (validated here: every index a kernel forms stays inside its buffer, whatever the tables hold);
+ * plans_dev: the same bytes in DEVICE memory; norm_lut: DEVICE fp32 [256], the ImgNorm value of every byte; img [n][3][H][W] fp32,
+ * depthmap [n][H][W] fp32, pts3d [n][H][W][3] fp32, valid_mask [n][H][W] uint8 = (z > 0) & isfinite(pts3d). */
+int d3r_prepare_views(int n, const d3r_view_plan* plans_host, const void* plans_dev, int H, int W, const float* norm_lut, void* workspace,
+                      size_t workspace_bytes, float* img, float* depthmap, float* pts3d, uint8_t* valid_mask, void* stream);
+/* Host-only self tests of the shared arithmetic (no GPU touched; all pointers HOST). d3r_selftest_resample_host: both passes of the
+ * resampler over the first crop of src [src_h][src_w][3] -> out [rs_h][rs_w][3]. d3r_selftest_depth_host: the gather, back-projection
+ * and mask of one plan (its rgb / table pointers unused, depth HOST) -> depthmap / pts3d / valid_mask of shape (H, W). */
+int d3r_selftest_resample_host(const uint8_t* src, int src_w, int src_h, int crop_l, int crop_t, int crop_w, int crop_h, int rs_w, int rs_h,
+                               const int32_t* kx, const int32_t* bx, int kxs, const int32_t* ky, const int32_t* by, int kys, uint8_t* out);
+int d3r_selftest_depth_host(const d3r_view_plan* plan, int H, int W, float* depthmap, float* pts3d, uint8_t* valid_mask);
+
 #ifdef __cplusplus
 }
 #endif
