@@ -65,6 +65,8 @@ class PairMaps:
         out = []
         for side in (0, 1):
             t = self.confs[side]
+            # the kernel loads float4 (include/dust3r_hip.h): every row start on 16 bytes
+            assert all(self.conf_addr(side, e) % 16 == 0 for e in range(len(self.edges))), 'confidence rows must be 16-byte aligned'
             areas = {self.npix(side, e) for e in range(len(self.edges))}
             m = torch.empty(len(self.edges), dtype=torch.float32, device=self.dev)
             if len(areas) == 1:
@@ -85,9 +87,10 @@ class PairMaps:
         if not jobs:
             return np.zeros((0, 17))
         n = len(jobs)
-        src = self._i64([self.map_addr(*j[0]) for j in jobs])
-        tgt = self._i64([self.map_addr(*j[1]) for j in jobs])
-        wgt = self._i64([self.conf_addr(*j[2]) for j in jobs])
+        addrs = [[self.map_addr(*j[0]) for j in jobs], [self.map_addr(*j[1]) for j in jobs], [self.conf_addr(*j[2]) for j in jobs]]
+        # the kernel loads float4 and cannot check its device-side pointer tables (include/dust3r_hip.h): checked here
+        assert all(a % 16 == 0 for table in addrs for a in table), 'similarity_moments: maps and weights must be 16-byte aligned'
+        src, tgt, wgt = (self._i64(table) for table in addrs)
         npix = [self.npix(*j[0]) for j in jobs]
         assert all(self.npix(*j[1]) == a for j, a in zip(jobs, npix)), 'registration between clouds of different sizes'
         npix_d = self._i32(npix)

@@ -334,6 +334,7 @@ static inline int rc_of(hipError_t e) { return e == hipSuccess ? D3R_OK : 1000 +
 
 extern "C" int d3r_row_means(const float* x, int rows, int cols, int ld, float* out, void* stream) {
     if (!x || !out || rows <= 0 || cols <= 0 || ld < cols || (ld & 3)) return D3R_ERR_INVALID;
+    if ((uintptr_t)x & 15) return D3R_ERR_INVALID;   // float4 loads: x and, with ld a multiple of 4, every row start on 16 bytes
     hipLaunchKernelGGL(row_mean_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, cols, ld, out);
     return rc_of(hipGetLastError());
 }

@@ -470,12 +470,17 @@ int d3r_selftest_ransac_iters_host(double confidence, double ep, int model_point
  * :220-223, estimate_focal -> post_process.py:40-56, fast_pnp -> cv2.solvePnPRansac at :247-287) and pair_viewer.py:30-76. All
  * pointer TABLES (`*_ptrs`) are DEVICE arrays of device addresses; sums come back as DEVICE fp64. Nothing synchronises. */
 
-/* out[r] = mean(x[r][0..cols)), x row stride ld (multiple of 4 floats): the edge confidence scores of commons.py:20-25. */
+/* out[r] = mean(x[r][0..cols)), x row stride ld (multiple of 4 floats): the edge confidence scores of commons.py:20-25.
+ * Alignment: the kernel loads 16 bytes at a time, so x must be 16-byte aligned (with ld a multiple of 4 floats every row start then
+ * is); D3R_ERR_INVALID otherwise, nothing is launched. Only x[r][0..cols) is read, whatever lies between cols and ld. */
 int d3r_row_means(const float* x, int rows, int cols, int ld, float* out, void* stream);
 
 /* Weighted similarity-registration moments of n_jobs independent cloud pairs in one launch. Job j: source cloud src_ptrs[j]
  * ([npix[j]][3] fp32), target cloud tgt_ptrs[j], weights wgt_ptrs[j] ([npix[j]]). out[j][17] = { W, Sx[3], Sy[3], Sxy[3][3] (x_a y_b),
- * Sxx } with S = sum_p w_p (.); the caller finishes Umeyama (centre, 3x3 SVD, scale) on the host. npix: DEVICE int array. */
+ * Sxx } with S = sum_p w_p (.); the caller finishes Umeyama (centre, 3x3 SVD, scale) on the host. npix: DEVICE int array.
+ * Alignment: the kernel loads 16 bytes at a time, so EVERY address in src_ptrs, tgt_ptrs and wgt_ptrs must be 16-byte aligned (a map that
+ * is a row of a larger tensor: row stride a multiple of 4 floats). The tables live on the device, so the call cannot check this: a
+ * misaligned address is undefined behaviour, and the caller checks (cloud_opt/bootstrap.py does). Only the npix[j] points of a job are read. */
 size_t d3r_similarity_moments_workspace(int n_jobs, int max_points);
 int d3r_similarity_moments(int n_jobs, const void* src_ptrs, const void* tgt_ptrs, const void* wgt_ptrs, const int* npix, int max_points,
                            void* workspace, double* out, void* stream);

@@ -351,3 +351,13 @@ def test_batched_host_algebra_equals_the_per_item_functions():
     pr = pose_params_batch(rigid, False)
     for k, g in enumerate(rigid):
         assert np.abs(pr[k] - pose_params(g[:3, :3], g[:3, 3])).max() < 1e-12, k
+
+
+def test_bootstrap_kernel_test_inputs_meet_their_conditions():
+    """The conditions tests/test_bootstrap_gpu.py puts on its own inputs, evaluated on its fp64 references alone: no anchor depth in
+    (0, 0.25), the inlier / outlier residual gap of the PnP maps, at most 0.1 % undecided points per hypothesis and a hypothesis ladder whose
+    rungs lie more than ten times that apart."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_bootstrap_gpu
+    test_bootstrap_gpu.check_input_conditions()
