@@ -16,6 +16,11 @@ DTYPES = {'bf16': DTYPE_BF16, 'bfloat16': DTYPE_BF16, 'f16': DTYPE_F16, 'fp16': 
           'f32': DTYPE_F32, 'fp32': DTYPE_F32, 'float32': DTYPE_F32, 'fp16x3': DTYPE_F16X3, 'f16x3': DTYPE_F16X3,
           'fp16f8': DTYPE_F16F8, 'f16f8': DTYPE_F16F8, 'fp16x2f8': DTYPE_F16X2F8}
 TORCH_DTYPE = {DTYPE_BF16: torch.bfloat16, DTYPE_F16: torch.float16, DTYPE_F32: torch.float32}
+# the aligner's option, trainability-kind and schedule ids: D3R_<name> of include/dust3r_hip.h
+(ALIGNER_OPT_DPP_REDUCE, ALIGNER_OPT_RESET_ADAM, ALIGNER_OPT_OPTIMIZE_PP, ALIGNER_OPT_OPTIMIZE_ADAPTORS, ALIGNER_OPT_GENERIC_SMALL,
+ ALIGNER_OPT_EDGE_MEAN_LOSS, ALIGNER_OPT_FX_AND_FY) = 1, 2, 3, 4, 5, 6, 7
+ALIGNER_TRAIN_POSES, ALIGNER_TRAIN_FOCALS, ALIGNER_TRAIN_PP = 0, 1, 2
+SCHEDULE_COSINE, SCHEDULE_LINEAR = 0, 1
 
 ERRORS = {0: 'OK', -1: 'invalid argument', -2: 'allocation failed', -3: 'kernel launch failed', -4: 'unknown state-dict key',
           -5: 'shape mismatch', -6: 'bad state (weights missing / no gfx950 device)'}

@@ -20,7 +20,7 @@ import tqdm
 
 from .. import _lib
 from .._lib import check, current_stream, lib, ptr
-from ..utils.geometry import inv
+from ..utils.geometry import geotrf, inv, xy_grid
 from ..utils.rigid import quat_translation_to_homogeneous, rotmat_to_unitquat
 from . import init_im_poses as init_fun
 from .commons import (cosine_schedule, edge_str, get_conf_trf, get_imshapes, linear_schedule, signed_expm1,
@@ -141,6 +141,7 @@ class BasePCOptimizer(nn.Module):
                 imgs[view1['idx'][v]] = view1['img'][v]
                 imgs[view2['idx'][v]] = view2['img'][v]
             self.imgs = rgb(imgs)
+        self._grid_cache = None        # (n, max_area, 2) pixel grid of depth_to_pts3d, built on first use on the scene's device
         self._engine = None
         self._engine_sig = None
 
@@ -251,26 +252,70 @@ class BasePCOptimizer(nn.Module):
         trf = self.conf_trf if mode is None else get_conf_trf(mode)
         return [trf(c) for c in self.im_conf]
 
-    def depth_to_pts3d(self):
-        raise NotImplementedError()
-
     def get_pts3d(self, raw=False):
         res = self.depth_to_pts3d()
         if not raw:
             res = [dm[:h * w].view(h, w, 3) for dm, (h, w) in zip(res, self.imshapes)]
         return res
 
+    # ------------------------------------------------------------------ image parameters
+    # A scene with image parameters keeps them in flat storage -- `_flat_im_poses` (n, 7), `_flat_im_depthmaps` (n, max_area) log-depth, zero in the
+    # padding, `_flat_im_focals` (n, 1 | 2) = focal_break * log f, `_flat_im_pp` (n, 2) -- beside `focal_break` and the buffer `_pp` (n, 2) of image
+    # centres; the getters and the engine binding below read these and nothing else of the scene class.
+    def _get_msk_indices(self, msk):
+        if msk is None:
+            return range(self.n_imgs)
+        if isinstance(msk, int):
+            return [msk]
+        if isinstance(msk, (tuple, list)):
+            return self._get_msk_indices(np.array(msk))
+        if msk.dtype in (bool, torch.bool, np.bool_):
+            assert len(msk) == self.n_imgs
+            return np.where(msk)[0]
+        if np.issubdtype(msk.dtype, np.integer):
+            return msk
+        raise ValueError(f'bad {msk=}')
+
     def get_focals(self):
-        raise NotImplementedError()
+        """(n, 1), or (n, 2) = (fx, fy) for a scene with two focals per image."""
+        return (self._flat_im_focals / self.focal_break).exp()
 
-    def get_im_poses(self):
-        raise NotImplementedError()
-
-    def get_depthmaps(self, raw=False):
-        raise NotImplementedError()
+    def get_principal_points(self):
+        return self._pp + 10 * self._flat_im_pp
 
     def get_intrinsics(self):
-        raise NotImplementedError()
+        K = torch.zeros((self.n_imgs, 3, 3), device=self.device)
+        focals = self.get_focals().view(self.n_imgs, -1)
+        K[:, 0, 0] = focals[:, 0]
+        K[:, 1, 1] = focals[:, -1]
+        K[:, :2, 2] = self.get_principal_points()
+        K[:, 2, 2] = 1
+        return K
+
+    def get_im_poses(self):  # cam to world
+        return self._get_poses(self._flat_im_poses)
+
+    def get_depthmaps(self, raw=False):
+        res = self._flat_im_depthmaps.exp()
+        if not raw:
+            res = [dm[:h * w].view(h, w) for dm, (h, w) in zip(res, self.imshapes)]
+        return res
+
+    @property
+    def _grid(self):
+        g = self._grid_cache
+        if g is None or g.device != self.device:
+            dev = self.device
+            per_shape = {hw: _ravel_hw(xy_grid(hw[1], hw[0], device=dev).float(), self.max_area) for hw in set(self.imshapes)}
+            g = self._grid_cache = torch.stack([per_shape[hw] for hw in self.imshapes])
+        return g
+
+    def depth_to_pts3d(self):
+        focals = self.get_focals().unsqueeze(1)                 # (n,1,1 | 2): x = d (u - cx) / fx, y = d (v - cy) / fy
+        pp = self.get_principal_points().unsqueeze(1)           # (n,1,2)
+        depth = self.get_depthmaps(raw=True).unsqueeze(-1)      # (n,A,1)
+        rel = torch.cat((depth * (self._grid - pp) / focals, depth), dim=-1)
+        return geotrf(self.get_im_poses(), rel)
 
     @torch.no_grad()
     def clean_pointcloud(self, **kw):
@@ -366,9 +411,54 @@ class BasePCOptimizer(nn.Module):
                 out[i] = (res['rgb'][k], res['depth'][k]) if return_depth else res[k]
         return out
 
-    # ------------------------------------------------------------------ engine
-    def _engine_signature(self):
-        return None
+    # ------------------------------------------------------------------ engine binding
+    def _engine_tensors(self):
+        """The six tensors the engine reads and updates in place, under their parameter names and in d3r_aligner_create's order: pw_poses (E, 8),
+        pw_adaptors (E, 2), im_poses (n, 7), im_depthmaps (n, max_area), im_focals (n, 1 | 2), im_pp (n, 2); the scene's own storage, never a copy."""
+        return {'pw_poses': self.pw_poses.data, 'pw_adaptors': self.pw_adaptors.data, 'im_poses': self._flat_im_poses.data,
+                'im_depthmaps': self._flat_im_depthmaps.data, 'im_focals': self._flat_im_focals.data, 'im_pp': self._flat_im_pp.data}
+
+    def _engine_setup(self):
+        """What the scene class decides about its engine: (opt_im_poses, opt_im_focals, {_lib.ALIGNER_OPT_*: value} to set after create,
+        {_lib.ALIGNER_TRAIN_*: (n,) bool array} of per-image trainability or None)."""
+        raise NotImplementedError()
+
+    def _ensure_engine(self):
+        """The engine handle of the scene as it is now: a new engine whenever what it was created from -- the tensors' addresses, the loss, what is
+        trainable, the options -- has changed since the last call."""
+        _lib.require_device()
+        if self.device.type != 'cuda':
+            raise _lib.D3RError('the aligner is not on a GPU: call .to("cuda") (dust3r_amd has no CPU execution path)')
+        tensors = self._engine_tensors()
+        opt_im_poses, opt_im_focals, options, masks = self._engine_setup()
+        masks = {kind: np.asarray(m, dtype=bool) for kind, m in (masks or {}).items()}
+        sig = (self.norm_pw_scale, self.dist_name, bool(opt_im_poses), bool(opt_im_focals), tuple((k, int(v)) for k, v in options.items()),
+               tuple((k, tuple(m.tolist())) for k, m in masks.items()), tuple(t.data_ptr() for t in tensors.values()))
+        if self._engine is not None and sig == self._engine_sig:
+            return self._engine
+        self._destroy_engine()
+        inputs = {k: getattr(self, k) for k in ('_stacked_pred_i', '_stacked_pred_j', '_weight_i', '_weight_j')}
+        for k, t in (*inputs.items(), *tensors.items()):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32, f'{k} must be a contiguous fp32 CUDA tensor'
+        arr = lambda v: (C.c_int * len(v))(*v)  # noqa: E731
+        ei, ej = arr([i for i, j in self.edges]), arr([j for i, j in self.edges])
+        hh, ww = arr([h for h, w in self.imshapes]), arr([w for h, w in self.imshapes])
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib.d3r_aligner_create(C.byref(h), self.n_imgs, self.n_edges, ei, ej, hh, ww, self.max_area, *map(ptr, inputs.values()),
+                                         *map(ptr, tensors.values()), float(self.base_scale), float(self.pw_break), float(self.focal_break),
+                                         int(self.dist_name == 'l2'), int(self.norm_pw_scale), int(opt_im_poses), int(opt_im_focals), 1024,
+                                         current_stream()), 'aligner_create')
+            try:
+                for opt, value in options.items():
+                    check(lib.d3r_aligner_set_option(h, opt, int(value)), f'set_option({opt})')
+                for kind, m in masks.items():
+                    check(lib.d3r_aligner_set_trainable(h, kind, bytes(m.astype(np.uint8))), f'set_trainable({kind})')
+            except Exception:
+                lib.d3r_aligner_destroy(h)
+                raise
+        self._engine, self._engine_sig = h, sig
+        return h
 
     def _destroy_engine(self):
         if getattr(self, '_engine', None) is not None:
@@ -390,8 +480,29 @@ class BasePCOptimizer(nn.Module):
         except Exception:
             pass
 
+    @torch.no_grad()
     def forward(self, ret_details=False):
-        raise NotImplementedError()
+        """The alignment loss of the scene class (optimizer.py:188-201, or base_opt.py:246-273 for the Modular scene), evaluated by the engine (no
+        parameter update)."""
+        if ret_details:
+            raise NotImplementedError('ret_details: the per-pair loss matrix is not computed by the engine')
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        check(lib.d3r_aligner_loss_grad(self._ensure_engine(), ptr(loss), None, None, None, None, None, None, current_stream()), 'aligner_loss')
+        return loss[0]
+
+    @torch.no_grad()
+    def loss_and_grads(self):
+        """(loss, {name: grad}) of one forward/backward without a step -- the engine's analytic gradients, each shaped like its tensor of
+        _engine_tensors() and given for frozen entries too."""
+        eng = self._ensure_engine()
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        g = {k: torch.zeros_like(t) for k, t in self._engine_tensors().items()}
+        check(lib.d3r_aligner_loss_grad(eng, ptr(loss), ptr(g['pw_poses']), ptr(g['im_poses']), ptr(g['im_depthmaps']),
+                                        ptr(g['im_focals']), ptr(g['im_pp']), ptr(g['pw_adaptors']), current_stream()), 'aligner_loss_grad')
+        return loss[0], g
+
+    def set_reduction(self, use_dpp=True):
+        check(lib.d3r_aligner_set_option(self._ensure_engine(), _lib.ALIGNER_OPT_DPP_REDUCE, int(use_dpp)), 'set_option')
 
     def compute_global_alignment(self, init=None, niter_PnP=10, group=None, **kw):
         """`group` (new; the reference's loop is single-device): a torch.distributed process group (or True for the default one) whose ranks each hold this
@@ -410,20 +521,29 @@ class BasePCOptimizer(nn.Module):
         return global_alignment_loop(self, **kw)
 
 
-def global_alignment_loop(net, lr=0.01, niter=300, schedule='cosine', lr_min=1e-6):
-    """Mirror of base_opt.py:326-349: Adam(lr, betas=(0.9, 0.9)), lr scheduled per iteration; returns the
-    loss of the last iteration. The iterations run inside the fused HIP aligner."""
+def _loop_start(net, niter, schedule):
+    """What both loops begin with: (engine handle with its Adam state reset -- a fresh optimiser per call, as in the reference --, schedule id),
+    or None when there is nothing to iterate."""
     if schedule not in ('cosine', 'linear'):
         raise ValueError(f'bad lr {schedule=}')
     if niter <= 0:
+        return None
+    eng = net._ensure_engine()
+    check(lib.d3r_aligner_set_option(eng, _lib.ALIGNER_OPT_RESET_ADAM, 0), 'reset adam')
+    return eng, _lib.SCHEDULE_COSINE if schedule == 'cosine' else _lib.SCHEDULE_LINEAR
+
+
+def global_alignment_loop(net, lr=0.01, niter=300, schedule='cosine', lr_min=1e-6):
+    """Mirror of base_opt.py:326-349: Adam(lr, betas=(0.9, 0.9)), lr scheduled per iteration; returns the
+    loss of the last iteration. The iterations run inside the fused HIP aligner."""
+    start = _loop_start(net, niter, schedule)
+    if start is None:
         return float('inf')
+    eng, sched = start
     verbose = net.verbose
     if verbose:
         print('Global alignement - optimizing for:')
         print(net.trainable_names())
-    eng = net._ensure_engine()
-    check(lib.d3r_aligner_set_option(eng, 2, 0), 'reset adam')          # a fresh optimiser per call, as in the reference
-    sched = 0 if schedule == 'cosine' else 1
     chunk = min(niter, 50 if verbose else 1024)
     losses = torch.empty(chunk, dtype=torch.float32, device=net.device)
     loss = float('inf')
@@ -478,25 +598,23 @@ def global_alignment_loop_sharded(net, group=None, lr=0.01, niter=300, schedule=
     zeros, so losses and parameters are bit-identical to the single-GPU loop for any number of ranks. Start: all six parameter tensors are broadcast from rank 0 (a
     random `init=None` start differs between processes, for frozen tensors too); end: every rank receives the other ranks' rows of im_depthmaps."""
     import torch.distributed as dist
-    if schedule not in ('cosine', 'linear'):
-        raise ValueError(f'bad lr {schedule=}')
-    if niter <= 0:
+    start = _loop_start(net, niter, schedule)
+    if start is None:
         return float('inf')
+    eng, sched = start
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     # ALL six parameter tensors, frozen ones included: a frozen tensor without a preset still holds its per-process random start (init=None), and the replicated
     # pose / focal step would then diverge silently between ranks (a few KB apart from the depth maps)
-    for name in net._TRAINABLE_KEYS:
-        dist.broadcast(getattr(net, name).data, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
-    eng = net._ensure_engine()
+    tensors = net._engine_tensors()
+    for t in tensors.values():
+        dist.broadcast(t, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
     ranges = image_ranges(net.edges, net.imshapes, world)
     first, count = ranges[rank]
-    check(lib.d3r_aligner_set_option(eng, 2, 0), 'reset adam')
     check(lib.d3r_aligner_set_image_range(eng, first, count), 'set_image_range')
     red_ptr, red_n = C.c_void_p(), C.c_longlong()
     check(lib.d3r_aligner_reduced_sums(eng, C.byref(red_ptr), C.byref(red_n)), 'reduced_sums')
     # the engine's reduction buffer seen as a tensor (no copy): the collective works on it in place
     red = _device_view(red_ptr.value, int(red_n.value), torch.float64, net.device)
-    sched = 0 if schedule == 'cosine' else 1
     cap = int(getattr(net, '_engine_max_iters', 1024))
     losses = torch.empty(min(niter, cap), dtype=torch.float32, device=net.device)
     done, loss = 0, float('inf')
@@ -517,7 +635,7 @@ def global_alignment_loop_sharded(net, group=None, lr=0.01, niter=300, schedule=
             import logging
             logging.getLogger('dust3r_amd').error('d3r_aligner_set_image_range(all) failed with code %d after the sharded loop', rc)
     # every rank's own rows of the log-depth maps -> all ranks (sum with zeros elsewhere: exact)
-    depth = net.im_depthmaps.data
+    depth = tensors['im_depthmaps']
     own = torch.zeros_like(depth)
     own[first:first + count] = depth[first:first + count]
     dist.all_reduce(own, op=dist.ReduceOp.SUM, group=group)

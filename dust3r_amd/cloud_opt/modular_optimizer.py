@@ -12,23 +12,15 @@ ALIAS rows of that storage: `scene.im_poses[i].requires_grad` answers per image 
 `im_depthmaps.<i>` as (H, W), ...). The per-image `requires_grad` flags become the engine's trainability masks
 (d3r_aligner_set_trainable): frozen entries get no Adam update, as in the reference where they are not in the optimiser.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _lib
-from .._lib import check, current_stream, lib, ptr
 from ..utils.device import to_numpy
-from ..utils.geometry import geotrf
 from .base_opt import BasePCOptimizer
-from .optimizer import PointCloudOptimizer
 
 _ENTRIES = ('im_poses', 'im_depthmaps', 'im_focals', 'im_pp')
-# C ABI (include/dust3r_hip.h)
-_OPT_OPTIMIZE_PP, _OPT_ADAPTORS, _OPT_EDGE_MEAN_LOSS, _OPT_FX_AND_FY = 3, 4, 6, 7
-_TRAIN_KIND = {'im_poses': 0, 'im_focals': 1, 'im_pp': 2}
 
 
 class ParamEntries(list):
@@ -61,7 +53,6 @@ class ModularPointCloudOptimizer(BasePCOptimizer):
         self.register_buffer('_flat_im_focals', focals)
         self.register_buffer('_flat_im_pp', torch.zeros((n, 2)))
         self.register_buffer('_pp', torch.tensor([(w / 2, h / 2) for h, w in self.imshapes], dtype=torch.float32))
-        self._grid_cache = None
         self._bind_entries({'im_pp': [bool(optimize_pp)] * n})
 
     # ------------------------------------------------------------------ per-image views of the flat storage
@@ -131,8 +122,6 @@ class ModularPointCloudOptimizer(BasePCOptimizer):
         return self
 
     # ------------------------------------------------------------------ presets (modular_optimizer.py:37-92)
-    _get_msk_indices = PointCloudOptimizer._get_msk_indices
-
     def _no_grad(self, tensor):
         return tensor.requires_grad_(False)
 
@@ -197,104 +186,13 @@ class ModularPointCloudOptimizer(BasePCOptimizer):
                 param.data[:] = torch.as_tensor(depth).log().nan_to_num(neginf=0).to(param.device)
         return param
 
-    # ------------------------------------------------------------------ getters (modular_optimizer.py:94-151)
-    def get_focals(self):
-        """(n, 1), or (n, 2) = (fx, fy) with fx_and_fy."""
-        return (self._flat_im_focals / self.focal_brake).exp()
-
-    def get_principal_points(self):
-        return self._pp + 10 * self._flat_im_pp
-
-    def get_intrinsics(self):
-        K = torch.zeros((self.n_imgs, 3, 3), device=self.device)
-        focals = self.get_focals().view(self.n_imgs, -1)
-        K[:, 0, 0] = focals[:, 0]
-        K[:, 1, 1] = focals[:, -1]
-        K[:, :2, 2] = self.get_principal_points()
-        K[:, 2, 2] = 1
-        return K
-
-    def get_im_poses(self):  # cam to world
-        return self._get_poses(self._flat_im_poses)
-
-    def get_depthmaps(self, raw=False):
-        res = self._flat_im_depthmaps.exp()
-        if not raw:
-            res = [dm[:h * w].view(h, w) for dm, (h, w) in zip(res, self.imshapes)]
-        return res
-
-    _grid = PointCloudOptimizer._grid
-
-    def depth_to_pts3d(self):
-        focals = self.get_focals().unsqueeze(1)                 # (n,1,1 | 2): x = d (u - cx) / fx, y = d (v - cy) / fy
-        pp = self.get_principal_points().unsqueeze(1)           # (n,1,2)
-        depth = self.get_depthmaps(raw=True).unsqueeze(-1)      # (n,A,1)
-        rel = torch.cat((depth * (self._grid - pp) / focals, depth), dim=-1)
-        return geotrf(self.get_im_poses(), rel)
-
-    # ------------------------------------------------------------------ engine binding
-    def _ensure_engine(self):
-        _lib.require_device()
-        if self.device.type != 'cuda':
-            raise _lib.D3RError('the aligner is not on a GPU: call .to("cuda") (dust3r_amd has no CPU execution path)')
-        masks = {k: self._trainable(k) for k in ('im_poses', 'im_focals', 'im_pp')}
-        sig = (self.norm_pw_scale, self.pw_adaptors.requires_grad, self.dist_name, self.fx_and_fy,
-               tuple(tuple(m.tolist()) for m in masks.values()),
-               tuple(t.data_ptr() for t in (self.pw_poses, self.pw_adaptors, self._flat_im_depthmaps, self._flat_im_poses, self._flat_im_focals, self._flat_im_pp)))
-        if self._engine is not None and sig == self._engine_sig:
-            return self._engine
-        self._destroy_engine()
-        for k in ('_stacked_pred_i', '_stacked_pred_j', '_weight_i', '_weight_j', 'pw_poses', 'pw_adaptors', '_flat_im_poses',
-                  '_flat_im_depthmaps', '_flat_im_focals', '_flat_im_pp'):
-            t = getattr(self, k)
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32, f'{k} must be a contiguous fp32 CUDA tensor'
-        n, E = self.n_imgs, self.n_edges
-        arr = lambda v: (C.c_int * len(v))(*v)  # noqa: E731
-        ei, ej = arr([i for i, j in self.edges]), arr([j for i, j in self.edges])
-        hh, ww = arr([h for h, w in self.imshapes]), arr([w for h, w in self.imshapes])
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            # opt_im_poses / opt_im_focals = 1: the per-image masks below decide
-            check(lib.d3r_aligner_create(C.byref(h), n, E, ei, ej, hh, ww, self.max_area, ptr(self._stacked_pred_i),
-                                         ptr(self._stacked_pred_j), ptr(self._weight_i), ptr(self._weight_j), ptr(self.pw_poses.data),
-                                         ptr(self.pw_adaptors.data), ptr(self._flat_im_poses), ptr(self._flat_im_depthmaps),
-                                         ptr(self._flat_im_focals), ptr(self._flat_im_pp), float(self.base_scale), float(self.pw_break),
-                                         float(self.focal_brake), int(self.dist_name == 'l2'), int(self.norm_pw_scale), 1, 1, 1024,
-                                         current_stream()), 'aligner_create')
-            try:
-                check(lib.d3r_aligner_set_option(h, _OPT_OPTIMIZE_PP, int(masks['im_pp'].any())), 'set_option(optimize_pp)')
-                check(lib.d3r_aligner_set_option(h, _OPT_ADAPTORS, int(self.pw_adaptors.requires_grad)), 'set_option(allow_pw_adaptors)')
-                check(lib.d3r_aligner_set_option(h, _OPT_EDGE_MEAN_LOSS, 1), 'set_option(edge_mean_loss)')
-                check(lib.d3r_aligner_set_option(h, _OPT_FX_AND_FY, int(self.fx_and_fy)), 'set_option(fx_and_fy)')
-                for name, m in masks.items():
-                    check(lib.d3r_aligner_set_trainable(h, _TRAIN_KIND[name], bytes(m.astype(np.uint8))), f'set_trainable({name})')
-            except Exception:
-                lib.d3r_aligner_destroy(h)
-                raise
-        self._engine, self._engine_sig = h, sig
-        return h
-
-    @torch.no_grad()
-    def forward(self, ret_details=False):
-        """The alignment loss (base_opt.py:246-273), evaluated by the engine (no parameter update)."""
-        if ret_details:
-            raise NotImplementedError('ret_details: the per-pair loss matrix is not computed by the engine')
-        eng = self._ensure_engine()
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        check(lib.d3r_aligner_loss_grad(eng, ptr(loss), None, None, None, None, None, None, current_stream()), 'aligner_loss')
-        return loss[0]
-
-    @torch.no_grad()
-    def loss_and_grads(self):
-        """(loss, {name: grad}) of one forward/backward without a step. Image groups come flat: im_poses (n, 7), im_depthmaps (n, max_area),
-        im_focals (n, 1 | 2), im_pp (n, 2); gradients are given for frozen entries too."""
-        eng = self._ensure_engine()
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        g = {k: torch.zeros_like(getattr(self, k).data) for k in ('pw_poses', 'pw_adaptors')}
-        g.update({k: torch.zeros_like(getattr(self, '_flat_' + k)) for k in _ENTRIES})
-        check(lib.d3r_aligner_loss_grad(eng, ptr(loss), ptr(g['pw_poses']), ptr(g['im_poses']), ptr(g['im_depthmaps']),
-                                        ptr(g['im_focals']), ptr(g['im_pp']), ptr(g['pw_adaptors']), current_stream()), 'aligner_loss_grad')
-        return loss[0], g
+    # ------------------------------------------------------------------ getters (modular_optimizer.py:94-151) and engine binding: BasePCOptimizer's
+    def _engine_setup(self):
+        masks = {_lib.ALIGNER_TRAIN_POSES: self._trainable('im_poses'), _lib.ALIGNER_TRAIN_FOCALS: self._trainable('im_focals'),
+                 _lib.ALIGNER_TRAIN_PP: self._trainable('im_pp')}
+        options = {_lib.ALIGNER_OPT_OPTIMIZE_PP: masks[_lib.ALIGNER_TRAIN_PP].any(), _lib.ALIGNER_OPT_OPTIMIZE_ADAPTORS: self.pw_adaptors.requires_grad,
+                   _lib.ALIGNER_OPT_EDGE_MEAN_LOSS: 1, _lib.ALIGNER_OPT_FX_AND_FY: self.fx_and_fy}
+        return 1, 1, options, masks           # opt_im_poses / opt_im_focals = 1: the per-image masks decide
 
     def compute_global_alignment(self, init=None, niter_PnP=10, group=None, **kw):
         if group is not None and group is not False:

@@ -829,11 +829,13 @@ static void aligner_wait_ready(d3r_aligner* a, hipStream_t st) {
     if (a->ev_ready && st != a->create_stream) (void)hipStreamWaitEvent(st, a->ev_ready, 0);
 }
 
-#define HIPCHK(x)                                  \
-    do {                                           \
-        hipError_t e_ = (x);                       \
-        if (e_ != hipSuccess) return (int)e_ + 1000; \
+#define HIPCHK(x)                            \
+    do {                                     \
+        const int rc_ = rc_of(x);            \
+        if (rc_ != D3R_OK) return rc_;       \
     } while (0)
+
+static int launch_rc() { return hipGetLastError() == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH; }
 
 extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, const int* ei, const int* ej, const int* img_h,
                                   const int* img_w, int max_area, const float* pred_i, const float* pred_j, const float* w_i,
@@ -845,6 +847,7 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     if (((uintptr_t)pw_poses & 15) || ((uintptr_t)im_depth & 15) || ((uintptr_t)pw_adaptors & 7)) return D3R_ERR_INVALID;
     d3r_aligner* a = new (std::nothrow) d3r_aligner();
     if (!a) return D3R_ERR_ALLOC;
+    auto fail = [a](int rc) { d3r_aligner_destroy(a); return rc; };   // whatever is allocated so far goes with it
     a->n = n_imgs; a->E = n_edges; a->maxA = max_area;
     // the block-interleaved stream copy (round 5; measured against the planar copy of rounds 1-4, profiles/r05_k: 3998 -> 4085 it/s at 190 edges,
     // 2142 -> 2161 at 380, bit-identical losses)
@@ -856,12 +859,12 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     double ta[2] = {0, 0};
     for (int i = 0; i < n_imgs; ++i) {
         a->h_area[i] = img_h[i] * img_w[i];
-        if (a->h_area[i] > max_area || a->h_area[i] % 4 != 0) { delete a; return D3R_ERR_INVALID; }
+        if (a->h_area[i] > max_area || a->h_area[i] % 4 != 0) return fail(D3R_ERR_INVALID);
     }
     // adjacency (CSR by projecting image): side 0 entries project onto ei, side 1 onto ej
     std::vector<int> off(n_imgs + 1, 0), es(2 * (size_t)n_edges);
     for (int e = 0; e < n_edges; ++e) {
-        if (ei[e] < 0 || ei[e] >= n_imgs || ej[e] < 0 || ej[e] >= n_imgs) { delete a; return D3R_ERR_INVALID; }
+        if (ei[e] < 0 || ei[e] >= n_imgs || ej[e] < 0 || ej[e] >= n_imgs) return fail(D3R_ERR_INVALID);
         off[ei[e] + 1]++; off[ej[e] + 1]++;
         ta[0] += a->h_area[ei[e]]; ta[1] += a->h_area[ej[e]];
     }
@@ -889,9 +892,9 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
                  o_lh = take(a->loss_cap), o_gs = take((size_t)n_edges * 8);
     const size_t dbl = ((size_t)2 * n_edges * PW + (size_t)n_imgs * PW + (size_t)n_edges * 8 + 8);
     a->state_bytes = fl * sizeof(float) + dbl * sizeof(double) + 64;
-    if (hipMalloc((void**)&a->state, a->state_bytes) != hipSuccess) { delete a; return D3R_ERR_ALLOC; }
+    if (hipMalloc((void**)&a->state, a->state_bytes) != hipSuccess) { a->state = nullptr; return fail(D3R_ERR_ALLOC); }
     hipStream_t st = (hipStream_t)stream;   // the clear and the re-layout below are ordered on the caller's stream, like every later call
-    if (hipMemsetAsync(a->state, 0, a->state_bytes, st) != hipSuccess) { (void)hipFree(a->state); delete a; return D3R_ERR_LAUNCH; }
+    if (hipMemsetAsync(a->state, 0, a->state_bytes, st) != hipSuccess) return fail(D3R_ERR_LAUNCH);
     float* b = a->state;
     a->depth_m = b + o_dm; a->depth_v = b + o_dv; a->pw_m = b + o_pwm; a->pw_v = b + o_pwv; a->imp_m = b + o_im;
     a->imp_v = b + o_iv; a->foc_m = b + o_fm; a->foc_v = b + o_fv; a->pp_m = b + o_pm; a->pp_v = b + o_pv; a->pa_m = b + o_am; a->pa_v = b + o_av; a->d_edge = b + o_de; a->d_img = b + o_di;
@@ -900,7 +903,7 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     a->red_edge = db; a->red_img = db + (size_t)2 * n_edges * PW; a->scratch = a->red_img + (size_t)n_imgs * PW;
 
     const size_t ib = (3 * (size_t)n_imgs + (n_imgs + 1) + 2 * (size_t)n_edges) * sizeof(int);
-    if (hipMalloc((void**)&a->d_w, ib) != hipSuccess) { (void)hipFree(a->state); delete a; return D3R_ERR_ALLOC; }
+    if (hipMalloc((void**)&a->d_w, ib) != hipSuccess) { a->d_w = nullptr; return fail(D3R_ERR_ALLOC); }
     a->d_h = a->d_w + n_imgs; a->d_area = a->d_h + n_imgs; a->d_adj_off = a->d_area + n_imgs; a->d_adj_es = a->d_adj_off + n_imgs + 1;
     // blocking copies (pageable host vectors): complete in device memory when they return, whatever stream the caller works on
     (void)hipMemcpy(a->d_w, a->h_w.data(), n_imgs * sizeof(int), hipMemcpyHostToDevice);
@@ -910,12 +913,12 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     (void)hipMemcpy(a->d_adj_es, es.data(), 2 * (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice);
     {
         const size_t per_side = (size_t)n_edges * 4 * a->maxAp;
-        if (hipMalloc((void**)&a->inter, 2 * per_side * sizeof(float)) != hipSuccess) { (void)hipFree(a->state); (void)hipFree(a->d_w); delete a; return D3R_ERR_ALLOC; }
+        if (hipMalloc((void**)&a->inter, 2 * per_side * sizeof(float)) != hipSuccess) { a->inter = nullptr; return fail(D3R_ERR_ALLOC); }
         const size_t total = (size_t)n_edges * a->maxAp;
         const int grid = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
         hipLaunchKernelGGL(aligner_interleave_kernel, dim3(grid), dim3(256), 0, st, pred_i, w_i, a->inter, n_edges, max_area, a->maxAp);
         hipLaunchKernelGGL(aligner_interleave_kernel, dim3(grid), dim3(256), 0, st, pred_j, w_j, a->inter + per_side, n_edges, max_area, a->maxAp);
-        if (hipGetLastError() != hipSuccess) { (void)hipFree(a->inter); (void)hipFree(a->state); (void)hipFree(a->d_w); delete a; return D3R_ERR_LAUNCH; }
+        if (hipGetLastError() != hipSuccess) return fail(D3R_ERR_LAUNCH);
     }
     a->create_stream = st;
     if (hipEventCreateWithFlags(&a->ev_ready, hipEventDisableTiming) == hipSuccess) (void)hipEventRecord(a->ev_ready, st);
@@ -924,13 +927,14 @@ extern "C" int d3r_aligner_create(d3r_aligner** out, int n_imgs, int n_edges, co
     return D3R_OK;
 }
 
+// also the failure path of d3r_aligner_create: whatever of the object is built so far is released
 extern "C" int d3r_aligner_destroy(d3r_aligner* a) {
     if (!a) return D3R_OK;
     if (a->ev_ready) (void)hipEventDestroy(a->ev_ready);
     if (a->inter) (void)hipFree(a->inter);
     if (a->d_train) (void)hipFree(a->d_train);
-    (void)hipFree(a->state);
-    (void)hipFree(a->d_w);
+    if (a->state) (void)hipFree(a->state);
+    if (a->d_w) (void)hipFree(a->d_w);
     delete a;
     return D3R_OK;
 }
@@ -944,66 +948,79 @@ static AdamCoef adam_coef(double lr, long step) {
     return c;
 }
 
-// phase 0: the whole iteration; 1: [derived matrices] + main kernel + reduction (d3r_aligner_step_begin); 2: pose / focal step + step count (d3r_aligner_step_end)
-static int aligner_pass(d3r_aligner* a, bool update, double lr, int hist_idx, float* g_pw, float* g_imp, float* g_depth, float* g_foc,
-                        bool refresh_derived_first, hipStream_t st, float* g_pp = nullptr, float* g_pa = nullptr, int phase = 0) {
+// What one host pass does: an Adam iteration (update) or a loss / gradient evaluation, whole or one half of it.
+struct PassArgs {
+    bool update = false;
+    double lr = 0.0;
+    int hist_idx = 0;                     // slot of loss_hist that receives the loss
+    float *g_pw = nullptr, *g_imp = nullptr, *g_depth = nullptr, *g_foc = nullptr, *g_pp = nullptr, *g_pa = nullptr;   // optional gradient export (tests)
+    bool refresh_derived_first = false;   // recompute the derived matrices from the parameters before the main kernel
+    int phase = 0;   // 0: the whole iteration; 1: [derived matrices] + main kernel + reduction (d3r_aligner_step_begin); 2: pose / focal step + step count (d3r_aligner_step_end)
+};
+
+// the pose / focal step as it refreshes the derived matrices: no update, no gradient export (finish_pass adds them for the step that closes a pass)
+static SmallView small_view(const d3r_aligner* a, const PassArgs& p) {
     SmallView s;
     s.n = a->n; s.E = a->E; s.pw_poses = a->pw_poses; s.pw_adaptors = a->pw_adaptors; s.im_poses = a->im_poses;
     s.im_focals = a->im_focals; s.im_pp = a->im_pp; s.img_w = a->d_w; s.img_h = a->d_h;
     s.pw_m = a->pw_m; s.pw_v = a->pw_v; s.imp_m = a->imp_m; s.imp_v = a->imp_v; s.foc_m = a->foc_m; s.foc_v = a->foc_v;
-    s.pp_m = a->pp_m; s.pp_v = a->pp_v; s.g_pp = nullptr; s.opt_pp = a->opt_pp;
-    s.pa_m = a->pa_m; s.pa_v = a->pa_v; s.g_pa = nullptr; s.opt_adapt = a->opt_adapt;
+    s.pp_m = a->pp_m; s.pp_v = a->pp_v; s.opt_pp = a->opt_pp; s.pa_m = a->pa_m; s.pa_v = a->pa_v; s.opt_adapt = a->opt_adapt;
     s.red_edge = a->red_edge; s.red_img = a->red_img; s.d_edge = a->d_edge; s.d_img = a->d_img; s.scratch = a->scratch;
-    s.loss_hist = a->loss_hist; s.iter = hist_idx; s.g_pw = nullptr; s.g_imp = nullptr; s.g_foc = nullptr;
+    s.loss_hist = a->loss_hist; s.iter = p.hist_idx;
     s.base_scale = a->base_scale; s.pw_break = a->pw_break; s.focal_break = a->focal_break;
     s.norm_pw_scale = a->norm_pw_scale; s.opt_poses = a->opt_poses; s.opt_focals = a->opt_focals;
-    s.update = 0; s.adam = adam_coef(lr, a->step + 1);
+    s.adam = adam_coef(p.lr, a->step + 1);
     s.tr_pose = a->d_train; s.tr_foc = a->d_train ? a->d_train + a->n : nullptr; s.tr_pp = a->d_train ? a->d_train + 2 * a->n : nullptr;
     s.nfoc = a->nfoc;
-    const bool modular = a->modular();
-    if (phase == 2) {
-        s.update = update ? 1 : 0;
-        s.g_pw = g_pw; s.g_imp = g_imp; s.g_foc = g_foc; s.g_pp = g_pp; s.g_pa = g_pa;
-        launch_small(s, st, a->generic_small, modular);
-        if (update) a->step++;
-        return hipGetLastError() == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH;
-    }
-    if (refresh_derived_first) {
+    s.update = 0; s.g_pw = s.g_imp = s.g_foc = s.g_pp = s.g_pa = nullptr;
+    return s;
+}
+
+static AlignerView main_view(const d3r_aligner* a, const PassArgs& p, const AdamCoef& adam) {
+    AlignerView v;
+    v.img0 = a->img0;
+    v.n = a->n; v.E = a->E; v.maxA = a->maxA; v.nslot = a->nslot; v.img_w = a->d_w; v.img_area = a->d_area;
+    v.adj_off = a->d_adj_off; v.adj_es = a->d_adj_es; v.inter = a->inter; v.maxAp = a->maxAp;
+    v.depth = a->im_depth; v.depth_m = a->depth_m; v.depth_v = a->depth_v;
+    v.depth_grad = p.g_depth; v.d_edge = a->d_edge; v.d_img = a->d_img; v.part_edge = a->part_edge; v.part_img = a->part_img;
+    v.inv_area[0] = a->inv_area[0]; v.inv_area[1] = a->inv_area[1]; v.l2 = a->l2; v.update = p.update ? 1 : 0;
+    v.use_dpp = a->use_dpp; v.adam = adam; v.edge_mean = a->edge_mean;
+    return v;
+}
+
+static void launch_main(const AlignerView& v, const dim3 grid, hipStream_t st, bool modular) {
+    void (*const kernel)(AlignerView) = modular ? (v.l2 ? aligner_main_kernel<true, true> : aligner_main_kernel<false, true>)
+                                                : (v.l2 ? aligner_main_kernel<true, false> : aligner_main_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(ALIGNER_NWV * 64), 0, st, v);
+}
+
+// the pose / focal step that closes a pass (with the update and the gradient exports), the step count and the launch check of the whole pass
+static int finish_pass(d3r_aligner* a, const PassArgs& p, SmallView s, hipStream_t st) {
+    s.update = p.update ? 1 : 0;
+    s.g_pw = p.g_pw; s.g_imp = p.g_imp; s.g_foc = p.g_foc; s.g_pp = p.g_pp; s.g_pa = p.g_pa;
+    launch_small(s, st, a->generic_small, a->modular());
+    if (p.update) a->step++;
+    return launch_rc();
+}
+
+static int aligner_pass(d3r_aligner* a, const PassArgs& p, hipStream_t st) {
+    const SmallView s = small_view(a, p);
+    if (p.phase == 2) return finish_pass(a, p, s, st);
+    if (p.refresh_derived_first) {
         SmallView s0 = s;
         s0.loss_hist = nullptr;
-        launch_small(s0, st, a->generic_small, modular);
+        launch_small(s0, st, a->generic_small, a->modular());
     }
     const int imgc = a->imgc < 0 ? a->n : a->imgc;
     if (a->part_clear_pending) {        // records of images outside the range must read as zero (they are never written here)
         HIPCHK(hipMemsetAsync(a->part_edge, 0, (size_t)(2 * a->E + a->n) * a->nslot * PW * sizeof(float), st));
         a->part_clear_pending = false;
     }
-    AlignerView v;
-    v.img0 = a->img0;
-    v.n = a->n; v.E = a->E; v.maxA = a->maxA; v.nslot = a->nslot; v.img_w = a->d_w; v.img_area = a->d_area;
-    v.adj_off = a->d_adj_off; v.adj_es = a->d_adj_es; v.inter = a->inter; v.maxAp = a->maxAp;
-    v.depth = a->im_depth; v.depth_m = a->depth_m; v.depth_v = a->depth_v;
-    v.depth_grad = g_depth; v.d_edge = a->d_edge; v.d_img = a->d_img; v.part_edge = a->part_edge; v.part_img = a->part_img;
-    v.inv_area[0] = a->inv_area[0]; v.inv_area[1] = a->inv_area[1]; v.l2 = a->l2; v.update = update ? 1 : 0;
-    v.use_dpp = a->use_dpp; v.adam = s.adam; v.edge_mean = a->edge_mean;
-    const dim3 grid(imgc * a->nslot);
-    if (imgc > 0) {
-        if (modular) {
-            if (a->l2) hipLaunchKernelGGL((aligner_main_kernel<true, true>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
-            else hipLaunchKernelGGL((aligner_main_kernel<false, true>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
-        } else {
-            if (a->l2) hipLaunchKernelGGL((aligner_main_kernel<true, false>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
-            else hipLaunchKernelGGL((aligner_main_kernel<false, false>), grid, dim3(ALIGNER_NWV * 64), 0, st, v);
-        }
-    }
+    if (imgc > 0) launch_main(main_view(a, p, s.adam), dim3(imgc * a->nslot), st, a->modular());
     // part_edge | part_img and red_edge | red_img are contiguous: one launch reduces the 2E + n entries
     hipLaunchKernelGGL(aligner_reduce_kernel, dim3(2 * a->E + a->n), dim3(256), 0, st, a->part_edge, a->red_edge, a->nslot);
-    if (phase == 1) return hipGetLastError() == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH;
-    s.update = update ? 1 : 0;
-    s.g_pw = g_pw; s.g_imp = g_imp; s.g_foc = g_foc; s.g_pp = g_pp; s.g_pa = g_pa;
-    launch_small(s, st, a->generic_small, modular);
-    if (update) a->step++;
-    return hipGetLastError() == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH;
+    if (p.phase == 1) return launch_rc();
+    return finish_pass(a, p, s, st);
 }
 
 extern "C" int d3r_aligner_set_option(d3r_aligner* a, int option, int value) {
@@ -1016,7 +1033,7 @@ extern "C" int d3r_aligner_set_option(d3r_aligner* a, int option, int value) {
         case D3R_ALIGNER_OPT_EDGE_MEAN_LOSS: a->edge_mean = value != 0; return D3R_OK;
         case D3R_ALIGNER_OPT_FX_AND_FY: a->nfoc = value != 0 ? 2 : 1; return D3R_OK;
         case D3R_ALIGNER_OPT_RESET_ADAM:
-            // the moments are cleared on the stream of the NEXT d3r_aligner_run / loss_grad call (ordered against the iterations that
+            // the moments are cleared on the stream of the NEXT d3r_aligner_run / step_begin call (ordered against the iterations that
             // are still in flight there), not on the legacy NULL stream
             a->reset_pending = true;
             a->step = 0;
@@ -1041,22 +1058,39 @@ extern "C" int d3r_aligner_set_trainable(d3r_aligner* a, int kind, const unsigne
     return D3R_OK;
 }
 
+static double sched_lr(int k, int iter0, int niter_total, float lr_base, float lr_min, int schedule) {
+    const double t = (double)(iter0 + k) / (double)niter_total;
+    return schedule == D3R_SCHEDULE_COSINE ? (double)lr_min + ((double)lr_base - (double)lr_min) * (1.0 + cos(t * M_PI)) / 2.0
+                                           : (double)lr_base + ((double)lr_min - (double)lr_base) * t;
+}
+
+// what precedes iterations on `st`: it is ordered behind create's work, and a pending D3R_ALIGNER_OPT_RESET_ADAM clears the moments there
+static int begin_iterations(d3r_aligner* a, hipStream_t st) {
+    aligner_wait_ready(a, st);
+    if (a->reset_pending) {
+        HIPCHK(hipMemsetAsync(a->depth_m, 0, (size_t)((char*)a->d_edge - (char*)a->depth_m), st));
+        a->reset_pending = false;
+    }
+    return D3R_OK;
+}
+
+// iteration k of a run in the given phase (PassArgs::phase)
+static int aligner_iteration(d3r_aligner* a, int k, double lr, int phase, hipStream_t st) {
+    PassArgs p;
+    p.update = true; p.lr = lr; p.hist_idx = k; p.refresh_derived_first = k == 0 && phase != 2; p.phase = phase;
+    return aligner_pass(a, p, st);
+}
+
 // niter iterations of global_alignment_iter; lr follows the reference schedule evaluated at
 // t = (iter0 + k) / niter_total (base_opt.py:352-366, commons.py:83-90). losses (device or null).
 extern "C" int d3r_aligner_run(d3r_aligner* a, int niter, int iter0, int niter_total, float lr_base, float lr_min, int schedule,
                                float* losses_out_device, void* stream) {
     if (!a || niter <= 0 || niter > a->loss_cap || niter_total <= 0) return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    aligner_wait_ready(a, st);
-    if (a->reset_pending) {
-        HIPCHK(hipMemsetAsync(a->depth_m, 0, (size_t)((char*)a->d_edge - (char*)a->depth_m), st));
-        a->reset_pending = false;
-    }
+    const int rc0 = begin_iterations(a, st);
+    if (rc0 != D3R_OK) return rc0;
     for (int k = 0; k < niter; ++k) {
-        const double t = (double)(iter0 + k) / (double)niter_total;
-        const double lr = schedule == D3R_SCHEDULE_COSINE ? (double)lr_min + ((double)lr_base - (double)lr_min) * (1.0 + cos(t * M_PI)) / 2.0
-                                                          : (double)lr_base + ((double)lr_min - (double)lr_base) * t;
-        const int rc = aligner_pass(a, true, lr, k, nullptr, nullptr, nullptr, nullptr, k == 0, st);
+        const int rc = aligner_iteration(a, k, sched_lr(k, iter0, niter_total, lr_base, lr_min, schedule), 0, st);
         if (rc != D3R_OK) return rc;
     }
     if (losses_out_device) HIPCHK(hipMemcpyAsync(losses_out_device, a->loss_hist, niter * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1064,12 +1098,6 @@ extern "C" int d3r_aligner_run(d3r_aligner* a, int niter, int iter0, int niter_t
 }
 
 // ---- one iteration in two calls, for one process per GPU (include/dust3r_hip.h) ------------------------------------------------------------------
-static double sched_lr(int k, int iter0, int niter_total, float lr_base, float lr_min, int schedule) {
-    const double t = (double)(iter0 + k) / (double)niter_total;
-    return schedule == D3R_SCHEDULE_COSINE ? (double)lr_min + ((double)lr_base - (double)lr_min) * (1.0 + cos(t * M_PI)) / 2.0
-                                           : (double)lr_base + ((double)lr_min - (double)lr_base) * t;
-}
-
 extern "C" int d3r_aligner_set_image_range(d3r_aligner* a, int first, int count) {
     if (!a || first < 0 || count < 0 || first + count > a->n) return D3R_ERR_INVALID;
     a->img0 = first;
@@ -1081,17 +1109,14 @@ extern "C" int d3r_aligner_set_image_range(d3r_aligner* a, int first, int count)
 extern "C" int d3r_aligner_step_begin(d3r_aligner* a, int k, int iter0, int niter_total, float lr_base, float lr_min, int schedule, void* stream) {
     if (!a || k < 0 || k >= a->loss_cap || niter_total <= 0 || a->modular()) return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    aligner_wait_ready(a, st);
-    if (a->reset_pending) {
-        HIPCHK(hipMemsetAsync(a->depth_m, 0, (size_t)((char*)a->d_edge - (char*)a->depth_m), st));
-        a->reset_pending = false;
-    }
-    return aligner_pass(a, true, sched_lr(k, iter0, niter_total, lr_base, lr_min, schedule), k, nullptr, nullptr, nullptr, nullptr, k == 0, st, nullptr, nullptr, 1);
+    const int rc = begin_iterations(a, st);
+    if (rc != D3R_OK) return rc;
+    return aligner_iteration(a, k, sched_lr(k, iter0, niter_total, lr_base, lr_min, schedule), 1, st);
 }
 
 extern "C" int d3r_aligner_step_end(d3r_aligner* a, int k, int iter0, int niter_total, float lr_base, float lr_min, int schedule, void* stream) {
     if (!a || k < 0 || k >= a->loss_cap || niter_total <= 0 || a->modular()) return D3R_ERR_INVALID;
-    return aligner_pass(a, true, sched_lr(k, iter0, niter_total, lr_base, lr_min, schedule), k, nullptr, nullptr, nullptr, nullptr, false, (hipStream_t)stream, nullptr, nullptr, 2);
+    return aligner_iteration(a, k, sched_lr(k, iter0, niter_total, lr_base, lr_min, schedule), 2, (hipStream_t)stream);
 }
 
 extern "C" int d3r_aligner_reduced_sums(d3r_aligner* a, void** ptr, long long* count) {
@@ -1107,14 +1132,18 @@ extern "C" int d3r_aligner_read_losses(d3r_aligner* a, int niter, float* losses_
     return D3R_OK;
 }
 
-// one forward/backward WITHOUT a step: loss (device float[1]) and gradients (device, any may be null)
+// one forward/backward WITHOUT a step: loss (device float[1]) and gradients (device, any may be null). Waits for create's work only: a pending
+// D3R_ALIGNER_OPT_RESET_ADAM stays pending for the next iterations
 extern "C" int d3r_aligner_loss_grad(d3r_aligner* a, float* loss_device, float* g_pw_poses, float* g_im_poses, float* g_im_depth,
                                      float* g_im_focals, float* g_im_pp, float* g_pw_adaptors, void* stream) {
     if (!a) return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     aligner_wait_ready(a, st);
-    float* gpw = g_pw_poses ? g_pw_poses : a->g_scratch;  // forces the gradient branch of the small kernel
-    const int rc = aligner_pass(a, false, 0.0, 0, gpw, g_im_poses, g_im_depth, g_im_focals, true, st, g_im_pp, g_pw_adaptors);
+    PassArgs p;
+    p.g_pw = g_pw_poses ? g_pw_poses : a->g_scratch;  // forces the gradient branch of the small kernel
+    p.g_imp = g_im_poses; p.g_depth = g_im_depth; p.g_foc = g_im_focals; p.g_pp = g_im_pp; p.g_pa = g_pw_adaptors;
+    p.refresh_derived_first = true;
+    const int rc = aligner_pass(a, p, st);
     if (rc != D3R_OK) return rc;
     if (loss_device) HIPCHK(hipMemcpyAsync(loss_device, a->loss_hist, sizeof(float), hipMemcpyDeviceToDevice, st));
     return D3R_OK;

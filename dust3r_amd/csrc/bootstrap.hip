@@ -330,7 +330,6 @@ __global__ __launch_bounds__(64) void pnp_reduce_kernel(const double* partial, i
 }  // namespace d3r
 
 using namespace d3r;
-static inline int rc_of(hipError_t e) { return e == hipSuccess ? D3R_OK : 1000 + (int)e; }
 
 extern "C" int d3r_row_means(const float* x, int rows, int cols, int ld, float* out, void* stream) {
     if (!x || !out || rows <= 0 || cols <= 0 || ld < cols || (ld & 3)) return D3R_ERR_INVALID;

@@ -4,7 +4,6 @@
 
 using namespace d3r;
 
-static inline int rc_of(hipError_t e) { return e == hipSuccess ? D3R_OK : 1000 + (int)e; }
 static inline int rup(int a, int b) { return (a + b - 1) / b * b; }
 
 extern "C" int d3r_rope2d(void* tokens, const int64_t* positions, int B, int N, int H, int D, float base, float F0, int dtype, void* stream) {

@@ -393,8 +393,6 @@ __global__ void drop_gt_norm_kernel(double* out, int B) {
 
 using namespace d3r::losses;
 
-static inline int rc_of(hipError_t e) { return e == hipSuccess ? D3R_OK : 1000 + (int)e; }
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 static size_t hist_bytes(int B) { return align256((size_t)B * MAXSEL * BINS * sizeof(uint32_t)); }
 static size_t sel_bytes(int B) { return align256((size_t)B * MAXSEL * 2 * sizeof(uint32_t)); }
 static size_t partial_bytes(int B) { return align256((size_t)B * 2 * MAXGX * 4 * sizeof(double)); }

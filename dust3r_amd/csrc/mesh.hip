@@ -320,10 +320,6 @@ __global__ __launch_bounds__(256) void mesh_bounds_kernel(int n_parts, const flo
 
 using namespace d3r::mesh;
 
-static inline int rc_of(hipError_t e) { return e == hipSuccess ? D3R_OK : 1000 + (int)e; }
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // grid.x of every tile / pixel launch, and the tiles a view can have: a 512 x 384 view has 192 tiles; grid-stride beyond 1024
 static int mesh_tiles(int max_area) { return (int)(((long long)max_area + NT - 1) / NT); }
 static int mesh_blocks(int max_area) { return std::min(mesh_tiles(max_area), 1024); }

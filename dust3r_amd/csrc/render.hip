@@ -287,8 +287,6 @@ __global__ __launch_bounds__(NT) void render_resolve_kernel(const float* __restr
 
 using namespace d3r::render;
 
-static inline int rc_of(hipError_t e) { return e == hipSuccess ? D3R_OK : 1000 + (int)e; }
-
 static bool cams_ok(int n_cams, const float* w2c, int stride, const float* intr, float near) {
     return n_cams > 0 && n_cams <= 65535 && w2c && intr && (stride == 12 || stride == 16) && near > 0.f && near < __builtin_huge_valf();
 }

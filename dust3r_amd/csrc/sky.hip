@@ -279,10 +279,6 @@ __global__ __launch_bounds__(256) void sky_select_kernel(const int* __restrict__
 
 using namespace d3r::sky;
 
-static inline int rc_of(hipError_t e) { return e == hipSuccess ? D3R_OK : 1000 + (int)e; }
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 extern "C" size_t d3r_segment_sky_workspace_bytes(int n_imgs, int max_area) {
     if (n_imgs <= 0 || max_area <= 0) return 0;
     return 2 * align256((size_t)n_imgs * max_area * sizeof(int)) + align256((size_t)n_imgs * sizeof(int));

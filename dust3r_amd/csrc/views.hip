@@ -13,11 +13,8 @@
 // Lanes run along the OUTPUT row in the two kernels that write the results, so a wave stores 256 contiguous bytes per channel whether
 // or not the view is transposed. No atomics, no scratch; the integer arithmetic and index rules live in views_math.hpp, shared with
 // the host build that the CPU tests exercise.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
 #include "../../include/dust3r_hip.h"
+#include "common.hpp"
 #include "views_math.hpp"
 
 namespace d3r {
@@ -136,8 +133,6 @@ __global__ __launch_bounds__(TILE_X * TILE_R) void views_depth_kernel(const d3r_
     pts3d[3 * i + 2] = p[2];
     valid_mask[i] = ok;
 }
-
-static inline int rc_of(hipError_t e) { return e == hipSuccess ? D3R_OK : 1000 + (int)e; }
 
 // every index the kernels form from this plan stays inside its buffers (the tables' contents are clamped by the kernels themselves)
 static bool plan_ok(const d3r_view_plan& p, int H, int W, size_t workspace_bytes) {

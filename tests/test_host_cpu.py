@@ -179,6 +179,42 @@ def test_analytic_aligner_gradients_on_host():
     assert rel(gfoc, grads['im_focals'].numpy().ravel()) < 2e-5
 
 
+def test_aligner_constants_match_the_header():
+    """_lib's ALIGNER_OPT_* / ALIGNER_TRAIN_* / SCHEDULE_* are the header's D3R_<name> values, none missing on either side."""
+    from dust3r_amd import _lib
+    hdr = open(os.path.join(ROOT, 'include', 'dust3r_hip.h')).read()
+    prefixes = ('ALIGNER_OPT_', 'ALIGNER_TRAIN_', 'SCHEDULE_')
+    defines = {name: int(value) for name, value in re.findall(r'^#define D3R_(\w+)[ \t]+(-?\d+)', hdr, re.M) if name.startswith(prefixes)}
+    assert sum(k.startswith('ALIGNER_OPT_') for k in defines) == 7 and sum(k.startswith('ALIGNER_TRAIN_') for k in defines) == 3
+    assert sum(k.startswith('SCHEDULE_') for k in defines) == 2
+    assert {k: v for k, v in vars(_lib).items() if k.startswith(prefixes)} == defines
+
+
+@pytest.mark.parametrize('mode,kw', [('PointCloudOptimizer', {}), ('ModularPointCloudOptimizer', {}), ('ModularPointCloudOptimizer', {'fx_and_fy': True})])
+def test_both_scenes_expose_the_same_engine_binding(mode, kw):
+    """_engine_tensors(): six contiguous fp32 tensors in d3r_aligner_create's order that ARE the scene's storage; no engine without a GPU."""
+    from dust3r_amd import _lib
+    from dust3r_amd.cloud_opt import GlobalAlignerMode, global_aligner
+    from dust3r_amd.synthetic import synthetic_mixed_scene
+    scene = global_aligner(synthetic_mixed_scene([(8, 12), (12, 8), (8, 12)], seed=0), 'cpu', mode=GlobalAlignerMode(mode), verbose=False, **kw)
+    n, E, A = 3, 6, 96
+    tensors = scene._engine_tensors()
+    assert [(k, tuple(t.shape)) for k, t in tensors.items()] == [('pw_poses', (E, 8)), ('pw_adaptors', (E, 2)), ('im_poses', (n, 7)), ('im_depthmaps', (n, A)),
+                                                                 ('im_focals', (n, 2 if kw else 1)), ('im_pp', (n, 2))]
+    assert all(t.is_contiguous() and t.dtype == torch.float32 and not t.requires_grad for t in tensors.values())
+    for k, t in tensors.items():
+        own = getattr(scene, k)                                  # what state_dict() reads: a parameter, or the Modular scene's list of per-image ones
+        if isinstance(own, list):
+            assert [p.data_ptr() for p in own] == [t[i].data_ptr() for i in range(n)], k
+        else:
+            assert own.data_ptr() == t.data_ptr(), k
+    tensors['im_pp'].fill_(0.25)
+    state = scene.state_dict()
+    assert torch.equal(state['im_pp.2'] if 'im_pp.2' in state else state['im_pp'][2], torch.full((2,), 0.25))
+    with pytest.raises(_lib.D3RError):
+        scene._ensure_engine()
+
+
 def test_model_state_dict_duplication_and_parsing():
     from dust3r_amd.model import AsymmetricCroCo3DStereo, expected_state, parse_model_string
     from dust3r_amd.synthetic import MODEL_CONFIGS, synthetic_state_dict
