@@ -128,6 +128,10 @@ def _load():
         'd3r_sky_color_mask': (i, [i, vp, i, ip, ip, i, vp, vp]),
         'd3r_scene_mesh_workspace_bytes': (C.c_size_t, [i, i]),
         'd3r_scene_mesh': (i, [i, vp, vp, vp, i, ip, ip, i, i, vp, vp, vp, vp, vp, vp, vp]),
+        'd3r_scene_gallery_workspace_bytes': (C.c_size_t, [i, i]),
+        'd3r_scene_gallery': (i, [i, fp, fp, ip, i, fp, fp, fp, fp, vp, vp]),
+        'd3r_scene_gallery_launch_bound': (None, [C.POINTER(C.c_int)] * 3),
+        'd3r_selftest_gallery_index_host': (i, [fp, i, ip]),
         'd3r_render_project': (i, [i, fp, i, fp, i, fp, f, ip, vp, vp]),
         'd3r_render_clear': (i, [i, i, i, vp, vp]),
         'd3r_render_points': (i, [i, fp, vp, C.c_uint32, i, fp, i, fp, f, i, i, i, vp, vp, vp]),

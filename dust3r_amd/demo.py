@@ -7,15 +7,29 @@ binary:
 - the scene: a TRIANGLES primitive (indices, POSITION, COLOR_0 = the face colours averaged onto the vertices) or, with as_pointcloud, a
   POINTS primitive (POSITION, COLOR_0); left out when nothing is valid;
 - one wireframe per camera and, unless transparent_cams, its picture on a textured quad (PNG of np.uint8(255 * img)).
-`render_turntable` (new; the reference has no headless output) draws the same scene into PNG frames on the GPU instead."""
+`render_turntable` (new; the reference has no headless output) draws the same scene into PNG frames on the GPU instead.
+
+The function users call, `get_reconstructed_scene` (dust3r/demo.py:135-186): files -> load_images -> make_pairs -> inference -> global_aligner ->
+compute_global_alignment -> get_3D_model_from_scene, and the rgb / depth / confidence gallery it returns (`scene_gallery`: one GPU call
+for all images, csrc/gallery.hip, no matplotlib). `scenegraph_options` is the rule of set_scenegraph_options as plain data, and
+`python -m dust3r_amd.demo` the command line in place of the gradio page."""
+import argparse
+import copy
+import json
+import math
 import os
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
+from . import _lib
+from .cloud_opt import GlobalAlignerMode, global_aligner
 from .glb import ARRAY_BUFFER, FLOAT, POINTS, TRIANGLES, GlbBuilder
-from .utils.device import to_numpy, usable_cpus
+from .image_pairs import make_pairs
+from .inference import inference
+from .utils.device import host_tensor, to_numpy, usable_cpus
+from .utils.image import IMAGE_EXTENSIONS, load_images
 from .viz import CAM_COLORS, OPENGL, SceneViz, auto_cam_size, scene_camera_geometry, scene_mesh_batch, turntable_poses
 
 
@@ -187,3 +201,252 @@ def render_turntable(outdir, scene, n_frames=36, size=(1024, 768), as_pointcloud
     if not silent:
         print('(wrote', n_frames, 'frames to', outdir, ')')
     return names
+
+
+# ---- the gallery -------------------------------------------------------------------------------------------------------------------
+# matplotlib's `jet` as its segment data: per channel (x, y below x, y above x)
+_JET_SEGMENTS = {
+    'red': ((0.00, 0, 0), (0.35, 0, 0), (0.66, 1, 1), (0.89, 1, 1), (1.00, 0.5, 0.5)),
+    'green': ((0.000, 0, 0), (0.125, 0, 0), (0.375, 1, 1), (0.640, 1, 1), (0.910, 0, 0), (1.000, 0, 0)),
+    'blue': ((0.00, 0.5, 0.5), (0.11, 1, 1), (0.34, 1, 1), (0.65, 0, 0), (1.00, 0, 0)),
+}
+GALLERY_BAD_ROW = 256
+
+
+def jet_lut(n=256):
+    """The (n, 4) float64 RGBA table of matplotlib's `jet`: its segment data interpolated linearly at linspace(0, 1, n) the way
+    LinearSegmentedColormap builds its table, alpha 1."""
+    xind = (n - 1) * np.linspace(0, 1, n)
+    lut = np.ones((n, 4))
+    for c, name in enumerate(('red', 'green', 'blue')):
+        data = np.array(_JET_SEGMENTS[name], dtype=np.float64)
+        x, y0, y1 = data[:, 0] * (n - 1), data[:, 1], data[:, 2]
+        ind = np.searchsorted(x, xind)[1:-1]
+        distance = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+        lut[:, c] = np.clip(np.concatenate([[y1[0]], distance * (y0[ind] - y1[ind - 1]) + y1[ind - 1], [y0[-1]]]), 0.0, 1.0)
+    return lut
+
+
+def gallery_table():
+    """The (257, 4) float32 table of d3r_scene_gallery, built in fp64: rows 0-255 = rgb() of jet's colours -- x * 0.5 + 0.5, clipped; the
+    reference sends the looked-up float colours through rgb(), which washes them out --, row 256 the same of the "bad" colour (0, 0, 0, 0)."""
+    lut = np.concatenate([jet_lut(), np.zeros((1, 4))])
+    return np.float32((lut * 0.5 + 0.5).clip(min=0, max=1))
+
+
+_table_cache = {}
+
+
+def _device_table(device):
+    key = (device.type, device.index)
+    if key not in _table_cache:
+        _table_cache[key] = torch.from_numpy(gallery_table()).to(device)      # uploaded once per device
+    return _table_cache[key]
+
+
+def _padded_rows(maps, device, copy=False):
+    """The maps of a scene (a list of (H, W) tensors) as rows of one (n, row) fp32 device tensor, row % 4 == 0: the stack they are views of
+    when they are -- a scene keeps its depth and confidence maps as slices of padded (n, max_area) stacks --, else (or with copy) a
+    zero-padded copy with the shortest such row."""
+    n = len(maps)
+    areas = [int(m.numel()) for m in maps]
+    t0 = maps[0]
+    row = maps[1].storage_offset() - t0.storage_offset() if n > 1 else -(-areas[0] // 4) * 4
+    if (not copy and row > 0 and row % 4 == 0 and row >= max(areas) and t0.data_ptr() % 16 == 0
+            and all(m.dtype == torch.float32 and m.device == device and m.is_contiguous() and not m.requires_grad
+                    and m.untyped_storage().data_ptr() == t0.untyped_storage().data_ptr() and m.storage_offset() == t0.storage_offset() + i * row
+                    for i, m in enumerate(maps))
+            and (t0.storage_offset() + n * row) * 4 <= t0.untyped_storage().nbytes()):
+        return torch.as_strided(t0, (n, row), (row, 1), t0.storage_offset())
+    row = -(-max(areas) // 4) * 4
+    out = torch.zeros((n, row), dtype=torch.float32, device=device)
+    for i, m in enumerate(maps):
+        out[i, :areas[i]] = m.detach().to(device=device, dtype=torch.float32).reshape(-1)
+    return out
+
+
+@torch.no_grad()
+def gallery_images(depth, conf, npix):
+    """d3r_scene_gallery on padded stacks: depth, conf (n, row) fp32 device tensors (row % 4 == 0), npix (n,) int32 device tensor of pixel
+    counts. Returns device tensors: depth_img (n, row), conf_img (n, row, 4) -- what lies behind an image's count is left unwritten -- and
+    maxima (2,) = (depth maximum, confidence maximum) over all valid pixels. No synchronisation."""
+    _lib.require_device()
+    n, row = depth.shape
+    device = depth.device
+    depth_img = torch.empty((n, row), dtype=torch.float32, device=device)
+    conf_img = torch.empty((n, row, 4), dtype=torch.float32, device=device)
+    maxima = torch.empty((2,), dtype=torch.float32, device=device)
+    work = torch.empty(max(1, int(_lib.lib.d3r_scene_gallery_workspace_bytes(n, row))), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib.d3r_scene_gallery(n, _lib.ptr(depth), _lib.ptr(conf), _lib.ptr(npix), row, _lib.ptr(_device_table(device)), _lib.ptr(depth_img),
+                                              _lib.ptr(conf_img), _lib.ptr(maxima), _lib.ptr(work), _lib.current_stream()), 'scene_gallery')
+    return depth_img, conf_img, maxima
+
+
+@torch.no_grad()
+def scene_gallery(scene):
+    """The `imgs` that the reference's get_reconstructed_scene returns (dust3r/demo.py:168-184): [rgb_0, depth_0, conf_0, rgb_1, ...] with
+    rgb_i = scene.imgs[i], depth_i = rgb(depth / max over all images) as (H, W) float32 and conf_i = rgb(jet(conf / max over all images)) as
+    (H, W, 4) -- float32 where the reference returns float64: the values are np.float32 of the reference's. All images in one GPU call.
+    (A NaN in any map makes the maximum NaN, as numpy.max does; the reference's python max() over the per-image maxima keeps a NaN only
+    when the first image has it.)"""
+    if scene.imgs is None:
+        raise ValueError('scene_gallery needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
+    depths, confs = list(scene.get_depthmaps()), list(scene.im_conf)
+    device = confs[0].device
+    if device.type != 'cuda':
+        raise _lib.D3RError('scene_gallery runs on the GPU (dust3r_amd has no CPU execution path)')
+    shapes = [tuple(c.shape) for c in confs]
+    depth, conf = _padded_rows(depths, device), _padded_rows(confs, device)
+    if depth.shape != conf.shape:          # stacks of different row lengths: both are copied to the shortest
+        depth, conf = _padded_rows(depths, device, copy=True), _padded_rows(confs, device, copy=True)
+    npix = torch.tensor([h * w for h, w in shapes], dtype=torch.int32).to(device)
+    depth_img, conf_img, _ = gallery_images(depth, conf, npix)
+    host_d, host_c = host_tensor(depth_img.shape), host_tensor(conf_img.shape)
+    host_d.copy_(depth_img)
+    host_c.copy_(conf_img)
+    host_d, host_c = host_d.numpy(), host_c.numpy()
+    imgs = []
+    for i, (h, w) in enumerate(shapes):
+        imgs.append(scene.imgs[i])
+        imgs.append(host_d[i, :h * w].reshape(h, w))
+        imgs.append(host_c[i, :h * w].reshape(h, w, 4))
+    return imgs
+
+
+# ---- the reconstruction ---------------------------------------------------------------------------------------------------------------
+def get_reconstructed_scene(outdir, model, device, silent, image_size, filelist, schedule, niter, min_conf_thr,
+                            as_pointcloud, mask_sky, clean_depth, transparent_cams, cam_size,
+                            scenegraph_type, winsize, refid):
+    """
+    from a list of images, run dust3r inference, global aligner.
+    then run get_3D_model_from_scene
+    """
+    try:
+        square_ok = model.square_ok
+    except Exception:
+        square_ok = False
+    imgs = load_images(filelist, size=image_size, verbose=not silent, patch_size=model.patch_size, square_ok=square_ok)
+    if len(imgs) == 1:
+        imgs = [imgs[0], copy.deepcopy(imgs[0])]
+        imgs[1]['idx'] = 1
+    if scenegraph_type == 'swin':
+        scenegraph_type = scenegraph_type + '-' + str(winsize)
+    elif scenegraph_type == 'oneref':
+        scenegraph_type = scenegraph_type + '-' + str(refid)
+
+    pairs = make_pairs(imgs, scene_graph=scenegraph_type, prefilter=None, symmetrize=True)
+    output = inference(pairs, model, device, batch_size=1, verbose=not silent)
+
+    mode = GlobalAlignerMode.PointCloudOptimizer if len(imgs) > 2 else GlobalAlignerMode.PairViewer
+    scene = global_aligner(output, device=device, mode=mode, verbose=not silent)
+    lr = 0.01
+
+    if mode == GlobalAlignerMode.PointCloudOptimizer:
+        scene.compute_global_alignment(init='mst', niter=niter, schedule=schedule, lr=lr)
+
+    outfile = get_3D_model_from_scene(outdir, silent, scene, min_conf_thr, as_pointcloud, mask_sky,
+                                      clean_depth, transparent_cams, cam_size)
+
+    # also return rgb, depth and confidence imgs: depth normalized with the max value for all images, jet on the confidence maps
+    return scene, outfile, scene_gallery(scene)
+
+
+def scenegraph_options(num_files, winsize, refid, scenegraph_type):
+    """The rule of the reference's set_scenegraph_options (dust3r/demo.py:189-207) as data: ((value, minimum, maximum, visible) of the
+    window-size control, the same of the reference-id control) for num_files input files (None: no input yet, counted as one). Like the
+    reference, the incoming winsize / refid do not enter: every change resets the controls."""
+    num_files = num_files if num_files is not None else 1
+    max_winsize = max(1, math.ceil((num_files - 1) / 2))
+    return ((max_winsize, 1, max_winsize, scenegraph_type == 'swin'), (0, 0, num_files - 1, scenegraph_type == 'oneref'))
+
+
+# ---- the command line -------------------------------------------------------------------------------------------------------------------
+def get_args_parser():
+    parser = argparse.ArgumentParser(prog='python -m dust3r_amd.demo', description='pictures -> scene.glb, the rgb / depth / confidence gallery, cameras.json')
+    parser.add_argument('images', nargs='+', help='image files, or one folder of them')
+    parser.add_argument('--outdir', type=str, default='.', help='where scene.glb, gallery/ and cameras.json go')
+    parser.add_argument('--image_size', type=int, default=512, choices=[512, 224], help='image size')
+    parser_weights = parser.add_mutually_exclusive_group(required=True)
+    parser_weights.add_argument('--weights', type=str, help='path to the model weights', default=None)
+    parser_weights.add_argument('--model_name', type=str, help='a snapshot directory of the model weights (config.json + model.safetensors), for from_pretrained')
+    parser.add_argument('--device', type=str, default='cuda', help='pytorch device')
+    parser.add_argument('--silent', action='store_true', default=False, help='silence logs')
+    parser.add_argument('--schedule', type=str, default='linear', choices=['linear', 'cosine'], help='learning-rate schedule of the global alignment')
+    parser.add_argument('--niter', type=int, default=300, help='iterations of the global alignment')
+    parser.add_argument('--min_conf_thr', type=float, default=3.0)
+    parser.add_argument('--cam_size', type=float, default=0.05, help='size of the cameras in the exported scene')
+    parser.add_argument('--scenegraph_type', type=str, default='complete', choices=['complete', 'swin', 'oneref'], help='how pairs are made')
+    parser.add_argument('--winsize', type=int, default=None, help='swin: window size (default: the largest; clamped to the valid range)')
+    parser.add_argument('--refid', type=int, default=None, help='oneref: the reference image (default 0; clamped to the valid range)')
+    parser.add_argument('--as_pointcloud', action='store_true', default=False)
+    parser.add_argument('--mask_sky', action='store_true', default=False)
+    parser.add_argument('--clean_depth', action=argparse.BooleanOptionalAction, default=True, help='clean-up depthmaps')
+    parser.add_argument('--transparent_cams', action='store_true', default=False)
+    parser.add_argument('--turntable', type=int, default=0, metavar='N', help='also render N turntable frames into outdir/turntable')
+    return parser
+
+
+def clamp_scenegraph(num_files, winsize, refid, scenegraph_type):
+    """--winsize / --refid as the page's sliders would hold them: the control's default when not given, else clamped to its range."""
+    (w_value, w_min, w_max, _), (r_value, r_min, r_max, _) = scenegraph_options(num_files, winsize, refid, scenegraph_type)
+    winsize = w_value if winsize is None else min(max(int(winsize), w_min), w_max)
+    refid = r_value if refid is None else min(max(int(refid), r_min), r_max)
+    return winsize, refid
+
+
+def _input_files(images):
+    if len(images) == 1 and os.path.isdir(images[0]):
+        root = images[0]
+        return [os.path.join(root, name) for name in sorted(os.listdir(root)) if name.lower().endswith(IMAGE_EXTENSIONS)]
+    return list(images)
+
+
+def write_gallery(outdir, imgs):
+    """gallery/view{k}_{rgb,depth,conf}.png of the `imgs` of get_reconstructed_scene; returns the file names."""
+    os.makedirs(os.path.join(outdir, 'gallery'), exist_ok=True)
+    names = [os.path.join(outdir, 'gallery', f'view{k // 3}_{("rgb", "depth", "conf")[k % 3]}.png') for k in range(len(imgs))]
+
+    def write(k):
+        with open(names[k], 'wb') as f:
+            f.write(_png(imgs[k]))
+    with ThreadPoolExecutor(max(1, min(usable_cpus(), len(imgs)))) as ex:
+        list(ex.map(write, range(len(imgs))))
+    return names
+
+
+def write_cameras(outdir, scene):
+    """cameras.json: per image its cam2world matrix, focal(s) and (width, height)."""
+    with torch.no_grad():
+        cams2world = scene.get_im_poses().cpu().numpy()
+        focals = scene.get_focals().cpu().numpy().reshape(len(cams2world), -1)
+    name = os.path.join(outdir, 'cameras.json')
+    with open(name, 'w') as f:
+        json.dump(dict(cam2world=[m.tolist() for m in cams2world], focals=[[float(v) for v in row] for row in focals],
+                       image_sizes=[[int(w), int(h)] for w, h in scene.imsizes]), f, indent=1)
+    return name
+
+
+def main(argv=None):
+    from .model import AsymmetricCroCo3DStereo
+    args = get_args_parser().parse_args(argv)
+    files = _input_files(args.images)
+    if not files:
+        raise SystemExit(f'no image in {args.images}')
+    winsize, refid = clamp_scenegraph(len(files), args.winsize, args.refid, args.scenegraph_type)
+    model = AsymmetricCroCo3DStereo.from_pretrained(args.weights if args.weights is not None else args.model_name).to(args.device)
+    os.makedirs(args.outdir, exist_ok=True)
+    scene, outfile, imgs = get_reconstructed_scene(args.outdir, model, args.device, args.silent, args.image_size, files, args.schedule, args.niter,
+                                                   args.min_conf_thr, args.as_pointcloud, args.mask_sky, args.clean_depth, args.transparent_cams,
+                                                   args.cam_size, args.scenegraph_type, winsize, refid)
+    written = [outfile, write_cameras(args.outdir, scene)] + write_gallery(args.outdir, imgs)
+    if args.turntable > 0:
+        written += render_turntable(os.path.join(args.outdir, 'turntable'), scene, n_frames=args.turntable, min_conf_thr=args.min_conf_thr,
+                                    mask_sky=args.mask_sky, clean_depth=args.clean_depth, transparent_cams=args.transparent_cams, silent=args.silent)
+    if not args.silent:
+        print('(wrote', len(written), 'files to', args.outdir, ')')
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

@@ -349,6 +349,29 @@ int d3r_scene_mesh(int n_views, const float* pts, const uint8_t* mask, const voi
                    int max_area, int as_pointcloud, uint32_t* faces_out, float* points_out, uint32_t* colors_out, long long* counts_out,
                    float* bounds_out, void* workspace, void* stream);
 
+/* The depth / confidence gallery of the demo (the end of get_reconstructed_scene, dust3r/demo.py:168-184) for n images in one call.
+ * depth, conf [n][max_area] DEVICE fp32 (a scene's padded stacks), npix_dev [n] DEVICE int: the pixel count of each image (a count that is
+ * negative or above max_area makes its image empty); what lies behind a count is neither read into a result nor written. table [257][4]
+ * DEVICE fp32: row k < 256 = float32(lut[k] * 0.5 + 0.5) of the colour map's RGBA table (rgb()'s affine map applied to the looked-up
+ * colour), row 256 the same of the "bad" colour.
+ *   maxima_out [2] DEVICE fp32 = (dmax, cmax): the maxima of the valid depth and confidence pixels of all images; a NaN propagates
+ *     (numpy.max); -inf when no pixel is valid.
+ *   depth_img [n][max_area] fp32 = clip((d / dmax) * 0.5 + 0.5, 0, 1): IEEE division, product and sum rounded separately, NaN kept.
+ *   conf_img [n][max_area][4] fp32 = table[index(c / cmax)], index = matplotlib's Colormap.__call__ on a float: NaN -> 256; x = r * 256
+ *     in fp32; x < 0 -> 0; x >= 256 -> 255; else x truncated towards zero.
+ * Alignment contract: max_area is a multiple of 4 and depth, conf, table, depth_img and conf_img are 16-byte aligned (every group of
+ * four pixels is one 16-byte access); n * max_area / 4 <= 2^31 - 1. D3R_ERR_INVALID otherwise, and on NULL or non-positive arguments.
+ * workspace: d3r_scene_gallery_workspace_bytes(n, max_area) bytes of DEVICE memory (block partials; 0 for invalid shapes). Two launches on
+ * `stream`, no float atomics: the same bytes on every run. No allocation, no synchronisation.
+ * d3r_scene_gallery_launch_bound: the grid cap, the workgroup size and the pixels per thread and trip -- their product is the number of
+ * pixels one trip of the grid-stride loop covers. */
+size_t d3r_scene_gallery_workspace_bytes(int n_imgs, int max_area);
+int d3r_scene_gallery(int n_imgs, const float* depth, const float* conf, const int* npix_dev, int max_area, const float* table, float* depth_img,
+                      float* conf_img, float* maxima_out, void* workspace, void* stream);
+void d3r_scene_gallery_launch_bound(int* max_blocks, int* threads, int* pixels_per_thread);
+/* Host-only self test of the index rule above (csrc/gallery_math.hpp, the function the kernel calls): index_out[i] = index(ratios[i]). */
+int d3r_selftest_gallery_index_host(const float* ratios, int n, int* index_out);
+
 /* ---- headless rendering (csrc/render.hip): what scene.show(), scene.render_views() and demo.render_turntable draw with ------------ */
 
 /* A z-buffered software rasteriser for points and triangles, n_cams cameras in one call (the reference's show() opens a trimesh / pyglet
