@@ -21,18 +21,11 @@ import tqdm
 from .. import _lib
 from .._lib import check, current_stream, lib, ptr
 from ..utils.geometry import geotrf, inv, xy_grid
+from ..utils.padded import pad_views, shape_tables, split_views, zero_padding_
 from ..utils.rigid import quat_translation_to_homogeneous, rotmat_to_unitquat
 from . import init_im_poses as init_fun
 from .commons import (cosine_schedule, edge_str, get_conf_trf, get_imshapes, linear_schedule, signed_expm1,
                       signed_log1p)
-
-
-def _ravel_hw(tensor, fill=0):
-    """(H, W, ...) -> (H*W, ...) zero padded to `fill` rows (reference optimizer.py:231-237)."""
-    tensor = tensor.reshape((tensor.shape[0] * tensor.shape[1],) + tuple(tensor.shape[2:]))
-    if len(tensor) < fill:
-        tensor = torch.cat((tensor, tensor.new_zeros((fill - len(tensor),) + tuple(tensor.shape[1:]))))
-    return tensor
 
 
 class _EdgeView:
@@ -99,7 +92,8 @@ class BasePCOptimizer(nn.Module):
         def stack(seq):
             if isinstance(seq, torch.Tensor) and seq.shape[1] * seq.shape[2] == self.max_area:
                 return seq.detach().float().reshape((seq.shape[0], self.max_area) + tuple(seq.shape[3:])).contiguous()
-            return torch.stack([_ravel_hw(torch.as_tensor(p).detach().float(), self.max_area) for p in seq]).contiguous()
+            first = torch.as_tensor(seq[0])
+            return pad_views(seq, first.device, torch.float32, tail=first.shape[2:], row=self.max_area)
 
         self.register_buffer('_stacked_pred_i', stack(pred1_pts))
         self.register_buffer('_stacked_pred_j', stack(pred2_pts))
@@ -111,16 +105,13 @@ class BasePCOptimizer(nn.Module):
         self.min_conf_thr = min_conf_thr
         self.conf_mode = conf
         self.conf_trf = get_conf_trf(conf)
-        self.im_conf = self._compute_img_conf()
+        self.register_buffer('_im_conf', torch.zeros((self.n_imgs, self.max_area), dtype=torch.float32, device=self._conf_i.device))
+        self._compute_img_conf()
 
         # pre-computed pixel weights (zero in the padding, like ParameterStack(fill=max_area))
         def weights(c, side):
             w = self.conf_trf(c.clamp_min(1e-30)) if conf == 'log' else self.conf_trf(c)
-            for e, (i, j) in enumerate(self.edges):
-                a = im_areas[i if side == 0 else j]
-                if a < self.max_area:
-                    w[e, a:] = 0
-            return w.contiguous()
+            return zero_padding_(w, [im_areas[edge[side]] for edge in self.edges]).contiguous()
         self.register_buffer('_weight_i', weights(self._conf_i.clone(), 0))
         self.register_buffer('_weight_j', weights(self._conf_j.clone(), 1))
 
@@ -142,6 +133,7 @@ class BasePCOptimizer(nn.Module):
                 imgs[view2['idx'][v]] = view2['img'][v]
             self.imgs = rgb(imgs)
         self._grid_cache = None        # (n, max_area, 2) pixel grid of depth_to_pts3d, built on first use on the scene's device
+        self._tables_cache = None      # (heights, widths, npix) int32 on the scene's device, likewise
         self._engine = None
         self._engine_sig = None
 
@@ -170,14 +162,25 @@ class BasePCOptimizer(nn.Module):
     @torch.no_grad()
     def _compute_img_conf(self):
         """Per image, the pixel-wise maximum of the confidences of every edge side that shows it (base_opt.py:116-123 of the reference):
-        two scatter-max passes over the stacked (E, max_area) confidences instead of 2 E small launches."""
+        two scatter-max passes over the stacked (E, max_area) confidences instead of 2 E small launches, into the `_im_conf` stack."""
         dev = self._conf_i.device
-        acc = torch.zeros((self.n_imgs, self.max_area), dtype=torch.float32, device=dev)
         ei = torch.tensor([i for i, j in self.edges], device=dev)
         ej = torch.tensor([j for i, j in self.edges], device=dev)
-        acc.index_reduce_(0, ei, self._conf_i, 'amax', include_self=True)
-        acc.index_reduce_(0, ej, self._conf_j, 'amax', include_self=True)
-        return [acc[i, :h * w].view(h, w) for i, (h, w) in enumerate(self.imshapes)]
+        self._im_conf.zero_()
+        self._im_conf.index_reduce_(0, ei, self._conf_i, 'amax', include_self=True)
+        self._im_conf.index_reduce_(0, ej, self._conf_j, 'amax', include_self=True)
+
+    @property
+    def im_conf(self):
+        """The reference's list of (H, W) confidence maps: views of the `_im_conf` stack, so `scene.im_conf[i][...] = x` writes to the scene."""
+        return split_views(self._im_conf, self.imshapes)
+
+    @im_conf.setter
+    @torch.no_grad()
+    def im_conf(self, maps):
+        """`scene.im_conf = maps` copies the maps into the scene's stack (it does not keep the caller's tensors)."""
+        for dst, src in zip(self.im_conf, maps, strict=True):
+            dst.copy_(torch.as_tensor(src))
 
     _TRAINABLE_KEYS = ('pw_poses', 'pw_adaptors', 'im_depthmaps', 'im_poses', 'im_focals', 'im_pp')
 
@@ -199,9 +202,7 @@ class BasePCOptimizer(nn.Module):
 
     def to(self, device, *a, **k):
         self._destroy_engine()
-        super().to(device, *a, **k)
-        self.im_conf = [c.to(device) for c in self.im_conf]
-        return self
+        return super().to(device, *a, **k)
 
     # ------------------------------------------------------------------ parameter access (cam-to-world)
     def get_adaptors(self):
@@ -245,8 +246,9 @@ class BasePCOptimizer(nn.Module):
         scaled[:, :3] *= self.get_pw_scale().view(-1, 1, 1)
         return scaled
 
-    def get_masks(self):
-        return [(conf > self.min_conf_thr) for conf in self.im_conf]
+    def get_masks(self, raw=False):
+        masks = self._im_conf > self.min_conf_thr           # raw (new): the padded (n, max_area) stack the (H, W) masks are views of
+        return masks if raw else split_views(masks, self.imshapes)
 
     def get_conf(self, mode=None):
         trf = self.conf_trf if mode is None else get_conf_trf(mode)
@@ -254,9 +256,7 @@ class BasePCOptimizer(nn.Module):
 
     def get_pts3d(self, raw=False):
         res = self.depth_to_pts3d()
-        if not raw:
-            res = [dm[:h * w].view(h, w, 3) for dm, (h, w) in zip(res, self.imshapes)]
-        return res
+        return res if raw else split_views(res, self.imshapes)
 
     # ------------------------------------------------------------------ image parameters
     # A scene with image parameters keeps them in flat storage -- `_flat_im_poses` (n, 7), `_flat_im_depthmaps` (n, max_area) log-depth, zero in the
@@ -297,18 +297,23 @@ class BasePCOptimizer(nn.Module):
 
     def get_depthmaps(self, raw=False):
         res = self._flat_im_depthmaps.exp()
-        if not raw:
-            res = [dm[:h * w].view(h, w) for dm, (h, w) in zip(res, self.imshapes)]
-        return res
+        return res if raw else split_views(res, self.imshapes)
 
     @property
     def _grid(self):
         g = self._grid_cache
         if g is None or g.device != self.device:
             dev = self.device
-            per_shape = {hw: _ravel_hw(xy_grid(hw[1], hw[0], device=dev).float(), self.max_area) for hw in set(self.imshapes)}
-            g = self._grid_cache = torch.stack([per_shape[hw] for hw in self.imshapes])
+            per_shape = {hw: xy_grid(hw[1], hw[0], device=dev) for hw in set(self.imshapes)}
+            g = self._grid_cache = pad_views([per_shape[hw] for hw in self.imshapes], dev, torch.float32, tail=(2,), row=self.max_area)
         return g
+
+    @property
+    def _shape_tables(self):
+        """(heights, widths, npix): the int32 tables the batched kernels take beside a stack, on the scene's device."""
+        if self._tables_cache is None or self._tables_cache[0].device != self.device:
+            self._tables_cache = shape_tables(self.imshapes, self.device)
+        return self._tables_cache
 
     def depth_to_pts3d(self):
         focals = self.get_focals().unsqueeze(1)                 # (n,1,1 | 2): x = d (u - cx) / fx, y = d (v - cy) / fy
@@ -321,11 +326,9 @@ class BasePCOptimizer(nn.Module):
     def clean_pointcloud(self, **kw):
         if self.device.type != 'cuda':
             raise _lib.D3RError('clean_pointcloud runs on the GPU (dust3r_amd has no CPU execution path)')
-        cams = inv(self.get_im_poses())
-        new_confs = clean_pointcloud_hip(self.im_conf, self.get_intrinsics(), cams, self.get_depthmaps(), self.get_pts3d(),
-                                         tol=kw.get('tol', 0.001), bad_conf=kw.get('bad_conf', 0))
-        for i, c in enumerate(new_confs):
-            self.im_conf[i][:] = c
+        heights, widths, _ = self._shape_tables
+        _clean_stacks(self._im_conf, self.get_depthmaps(raw=True), self.get_pts3d(raw=True), self.get_intrinsics(), inv(self.get_im_poses()),
+                      heights, widths, tol=kw.get('tol', 0.001), bad_conf=kw.get('bad_conf', 0))
         return self
 
     @torch.no_grad()
@@ -391,14 +394,12 @@ class BasePCOptimizer(nn.Module):
             raise _lib.D3RError('render_views renders on the GPU (dust3r_amd has no CPU execution path)')
         from ..viz import SceneViz, scene_mesh_batch
         viz = SceneViz(self.device)
-        masks = self.get_masks()
         if as_mesh:
-            pts3d = self.get_pts3d(raw=True)
-            geo = scene_mesh_batch(self.imgs, pts3d if isinstance(pts3d, torch.Tensor) else self.get_pts3d(), masks, self.device, to_host=False)
+            geo = scene_mesh_batch(self.imgs, self.get_pts3d(raw=True), self.get_masks(raw=True), self.device, to_host=False)
             if len(geo['faces']):
                 viz.add_mesh(geo['positions'], geo['faces'], geo['colors'])
         else:
-            viz.add_pointcloud(list(self.get_pts3d()), list(self.imgs), list(masks))
+            viz.add_pointcloud(list(self.get_pts3d()), list(self.imgs), list(self.get_masks()))
         poses, K = self.get_im_poses().detach(), self.get_intrinsics().detach()
         out = [None] * self.n_imgs
         if viz.bounds() is None:
@@ -466,8 +467,8 @@ class BasePCOptimizer(nn.Module):
             self._engine = None
 
     def __deepcopy__(self, memo):
-        """Every tensor is copied (views of one storage stay views of one new storage); the copy has no engine and builds its own on first use:
-        the engine handle is a native pointer into this scene's tensors."""
+        """Every tensor is copied; the copy has no engine and builds its own on first use: the engine handle is a native pointer into this
+        scene's tensors."""
         res = type(self).__new__(type(self))
         memo[id(self)] = res
         for k, v in self.__dict__.items():
@@ -657,30 +658,31 @@ def _device_view(address, numel, dtype, device):
 
 
 @torch.no_grad()
+def _clean_stacks(conf, depth, pts3d, K, cams, heights, widths, tol=0.001, bad_conf=0):
+    """d3r_clean_pointcloud on padded stacks: conf (n, row) fp32, updated IN PLACE in the kernel's order (image i sees the cleaned confidences of
+    the images before it), depth (n, row), pts3d (n, row, 3), K (n, 3, 3), cams (n, 4, 4) world-to-camera, heights / widths (n,) int32."""
+    _lib.require_device()
+    n, row = conf.shape
+    depth, pts3d = depth.detach().float().contiguous(), pts3d.detach().float().contiguous()
+    assert conf.is_cuda and conf.is_contiguous() and conf.dtype == torch.float32 and depth.shape == (n, row) and pts3d.shape == (n, row, 3)
+    Kc = K.float().contiguous().reshape(n, 9)
+    w2c = cams.float().contiguous().reshape(n, 16)
+    with torch.cuda.device(conf.device):
+        check(lib.d3r_clean_pointcloud(n, ptr(conf), ptr(depth), ptr(pts3d), ptr(Kc), ptr(w2c), ptr(heights), ptr(widths), row, float(tol),
+                                       float(bad_conf), current_stream()), 'clean_pointcloud')
+
+
+@torch.no_grad()
 def clean_pointcloud_hip(im_confs, K, cams, depthmaps, all_pts3d, tol=0.001, bad_conf=0):
     """The reference's `clean_pointcloud` (base_opt.py:369-405: a point of image i that projects IN FRONT of image j's depthmap while
     being less confident than the pixel it lands on gets its confidence clipped to `bad_conf`; images visited in order, each seeing
     the already cleaned confidences of the earlier ones), computed by d3r_clean_pointcloud: n launches, one thread per pixel walking
-    the other cameras, instead of n (n - 1) rounds of ~15 elementwise torch kernels."""
-    _lib.require_device()
-    n = len(im_confs)
+    the other cameras, instead of n (n - 1) rounds of ~15 elementwise torch kernels. This is the list front end (the new confidences are
+    returned, the inputs left alone); a scene runs the same call on its own stacks."""
     dev = im_confs[0].device
     shapes = [tuple(c.shape) for c in im_confs]
-    maxA = max(h * w for h, w in shapes)
-
-    def stack(ts, tail=()):
-        out = torch.zeros((n, maxA) + tail, dtype=torch.float32, device=dev)
-        for i, t in enumerate(ts):
-            out[i, :t.numel() // max(1, int(np.prod(tail)))] = t.reshape((-1,) + tail).float()
-        return out
-    conf = stack(im_confs)
-    depth = stack(depthmaps)
-    pts = stack(all_pts3d, (3,))
-    Kc = K.float().contiguous().reshape(n, 9)
-    w2c = cams.float().contiguous().reshape(n, 16)
-    hs = torch.tensor([h for h, w in shapes], dtype=torch.int32).to(dev)
-    ws = torch.tensor([w for h, w in shapes], dtype=torch.int32).to(dev)
-    with torch.cuda.device(dev):
-        check(lib.d3r_clean_pointcloud(n, ptr(conf), ptr(depth), ptr(pts), ptr(Kc), ptr(w2c), ptr(hs), ptr(ws), maxA, float(tol), float(bad_conf),
-                                       current_stream()), 'clean_pointcloud')
-    return [conf[i, :h * w].view(h, w).to(im_confs[i].dtype) for i, (h, w) in enumerate(shapes)]
+    conf = pad_views(im_confs, dev, torch.float32, name='clean_pointcloud: confidence map')
+    depth = pad_views(depthmaps, dev, torch.float32, shapes=shapes, name='clean_pointcloud: depth map')
+    pts = pad_views(all_pts3d, dev, torch.float32, tail=(3,), shapes=shapes, name='clean_pointcloud: pointmap')
+    _clean_stacks(conf, depth, pts, K, cams, *shape_tables(shapes, dev)[:2], tol=tol, bad_conf=bad_conf)
+    return [c.to(im_confs[i].dtype) for i, c in enumerate(split_views(conf, shapes))]

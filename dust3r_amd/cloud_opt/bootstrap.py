@@ -477,13 +477,14 @@ def bootstrap_from_spanning_tree(scene, niter_PnP=10, maps=None):
         need = [k for k in range(n) if poses[k] is None]
         if need:
             pjobs, owner = [], []
-            confident = torch.stack([(scene.im_conf[k] > scene.min_conf_thr).sum() for k in need]).cpu().tolist()      # one copy back for all images
+            im_conf = scene.im_conf
+            confident = torch.stack([(im_conf[k] > scene.min_conf_thr).sum() for k in need]).cpu().tolist()      # one copy back for all images
             for k, n_conf in zip(need, confident):
                 side, e = plan.anchor[k]
                 H, W = scene.imshapes[k]
                 if n_conf < 4:
                     continue
-                conf_t = scene.im_conf[k].contiguous()
+                conf_t = im_conf[k].contiguous()
                 sweep = [focals[k]] if focals[k] is not None else list(np.geomspace(max(W, H) / 2, max(W, H) * 3, 21))
                 for f in sweep:
                     pjobs.append(dict(map=maps.map_addr(side, e), conf=conf_t.data_ptr(), G=G[k][:3], f=f, pp=(W / 2, H / 2), thr=scene.min_conf_thr,

@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..utils.device import to_numpy
+from ..utils.padded import pad_views, split_views
 from .base_opt import BasePCOptimizer
 
 _ENTRIES = ('im_poses', 'im_depthmaps', 'im_focals', 'im_pp')
@@ -43,9 +44,7 @@ class ModularPointCloudOptimizer(BasePCOptimizer):
         self.fx_and_fy = bool(fx_and_fy)
         n = self.n_imgs
         # the reference's initial distributions, drawn in its order (modular_optimizer.py:29-35): one randn(H, W) per image, then the poses
-        depth = torch.zeros((n, self.max_area))
-        for k, (H, W) in enumerate(self.imshapes):
-            depth[k, :H * W] = (torch.randn(H, W) / 10 - 3).reshape(-1)
+        depth = pad_views([torch.randn(H, W) / 10 - 3 for H, W in self.imshapes], 'cpu', torch.float32, row=self.max_area)
         poses = torch.stack([self.rand_pose(self.POSE_DIM) for _ in range(n)]).float()
         focals = torch.tensor([[self.focal_brake * np.log(max(H, W))] * (2 if self.fx_and_fy else 1) for H, W in self.imshapes], dtype=torch.float32)
         self.register_buffer('_flat_im_depthmaps', depth)
@@ -64,10 +63,7 @@ class ModularPointCloudOptimizer(BasePCOptimizer):
                 old = getattr(self, name, None)
                 flags[name] = [p.requires_grad for p in old] if old is not None else [True] * self.n_imgs
             flat = getattr(self, '_flat_' + name)
-            if name == 'im_depthmaps':
-                rows = [flat[k, :H * W].view(H, W) for k, (H, W) in enumerate(self.imshapes)]
-            else:
-                rows = [flat[k] for k in range(self.n_imgs)]
+            rows = split_views(flat, self.imshapes) if name == 'im_depthmaps' else [flat[k] for k in range(self.n_imgs)]
             object.__setattr__(self, name, ParamEntries(nn.Parameter(r, requires_grad=f) for r, f in zip(rows, flags[name])))
 
     @property

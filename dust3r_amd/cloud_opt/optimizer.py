@@ -12,7 +12,8 @@ import torch.nn as nn
 
 from .. import _lib
 from ..utils.device import to_numpy
-from .base_opt import BasePCOptimizer, _ravel_hw
+from ..utils.padded import pad_views
+from .base_opt import BasePCOptimizer
 
 
 class PointCloudOptimizer(BasePCOptimizer):
@@ -91,10 +92,10 @@ class PointCloudOptimizer(BasePCOptimizer):
         return self.im_pp[idx]
 
     def _set_depthmap(self, idx, depth, force=False):
-        depth = _ravel_hw(depth, self.max_area)
         if self.im_depthmaps.requires_grad or force:
             with torch.no_grad():
-                self.im_depthmaps.data[idx] = depth.log().nan_to_num(neginf=0).to(self.im_depthmaps.device)
+                row = pad_views([depth], depth.device, depth.dtype, row=self.max_area)[0]
+                self.im_depthmaps.data[idx] = row.log().nan_to_num(neginf=0).to(self.im_depthmaps.device)     # zero in the padding
         return self.im_depthmaps[idx]
 
     # ------------------------------------------------------------------ getters (optimizer.py:127-186) and engine binding: BasePCOptimizer's,

@@ -6,6 +6,7 @@ depth maps in one launch. Solved lazily on first use, once the scene sits on its
 import numpy as np
 import torch
 
+from ..utils.padded import pad_views, split_views
 from .base_opt import BasePCOptimizer
 from .bootstrap import PairMaps
 
@@ -57,7 +58,7 @@ class PairViewer(BasePCOptimizer):
             im_poses=torch.tensor(np.stack(poses), dtype=torch.float32, device=dev),
             focals=torch.tensor(np.asarray(focals), dtype=torch.float32, device=dev),
             pp=torch.tensor([(w / 2, h / 2) for h, w in self.imshapes], dtype=torch.float32, device=dev),
-            depth=[depth[i, :h * w].view(h, w) for i, (h, w) in enumerate(self.imshapes)])
+            depth=depth)                                          # the padded (2, max_area) stack; the padding is never written
         return self._solution
 
     def to(self, device, *a, **k):
@@ -73,7 +74,8 @@ class PairViewer(BasePCOptimizer):
             print('_set_depthmap is ignored in PairViewer')
 
     def get_depthmaps(self, raw=False):
-        return list(self._solved()['depth'])
+        depth = self._solved()['depth']
+        return depth if raw else split_views(depth, self.imshapes)
 
     def _set_focal(self, idx, focal, force=False):
         self._solved()['focals'][idx] = focal
@@ -102,8 +104,8 @@ class PairViewer(BasePCOptimizer):
         """World points of both views from (depth, intrinsics, pose): X = pose . (d (u - ppx) / f, d (v - ppy) / f, d)."""
         s = self._solved()
         out = []
-        for i, (h, w) in enumerate(self.imshapes):
-            d = s['depth'][i]
+        for i, d in enumerate(self.get_depthmaps()):
+            h, w = d.shape
             v, u = torch.meshgrid(torch.arange(h, device=d.device, dtype=torch.float32), torch.arange(w, device=d.device, dtype=torch.float32),
                                   indexing='ij')
             f, (px, py) = s['focals'][i], s['pp'][i]
@@ -113,7 +115,8 @@ class PairViewer(BasePCOptimizer):
         return out
 
     def get_pts3d(self, raw=False):
-        return self.depth_to_pts3d()
+        pts = self.depth_to_pts3d()
+        return pad_views(pts, pts[0].device, torch.float32, tail=(3,), row=self.max_area) if raw else pts
 
     def compute_global_alignment(self, *a, **k):
         return float('nan')

@@ -144,10 +144,10 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
         rgbimg = scene.imgs
         focals = scene.get_focals().cpu()
         cams2world = scene.get_im_poses().cpu()
-        # 3D pointcloud from depthmap, poses and intrinsics: the device tensors go to the mesh kernels as they are
+        # 3D pointcloud from depthmap, poses and intrinsics: the scene's padded stacks go to the mesh kernels as they are
         pts3d = scene.get_pts3d(raw=True)
         scene.min_conf_thr = float(scene.conf_trf(torch.tensor(min_conf_thr)))
-        msk = scene.get_masks()
+        msk = scene.get_masks(raw=True)
     return _convert_scene_output_to_glb(outdir, rgbimg, pts3d, msk, focals, cams2world, as_pointcloud=as_pointcloud,
                                         transparent_cams=transparent_cams, cam_size=cam_size, silent=silent)
 
@@ -172,13 +172,11 @@ def render_turntable(outdir, scene, n_frames=36, size=(1024, 768), as_pointcloud
         focals = scene.get_focals().cpu().numpy().reshape(-1)
         cams2world = scene.get_im_poses().cpu().numpy()
         scene.min_conf_thr = float(scene.conf_trf(torch.tensor(min_conf_thr)))
-        msk = scene.get_masks()
         viz = SceneViz(scene.device)
         if as_pointcloud:
-            viz.add_pointcloud(list(scene.get_pts3d()), list(scene.imgs), list(msk))
+            viz.add_pointcloud(list(scene.get_pts3d()), list(scene.imgs), list(scene.get_masks()))
         else:
-            pts3d = scene.get_pts3d(raw=True)
-            geo = scene_mesh_batch(scene.imgs, pts3d if isinstance(pts3d, torch.Tensor) else scene.get_pts3d(), msk, scene.device, to_host=False)
+            geo = scene_mesh_batch(scene.imgs, scene.get_pts3d(raw=True), scene.get_masks(raw=True), scene.device, to_host=False)
             if len(geo['faces']):
                 viz.add_mesh(geo['positions'], geo['faces'], geo['colors'])
         bounds = viz.bounds()
@@ -244,27 +242,6 @@ def _device_table(device):
     return _table_cache[key]
 
 
-def _padded_rows(maps, device, copy=False):
-    """The maps of a scene (a list of (H, W) tensors) as rows of one (n, row) fp32 device tensor, row % 4 == 0: the stack they are views of
-    when they are -- a scene keeps its depth and confidence maps as slices of padded (n, max_area) stacks --, else (or with copy) a
-    zero-padded copy with the shortest such row."""
-    n = len(maps)
-    areas = [int(m.numel()) for m in maps]
-    t0 = maps[0]
-    row = maps[1].storage_offset() - t0.storage_offset() if n > 1 else -(-areas[0] // 4) * 4
-    if (not copy and row > 0 and row % 4 == 0 and row >= max(areas) and t0.data_ptr() % 16 == 0
-            and all(m.dtype == torch.float32 and m.device == device and m.is_contiguous() and not m.requires_grad
-                    and m.untyped_storage().data_ptr() == t0.untyped_storage().data_ptr() and m.storage_offset() == t0.storage_offset() + i * row
-                    for i, m in enumerate(maps))
-            and (t0.storage_offset() + n * row) * 4 <= t0.untyped_storage().nbytes()):
-        return torch.as_strided(t0, (n, row), (row, 1), t0.storage_offset())
-    row = -(-max(areas) // 4) * 4
-    out = torch.zeros((n, row), dtype=torch.float32, device=device)
-    for i, m in enumerate(maps):
-        out[i, :areas[i]] = m.detach().to(device=device, dtype=torch.float32).reshape(-1)
-    return out
-
-
 @torch.no_grad()
 def gallery_images(depth, conf, npix):
     """d3r_scene_gallery on padded stacks: depth, conf (n, row) fp32 device tensors (row % 4 == 0), npix (n,) int32 device tensor of pixel
@@ -292,22 +269,15 @@ def scene_gallery(scene):
     when the first image has it.)"""
     if scene.imgs is None:
         raise ValueError('scene_gallery needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
-    depths, confs = list(scene.get_depthmaps()), list(scene.im_conf)
-    device = confs[0].device
-    if device.type != 'cuda':
+    if scene.device.type != 'cuda':
         raise _lib.D3RError('scene_gallery runs on the GPU (dust3r_amd has no CPU execution path)')
-    shapes = [tuple(c.shape) for c in confs]
-    depth, conf = _padded_rows(depths, device), _padded_rows(confs, device)
-    if depth.shape != conf.shape:          # stacks of different row lengths: both are copied to the shortest
-        depth, conf = _padded_rows(depths, device, copy=True), _padded_rows(confs, device, copy=True)
-    npix = torch.tensor([h * w for h, w in shapes], dtype=torch.int32).to(device)
-    depth_img, conf_img, _ = gallery_images(depth, conf, npix)
+    depth_img, conf_img, _ = gallery_images(scene.get_depthmaps(raw=True), scene._im_conf, scene._shape_tables[2])
     host_d, host_c = host_tensor(depth_img.shape), host_tensor(conf_img.shape)
     host_d.copy_(depth_img)
     host_c.copy_(conf_img)
     host_d, host_c = host_d.numpy(), host_c.numpy()
     imgs = []
-    for i, (h, w) in enumerate(shapes):
+    for i, (h, w) in enumerate(scene.imshapes):
         imgs.append(scene.imgs[i])
         imgs.append(host_d[i, :h * w].reshape(h, w))
         imgs.append(host_c[i, :h * w].reshape(h, w, 4))

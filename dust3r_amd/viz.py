@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import check, current_stream, lib, ptr
+from .utils.padded import pad_views, shape_tables, split_views
 
 OPENGL = np.array([[1, 0, 0, 0],
                    [0, -1, 0, 0],
@@ -45,17 +46,14 @@ def segment_sky_batch(images, device):
         raise TypeError('segment_sky_batch: mix of uint8 and float32 images')
     device = torch.device(device)
     shapes = [a.shape[:2] for a in arrays]
-    n, max_area = len(arrays), max(h * w for h, w in shapes)
-    rgb = torch.zeros((n, max_area, 3), dtype=torch.uint8 if is_u8 else torch.float32, device=device)
-    for i, a in enumerate(arrays):
-        rgb[i, :a.shape[0] * a.shape[1]] = a.reshape(-1, 3)            # one copy: host -> device, or device -> device
-    hs = torch.tensor([h for h, w in shapes], dtype=torch.int32, device=device)
-    ws = torch.tensor([w for h, w in shapes], dtype=torch.int32, device=device)
+    rgb = pad_views(arrays, device, torch.uint8 if is_u8 else torch.float32, tail=(3,))
+    n, max_area = rgb.shape[:2]
+    hs, ws, _ = shape_tables(shapes, device)
     masks = torch.empty((n, max_area), dtype=torch.bool, device=device)
     work = torch.empty(int(lib.d3r_segment_sky_workspace_bytes(n, max_area)), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
         check(lib.d3r_segment_sky(n, ptr(rgb), int(is_u8), ptr(hs), ptr(ws), max_area, ptr(masks), ptr(work), current_stream()), 'segment_sky')
-    return [masks[i, :h * w].view(h, w) for i, (h, w) in enumerate(shapes)]
+    return split_views(masks, shapes)
 
 
 def segment_sky(image):
@@ -73,9 +71,10 @@ def _tensor(x):
 def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False, to_host=True):
     """The geometry of the demo's GLB export for all views in one GPU call (csrc/mesh.hip).
 
-    imgs: H x W x 3 RGB images (numpy or tensors, all uint8 or all floating in [0, 1]; sizes may differ). pts3d: per view an (H, W, 3) map, or
-    the padded (n, max_area, 3) tensor of `scene.get_pts3d(raw=True)`. masks: per view an (H, W) boolean map. Numpy inputs are uploaded,
-    device tensors are used where they are.
+    imgs: H x W x 3 RGB images (numpy or tensors, all uint8 or all floating in [0, 1]; sizes may differ). pts3d: per view an (H, W, 3) map,
+    masks: per view an (H, W) boolean map; either may instead be the ready padded stack (utils/padded.py) -- the (n, row, 3) tensor of
+    `scene.get_pts3d(raw=True)`, the (n, row) tensor of `scene.get_masks(raw=True)` -- and the rest is padded to its rows. Numpy inputs are
+    uploaded, device tensors are used where they are.
 
     Mesh mode: the faces of the reference's `cat_meshes([pts3d_to_trimesh(img, pts, mask) ...])` as uint32 (every vertex of every view is
     kept), a colour per vertex (the mean of the colours of the valid faces that use it; include/dust3r_hip.h d3r_scene_mesh), and every
@@ -105,29 +104,13 @@ def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False, to_host=Tr
     n_vert = sum(areas)
     if n_vert >= 2 ** 32:
         raise ValueError(f'scene_mesh_batch: {n_vert} vertices do not fit uint32 indices (as_pointcloud=True or fewer views)')
-    max_area = max(areas)
-    if isinstance(pts3d, torch.Tensor) and pts3d.ndim == 3:          # the padded layout of scene.get_pts3d(raw=True)
-        if pts3d.shape[1] < max_area or pts3d.shape[2] != 3:
-            raise ValueError(f'scene_mesh_batch: padded pointmaps {tuple(pts3d.shape)} for views of up to {max_area} pixels')
-        pts = pts3d.detach().to(device=device, dtype=torch.float32).contiguous()
-        max_area = pts.shape[1]
-    else:
-        pts = torch.zeros((n, max_area, 3), dtype=torch.float32, device=device)
-        for i, (p, a) in enumerate(zip(pts3d, areas)):
-            p = _tensor(p)
-            if p.numel() != 3 * a:
-                raise ValueError(f'scene_mesh_batch: pointmap {i} has shape {tuple(p.shape)}, its image {shapes[i]}')
-            pts[i, :a] = p.reshape(a, 3)
-    mask = torch.zeros((n, max_area), dtype=torch.uint8, device=device)
-    rgb = torch.zeros((n, max_area, 3), dtype=torch.uint8 if is_u8 else torch.float32, device=device)
-    for i, (m, im, a) in enumerate(zip(masks, images, areas)):
-        m = _tensor(m)
-        if m.numel() != a:
-            raise ValueError(f'scene_mesh_batch: mask {i} has shape {tuple(m.shape)}, its image {shapes[i]}')
-        mask[i, :a] = m.reshape(a)
-        rgb[i, :a] = im.reshape(a, 3)
-    hs = torch.tensor([h for h, w in shapes], dtype=torch.int32, device=device)
-    ws = torch.tensor([w for h, w in shapes], dtype=torch.int32, device=device)
+    # a ready stack among the inputs sets the rows of all three
+    row = next((x.shape[1] for x, nd in ((pts3d, 3), (masks, 2)) if isinstance(x, torch.Tensor) and x.ndim == nd), None)
+    pts = pad_views(pts3d, device, torch.float32, (3,), row, shapes, 'scene_mesh_batch: pointmap')
+    mask = pad_views(masks, device, torch.uint8, (), row, shapes, 'scene_mesh_batch: mask')
+    rgb = pad_views(images, device, torch.uint8 if is_u8 else torch.float32, (3,), row, shapes, 'scene_mesh_batch: image')
+    max_area = pts.shape[1]
+    hs, ws, _ = shape_tables(shapes, device)
     n_faces = sum(4 * (h - 1) * (w - 1) for h, w in shapes if h > 1 and w > 1)
     faces = None if as_pointcloud else torch.empty((max(n_faces, 1), 3), dtype=torch.int32, device=device)
     points = torch.empty((n_vert, 3), dtype=torch.float32, device=device) if as_pointcloud else None
@@ -141,35 +124,19 @@ def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False, to_host=Tr
         counts = small[:n].numpy().copy()
         lo, hi = small[n:].view(torch.float32).numpy()[:3].copy(), small[n:].view(torch.float32).numpy()[3:].copy()
         total = int(counts.sum())
-        if not to_host:
-            if as_pointcloud:
-                dev_pos = points[:total]
-            else:
-                dev_pos = pts.view(n_vert, 3) if n * max_area == n_vert else torch.cat([pts[i, :a] for i, a in enumerate(areas)])
-            return dict(positions=dev_pos, colors=colors[:total] if as_pointcloud else colors, faces=None if as_pointcloud else faces[:total],
-                        counts=counts, bounds=(lo, hi) if total > 0 else None)
         if as_pointcloud:
-            positions = host_tensor((total, 3), torch.float32)
-            positions.copy_(points[:total])
-            col = host_tensor((total,), torch.int32)
-            col.copy_(colors[:total])
-            face_arr = None
-        else:
-            positions = host_tensor((n_vert, 3), torch.float32)
-            if n * max_area == n_vert:
-                positions.copy_(pts.view(n_vert, 3))
-            else:
-                start = 0
-                for i, a in enumerate(areas):
-                    positions[start:start + a].copy_(pts[i, :a])
-                    start += a
-            col = host_tensor((n_vert,), torch.int32)
-            col.copy_(colors)
-            face_host = host_tensor((total, 3), torch.int32)
-            face_host.copy_(faces[:total])
-            face_arr = face_host.numpy().view(np.uint32)
-    return dict(positions=positions.numpy(), colors=col.numpy().view(np.uint8).reshape(-1, 4), faces=face_arr, counts=counts,
-                bounds=(lo, hi) if total > 0 else None)
+            out = dict(positions=points[:total], colors=colors[:total], faces=None)
+        else:       # every vertex of every view: the stack itself when no view has padding
+            packed = pts.view(n_vert, 3) if n * max_area == n_vert else torch.cat([pts[i, :a] for i, a in enumerate(areas)])
+            out = dict(positions=packed, colors=colors, faces=faces[:total])
+        if to_host:
+            for k, t in out.items():
+                if t is not None:
+                    out[k] = host_tensor(t.shape, t.dtype)
+                    out[k].copy_(t)
+            out = dict(positions=out['positions'].numpy(), colors=out['colors'].numpy().view(np.uint8).reshape(-1, 4),
+                       faces=None if as_pointcloud else out['faces'].numpy().view(np.uint32))
+    return dict(out, counts=counts, bounds=(lo, hi) if total > 0 else None)
 
 
 def _rot_z(deg):

@@ -259,7 +259,8 @@ def test_get_reconstructed_scene_on_files(gpu, engine, tmp_path, sizes, image_si
 
 
 def test_scene_gallery_on_a_modular_scene_and_on_copied_maps(gpu):
-    """ModularPointCloudOptimizer, and a scene whose confidence maps are separate tensors (not views of one stack): the copy path."""
+    """ModularPointCloudOptimizer, and a scene that was assigned confidence maps of the caller's (`scene.im_conf = [...]`): the setter copies
+    them into the scene's stack, which the gallery then reads like any other."""
     from dust3r_amd.cloud_opt import GlobalAlignerMode, global_aligner
     from dust3r_amd.demo import scene_gallery
     from dust3r_amd.synthetic import synthetic_scene
