@@ -128,6 +128,10 @@ def _load():
         'd3r_sky_color_mask': (i, [i, vp, i, ip, ip, i, vp, vp]),
         'd3r_scene_mesh_workspace_bytes': (C.c_size_t, [i, i]),
         'd3r_scene_mesh': (i, [i, vp, vp, vp, i, ip, ip, i, i, vp, vp, vp, vp, vp, vp, vp]),
+        'd3r_fuse_bounds_workspace_bytes': (C.c_size_t, [i, i]),
+        'd3r_fuse_bounds': (i, [i, fp, vp, fp, ip, ip, i, fp, vp, vp, vp]),
+        'd3r_fuse_voxels_workspace_bytes': (C.c_size_t, [i, i, i]),
+        'd3r_fuse_voxels': (i, [i, fp, vp, fp, vp, i, ip, ip, i, C.POINTER(C.c_float), f, C.POINTER(C.c_int), i, fp, vp, fp, ip, vp, vp, vp]),
         'd3r_scene_gallery_workspace_bytes': (C.c_size_t, [i, i]),
         'd3r_scene_gallery': (i, [i, fp, fp, ip, i, fp, fp, fp, fp, vp, vp]),
         'd3r_scene_gallery_launch_bound': (None, [C.POINTER(C.c_int)] * 3),

@@ -12,7 +12,8 @@ binary:
 The function users call, `get_reconstructed_scene` (dust3r/demo.py:135-186): files -> load_images -> make_pairs -> inference -> global_aligner ->
 compute_global_alignment -> get_3D_model_from_scene, and the rgb / depth / confidence gallery it returns (`scene_gallery`: one GPU call
 for all images, csrc/gallery.hip, no matplotlib). `scenegraph_options` is the rule of set_scenegraph_options as plain data, and
-`python -m dust3r_amd.demo` the command line in place of the gradio page."""
+`python -m dust3r_amd.demo` the command line in place of the gradio page; its --fuse / --ply / --colmap (new) also write the fused cloud of
+`scene.fuse()` as scene.ply and as a COLMAP model (`write_fused`, dust3r_amd/export.py)."""
 import argparse
 import copy
 import json
@@ -354,6 +355,11 @@ def get_args_parser():
     parser.add_argument('--clean_depth', action=argparse.BooleanOptionalAction, default=True, help='clean-up depthmaps')
     parser.add_argument('--transparent_cams', action='store_true', default=False)
     parser.add_argument('--turntable', type=int, default=0, metavar='N', help='also render N turntable frames into outdir/turntable')
+    parser.add_argument('--fuse', type=float, nargs='?', const=0.0, default=None, metavar='VOXEL',
+                        help='fuse the views into one voxel-averaged cloud (scene.fuse) and write it as outdir/scene.ply; VOXEL: the voxel size '
+                             '(default: the median pixel footprint)')
+    parser.add_argument('--ply', action='store_true', default=False, help='write the fused cloud as outdir/scene.ply (implies --fuse)')
+    parser.add_argument('--colmap', action='store_true', default=False, help='write the fused cloud, cameras and images as a COLMAP model in outdir/colmap (implies --fuse)')
     return parser
 
 
@@ -397,6 +403,22 @@ def write_cameras(outdir, scene):
     return name
 
 
+def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, ply=True, colmap=False):
+    """outdir/scene.ply and / or outdir/colmap of the scene's fused cloud (scene.fuse; export.write_ply / write_colmap), with the mask of
+    get_3D_model_from_scene: min_conf_thr through the scene's confidence transform, the sky on request. Returns the file names."""
+    from .export import write_colmap
+    if mask_sky:
+        scene = scene.mask_sky()
+    scene.min_conf_thr = float(scene.conf_trf(torch.tensor(min_conf_thr)))
+    cloud = scene.fuse(voxel_size=voxel_size or None)
+    written = []
+    if ply:
+        written.append(cloud.save_ply(os.path.join(outdir, 'scene.ply')))
+    if colmap:
+        written += write_colmap(os.path.join(outdir, 'colmap'), scene, cloud)
+    return written
+
+
 def main(argv=None):
     from .model import AsymmetricCroCo3DStereo
     args = get_args_parser().parse_args(argv)
@@ -413,6 +435,9 @@ def main(argv=None):
     if args.turntable > 0:
         written += render_turntable(os.path.join(args.outdir, 'turntable'), scene, n_frames=args.turntable, min_conf_thr=args.min_conf_thr,
                                     mask_sky=args.mask_sky, clean_depth=args.clean_depth, transparent_cams=args.transparent_cams, silent=args.silent)
+    if args.fuse is not None or args.ply or args.colmap:
+        written += write_fused(args.outdir, scene, voxel_size=args.fuse, min_conf_thr=args.min_conf_thr, mask_sky=args.mask_sky,
+                               ply=args.ply or not args.colmap, colmap=args.colmap)
     if not args.silent:
         print('(wrote', len(written), 'files to', args.outdir, ')')
     return 0

@@ -6,6 +6,8 @@
   (`scene_camera_geometry`). dust3r_amd/glb.py writes the file, dust3r_amd/demo.py mirrors the demo's export functions;
 - `SceneViz` (viz.py:119-209) as a HEADLESS viewer: the same `add_pointcloud` / `add_camera` / `add_cameras`, and `render` / `show` that draw
   the scene into images with the rasteriser of csrc/render.hip (`render_batch`, C ABI `d3r_render_*`) instead of opening a window.
+- the fused cloud (new): `fuse_points` merges the views' pointmaps into one voxel-fused, weighted cloud (csrc/fuse.hip, C ABI
+  `d3r_fuse_bounds` / `d3r_fuse_voxels`), a `FusedCloud`; dust3r_amd/export.py writes it as PLY or as a COLMAP model.
 The interactive viewers (a window, show_raw_pointcloud*) are not mirrored."""
 import numpy as np
 import torch
@@ -137,6 +139,135 @@ def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False, to_host=Tr
             out = dict(positions=out['positions'].numpy(), colors=out['colors'].numpy().view(np.uint8).reshape(-1, 4),
                        faces=None if as_pointcloud else out['faces'].numpy().view(np.uint32))
     return dict(out, counts=counts, bounds=(lo, hi) if total > 0 else None)
+
+
+# ---- the fused cloud -------------------------------------------------------------------------------------------------------------------
+FUSE_MAX_AXIS_BITS = 21         # three axes in one 64-bit key
+
+
+class FusedCloud:
+    """The voxel-fused cloud of `fuse_points` / `scene.fuse()`: positions (M, 3) float32, colors (M, 3) uint8, weight (M,) float32 (the summed
+    weights of a voxel's points), count (M,) int32 (their number), in ascending voxel-key order; numpy arrays, or torch tensors on the device
+    with to_host=False. voxel_size, origin (3,) float32 (the minimum of the fused points: voxel (i, j, k) starts at origin + voxel_size (i, j,
+    k)) and bounds = (min, max) of the fused points, (+inf, -inf) for an empty cloud."""
+
+    def __init__(self, positions, colors, weight, count, voxel_size, bounds):
+        self.positions, self.colors, self.weight, self.count = positions, colors, weight, count
+        self.voxel_size = float(voxel_size)
+        self.bounds = bounds
+        self.origin = bounds[0]
+
+    def __len__(self):
+        return len(self.positions)
+
+    def save_ply(self, path):
+        """Binary little-endian PLY with the per-point confidence (= weight) and count (export.write_ply)."""
+        from .export import write_ply
+        return write_ply(path, *(_to_numpy(a) for a in (self.positions, self.colors, self.weight, self.count)))
+
+
+def check_voxel_size(voxel_size):
+    """voxel_size as np.float32; ValueError unless it is a normal positive fp32."""
+    with np.errstate(over='ignore'):
+        v = np.float32(voxel_size)
+    if not (np.isfinite(v) and v >= np.finfo(np.float32).tiny):
+        raise ValueError(f'voxel_size = {voxel_size!r} must be a normal positive float32')
+    return v
+
+
+def fuse_key_bits(lo, hi, voxel_size):
+    """Bits of each axis in the voxel key: max(1, bit_length(floor((hi_c - lo_c) / voxel))), the quotient in float32 exactly as the kernel
+    forms it for the farthest point. ValueError when an axis needs more than 21."""
+    v = check_voxel_size(voxel_size)
+    with np.errstate(over='ignore', invalid='ignore'):
+        ext = np.floor((np.asarray(hi, np.float32) - np.asarray(lo, np.float32)) / v)
+    if not (np.isfinite(ext).all() and (ext < 2.0 ** FUSE_MAX_AXIS_BITS).all()):
+        raise ValueError(f"voxel_size too small for the scene's extent: {voxel_size!r} for points from {np.asarray(lo).tolist()} to "
+                         f'{np.asarray(hi).tolist()} (at most 2^{FUSE_MAX_AXIS_BITS} voxels per axis)')
+    return [max(1, int(e).bit_length()) for e in ext]
+
+
+def default_voxel_size(depth, areas, focals):
+    """The voxel size of `scene.fuse()` when none is given, the median pixel footprint: the lower median over the views of
+    lower_median(depth_i over its h w pixels) / focal_i. depth: the padded (n, row) stack, areas: h w per view, focals (n,) or (n, 2) (fx, fy:
+    their mean). torch, on the stack's device."""
+    f = torch.as_tensor(focals, dtype=torch.float32, device=depth.device).reshape(len(areas), -1).mean(dim=1)
+    per_view = torch.stack([depth[i, :a].median() for i, a in enumerate(areas)]) / f
+    return float(per_view.median())
+
+
+@torch.no_grad()
+def fuse_points(imgs, pts3d, masks, weights, voxel_size, device, min_count=1, to_host=True):
+    """The views' pointmaps merged into one de-duplicated cloud on the GPU (csrc/fuse.hip): the valid pixels -- mask set, finite point, finite
+    weight > 0 -- are binned into voxels of `voxel_size` from the minimum of their bounds, and every voxel becomes one point: the weighted
+    mean of its points and of their colours (fp64 sums in view-then-raster order: the same bytes on every run). include/dust3r_hip.h,
+    d3r_fuse_bounds / d3r_fuse_voxels.
+
+    imgs, pts3d, masks as for `scene_mesh_batch` (lists of maps, or the ready padded stacks of a scene); weights: per view an (H, W) map, the
+    (n, row) stack, or None for ones. voxel_size: a number, or a function without arguments that gives it, called only when some pixel is
+    valid (`scene.fuse()`'s default comes from the depth maps; a scene without a valid point has none and needs none). min_count: voxels of
+    fewer points are dropped. Returns a `FusedCloud` (empty when nothing is valid). Two host synchronisations: the bounds, then the voxel
+    count. ValueError when voxel_size is not a normal positive float32, or too small for the extent (more than 2^21 voxels along an axis)."""
+    import ctypes as C
+    voxel = np.float32('nan') if callable(voxel_size) else check_voxel_size(voxel_size)
+    _lib.require_device()
+    device = torch.device(device)
+    n = len(masks)
+    if len(imgs) < n or len(pts3d) != n or (weights is not None and len(weights) != n):
+        raise ValueError(f'fuse_points: {len(imgs)} images, {len(pts3d)} pointmaps, {n} masks, {None if weights is None else len(weights)} weight maps')
+    if n == 0:
+        raise ValueError('fuse_points: no views')
+    images = [_tensor(im) for im in imgs[:n]]
+    images = [im.float() if im.is_floating_point() and im.dtype != torch.float32 else im for im in images]
+    images = [_as_hwc(im) for im in images]
+    is_u8 = images[0].dtype == torch.uint8
+    if any((im.dtype == torch.uint8) != is_u8 for im in images):
+        raise TypeError('fuse_points: mix of uint8 and float images')
+    shapes = [tuple(im.shape[:2]) for im in images]
+    # a ready stack among the inputs sets the rows of all four
+    row = next((x.shape[1] for x, nd in ((pts3d, 3), (masks, 2), (weights, 2)) if isinstance(x, torch.Tensor) and x.ndim == nd), None)
+    pts = pad_views(pts3d, device, torch.float32, (3,), row, shapes, 'fuse_points: pointmap')
+    mask = pad_views(masks, device, torch.uint8, (), row, shapes, 'fuse_points: mask')
+    wgt = None if weights is None else pad_views(weights, device, torch.float32, (), row, shapes, 'fuse_points: weight')
+    rgb = pad_views(images, device, torch.uint8 if is_u8 else torch.float32, (3,), row, shapes, 'fuse_points: image')
+    row = pts.shape[1]
+    if n * row >= 2 ** 31:
+        raise ValueError(f'fuse_points: {n} rows of {row} do not fit 31-bit pixel indices (fewer views per call)')
+    hs, ws, _ = shape_tables(shapes, device)
+    small = torch.empty((4,), dtype=torch.int64, device=device)           # bounds [6] fp32, then the count: one read-back
+    work = torch.empty(max(1, int(lib.d3r_fuse_bounds_workspace_bytes(n, row))), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        check(lib.d3r_fuse_bounds(n, ptr(pts), ptr(mask), ptr(wgt), ptr(hs), ptr(ws), row, ptr(small.view(torch.float32)), ptr(small[3:]), ptr(work),
+                                  current_stream()), 'fuse_bounds')
+        host = small.cpu()
+        lo, hi = host[:3].view(torch.float32).numpy()[:3].copy(), host[:3].view(torch.float32).numpy()[3:].copy()
+        n_valid = int(host[3])
+        cap = max(n_valid, 1)
+        positions = torch.empty((cap, 3), dtype=torch.float32, device=device)
+        colors = torch.empty((cap,), dtype=torch.int32, device=device)
+        weight = torch.empty((cap,), dtype=torch.float32, device=device)
+        count = torch.empty((cap,), dtype=torch.int32, device=device)
+        m = 0
+        if n_valid > 0:
+            if callable(voxel_size):
+                voxel = check_voxel_size(voxel_size())
+            bits = fuse_key_bits(lo, hi, voxel)                            # raises before anything else is launched
+            totals = torch.empty((2,), dtype=torch.int64, device=device)
+            work = torch.empty(int(lib.d3r_fuse_voxels_workspace_bytes(n, row, cap)), dtype=torch.uint8, device=device)
+            check(lib.d3r_fuse_voxels(n, ptr(pts), ptr(mask), ptr(wgt), ptr(rgb), int(is_u8), ptr(hs), ptr(ws), row, (C.c_float * 3)(*lo.tolist()),
+                                      float(voxel), (C.c_int * 3)(*bits), cap, ptr(positions), ptr(colors), ptr(weight), ptr(count), ptr(totals),
+                                      ptr(work), current_stream()), 'fuse_voxels')
+            got, m = (int(v) for v in totals.cpu())
+            if got != n_valid:
+                raise _lib.D3RError(f'fuse_voxels: {got} valid pixels, the bounds pass counted {n_valid}')
+        out = [positions[:m], colors[:m].view(torch.uint8).view(m, 4)[:, :3], weight[:m], count[:m]]
+        if min_count > 1:
+            keep = out[3] >= min_count
+            out = [t[keep] for t in out]
+        out[1] = out[1].contiguous()
+        if to_host:
+            out = [t.cpu().numpy() for t in out]
+    return FusedCloud(*out, voxel_size=voxel, bounds=(lo, hi))
 
 
 def _rot_z(deg):

@@ -349,6 +349,36 @@ int d3r_scene_mesh(int n_views, const float* pts, const uint8_t* mask, const voi
                    int max_area, int as_pointcloud, uint32_t* faces_out, float* points_out, uint32_t* colors_out, long long* counts_out,
                    float* bounds_out, void* workspace, void* stream);
 
+/* scene.fuse(): the pointmaps of n views merged into one voxel-fused, weighted cloud (new; csrc/fuse.hip). Inputs as for d3r_scene_mesh,
+ * rows of `row` elements: pts [n][row][3] DEVICE fp32, mask [n][row] DEVICE uint8, weight [n][row] DEVICE fp32 or NULL (all ones),
+ * rgb [n][row][3] DEVICE (uint8 when rgb_is_u8, else fp32; the colour q of a pixel as for d3r_scene_mesh), img_h / img_w DEVICE int
+ * arrays; n * row <= 2^31 - 1, at most 65535 views. What lies behind a view's h w elements is never read. A pixel is VALID when its mask
+ * is nonzero, its three coordinates are finite and its weight is finite and > 0.
+ * d3r_fuse_bounds: bounds_out [6] DEVICE fp32 = component-wise min, max of the valid points ((+inf, -inf) when there is none), count_out
+ *   [1] DEVICE int64 = their number. Per-workgroup partials, then one workgroup in index order. workspace:
+ *   d3r_fuse_bounds_workspace_bytes(n, row) bytes of DEVICE memory.
+ * d3r_fuse_voxels: lo [3] and bits [3] are HOST arrays read during the call, 1 <= bits <= 21; voxel a positive finite fp32.
+ *   1. every valid pixel gets the 64-bit key q_x | q_y << bits_x | q_z << (bits_x + bits_y), q_c = (int)floorf((p_c - lo_c) / voxel) --
+ *      fp32 subtraction and IEEE division, q clamped to [0, 2^bits_c - 1] (with lo = the bounds' minimum and bits_c = the bit length of
+ *      floorf((max_c - lo_c) / voxel) the clamp never acts) --, and the pairs (key, flat index v row + e) are compacted in view-then-raster
+ *      order; 2. a stable LSD radix sort by key over bits_x + bits_y + bits_z bits; 3. the voxels are the runs of equal keys; 4. per voxel,
+ *      over its points in sorted order (= view, then raster) in fp64: W = sum w, S_c = sum w p_c, C_k = sum w q_k.
+ *   positions_out [capacity][3] fp32 = (float)(S_c / W); colors_out [capacity] RGBA8 = floor(C_k / W + 1/2) clamped to [0, 255], alpha 255;
+ *   weight_out [capacity] fp32 = (float)W; count_out [capacity] int32 = the voxel's points; the first M rows are written, in ascending key
+ *   order. totals_out [2] DEVICE int64 = (valid pixels N, voxels M). capacity: the rows of the outputs and of the sort buffers; at least
+ *   the count of d3r_fuse_bounds (pixels beyond it are dropped, nothing is written out of bounds). workspace:
+ *   d3r_fuse_voxels_workspace_bytes(n, row, capacity) bytes of DEVICE memory (0 for invalid shapes).
+ * No atomics and no waiting between workgroups (every scan over tiles is a launch of its own): the same bytes on every run. A voxel that
+ * holds most of the scene is walked by one thread: slow, not wrong. D3R_ERR_INVALID on NULL or out-of-range arguments; no allocation,
+ * no synchronisation. */
+size_t d3r_fuse_bounds_workspace_bytes(int n_views, int row);
+int d3r_fuse_bounds(int n_views, const float* pts, const uint8_t* mask, const float* weight, const int* img_h_dev, const int* img_w_dev, int row,
+                    float* bounds_out, long long* count_out, void* workspace, void* stream);
+size_t d3r_fuse_voxels_workspace_bytes(int n_views, int row, int capacity);
+int d3r_fuse_voxels(int n_views, const float* pts, const uint8_t* mask, const float* weight, const void* rgb, int rgb_is_u8, const int* img_h_dev,
+                    const int* img_w_dev, int row, const float* lo, float voxel, const int* bits, int capacity, float* positions_out,
+                    uint32_t* colors_out, float* weight_out, int* count_out, long long* totals_out, void* workspace, void* stream);
+
 /* The depth / confidence gallery of the demo (the end of get_reconstructed_scene, dust3r/demo.py:168-184) for n images in one call.
  * depth, conf [n][max_area] DEVICE fp32 (a scene's padded stacks), npix_dev [n] DEVICE int: the pixel count of each image (a count that is
  * negative or above max_area makes its image empty); what lies behind a count is neither read into a result nor written. table [257][4]
