@@ -21,6 +21,8 @@ TORCH_DTYPE = {DTYPE_BF16: torch.bfloat16, DTYPE_F16: torch.float16, DTYPE_F32: 
  ALIGNER_OPT_EDGE_MEAN_LOSS, ALIGNER_OPT_FX_AND_FY) = 1, 2, 3, 4, 5, 6, 7
 ALIGNER_TRAIN_POSES, ALIGNER_TRAIN_FOCALS, ALIGNER_TRAIN_PP = 0, 1, 2
 SCHEDULE_COSINE, SCHEDULE_LINEAR = 0, 1
+HEAD_ROPE, HEAD_VT, HEAD_PLAIN = 1, 2, 3      # D3R_HEAD_* of include/dust3r_hip.h
+TILE_128W8 = 12                               # D3R_TILE_128W8
 
 ERRORS = {0: 'OK', -1: 'invalid argument', -2: 'allocation failed', -3: 'kernel launch failed', -4: 'unknown state-dict key',
           -5: 'shape mismatch', -6: 'bad state (weights missing / no gfx950 device)'}
@@ -83,6 +85,9 @@ def _load():
         'd3r_layernorm': (i, [fp, fp, fp, vp, i, i, f, i, vp]),
         'd3r_linear': (i, [vp, vp, fp, vp, fp, i, i, i, i, i, vp]),
         'd3r_linear_x3res': (i, [vp, vp, fp, vp, vp, fp, i, i, i, vp]),
+        'd3r_rope_table': (i, [fp, i, f, f, vp]),
+        'd3r_linear_heads': (i, [vp, vp, fp, i, i, i, i, ip, vp, i, i, i, i, fp, i, fp, fp, fp, fp, f, fp, C.c_size_t, vp, i, i, vp]),
+        'd3r_linear_heads_tile_config': (i, [i, i, i, i, ip, i, i, i, i, i, i]),
         'd3r_conv2d_nhwc': (i, [vp, vp, fp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, vp, i, vp]),
         'd3r_conv_k_slice_major': (i, []),
         'd3r_attention': (i, [vp, vp, vp, vp, i, i, i, i, i, f, i, vp]),

@@ -37,6 +37,56 @@ extern "C" int d3r_linear_x3res(const void* act, const void* wgt, const float* b
     return rc_of(launch_gemm(D3R_F16X3, p, (hipStream_t)stream));
 }
 
+extern "C" int d3r_rope_table(float* table, int max_pos, float base, float F0, void* stream) {
+    if (!table || max_pos <= 0 || !(base > 0.f)) return D3R_ERR_INVALID;
+    return rc_of(launch_rope_table(table, max_pos, base, F0, (hipStream_t)stream));
+}
+
+// The shape half of an EPI_HEADS launch (d3r_linear_heads, d3r_linear_heads_tile_config): the argument checks of the header, then the GemmParams
+// fields the tile heuristic reads. Weight rows as d3r_linear allocates them.
+static bool heads_shape(GemmParams& p, int dtype, int M, int K, int n_regions, int head_c, const int* kinds, int heads, int ntok, int tok_w, int ldv, int max_pos) {
+    if (dtype != D3R_BF16 && dtype != D3R_F16 && dtype != D3R_F32 && dtype != D3R_F16X3 && dtype != D3R_F16F8 && dtype != D3R_F16X2F8) return false;
+    if (M <= 0 || K <= 0 || n_regions < 1 || n_regions > 3 || !kinds || heads <= 0 || head_c != heads * 64 || ntok <= 0 || tok_w <= 0) return false;
+    if (M % ntok != 0 || ntok % tok_w != 0 || (ntok / tok_w > tok_w ? ntok / tok_w : tok_w) > max_pos) return false;
+    if (ldv < rup(ntok, 64) || ldv % 64 != 0) return false;
+    for (int r = 0; r < n_regions; ++r)
+        if (kinds[r] != HEAD_ROPE && kinds[r] != HEAD_VT && kinds[r] != HEAD_PLAIN) return false;
+    const int N = n_regions * head_c;
+    p.lda = K; p.M = M; p.K = K; p.n_pad = rup(N, 128); p.n_rows = rup(N, 256); p.n_store = N;
+    p.epi = EPI_HEADS; p.head_c = head_c; p.heads = heads; p.ntok = ntok; p.tok_w = tok_w; p.ldv = ldv;
+    for (int r = 0; r < n_regions; ++r) p.head_kind[r] = kinds[r];
+    return true;
+}
+
+extern "C" int d3r_linear_heads(const void* act, const void* wgt, const float* bias, int M, int K, int n_regions, int head_c, const int* kinds, void* const* dsts,
+                                int heads, int ntok, int tok_w, int ldv, const float* rope_table, int max_pos, float* ln_rstd, float* ln_nmr,
+                                const float* ln_colsum, const float* ln_part_in, float ln_eps, float* sk_slab, size_t sk_slab_floats, unsigned* sk_cnt,
+                                int sk_cnt_n, int dtype, void* stream) {
+    if (!act || !wgt || !dsts || !rope_table) return D3R_ERR_INVALID;
+    GemmParams p;
+    if (!heads_shape(p, dtype, M, K, n_regions, head_c, kinds, heads, ntok, tok_w, ldv, max_pos)) return D3R_ERR_INVALID;
+    for (int r = 0; r < n_regions; ++r) {
+        if (!dsts[r]) return D3R_ERR_INVALID;
+        p.head_dst[r] = dsts[r];
+    }
+    if ((ln_rstd || ln_nmr || ln_colsum || ln_part_in) && (dtype != D3R_F16X3 || !ln_rstd || !ln_nmr || !ln_colsum)) return D3R_ERR_INVALID;
+    p.act = act; p.wgt = wgt; p.bias = bias; p.rope_table = rope_table;
+    if (ln_rstd) { p.ln_rstd = ln_rstd; p.ln_nmr = ln_nmr; p.ln_colsum = ln_colsum; p.ln_part_in = ln_part_in; p.ln_eps = ln_eps; p.ln_inv_c = 1.0f / (float)K; }
+    if (sk_slab && sk_cnt) { p.splitk = 0; p.sk_slab = sk_slab; p.sk_slab_floats = sk_slab_floats; p.sk_cnt = sk_cnt; p.sk_cnt_n = sk_cnt_n; }      // launch_gemm decides whether it splits (engine.hip gemm_linear)
+    return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
+}
+
+extern "C" int d3r_linear_heads_tile_config(int M, int K, int n_regions, int head_c, const int* kinds, int heads, int ntok, int tok_w, int ldv, int max_pos,
+                                            int dtype) {
+    static const float dummy = 0.f;
+    GemmParams p;
+    if (!heads_shape(p, dtype, M, K, n_regions, head_c, kinds, heads, ntok, tok_w, ldv, max_pos)) return D3R_ERR_INVALID;
+    p.act = &dummy; p.wgt = &dummy;      // (never dereferenced)
+    p.flags |= gemm_env_flags(p);
+    const int cfg = gemm_pick_config(p, dtype);
+    return cfg == GEMM_CFG_128 && gemm_runs_128w8(p, dtype) ? D3R_TILE_128W8 : cfg;
+}
+
 extern "C" int d3r_conv_k_slice_major(void) { return 1; }
 
 extern "C" int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bias, void* out, const void* res1, const void* res2, void* out_relu_copy,

@@ -1660,6 +1660,18 @@ static int pick_config_raw(const GemmParams& p, int dt) {
     return GEMM_CFG_128;
 }
 
+bool gemm_runs_128w8(const GemmParams& p, int dt) {
+    if (dt != D3R_F16X3) return false;
+    const char* e = getenv("D3R_GEMM_T128W8");
+    const long t = e ? atol(e) : 1100;
+    return (long)cdiv(p.M, 128) * cdiv(p.n_store, 128) < t;
+}
+int gemm_env_flags(const GemmParams& p) {
+    // (the folded-LayerNorm producer launches keep their wide epilogue: it is where the row sums and the typed residual stream are written)
+    if (const char* e = getenv("D3R_GEMM_NOWIDE")) if (e[0] == '1' && !p.ln_part && !(p.flags & GF_X3RES)) return GF_NOWIDE;
+    return 0;
+}
+
 template <int DT> static hipError_t launch_t(const GemmParams& p, hipStream_t s) {
     const int cfg = gemm_pick_config(p, DT);       // already mapped onto the shapes DT has
     // the fused head tail needs a wave to hold every output channel of its rows: waves stacked along m, 128 columns per wave
@@ -1673,11 +1685,7 @@ template <int DT> static hipError_t launch_t(const GemmParams& p, hipStream_t s)
         // 128 x 128 launches of fewer than 1100 tiles (the one- to four-pair forwards) on the eight-wave shape. Measured (profiles/r03_k):
         // one pair 10.59 -> 10.26 ms, two 16.0 -> 15.3, four 26.3 -> 25.9; applied to the 1152-tile launches of the 32-pair step as well:
         // -0.1 %, hence the limit. D3R_GEMM_T128W8 moves it (0 = never).
-        if (cfg == GEMM_CFG_128) {
-            const char* e = getenv("D3R_GEMM_T128W8");
-            const long t = e ? atol(e) : 1100;
-            if ((long)cdiv(p.M, 128) * cdiv(p.n_store, 128) < t) return launch_cfg<DT, Cfg128w8>(p, s);
-        }
+        if (cfg == GEMM_CFG_128 && gemm_runs_128w8(p, DT)) return launch_cfg<DT, Cfg128w8>(p, s);
     }
     if constexpr (DT == D3R_F16F8) {
         // the 256-wide tiles with the DMA pieces interleaved with the MFMA rows (PP = 4). Measured on MI355X (profiles/r02_f8/bench_f8_il.log): +3 % on
@@ -1708,8 +1716,7 @@ void gemm_set_trace(unsigned long long* buf, size_t capacity_blocks) { g_trace_b
 hipError_t launch_gemm(int dt, const GemmParams& p_in, hipStream_t s) {
     GemmParams p = p_in;
     if (g_trace_buf && (size_t)cdiv(p.M, 128) * cdiv(p.n_store, 128) <= g_trace_cap) p.trace = g_trace_buf;   // capacity for the smallest tile
-    // (the folded-LayerNorm producer launches keep their wide epilogue: it is where the row sums and the typed residual stream are written)
-    if (const char* e = getenv("D3R_GEMM_NOWIDE")) if (e[0] == '1' && !p.ln_part && !(p.flags & GF_X3RES)) p.flags |= GF_NOWIDE;
+    p.flags |= gemm_env_flags(p);
     p.flags |= GF_NTSTORE;      // wide epilogues store with the non-temporal policy (measured +3..10 % on isolated GEMMs, +1 % on the forward)
     const int kt = 128 / (int)dt_bytes(dt);
     if (p.M <= 0 || p.n_pad % 128 != 0 || p.n_store > p.n_pad || p.K % kt != 0 || p.K <= 0) return hipErrorInvalidValue;

@@ -71,6 +71,11 @@ void gemm_set_trace(unsigned long long* buf, size_t capacity_blocks);
 
 hipError_t launch_gemm(int dt, const GemmParams& p, hipStream_t s);
 int gemm_pick_config(const GemmParams& p, int dt);
+// what launch_gemm reads from the environment for a launch of p before it asks gemm_pick_config: GF_NOWIDE under D3R_GEMM_NOWIDE=1 (it changes the V^T route of
+// the 16-bit attention projections, hence the tiles a heads launch may take). Host queries of the heuristic (capi.hip) add the same flags.
+int gemm_env_flags(const GemmParams& p);
+// true when a launch that gemm_pick_config sends to GEMM_CFG_128 runs the tile on EIGHT waves (split-fp16, fewer than D3R_GEMM_T128W8 = 1100 tiles)
+bool gemm_runs_128w8(const GemmParams& p, int dt);
 // gemm_p4.hip: the persistent split-fp16 kernel whose epilogue runs under the next tile's K loop (tile configuration 10 in profiles)
 bool gemm_p4_eligible(const GemmParams& p, int dt);
 hipError_t launch_gemm_p4(const GemmParams& p, hipStream_t s);

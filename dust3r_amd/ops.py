@@ -1,5 +1,5 @@
 """Thin torch-tensor wrappers over the building-block entry points of libdust3r_hip.so
-(d3r_rope2d / d3r_layernorm / d3r_linear / d3r_conv2d_nhwc / d3r_attention / d3r_upsample2x_nhwc).
+(d3r_rope2d / d3r_layernorm / d3r_linear / d3r_linear_heads / d3r_conv2d_nhwc / d3r_attention / d3r_upsample2x_nhwc).
 
 `rope_2d` is the drop-in for the reference's only native op, croco's `curope.rope_2d(tokens,
 positions, base, F0)` (in place; see include/dust3r_hip.h). The other wrappers exist so the parity
@@ -198,6 +198,75 @@ def linear_x2f8(act, weight, bias=None, epilogue='store', residual=None):
     out = torch.empty((M, N), dtype=torch.float32, device=act.device) if epi == 1 else torch.empty((M, 4 * N), dtype=torch.uint8, device=act.device)
     check(lib.d3r_linear(ptr(ap), ptr(wp), ptr(bp), ptr(out), ptr(residual), M, N, K, epi, _lib.DTYPE_F16X2F8, current_stream()), 'linear(f16x2f8)')
     return out if epi == 1 else unpack_f8(out)
+
+
+_HEAD_KINDS = {'rope': _lib.HEAD_ROPE, 'vt': _lib.HEAD_VT, 'plain': _lib.HEAD_PLAIN}
+# destination element type of an attention-projection launch per precision mode (the fp8 modes hand split-fp16 rows to the attention kernel),
+# and the storage elements per logical element
+_HEAD_STORE = {'fp32': (torch.float32, 1), 'bf16': (torch.bfloat16, 1), 'fp16': (torch.float16, 1), 'fp16x3': (torch.float16, 2), 'fp16f8': (torch.float16, 2),
+               'fp16x2f8': (torch.float16, 2)}
+
+
+def rope_table(max_pos, base, F0=1.0, device='cuda'):
+    """d3r_rope_table: (max_pos, 16, 2) fp32 (cos, sin) pairs of pos * F0 / base^(i/16)."""
+    _lib.require_device()
+    t = torch.empty((max_pos, 16, 2), dtype=torch.float32, device=device)
+    check(lib.d3r_rope_table(ptr(t), max_pos, float(base), float(F0), current_stream()), 'rope_table')
+    return t
+
+
+def heads_dst_numel(kind, B, H, ntok, ldv, dtype):
+    """storage elements of one destination of linear_heads (q / k: B H ntok 64, V^T: B H 64 ldv logical elements)"""
+    return B * H * 64 * (ldv if kind == 'vt' else ntok) * _HEAD_STORE[dtype][1]
+
+
+def heads_tile_config(M, K, kinds, head_c, ntok, tok_w, ldv, dtype, max_pos=512):
+    """d3r_linear_heads_tile_config (host only): the tile configuration that launch runs on, environment pins applied."""
+    import ctypes as C
+    kk = (C.c_int * 3)(*([_HEAD_KINDS[k] for k in kinds] + [0] * (3 - len(kinds))))
+    return lib.d3r_linear_heads_tile_config(M, K, len(kinds), head_c, kk, head_c // 64, ntok, tok_w, ldv, max_pos, _lib.DTYPES[dtype])
+
+
+def linear_heads(act, weight, bias, kinds, head_c, ntok, tok_w, ldv, table, dtype='fp16x3', dsts=None, ln=None, splitk=None):
+    """One attention-projection launch (d3r_linear_heads): act (M, K), weight (N, K) fp32, N = len(kinds) * head_c, kinds of 'rope' | 'vt' | 'plain';
+    the operands are packed for `dtype` (a key of _lib.DTYPES). dsts: one flat tensor per region in the mode's destination type, at least
+    heads_dst_numel elements, filled by the CALLER (nothing here zeroes them: what the launch leaves untouched stays visible); None: allocated here,
+    filled with 1.0. ln: dict(rstd, nmr, colsum[, part_in, eps]) of fp32 tensors -- the folded-LayerNorm consumer; splitk: (slab fp32, counters int32).
+    Returns the regions as fp32: q / k (B, H, ntok, 64), V^T (B, H, 64, ldv)."""
+    import ctypes as C
+    _lib.require_device()
+    M, K = act.shape
+    N = weight.shape[0]
+    B, H = M // ntok, head_c // 64
+    if dtype == 'fp16x3':
+        ap, wp = pack_x3(act), pad_rows(pack_x3(weight))
+    elif dtype == 'fp16f8':
+        ap, wp = pack_f8(act), pad_rows(pack_f8(weight, weight=True))
+    elif dtype == 'fp16x2f8':
+        ap, wp = pack_f8(act), pad_rows(pack_w5(weight))
+    else:
+        tdt = _lib.TORCH_DTYPE[_lib.DTYPES[dtype]]
+        ap, wp = act.to(tdt).contiguous(), pad_rows(weight.to(tdt))
+    bp = None if bias is None else pad_rows(bias.float())
+    sdt, per = _HEAD_STORE[dtype]
+    if dsts is None:
+        dsts = [torch.ones(heads_dst_numel(k, B, H, ntok, ldv, dtype), dtype=sdt, device=act.device) for k in kinds]
+    for d, k in zip(dsts, kinds):
+        assert d.dtype == sdt and d.is_contiguous() and d.numel() >= heads_dst_numel(k, B, H, ntok, ldv, dtype)
+    kk = (C.c_int * 3)(*([_HEAD_KINDS[k] for k in kinds] + [0] * (3 - len(kinds))))
+    dd = (C.c_void_p * 3)(*([d.data_ptr() for d in dsts] + [None] * (3 - len(kinds))))
+    ln = ln or {}
+    colsum = None if ln.get('colsum') is None else pad_rows(ln['colsum'].float())
+    slab, cnt = splitk if splitk is not None else (None, None)
+    check(lib.d3r_linear_heads(ptr(ap), ptr(wp), ptr(bp), M, K, len(kinds), head_c, kk, dd, H, ntok, tok_w, ldv, ptr(table), table.shape[0],
+                               ptr(ln.get('rstd')), ptr(ln.get('nmr')), ptr(colsum), ptr(ln.get('part_in')), float(ln.get('eps', 1e-6)),
+                               ptr(slab), 0 if slab is None else slab.numel(), ptr(cnt), 0 if cnt is None else cnt.numel(),
+                               _lib.DTYPES[dtype], current_stream()), f'linear_heads({dtype})')
+    out = []
+    for d, k in zip(dsts, kinds):
+        v = d[:heads_dst_numel(k, B, H, ntok, ldv, dtype)].view((B, H, 64, ldv * per) if k == 'vt' else (B, H, ntok, 64 * per))
+        out.append(unpack_x3(v) if per == 2 else v.float())
+    return out
 
 
 def layernorm_f8(x, gamma, beta, eps=1e-6):

@@ -83,6 +83,44 @@ int d3r_linear(const void* act, const void* wgt, const float* bias, void* out, c
 int d3r_linear_x3res(const void* act, const void* wgt, const float* bias, void* out_rows, const void* residual_rows, float* ln_part, int M, int N,
                      int K, void* stream);
 
+/* The cos / sin table the attention projections rotate with: table[pos][i] = (cos, sin)(pos * inv_freq_i) for pos in [0, max_pos), i in [0, 16),
+ * inv_freq_i = fp32(F0 / base^(i/16)) formed in fp64, the angle their fp32 product (as croco's pure-torch RoPE2D forms it), cos / sin evaluated in
+ * fp64 and rounded to fp32. table: max_pos * 32 floats of device memory. */
+int d3r_rope_table(float* table, int max_pos, float base, float F0, void* stream);
+
+/* The attention projections of a croco Block / DecoderBlock (qkv, projq, projk | projv: dust3r/model.py:136-137,176-186 via croco blocks.py) as ONE
+ * launch of the GEMM with its head-scatter epilogue -- exported so that the kernel tests can pin it against fp64 (the engine calls it from C++):
+ *   y[M][N] = act[M][K] . wgt[N][K]^T + bias,  N = n_regions * head_c,  head_c = heads * 64,  row m = token t = m % ntok of image b = m / ntok,
+ *   token position (ty, tx) = (t / tok_w, t % tok_w).
+ * Column n belongs to region n / head_c and head h = (n % head_c) / 64, d = n % 64; region r is stored to dsts[r] by kinds[r]: */
+#define D3R_HEAD_ROPE 1  /* [B][heads][ntok][64], 2-D RoPE applied: d 0-31 rotate with ty, d 32-63 with tx; inside a half the pairs are (c, c + 16),
+                          * (u, v) -> (u cos - v sin, v cos + u sin) with rope_table[pos][c % 16]; the bias is added BEFORE the rotation */
+#define D3R_HEAD_VT 2    /* [B][heads][64][ldv]: transposed, token t in column t. The padding columns [ntok, ldv) of a V^T destination are never written. */
+#define D3R_HEAD_PLAIN 3 /* [B][heads][ntok][64] without a rotation (the engine never asks for it; every route of the epilogue honours it) */
+/* Nothing outside [B][heads][ntok][64] / [B][heads][64][ldv] elements of a destination is written either. Destinations are in `dtype`; for
+ * D3R_DTYPE_F16F8 / D3R_DTYPE_F16X2F8 they are split-fp16 rows (what the attention kernel of those engines reads).
+ * act, wgt, bias (NULL: none) as for d3r_linear: wgt and bias hold round_up(N, 256) rows, the extra rows zero. rope_table: d3r_rope_table's, max_pos rows.
+ * Folded LayerNorm (split-fp16 only; all NULL: none): with wgt = W diag(gamma), bias = b + W beta, ln_colsum[n] = sum_k wgt[n][k] (of the ROUNDED operand;
+ * round_up(N, 256) floats) the launch computes rstd_m (acc - mean_m colsum_n) + bias_n from ln_rstd[m] = rstd and ln_nmr[m] = -mean rstd of the input
+ * rows; with ln_part_in != NULL ([M][K / 32][2]: (sum, sum of squares) of every 32-column group of act's rows, K <= 2048) the launch forms the two
+ * statistics itself (eps = ln_eps, 1 / K as the mean's factor) and WRITES them to ln_rstd / ln_nmr.
+ * Split-K: sk_slab (sk_slab_floats floats) and sk_cnt (sk_cnt_n counters) are a loan the launch MAY use (split-fp16, a problem the heuristic sends
+ * to the 64 x 64 tile, at least 16 K steps of 32 per slice); sk_cnt must be zero before the first launch that uses it and is zero again after every launch.
+ * D3R_ERR_INVALID: a NULL operand (act, wgt, dsts, a dsts[r], rope_table), heads * 64 != head_c, M % ntok != 0, ntok % tok_w != 0,
+ * max(ntok / tok_w, tok_w) > max_pos, ldv < round_up(ntok, 64) or ldv % 64 != 0, n_regions outside 1..3, a kind outside the three above,
+ * statistics without all of ln_rstd / ln_nmr / ln_colsum or in another dtype than split-fp16. */
+int d3r_linear_heads(const void* act, const void* wgt, const float* bias, int M, int K, int n_regions, int head_c, const int* kinds, void* const* dsts,
+                     int heads, int ntok, int tok_w, int ldv, const float* rope_table, int max_pos, float* ln_rstd, float* ln_nmr,
+                     const float* ln_colsum, const float* ln_part_in, float ln_eps, float* sk_slab, size_t sk_slab_floats, unsigned* sk_cnt,
+                     int sk_cnt_n, int dtype, void* stream);
+/* Diagnostics, host only (no device needed): the tile configuration that launch runs on (codes of d3r_gemm_tile_config), with D3R_GEMM_CFG,
+ * D3R_GEMM_NOWIDE and D3R_GEMM_T128W8 applied -- a pinned configuration that is infeasible for the launch is IGNORED, and this is how a caller sees it.
+ * D3R_TILE_128W8: the 128x128 tile on eight waves (split-fp16 launches of fewer than D3R_GEMM_T128W8 = 1100 tiles). Feasible for a heads launch:
+ * 0 and 8 (8: split-fp16 only); 1 when head_c % 256 == 0; 2 and 3 for bf16 / fp16 when ntok % 64 == 0 and D3R_GEMM_NOWIDE is not set (only then is V^T
+ * transposed in the staging tile; every other V^T route swaps the MFMA operand roles and needs a square tile); never 7, 9, 11. */
+#define D3R_TILE_128W8 12
+int d3r_linear_heads_tile_config(int M, int K, int n_regions, int head_c, const int* kinds, int heads, int ntok, int tok_w, int ldv, int max_pos, int dtype);
+
 /* 2-D convolution, NHWC, as implicit GEMM: in [B][Hin][Win][Cin] dtype, wgt [round_up(Cout,256)][k*k*Cin] dtype;
  * out [B][Hout][Wout][Cout] dtype = [relu](conv + bias + res1 + res2)   (DPT head convs, dust3r/heads/dpt_head.py:34-65).
  * K order of a weight row: with S = 128 / sizeof(dtype) channels per K step (Cin % S == 0),
