@@ -23,6 +23,7 @@ ALIGNER_TRAIN_POSES, ALIGNER_TRAIN_FOCALS, ALIGNER_TRAIN_PP = 0, 1, 2
 SCHEDULE_COSINE, SCHEDULE_LINEAR = 0, 1
 HEAD_ROPE, HEAD_VT, HEAD_PLAIN = 1, 2, 3      # D3R_HEAD_* of include/dust3r_hip.h
 TILE_128W8 = 12                               # D3R_TILE_128W8
+CONV_RELU, CONV_NOWIDE, DECLINED = 1, 4, 1    # D3R_CONV_RELU / D3R_CONV_NOWIDE (flags of d3r_conv2d_nhwc_x), D3R_DECLINED (d3r_conv_head4)
 
 ERRORS = {0: 'OK', -1: 'invalid argument', -2: 'allocation failed', -3: 'kernel launch failed', -4: 'unknown state-dict key',
           -5: 'shape mismatch', -6: 'bad state (weights missing / no gfx950 device)'}
@@ -90,6 +91,13 @@ def _load():
         'd3r_linear_heads_tile_config': (i, [i, i, i, i, ip, i, i, i, i, i, i]),
         'd3r_conv2d_nhwc': (i, [vp, vp, fp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, vp, i, vp]),
         'd3r_conv_k_slice_major': (i, []),
+        'd3r_pack_conv_weight': (i, [fp, vp, i, i, i, i, i, i, i, vp]),
+        'd3r_pack_convt_bias': (i, [fp, fp, i, i, i, vp]),
+        'd3r_conv2d_nhwc_x': (i, [vp, vp, fp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, i, vp, i, vp]),
+        'd3r_convt_gemm': (i, [vp, vp, fp, vp, i, i, i, i, i, i, i, i, i, vp]),
+        'd3r_conv_head4': (i, [vp, vp, fp, fp, fp, fp, fp, i, i, i, i, i, i, i, i, i, i, i, f, f, vp, i, vp]),
+        'd3r_head_final': (i, [vp, i, fp, fp, fp, fp, C.c_size_t, i, i, i, i, f, f, i, vp]),
+        'd3r_linear_head_post': (i, [fp, fp, fp, i, i, i, i, i, i, i, i, f, f, vp]),
         'd3r_attention': (i, [vp, vp, vp, vp, i, i, i, i, i, f, i, vp]),
         'd3r_upsample2x_nhwc': (i, [vp, vp, i, i, i, i, i, i, i, vp]),
         'd3r_gemm_set_trace': (i, [vp, C.c_size_t]),

@@ -103,6 +103,85 @@ extern "C" int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bia
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
+// ---- the DPT head's kernels alone (include/dust3r_hip.h): the launches of engine.hip run_dpt, for the kernel tests -------------------------------
+static inline bool conv_dtype(int dtype) { return dtype == D3R_BF16 || dtype == D3R_F16 || dtype == D3R_F32 || dtype == D3R_F16X3; }
+static inline bool post_mode(PostMode& pm, int depth_mode, int conf_mode, float vmin, float vmax) {      // d3r_model_set_postprocess's rules
+    if (depth_mode < POST_DEPTH_EXP || depth_mode > POST_DEPTH_SQUARE || conf_mode < POST_CONF_EXP || conf_mode > POST_CONF_SIGMOID) return false;
+    if (!(vmin < vmax) || (conf_mode == POST_CONF_SIGMOID && !(vmax < __builtin_huge_valf() && vmin > -__builtin_huge_valf()))) return false;
+    pm.depth = depth_mode; pm.conf = conf_mode; pm.cmin = vmin; pm.cmax = vmax;
+    return true;
+}
+
+extern "C" int d3r_pack_conv_weight(const float* src, void* dst, int transposed, int Cout, int Cin, int ksize, int cin_pad, int cout_pad, int dtype,
+                                    void* stream) {
+    if (!src || !dst || !conv_dtype(dtype) || Cout <= 0 || Cin <= 0 || ksize <= 0) return D3R_ERR_INVALID;
+    if (cin_pad < Cin || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || (transposed && (cout_pad < Cout || cout_pad % 4 != 0))) return D3R_ERR_INVALID;
+    PackParams pp;
+    pp.src = src; pp.dst = dst; pp.numel = (size_t)Cout * Cin * ksize * ksize; pp.ksize = ksize;
+    if (transposed) { pp.kind = PACK_CONVT; pp.cols = Cout; pp.cout_pad = cout_pad; pp.dst_cols = cin_pad; }                 // engine.hip reg_convt / PK_CONVT
+    else { pp.kind = PACK_CONV; pp.cin = Cin; pp.cin_pad = cin_pad; pp.dst_cols = ksize * ksize * cin_pad; }                 // engine.hip reg_conv / PK_CONV
+    return rc_of(launch_pack_weight(dtype, pp, (hipStream_t)stream));
+}
+
+extern "C" int d3r_pack_convt_bias(const float* src, float* dst, int Cout, int cout_pad, int ksize, void* stream) {
+    if (!src || !dst || Cout <= 0 || cout_pad < Cout || ksize <= 0) return D3R_ERR_INVALID;
+    return rc_of(launch_pack_convt_bias(src, dst, Cout, cout_pad, ksize * ksize, (hipStream_t)stream));
+}
+
+extern "C" int d3r_conv2d_nhwc_x(const void* in, const void* wgt, const float* bias, void* out, const void* res1, const void* res2, void* out_relu_copy,
+                                 int B, int Hin, int Win, int cstride, int cin_pad, int Cout, int n_store, int ldo, int ksize, int stride, int pad, int flags,
+                                 const void* zero_page, int dtype, void* stream) {
+    if (!in || !wgt || !out || !zero_page || !conv_dtype(dtype) || B <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || ksize <= 0 || stride <= 0 || pad < 0) return D3R_ERR_INVALID;
+    if (n_store < 0) n_store = Cout;
+    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || cstride < cin_pad) return D3R_ERR_INVALID;      // whole K steps per tap, inside a pixel's row
+    if (n_store % 4 != 0 || n_store > rup(Cout, 128) || ldo < n_store || (flags & ~(GF_RELU | GF_NOWIDE))) return D3R_ERR_INVALID;
+    if (Hin + 2 * pad < ksize || Win + 2 * pad < ksize) return D3R_ERR_INVALID;
+    GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, wgt, bias, cin_pad, Cout, ksize, stride, pad, zero_page);
+    p.n_store = n_store;
+    p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.res1 = res1; p.res2 = res2; p.ldr = ldo; p.out2 = out_relu_copy; p.ldo2 = ldo;      // engine.hip conv()
+    return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
+}
+
+extern "C" int d3r_convt_gemm(const void* act, const void* wgt, const float* bias, void* out, int B, int th, int tw, int lda, int cin_pad, int cout_pad,
+                              int ksize, int ldo, int dtype, void* stream) {
+    if (!act || !wgt || !out || !conv_dtype(dtype) || B <= 0 || th <= 0 || tw <= 0 || ksize <= 0) return D3R_ERR_INVALID;
+    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || lda < cin_pad || cout_pad <= 0 || cout_pad % 4 != 0 || ldo < cout_pad) return D3R_ERR_INVALID;
+    const int N = ksize * ksize * cout_pad;
+    GemmParams p;      // engine.hip run_dpt, the EPI_CONVT launch
+    p.act = act; p.lda = lda; p.wgt = wgt; p.bias = bias; p.M = B * th * tw; p.K = cin_pad;
+    p.n_pad = rup(N, 128); p.n_rows = rup(N, 256); p.n_store = N; p.epi = EPI_CONVT; p.ksize = ksize; p.ct_cout = cout_pad;
+    p.Hin = th; p.Win = tw; p.out = out; p.ldo = ldo;
+    return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
+}
+
+extern "C" int d3r_conv_head4(const void* in, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B, int Hin,
+                              int Win, int cstride, int cin_pad, int Cout, int ksize, int pstride, int conf_stride, int depth_mode, int conf_mode,
+                              float conf_vmin, float conf_vmax, const void* zero_page, int dtype, void* stream) {
+    if (!in || !wgt || !w4 || !b4 || !pts || !conf || !zero_page || !conv_dtype(dtype) || B <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || ksize <= 0) return D3R_ERR_INVALID;
+    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || cstride < cin_pad || pstride < 3 || conf_stride < 1) return D3R_ERR_INVALID;
+    GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, wgt, bias, cin_pad, Cout, ksize, 1, 1, zero_page);      // engine.hip conv_head4()
+    p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = conf_stride; p.res1 = w4; p.res2 = b4;
+    if (!post_mode(p.post, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
+    if (head4_tile(p, dtype) < 0) return D3R_DECLINED;
+    return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
+}
+
+extern "C" int d3r_head_final(const void* feat, int C, const float* w4, const float* b4, float* pts, float* conf, size_t npix, int pstride, int conf_stride,
+                              int depth_mode, int conf_mode, float conf_vmin, float conf_vmax, int dtype, void* stream) {
+    PostMode pm;
+    if (!feat || !w4 || !b4 || !pts || !conf || !conv_dtype(dtype) || C <= 0 || C % 8 != 0 || npix == 0 || pstride < 3 || conf_stride < 1) return D3R_ERR_INVALID;
+    if (!post_mode(pm, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
+    return rc_of(launch_head_final(dtype, feat, C, w4, b4, pts, conf, npix, pstride, conf_stride, pm, (hipStream_t)stream));
+}
+
+extern "C" int d3r_linear_head_post(const float* feat, float* pts, float* conf, int B, int th, int tw, int ps, int pstride, int conf_stride, int depth_mode,
+                                    int conf_mode, float conf_vmin, float conf_vmax, void* stream) {
+    PostMode pm;
+    if (!feat || !pts || !conf || B <= 0 || th <= 0 || tw <= 0 || ps <= 0 || pstride < 3 || conf_stride < 1) return D3R_ERR_INVALID;
+    if (!post_mode(pm, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
+    return rc_of(launch_linear_head_post(feat, pts, conf, B, th, tw, ps, pstride, conf_stride, pm, (hipStream_t)stream));
+}
+
 extern "C" int d3r_attention(const void* q, const void* k, const void* vt, void* out, int B, int H, int Nq, int Nk, int ldv, float scale, int dtype,
                              void* stream) {
     if (!q || !k || !vt || !out) return D3R_ERR_INVALID;

@@ -443,12 +443,8 @@ void gemm_heads(Ctx& c, const void* act, int lda, const Lin& L, int M, int head_
 
 void conv(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const ConvW& w, int stride, int pad, void* out, int ldo,
           int flags, const void* res1 = nullptr, const void* res2 = nullptr, void* out2 = nullptr, int n_store = -1) {
-    GemmParams p;
-    p.amode = AMODE_CONV; p.act = in; p.wgt = w.w; p.bias = w.b;
-    p.Hin = Hin; p.Win = Win; p.Cin = w.cin_pad; p.cstride = cstride; p.ksize = w.k; p.stride = stride; p.pad = pad;
-    p.Hout = (Hin + 2 * pad - w.k) / stride + 1; p.Wout = (Win + 2 * pad - w.k) / stride + 1;
-    p.M = B * p.Hout * p.Wout; p.K = w.K; p.n_pad = w.n_pad; p.n_rows = w.n_rows; p.n_store = n_store >= 0 ? n_store : w.Cout;
-    p.zero_page = c.m->zero_page;
+    GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, w.w, w.b, w.cin_pad, w.Cout, w.k, stride, pad, c.m->zero_page);   // K, n_pad, n_rows: reg_conv's
+    if (n_store >= 0) p.n_store = n_store;
     p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.res1 = res1; p.res2 = res2; p.ldr = ldo; p.out2 = out2; p.ldo2 = ldo;
     c.mark(prf_kind(PRF_CONV, gemm_pick_config(p, c.m->dt)), 2.0 * p.M * (double)w.Cout * w.k * w.k * w.Cin, p.M, w.Cout, w.k * w.k * w.Cin);
     c.chk(launch_gemm(c.m->dt, p, c.st));
@@ -458,20 +454,10 @@ void conv(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const Co
 // the problem does not get a tile shape whose waves hold all output channels
 bool conv_head4(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const ConvW& w, const float* w4, const float* b4,
                 float* pts, float* conf, int pstride, int cstride_conf) {
-    GemmParams p;
-    p.amode = AMODE_CONV; p.act = in; p.wgt = w.w; p.bias = w.b;
-    p.Hin = Hin; p.Win = Win; p.Cin = w.cin_pad; p.cstride = cstride; p.ksize = w.k; p.stride = 1; p.pad = 1;
-    p.Hout = Hin; p.Wout = Win;
-    p.M = B * p.Hout * p.Wout; p.K = w.K; p.n_pad = w.n_pad; p.n_rows = w.n_rows; p.n_store = w.Cout;
-    p.zero_page = c.m->zero_page;
+    GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, w.w, w.b, w.cin_pad, w.Cout, w.k, 1, 1, c.m->zero_page);
     p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = cstride_conf; p.res1 = w4; p.res2 = b4; p.post = c.m->post;
-    if (w.k != 3 || w.Cout > 128 || w.Cout % 4 != 0) return false;
-    int cfg = gemm_pick_config(p, c.m->dt);
-    if (cfg != GEMM_CFG_512x128) {      // fewer pixels (one or two images): the same tile by four waves stacked along m. ANY pixel count below the 512 x 128
-        p.force_cfg = GEMM_CFG_256x128R;   // tile's takes this shape (round 5): with the heuristic's 128 x 128 choice for < 512 tiles the head of ONE 512 x 160
-        cfg = gemm_pick_config(p, c.m->dt);   // pair took the two-kernel route and a batch of three the fused one -- 3e-6 apart, the only place where a batch was not
-    }                                      // bit-equal to its one-pair calls (tests/test_timed_configs_gpu.py::test_full_size_released_resolutions_match_oracle)
-    if (cfg != GEMM_CFG_512x128 && cfg != GEMM_CFG_256x128R) return false;
+    const int cfg = head4_tile(p, c.m->dt);      // 512 x 128, else the forced 256 x 128 R (kernels.hpp)
+    if (cfg < 0) return false;
     c.mark(prf_kind(PRF_CONV, cfg), 2.0 * p.M * (double)w.Cout * w.k * w.k * w.Cin, p.M, w.Cout, w.k * w.k * w.Cin);
     c.chk(launch_gemm(c.m->dt, p, c.st));
     return true;

@@ -81,6 +81,35 @@ bool gemm_p4_eligible(const GemmParams& p, int dt);
 hipError_t launch_gemm_p4(const GemmParams& p, hipStream_t s);
 int gemm_p4_mode();              // -1: the heuristic decides, 0: never, 1: every eligible launch (D3R_GEMM_PERSIST, read per call: probes and tests move it)
 
+// The implicit-GEMM launches of the DPT head, built in ONE place for the engine (engine.hip conv / conv_head4) and for the kernel-level C ABI
+// (capi.hip d3r_conv2d_nhwc_x / d3r_conv_head4): what the kernel tests pin is what the engine launches.
+// conv_gemm_params: operand, geometry and weight-row fields of Conv2d(k, stride, pad) on NHWC rows of `cstride` elements per pixel whose first cin_pad
+// channels are read; weight rows as the loader allocates them (round_up(Cout, 256) rows of k k cin_pad). The caller adds the epilogue.
+inline GemmParams conv_gemm_params(const void* in, int B, int Hin, int Win, int cstride, const void* wgt, const float* bias, int cin_pad, int Cout, int k,
+                                   int stride, int pad, const void* zero_page) {
+    GemmParams p;
+    p.amode = AMODE_CONV; p.act = in; p.wgt = wgt; p.bias = bias;
+    p.Hin = Hin; p.Win = Win; p.Cin = cin_pad; p.cstride = cstride; p.ksize = k; p.stride = stride; p.pad = pad;
+    p.Hout = (Hin + 2 * pad - k) / stride + 1; p.Wout = (Win + 2 * pad - k) / stride + 1;
+    p.M = B * p.Hout * p.Wout; p.K = k * k * cin_pad; p.n_pad = (Cout + 127) / 128 * 128; p.n_rows = (Cout + 255) / 256 * 256; p.n_store = Cout;
+    p.zero_page = zero_page;
+    return p;
+}
+// head4_tile: the tile shape of an EPI_HEAD4 launch -- 512 x 128 where the heuristic picks it, else the FORCED 256 x 128 R (p.force_cfg is set) -- or -1 when
+// the launch cannot hold every output channel of a row in one wave (more than 128 channels, another precision mode): the caller takes the two-kernel route.
+// Fewer pixels (one or two images) take the same tile by four waves stacked along m. ANY pixel count below the 512 x 128 tile's takes this shape (round 5): with the
+// heuristic's 128 x 128 choice for < 512 tiles the head of ONE 512 x 160 pair took the two-kernel route and a batch of three the fused one -- 3e-6 apart, the only place where
+// a batch was not bit-equal to its one-pair calls (tests/test_timed_configs_gpu.py::test_full_size_released_resolutions_match_oracle)
+inline int head4_tile(GemmParams& p, int dt) {
+    if (p.ksize != 3 || p.n_store > 128 || p.n_store % 4 != 0) return -1;
+    int cfg = gemm_pick_config(p, dt);
+    if (cfg != GEMM_CFG_512x128) {
+        p.force_cfg = GEMM_CFG_256x128R;
+        cfg = gemm_pick_config(p, dt);
+    }
+    return (cfg == GEMM_CFG_512x128 || cfg == GEMM_CFG_256x128R) ? cfg : -1;
+}
+
 // ------------------------------------------------------------------------------ attention
 struct AttnParams {
     const void* q = nullptr;   // [B][H][Nq][64]

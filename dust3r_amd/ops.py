@@ -311,6 +311,140 @@ def conv2d_nhwc(x, weight, bias=None, stride=1, pad=0, relu=False, res1=None, re
     return (out, out2) if relu_copy else out
 
 
+# ---- the DPT head's kernels alone (include/dust3r_hip.h: d3r_pack_conv_weight ... d3r_linear_head_post). Tensors go in and come out as fp32 LOGICAL values;
+# `dtype` (a key of _lib.DTYPES: 'fp32' | 'bf16' | 'fp16' | 'fp16x3') is the layout the kernel works on. `out` / `pts` / `conf`: storage the CALLER filled
+# (what a launch leaves untouched stays visible to it); None: allocated here, zeroed.
+def to_rows(x, dtype='fp16x3'):
+    """fp32 (..., C) -> the storage rows of `dtype` (split-fp16: pack_x3, an fp16 tensor (..., 2C))."""
+    return pack_x3(x) if dtype == 'fp16x3' else x.to(_lib.TORCH_DTYPE[_lib.DTYPES[dtype]]).contiguous()
+
+
+def from_rows(t, dtype='fp16x3'):
+    return unpack_x3(t) if dtype == 'fp16x3' else t.float()
+
+
+def _post_args(post):
+    """(depth_mode, conf_mode, vmin, vmax) with the reference's names -> the arguments of d3r_model_set_postprocess"""
+    depth, conf, vmin, vmax = post
+    return ('exp', 'linear', 'square').index(depth), ('exp', 'sigmoid').index(conf), float(vmin), float(vmax)
+
+
+def pack_conv_weight_device(w, cin_pad=None, dtype='fp16x3', transposed=False, cout_pad=None):
+    """d3r_pack_conv_weight, the engine's loader: fp32 Conv2d weight (Cout, Cin, k, k) -> storage rows (round_up(Cout, 256), k*k*cin_pad), or --
+    transposed -- ConvTranspose2d weight (Cin, Cout, k, k) -> (round_up(k*k*cout_pad, 256), cin_pad)."""
+    _lib.require_device()
+    w = w.float().contiguous()
+    Cout, Cin = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
+    k = w.shape[2]
+    cin_pad, cout_pad = cin_pad or Cin, cout_pad or Cout
+    rows, cols = ((k * k * cout_pad + 255) // 256 * 256, cin_pad) if transposed else ((Cout + 255) // 256 * 256, k * k * cin_pad)
+    dst = to_rows(torch.zeros((rows, cols), dtype=torch.float32, device=w.device), dtype)
+    check(lib.d3r_pack_conv_weight(ptr(w), ptr(dst), int(transposed), Cout, Cin, k, cin_pad, cout_pad, _lib.DTYPES[dtype], current_stream()), 'pack_conv_weight')
+    return dst
+
+
+def pack_convt_bias_device(b, k, cout_pad=None):
+    """d3r_pack_convt_bias: (Cout,) -> fp32 (round_up(k*k*cout_pad, 256),), element (ky*k + kx) * cout_pad + co = b[co]."""
+    _lib.require_device()
+    b = b.float().contiguous()
+    cout_pad = cout_pad or b.numel()
+    dst = torch.zeros((k * k * cout_pad + 255) // 256 * 256, dtype=torch.float32, device=b.device)
+    check(lib.d3r_pack_convt_bias(ptr(b), ptr(dst), b.numel(), cout_pad, k, current_stream()), 'pack_convt_bias')
+    return dst
+
+
+def conv2d_nhwc_x(x, wp, bias, Cout, k, stride=1, pad=0, cin_pad=None, relu=False, nowide=False, res1=None, res2=None, relu_copy=False, n_store=None, ldo=None,
+                  dtype='fp16x3'):
+    """d3r_conv2d_nhwc_x (the engine's conv()): x (B, H, W, cstride) of which the first cin_pad channels are read, wp from pack_conv_weight_device, bias (Cout,) or None;
+    res1 / res2 (B, Ho, Wo, ldo). Returns (B, Ho, Wo, ldo) [, its ReLU copy]."""
+    _lib.require_device()
+    B, H, W, cstride = x.shape
+    cin_pad = cin_pad or cstride
+    n_store = Cout if n_store is None else n_store
+    ldo = n_store if ldo is None else ldo
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    xr = to_rows(x, dtype)
+    bp = None if bias is None else pad_rows(bias.float())
+    out = to_rows(torch.zeros((B, Ho, Wo, ldo), dtype=torch.float32, device=x.device), dtype)
+    out2 = torch.zeros_like(out) if relu_copy else None
+    r1, r2 = (None if r is None else to_rows(r, dtype) for r in (res1, res2))
+    flags = (_lib.CONV_RELU if relu else 0) | (_lib.CONV_NOWIDE if nowide else 0)
+    check(lib.d3r_conv2d_nhwc_x(ptr(xr), ptr(wp), ptr(bp), ptr(out), ptr(r1), ptr(r2), ptr(out2), B, H, W, cstride, cin_pad, Cout, n_store, ldo, k, stride, pad, flags,
+                                ptr(_zero_page(x.device)), _lib.DTYPES[dtype], current_stream()), f'conv2d_nhwc_x({dtype})')
+    return (from_rows(out, dtype), from_rows(out2, dtype)) if relu_copy else from_rows(out, dtype)
+
+
+def convt_gemm(x, wp, bp, k, cout_pad, cin_pad=None, ldo=None, dtype='fp16x3', out=None):
+    """d3r_convt_gemm (ConvTranspose2d, kernel = stride = k): x (B, th, tw, lda), wp / bp from pack_conv_weight_device(transposed=True) / pack_convt_bias_device.
+    Returns (B, k*th, k*tw, ldo)."""
+    _lib.require_device()
+    B, th, tw, lda = x.shape
+    cin_pad = cin_pad or lda
+    ldo = cout_pad if ldo is None else ldo
+    xr = to_rows(x, dtype)
+    if out is None:
+        out = to_rows(torch.zeros((B, k * th, k * tw, ldo), dtype=torch.float32, device=x.device), dtype)
+    check(lib.d3r_convt_gemm(ptr(xr), ptr(wp), ptr(bp), ptr(out), B, th, tw, lda, cin_pad, cout_pad, k, ldo, _lib.DTYPES[dtype], current_stream()), f'convt_gemm({dtype})')
+    n = B * k * th * k * tw * ldo
+    per = 2 if dtype == 'fp16x3' else 1
+    return from_rows(out.view(-1)[:n * per].view(B, k * th, k * tw, ldo * per), dtype)
+
+
+def _head_outputs(npix, strides, pts, conf, device):
+    ps, cs = strides
+    if pts is None:
+        pts = torch.zeros(npix * ps, dtype=torch.float32, device=device)
+    if conf is None:
+        conf = torch.zeros(npix * cs, dtype=torch.float32, device=device)
+    assert pts.dtype == conf.dtype == torch.float32 and pts.numel() >= (npix - 1) * ps + 3 and conf.numel() >= (npix - 1) * cs + 1
+    return pts, conf
+
+
+def _head_views(npix, strides, pts, conf):
+    """(npix, 3) and (npix,) strided views of the two outputs"""
+    ps, cs = strides
+    return pts.as_strided((npix, 3), (ps, 1)), conf.as_strided((npix,), (cs,))
+
+
+def conv_head4(x, wp, bias, w4, b4, Cout, post=('exp', 'exp', 1.0, float('inf')), strides=(3, 1), cin_pad=None, k=3, dtype='fp16x3', pts=None, conf=None):
+    """d3r_conv_head4 (the engine's conv_head4(): 3x3 conv + ReLU + 1x1 conv to 4 + postprocess in one launch): x (B, H, W, cstride), w4 (4, Cout), b4 (4,).
+    Returns (launched, pts (B*H*W, 3), conf (B*H*W,)); launched False = the entry point declined and wrote nothing."""
+    _lib.require_device()
+    B, H, W, cstride = x.shape
+    npix = B * H * W
+    pts, conf = _head_outputs(npix, strides, pts, conf, x.device)
+    xr = to_rows(x, dtype)
+    bp = None if bias is None else pad_rows(bias.float())
+    w4, b4 = w4.float().contiguous(), b4.float().contiguous()
+    rc = lib.d3r_conv_head4(ptr(xr), ptr(wp), ptr(bp), ptr(w4), ptr(b4), ptr(pts), ptr(conf), B, H, W, cstride,
+                            cin_pad or cstride, Cout, k, strides[0], strides[1], *_post_args(post), ptr(_zero_page(x.device)), _lib.DTYPES[dtype], current_stream())
+    if rc != _lib.DECLINED:
+        check(rc, f'conv_head4({dtype})')
+    return (rc == 0,) + _head_views(npix, strides, pts, conf)
+
+
+def head_final(feat, w4, b4, post=('exp', 'exp', 1.0, float('inf')), strides=(3, 1), dtype='fp16x3', pts=None, conf=None):
+    """d3r_head_final: feat (npix, C) ReLU'd features, w4 (4, C), b4 (4,) -> pts (npix, 3), conf (npix,)."""
+    _lib.require_device()
+    npix, Cc = feat.shape
+    pts, conf = _head_outputs(npix, strides, pts, conf, feat.device)
+    fr = to_rows(feat, dtype)
+    w4, b4 = w4.float().contiguous(), b4.float().contiguous()
+    check(lib.d3r_head_final(ptr(fr), Cc, ptr(w4), ptr(b4), ptr(pts), ptr(conf), npix, strides[0], strides[1],
+                             *_post_args(post), _lib.DTYPES[dtype], current_stream()), f'head_final({dtype})')
+    return _head_views(npix, strides, pts, conf)
+
+
+def linear_head_post(feat, B, th, tw, ps, post=('exp', 'exp', 1.0, float('inf')), strides=(3, 1), pts=None, conf=None):
+    """d3r_linear_head_post: feat fp32 (B*th*tw, 4*ps*ps) -> pts (B*th*ps*tw*ps, 3), conf (B*th*ps*tw*ps,)."""
+    _lib.require_device()
+    npix = B * th * ps * tw * ps
+    assert feat.shape == (B * th * tw, 4 * ps * ps) and feat.dtype == torch.float32
+    pts, conf = _head_outputs(npix, strides, pts, conf, feat.device)
+    check(lib.d3r_linear_head_post(ptr(feat), ptr(pts), ptr(conf), B, th, tw, ps, strides[0], strides[1], *_post_args(post), current_stream()), 'linear_head_post')
+    return _head_views(npix, strides, pts, conf)
+
+
 def attention(q, k, vt, Nk=None, scale=0.125):
     """q (B,H,Nq,64), k (B,H,Nk,64), vt (B,H,64,ldv) with ldv % 64 == 0 and zero padding -> (B,Nq,H*64)."""
     _lib.require_device()

@@ -132,6 +132,52 @@ int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bias, void* ou
                     void* out_relu_copy, int B, int Hin, int Win, int Cin, int Cout, int ksize, int stride, int pad, int relu,
                     const void* zero_page, int dtype, void* stream);
 
+/* ---- The DPT head's kernels alone (dust3r/heads/dpt_head.py:34-65, croco dpt_block.py; postprocess.py:10-58): the launches the model engine makes,
+ * exported so that the kernel tests can pin each against fp64 at the engine's operand layouts. dtype: bf16 / fp16 / fp32 / split-fp16 (the head never
+ * runs in the fp8 layouts); S = 128 / sizeof(dtype) channels per K step (32 for split-fp16 and fp32, 64 for the 16-bit types).
+ *
+ * Load-time weight packing on the device, fp32 PyTorch layout -> engine rows. dst must be ZERO before the call (only source elements are written: padding
+ * rows and channels stay zero), cin_pad % S == 0, cin_pad >= Cin.
+ *   transposed = 0, Conv2d weight src [Cout][Cin][k][k] -> dst [round_up(Cout, 256)][k*k*cin_pad] in d3r_conv2d_nhwc's K order over cin_pad channels;
+ *   transposed = 1, ConvTranspose2d weight src [Cin][Cout][k][k] -> dst [round_up(k*k*cout_pad, 256)][cin_pad], row (ky*k + kx) * cout_pad + co
+ *                   (cout_pad % 4 == 0, >= Cout): the weight rows of d3r_convt_gemm.
+ * d3r_pack_convt_bias: src [Cout] -> dst fp32 [k*k][cout_pad] (dst zero before the call, at least round_up(k*k*cout_pad, 256) floats for d3r_convt_gemm). */
+int d3r_pack_conv_weight(const float* src, void* dst, int transposed, int Cout, int Cin, int ksize, int cin_pad, int cout_pad, int dtype, void* stream);
+int d3r_pack_convt_bias(const float* src, float* dst, int Cout, int cout_pad, int ksize, void* stream);
+
+/* d3r_conv2d_nhwc with the engine's strides: input rows of `cstride` elements per pixel of which the first cin_pad are read (weights packed over cin_pad
+ * channels: whatever the activation rows hold in [Cin, cin_pad) meets zero weights); columns [0, n_store) of every output pixel are written (n_store < 0:
+ * Cout; n_store % 4 == 0, <= round_up(Cout, 128)) into rows of `ldo` elements -- out, res1, res2 and out_relu_copy all have that row stride. wgt: round_up(Cout, 256) rows
+ * of k*k*cin_pad, bias (NULL: none) that many floats. flags: D3R_CONV_RELU | D3R_CONV_NOWIDE (direct fragment stores instead of the LDS-staged rows: same values).
+ * D3R_ERR_INVALID (nothing launched): NULL in / wgt / out / zero_page, cin_pad % S != 0, cstride < cin_pad, ldo < n_store, an unknown flag or dtype. */
+#define D3R_CONV_RELU 1
+#define D3R_CONV_NOWIDE 4
+int d3r_conv2d_nhwc_x(const void* in, const void* wgt, const float* bias, void* out, const void* res1, const void* res2, void* out_relu_copy,
+                      int B, int Hin, int Win, int cstride, int cin_pad, int Cout, int n_store, int ldo, int ksize, int stride, int pad, int flags,
+                      const void* zero_page, int dtype, void* stream);
+
+/* ConvTranspose2d(kernel = stride = k, padding 0) as a GEMM with a scatter epilogue: act [B*th*tw][lda] rows (the first cin_pad elements read),
+ * wgt / bias from d3r_pack_conv_weight(transposed = 1) / d3r_pack_convt_bias; out [B][k*th][k*tw][ldo]: channels [0, cout_pad) of every output pixel
+ * are written (the padding channels with zeros), nothing else is. cout_pad % 4 == 0, ldo >= cout_pad. */
+int d3r_convt_gemm(const void* act, const void* wgt, const float* bias, void* out, int B, int th, int tw, int lda, int cin_pad, int cout_pad,
+                   int ksize, int ldo, int dtype, void* stream);
+
+/* The head's tail. depth_mode / conf_mode / conf_vmin / conf_vmax as d3r_model_set_postprocess; pts / conf are fp32 with pstride / conf_stride floats
+ * between pixels: (3, 1) = separate pts3d [npix][3] and conf [npix]; (8, 8) = the packed records of d3r_model_forward_packed. w4 fp32 [4][C], b4 fp32 [4].
+ * d3r_conv_head4 (split-fp16): Conv2d(cin_pad -> Cout, 3, padding 1) + bias + ReLU + Conv2d(Cout, 4, 1) + postprocess in ONE launch, on the 512 x 128 tile
+ *   where the tile heuristic picks it and on the 256 x 128 by-four-waves tile otherwise. Returns D3R_DECLINED -- nothing launched -- when no wave can hold all
+ *   channels of a pixel (ksize != 3, Cout > 128 or Cout % 4 != 0, another dtype): the engine then runs the two kernels below.
+ * d3r_head_final: Conv2d(C, 4, 1) + postprocess on ReLU'd features feat [npix][C] in `dtype`, C % 8 == 0.
+ * d3r_linear_head_post: LinearPts3d's tail (linear_head.py:36-41): pixel_shuffle(ps) of feat fp32 [B*th*tw][4*ps*ps] + postprocess, B*th*ps*tw*ps pixels. */
+#define D3R_DECLINED 1
+int d3r_conv_head4(const void* in, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B, int Hin,
+                   int Win, int cstride, int cin_pad, int Cout, int ksize, int pstride, int conf_stride, int depth_mode, int conf_mode,
+                   float conf_vmin, float conf_vmax, const void* zero_page, int dtype, void* stream);
+int d3r_head_final(const void* feat, int C, const float* w4, const float* b4, float* pts, float* conf, size_t npix, int pstride, int conf_stride,
+                   int depth_mode, int conf_mode, float conf_vmin, float conf_vmax, int dtype, void* stream);
+int d3r_linear_head_post(const float* feat, float* pts, float* conf, int B, int th, int tw, int ps, int pstride, int conf_stride, int depth_mode,
+                         int conf_mode, float conf_vmin, float conf_vmax, void* stream);
+
 /* softmax(q k^T * scale) v: q [B][H][Nq][64], k [B][H][Nk][64], vt [B][H][64][ldv] (ldv % 64 == 0, pad zero),
  * out [B][Nq][H*64]; all `dtype`   (croco Attention / CrossAttention core) */
 int d3r_attention(const void* q, const void* k, const void* vt, void* out, int B, int H, int Nq, int Nk, int ldv, float scale,
