@@ -145,6 +145,11 @@ def _load():
         'd3r_fuse_bounds': (i, [i, fp, vp, fp, ip, ip, i, fp, vp, vp, vp]),
         'd3r_fuse_voxels_workspace_bytes': (C.c_size_t, [i, i, i]),
         'd3r_fuse_voxels': (i, [i, fp, vp, fp, vp, i, ip, ip, i, C.POINTER(C.c_float), f, C.POINTER(C.c_int), i, fp, vp, fp, ip, vp, vp, vp]),
+        'd3r_cloud_grid_workspace_bytes': (C.c_size_t, [i, i]),
+        'd3r_cloud_grid_build': (i, [i, fp, C.POINTER(C.c_float), f, C.POINTER(C.c_int), vp, vp]),
+        'd3r_cloud_nearest': (i, [i, i, fp, f, C.POINTER(C.c_float), f, C.POINTER(C.c_int), i, fp, ip, ip, vp, vp]),
+        'd3r_cloud_distance_stats_workspace_bytes': (C.c_size_t, [i]),
+        'd3r_cloud_distance_stats': (i, [i, fp, fp, ip, i, C.POINTER(C.c_float), vp, vp, vp, vp]),
         'd3r_scene_gallery_workspace_bytes': (C.c_size_t, [i, i]),
         'd3r_scene_gallery': (i, [i, fp, fp, ip, i, fp, fp, fp, fp, vp, vp]),
         'd3r_scene_gallery_launch_bound': (None, [C.POINTER(C.c_int)] * 3),

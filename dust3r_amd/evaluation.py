@@ -7,7 +7,19 @@
 leave HBM); the table holds, for `loss` and every key of the criterion's details, `<key>_avg` = the mean of the per-batch values and
 `<key>_med` = their lower median -- what the reference's SmoothedValue reports with an unbounded window. `batches` can be a
 `dust3r_amd.datasets.get_data_loader(...)`: its batches are prepared on the GPU and arrive where the criterion reads them. Multi-rank
-evaluation is out of scope (ranks would add their per-pair sums and counts, see dust3r_amd/losses.py)."""
+evaluation is out of scope (ranks would add their per-pair sums and counts, see dust3r_amd/losses.py).
+
+    metrics = evaluate_scene(scene, gt_views)
+
+scores an aligned SCENE against ground-truth views (new; the reference has no such code): the scene is registered to the ground truth, both
+sides are voxel-fused at one voxel size and the two clouds are compared by `dust3r_amd.cloud_metrics` (accuracy, completeness, Chamfer,
+precision / recall / F-score), all on the GPU. `python -m dust3r_amd.evaluation PRED.ply GT.ply --max-dist D` does the last step on two
+PLY files."""
+import json
+import math
+import sys
+
+import numpy as np
 import torch
 
 from .inference import loss_of_one_batch
@@ -43,3 +55,130 @@ def evaluate(model, criterion, batches, device, symmetrize_batch=True, engine_ba
         table[f'{key}_avg'] = float(t.mean())
         table[f'{key}_med'] = float(t.median())
     return table
+
+
+# ---- a scene against ground-truth views ------------------------------------------------------------------------------------------------
+def _stack_moments(src, tgt, wgt, areas):
+    """(17,) weighted Umeyama moments of the padded stacks src -> tgt (n, row, 3) with weights (n, row): one d3r_similarity_moments job per
+    view (its h w elements), added in fp64 on the host (the moments are additive). Rows of pad_views / a scene are multiples of 4
+    elements, so every row starts on 16 bytes, as the kernel's float4 loads need."""
+    from ._lib import check, current_stream, lib, ptr
+    n, dev = len(areas), src.device
+    addrs = [[t.data_ptr() + i * t.stride(0) * 4 for i in range(n)] for t in (src, tgt, wgt)]
+    if not all(a % 16 == 0 for table in addrs for a in table):
+        raise ValueError('evaluate_scene: the stacks must have rows of a multiple of 4 elements (16-byte aligned rows)')
+    tables = [torch.tensor(table, dtype=torch.int64).to(dev) for table in addrs]
+    npix = torch.tensor(areas, dtype=torch.int32).to(dev)
+    out = torch.empty((n, 17), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(lib.d3r_similarity_moments_workspace(n, max(areas))), dtype=torch.uint8, device=dev)
+        check(lib.d3r_similarity_moments(n, ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), ptr(npix), max(areas), ptr(ws), ptr(out), current_stream()),
+              'similarity_moments')
+    return out.cpu().numpy().sum(axis=0)
+
+
+def pose_errors(pred_c2w, gt_c2w):
+    """(ate_rmse, mean rotation error, max rotation error in degrees) of cam-to-world poses (n, 4, 4) whose rotation blocks are rotations;
+    fp64 on the host. The angle between Rp and Rg is 2 asin(||Rp - Rg||_F / (2 sqrt 2)) (||R - I||_F = 2 sqrt 2 sin(angle / 2)): accurate
+    near zero, where arccos((trace - 1) / 2) has a noise floor of sqrt(2 eps)."""
+    P, G = np.asarray(pred_c2w, np.float64), np.asarray(gt_c2w, np.float64)
+    ate = math.sqrt(float(((P[:, :3, 3] - G[:, :3, 3]) ** 2).sum(axis=1).mean()))
+    chord = np.sqrt(((P[:, :3, :3] - G[:, :3, :3]) ** 2).sum(axis=(1, 2))) / (2 * math.sqrt(2))
+    ang = np.degrees(2 * np.arcsin(np.clip(chord, 0.0, 1.0)))
+    return ate, float(ang.mean()), float(ang.max())
+
+
+@torch.no_grad()
+def evaluate_scene(scene, gt_views, align='points', voxel_size=None, max_dist=None, thresholds=None, return_details=False):
+    """The cloud metrics of an aligned scene against ground truth. gt_views: per image a dict with `pts3d` (H, W, 3) world points,
+    `valid_mask` (H, W) and optionally `camera_pose` (4, 4) cam-to-world (the keys of dust3r_amd.datasets).
+    1. the similarity S that takes the scene into the ground truth's frame. align='points': one weighted Umeyama over all pixels valid on
+       both sides (the scene's mask and finite point, the ground truth's valid_mask and finite point; weight 1, the others zeroed with
+       weight 0) -- the 17 moments per image by d3r_similarity_moments, added in fp64 on the host, finished by
+       bootstrap.similarity_from_moments. align='poses': bootstrap.align_pose_sets of the scene's poses onto the camera_poses. None: identity.
+    2. both sides through viz.fuse_points at one voxel_size (default: the scene's default_voxel_size times the scale of S): the scene's
+       masked points, moved by S, weighted by confidence; the ground truth's valid points weighted by ones.
+    3. cloud_metrics(pred cloud, gt cloud, max_dist, thresholds); defaults thresholds = (1, 2, 4) voxel_size, max_dist = 16 voxel_size.
+    With camera_pose in every view: ate_rmse and rot_err_mean_deg / rot_err_max_deg of the scene's poses moved by S (fp64, host).
+    return_details: (metrics, details) with every stage's output: similarity (4, 4), scale, pred_pts / gt_pts / pred_mask / gt_mask
+    (the padded stacks that were fused), pred_cloud / gt_cloud, d2_pred / idx_pred / d2_gt / idx_gt, voxel_size, max_dist, thresholds."""
+    from . import _lib
+    from .cloud_metrics import cloud_metrics
+    from .cloud_opt.bootstrap import align_pose_sets, similarity_from_moments, split_similarity
+    from .utils.padded import pad_views
+    from .viz import default_voxel_size, fuse_points
+    if align not in ('points', 'poses', None):
+        raise ValueError(f"evaluate_scene: align is 'points', 'poses' or None, got {align!r}")
+    if scene.device.type != 'cuda':
+        raise _lib.D3RError('evaluate_scene runs on the GPU (dust3r_amd has no CPU execution path)')
+    _lib.require_device()
+    if scene.imgs is None:
+        raise ValueError('evaluate_scene needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
+    if len(gt_views) != scene.n_imgs:
+        raise ValueError(f'evaluate_scene: {len(gt_views)} ground-truth views for a scene of {scene.n_imgs} images')
+    dev, shapes = scene.device, [tuple(s) for s in scene.imshapes]
+    areas = [h * w for h, w in shapes]
+    pred = scene.get_pts3d(raw=True).detach().contiguous()
+    row = pred.shape[1]
+    pred_mask = scene.get_masks(raw=True)
+    gt = pad_views([v['pts3d'] for v in gt_views], dev, torch.float32, (3,), row, shapes, 'evaluate_scene: ground-truth pointmap')
+    gt_mask = pad_views([v['valid_mask'] for v in gt_views], dev, torch.uint8, (), row, shapes, 'evaluate_scene: valid_mask') != 0
+    has_poses = all(v.get('camera_pose') is not None for v in gt_views)
+    gt_poses = np.stack([np.asarray(torch.as_tensor(v['camera_pose']).detach().cpu(), np.float64) for v in gt_views]) if has_poses else None
+    poses = scene.get_im_poses().detach().double().cpu().numpy()
+    if align == 'points':
+        both = pred_mask & gt_mask & torch.isfinite(pred).all(dim=-1) & torch.isfinite(gt).all(dim=-1)
+        wgt = both.float().contiguous()
+        moments = _stack_moments(torch.where(both[..., None], pred, 0.0).contiguous(), torch.where(both[..., None], gt, 0.0).contiguous(), wgt, areas)
+        if not moments[0] > 0:
+            raise ValueError('evaluate_scene: no pixel is valid on both sides; nothing to register')
+        S = similarity_from_moments(moments)
+    elif align == 'poses':
+        if not has_poses:
+            raise ValueError("evaluate_scene: align='poses' needs camera_pose in every ground-truth view")
+        S = align_pose_sets(poses, gt_poses)
+    else:
+        S = np.eye(4)
+    scale, R, t = split_similarity(S)
+    A = torch.tensor(S[:3, :3], dtype=torch.float32, device=dev)
+    aligned = (pred @ A.T + torch.tensor(S[:3, 3], dtype=torch.float32, device=dev)).contiguous() if align is not None else pred
+    if voxel_size is None:
+        voxel_size = default_voxel_size(scene.get_depthmaps(raw=True), areas, scene.get_focals()) * scale
+    thresholds = [k * voxel_size for k in (1, 2, 4)] if thresholds is None else list(thresholds)
+    max_dist = 16 * voxel_size if max_dist is None else max_dist
+    pred_cloud = fuse_points(scene.imgs, aligned, pred_mask, scene._im_conf, voxel_size, dev, to_host=False)
+    gt_cloud = fuse_points(scene.imgs, gt, gt_mask, None, voxel_size, dev, to_host=False)
+    details = {}
+    metrics = cloud_metrics(pred_cloud, gt_cloud, max_dist, thresholds, details=details)
+    metrics.update(voxel_size=float(voxel_size), max_dist=float(max_dist), scale=scale)
+    if has_poses:
+        moved = poses.copy()
+        moved[:, :3, :3] = R @ poses[:, :3, :3]
+        moved[:, :3, 3] = poses[:, :3, 3] @ S[:3, :3].T + S[:3, 3]
+        metrics['ate_rmse'], metrics['rot_err_mean_deg'], metrics['rot_err_max_deg'] = pose_errors(moved, gt_poses)
+    if not return_details:
+        return metrics
+    details.update(similarity=S, scale=scale, pred_pts=aligned, gt_pts=gt, pred_mask=pred_mask, gt_mask=gt_mask, pred_cloud=pred_cloud,
+                   gt_cloud=gt_cloud, voxel_size=float(voxel_size), max_dist=float(max_dist), thresholds=[float(x) for x in thresholds])
+    return metrics, details
+
+
+def main(argv=None):
+    """python -m dust3r_amd.evaluation PRED.ply GT.ply --max-dist D [--thresholds T ...]: the dict of cloud_metrics as one JSON line"""
+    import argparse
+    parser = argparse.ArgumentParser(prog='python -m dust3r_amd.evaluation', description='cloud-to-cloud metrics of two PLY files on the GPU')
+    parser.add_argument('pred')
+    parser.add_argument('gt')
+    parser.add_argument('--max-dist', type=float, required=True, help='distances beyond it are outliers')
+    parser.add_argument('--thresholds', type=float, nargs='*', default=None, help='precision / recall distances (default: max-dist / 16, / 8, / 4)')
+    args = parser.parse_args(argv)
+    from .cloud_metrics import cloud_metrics
+    from .export import read_ply
+    clouds = [read_ply(p)['positions'] for p in (args.pred, args.gt)]
+    thresholds = [args.max_dist / 16, args.max_dist / 8, args.max_dist / 4] if args.thresholds is None else args.thresholds
+    print(json.dumps(cloud_metrics(clouds[0], clouds[1], args.max_dist, thresholds)))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

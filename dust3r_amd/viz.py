@@ -165,6 +165,12 @@ class FusedCloud:
         from .export import write_ply
         return write_ply(path, *(_to_numpy(a) for a in (self.positions, self.colors, self.weight, self.count)))
 
+    def distance_to(self, other, max_dist, to_host=True):
+        """(d2, idx) of every point of this cloud in `other` (a FusedCloud or (N, 3) points) within max_dist: squared distances (+inf where
+        there is none) and rows of `other` (-1); cloud_metrics.nearest_in_cloud on the GPU."""
+        from .cloud_metrics import nearest_in_cloud
+        return nearest_in_cloud(self, other, max_dist, to_host=to_host)
+
 
 def check_voxel_size(voxel_size):
     """voxel_size as np.float32; ValueError unless it is a normal positive fp32."""

@@ -463,6 +463,46 @@ int d3r_fuse_voxels(int n_views, const float* pts, const uint8_t* mask, const fl
                     const int* img_w_dev, int row, const float* lo, float voxel, const int* bits, int capacity, float* positions_out,
                     uint32_t* colors_out, float* weight_out, int* count_out, long long* totals_out, void* workspace, void* stream);
 
+/* Cloud-to-cloud metrics (new; csrc/cloud_nn.hip): the truncated exact nearest neighbour of every point of a query cloud in a reference
+ * cloud, and the sums and counts of the distances. ref [n_ref][3] and query [n_query][3] DEVICE fp32, 1 <= n <= 2^31 - 1. A point is VALID
+ * when its three coordinates are finite. d2(q, p) = (dx dx + dy dy) + dz dz with dx = q_x - p_x, ..., every operation a separate IEEE
+ * fp32 rounding (no contraction). r a positive fp32 whose square r2 = r r (fp32) is a NORMAL number, about 1.1e-19 <= r <= 1.8e19: with a
+ * subnormal, zero or infinite r2 the test d2 <= r2 would accept points whose coordinates lie far beyond r, and the call refuses such an r.
+ * THE RESULT: for a valid query q, idx_out[q] = the lowest index i among the valid reference points that minimise d2(q, R_i), provided that
+ *   minimum is <= r2, and d2_out[q] = that minimum; otherwise, and for an invalid query, idx_out[q] = -1 and d2_out[q] = +inf. This is what
+ *   an fp32 brute force over all pairs gives, bit for bit in d2 and idx; the grid below only limits which pairs are evaluated.
+ * d3r_cloud_grid_build: lo [3] and bits [3] are HOST arrays read during the call. lo = the minimum of the valid reference points (bounds_out
+ *   [0..3) of d3r_fuse_bounds), cell a positive finite fp32, bits_c = the bit length of floorf((max_c - lo_c) / cell), at least 1, at most 21.
+ *   The valid reference points get the key of d3r_fuse_voxels (voxel = cell), are sorted by it with the same stable radix sort, and are
+ *   stored in that order as (x, y, z, index) with the key and the first point of every cell. The grid lives in `workspace` until the next
+ *   build; exactness does not depend on cell (a large cell is slower: every query walks the points of the cells it touches).
+ * d3r_cloud_nearest: the same n_ref, lo, cell, bits and workspace as the build before it. Per axis a query a searches the cells from
+ *   q(nextafter(a_c - r', -inf)) to q(nextafter(a_c + r', +inf)), r' = r (1 + 2^-10) in fp32, q(x) = floorf((x - lo_c) / cell) clamped to
+ *   [0, 2^bits_c - 1]: q is monotone, and every reference point with d2 <= r2 has each coordinate inside the padded interval, so it lies in a
+ *   searched cell. A query whose interval ends below cell 0 or begins above cell 2^bits_c - 1 on some axis evaluates nothing -- exact when lo
+ *   and bits are the ones stated above. The queries are processed in the order of their own cell keys; results go to their original rows.
+ *   only_unresolved = 0: every row of d2_out / idx_out is written. only_unresolved != 0: the rows with idx_out[q] >= 0 on entry are kept
+ *   and their queries are not searched (the radius ladder of dust3r_amd/cloud_metrics.py); the other rows are written.
+ *   evals (optional, DEVICE int [n_query]): evals[q] += the distances evaluated for q in this call.
+ *   workspace: d3r_cloud_grid_workspace_bytes(n_ref, n_query) bytes of DEVICE memory (0 for invalid sizes), n_query the largest query
+ *   cloud asked of this grid (the build itself does not depend on it).
+ * d3r_cloud_distance_stats: over rows q < n of d2 / idx as written above, tau [n_tau] a HOST array, 0 <= n_tau <= D3R_CLOUD_MAX_THRESHOLDS,
+ *   every tau_j a finite fp32 >= 0. counts_out [2 + D3R_CLOUD_MAX_THRESHOLDS] DEVICE int64 = { n_valid (the valid points of query [n][3];
+ *   query NULL: n), n_found (idx >= 0), count_j = found rows with d2 <= tau_j tau_j (fp32 product), 0 for j >= n_tau }; sums_out [2] DEVICE
+ *   fp64 = { sum_d = sum of sqrt((double)d2) (IEEE square root), sum_d2 = sum of (double)d2 } over the found rows. Per-workgroup partials of
+ *   a fixed launch shape, then one workgroup in index order: the same bytes on every run. workspace:
+ *   d3r_cloud_distance_stats_workspace_bytes(n) bytes of DEVICE memory. The lower median of d2 over the found rows is d3r_masked_median's.
+ * No atomics and no waiting between workgroups. D3R_ERR_INVALID on NULL, non-positive sizes, r r not a normal fp32, cell not positive finite, bits outside
+ * [1, 21], lo not finite, n_tau or a tau out of range; nothing is launched then. No allocation, no synchronisation. */
+#define D3R_CLOUD_MAX_THRESHOLDS 8
+size_t d3r_cloud_grid_workspace_bytes(int n_ref, int n_query);
+int d3r_cloud_grid_build(int n_ref, const float* ref, const float* lo, float cell, const int* bits, void* workspace, void* stream);
+int d3r_cloud_nearest(int n_ref, int n_query, const float* query, float r, const float* lo, float cell, const int* bits, int only_unresolved,
+                      float* d2_out, int* idx_out, int* evals, void* workspace, void* stream);
+size_t d3r_cloud_distance_stats_workspace_bytes(int n);
+int d3r_cloud_distance_stats(int n, const float* query, const float* d2, const int* idx, int n_tau, const float* tau, long long* counts_out,
+                             double* sums_out, void* workspace, void* stream);
+
 /* The depth / confidence gallery of the demo (the end of get_reconstructed_scene, dust3r/demo.py:168-184) for n images in one call.
  * depth, conf [n][max_area] DEVICE fp32 (a scene's padded stacks), npix_dev [n] DEVICE int: the pixel count of each image (a count that is
  * negative or above max_area makes its image empty); what lies behind a count is neither read into a result nor written. table [257][4]
