@@ -729,13 +729,7 @@ template <int ODT, bool DMA, bool SC> static hipError_t launch_x3_v2p(const Attn
     constexpr int LDS = DMA ? 4 * 64 * 256 : 2 * 64 * (256 + 16) + 2 * 64 * (256 + 8);
     constexpr int QPB = ATTN_X3_NW * 32;
     static std::atomic<unsigned long long> attr_done{0};
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    const unsigned long long dev_bit = 1ull << (dev_id & 63);
-    if (!(attr_done.load(std::memory_order_relaxed) & dev_bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x3_kernel<ODT, DMA, SC>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_done.fetch_or(dev_bit, std::memory_order_relaxed);
-    }
+    raise_dynamic_lds_once(attr_done, reinterpret_cast<const void*>(attention_x3_kernel<ODT, DMA, SC>), LDS);
     const int grid = p.B * p.H * ((p.Nq + QPB - 1) / QPB);
     hipLaunchKernelGGL((attention_x3_kernel<ODT, DMA, SC>), dim3(grid), dim3(ATTN_X3_NW * 64), LDS, s, p);
     return hipGetLastError();
@@ -753,16 +747,8 @@ template <int ODT> static hipError_t launch_x3_v2(const AttnParams& p, hipStream
 }
 
 template <int DT, int ODT = DT> static hipError_t launch_t(const AttnParams& p, hipStream_t s) {
-    // the dynamic-LDS limit is a per-device function attribute: raise it once on every device this process launches on
     static std::atomic<unsigned long long> attr_done{0};
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    const unsigned long long dev_bit = 1ull << (dev_id & 63);
-    if (!(attr_done.load(std::memory_order_relaxed) & dev_bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<DT, ODT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  AttnCfg<DT>::LDS);
-        attr_done.fetch_or(dev_bit, std::memory_order_relaxed);
-    }
+    raise_dynamic_lds_once(attr_done, reinterpret_cast<const void*>(attention_kernel<DT, ODT>), AttnCfg<DT>::LDS);
     const int grid = p.B * p.H * ((p.Nq + 127) / 128);
     hipLaunchKernelGGL((attention_kernel<DT, ODT>), dim3(grid), dim3(256), AttnCfg<DT>::LDS, s, p);
     return hipGetLastError();

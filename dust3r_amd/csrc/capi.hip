@@ -19,8 +19,7 @@ extern "C" int d3r_layernorm(const float* x, const float* gamma, const float* be
 extern "C" int d3r_linear(const void* act, const void* wgt, const float* bias, void* out, const float* residual, int M, int N, int K, int epilogue,
                           int dtype, void* stream) {
     if (!act || !wgt || !out || N % 4 != 0) return D3R_ERR_INVALID;
-    GemmParams p;
-    p.act = act; p.lda = K; p.wgt = wgt; p.bias = bias; p.M = M; p.K = K; p.n_pad = rup(N, 128); p.n_rows = rup(N, 256); p.n_store = N;      // the engine's weight loader allocates rows the same way (engine.hip: Lin / ConvW)
+    GemmParams p = linear_gemm_params(act, K, wgt, bias, M, N, K);
     p.epi = epilogue == 1 ? EPI_F32 : (epilogue == 2 ? EPI_GELU : EPI_T);
     p.out = out; p.ldo = N; p.res1 = epilogue == 1 ? residual : nullptr; p.ldr = N;
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
@@ -31,8 +30,7 @@ extern "C" int d3r_linear(const void* act, const void* wgt, const float* bias, v
 extern "C" int d3r_linear_x3res(const void* act, const void* wgt, const float* bias, void* out_rows, const void* residual_rows, float* ln_part, int M, int N,
                                 int K, void* stream) {
     if (!act || !wgt || !out_rows || N % 8 != 0) return D3R_ERR_INVALID;
-    GemmParams p;
-    p.act = act; p.lda = K; p.wgt = wgt; p.bias = bias; p.M = M; p.K = K; p.n_pad = rup(N, 128); p.n_rows = rup(N, 256); p.n_store = N;
+    GemmParams p = linear_gemm_params(act, K, wgt, bias, M, N, K);
     p.epi = EPI_F32; p.flags = GF_X3RES; p.res1 = residual_rows; p.ldr = N; p.out2 = out_rows; p.ldo2 = N; p.ln_part = ln_part;
     return rc_of(launch_gemm(D3R_F16X3, p, (hipStream_t)stream));
 }
@@ -43,16 +41,15 @@ extern "C" int d3r_rope_table(float* table, int max_pos, float base, float F0, v
 }
 
 // The shape half of an EPI_HEADS launch (d3r_linear_heads, d3r_linear_heads_tile_config): the argument checks of the header, then the GemmParams
-// fields the tile heuristic reads. Weight rows as d3r_linear allocates them.
-static bool heads_shape(GemmParams& p, int dtype, int M, int K, int n_regions, int head_c, const int* kinds, int heads, int ntok, int tok_w, int ldv, int max_pos) {
+// fields the dispatch reads. Weight rows as d3r_linear allocates them.
+static bool heads_shape(GemmParams& p, const void* act, const void* wgt, const float* bias, int dtype, int M, int K, int n_regions, int head_c, const int* kinds, int heads, int ntok, int tok_w, int ldv, int max_pos) {
     if (dtype != D3R_BF16 && dtype != D3R_F16 && dtype != D3R_F32 && dtype != D3R_F16X3 && dtype != D3R_F16F8 && dtype != D3R_F16X2F8) return false;
     if (M <= 0 || K <= 0 || n_regions < 1 || n_regions > 3 || !kinds || heads <= 0 || head_c != heads * 64 || ntok <= 0 || tok_w <= 0) return false;
     if (M % ntok != 0 || ntok % tok_w != 0 || (ntok / tok_w > tok_w ? ntok / tok_w : tok_w) > max_pos) return false;
     if (ldv < rup(ntok, 64) || ldv % 64 != 0) return false;
     for (int r = 0; r < n_regions; ++r)
         if (kinds[r] != HEAD_ROPE && kinds[r] != HEAD_VT && kinds[r] != HEAD_PLAIN) return false;
-    const int N = n_regions * head_c;
-    p.lda = K; p.M = M; p.K = K; p.n_pad = rup(N, 128); p.n_rows = rup(N, 256); p.n_store = N;
+    p = linear_gemm_params(act, K, wgt, bias, M, n_regions * head_c, K);
     p.epi = EPI_HEADS; p.head_c = head_c; p.heads = heads; p.ntok = ntok; p.tok_w = tok_w; p.ldv = ldv;
     for (int r = 0; r < n_regions; ++r) p.head_kind[r] = kinds[r];
     return true;
@@ -64,13 +61,13 @@ extern "C" int d3r_linear_heads(const void* act, const void* wgt, const float* b
                                 int sk_cnt_n, int dtype, void* stream) {
     if (!act || !wgt || !dsts || !rope_table) return D3R_ERR_INVALID;
     GemmParams p;
-    if (!heads_shape(p, dtype, M, K, n_regions, head_c, kinds, heads, ntok, tok_w, ldv, max_pos)) return D3R_ERR_INVALID;
+    if (!heads_shape(p, act, wgt, bias, dtype, M, K, n_regions, head_c, kinds, heads, ntok, tok_w, ldv, max_pos)) return D3R_ERR_INVALID;
     for (int r = 0; r < n_regions; ++r) {
         if (!dsts[r]) return D3R_ERR_INVALID;
         p.head_dst[r] = dsts[r];
     }
     if ((ln_rstd || ln_nmr || ln_colsum || ln_part_in) && (dtype != D3R_F16X3 || !ln_rstd || !ln_nmr || !ln_colsum)) return D3R_ERR_INVALID;
-    p.act = act; p.wgt = wgt; p.bias = bias; p.rope_table = rope_table;
+    p.rope_table = rope_table;
     if (ln_rstd) { p.ln_rstd = ln_rstd; p.ln_nmr = ln_nmr; p.ln_colsum = ln_colsum; p.ln_part_in = ln_part_in; p.ln_eps = ln_eps; p.ln_inv_c = 1.0f / (float)K; }
     if (sk_slab && sk_cnt) { p.splitk = 0; p.sk_slab = sk_slab; p.sk_slab_floats = sk_slab_floats; p.sk_cnt = sk_cnt; p.sk_cnt_n = sk_cnt_n; }      // launch_gemm decides whether it splits (engine.hip gemm_linear)
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
@@ -80,11 +77,9 @@ extern "C" int d3r_linear_heads_tile_config(int M, int K, int n_regions, int hea
                                             int dtype) {
     static const float dummy = 0.f;
     GemmParams p;
-    if (!heads_shape(p, dtype, M, K, n_regions, head_c, kinds, heads, ntok, tok_w, ldv, max_pos)) return D3R_ERR_INVALID;
-    p.act = &dummy; p.wgt = &dummy;      // (never dereferenced)
-    p.flags |= gemm_env_flags(p);
-    const int cfg = gemm_pick_config(p, dtype);
-    return cfg == GEMM_CFG_128 && gemm_runs_128w8(p, dtype) ? D3R_TILE_128W8 : cfg;
+    if (!heads_shape(p, &dummy, &dummy, nullptr, dtype, M, K, n_regions, head_c, kinds, heads, ntok, tok_w, ldv, max_pos)) return D3R_ERR_INVALID;      // (operands never dereferenced)
+    const GemmPlan plan = gemm_plan_for(p, dtype);
+    return plan.w8 ? D3R_TILE_128W8 : plan.cfg;
 }
 
 extern "C" int d3r_conv_k_slice_major(void) { return 1; }
@@ -93,11 +88,7 @@ extern "C" int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bia
                                int B, int Hin, int Win, int Cin, int Cout, int ksize, int stride, int pad, int relu, const void* zero_page, int dtype,
                                void* stream) {
     if (!in || !wgt || !out || !zero_page || Cout % 4 != 0) return D3R_ERR_INVALID;
-    GemmParams p;
-    p.amode = AMODE_CONV; p.act = in; p.wgt = wgt; p.bias = bias;
-    p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.cstride = Cin; p.ksize = ksize; p.stride = stride; p.pad = pad;
-    p.Hout = (Hin + 2 * pad - ksize) / stride + 1; p.Wout = (Win + 2 * pad - ksize) / stride + 1;
-    p.M = B * p.Hout * p.Wout; p.K = ksize * ksize * Cin; p.n_pad = rup(Cout, 128); p.n_rows = rup(Cout, 256); p.n_store = Cout; p.zero_page = zero_page;
+    GemmParams p = conv_gemm_params(in, B, Hin, Win, Cin, wgt, bias, Cin, Cout, ksize, stride, pad, zero_page);
     p.epi = EPI_T; p.flags = relu ? GF_RELU : 0; p.out = out; p.ldo = Cout; p.res1 = res1; p.res2 = res2; p.ldr = Cout;
     p.out2 = out_relu_copy; p.ldo2 = Cout;
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
@@ -147,9 +138,8 @@ extern "C" int d3r_convt_gemm(const void* act, const void* wgt, const float* bia
     if (!act || !wgt || !out || !conv_dtype(dtype) || B <= 0 || th <= 0 || tw <= 0 || ksize <= 0) return D3R_ERR_INVALID;
     if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || lda < cin_pad || cout_pad <= 0 || cout_pad % 4 != 0 || ldo < cout_pad) return D3R_ERR_INVALID;
     const int N = ksize * ksize * cout_pad;
-    GemmParams p;      // engine.hip run_dpt, the EPI_CONVT launch
-    p.act = act; p.lda = lda; p.wgt = wgt; p.bias = bias; p.M = B * th * tw; p.K = cin_pad;
-    p.n_pad = rup(N, 128); p.n_rows = rup(N, 256); p.n_store = N; p.epi = EPI_CONVT; p.ksize = ksize; p.ct_cout = cout_pad;
+    GemmParams p = linear_gemm_params(act, lda, wgt, bias, B * th * tw, N, cin_pad);      // engine.hip run_dpt, the EPI_CONVT launch
+    p.epi = EPI_CONVT; p.ksize = ksize; p.ct_cout = cout_pad;
     p.Hin = th; p.Win = tw; p.out = out; p.ldo = ldo;
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
 }
@@ -162,8 +152,9 @@ extern "C" int d3r_conv_head4(const void* in, const void* wgt, const float* bias
     GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, wgt, bias, cin_pad, Cout, ksize, 1, 1, zero_page);      // engine.hip conv_head4()
     p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = conf_stride; p.res1 = w4; p.res2 = b4;
     if (!post_mode(p.post, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
-    if (head4_tile(p, dtype) < 0) return D3R_DECLINED;
-    return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
+    GemmPlan plan;
+    if (!head4_tile(p, dtype, plan)) return D3R_DECLINED;
+    return rc_of(launch_gemm(dtype, p, plan, (hipStream_t)stream));
 }
 
 extern "C" int d3r_head_final(const void* feat, int C, const float* w4, const float* b4, float* pts, float* conf, size_t npix, int pstride, int conf_stride,
@@ -204,17 +195,16 @@ extern "C" int d3r_gemm_set_trace(void* buf, size_t capacity_blocks) {
 // 0: there is one build flavour, without the ablation kernels of earlier rounds; kept for the C ABI
 extern "C" int d3r_build_has_probes(void) { return 0; }
 
-// Diagnostics, host only (no GPU, no launch): the tile configuration the heuristic of gemm.hip picks for an nn.Linear-shaped problem
+// Diagnostics, host only (no GPU, no launch): the tile configuration of the plan (gemm_plan.hpp) that d3r_linear runs for an nn.Linear-shaped problem
 // (same `epilogue` codes as d3r_linear; with_residual: an fp32 residual is added). The dispatch table of DESIGN.md section 4.1 as a function.
 extern "C" int d3r_gemm_tile_config(int dtype, int M, int N, int K, int epilogue, int with_residual) {
     if (M <= 0 || N <= 0 || K <= 0 || N % 4 != 0) return D3R_ERR_INVALID;
     if (dtype != D3R_BF16 && dtype != D3R_F16 && dtype != D3R_F32 && dtype != D3R_F16X3 && dtype != D3R_F16F8 && dtype != D3R_F16X2F8) return D3R_ERR_INVALID;
     static const float dummy = 0.f;
-    GemmParams p;
-    p.lda = K; p.M = M; p.K = K; p.n_pad = rup(N, 128); p.n_rows = rup(N, 256); p.n_store = N;      // the engine's weight loader allocates rows the same way (engine.hip: Lin / ConvW)
+    GemmParams p = linear_gemm_params(&dummy, K, &dummy, nullptr, M, N, K);      // (never dereferenced: the rules only ask whether the operands exist)
     p.epi = epilogue == 1 ? EPI_F32 : (epilogue == 2 ? EPI_GELU : EPI_T);
     p.res1 = (epilogue == 1 && with_residual) ? &dummy : nullptr;
-    p.act = &dummy; p.wgt = &dummy; p.out = const_cast<float*>(&dummy);      // (never dereferenced: the rule only asks whether the operands exist)
-    return gemm_pick_config(p, dtype);
+    p.out = const_cast<float*>(&dummy);
+    return gemm_plan_for(p, dtype).cfg;
 }
 

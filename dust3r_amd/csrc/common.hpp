@@ -21,6 +21,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #define D3R_BF16 0
 #define D3R_F16 1
 #define D3R_F32 2
@@ -500,3 +502,31 @@ static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline int rc_of(hipError_t e) { return e == hipSuccess ? 0 : 1000 + (int)e; }   // the C ABI's code of a HIP status (include/dust3r_hip.h: D3R_OK = 0, 1000 + hipError_t)
 static inline size_t dt_bytes(int dt) { return (dt == D3R_F32 || dt == D3R_F16X3 || dt == D3R_F16F8 || dt == D3R_F16X2F8) ? 4 : 2; }   // bytes per logical element of an ACTIVATION row
 static inline size_t wgt_bytes(int dt) { return dt == D3R_F16X2F8 ? 5 : dt_bytes(dt); }                                                  // ... of a WEIGHT row
+
+// ---- host side, per device of this process ----------------------------------------------------------------------------------
+// compute units of the current device, cached per device id (the whole-rounds rules of the GEMM dispatch and the persistent kernel's grid are about THIS chip's
+// CU count, not a constant; 256, the MI355X's, where no device answers)
+inline int device_cus() {
+    static std::atomic<int> cache[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const int slot = dev & 63;
+    int v = cache[slot].load(std::memory_order_relaxed);
+    if (v <= 0) {
+        int q = 0;
+        v = (hipDeviceGetAttribute(&q, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && q > 0) ? q : 256;
+        cache[slot].store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
+// the dynamic-LDS limit is a per-device attribute of a kernel function: raise it once on every device this process launches `kernel` on. `done`: that kernel
+// instantiation's own flag, one bit per device id.
+inline void raise_dynamic_lds_once(std::atomic<unsigned long long>& done, const void* kernel, int bytes) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(done.load(std::memory_order_relaxed) & bit)) {
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        done.fetch_or(bit, std::memory_order_relaxed);
+    }
+}

@@ -425,8 +425,9 @@ void gemm_linear(Ctx& c, const void* act, int lda, const Lin& L, int M, int epi,
             p.splitk = 0; p.sk_slab = c.m->sk_slab[sset]; p.sk_cnt = c.m->sk_cnt[sset]; p.sk_slab_floats = d3r_model::SK_SLAB_FLOATS; p.sk_cnt_n = d3r_model::SK_CNT;
         }
     }
-    c.mark(prf_kind((L.dt == D3R_F16F8 || L.dt == D3R_F16X2F8) ? PRF_GEMM_F8 : PRF_GEMM, gemm_pick_config(p, L.dt)), 2.0 * M * (double)L.N * L.K, M, L.N, L.K);
-    c.chk(launch_gemm(L.dt, p, c.st));
+    const GemmPlan plan = gemm_plan_for(p, L.dt);
+    c.mark(prf_kind((L.dt == D3R_F16F8 || L.dt == D3R_F16X2F8) ? PRF_GEMM_F8 : PRF_GEMM, plan.cfg), 2.0 * M * (double)L.N * L.K, M, L.N, L.K);
+    c.chk(launch_gemm(L.dt, p, plan, c.st));
 }
 
 void gemm_heads(Ctx& c, const void* act, int lda, const Lin& L, int M, int head_c, int nreg, const int* kinds, void* const* dsts, int heads,
@@ -437,8 +438,9 @@ void gemm_heads(Ctx& c, const void* act, int lda, const Lin& L, int M, int head_
     p.epi = EPI_HEADS; p.head_c = head_c;
     for (int i = 0; i < nreg; ++i) { p.head_kind[i] = kinds[i]; p.head_dst[i] = dsts[i]; }
     p.heads = heads; p.ntok = ntok; p.tok_w = tok_w; p.ldv = ldv; p.rope_table = c.m->rope_table;
-    c.mark(prf_kind((L.dt == D3R_F16F8 || L.dt == D3R_F16X2F8) ? PRF_GEMM_F8 : PRF_GEMM, gemm_pick_config(p, L.dt)), 2.0 * M * (double)L.N * L.K, M, L.N, L.K);
-    c.chk(launch_gemm(L.dt, p, c.st));
+    const GemmPlan plan = gemm_plan_for(p, L.dt);
+    c.mark(prf_kind((L.dt == D3R_F16F8 || L.dt == D3R_F16X2F8) ? PRF_GEMM_F8 : PRF_GEMM, plan.cfg), 2.0 * M * (double)L.N * L.K, M, L.N, L.K);
+    c.chk(launch_gemm(L.dt, p, plan, c.st));
 }
 
 void conv(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const ConvW& w, int stride, int pad, void* out, int ldo,
@@ -446,8 +448,9 @@ void conv(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const Co
     GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, w.w, w.b, w.cin_pad, w.Cout, w.k, stride, pad, c.m->zero_page);   // K, n_pad, n_rows: reg_conv's
     if (n_store >= 0) p.n_store = n_store;
     p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.res1 = res1; p.res2 = res2; p.ldr = ldo; p.out2 = out2; p.ldo2 = ldo;
-    c.mark(prf_kind(PRF_CONV, gemm_pick_config(p, c.m->dt)), 2.0 * p.M * (double)w.Cout * w.k * w.k * w.Cin, p.M, w.Cout, w.k * w.k * w.Cin);
-    c.chk(launch_gemm(c.m->dt, p, c.st));
+    const GemmPlan plan = gemm_plan_for(p, c.m->dt);
+    c.mark(prf_kind(PRF_CONV, plan.cfg), 2.0 * p.M * (double)w.Cout * w.k * w.k * w.Cin, p.M, w.Cout, w.k * w.k * w.Cin);
+    c.chk(launch_gemm(c.m->dt, p, plan, c.st));
 }
 
 // 3x3 convolution (stride 1, pad 1) + ReLU + Conv2d(Cout, 4, 1) + postprocess in one launch (EPI_HEAD4); false (nothing launched) when
@@ -456,10 +459,10 @@ bool conv_head4(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, co
                 float* pts, float* conf, int pstride, int cstride_conf) {
     GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, w.w, w.b, w.cin_pad, w.Cout, w.k, 1, 1, c.m->zero_page);
     p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = cstride_conf; p.res1 = w4; p.res2 = b4; p.post = c.m->post;
-    const int cfg = head4_tile(p, c.m->dt);      // 512 x 128, else the forced 256 x 128 R (kernels.hpp)
-    if (cfg < 0) return false;
-    c.mark(prf_kind(PRF_CONV, cfg), 2.0 * p.M * (double)w.Cout * w.k * w.k * w.Cin, p.M, w.Cout, w.k * w.k * w.Cin);
-    c.chk(launch_gemm(c.m->dt, p, c.st));
+    GemmPlan plan;
+    if (!head4_tile(p, c.m->dt, plan)) return false;      // 512 x 128, else the forced 256 x 128 R (kernels.hpp)
+    c.mark(prf_kind(PRF_CONV, plan.cfg), 2.0 * p.M * (double)w.Cout * w.k * w.k * w.Cin, p.M, w.Cout, w.k * w.k * w.Cin);
+    c.chk(launch_gemm(c.m->dt, p, plan, c.st));
     return true;
 }
 
@@ -706,8 +709,9 @@ void run_dpt(Ctx& c, const DptHead& D, Arena ar, const void* const hooks[4], con
             p.n_pad = D.convt[i].n_pad; p.n_rows = D.convt[i].n_rows; p.n_store = D.convt[i].N; p.epi = EPI_CONVT; p.ksize = D.convt_k[i]; p.ct_cout = D.convt_coutp[i];
             p.Hin = th; p.Win = tw; p.out = cmap[i]; p.ldo = D.cstride[i];
             const int ldi[2] = {96, 192};
-            c.mark(prf_kind(PRF_CONV, gemm_pick_config(p, m->dt)), 2.0 * p.M * (double)(D.convt_k[i] * D.convt_k[i] * ldi[i]) * ldi[i], p.M, D.convt_k[i] * D.convt_k[i] * ldi[i], ldi[i]);
-            c.chk(launch_gemm(m->dt, p, c.st));
+            const GemmPlan plan = gemm_plan_for(p, m->dt);
+            c.mark(prf_kind(PRF_CONV, plan.cfg), 2.0 * p.M * (double)(D.convt_k[i] * D.convt_k[i] * ldi[i]) * ldi[i], p.M, D.convt_k[i] * D.convt_k[i] * ldi[i], ldi[i]);
+            c.chk(launch_gemm(m->dt, p, plan, c.st));
         } else if (i == 3) {
             conv(c, t1, B, th, tw, D.cstride[3], D.act3conv, 2, 1, cmap[3], D.cstride[3], 0);
         }

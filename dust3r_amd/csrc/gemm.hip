@@ -8,11 +8,19 @@
 //   GEMMs over NHWC activations, and LinearPts3d.proj (dust3r/heads/linear_head.py:30-41).
 //
 // Shape: out[m][n] = sum_k act[m][k] * wgt[n][k]   ("NT": both operands K-contiguous).
-// Tile configurations (template Cfg; 128 bytes of K per step = 64 bf16; 16x16x32 MFMA fragments):
-//   256 x 256, 8 waves (2 x 4), each wave 128 (n) x 64 (m) = 8 x 4 fragments   -- the large-GEMM shape
-//   256 x 128, 8 waves, each wave 64 x 64                                       -- mid-size problems
-//   512 x 128, 8 waves (1 x 8), each wave 128 (n) x 64 (m)                      -- N <= 128 convolutions (DPT head)
-//   128 x 128, 4 waves (2 x 2), each wave 64 x 64, 2 blocks per CU              -- small problems / tails
+// Tile configurations (template Cfg; 128 bytes of K per step = 64 bf16; 16x16x32 MFMA fragments; M x N below, GEMM_CFG_* code in brackets):
+//   256 x 256, 8 waves (2 x 4), each wave 128 (n) x 64 (m) = 8 x 4 fragments   -- the large-GEMM shape [1]
+//   256 x 128, 8 waves, each wave 64 x 64                                       -- mid-size problems [2]
+//   512 x 128, 8 waves (1 x 8), each wave 128 (n) x 64 (m)                      -- N <= 128 convolutions (DPT head) [3]
+//   128 x 128, 4 waves (2 x 2), each wave 64 x 64, 2 blocks per CU              -- small problems / tails [0]
+//   the first three with the DMA pieces interleaved with the MFMA rows          -- fp16 + fp8 rows (Cfg*il)
+//  split-fp16 only:
+//   256 x 128 R, 4 waves of 128 (n) x 64 (m), weight rows in registers, 2 blocks per CU   -- fp32-residual projections at K <= 1024; the fused head tail [7]
+//   64 x 64, 4 waves of 32 x 32, three-slot ring                                -- the small-batch forwards [8]
+//   96 x 64, 4 waves of 32 (n) x 48 (m), three-slot ring                        -- their long K loops [11]
+//   128 x 128 by 8 waves of 64 (n) x 32 (m)                                     -- 128 x 128 launches of fewer than 1100 tiles [0, D3R_TILE_128W8]
+//   384 x 192, 8 waves of 192 (n) x 48 (m)                                      -- the decoder's 24576-row GEMMs: whole rounds of the CUs [9]
+// The persistent 256 x 128 kernel [10] is gemm_p4.hip; which launch takes which shape is decided in gemm_plan.hpp.
 // Operands go HBM/L2 -> LDS with global_load_lds_dwordx4 (no VGPR round trip), double buffered; the LDS image is
 // lane-linear, the bank swizzle (chunk ^= (row>>1)&7, conflict-free for ds_read_b128 on 128-byte rows) is applied
 // on the per-lane SOURCE address and again on the fragment read.
@@ -90,7 +98,7 @@ typedef GemmCfg<2, 2, 2, 3, 4, 128, 3> Cfg96x64;
 typedef GemmCfg<2, 4, 4, 2, 4> Cfg128w8;
 // M 384 x N 192 by eight waves stacked along m, each 192 (n) x 48 (m) = 12 x 3 fragments (144 accumulators; 147 KiB of LDS): the decoder's 24576-row GEMMs with
 // N = 768 / 1536 / 2304 / 3072 are exactly 1 / 2 / 3 / 4 rounds of 256 CUs on it (128 x 128: 1152 tiles = 2.25 rounds of 512 slots). Round 4; tile configuration 9,
-// chosen by gemm_pick_config. Same K order per output element as every other shape: bit-identical results.
+// chosen by gemm_plan. Same K order per output element as every other shape: bit-identical results.
 typedef GemmCfg<1, 8, 12, 3, 2> Cfg384x192;
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -1514,178 +1522,25 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
     }
 }
 
-// ---- host side: configuration choice + launch ------------------------------------------------------------------
+// ---- host side: the plan of a launch (gemm_plan.hpp) under this process's environment and device, and its dispatch ------------------
 template <int DT, class CF> static hipError_t launch_cfg(const GemmParams& p, hipStream_t s) {
-    // the dynamic-LDS limit is a per-device function attribute: raise it once on every device this process launches on
     static std::atomic<unsigned long long> attr_done{0};
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    const unsigned long long dev_bit = 1ull << (dev_id & 63);
-    if (!(attr_done.load(std::memory_order_relaxed) & dev_bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<DT, CF>), hipFuncAttributeMaxDynamicSharedMemorySize, CF::LDS);
-        attr_done.fetch_or(dev_bit, std::memory_order_relaxed);
-    }
+    raise_dynamic_lds_once(attr_done, reinterpret_cast<const void*>(gemm_kernel<DT, CF>), CF::LDS);
     const int grid = cdiv(p.M, CF::BM) * cdiv(p.n_store, CF::BN) * (p.splitk > 1 ? p.splitk : 1);
     hipLaunchKernelGGL((gemm_kernel<DT, CF>), dim3(grid), dim3(CF::NT), CF::LDS, s, p);
     return hipGetLastError();
 }
 
-// (A persistent variant -- resident blocks walking several tiles and prefetching the next tile's first K step across the
-// epilogue -- was measured 5-10 % slower on MI355X, profiles/r01_call4: on gfx9 vmcnt also counts the epilogue's stores, so
-// the next tile's first wait drains them, which a fresh block never does. One block per tile it is.)
-// Tile configuration choice, from measurements on MI355X (tools/gpu_probe.py gemm, profiles/): the 256x256 tile wins
-// once there are at least ~3 full rounds of 256 resident blocks (M = 49152: 760-1070 vs 640-830 TF/s), the 128x128 tile
-// (2 blocks per CU: one block's prologue / epilogue hides behind the other's K loop) wins below that; N <= 128 problems
-// (DPT head convolutions) take the 512x128 / 256x128 tiles so that no half-empty 256-wide tile is computed.
-static int pick_config_raw(const GemmParams& p, int dt);
-// compute units of the current device, cached per device id (the whole-rounds rules below are about THIS chip's CU count, not a constant)
-static int device_cus() {
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int slot = dev & 63;
-    int v = cache[slot].load(std::memory_order_relaxed);
-    if (v <= 0) {
-        int q = 0;
-        v = (hipDeviceGetAttribute(&q, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && q > 0) ? q : 256;
-        cache[slot].store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-// the tile configuration a launch of (p, dt) RUNS on -- what the engine's profile records and d3r_gemm_tile_config reports: the heuristic's
-// choice, then the remaps launch_t applies for operand types that do not have every shape
-static int device_cus();
-// D3R_GEMM_CFG=0..9: the tile configuration pinned from the environment (parity tests, A/B runs); read per call, -1 = not set
-static int env_forced_cfg() {
-    const char* e = getenv("D3R_GEMM_CFG");
-    if (!e || e[0] < '0' || e[0] > '9') return -1;
-    if (e[1] == 0) return e[0] - '0';
-    return (e[0] == '1' && e[1] == '1' && e[2] == 0) ? GEMM_CFG_96x64 : -1;
-}
-int gemm_p4_mode() {
-    const char* e = getenv("D3R_GEMM_PERSIST");
-    return e ? (e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1)) : -1;
-}
-// persistent kernel (gemm_p4.hip) for this launch? Measured on MI355X inside the 32-pair forward (tools/launch_table.py, profiles/r06_*): it wins where the
-// epilogue is a large share of a tile's life and the tiles fill whole rounds of the CUs -- fc1 + GELU 395 -> 427 (encoder) / 363 -> 398 TFLOP/s (decoder),
-// the typed-residual projections at K <= 1024 348 -> 362, typed stores +4..12 % -- ties at K = 4096 (fc2: the K loop dominates; the one-tile-per-block
-// kernels keep it) and loses where its 256 x 128 tiles leave the last round of CUs mostly empty (the decoder's N = 768 GEMMs: 576 tiles = 2.25 rounds).
-static bool use_p4(const GemmParams& p, int dt) {
-    if (dt != D3R_F16X3 || p.force_cfg >= 0 || env_forced_cfg() >= 0) return false;
-    const int mode = gemm_p4_mode();
-    if (mode == 0 || !gemm_p4_eligible(p, dt)) return false;
-    if (mode == 1) return true;
-    const long tiles = (long)(p.M / 256) * (p.n_store / 128);
-    const int cus = device_cus();
-    const long rounds = (tiles + cus - 1) / cus;
-    if (tiles < cus || tiles * 100 < rounds * cus * 88) return false;      // the last round at least ~half full on average: >= 88 % of the tile slots used
-    if (p.epi == EPI_F32 && p.K > 1024) return false;
-    return true;
-}
-int gemm_pick_config(const GemmParams& p, int dt) {
-    if (use_p4(p, dt)) return GEMM_CFG_P4;
-    int cfg = pick_config_raw(p, dt);
-    if ((cfg == GEMM_CFG_256x128R || cfg == GEMM_CFG_64 || cfg == GEMM_CFG_96x64 || cfg == GEMM_CFG_384x192) && dt != D3R_F16X3) cfg = cfg == GEMM_CFG_256x128R ? GEMM_CFG_256x128 : GEMM_CFG_128;
-    if (dt == D3R_F16X2F8 && cfg != GEMM_CFG_256) cfg = GEMM_CFG_128;      // the 2.5-unit K loop exists on the two square tiles
-    return cfg;
-}
-static int pick_config_raw(const GemmParams& p, int dt) {
-    const int n_rows = p.n_rows > 0 ? p.n_rows : p.n_pad;
-    const bool wide_vt = (dt == D3R_BF16 || dt == D3R_F16) && (p.ntok & 63) == 0 && !(p.flags & GF_NOWIDE);
-    const bool heads = p.epi == EPI_HEADS && !wide_vt;   // "heads" = needs a square tile (operand-role swap for V^T)
-    const bool ok256 = cdiv(p.n_store, 256) * 256 <= n_rows && (p.epi != EPI_HEADS || p.head_c % 256 == 0);
-    int forced = p.force_cfg;
-    if (forced < 0) {   // D3R_GEMM_CFG=0|1|2|3 pins the tile configuration (parity tests, A/B runs); infeasible choices are ignored
-        forced = env_forced_cfg();
-    }
-    // retired shapes: 4 (four-wave 256 x 128) runs on the eight-wave 256 x 128 tile, 5 / 6 (four-stage, ping-pong 256 x 256) on the two-stage one
-    if (forced == GEMM_CFG_256x128W4) forced = GEMM_CFG_256x128;
-    if (forced == GEMM_CFG_256S4 || forced == GEMM_CFG_256PP) forced = GEMM_CFG_256;
-    if (forced == GEMM_CFG_384x192 && dt == D3R_F16X3 && !heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4 && p.amode == AMODE_LINEAR && cdiv(p.n_store, 192) * 192 <= n_rows) return forced;
-    if (forced == GEMM_CFG_96x64 && dt == D3R_F16X3 && !heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4) return forced;
-    if (forced == GEMM_CFG_128 || forced == GEMM_CFG_64 || (forced == GEMM_CFG_256 && ok256) ||
-        ((forced == GEMM_CFG_256x128 || forced == GEMM_CFG_512x128 || forced == GEMM_CFG_256x128R) && !heads))
-        return forced;
-    if (!heads && p.n_store <= 128) {
-        if (cdiv(p.M, 512) >= 512) return GEMM_CFG_512x128;
-        if (cdiv(p.M, 256) >= 512) return GEMM_CFG_256x128;
-        return GEMM_CFG_128;
-    }
-    // split-fp16, nn.Linear launches without attention heads whose (M / 384) x (N / 192) tiles fill whole rounds of the 256 CUs: the decoder's 24576-row
-    // GEMMs at 32 pairs per step (N = 768 / 3072 -> 256 / 1024 tiles; on the 128 x 128 tile 1152 tiles = 2.25 rounds of the 512 slots). Measured
-    // (profiles/r04_i, r04_k). In isolation, us per launch, default tile -> this one: fc2 24576 x 768 x 3072 + residual 389 -> 280, fc1 24576 x 3072 x 768
-    // + GELU 384 -> 364, plain stores 108 -> 88 / 222 -> 161 / 286 -> 224 (N = 768 / 1536 / 2304), the fp32-residual projections at K = 768 90 -> 94.
-    // On the forward the isolated gains mostly vanish (in the network the default tiles run faster than back to back on one shape, and the two decoder
-    // sides overlap their tails on the two streams): every eligible launch on it 194.55 -> 196.75 and 191.7 -> 192.7 pairs/s (two boxes, every run above every
-    // baseline run); WITHOUT the K <= 1024 projections 191.7 -> 190.9 -- so the rule is "every eligible launch".
-    if (dt == D3R_F16X3 && !heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4 && p.amode == AMODE_LINEAR && p.n_store % 192 == 0 && cdiv(p.n_store, 192) * 192 <= n_rows) {
-        const long t384 = (long)cdiv(p.M, 384) * cdiv(p.n_store, 192);
-        const int cus = device_cus();       // whole rounds of THIS device's compute units (256 on MI355X; a partitioned device has fewer)
-        if (t384 >= cus * 9 / 10 && (t384 % cus == 0 || t384 % cus >= cus * 9 / 10)) return GEMM_CFG_384x192;
-    }
-    // split-fp16, launches without attention heads (their V^T regions need a square tile): the two-blocks-per-CU 256 x 128 shape with the
-    // weights of a K step in registers. Measured on MI355X (profiles/r03_c/gemmtrace_cfg7.log, bench_r*.log): it wins where the epilogue
-    // is an HBM burst that the other block's MFMAs can run under -- the fp32-residual projections at K <= 1024 (proj 49152 x 1024 x
-    // 1024: 337 vs 296 TFLOP/s) -- and loses 1-6 % where the epilogue is VALU work (GELU, typed stores: on gfx950 VALU and MFMA of a
-    // SIMD overlap only by half, tools/issue_probe.hip) or the K loop dominates (fc2): default = those projections only.
-    if (dt == D3R_F16X3 && !heads && p.epi != EPI_HEADS && p.n_store > 128) {
-        const long tiles = (long)cdiv(p.M, 256) * cdiv(p.n_store, 128);
-        if (p.epi == EPI_F32 && p.res1 != nullptr && p.K <= 1024 && p.amode == AMODE_LINEAR && tiles >= 1024) return GEMM_CFG_256x128R;
-    }
-    // split-fp16, small problems (the one- and two-pair forwards of dust3r/demo.py:156 / visloc.py:88, batch_size = 1): below ~1.5
-    // 128 x 128 tiles per CU the chip is not full -- the 64 x 64 tile by four waves of 32 x 32 runs the same problem on four times the
-    // waves. The crossover, 200 tiles of 128 x 128, was measured against 400 / 600 / 1000 / 2000 for 1-8 pairs per call: the best or within
-    // noise of it everywhere (profiles/r03_f/latency_small_tiles.log).
-    if (dt == D3R_F16X3 && p.n_store > 128) {
-        if ((long)cdiv(p.M, 128) * cdiv(p.n_store, 128) < 200) {
-            // round 6: M 96 x N 64 instead, where its tiles come to 1.5 ... 2 per CU. The small tiles run at the rate their operand rows arrive: the 96 x 64
-            // shape moves 17 % fewer bytes per flop, but a CU needs two or three resident blocks' worth of loads in flight to keep that rate -- measured on MI355X
-            // (tools/tile_probe.py, profiles/r06_f; 64 x 64 -> 96 x 64, us per launch): 3072 x 1024 x 4096 81 -> 71, 2304 x 1024 x 4096 75 -> 61, 3072 x 768 x 3072 66 -> 53,
-            // 1536 x 1536 x 768 20 -> 18, 768 x 3072 x 768 20 -> 18 (384 or 512 tiles); 1536 x 1024 x 4096 56 -> 61 (256 tiles: one block per CU), 1152 x 768 x 3072 33 -> 40 (144),
-            // 1536 x 2304 x 768 28 -> 30 (576). nn.Linear operands without attention heads only. INSIDE the forward (same process, rule on | off) the
-            // K = 768 / 1024 cases do not carry over -- one pair 10.04 vs 9.96 ms (the decoder's two sides run side by side: twice the tiles in flight), two pairs 14.49 vs
-            // 14.68 -- so the rule keeps the long K loops only (K >= 2048: fc2 of the encoder at two / three pairs, of the decoder at four).
-            const long t96 = (long)cdiv(p.M, 96) * cdiv(p.n_store, 64);
-            const int cus = device_cus();
-            if (!heads && p.epi != EPI_HEADS && p.epi != EPI_HEAD4 && p.amode == AMODE_LINEAR && p.K >= 2048 && t96 * 2 >= (long)cus * 3 && t96 <= (long)cus * 2) return GEMM_CFG_96x64;
-            return GEMM_CFG_64;
-        }
-    }
-    const long tiles256 = (long)cdiv(p.M, 256) * cdiv(p.n_store, 256);
-    // fp16 + fp8 rows: the 256-wide tile is 1.3-1.6x ahead of the 128 x 128 one per tile (its K loop lost a third of its MFMA work, the small
-    // tile's LDS read traffic per MFMA is twice as high), so it pays from a single round of resident blocks on: measured +1.5 % on the
-    // forward with the decoder's 24576 x 768 GEMMs (288 tiles, two such launches side by side on the two streams) on it
-    const long t256 = (dt == D3R_F16F8 || dt == D3R_F16X2F8) ? 250 : 700;
-    if (ok256 && tiles256 >= t256) return GEMM_CFG_256;
-    return GEMM_CFG_128;
-}
-
-bool gemm_runs_128w8(const GemmParams& p, int dt) {
-    if (dt != D3R_F16X3) return false;
-    const char* e = getenv("D3R_GEMM_T128W8");
-    const long t = e ? atol(e) : 1100;
-    return (long)cdiv(p.M, 128) * cdiv(p.n_store, 128) < t;
-}
-int gemm_env_flags(const GemmParams& p) {
-    // (the folded-LayerNorm producer launches keep their wide epilogue: it is where the row sums and the typed residual stream are written)
-    if (const char* e = getenv("D3R_GEMM_NOWIDE")) if (e[0] == '1' && !p.ln_part && !(p.flags & GF_X3RES)) return GF_NOWIDE;
-    return 0;
-}
-
-template <int DT> static hipError_t launch_t(const GemmParams& p, hipStream_t s) {
-    const int cfg = gemm_pick_config(p, DT);       // already mapped onto the shapes DT has
-    // the fused head tail needs a wave to hold every output channel of its rows: waves stacked along m, 128 columns per wave
-    if (p.epi == EPI_HEAD4 && (DT != D3R_F16X3 || !(cfg == GEMM_CFG_512x128 || cfg == GEMM_CFG_256x128R))) return hipErrorInvalidValue;
+// the plan's tile on the Cfg that runs it for DT (gemm_plan has already mapped plan.cfg onto the shapes DT has): nothing is decided here
+template <int DT> static hipError_t launch_t(const GemmParams& p, const GemmPlan& plan, hipStream_t s) {
+    const int cfg = plan.cfg;
     if constexpr (DT == D3R_F16X3) {
         if (cfg == GEMM_CFG_384x192) return launch_cfg<DT, Cfg384x192>(p, s);
         if (cfg == GEMM_CFG_256x128R) return launch_cfg<DT, Cfg256x128r>(p, s);
         if (cfg == GEMM_CFG_96x64) return launch_cfg<DT, Cfg96x64>(p, s);
         // the 64 x 64 tile on a three-slot ring. Measured (profiles/r03_f): one pair 14.56 ms on the 128 x 128 tile, 12.36 / 10.38 / 10.48 ms with 2 / 3 / 4 slots
         if (cfg == GEMM_CFG_64) return launch_cfg<DT, Cfg64s3>(p, s);
-        // 128 x 128 launches of fewer than 1100 tiles (the one- to four-pair forwards) on the eight-wave shape. Measured (profiles/r03_k):
-        // one pair 10.59 -> 10.26 ms, two 16.0 -> 15.3, four 26.3 -> 25.9; applied to the 1152-tile launches of the 32-pair step as well:
-        // -0.1 %, hence the limit. D3R_GEMM_T128W8 moves it (0 = never).
-        if (cfg == GEMM_CFG_128 && gemm_runs_128w8(p, DT)) return launch_cfg<DT, Cfg128w8>(p, s);
+        if (cfg == GEMM_CFG_128 && plan.w8) return launch_cfg<DT, Cfg128w8>(p, s);
     }
     if constexpr (DT == D3R_F16F8) {
         // the 256-wide tiles with the DMA pieces interleaved with the MFMA rows (PP = 4). Measured on MI355X (profiles/r02_f8/bench_f8_il.log): +3 % on
@@ -1709,61 +1564,71 @@ template <int DT> static hipError_t launch_t(const GemmParams& p, hipStream_t s)
     }
 }
 
+// the only place the GEMM reads the environment; not cached: parity tests, A/B runs and probes move the values inside one process
+GemmEnv gemm_env() {
+    GemmEnv env;
+    if (const char* e = getenv("D3R_GEMM_CFG"))
+        if (e[0] >= '0' && e[0] <= '9') env.forced_cfg = e[1] == 0 ? e[0] - '0' : ((e[0] == '1' && e[1] == '1' && e[2] == 0) ? GEMM_CFG_96x64 : -1);
+    if (const char* e = getenv("D3R_GEMM_PERSIST")) env.persist = e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1);
+    if (const char* e = getenv("D3R_GEMM_T128W8")) env.t128w8 = atol(e);
+    if (const char* e = getenv("D3R_GEMM_NOWIDE")) env.nowide = e[0] == '1';
+    return env;
+}
+
 static unsigned long long* g_trace_buf = nullptr;
 static size_t g_trace_cap = 0;
 void gemm_set_trace(unsigned long long* buf, size_t capacity_blocks) { g_trace_buf = buf; g_trace_cap = capacity_blocks; }
 
-hipError_t launch_gemm(int dt, const GemmParams& p_in, hipStream_t s) {
-    GemmParams p = p_in;
-    if (g_trace_buf && (size_t)cdiv(p.M, 128) * cdiv(p.n_store, 128) <= g_trace_cap) p.trace = g_trace_buf;   // capacity for the smallest tile
-    p.flags |= gemm_env_flags(p);
-    p.flags |= GF_NTSTORE;      // wide epilogues store with the non-temporal policy (measured +3..10 % on isolated GEMMs, +1 % on the forward)
+// the trace buffer of a launch of p, when one is set and has the capacity for the smallest tile
+static unsigned long long* trace_of(const GemmParams& p) { return g_trace_buf && (size_t)cdiv(p.M, 128) * cdiv(p.n_store, 128) <= g_trace_cap ? g_trace_buf : nullptr; }
+
+GemmPlan gemm_plan_for(const GemmParams& p, int dt) { return gemm_plan(p, dt, gemm_env(), device_cus(), trace_of(p) != nullptr); }
+
+static bool gemm_args_ok(const GemmParams& p, int dt) {
     const int kt = 128 / (int)dt_bytes(dt);
-    if (p.M <= 0 || p.n_pad % 128 != 0 || p.n_store > p.n_pad || p.K % kt != 0 || p.K <= 0) return hipErrorInvalidValue;
-    if (p.amode == AMODE_CONV && (p.Cin % kt != 0 || p.zero_page == nullptr)) return hipErrorInvalidValue;
-    if (p.epi == EPI_HEADS && p.head_c % 128 != 0 && p.head_c < (1 << 29)) return hipErrorInvalidValue;
-    if (p.epi == EPI_HEAD4 && (p.n_store > 128 || p.n_store % 4 != 0 || !p.res1 || !p.res2 || !p.out || !p.out2)) return hipErrorInvalidValue;
+    if (p.M <= 0 || p.n_pad % 128 != 0 || p.n_store > p.n_pad || p.K % kt != 0 || p.K <= 0) return false;
+    if (p.amode == AMODE_CONV && (p.Cin % kt != 0 || p.zero_page == nullptr)) return false;
+    if (p.epi == EPI_HEADS && p.head_c % 128 != 0 && p.head_c < (1 << 29)) return false;
+    if (p.epi == EPI_HEAD4 && (p.n_store > 128 || p.n_store % 4 != 0 || !p.res1 || !p.res2 || !p.out || !p.out2)) return false;
     // folded LayerNorm (kernels.hpp): statistics come out of the wide fp32 epilogue only; the consumer side exists for split-fp16 operands, typed / GELU / head outputs
-    if (p.ln_part && (p.epi != EPI_F32 || !(p.flags & GF_X3RES) || p.n_store % 32 != 0)) return hipErrorInvalidValue;   // the row sums come out of the typed-stream epilogue
-    if ((p.flags & GF_X3RES) && (dt != D3R_F16X3 || p.epi != EPI_F32 || (p.flags & GF_NOWIDE) || !p.out2 || (p.ldo2 & 7) || (p.n_store & 7) || (p.res1 && (p.ldr & 7)))) return hipErrorInvalidValue;
-    if (p.ln_part_in && (!p.ln_rstd || p.K % 32 != 0 || p.K > 2048)) return hipErrorInvalidValue;
-    if (p.ln_rstd && (dt != D3R_F16X3 || !p.ln_nmr || !p.ln_colsum || p.amode != AMODE_LINEAR || !(p.epi == EPI_T || p.epi == EPI_GELU || p.epi == EPI_HEADS) || p.res1 || p.res2 || p.out2)) return hipErrorInvalidValue;
+    if (p.ln_part && (p.epi != EPI_F32 || !(p.flags & GF_X3RES) || p.n_store % 32 != 0)) return false;   // the row sums come out of the typed-stream epilogue
+    if ((p.flags & GF_X3RES) && (dt != D3R_F16X3 || p.epi != EPI_F32 || (p.flags & GF_NOWIDE) || !p.out2 || (p.ldo2 & 7) || (p.n_store & 7) || (p.res1 && (p.ldr & 7)))) return false;
+    if (p.ln_part_in && (!p.ln_rstd || p.K % 32 != 0 || p.K > 2048)) return false;
+    if (p.ln_rstd && (dt != D3R_F16X3 || !p.ln_nmr || !p.ln_colsum || p.amode != AMODE_LINEAR || !(p.epi == EPI_T || p.epi == EPI_GELU || p.epi == EPI_HEADS) || p.res1 || p.res2 || p.out2)) return false;
     // fp16 + fp8 rows: nn.Linear operands only, whole 64-element super-groups; outputs: fp32 (+ residual), GELU / plain activation rows, heads
     const bool f8rows = dt == D3R_F16F8 || dt == D3R_F16X2F8;
-    if (f8rows && ((size_t)512 * p.lda * 4 >= (1ull << 32) || (size_t)512 * p.K * 5 >= (1ull << 32))) return hipErrorInvalidValue;   // 32-bit offsets inside a tile
-    if (dt == D3R_F16X2F8 && p.K % 128 != 0) return hipErrorInvalidValue;      // whole 128-k blocks of five chunks
+    if (f8rows && ((size_t)512 * p.lda * 4 >= (1ull << 32) || (size_t)512 * p.K * 5 >= (1ull << 32))) return false;   // 32-bit offsets inside a tile
+    if (dt == D3R_F16X2F8 && p.K % 128 != 0) return false;      // whole 128-k blocks of five chunks
     if (f8rows && (p.amode != AMODE_LINEAR || p.K % 64 != 0 || p.lda % 64 != 0 || p.epi == EPI_CONVT || p.res2 ||
                             (p.epi == EPI_T && (p.res1 || p.out2)) || ((p.epi == EPI_T || p.epi == EPI_GELU) && (p.ldo % 64 != 0 || p.n_store % 4 != 0))))
-        return hipErrorInvalidValue;
-    if (use_p4(p, dt)) return launch_gemm_p4(p, s);
-    {   // split-K (kernels.hpp): only with the caller's buffers, split-fp16 nn.Linear launches of the small-batch forwards (the problems the heuristic sends to the
-        // 64 x 64 tile: fewer than 200 tiles of 128 x 128), the plain K loop; at most 3 blocks per CU after the split, at least 16 K steps (of 32) per slice.
-        int sk = 1;
-        if (p.sk_slab && p.sk_cnt && p.splitk != 1 && dt == D3R_F16X3 && p.amode == AMODE_LINEAR && !p.trace && p.force_cfg < 0 &&
-            gemm_pick_config(p, dt) == GEMM_CFG_64) {
-            constexpr int tile = 64, minsteps = 16;
-            const long maxblocks = (long)device_cus() * 3;
-            const long tiles = (long)cdiv(p.M, tile) * cdiv(p.n_store, tile);
-            const int nk32 = p.K / 32;
-            for (int c : {8, 6, 4, 3, 2}) {
-                if (tiles * c <= maxblocks && nk32 % c == 0 && nk32 / c >= minsteps && (size_t)tiles * c * tile * tile <= p.sk_slab_floats && tiles <= p.sk_cnt_n) { sk = c; break; }
-            }
-        }
-        p.splitk = sk;
-    }
+        return false;
+    return true;
+}
+
+static hipError_t run_plan(int dt, const GemmParams& p_in, const GemmPlan& plan, hipStream_t s) {
+    GemmParams p = p_in;
+    if (unsigned long long* t = trace_of(p)) p.trace = t;
+    p.flags |= plan.flags;
+    p.splitk = plan.splitk;
+    if (plan.cfg == GEMM_CFG_P4) return launch_gemm_p4(p, s);
+    // the fused head tail needs a wave to hold every output channel of its rows: waves stacked along m, 128 columns per wave
+    if (p.epi == EPI_HEAD4 && (dt != D3R_F16X3 || !(plan.cfg == GEMM_CFG_512x128 || plan.cfg == GEMM_CFG_256x128R))) return hipErrorInvalidValue;
 #ifdef D3R_GEMM_ONLY_DT      // development builds (-DD3R_GEMM_ONLY_DT=4): one precision mode only, a tenth of the compile time
-    if (dt == D3R_GEMM_ONLY_DT) return launch_t<D3R_GEMM_ONLY_DT>(p, s);
+    if (dt == D3R_GEMM_ONLY_DT) return launch_t<D3R_GEMM_ONLY_DT>(p, plan, s);
 #else
     switch (dt) {
-        case D3R_BF16: return launch_t<D3R_BF16>(p, s);
-        case D3R_F16: return launch_t<D3R_F16>(p, s);
-        case D3R_F32: return launch_t<D3R_F32>(p, s);
-        case D3R_F16X3: return launch_t<D3R_F16X3>(p, s);
-        case D3R_F16F8: return launch_t<D3R_F16F8>(p, s);
-        case D3R_F16X2F8: return launch_t<D3R_F16X2F8>(p, s);
+        case D3R_BF16: return launch_t<D3R_BF16>(p, plan, s);
+        case D3R_F16: return launch_t<D3R_F16>(p, plan, s);
+        case D3R_F32: return launch_t<D3R_F32>(p, plan, s);
+        case D3R_F16X3: return launch_t<D3R_F16X3>(p, plan, s);
+        case D3R_F16F8: return launch_t<D3R_F16F8>(p, plan, s);
+        case D3R_F16X2F8: return launch_t<D3R_F16X2F8>(p, plan, s);
     }
 #endif
     return hipErrorInvalidValue;
 }
+hipError_t launch_gemm(int dt, const GemmParams& p, hipStream_t s) { return gemm_args_ok(p, dt) ? run_plan(dt, p, gemm_plan_for(p, dt), s) : hipErrorInvalidValue; }
+hipError_t launch_gemm(int dt, const GemmParams& p, const GemmPlan& plan, hipStream_t s) { return gemm_args_ok(p, dt) ? run_plan(dt, p, plan, s) : hipErrorInvalidValue; }
+
 
 }  // namespace d3r

@@ -566,20 +566,8 @@ bool gemm_p4_eligible(const GemmParams& p, int dt) {
 
 template <int EPK, int NF, bool L32 = false> static hipError_t launch_p4(const GemmParams& p, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    const unsigned long long dev_bit = 1ull << (dev_id & 63);
-    if (!(attr_done.load(std::memory_order_relaxed) & dev_bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(p4::gemm_p4_kernel<EPK, NF, L32>), hipFuncAttributeMaxDynamicSharedMemorySize, p4::LDS);
-        attr_done.fetch_or(dev_bit, std::memory_order_relaxed);
-    }
-    static std::atomic<int> cus_cache[64];
-    int cus = cus_cache[dev_id & 63].load(std::memory_order_relaxed);
-    if (cus <= 0) {
-        int q = 0;
-        cus = (hipDeviceGetAttribute(&q, hipDeviceAttributeMultiprocessorCount, dev_id) == hipSuccess && q > 0) ? q : 256;
-        cus_cache[dev_id & 63].store(cus, std::memory_order_relaxed);
-    }
+    raise_dynamic_lds_once(attr_done, reinterpret_cast<const void*>(p4::gemm_p4_kernel<EPK, NF, L32>), p4::LDS);
+    const int cus = device_cus();
     const int tiles_m = p.M / p4::BM, tiles_n = p.n_store / p4::BN, ntiles = tiles_m * tiles_n;
     int grid = cus < ntiles ? cus : ntiles;
     grid &= ~7;                          // XCD-contiguous tile ranges need the grid stride to keep a block on its XCD (v & 7 == blockIdx & 7)

@@ -12,7 +12,7 @@ enum { EPI_T = 0, EPI_F32 = 1, EPI_GELU = 2, EPI_HEADS = 3, EPI_CONVT = 4, EPI_H
 // pts / conf (dpt_head.py:63 + postprocess.py:10-58). Field reuse: out = pts (float*), ldo = its pixel stride, out2 = conf (float*),
 // ldo2 = its pixel stride, res1 = the 1x1 weights [4][n_store] fp32, res2 = its bias [4] fp32. Nothing of the C-channel map is stored.
 enum { HEAD_ROPE = 1, HEAD_VT = 2, HEAD_PLAIN = 3 };
-enum { GF_RELU = 1, GF_NOWIDE = 4, GF_NTSTORE = 8, GF_X3RES = 16 };   // GF_X3RES (EPI_F32, split-fp16): res1 and the result live in split-fp16 rows only (out2); no fp32 row is stored   // GF_NTSTORE: wide epilogues store with the non-temporal policy (set by launch_gemm)
+enum { GF_RELU = 1, GF_NOWIDE = 4, GF_NTSTORE = 8, GF_X3RES = 16 };   // GF_X3RES (EPI_F32, split-fp16): res1 and the result live in split-fp16 rows only (out2); no fp32 row is stored   // GF_NTSTORE: wide epilogues store with the non-temporal policy (set by every plan, gemm_plan.hpp)
 // tile map of both GEMM kernels: block ids walk column panels GEMM_PANEL tiles wide, row by row
 constexpr int GEMM_PANEL = 8;
 // 4 / 5 / 6 name retired shapes; pinned (D3R_GEMM_CFG, force_cfg) they run configurations 2 / 1 / 1
@@ -64,22 +64,31 @@ struct GemmParams {
     const float* ln_part_in = nullptr; float ln_eps = 1e-6f, ln_inv_c = 0.f;
     // ---- split-K for SMALL problems (round 6; split-fp16, nn.Linear operands, the plain K loop): `splitk` blocks share a tile, each over 1 / splitk of the K steps;
     // every block stores its fp32 partial tile in sk_slab ([tile][slice][wave][fragment][lane] float4), the block that draws the last ticket of sk_cnt[tile] adds the
-    // slices up in slice order (deterministic whichever block is last) and runs the epilogue. Chosen by launch_gemm when the caller lends it the two buffers.
+    // slices up in slice order (deterministic whichever block is last) and runs the epilogue. Chosen by gemm_plan when the caller lends the launch the two buffers.
     int splitk = 1; float* sk_slab = nullptr; unsigned* sk_cnt = nullptr; size_t sk_slab_floats = 0; int sk_cnt_n = 0;
 };
 void gemm_set_trace(unsigned long long* buf, size_t capacity_blocks);
 
-hipError_t launch_gemm(int dt, const GemmParams& p, hipStream_t s);
-int gemm_pick_config(const GemmParams& p, int dt);
-// what launch_gemm reads from the environment for a launch of p before it asks gemm_pick_config: GF_NOWIDE under D3R_GEMM_NOWIDE=1 (it changes the V^T route of
-// the 16-bit attention projections, hence the tiles a heads launch may take). Host queries of the heuristic (capi.hip) add the same flags.
-int gemm_env_flags(const GemmParams& p);
-// true when a launch that gemm_pick_config sends to GEMM_CFG_128 runs the tile on EIGHT waves (split-fp16, fewer than D3R_GEMM_T128W8 = 1100 tiles)
-bool gemm_runs_128w8(const GemmParams& p, int dt);
 // gemm_p4.hip: the persistent split-fp16 kernel whose epilogue runs under the next tile's K loop (tile configuration 10 in profiles)
 bool gemm_p4_eligible(const GemmParams& p, int dt);
 hipError_t launch_gemm_p4(const GemmParams& p, hipStream_t s);
-int gemm_p4_mode();              // -1: the heuristic decides, 0: never, 1: every eligible launch (D3R_GEMM_PERSIST, read per call: probes and tests move it)
+}  // namespace d3r
+#include "gemm_plan.hpp"      // GemmEnv, GemmPlan, gemm_plan(): the dispatch decision, pure
+namespace d3r {
+GemmEnv gemm_env();                                      // the four D3R_GEMM_* values, read on every call (probes and tests move them inside one process)
+GemmPlan gemm_plan_for(const GemmParams& p, int dt);     // gemm_plan under gemm_env(), the current device's CU count and the trace switch: what launch_gemm(dt, p, s) runs
+hipError_t launch_gemm(int dt, const GemmParams& p, hipStream_t s);
+// the same launch on a plan the caller already took from gemm_plan_for (the engine marks its profile with plan.cfg, then launches)
+hipError_t launch_gemm(int dt, const GemmParams& p, const GemmPlan& plan, hipStream_t s);
+
+// nn.Linear-shaped operands [M][lda] x [N][K]^T: weight rows as the loader allocates them (engine.hip Lin: n_pad = round_up(N, 128), round_up(N, 256) rows).
+// The caller adds the epilogue.
+inline GemmParams linear_gemm_params(const void* act, int lda, const void* wgt, const float* bias, int M, int N, int K) {
+    GemmParams p;
+    p.act = act; p.lda = lda; p.wgt = wgt; p.bias = bias; p.M = M; p.K = K;
+    p.n_pad = (N + 127) / 128 * 128; p.n_rows = (N + 255) / 256 * 256; p.n_store = N;
+    return p;
+}
 
 // The implicit-GEMM launches of the DPT head, built in ONE place for the engine (engine.hip conv / conv_head4) and for the kernel-level C ABI
 // (capi.hip d3r_conv2d_nhwc_x / d3r_conv_head4): what the kernel tests pin is what the engine launches.
@@ -95,19 +104,19 @@ inline GemmParams conv_gemm_params(const void* in, int B, int Hin, int Win, int 
     p.zero_page = zero_page;
     return p;
 }
-// head4_tile: the tile shape of an EPI_HEAD4 launch -- 512 x 128 where the heuristic picks it, else the FORCED 256 x 128 R (p.force_cfg is set) -- or -1 when
+// head4_tile: the plan of an EPI_HEAD4 launch -- 512 x 128 where the heuristic picks it, else the FORCED 256 x 128 R (p.force_cfg is set) -- or false when
 // the launch cannot hold every output channel of a row in one wave (more than 128 channels, another precision mode): the caller takes the two-kernel route.
 // Fewer pixels (one or two images) take the same tile by four waves stacked along m. ANY pixel count below the 512 x 128 tile's takes this shape (round 5): with the
 // heuristic's 128 x 128 choice for < 512 tiles the head of ONE 512 x 160 pair took the two-kernel route and a batch of three the fused one -- 3e-6 apart, the only place where
 // a batch was not bit-equal to its one-pair calls (tests/test_timed_configs_gpu.py::test_full_size_released_resolutions_match_oracle)
-inline int head4_tile(GemmParams& p, int dt) {
-    if (p.ksize != 3 || p.n_store > 128 || p.n_store % 4 != 0) return -1;
-    int cfg = gemm_pick_config(p, dt);
-    if (cfg != GEMM_CFG_512x128) {
+inline bool head4_tile(GemmParams& p, int dt, GemmPlan& plan) {
+    if (p.ksize != 3 || p.n_store > 128 || p.n_store % 4 != 0) return false;
+    plan = gemm_plan_for(p, dt);
+    if (plan.cfg != GEMM_CFG_512x128) {
         p.force_cfg = GEMM_CFG_256x128R;
-        cfg = gemm_pick_config(p, dt);
+        plan = gemm_plan_for(p, dt);
     }
-    return (cfg == GEMM_CFG_512x128 || cfg == GEMM_CFG_256x128R) ? cfg : -1;
+    return plan.cfg == GEMM_CFG_512x128 || plan.cfg == GEMM_CFG_256x128R;
 }
 
 // ------------------------------------------------------------------------------ attention

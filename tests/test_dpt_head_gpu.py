@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 
 X3_TOL = 3e-6
 SENT = -1234.5          # sentinel of the guard regions: exact in fp16 and fp32
-# D3R_GEMM_CFG values a split-fp16 convolution launch can be pinned to (gemm.hip pick_config_raw): 0 = 128 x 128 (by four waves, and '0w8' by eight),
+# D3R_GEMM_CFG values a split-fp16 convolution launch can be pinned to (gemm_plan.hpp gemm_plan): 0 = 128 x 128 (by four waves, and '0w8' by eight),
 # 1 = 256 x 256, 2 = 256 x 128, 3 = 512 x 128, 7 = 256 x 128 by four waves with the weights of a K step in registers, 8 = 64 x 64, 11 = 96 x 64;
 # 'auto' = the heuristic. 9 (384 x 192) is for nn.Linear operands only: the transposed convolution's GEMM takes it where its columns are whole tiles
 # (the 96 -> 96, k = 4 case: N = 1536), elsewhere the pin is ignored and the heuristic's tile runs.
@@ -228,7 +228,7 @@ def outputs(npix, strides, device):
 TAIL_GEOM = {   # tile shape -> (D3R_GEMM_CFG, B, H, W)
     # 384 pixels: below one tile; conv_head4 forces the four-wave 256 x 128 shape for every pixel count the heuristic does not give the 512 x 128 tile
     'r256': ('auto', 1, 16, 24),
-    # The heuristic picks 512 x 128 from 512 tiles on (gemm.hip pick_config_raw: cdiv(M, 512) >= 512, i.e. M >= 261 633 pixels). Such an image is 134 MB of input
+    # The heuristic picks 512 x 128 from 512 tiles on (gemm_plan.hpp gemm_plan: cdiv(M, 512) >= 512, i.e. M >= 261 633 pixels). Such an image is 134 MB of input
     # rows and a 77 GFLOP fp64 reference convolution (seconds on the CPU, gigabytes of im2col): too large for a test of a few seconds, so the shape is pinned
     # with D3R_GEMM_CFG: 960 pixels = one full tile and a ragged one (448 rows)
     't512': ('3', 1, 24, 40),

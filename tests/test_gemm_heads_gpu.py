@@ -53,7 +53,7 @@ CFGS = {'fp32': ['0', '1', '2', '3'], 'bf16': ['0', '1', '2', '3'], 'fp16': ['0'
         'fp16f8': ['0', '1', '2', '3'],                                    # test_linear_fp16_fp8's
         'fp16x2f8': ['0', '1']}                                            # test_linear_2p5_unit's
 TOL = {'fp32': 2e-5, 'bf16': OUT_TOL[torch.bfloat16], 'fp16': OUT_TOL[torch.float16], 'fp16x3': 3e-6, 'fp16f8': 3e-6, 'fp16x2f8': 3e-6}
-# configurations that pick_config_raw (gemm.hip) must take for some shape of the list, per dtype
+# configurations that gemm_plan (gemm_plan.hpp) must take for some shape of the list, per dtype
 MUST_TAKE = {'fp32': {'0', '1'}, 'bf16': {'0', '1', '2', '3'}, 'fp16': {'0', '1', '2', '3'}, 'fp16x3': {'0', '0w8', '1', '8'}, 'fp16f8': {'0', '1'},
              'fp16x2f8': {'0', '1'}}
 

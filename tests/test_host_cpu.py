@@ -435,6 +435,40 @@ def test_gemm_tile_dispatch_table(monkeypatch):
     assert lib.d3r_gemm_tile_config(x3, 0, 8, 8, 0, 0) < 0 or lib.d3r_gemm_tile_config(x3, 0, 8, 8, 0, 0) > 8     # invalid arguments: an error code, not a configuration
 
 
+def test_gemm_plan_matches_recorded_table(monkeypatch):
+    """The GEMM dispatch (csrc/gemm_plan.hpp) through its two host queries, no device: every answer over the grids of tests/golden/gemm_plan_table.json
+    (tools/make_gemm_plan_golden.py: recorded BEFORE the dispatch became one function; six operand types x 13 M x 9 N x 4 K x 4 epilogues under 15 D3R_GEMM_*
+    environments, and the attention-projection launches with and without D3R_GEMM_NOWIDE) equals the recorded one. D3R_GEMM_NOWIDE is not recorded for
+    d3r_gemm_tile_config: that query now reports what launch_gemm runs under it, pinned by the two asserts at the end."""
+    import importlib.util
+    import json
+    from dust3r_amd._lib import DTYPE_F16X3, lib
+    spec = importlib.util.spec_from_file_location('make_gemm_plan_golden', os.path.join(ROOT, 'tools', 'make_gemm_plan_golden.py'))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    table = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'gemm_plan_table.json')))
+    assert table['codes'] == gen.CODES
+    assert table['tile_config']['grid'] == gen.TILE_GRID and table['tile_config']['envs'] == gen.TILE_ENVS       # the grid the issue states, as recorded
+    assert table['heads_tile_config']['grid'] == gen.HEADS_GRID and table['heads_tile_config']['envs'] == gen.HEADS_ENVS
+    got = gen.replay(table)
+    for key in ('tile_config', 'heads_tile_config'):
+        want = table[key]['answers']
+        assert len(want) == len(table[key]['envs']) and len(set(map(len, want))) == 1 and len(want[0]) > 500
+        for env, w, g in zip(table[key]['envs'], want, got[key]):
+            diff = [i for i in range(len(w)) if w[i] != g[i]] if w != g else []
+            assert not diff, f'{key} under {env}: {len(diff)} of {len(w)} answers differ, first at grid index {diff[0]}: recorded {w[diff[0]]}, now {g[diff[0]]}'
+    # fc1 + GELU of the encoder at 32 pairs: the persistent kernel by default; under D3R_GEMM_NOWIDE=1 launch_gemm keeps it off that kernel, and the query says so
+    for name in gen.ENV_VARS:
+        monkeypatch.delenv(name, raising=False)
+    fc1 = lambda: lib.d3r_gemm_tile_config(DTYPE_F16X3, 49152, 4096, 1024, 2, 0)      # noqa: E731
+    assert fc1() == 10
+    monkeypatch.setenv('D3R_GEMM_PERSIST', '0')
+    one_tile_per_block = fc1()
+    monkeypatch.delenv('D3R_GEMM_PERSIST')
+    monkeypatch.setenv('D3R_GEMM_NOWIDE', '1')
+    assert fc1() == one_tile_per_block != 10
+
+
 def test_postprocess_mode_keywords_follow_the_reference():
     """model.py:58-62 / heads/postprocess.py:23-58: every depth / conf mode of the reference is accepted (the engine implements them,
     include/dust3r_hip.h d3r_model_set_postprocess), an unknown mode raises the reference's ValueError, depth bounds are asserted away."""
