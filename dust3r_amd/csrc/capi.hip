@@ -69,7 +69,7 @@ extern "C" int d3r_linear_heads(const void* act, const void* wgt, const float* b
     if ((ln_rstd || ln_nmr || ln_colsum || ln_part_in) && (dtype != D3R_F16X3 || !ln_rstd || !ln_nmr || !ln_colsum)) return D3R_ERR_INVALID;
     p.rope_table = rope_table;
     if (ln_rstd) { p.ln_rstd = ln_rstd; p.ln_nmr = ln_nmr; p.ln_colsum = ln_colsum; p.ln_part_in = ln_part_in; p.ln_eps = ln_eps; p.ln_inv_c = 1.0f / (float)K; }
-    if (sk_slab && sk_cnt) { p.splitk = 0; p.sk_slab = sk_slab; p.sk_slab_floats = sk_slab_floats; p.sk_cnt = sk_cnt; p.sk_cnt_n = sk_cnt_n; }      // launch_gemm decides whether it splits (engine.hip gemm_linear)
+    if (sk_slab && sk_cnt) { p.splitk = 0; p.sk_slab = sk_slab; p.sk_slab_floats = sk_slab_floats; p.sk_cnt = sk_cnt; p.sk_cnt_n = sk_cnt_n; }      // launch_gemm decides whether it splits (engine.hip launch(), lend_sk: gemm_linear)
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
@@ -94,7 +94,7 @@ extern "C" int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bia
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
-// ---- the DPT head's kernels alone (include/dust3r_hip.h): the launches of engine.hip run_dpt, for the kernel tests -------------------------------
+// ---- the DPT head's kernels alone (include/dust3r_hip.h): the launches of engine.hip run_dpt (through conv / conv_head4 / launch), for the kernel tests -------------------------------
 static inline bool conv_dtype(int dtype) { return dtype == D3R_BF16 || dtype == D3R_F16 || dtype == D3R_F32 || dtype == D3R_F16X3; }
 static inline bool post_mode(PostMode& pm, int depth_mode, int conf_mode, float vmin, float vmax) {      // d3r_model_set_postprocess's rules
     if (depth_mode < POST_DEPTH_EXP || depth_mode > POST_DEPTH_SQUARE || conf_mode < POST_CONF_EXP || conf_mode > POST_CONF_SIGMOID) return false;
@@ -138,7 +138,7 @@ extern "C" int d3r_convt_gemm(const void* act, const void* wgt, const float* bia
     if (!act || !wgt || !out || !conv_dtype(dtype) || B <= 0 || th <= 0 || tw <= 0 || ksize <= 0) return D3R_ERR_INVALID;
     if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || lda < cin_pad || cout_pad <= 0 || cout_pad % 4 != 0 || ldo < cout_pad) return D3R_ERR_INVALID;
     const int N = ksize * ksize * cout_pad;
-    GemmParams p = linear_gemm_params(act, lda, wgt, bias, B * th * tw, N, cin_pad);      // engine.hip run_dpt, the EPI_CONVT launch
+    GemmParams p = linear_gemm_params(act, lda, wgt, bias, B * th * tw, N, cin_pad);      // engine.hip run_dpt, the EPI_CONVT launch: lin_params on the packed matrix
     p.epi = EPI_CONVT; p.ksize = ksize; p.ct_cout = cout_pad;
     p.Hin = th; p.Win = tw; p.out = out; p.ldo = ldo;
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));

@@ -128,7 +128,6 @@ struct d3r_model {
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
     bool two_streams = true;
     PostMode post;                          // depth_mode / conf_mode of the heads (d3r_model_set_postprocess; default = the released checkpoints')
-    int out_pstride = 3, out_cstride = 1;   // output element strides between pixels (8, 8 while d3r_model_forward_packed runs)
     // ---- hipGraph replay of small-batch forwards (d3r_model_forward* with B <= graph_max_pairs) ------------------------------------
     // One pair per call (dust3r/demo.py:156 batch_size=1, visloc.py:88) is ~700 launches of kernels that each fill a fraction of the
     // chip: the host-side enqueue and the two-stream event traffic, not the GPU, set the pace. The second call with the same
@@ -342,7 +341,6 @@ bool build_slots(d3r_model* m) {
 int pack_slot(d3r_model* m, Slot& s, const float* data, int ndim, const int64_t* shape) {
     size_t numel = 1;
     for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
-    const size_t eb = dt_bytes(m->dt);
     PackParams pp;
     pp.src = data; pp.numel = numel; pp.dst = s.dst; pp.dst_cols = s.dst_cols;
     switch (s.kind) {
@@ -378,7 +376,6 @@ int pack_slot(d3r_model* m, Slot& s, const float* data, int ndim, const int64_t*
             if (numel != (size_t)s.rows) return D3R_ERR_SHAPE;
             return launch_pack_convt_bias(data, (float*)s.dst, s.rows, s.cout_pad, s.ksize * s.ksize, nullptr) == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH;
     }
-    (void)eb;
     return launch_pack_weight(s.dt < 0 ? m->dt : s.dt, pp, nullptr) == hipSuccess ? D3R_OK : D3R_ERR_LAUNCH;
 }
 
@@ -408,49 +405,63 @@ enum { PRF_GEMM = 0, PRF_CONV = 8, PRF_ATTN = 16, PRF_OTHER = 17, PRF_GEMM_64 = 
 static inline int prf_kind(int base, int cfg) { return cfg == GEMM_CFG_P4 ? PRF_GEMM_P4 : cfg == GEMM_CFG_384x192 ? PRF_GEMM_384 : (cfg == GEMM_CFG_64 || cfg == GEMM_CFG_96x64) ? (base == PRF_CONV ? PRF_CONV_64 : PRF_GEMM_64) : base + cfg; }
 #define D3R_OTHER(call) do { c.mark(PRF_OTHER, 0.0); c.chk(call); } while (0)
 
-// folded LayerNorm (kernels.hpp GemmParams::ln_*): `stats` = the consumer side (rstd, -mean rstd of the input rows; the Lin carries column sums and
-// folded bias), `part` = the producer side (partial sums of the rows this launch stores, next to their raw typed copy out2)
-struct LnStats { const float* rstd = nullptr; const float* nmr = nullptr; const float* part_in = nullptr; };   // part_in: small problem, the consumer forms rstd / nmr itself (no ln_finalize launch)
-void gemm_linear(Ctx& c, const void* act, int lda, const Lin& L, int M, int epi, void* out, int ldo, const void* res1 = nullptr,
-                 void* out2 = nullptr, int ldo2 = 0, int n_store = -1, int flags = 0, LnStats stats = LnStats(), float* part = nullptr) {
-    GemmParams p;
-    p.act = act; p.lda = lda; p.wgt = L.w; p.bias = L.b; p.M = M; p.K = L.K; p.n_pad = L.n_pad; p.n_rows = L.n_rows;
-    p.n_store = n_store >= 0 ? n_store : L.N;
-    p.epi = epi; p.out = out; p.ldo = ldo; p.res1 = res1; p.ldr = ldo; p.out2 = out2; p.ldo2 = ldo2; p.flags = flags;
-    if (stats.rstd) { p.ln_rstd = stats.rstd; p.ln_nmr = stats.nmr; p.ln_colsum = L.ln_s; p.bias = L.b_fold; p.ln_part_in = stats.part_in; p.ln_inv_c = 1.0f / (float)L.K; }
-    p.ln_part = part;
-    {   // split-K buffers of this launch's stream (launch_gemm decides whether the launch splits; never while profiling: one event per launch)
-        const int sset = c.st == c.st0 ? 0 : (c.st == c.m->side ? 1 : -1);
-        if (c.m->splitk_on && sset >= 0 && c.m->sk_slab[sset] && !c.m->prof_on) {
-            p.splitk = 0; p.sk_slab = c.m->sk_slab[sset]; p.sk_cnt = c.m->sk_cnt[sset]; p.sk_slab_floats = d3r_model::SK_SLAB_FLOATS; p.sk_cnt_n = d3r_model::SK_CNT;
-        }
-    }
-    const GemmPlan plan = gemm_plan_for(p, L.dt);
-    c.mark(prf_kind((L.dt == D3R_F16F8 || L.dt == D3R_F16X2F8) ? PRF_GEMM_F8 : PRF_GEMM, plan.cfg), 2.0 * M * (double)L.N * L.K, M, L.N, L.K);
-    c.chk(launch_gemm(L.dt, p, plan, c.st));
+// The two views of a pair may have different sizes (dust3r/model.py:148-150: the reference then encodes them separately): every
+// per-side quantity of the decoder / heads is indexed by side -- token grid (th, tw), tokens per image N, rows M = B N, V^T row
+// stride -- and cross attention runs Nq != Nk. With equal sizes this is the old schedule bit for bit.
+struct SideDim { int H, W, th, tw, N, ldv; };
+SideDim side_dim(int H, int W, int ps) {
+    SideDim d;
+    d.H = H; d.W = W; d.th = H / ps; d.tw = W / ps; d.N = d.th * d.tw; d.ldv = rup(d.N, 64);
+    return d;
 }
 
-void gemm_heads(Ctx& c, const void* act, int lda, const Lin& L, int M, int head_c, int nreg, const int* kinds, void* const* dsts, int heads,
-                int ntok, int tok_w, int ldv, LnStats stats = LnStats()) {
-    GemmParams p;
-    p.act = act; p.lda = lda; p.wgt = L.w; p.bias = L.b; p.M = M; p.K = L.K; p.n_pad = L.n_pad; p.n_rows = L.n_rows; p.n_store = L.N;
+// folded LayerNorm (kernels.hpp GemmParams::ln_*): `stats` = the consumer side (rstd, -mean rstd of the input rows; the Lin carries column sums and
+// folded bias), GemmParams::ln_part = the producer side (partial sums of the rows this launch stores, next to their raw typed copy out2)
+struct LnStats { const float* rstd = nullptr; const float* nmr = nullptr; const float* part_in = nullptr; };   // part_in: small problem, the consumer forms rstd / nmr itself (no ln_finalize launch)
+
+// EVERY GEMM-kernel launch of the forward: lend the split-K buffers, plan, mark the profile with the plan's tile and the logical problem (M, N, K), launch that plan.
+// lend_sk: the buffers of this launch's stream go with it and gemm_plan decides whether it splits (never while profiling: one event per launch). Only gemm_linear lends
+// them: gemm_plan would split an attention-projection launch too. planned: the caller's own plan (conv_head4).
+void launch(Ctx& c, int dt, GemmParams& p, int base, int N, int K, bool lend_sk = false, const GemmPlan* planned = nullptr) {
+    const int sset = c.st == c.st0 ? 0 : (c.st == c.m->side ? 1 : -1);
+    if (lend_sk && c.m->splitk_on && sset >= 0 && c.m->sk_slab[sset] && !c.m->prof_on) {
+        p.splitk = 0; p.sk_slab = c.m->sk_slab[sset]; p.sk_cnt = c.m->sk_cnt[sset]; p.sk_slab_floats = d3r_model::SK_SLAB_FLOATS; p.sk_cnt_n = d3r_model::SK_CNT;
+    }
+    const GemmPlan plan = planned ? *planned : gemm_plan_for(p, dt);
+    if (base == PRF_GEMM && (dt == D3R_F16F8 || dt == D3R_F16X2F8)) base = PRF_GEMM_F8;
+    c.mark(prf_kind(base, plan.cfg), 2.0 * p.M * (double)N * K, p.M, N, K);
+    c.chk(launch_gemm(dt, p, plan, c.st));
+}
+
+// operands of the nn.Linear `L` on M rows of `act`, with the statistics of a folded LayerNorm in front of it; the caller names epilogue, outputs, residual and flags
+GemmParams lin_params(const Lin& L, const void* act, int lda, int M, const LnStats& stats = LnStats()) {
+    GemmParams p = linear_gemm_params(act, lda, L.w, L.b, M, L.N, L.K);
     if (stats.rstd) { p.ln_rstd = stats.rstd; p.ln_nmr = stats.nmr; p.ln_colsum = L.ln_s; p.bias = L.b_fold; p.ln_part_in = stats.part_in; p.ln_inv_c = 1.0f / (float)L.K; }
-    p.epi = EPI_HEADS; p.head_c = head_c;
-    for (int i = 0; i < nreg; ++i) { p.head_kind[i] = kinds[i]; p.head_dst[i] = dsts[i]; }
-    p.heads = heads; p.ntok = ntok; p.tok_w = tok_w; p.ldv = ldv; p.rope_table = c.m->rope_table;
-    const GemmPlan plan = gemm_plan_for(p, L.dt);
-    c.mark(prf_kind((L.dt == D3R_F16F8 || L.dt == D3R_F16X2F8) ? PRF_GEMM_F8 : PRF_GEMM, plan.cfg), 2.0 * M * (double)L.N * L.K, M, L.N, L.K);
-    c.chk(launch_gemm(L.dt, p, plan, c.st));
+    return p;
+}
+void gemm_linear(Ctx& c, const Lin& L, GemmParams& p) {
+    p.ldr = p.ldo;      // residual rows have the output's stride
+    launch(c, L.dt, p, PRF_GEMM, L.N, L.K, true);
+}
+
+// the input rows of an nn.Linear behind a LayerNorm: normalised rows, or (folded) the raw rows with their statistics -- norm_in() below
+struct NormIn { const void* rows; LnStats stats; };
+// q | k | v projection (EPI_HEADS): up to three regions of C columns each, stored per head in the attention kernel's layouts for the token grid `d`
+struct Region { int kind = 0; void* dst = nullptr; };
+void gemm_heads(Ctx& c, const Lin& L, const NormIn& in, int M, int C, int heads, const SideDim& d, Region r0, Region r1 = Region(), Region r2 = Region()) {
+    GemmParams p = lin_params(L, in.rows, C, M, in.stats);
+    p.epi = EPI_HEADS; p.head_c = C;
+    const Region r[3] = {r0, r1, r2};
+    for (int i = 0; i < 3; ++i) { p.head_kind[i] = r[i].kind; p.head_dst[i] = r[i].dst; }
+    p.heads = heads; p.ntok = d.N; p.tok_w = d.tw; p.ldv = d.ldv; p.rope_table = c.m->rope_table;
+    launch(c, L.dt, p, PRF_GEMM, L.N, L.K);
 }
 
 void conv(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const ConvW& w, int stride, int pad, void* out, int ldo,
-          int flags, const void* res1 = nullptr, const void* res2 = nullptr, void* out2 = nullptr, int n_store = -1) {
+          int flags, const void* res1 = nullptr, const void* res2 = nullptr, void* out2 = nullptr) {
     GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, w.w, w.b, w.cin_pad, w.Cout, w.k, stride, pad, c.m->zero_page);   // K, n_pad, n_rows: reg_conv's
-    if (n_store >= 0) p.n_store = n_store;
     p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.res1 = res1; p.res2 = res2; p.ldr = ldo; p.out2 = out2; p.ldo2 = ldo;
-    const GemmPlan plan = gemm_plan_for(p, c.m->dt);
-    c.mark(prf_kind(PRF_CONV, plan.cfg), 2.0 * p.M * (double)w.Cout * w.k * w.k * w.Cin, p.M, w.Cout, w.k * w.k * w.Cin);
-    c.chk(launch_gemm(c.m->dt, p, plan, c.st));
+    launch(c, c.m->dt, p, PRF_CONV, w.Cout, w.k * w.k * w.Cin);
 }
 
 // 3x3 convolution (stride 1, pad 1) + ReLU + Conv2d(Cout, 4, 1) + postprocess in one launch (EPI_HEAD4); false (nothing launched) when
@@ -461,8 +472,7 @@ bool conv_head4(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, co
     p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = cstride_conf; p.res1 = w4; p.res2 = b4; p.post = c.m->post;
     GemmPlan plan;
     if (!head4_tile(p, c.m->dt, plan)) return false;      // 512 x 128, else the forced 256 x 128 R (kernels.hpp)
-    c.mark(prf_kind(PRF_CONV, plan.cfg), 2.0 * p.M * (double)w.Cout * w.k * w.k * w.Cin, p.M, w.Cout, w.k * w.k * w.Cin);
-    c.chk(launch_gemm(c.m->dt, p, plan, c.st));
+    launch(c, c.m->dt, p, PRF_CONV, w.Cout, w.k * w.k * w.Cin, false, &plan);
     return true;
 }
 
@@ -677,416 +687,351 @@ extern "C" int d3r_model_profile_launch(d3r_model* m, int index, int* kind, int*
 // ---- the forward ---------------------------------------------------------------------------------------------
 namespace {
 
-void self_attention(Ctx& c, const void* xn, const Lin& qkv, int M, int C, int heads, int nimg, int ntok, int tok_w, int ldv, void* q, void* k,
-                    void* vt, void* ao, LnStats stats = LnStats()) {
-    const int kinds[3] = {HEAD_ROPE, HEAD_ROPE, HEAD_VT};
-    void* dsts[3] = {q, k, vt};
-    gemm_heads(c, xn, C, qkv, M, C, 3, kinds, dsts, heads, ntok, tok_w, ldv, stats);
-    AttnParams a;
-    a.q = q; a.k = k; a.vt = vt; a.out = ao; a.B = nimg; a.H = heads; a.Nq = ntok; a.Nk = ntok; a.ldv = ldv; a.scale = 0.125f;
-    a.out_dt = c.m->bdt;      // rows for the proj GEMM
-    c.mark(PRF_ATTN, 4.0 * nimg * heads * (double)ntok * ntok * 64, nimg * heads, ntok, ntok);
-    c.chk(launch_attention(c.m->dt, a, c.st));
-}
-
-void run_dpt(Ctx& c, const DptHead& D, Arena ar, const void* const hooks[4], const int hook_c[4], int B, int th, int tw, float* pts, float* conf) {
-    d3r_model* m = c.m;
-    const size_t eb = dt_bytes(m->dt);
-    const int N = th * tw;
-    const int th2 = (th - 1) / 2 + 1, tw2 = (tw - 1) / 2 + 1;
-    const int Hl[4] = {4 * th, 2 * th, th, th2}, Wl[4] = {4 * tw, 2 * tw, tw, tw2};
-    // reassemble: 1x1 conv (+ ConvTranspose / strided conv)
-    void* cmap[4];
-    for (int i = 0; i < 4; ++i) cmap[i] = ar.take((size_t)B * Hl[i] * Wl[i] * D.cstride[i] * eb);
-    void* t1 = ar.take((size_t)B * N * 768 * eb);
-    for (int i = 0; i < 4; ++i) {
-        const Lin& L = D.act1x1[i];
-        const bool direct = (i == 2);
-        gemm_linear(c, hooks[i], hook_c[i], L, B * N, EPI_T, direct ? cmap[2] : t1, D.cstride[i], nullptr, nullptr, 0, D.cstride[i]);
-        if (i < 2) {
-            GemmParams p;
-            p.act = t1; p.lda = D.cstride[i]; p.wgt = D.convt[i].w; p.bias = D.convt[i].b; p.M = B * N; p.K = D.convt[i].K;
-            p.n_pad = D.convt[i].n_pad; p.n_rows = D.convt[i].n_rows; p.n_store = D.convt[i].N; p.epi = EPI_CONVT; p.ksize = D.convt_k[i]; p.ct_cout = D.convt_coutp[i];
-            p.Hin = th; p.Win = tw; p.out = cmap[i]; p.ldo = D.cstride[i];
-            const int ldi[2] = {96, 192};
-            const GemmPlan plan = gemm_plan_for(p, m->dt);
-            c.mark(prf_kind(PRF_CONV, plan.cfg), 2.0 * p.M * (double)(D.convt_k[i] * D.convt_k[i] * ldi[i]) * ldi[i], p.M, D.convt_k[i] * D.convt_k[i] * ldi[i], ldi[i]);
-            c.chk(launch_gemm(m->dt, p, plan, c.st));
-        } else if (i == 3) {
-            conv(c, t1, B, th, tw, D.cstride[3], D.act3conv, 2, 1, cmap[3], D.cstride[3], 0);
-        }
-    }
-    // layer_rn: 3x3 -> 256 (no bias), plus ReLU copy for the residual units' pre-activation
-    void *r[4], *rr[4];
-    for (int i = 0; i < 4; ++i) {
-        const size_t bytes = (size_t)B * Hl[i] * Wl[i] * 256 * eb;
-        r[i] = ar.take(bytes); rr[i] = ar.take(bytes);
-        conv(c, cmap[i], B, Hl[i], Wl[i], D.cstride[i], D.layer_rn[i], 1, 1, r[i], 256, 0, nullptr, nullptr, rr[i]);
-    }
-    const size_t big = (size_t)B * Hl[0] * Wl[0] * 256 * eb;
-    void *tA = ar.take(big), *tB = ar.take(big), *tC = ar.take(big);
-    void* path = nullptr;  // output of the previous refinenet (already upsampled)
-    for (int lvl = 3; lvl >= 0; --lvl) {
-        const Refine& R = D.rn[lvl];
-        const int H = Hl[lvl], W = Wl[lvl];
-        const void* skip;      // input of resConfUnit2 (un-activated) ...
-        const void* skip_relu; // ... and its ReLU
-        if (lvl == 3) {
-            skip = r[3]; skip_relu = rr[3];
-        } else {
-            conv(c, rr[lvl], B, H, W, 256, R.r1c1, 1, 1, tA, 256, GF_RELU);
-            conv(c, tA, B, H, W, 256, R.r1c2, 1, 1, tB, 256, 0, m->cfg.dpt_skip_relu_inplace ? rr[lvl] : r[lvl], path, tC);
-            skip = tB; skip_relu = tC;
-        }
-        conv(c, skip_relu, B, H, W, 256, R.r2c1, 1, 1, tA, 256, GF_RELU);
-        void* o = (lvl == 3) ? tB : tC;
-        conv(c, tA, B, H, W, 256, R.r2c2, 1, 1, o, 256, 0, m->cfg.dpt_skip_relu_inplace ? skip_relu : skip);
-        // out_conv (1x1) commutes with the bilinear upsampling (both linear, weights sum to 1): run it at low resolution
-        gemm_linear(c, o, 256, R.outc, B * H * W, EPI_T, tA, 256);
-        const int Ho = lvl == 3 ? Hl[2] : 2 * H, Wo = lvl == 3 ? Wl[2] : 2 * W;  // dpt_head.py:57 crops refinenet4 to layer 3's size
-        void* np = ar.take((size_t)B * Ho * Wo * 256 * eb);
-        D3R_OTHER(launch_upsample2x(m->dt, tA, np, nullptr, B, H, W, 256, 256, Ho, Wo, c.st));
-        path = np;
-    }
-    // head: 3x3 256->128, x2, 3x3 128->128 + ReLU, 1x1 128->4 + postprocess
-    const int H8 = 8 * th, W8 = 8 * tw;
-    void* h0 = ar.take((size_t)B * H8 * W8 * 128 * eb);
-    conv(c, path, B, H8, W8, 256, D.head0, 1, 1, h0, 128, 0);
-    void* h1 = ar.take((size_t)B * 4 * H8 * W8 * 128 * eb);
-    D3R_OTHER(launch_upsample2x(m->dt, h0, h1, nullptr, B, H8, W8, 128, 128, 2 * H8, 2 * W8, c.st));
-    void* h2 = ar.take((size_t)B * 4 * H8 * W8 * 128 * eb);
-    // Split-fp16, enough pixels for the 512 x 128 tile (every wave then holds all 128 channels of its 64 pixels): the 1x1 convolution and
-    // the postprocess run in the epilogue of the last 3x3 convolution, on its fp32 accumulators -- the 128-channel full-resolution map
-    // (3.2 GB per head at 32 pairs) is neither written nor read back. D3R_HEAD_FUSE=0: the two-kernel route (test A/B).
-    bool fused = false;
-    if (m->dt == D3R_F16X3) {
-        const char* e = getenv("D3R_HEAD_FUSE");
-        if (!(e && e[0] == '0')) fused = conv_head4(c, h1, B, 2 * H8, 2 * W8, 128, D.head2, D.head4_w, D.head4_b, pts, conf, m->out_pstride, m->out_cstride);
-    }
-    if (!fused) {
-        conv(c, h1, B, 2 * H8, 2 * W8, 128, D.head2, 1, 1, h2, 128, GF_RELU);
-        D3R_OTHER(launch_head_final(m->dt, h2, 128, D.head4_w, D.head4_b, pts, conf, (size_t)B * 4 * H8 * W8, m->out_pstride, m->out_cstride, m->post, c.st));
-    }
-    if (ar.base && ar.off > ar.cap) c.rc = D3R_ERR_ALLOC;
-}
-
-// bytes of the DPT head arena for `bc` images (the allocation sequence of run_dpt)
-size_t dpt_arena_bytes(const d3r_model* m, const DptHead& D, int bc, int th, int tw) {
-    const size_t eb = dt_bytes(m->dt);
-    const int N = th * tw;
-    const int th2 = (th - 1) / 2 + 1, tw2 = (tw - 1) / 2 + 1;
-    const int Hl[4] = {4 * th, 2 * th, th, th2}, Wl[4] = {4 * tw, 2 * tw, tw, tw2};
-    Arena sub(nullptr, 0);
-    for (int i = 0; i < 4; ++i) sub.take((size_t)bc * Hl[i] * Wl[i] * D.cstride[i] * eb);
-    sub.take((size_t)bc * N * 768 * eb);
-    for (int i = 0; i < 4; ++i) { sub.take((size_t)bc * Hl[i] * Wl[i] * 256 * eb); sub.take((size_t)bc * Hl[i] * Wl[i] * 256 * eb); }
-    for (int i = 0; i < 3; ++i) sub.take((size_t)bc * Hl[0] * Wl[0] * 256 * eb);
-    for (int lvl = 3; lvl >= 0; --lvl) {
-        const int Ho = lvl == 3 ? Hl[2] : 2 * Hl[lvl], Wo = lvl == 3 ? Wl[2] : 2 * Wl[lvl];
-        sub.take((size_t)bc * Ho * Wo * 256 * eb);
-    }
-    sub.take((size_t)bc * 64 * N * 128 * eb);
-    sub.take((size_t)bc * 256 * N * 128 * eb);
-    sub.take((size_t)bc * 256 * N * 128 * eb);
-    return ((sub.off + 255) & ~(size_t)255) + 256;
-}
-
-// returns bytes needed when ws == nullptr (dry run), else runs
 // Phases: the encoder runs over `nimg` images (img1 holds the first nimg1 of them, img2 the rest: forward passes B + B,
 // d3r_model_encode passes everything in img1) and leaves the normalised features [nimg][N][Ce] in `feat`; the decoder +
 // heads run over B pairs whose features are feat[0..B) (view 1) and feat[B..2B) (view 2). forward = both phases with
 // feat inside the workspace; encode / decode run one phase with a caller-owned feature buffer.
 enum { PH_ENCODE = 1, PH_DECODE = 2 };
-// The two views of a pair may have different sizes (dust3r/model.py:148-150: the reference then encodes them separately): every
-// per-side quantity of the decoder / heads is indexed by side -- token grid (th, tw), tokens per image N, rows M = B N, V^T row
-// stride -- and cross attention runs Nq != Nk. With equal sizes this is the old schedule bit for bit.
-struct SideDim { int H, W, th, tw, N, ldv; };
-static SideDim side_dim(int H, int W, int ps) {
-    SideDim d;
-    d.H = H; d.W = W; d.th = H / ps; d.tw = W / ps; d.N = d.th * d.tw; d.ldv = rup(d.N, 64);
+// one call of the engine, as its entry point describes it
+struct Call {
+    int phases = 0;
+    const float* img1 = nullptr; const float* img2 = nullptr; int nimg1 = 0, nimg = 0;
+    void* feat = nullptr;                   // caller-owned feature buffer (encode / decode); null: inside the workspace
+    int B = 0;
+    SideDim d[2];
+    float* pts[2] = {nullptr, nullptr}; float* conf[2] = {nullptr, nullptr};
+    int pstride = 3, cstride = 1;           // output element strides between pixels (8, 8: the packed entry points)
+};
+
+// row counts of a call. Shared scratch is sized for the wider of encoder / decoder (Cmax, Hmax); Ge, Gd: 32-column groups of a folded LayerNorm's partial sums
+struct Dims { int Ce, Cd, He, Hd, Cmax, Hmax, Ge, Gd, Me, Ms[2], Roff[2], M2d, Mmax, M2, ldv_max, nvt, chunk; bool same, do_enc, do_dec; size_t eb; };
+Dims dims_of(const d3r_model* m, const Call& k) {
+    const d3r_model_config& cf = m->cfg;
+    const SideDim &d0 = k.d[0], &d1 = k.d[1];
+    Dims d;
+    d.Ce = cf.enc_embed_dim; d.Cd = cf.dec_embed_dim; d.He = cf.enc_num_heads; d.Hd = cf.dec_num_heads;
+    d.Cmax = d.Ce > d.Cd ? d.Ce : d.Cd; d.Hmax = d.He > d.Hd ? d.He : d.Hd; d.Ge = d.Ce / 32; d.Gd = d.Cd / 32;
+    d.same = d0.H == d1.H && d0.W == d1.W; d.do_enc = (k.phases & PH_ENCODE) != 0; d.do_dec = (k.phases & PH_DECODE) != 0;
+    // encoder rows: one pass over all images when the views share a size, else one pass per view (view 1 rows first)
+    d.Me = !d.do_enc ? 0 : (d.same ? k.nimg * d0.N : k.nimg1 * d0.N + (k.nimg - k.nimg1) * d1.N);
+    d.Ms[0] = d.do_dec ? k.B * d0.N : 0; d.Ms[1] = d.do_dec ? k.B * d1.N : 0;     // decoder rows per side
+    d.Roff[0] = 0; d.Roff[1] = d.Ms[0];                                           // first row of a side in the two-sided buffers
+    d.M2d = d.Ms[0] + d.Ms[1];
+    d.Mmax = d.Ms[0] > d.Ms[1] ? d.Ms[0] : d.Ms[1];                               // a side's scratch part holds its own rows OR the other view's (cross attention)
+    d.M2 = d.Me > 2 * d.Mmax ? d.Me : 2 * d.Mmax;                                 // rows of the shared scratch buffers
+    d.ldv_max = d0.ldv > d1.ldv ? d0.ldv : d1.ldv;
+    d.nvt = (d.do_enc ? k.nimg : 0) > 2 * (d.do_dec ? k.B : 0) ? k.nimg : 2 * k.B;   // images the v^T buffer must hold
+    d.chunk = k.B < 32 ? k.B : 32;   // 288 GB of HBM: batch the head as wide as the encoder (low-resolution stages need the rows)
+    d.eb = dt_bytes(m->dt);
     return d;
 }
 
-size_t forward_impl(d3r_model* m, void* ws, size_t ws_cap, int phases, const float* img1, const float* img2, int nimg1, int nimg, void* feat_ext,
-                    int B, SideDim d0, SideDim d1, float* pts1, float* conf1, float* pts2, float* conf2, hipStream_t st, int* rc_out) {
-    const d3r_model_config& cf = m->cfg;
-    const int ps = cf.patch_size;
-    const SideDim D[2] = {d0, d1};
-    const bool same = d0.H == d1.H && d0.W == d1.W;
-    const int Ce = cf.enc_embed_dim, Cd = cf.dec_embed_dim, He = cf.enc_num_heads, Hd = cf.dec_num_heads;
-    const int Cmax = Ce > Cd ? Ce : Cd, Hmax = He > Hd ? He : Hd;     // shared scratch is sized for the wider of encoder / decoder
-    const bool do_enc = (phases & PH_ENCODE) != 0, do_dec = (phases & PH_DECODE) != 0;
-    // encoder rows: one pass over all images when the views share a size, else one pass per view (view 1 rows first)
-    const int Me = !do_enc ? 0 : (same ? nimg * d0.N : nimg1 * d0.N + (nimg - nimg1) * d1.N);
-    const int Ms[2] = {do_dec ? B * d0.N : 0, do_dec ? B * d1.N : 0};     // decoder rows per side
-    const int Roff[2] = {0, Ms[0]};                                       // first row of a side in the two-sided buffers
-    const int M2d = Ms[0] + Ms[1];
-    const int Mmax = Ms[0] > Ms[1] ? Ms[0] : Ms[1];                       // a side's scratch part holds its own rows OR the other view's (cross attention)
-    const int M2 = Me > 2 * Mmax ? Me : 2 * Mmax;                         // rows of the shared scratch buffers
-    const int ldv_max = d0.ldv > d1.ldv ? d0.ldv : d1.ldv;
-    const int nvt = (do_enc ? nimg : 0) > 2 * (do_dec ? B : 0) ? nimg : 2 * B;   // images the v^T buffer must hold
-    const size_t eb = dt_bytes(m->dt);
-    const bool dry = ws == nullptr;
-    Arena ar(ws, ws_cap);
-    Ctx c{m, st};
-    c.st0 = st;
+// ---- workspace layouts: ONE sequence of takes per arena. On Arena(nullptr, 0) it sizes the arena, on the real base it yields the pointers. ----
+struct DptGrid { int H[4], W[4]; };       // the four reassembled maps of a th x tw token grid
+DptGrid dpt_grid(int th, int tw) { return DptGrid{{4 * th, 2 * th, th, (th - 1) / 2 + 1}, {4 * tw, 2 * tw, tw, (tw - 1) / 2 + 1}}; }
+struct DptBufs { void *cmap[4], *t1, *r[4], *rr[4], *tA, *tB, *tC, *up[4], *h0, *h1, *h2; };      // up[lvl]: refinenet lvl's upsampled output
+DptBufs dpt_layout(const d3r_model* m, const DptHead& D, Arena& ar, int B, int th, int tw) {
+    const size_t eb = dt_bytes(m->dt), px8 = (size_t)B * 8 * th * 8 * tw;
+    const DptGrid g = dpt_grid(th, tw);
+    DptBufs b;
+    for (int i = 0; i < 4; ++i) b.cmap[i] = ar.take((size_t)B * g.H[i] * g.W[i] * D.cstride[i] * eb);
+    b.t1 = ar.take((size_t)B * th * tw * 768 * eb);
+    for (int i = 0; i < 4; ++i) { b.r[i] = ar.take((size_t)B * g.H[i] * g.W[i] * 256 * eb); b.rr[i] = ar.take((size_t)B * g.H[i] * g.W[i] * 256 * eb); }
+    for (void** t : {&b.tA, &b.tB, &b.tC}) *t = ar.take((size_t)B * g.H[0] * g.W[0] * 256 * eb);
+    for (int lvl = 3; lvl >= 0; --lvl)      // dpt_head.py:57 crops refinenet4's output to layer 3's size
+        b.up[lvl] = ar.take((size_t)B * (lvl == 3 ? g.H[2] : 2 * g.H[lvl]) * (lvl == 3 ? g.W[2] : 2 * g.W[lvl]) * 256 * eb);
+    b.h0 = ar.take(px8 * 128 * eb); b.h1 = ar.take(4 * px8 * 128 * eb); b.h2 = ar.take(4 * px8 * 128 * eb);
+    return b;
+}
 
-    float* x = (float*)ar.take((size_t)Me * Ce * 4);
-    void* xn = ar.take((size_t)M2 * Cmax * eb);
-    void* q = ar.take((size_t)M2 * Cmax * eb);
-    void* k = ar.take((size_t)M2 * Cmax * eb);
-    void* vt = ar.take((size_t)nvt * Hmax * 64 * ldv_max * eb);
-    void* ao = ar.take((size_t)M2 * Cmax * eb);
-    void* hb = ar.take((size_t)M2 * 4 * Cmax * eb);   // MLP hidden; also holds the gathered patches
-    void* encn = feat_ext ? feat_ext : ar.take((size_t)(Me > M2d ? Me : M2d) * Ce * eb);
-    float* f[2] = {(float*)ar.take((size_t)M2d * Cd * 4), (float*)ar.take((size_t)M2d * Cd * 4)};
-    void* yn = ar.take((size_t)2 * Mmax * Cd * eb);
-    void* hook[2][3];
+// folded LayerNorm (d3r_model::ln_fold): partial sums [rows][C / 32][2], rstd / -mean rstd per row
+struct FoldSet { float *part = nullptr, *rs = nullptr, *nm = nullptr; };
+FoldSet take_fold(Arena& ar, int rows, int groups) {
+    FoldSet s;
+    s.part = (float*)ar.take((size_t)rows * groups * 8); s.rs = (float*)ar.take((size_t)rows * 4 + 16); s.nm = (float*)ar.take((size_t)rows * 4 + 16);
+    return s;
+}
+struct Workspace {
+    float* x; void *xn, *q, *k, *vt, *ao, *hb, *encn; float* f[2]; void* yn; void* hook[2][3]; float* lin_out;
+    // fold sets: one for the encoder (e), one per decoder LAYER OUTPUT and buffer (l: both sides' rows, read by the own side's norm1 and the other side's norm_y) with
+    // the raw typed copy fr of that output, one per side for the block-internal norm2 / norm3 (s)
+    FoldSet e, l[2], s[2]; void* fr[2] = {nullptr, nullptr};
+    void* head_arena[2]; size_t head_bytes = 0;     // the DPT head's arena of each side
+    size_t bytes = 0;                               // the whole workspace
+};
+Workspace ws_layout(const d3r_model* m, const Call& k, const Dims& d, Arena& ar) {
+    const size_t eb = d.eb, scratch = (size_t)d.M2 * d.Cmax * eb;
+    const int ps = m->cfg.patch_size;
+    Workspace w;
+    w.x = (float*)ar.take((size_t)d.Me * d.Ce * 4);
+    w.xn = ar.take(scratch); w.q = ar.take(scratch); w.k = ar.take(scratch);
+    w.vt = ar.take((size_t)d.nvt * d.Hmax * 64 * d.ldv_max * eb);
+    w.ao = ar.take(scratch);
+    w.hb = ar.take(4 * scratch);   // MLP hidden; also holds the gathered patches
+    w.encn = k.feat ? k.feat : ar.take((size_t)(d.Me > d.M2d ? d.Me : d.M2d) * d.Ce * eb);
+    for (int b = 0; b < 2; ++b) w.f[b] = (float*)ar.take((size_t)d.M2d * d.Cd * 4);
+    w.yn = ar.take((size_t)2 * d.Mmax * d.Cd * eb);
     for (int s = 0; s < 2; ++s)
-        for (int j = 0; j < 3; ++j) hook[s][j] = ar.take((size_t)Ms[s] * Cd * eb);
-    float* lin_out = cf.head_type == 0 ? (float*)ar.take((size_t)M2d * 4 * ps * ps * 4) : nullptr;
-    // folded LayerNorm (d3r_model::ln_fold): partial sums [rows][C / 32][2], rstd / -mean rstd per row -- one set for the encoder (e_), one per
-    // decoder LAYER OUTPUT and buffer (l_: both sides' rows, read by the own side's norm1 and the other side's norm_y) with the raw typed copy fr
-    // of that output, one per side for the block-internal norm2 / norm3 (s_)
-    const bool fold = m->ln_fold;
-    const int Ge = Ce / 32, Gd = Cd / 32;
-    // rows up to which a folded LayerNorm's statistics are formed in the consumer GEMM's prologue instead of by a launch (D3R_LN_INLINE_ROWS; 0 = always launch)
-    const int inline_rows = m->ln_inline_rows;
-    float *e_part = nullptr, *e_rs = nullptr, *e_nm = nullptr, *l_part[2] = {nullptr, nullptr}, *l_rs[2] = {nullptr, nullptr}, *l_nm[2] = {nullptr, nullptr};
-    float *s_part[2] = {nullptr, nullptr}, *s_rs[2] = {nullptr, nullptr}, *s_nm[2] = {nullptr, nullptr};
-    void* fr[2] = {nullptr, nullptr};
-    if (fold) {
-        e_part = (float*)ar.take((size_t)Me * Ge * 8); e_rs = (float*)ar.take((size_t)Me * 4 + 16); e_nm = (float*)ar.take((size_t)Me * 4 + 16);
-        for (int b = 0; b < 2; ++b) {
-            fr[b] = ar.take((size_t)M2d * Cd * eb);
-            l_part[b] = (float*)ar.take((size_t)M2d * Gd * 8); l_rs[b] = (float*)ar.take((size_t)M2d * 4 + 16); l_nm[b] = (float*)ar.take((size_t)M2d * 4 + 16);
-            s_part[b] = (float*)ar.take((size_t)Mmax * Gd * 8); s_rs[b] = (float*)ar.take((size_t)Mmax * 4 + 16); s_nm[b] = (float*)ar.take((size_t)Mmax * 4 + 16);
+        for (int j = 0; j < 3; ++j) w.hook[s][j] = ar.take((size_t)d.Ms[s] * d.Cd * eb);
+    w.lin_out = m->cfg.head_type == 0 ? (float*)ar.take((size_t)d.M2d * 4 * ps * ps * 4) : nullptr;
+    if (m->ln_fold) {
+        w.e = take_fold(ar, d.Me, d.Ge);
+        for (int b = 0; b < 2; ++b) { w.fr[b] = ar.take((size_t)d.M2d * d.Cd * eb); w.l[b] = take_fold(ar, d.M2d, d.Gd); w.s[b] = take_fold(ar, d.Mmax, d.Gd); }
+    }
+    for (int s = 0; s < 2 && m->cfg.head_type == 1 && d.do_dec; ++s) {      // both sides' arenas hold a chunk of the larger view
+        Arena sub(nullptr, 0);
+        dpt_layout(m, m->dpt[0], sub, d.chunk, k.d[s].th, k.d[s].tw);
+        const size_t a = ((sub.off + 255) & ~(size_t)255) + 256;
+        w.head_bytes = a > w.head_bytes ? a : w.head_bytes;
+    }
+    for (int s = 0; s < 2; ++s) w.head_arena[s] = ar.take(w.head_bytes);
+    w.bytes = ar.off + 256;
+    return w;
+}
+
+// ---- the residual stream of a transformer block in its two representations -------------------------------------------------------------------
+// M rows of the stream at one point of a block. LayerNorm-kernel engines: fp32 rows `f32` (`raw`: a typed copy where one is wanted -- the DPT hooks).
+// ln_fold engines: the typed rows `raw` ARE the stream (GF_X3RES) and carry a statistics set: `part` is written by the GEMM that stores the rows (null: none
+// wanted, a LayerNorm kernel follows), rs / nm by an ln_finalize launch behind it or, up to ln_inline_rows rows (`inl`), by the consumer GEMM's prologue.
+struct Res { int M = 0; float* f32 = nullptr; void* raw = nullptr; float* part = nullptr; float* rs = nullptr; float* nm = nullptr; bool inl = false; };
+Res rows_of(const d3r_model* m, int M, float* f32, void* raw, const FoldSet& s, int first = 0, int groups = 0) {
+    Res r; r.M = M; r.f32 = f32; r.raw = raw; r.inl = M <= m->ln_inline_rows;
+    if (s.part) { r.part = s.part + (size_t)first * groups * 2; r.rs = s.rs + first; r.nm = s.nm + first; }
+    return r;
+}
+// normalised input of the nn.Linear behind LayerNorm `ln`: the LayerNorm kernel into `scratch`, or (folded) nothing -- the raw rows and their statistics
+NormIn norm_in(Ctx& c, const Res& r, const LNp& ln, void* scratch, int C) {
+    if (c.m->ln_fold) return NormIn{r.raw, LnStats{r.rs, r.nm, r.inl ? r.part : nullptr}};
+    D3R_OTHER(launch_layernorm(c.m->bdt, r.f32, ln.g, ln.b, scratch, r.M, C, 1e-6f, c.st));
+    return NormIn{scratch, LnStats()};
+}
+// out = in + Linear(act) (`in` may be empty): fp32 rows, or (folded) typed rows + partial sums and the ln_finalize launch directly behind their producer
+void residual_linear(Ctx& c, const Lin& L, const void* act, int lda, const Res& in, const Res& out, int C, bool typed_copy = false) {
+    const bool fold = c.m->ln_fold;
+    GemmParams p = lin_params(L, act, lda, out.M);
+    p.epi = EPI_F32; p.ldo = C;
+    if (fold) { p.flags = GF_X3RES; p.res1 = in.raw; p.ln_part = out.part; }
+    else { p.out = out.f32; p.res1 = in.f32; }
+    if (fold || typed_copy) { p.out2 = out.raw; p.ldo2 = C; }
+    gemm_linear(c, L, p);
+    if (fold && out.part && !out.inl) D3R_OTHER(launch_ln_finalize(out.part, out.M, C, 1e-6f, out.rs, out.nm, c.st));
+}
+// a LayerNorm whose output leaves the blocks (enc_norm, dec_norm): always a kernel
+void final_norm(Ctx& c, const Res& r, const LNp& ln, void* dst, int C) {
+    if (c.m->ln_fold) D3R_OTHER(launch_layernorm_x3in(r.raw, ln.g, ln.b, dst, r.M, C, 1e-6f, c.st));
+    else D3R_OTHER(launch_layernorm(c.m->dt, r.f32, ln.g, ln.b, dst, r.M, C, 1e-6f, c.st));
+}
+// a Linear with nothing but an epilogue and one output (n_store: columns written when not L.N)
+void plain_linear(Ctx& c, const Lin& L, const NormIn& in, int lda, int M, int epi, void* out, int ldo, int n_store = -1) {
+    GemmParams p = lin_params(L, in.rows, lda, M, in.stats);
+    p.epi = epi; p.out = out; p.ldo = ldo;
+    if (n_store >= 0) p.n_store = n_store;
+    gemm_linear(c, L, p);
+}
+// softmax(q k^T / 8) v over nimg x heads problems: qd = the queries' token grid, kd = the keys' (self attention: the same)
+struct AttnBufs { void *q, *k, *vt, *ao; };
+void attention(Ctx& c, const AttnBufs& b, int nimg, int heads, const SideDim& qd, const SideDim& kd) {
+    AttnParams a;
+    a.q = b.q; a.k = b.k; a.vt = b.vt; a.out = b.ao; a.B = nimg; a.H = heads; a.Nq = qd.N; a.Nk = kd.N; a.ldv = kd.ldv; a.scale = 0.125f;
+    a.out_dt = c.m->bdt;      // rows for the proj GEMM
+    c.mark(PRF_ATTN, 4.0 * nimg * heads * (double)qd.N * kd.N * 64, nimg * heads, qd.N, kd.N);
+    c.chk(launch_attention(c.m->dt, a, c.st));
+}
+
+// ---- the DPT head of one side for B images of a th x tw token grid, in its arena `ar` ------------------------------------------------------------
+void run_dpt(Ctx& c, const DptHead& D, Arena ar, const Call& k, const void* const hooks[4], const int hook_c[4], int B, int th, int tw, float* pts, float* conf) {
+    d3r_model* m = c.m;
+    const DptGrid g = dpt_grid(th, tw);
+    const DptBufs b = dpt_layout(m, D, ar, B, th, tw);
+    // reassemble: 1x1 conv (+ ConvTranspose / strided conv)
+    for (int i = 0; i < 4; ++i) {
+        plain_linear(c, D.act1x1[i], NormIn{hooks[i]}, hook_c[i], B * th * tw, EPI_T, i == 2 ? b.cmap[2] : b.t1, D.cstride[i], D.cstride[i]);
+        if (i < 2) {
+            const int ldi[2] = {96, 192}, kk = D.convt_k[i] * D.convt_k[i];
+            GemmParams p = lin_params(D.convt[i], b.t1, D.cstride[i], B * th * tw);
+            p.epi = EPI_CONVT; p.ksize = D.convt_k[i]; p.ct_cout = D.convt_coutp[i]; p.Hin = th; p.Win = tw; p.out = b.cmap[i]; p.ldo = D.cstride[i];
+            launch(c, m->dt, p, PRF_CONV, kk * ldi[i], ldi[i]);
+        } else if (i == 3) {
+            conv(c, b.t1, B, th, tw, D.cstride[3], D.act3conv, 2, 1, b.cmap[3], D.cstride[3], 0);
         }
     }
-    const size_t common_end = (ar.off + 255) & ~(size_t)255;
-    const int chunk = B < 32 ? B : 32;   // 288 GB of HBM: batch the head as wide as the encoder (low-resolution stages need the rows)
-    size_t head_arena = 0;
-    if (cf.head_type == 1 && do_dec)
-        for (int s = 0; s < 2; ++s) {
-            const size_t a = dpt_arena_bytes(m, m->dpt[0], chunk, D[s].th, D[s].tw);
-            head_arena = a > head_arena ? a : head_arena;
+    // layer_rn: 3x3 -> 256 (no bias), plus ReLU copy for the residual units' pre-activation
+    for (int i = 0; i < 4; ++i) conv(c, b.cmap[i], B, g.H[i], g.W[i], D.cstride[i], D.layer_rn[i], 1, 1, b.r[i], 256, 0, nullptr, nullptr, b.rr[i]);
+    void* path = nullptr;  // output of the previous refinenet (already upsampled)
+    for (int lvl = 3; lvl >= 0; --lvl) {
+        const Refine& R = D.rn[lvl];
+        const int H = g.H[lvl], W = g.W[lvl];
+        const void* skip = b.r[3];         // input of resConfUnit2 (un-activated) ...
+        const void* skip_relu = b.rr[3];   // ... and its ReLU
+        if (lvl != 3) {
+            conv(c, b.rr[lvl], B, H, W, 256, R.r1c1, 1, 1, b.tA, 256, GF_RELU);
+            conv(c, b.tA, B, H, W, 256, R.r1c2, 1, 1, b.tB, 256, 0, m->cfg.dpt_skip_relu_inplace ? b.rr[lvl] : b.r[lvl], path, b.tC);
+            skip = b.tB; skip_relu = b.tC;
         }
+        conv(c, skip_relu, B, H, W, 256, R.r2c1, 1, 1, b.tA, 256, GF_RELU);
+        void* o = (lvl == 3) ? b.tB : b.tC;
+        conv(c, b.tA, B, H, W, 256, R.r2c2, 1, 1, o, 256, 0, m->cfg.dpt_skip_relu_inplace ? skip_relu : skip);
+        // out_conv (1x1) commutes with the bilinear upsampling (both linear, weights sum to 1): run it at low resolution
+        plain_linear(c, R.outc, NormIn{o}, 256, B * H * W, EPI_T, b.tA, 256);
+        D3R_OTHER(launch_upsample2x(m->dt, b.tA, b.up[lvl], nullptr, B, H, W, 256, 256, lvl == 3 ? g.H[2] : 2 * H, lvl == 3 ? g.W[2] : 2 * W, c.st));
+        path = b.up[lvl];
+    }
+    // head: 3x3 256->128, x2, 3x3 128->128 + ReLU, 1x1 128->4 + postprocess
+    const int H8 = 8 * th, W8 = 8 * tw;
+    conv(c, path, B, H8, W8, 256, D.head0, 1, 1, b.h0, 128, 0);
+    D3R_OTHER(launch_upsample2x(m->dt, b.h0, b.h1, nullptr, B, H8, W8, 128, 128, 2 * H8, 2 * W8, c.st));
+    // Split-fp16, enough pixels for the 512 x 128 tile (every wave then holds all 128 channels of its 64 pixels): the 1x1 convolution and
+    // the postprocess run in the epilogue of the last 3x3 convolution, on its fp32 accumulators -- the 128-channel full-resolution map
+    // (3.2 GB per head at 32 pairs) is neither written nor read back. D3R_HEAD_FUSE=0: the two-kernel route (test A/B).
+    const char* e = m->dt == D3R_F16X3 ? getenv("D3R_HEAD_FUSE") : "0";
+    if (!(e && e[0] == '0') && conv_head4(c, b.h1, B, 2 * H8, 2 * W8, 128, D.head2, D.head4_w, D.head4_b, pts, conf, k.pstride, k.cstride)) return;
+    conv(c, b.h1, B, 2 * H8, 2 * W8, 128, D.head2, 1, 1, b.h2, 128, GF_RELU);
+    D3R_OTHER(launch_head_final(m->dt, b.h2, 128, D.head4_w, D.head4_b, pts, conf, (size_t)B * 4 * H8 * W8, k.pstride, k.cstride, m->post, c.st));
+}
 
-    if (!dry) {
-        // stream plan: encoder on the caller's stream; then side 0 stays there and side 1 runs on the model's second
-        // stream, re-joined at every layer boundary (each side reads the other's previous-layer output) and at the end.
-        // Each side has its own part of every scratch buffer and its own head arena.
-        const bool two = m->two_streams && !m->prof_on && m->side != nullptr;
-        hipStream_t S[2] = {st, two ? m->side : st};
-        auto cross_sync = [&]() {
-            if (!two) return;
-            c.chk(hipEventRecord(m->ev_main, S[0]));
-            c.chk(hipEventRecord(m->ev_side, S[1]));
-            c.chk(hipStreamWaitEvent(S[0], m->ev_side, 0));
-            c.chk(hipStreamWaitEvent(S[1], m->ev_main, 0));
-        };
-        if (d0.ldv != d0.N || d1.ldv != d1.N) D3R_OTHER(hipMemsetAsync(vt, 0, (size_t)nvt * Hmax * 64 * ldv_max * eb, st));
-        if (do_enc) {
-            // ---- encoder: all images of the call in one pass when the views share a size (model.py:142-151 concatenates the
-            // two views), else view 1's images then view 2's (model.py:148-150) -----------------------------------------------
-            const size_t pk = 3 * (size_t)ps * ps;
-            // Encoder work is a list of GROUPS of images of one size: one group (both views) when the views share a size, else one per view, one after the
-            // other on the caller's stream, each in the scratch buffers from row 0.
-            struct EncGroup { const float* im[2]; int n[2]; const SideDim* dd; size_t row0; };
-            EncGroup groups[2];
-            int ngroups = 0;
-            if (same) {
-                groups[ngroups++] = EncGroup{{img1, img2}, {nimg1, nimg - nimg1}, &D[0], 0};
-            } else {
-                if (nimg1 > 0) groups[ngroups++] = EncGroup{{img1, nullptr}, {nimg1, 0}, &D[0], 0};
-                if (nimg > nimg1) groups[ngroups++] = EncGroup{{img2, nullptr}, {nimg - nimg1, 0}, &D[1], (size_t)nimg1 * d0.N};
-            }
-            // phase -1: patches + patch embedding; 0 .. depth - 1: block l; depth: enc_norm
-            auto enc_phase = [&](const EncGroup& g, int phase) {
-                const SideDim& dd = *g.dd;
-                const int n_img = g.n[0] + g.n[1];
-                const int Mp = n_img * dd.N;
-                float* xp = x + g.row0 * Ce;
-                void* gxn = xn;
-                void* gq = q;
-                void* gk = k;
-                void* gvt = vt;
-                void* gao = ao;
-                void* ghb = hb;        // hidden rows; the patches of the group start at the same place
-                float* gpart = fold ? e_part : nullptr;
-                float* grs = fold ? e_rs : nullptr;
-                float* gnm = fold ? e_nm : nullptr;
-                const bool inl = fold && Mp <= inline_rows;
-                const LnStats es{grs, gnm, inl ? gpart : nullptr};
-                if (phase < 0) {
-                    if (g.n[0] > 0) D3R_OTHER(launch_patchify(m->dt, g.im[0], ghb, g.n[0], dd.H, dd.W, ps, c.st));
-                    if (g.n[1] > 0) D3R_OTHER(launch_patchify(m->dt, g.im[1], (char*)ghb + (size_t)g.n[0] * dd.N * pk * eb, g.n[1], dd.H, dd.W, ps, c.st));
-                    // fold: every residual epilogue stores the typed rows (the residual stream itself, GF_X3RES) and their partial sums; the LayerNorm is two fmas in
-                    // the epilogue of the nn.Linear behind it (weights packed as W diag(gamma)) -- DESIGN 4.0
-                    if (fold) gemm_linear(c, ghb, (int)pk, m->patch, Mp, EPI_F32, nullptr, Ce, nullptr, gxn, Ce, -1, GF_X3RES, LnStats(), gpart);
-                    else gemm_linear(c, ghb, (int)pk, m->patch, Mp, EPI_F32, xp, Ce);
-                } else if (phase < cf.enc_depth) {
-                    const EncBlk& b = m->enc[phase];
-                    if (fold) {
-                        const bool last = phase + 1 == cf.enc_depth;        // enc_norm (a kernel) follows: no sums
-                        if (!inl) D3R_OTHER(launch_ln_finalize(gpart, Mp, Ce, 1e-6f, grs, gnm, c.st));
-                        self_attention(c, gxn, b.qkv, Mp, Ce, He, n_img, dd.N, dd.tw, dd.ldv, gq, gk, gvt, gao, es);
-                        gemm_linear(c, gao, Ce, b.proj, Mp, EPI_F32, nullptr, Ce, gxn, gxn, Ce, -1, GF_X3RES, LnStats(), gpart);
-                        if (!inl) D3R_OTHER(launch_ln_finalize(gpart, Mp, Ce, 1e-6f, grs, gnm, c.st));
-                        gemm_linear(c, gxn, Ce, b.fc1, Mp, EPI_GELU, ghb, 4 * Ce, nullptr, nullptr, 0, -1, 0, es);
-                        gemm_linear(c, ghb, 4 * Ce, b.fc2, Mp, EPI_F32, nullptr, Ce, gxn, gxn, Ce, -1, GF_X3RES, LnStats(), last ? nullptr : gpart);
-                    } else {
-                        D3R_OTHER(launch_layernorm(m->bdt, xp, b.n1.g, b.n1.b, gxn, Mp, Ce, 1e-6f, c.st));
-                        self_attention(c, gxn, b.qkv, Mp, Ce, He, n_img, dd.N, dd.tw, dd.ldv, gq, gk, gvt, gao);
-                        gemm_linear(c, gao, Ce, b.proj, Mp, EPI_F32, xp, Ce, xp);
-                        D3R_OTHER(launch_layernorm(m->bdt, xp, b.n2.g, b.n2.b, gxn, Mp, Ce, 1e-6f, c.st));
-                        gemm_linear(c, gxn, Ce, b.fc1, Mp, EPI_GELU, ghb, 4 * Ce);
-                        gemm_linear(c, ghb, 4 * Ce, b.fc2, Mp, EPI_F32, xp, Ce, xp);
-                    }
-                } else {
-                    void* dst = (char*)encn + g.row0 * Ce * eb;
-                    if (fold) D3R_OTHER(launch_layernorm_x3in(gxn, m->enc_norm.g, m->enc_norm.b, dst, Mp, Ce, 1e-6f, c.st));
-                    else D3R_OTHER(launch_layernorm(m->dt, xp, m->enc_norm.g, m->enc_norm.b, dst, Mp, Ce, 1e-6f, c.st));
-                }
-            };
-            for (int gi = 0; gi < ngroups; ++gi)
-                for (int phase = -1; phase <= cf.enc_depth; ++phase) enc_phase(groups[gi], phase);
-            m->last_encn = encn; m->last_encn_elems = (size_t)Me * Ce;
+// ---- one forward -------------------------------------------------------------------------------------------------------------------------------
+// Stream plan: encoder on the caller's stream; then side 0 stays there and side 1 runs on the model's second stream, re-joined at every layer boundary (each
+// side reads the other's previous-layer output) and at the end. Each side has its own part of every scratch buffer and its own head arena.
+struct EncGroup { const float* im[2]; int n[2]; const SideDim* dd; size_t row0; };
+struct Fwd {
+    d3r_model* m; const Call& k; const Dims d; const Workspace w; Ctx c;
+    bool two; hipStream_t S[2];
+    int cur = 0;                                                  // decoder: the buffer (f / fr / l) that holds the layers' input
+    void* typed[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; // typed rows of a layer's output [buffer][side]: folded, the stream itself (fr, or a DPT hook buffer at the hook layers); else the hook copy or null
+
+    // fork: side 1 waits for what side 0 has enqueued; join: side 0 for side 1; both: a layer boundary
+    void sync(bool fork, bool join) {
+        if (!two) return;
+        if (fork) c.chk(hipEventRecord(m->ev_main, S[0]));
+        if (join) c.chk(hipEventRecord(m->ev_side, S[1]));
+        if (join) c.chk(hipStreamWaitEvent(S[0], m->ev_side, 0));
+        if (fork) c.chk(hipStreamWaitEvent(S[1], m->ev_main, 0));
+    }
+    // side sd's rows of the decoder's layer boundary `buf`: the statistics set of side t has Ms[t] rows whoever consumes it
+    Res boundary(int buf, int sd) const { return rows_of(m, d.Ms[sd], w.f[buf] + (size_t)d.Roff[sd] * d.Cd, typed[buf][sd], w.l[buf], d.Roff[sd], d.Gd); }
+
+    // Encoder: the images of one size in one pass, in the scratch buffers from row 0. Fold: every residual epilogue stores the typed rows (the residual stream
+    // itself, GF_X3RES) and their partial sums; the LayerNorm is two fmas in the epilogue of the nn.Linear behind it (weights packed as W diag(gamma)) -- DESIGN 4.0
+    void encode_group(const EncGroup& g) {
+        const SideDim& dd = *g.dd;
+        const int Ce = d.Ce, ps = m->cfg.patch_size, depth = m->cfg.enc_depth, n_img = g.n[0] + g.n[1], Mp = n_img * dd.N;
+        const size_t pk = 3 * (size_t)ps * ps;
+        const Res x = rows_of(m, Mp, w.x + g.row0 * Ce, w.xn, w.e);
+        if (g.n[0] > 0) D3R_OTHER(launch_patchify(m->dt, g.im[0], w.hb, g.n[0], dd.H, dd.W, ps, c.st));     // the patches start where the hidden rows do
+        if (g.n[1] > 0) D3R_OTHER(launch_patchify(m->dt, g.im[1], (char*)w.hb + (size_t)g.n[0] * dd.N * pk * d.eb, g.n[1], dd.H, dd.W, ps, c.st));
+        residual_linear(c, m->patch, w.hb, (int)pk, Res(), x, Ce);
+        for (int l = 0; l < depth; ++l) {
+            const EncBlk& b = m->enc[l];
+            gemm_heads(c, b.qkv, norm_in(c, x, b.n1, w.xn, Ce), Mp, Ce, d.He, dd, {HEAD_ROPE, w.q}, {HEAD_ROPE, w.k}, {HEAD_VT, w.vt});
+            attention(c, AttnBufs{w.q, w.k, w.vt, w.ao}, n_img, d.He, dd, dd);
+            residual_linear(c, b.proj, w.ao, Ce, x, x, Ce);
+            plain_linear(c, b.fc1, norm_in(c, x, b.n2, w.xn, Ce), Ce, Mp, EPI_GELU, w.hb, 4 * Ce);
+            Res y = x;
+            if (l + 1 == depth) y.part = nullptr;        // enc_norm (a kernel) follows: no sums
+            residual_linear(c, b.fc2, w.hb, 4 * Ce, x, y, Ce);
         }
-        if (do_dec) {
-        // ---- decoder (model.py:172-191): side s reads the PREVIOUS layer's (f_s, f_other) ---------------------
-        void* frp[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // fold: raw typed copy of layer output [buffer][side] (fr, or a DPT hook buffer at the hook layers)
-        if (fold) {
-            gemm_linear(c, encn, Ce, m->dec_embed, M2d, EPI_F32, nullptr, Cd, nullptr, fr[0], Cd, -1, GF_X3RES, LnStats(), l_part[0]);
-            if (!(Ms[0] <= inline_rows && Ms[1] <= inline_rows)) D3R_OTHER(launch_ln_finalize(l_part[0], M2d, Cd, 1e-6f, l_rs[0], l_nm[0], st));
-            for (int sd = 0; sd < 2; ++sd) frp[0][sd] = (char*)fr[0] + (size_t)Roff[sd] * Cd * eb;
-        } else {
-        gemm_linear(c, encn, Ce, m->dec_embed, M2d, EPI_F32, f[0], Cd);
+        final_norm(c, x, m->enc_norm, (char*)w.encn + g.row0 * Ce * d.eb, Ce);
+    }
+    // all images of the call as one group when the views share a size (model.py:142-151 concatenates the two views), else view 1's images, then view 2's (model.py:148-150)
+    void encoder() {
+        if (d.same) encode_group(EncGroup{{k.img1, k.img2}, {k.nimg1, k.nimg - k.nimg1}, &k.d[0], 0});
+        if (!d.same && k.nimg1 > 0) encode_group(EncGroup{{k.img1, nullptr}, {k.nimg1, 0}, &k.d[0], 0});
+        if (!d.same && k.nimg > k.nimg1) encode_group(EncGroup{{k.img2, nullptr}, {k.nimg - k.nimg1, 0}, &k.d[1], (size_t)k.nimg1 * k.d[0].N});
+        m->last_encn = w.encn; m->last_encn_elems = (size_t)d.Me * d.Ce;
+    }
+
+    // Decoder block l of side s (model.py:172-191) on the stream c.st: reads the PREVIOUS layer's output of both sides (buffer cur), writes its own into cur ^ 1.
+    // The stream: layer input `in` -> `mid` (after self attention, then in place after cross attention) -> `out`, the next layer's input.
+    void decoder_block(int l, int s) {
+        const int Cd = d.Cd, M = d.Ms[s], layer_no = l + 1, hk6 = m->cfg.dec_depth * 2 / 4, hk9 = m->cfg.dec_depth * 3 / 4;
+        const SideDim &own = k.d[s], &oth = k.d[1 - s];
+        const DecBlk& b = m->dec[s][l];
+        // this side's part of the scratch buffers (the encoder used them whole)
+        const size_t part = (size_t)s * d.Mmax * d.Cmax * d.eb;
+        void *sxn = (char*)w.xn + part, *shb = (char*)w.hb + 4 * part;
+        void* syn = (char*)w.yn + (size_t)s * d.Mmax * Cd * d.eb;         // norm_y of the OTHER view's tokens (Ms[1 - s] <= Mmax rows)
+        const AttnBufs ab{(char*)w.q + part, (char*)w.k + part, (char*)w.vt + (size_t)s * k.B * d.Hmax * 64 * d.ldv_max * d.eb, (char*)w.ao + part};
+        // fc2 also stores the typed rows of its output: at the hook layers into the DPT hook buffer (folded: the typed layer output IS the hook), else (folded) into fr
+        void* hook = (m->cfg.head_type == 1 && (layer_no == hk6 || layer_no == hk9)) ? w.hook[s][layer_no == hk6 ? 0 : 1] : nullptr;
+        typed[cur ^ 1][s] = hook || !m->ln_fold ? hook : (void*)((char*)w.fr[cur ^ 1] + (size_t)d.Roff[s] * Cd * d.eb);
+        const Res in = boundary(cur, s), other = boundary(cur, 1 - s), mid = rows_of(m, M, w.f[cur ^ 1] + (size_t)d.Roff[s] * Cd, sxn, w.s[s]);
+        Res out = boundary(cur ^ 1, s);
+        if (layer_no == m->cfg.dec_depth) out.part = nullptr;          // dec_norm (a kernel) follows: no sums
+        gemm_heads(c, b.qkv, norm_in(c, in, b.n1, sxn, Cd), M, Cd, d.Hd, own, {HEAD_ROPE, ab.q}, {HEAD_ROPE, ab.k}, {HEAD_VT, ab.vt});
+        attention(c, ab, k.B, d.Hd, own, own);
+        residual_linear(c, b.proj, ab.ao, Cd, in, mid, Cd);
+        // cross attention: q from norm2(x), k / v from norm_y(y) -- the other side's rows (and statistics); Nk = the other view's token count
+        const NormIn y = norm_in(c, other, b.ny, syn, Cd);
+        gemm_heads(c, b.cq, norm_in(c, mid, b.n2, sxn, Cd), M, Cd, d.Hd, own, {HEAD_ROPE, ab.q});
+        gemm_heads(c, b.ckv, y, other.M, Cd, d.Hd, oth, {HEAD_ROPE, ab.k}, {HEAD_VT, ab.vt});
+        attention(c, ab, k.B, d.Hd, own, oth);
+        residual_linear(c, b.cproj, ab.ao, Cd, mid, mid, Cd);
+        plain_linear(c, b.fc1, norm_in(c, mid, b.n3, sxn, Cd), Cd, M, EPI_GELU, shb, 4 * Cd);
+        residual_linear(c, b.fc2, shb, 4 * Cd, mid, out, Cd, true);
+    }
+    // decoder_embed over both sides' rows in one launch, then the layers
+    void decoder() {
+        for (int sd = 0; sd < 2 && m->ln_fold; ++sd) typed[0][sd] = (char*)w.fr[0] + (size_t)d.Roff[sd] * d.Cd * d.eb;
+        Res e = rows_of(m, d.M2d, w.f[0], w.fr[0], w.l[0]);
+        e.inl = d.Ms[0] <= m->ln_inline_rows && d.Ms[1] <= m->ln_inline_rows;      // the consumers are per side
+        residual_linear(c, m->dec_embed, w.encn, d.Ce, Res(), e, d.Cd);
+        sync(true, false);
+        for (int l = 0; l < m->cfg.dec_depth; ++l, cur ^= 1) {
+            for (int s = 0; s < 2; ++s) { c.st = S[s]; decoder_block(l, s); }
+            sync(true, true);
         }
-        if (two) {
-            c.chk(hipEventRecord(m->ev_main, S[0]));
-            c.chk(hipStreamWaitEvent(S[1], m->ev_main, 0));
-        }
-        int cur = 0;
-        const int hk6 = cf.dec_depth * 2 / 4, hk9 = cf.dec_depth * 3 / 4;
-        for (int l = 0; l < cf.dec_depth; ++l) {
-            for (int s = 0; s < 2; ++s) {
-                c.st = S[s];
-                const SideDim& own = D[s];
-                const SideDim& oth = D[1 - s];
-                // this side's part of the scratch buffers (the encoder used them whole)
-                void* sxn = (char*)xn + (size_t)s * Mmax * Cmax * eb;
-                void* sq = (char*)q + (size_t)s * Mmax * Cmax * eb;
-                void* sk = (char*)k + (size_t)s * Mmax * Cmax * eb;
-                void* svt = (char*)vt + (size_t)s * B * Hmax * 64 * ldv_max * eb;
-                void* sao = (char*)ao + (size_t)s * Mmax * Cmax * eb;
-                void* shb = (char*)hb + (size_t)s * Mmax * 4 * Cmax * eb;
-                void* syn = (char*)yn + (size_t)s * Mmax * Cd * eb;         // norm_y of the OTHER view's tokens (Ms[1 - s] <= Mmax rows)
-                const DecBlk& b = m->dec[s][l];
-                const float* xo = f[cur] + (size_t)Roff[s] * Cd;         // own stream (old)
-                const float* yo = f[cur] + (size_t)Roff[1 - s] * Cd;     // other view (old)
-                float* xw = f[cur ^ 1] + (size_t)Roff[s] * Cd;           // own stream (new)
-                if (fold) {
-                    // small problems: the consumers form rstd / nmr of their input rows themselves (the set of side t has Ms[t] rows whoever consumes it)
-                    const bool inl_own = Ms[s] <= inline_rows, inl_oth = Ms[1 - s] <= inline_rows;
-                    const LnStats sx{l_rs[cur] + Roff[s], l_nm[cur] + Roff[s], inl_own ? l_part[cur] + (size_t)Roff[s] * Gd * 2 : nullptr},
-                                  sy{l_rs[cur] + Roff[1 - s], l_nm[cur] + Roff[1 - s], inl_oth ? l_part[cur] + (size_t)Roff[1 - s] * Gd * 2 : nullptr},
-                                  ss{s_rs[s], s_nm[s], inl_own ? s_part[s] : nullptr};
-                    self_attention(c, frp[cur][s], b.qkv, Ms[s], Cd, Hd, B, own.N, own.tw, own.ldv, sq, sk, svt, sao, sx);      // norm1 folded
-                    // the residual stream is the typed rows themselves (GF_X3RES): layer input frp[cur][s] -> sxn (after self attention, then in place after
-                    // cross attention) -> the next layer's input fr[cur ^ 1] (or a DPT hook buffer)
-                    gemm_linear(c, sao, Cd, b.proj, Ms[s], EPI_F32, nullptr, Cd, frp[cur][s], sxn, Cd, -1, GF_X3RES, LnStats(), s_part[s]);
-                    if (!inl_own) D3R_OTHER(launch_ln_finalize(s_part[s], Ms[s], Cd, 1e-6f, s_rs[s], s_nm[s], c.st));
-                    {
-                        const int kq[1] = {HEAD_ROPE};
-                        void* dq[1] = {sq};
-                        gemm_heads(c, sxn, Cd, b.cq, Ms[s], Cd, 1, kq, dq, Hd, own.N, own.tw, own.ldv, ss);                     // norm2 folded
-                        const int kkv[2] = {HEAD_ROPE, HEAD_VT};
-                        void* dkv[2] = {sk, svt};
-                        gemm_heads(c, frp[cur][1 - s], Cd, b.ckv, Ms[1 - s], Cd, 2, kkv, dkv, Hd, oth.N, oth.tw, oth.ldv, sy);  // norm_y folded: the other side's raw rows and statistics
-                        AttnParams a;
-                        a.q = sq; a.k = sk; a.vt = svt; a.out = sao; a.B = B; a.H = Hd; a.Nq = own.N; a.Nk = oth.N; a.ldv = oth.ldv; a.scale = 0.125f;
-                        a.out_dt = m->bdt;
-                        c.mark(PRF_ATTN, 4.0 * B * Hd * (double)own.N * oth.N * 64, B * Hd, own.N, oth.N);
-                        c.chk(launch_attention(m->dt, a, c.st));
-                    }
-                    gemm_linear(c, sao, Cd, b.cproj, Ms[s], EPI_F32, nullptr, Cd, sxn, sxn, Cd, -1, GF_X3RES, LnStats(), s_part[s]);
-                    if (!inl_own) D3R_OTHER(launch_ln_finalize(s_part[s], Ms[s], Cd, 1e-6f, s_rs[s], s_nm[s], c.st));
-                    gemm_linear(c, sxn, Cd, b.fc1, Ms[s], EPI_GELU, shb, 4 * Cd, nullptr, nullptr, 0, -1, 0, ss);                 // norm3 folded
-                    const int layer_no = l + 1;
-                    void* hcopy = (cf.head_type == 1 && (layer_no == hk6 || layer_no == hk9)) ? hook[s][layer_no == hk6 ? 0 : 1] : nullptr;
-                    // the typed layer output IS a DPT hook at the hook layers; after the last layer dec_norm (a kernel) follows: no sums
-                    void* raw = hcopy ? hcopy : (void*)((char*)fr[cur ^ 1] + (size_t)Roff[s] * Cd * eb);
-                    float* lp = layer_no == cf.dec_depth ? nullptr : l_part[cur ^ 1] + (size_t)Roff[s] * Gd * 2;
-                    gemm_linear(c, shb, 4 * Cd, b.fc2, Ms[s], EPI_F32, nullptr, Cd, sxn, raw, Cd, -1, GF_X3RES, LnStats(), lp);
-                    if (lp && !inl_own) D3R_OTHER(launch_ln_finalize(lp, Ms[s], Cd, 1e-6f, l_rs[cur ^ 1] + Roff[s], l_nm[cur ^ 1] + Roff[s], c.st));
-                    frp[cur ^ 1][s] = raw;
-                    continue;
-                }
-                D3R_OTHER(launch_layernorm(m->bdt, xo, b.n1.g, b.n1.b, sxn, Ms[s], Cd, 1e-6f, c.st));
-                self_attention(c, sxn, b.qkv, Ms[s], Cd, Hd, B, own.N, own.tw, own.ldv, sq, sk, svt, sao);
-                gemm_linear(c, sao, Cd, b.proj, Ms[s], EPI_F32, xw, Cd, xo);
-                // cross attention: q from norm2(x), k/v from norm_y(y): Nk = the other view's token count
-                D3R_OTHER(launch_layernorm(m->bdt, yo, b.ny.g, b.ny.b, syn, Ms[1 - s], Cd, 1e-6f, c.st));
-                D3R_OTHER(launch_layernorm(m->bdt, xw, b.n2.g, b.n2.b, sxn, Ms[s], Cd, 1e-6f, c.st));
-                {
-                    const int kq[1] = {HEAD_ROPE};
-                    void* dq[1] = {sq};
-                    gemm_heads(c, sxn, Cd, b.cq, Ms[s], Cd, 1, kq, dq, Hd, own.N, own.tw, own.ldv);
-                    const int kkv[2] = {HEAD_ROPE, HEAD_VT};
-                    void* dkv[2] = {sk, svt};
-                    gemm_heads(c, syn, Cd, b.ckv, Ms[1 - s], Cd, 2, kkv, dkv, Hd, oth.N, oth.tw, oth.ldv);
-                    AttnParams a;
-                    a.q = sq; a.k = sk; a.vt = svt; a.out = sao; a.B = B; a.H = Hd; a.Nq = own.N; a.Nk = oth.N; a.ldv = oth.ldv; a.scale = 0.125f;
-                    a.out_dt = m->bdt;
-                    c.mark(PRF_ATTN, 4.0 * B * Hd * (double)own.N * oth.N * 64, B * Hd, own.N, oth.N);
-                    c.chk(launch_attention(m->dt, a, c.st));
-                }
-                gemm_linear(c, sao, Cd, b.cproj, Ms[s], EPI_F32, xw, Cd, xw);
-                D3R_OTHER(launch_layernorm(m->bdt, xw, b.n3.g, b.n3.b, sxn, Ms[s], Cd, 1e-6f, c.st));
-                gemm_linear(c, sxn, Cd, b.fc1, Ms[s], EPI_GELU, shb, 4 * Cd);
-                const int layer_no = l + 1;
-                void* hcopy = (cf.head_type == 1 && (layer_no == hk6 || layer_no == hk9)) ? hook[s][layer_no == hk6 ? 0 : 1] : nullptr;
-                gemm_linear(c, shb, 4 * Cd, b.fc2, Ms[s], EPI_F32, xw, Cd, xw, hcopy, Cd);
-            }
-            cross_sync();
-            cur ^= 1;
-        }
-        // ---- dec_norm + heads, each side on its own stream ---------------------------------------------------
-        float* pts[2] = {pts1, pts2};
-        float* cnf[2] = {conf1, conf2};
+    }
+    // dec_norm + heads, each side on its own stream; the caller's stream continues only after side 1 has finished
+    void heads() {
+        const int Ce = d.Ce, Cd = d.Cd, ps = m->cfg.patch_size, B = k.B;
         for (int s = 0; s < 2; ++s) {
             c.st = S[s];
-            const SideDim& own = D[s];
-            if (fold) D3R_OTHER(launch_layernorm_x3in(frp[cur][s], m->dec_norm.g, m->dec_norm.b, hook[s][2], Ms[s], Cd, 1e-6f, c.st));
-            else
-            D3R_OTHER(launch_layernorm(m->dt, f[cur] + (size_t)Roff[s] * Cd, m->dec_norm.g, m->dec_norm.b, hook[s][2], Ms[s], Cd, 1e-6f, c.st));
-            if (cf.head_type == 0) {
-                float* lo = lin_out + (size_t)Roff[s] * 4 * ps * ps;
-                gemm_linear(c, hook[s][2], Cd, m->lin_head[s], Ms[s], EPI_F32, lo, 4 * ps * ps);
-                D3R_OTHER(launch_linear_head_post(lo, pts[s], cnf[s], B, own.th, own.tw, ps, m->out_pstride, m->out_cstride, m->post, c.st));
-            } else {
-                for (int b0 = 0; b0 < B; b0 += chunk) {
-                    const int bc = (B - b0) < chunk ? (B - b0) : chunk;
-                    Arena sub((char*)ws + common_end + (size_t)s * head_arena, head_arena);
-                    const void* hooks[4] = {(const char*)encn + ((size_t)Roff[s] + (size_t)b0 * own.N) * Ce * eb, (const char*)hook[s][0] + (size_t)b0 * own.N * Cd * eb,
-                                            (const char*)hook[s][1] + (size_t)b0 * own.N * Cd * eb, (const char*)hook[s][2] + (size_t)b0 * own.N * Cd * eb};
-                    const int hc[4] = {Ce, Cd, Cd, Cd};
-                    run_dpt(c, m->dpt[s], sub, hooks, hc, bc, own.th, own.tw, pts[s] + (size_t)b0 * own.H * own.W * m->out_pstride,
-                            cnf[s] + (size_t)b0 * own.H * own.W * m->out_cstride);
-                }
+            const SideDim& own = k.d[s];
+            final_norm(c, boundary(cur, s), m->dec_norm, w.hook[s][2], Cd);
+            if (m->cfg.head_type == 0) {
+                float* lo = w.lin_out + (size_t)d.Roff[s] * 4 * ps * ps;
+                plain_linear(c, m->lin_head[s], NormIn{w.hook[s][2]}, Cd, d.Ms[s], EPI_F32, lo, 4 * ps * ps);
+                D3R_OTHER(launch_linear_head_post(lo, k.pts[s], k.conf[s], B, own.th, own.tw, ps, k.pstride, k.cstride, m->post, c.st));
+            }
+            for (int b0 = 0; b0 < B && m->cfg.head_type == 1; b0 += d.chunk) {
+                const size_t r0 = (size_t)b0 * own.N, px0 = (size_t)b0 * own.H * own.W;
+                const void* hooks[4] = {(const char*)w.encn + ((size_t)d.Roff[s] + r0) * Ce * d.eb, (const char*)w.hook[s][0] + r0 * Cd * d.eb,
+                                        (const char*)w.hook[s][1] + r0 * Cd * d.eb, (const char*)w.hook[s][2] + r0 * Cd * d.eb};
+                const int hc[4] = {Ce, Cd, Cd, Cd};
+                run_dpt(c, m->dpt[s], Arena(w.head_arena[s], w.head_bytes), k, hooks, hc, (B - b0) < d.chunk ? (B - b0) : d.chunk, own.th, own.tw,
+                        k.pts[s] + px0 * k.pstride, k.conf[s] + px0 * k.cstride);
             }
         }
-        c.st = st;
-        if (two) {   // join: the caller's stream continues only after side 1 has finished
-            c.chk(hipEventRecord(m->ev_side, S[1]));
-            c.chk(hipStreamWaitEvent(S[0], m->ev_side, 0));
-        }
-        }  // do_dec
-        c.mark(PRF_END, 0.0);
+        c.st = S[0];
+        sync(false, true);
     }
-    if (rc_out) *rc_out = c.rc;
-    return common_end + 2 * head_arena + 256;
+};
+
+// bytes of the workspace a call needs: its layout on no base
+size_t workspace_bytes(const d3r_model* m, const Call& k) {
+    Arena ar(nullptr, 0);
+    return ws_layout(m, k, dims_of(m, k), ar).bytes;
+}
+
+// enqueues the call on `st`, in the model's workspace; refuses it before the first launch when a layout does not fit its arena
+int forward(d3r_model* m, const Call& k, hipStream_t st) {
+    Arena ar(m->ws, m->ws_bytes);
+    const Dims d = dims_of(m, k);
+    Fwd F{m, k, d, ws_layout(m, k, d, ar), Ctx{m, st, D3R_OK, st}};
+    if (!m->ws || F.w.bytes > ar.cap) return D3R_ERR_ALLOC;
+    for (int s = 0; s < 2 && F.w.head_bytes; ++s) {
+        Arena sub(F.w.head_arena[s], F.w.head_bytes);
+        dpt_layout(m, m->dpt[s], sub, d.chunk, k.d[s].th, k.d[s].tw);
+        if (sub.off > sub.cap) return D3R_ERR_ALLOC;
+    }
+    Ctx& c = F.c;
+    F.two = m->two_streams && !m->prof_on && m->side != nullptr;
+    F.S[0] = st; F.S[1] = F.two ? m->side : st;
+    if (k.d[0].ldv != k.d[0].N || k.d[1].ldv != k.d[1].N) D3R_OTHER(hipMemsetAsync(F.w.vt, 0, (size_t)d.nvt * d.Hmax * 64 * d.ldv_max * d.eb, st));
+    if (d.do_enc) F.encoder();
+    if (d.do_dec) { F.decoder(); F.heads(); }
+    c.mark(PRF_END, 0.0);
+    return c.rc;
 }
 
 }  // namespace
@@ -1120,22 +1065,92 @@ static int finalize_fold(d3r_model* m) {
     return D3R_OK;
 }
 
-static int run_phases(d3r_model* m, int phases, const float* img1, const float* img2, int nimg1, int nimg, void* feat, int B, int H1, int W1,
-                      int H2, int W2, float* pts1, float* conf1, float* pts2, float* conf2, hipStream_t st) {
+// ---- small whole forwards: replay a captured graph (see d3r_model::GraphEntry). True: the call was served by a replay (or failed trying), *rc is its result;
+// false: the caller enqueues it eagerly ----------------------------------------------------------------------------------------------------------
+static bool graph_forward(d3r_model* m, const Call& k, hipStream_t st, int* rc) {
+    const int B = k.B, H1 = k.d[0].H, W1 = k.d[0].W, H2 = k.d[1].H, W2 = k.d[1].W;
+    const bool graphable = k.phases == (PH_ENCODE | PH_DECODE) && m->graph_max_pairs > 0 && B <= m->graph_max_pairs && !m->prof_on && k.nimg1 == B && k.nimg == 2 * B;
+    if (!graphable) return false;
+    const d3r_model::GraphKey key{B, H1, W1, H2, W2, k.pstride, (m->two_streams && m->side) ? 1 : 0};
+    d3r_model::GraphEntry* ge = nullptr;
+    for (auto& g : m->graphs)
+        if (g.key == key) { ge = &g; break; }
+    if (!ge) {
+        if (m->graphs.size() >= 16) {                       // a handful of (batch, size) combinations is the expected use
+            (void)hipStreamSynchronize(st);                 // a replay enqueued by the previous call (and its staging copies) may still be in flight
+            if (m->side) (void)hipStreamSynchronize(m->side);
+            if (m->cap) (void)hipStreamSynchronize(m->cap);
+            m->drop_graphs();
+        }
+        m->graphs.push_back(d3r_model::GraphEntry());
+        ge = &m->graphs.back();
+        ge->key = key;
+    }
+    const size_t n_in1 = (size_t)B * 3 * H1 * W1, n_in2 = (size_t)B * 3 * H2 * W2;
+    const size_t a1 = (size_t)B * H1 * W1, a2 = (size_t)B * H2 * W2;
+    const bool packed = k.pstride == 8;                      // one [B][H][W][8] payload (H1 == H2, W1 == W2)
+    const size_t n_out = packed ? a1 * 8 : 4 * (a1 + a2);
+    // staging layout (floats): img1 | img2 | pts1 conf1 pts2 conf2 (or the packed payload)
+    if (ge->seen >= 1 && !ge->exec && ge->seen < 1000) {     // second call: capture
+        bool ok = true;
+        if (!m->cap) ok = hipStreamCreateWithFlags(&m->cap, hipStreamNonBlocking) == hipSuccess;
+        const size_t bytes = (n_in1 + n_in2 + n_out) * sizeof(float);
+        if (ok && !ge->io) { ok = hipMalloc((void**)&ge->io, bytes) == hipSuccess; ge->io_bytes = bytes; }
+        if (ok) {
+            Call staged = k;
+            staged.img1 = ge->io; staged.img2 = ge->io + n_in1;
+            float* o1 = ge->io + n_in1 + n_in2;
+            staged.pts[0] = o1;
+            if (packed) { staged.conf[0] = o1 + 3; staged.pts[1] = o1 + 4; staged.conf[1] = o1 + 7; }
+            else { staged.conf[0] = o1 + 3 * a1; staged.pts[1] = staged.conf[0] + a1; staged.conf[1] = staged.pts[1] + 3 * a2; }
+            ok = hipStreamBeginCapture(m->cap, hipStreamCaptureModeRelaxed) == hipSuccess;
+            if (ok) {
+                const int crc = forward(m, staged, m->cap);
+                hipGraph_t g = nullptr;
+                const bool ended = hipStreamEndCapture(m->cap, &g) == hipSuccess && g != nullptr;
+                ok = ended && crc == D3R_OK && hipGraphInstantiate(&ge->exec, g, nullptr, nullptr, 0) == hipSuccess;
+                if (ok) ge->graph = g;
+                else if (g) (void)hipGraphDestroy(g);
+            }
+        }
+        if (!ok) {                        // this shape stays eager
+            (void)hipGetLastError();
+            ge->exec = nullptr;
+            ge->seen = 1000;
+        }
+    }
+    if (!ge->exec) {
+        if (ge->seen < 1000) ++ge->seen;
+        return false;
+    }
+    float* io = ge->io;
+    const float* o1 = io + n_in1 + n_in2;
+    bool ok = hipMemcpyAsync(io, k.img1, n_in1 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(io + n_in1, k.img2, n_in2 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
+              hipGraphLaunch(ge->exec, st) == hipSuccess;
+    if (ok && packed) ok = hipMemcpyAsync(k.pts[0], o1, n_out * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess;
+    else if (ok)
+        ok = hipMemcpyAsync(k.pts[0], o1, 3 * a1 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(k.conf[0], o1 + 3 * a1, a1 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(k.pts[1], o1 + 4 * a1, 3 * a2 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(k.conf[1], o1 + 4 * a1 + 3 * a2, a2 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess;
+    if (ok) ++m->graph_replays;
+    *rc = ok ? D3R_OK : D3R_ERR_LAUNCH;
+    return true;
+}
+
+static int run_phases(d3r_model* m, const Call& k, hipStream_t st) {
     // The engines of a process share their helper streams (shared_stream above): the ENQUEUE of a forward -- host side only, the device work stays asynchronous --
     // is therefore one critical section per process. Engines driven from different host threads stay correct (one engine's stream capture cannot swallow another
     // engine's launches on the shared side stream; fork / join events of two forwards do not interleave); their side-stream halves run in enqueue order.
     static std::mutex enqueue_mu;
     std::lock_guard<std::mutex> enqueue_lock(enqueue_mu);
     const int ps = m->cfg.patch_size;
-    for (int v = 0; v < 2; ++v) {
-        const int H = v ? H2 : H1, W = v ? W2 : W1;
-        if (H % ps || W % ps || H <= 0 || W <= 0 || H / ps > 511 || W / ps > 511) return D3R_ERR_SHAPE;
-    }
+    for (const SideDim& v : k.d)
+        if (v.H % ps || v.W % ps || v.H <= 0 || v.W <= 0 || v.H / ps > 511 || v.W / ps > 511) return D3R_ERR_SHAPE;
     if (d3r_model_missing(m) != 0) return D3R_ERR_STATE;
     { const int frc = finalize_fold(m); if (frc != D3R_OK) return frc; }
-    const SideDim d0 = side_dim(H1, W1, ps), d1 = side_dim(H2, W2, ps);
-    const size_t need = forward_impl(m, nullptr, 0, phases, img1, img2, nimg1, nimg, feat, B, d0, d1, pts1, conf1, pts2, conf2, st, nullptr);
+    const size_t need = workspace_bytes(m, k);
     if (need > m->ws_bytes) {
         (void)hipStreamSynchronize(st);
         if (m->side) (void)hipStreamSynchronize(m->side);
@@ -1145,102 +1160,46 @@ static int run_phases(d3r_model* m, int phases, const float* img1, const float* 
         if (hipMalloc(&m->ws, need) != hipSuccess) return D3R_ERR_ALLOC;
         m->ws_bytes = need;
     }
-    int rc = D3R_OK;
     m->prof_rec.clear();
-    // ---- small whole forwards: replay a captured graph (see d3r_model::GraphEntry) ---------------------------------------------------
-    const bool graphable = phases == (PH_ENCODE | PH_DECODE) && m->graph_max_pairs > 0 && B <= m->graph_max_pairs && !m->prof_on && nimg1 == B && nimg == 2 * B;
-    if (graphable) {
-        const d3r_model::GraphKey key{B, H1, W1, H2, W2, m->out_pstride, (m->two_streams && m->side) ? 1 : 0};
-        d3r_model::GraphEntry* ge = nullptr;
-        for (auto& g : m->graphs)
-            if (g.key == key) { ge = &g; break; }
-        if (!ge) {
-            if (m->graphs.size() >= 16) {                       // a handful of (batch, size) combinations is the expected use
-                (void)hipStreamSynchronize(st);                 // a replay enqueued by the previous call (and its staging copies) may still be in flight
-                if (m->side) (void)hipStreamSynchronize(m->side);
-                if (m->cap) (void)hipStreamSynchronize(m->cap);
-                m->drop_graphs();
-            }
-            m->graphs.push_back(d3r_model::GraphEntry());
-            ge = &m->graphs.back();
-            ge->key = key;
-        }
-        const size_t n_in1 = (size_t)B * 3 * H1 * W1, n_in2 = (size_t)B * 3 * H2 * W2;
-        const size_t a1 = (size_t)B * H1 * W1, a2 = (size_t)B * H2 * W2;
-        const bool packed = m->out_pstride == 8;                 // one [B][H][W][8] payload (H1 == H2, W1 == W2)
-        const size_t n_out = packed ? a1 * 8 : 4 * (a1 + a2);
-        // staging layout (floats): img1 | img2 | pts1 conf1 pts2 conf2 (or the packed payload)
-        float* io = ge->io;
-        auto s_img1 = [&]() { return io; };
-        auto s_img2 = [&]() { return io + n_in1; };
-        auto s_out = [&]() { return io + n_in1 + n_in2; };
-        if (ge->seen >= 1 && !ge->exec && ge->seen < 1000) {     // second call: capture
-            bool ok = true;
-            if (!m->cap) ok = hipStreamCreateWithFlags(&m->cap, hipStreamNonBlocking) == hipSuccess;
-            const size_t bytes = (n_in1 + n_in2 + n_out) * sizeof(float);
-            if (ok && !ge->io) { ok = hipMalloc((void**)&ge->io, bytes) == hipSuccess; ge->io_bytes = bytes; io = ge->io; }
-            if (ok) {
-                float *o1 = s_out(), *c1, *o2, *c2;
-                if (packed) { c1 = o1 + 3; o2 = o1 + 4; c2 = o1 + 7; }
-                else { c1 = o1 + 3 * a1; o2 = c1 + a1; c2 = o2 + 3 * a2; }
-                ok = hipStreamBeginCapture(m->cap, hipStreamCaptureModeRelaxed) == hipSuccess;
-                if (ok) {
-                    int crc = D3R_OK;
-                    forward_impl(m, m->ws, m->ws_bytes, phases, s_img1(), s_img2(), nimg1, nimg, feat, B, d0, d1, o1, c1, o2, c2, m->cap, &crc);
-                    hipGraph_t g = nullptr;
-                    const bool ended = hipStreamEndCapture(m->cap, &g) == hipSuccess && g != nullptr;
-                    ok = ended && crc == D3R_OK && hipGraphInstantiate(&ge->exec, g, nullptr, nullptr, 0) == hipSuccess;
-                    if (ok) ge->graph = g;
-                    else if (g) (void)hipGraphDestroy(g);
-                }
-            }
-            if (!ok) {                        // this shape stays eager
-                (void)hipGetLastError();
-                ge->exec = nullptr;
-                ge->seen = 1000;
-            }
-        }
-        if (ge->exec) {
-            io = ge->io;
-            bool ok = hipMemcpyAsync(s_img1(), img1, n_in1 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                      hipMemcpyAsync(s_img2(), img2, n_in2 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                      hipGraphLaunch(ge->exec, st) == hipSuccess;
-            const float* o1 = s_out();
-            if (ok && packed) ok = hipMemcpyAsync(pts1, o1, n_out * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess;
-            else if (ok)
-                ok = hipMemcpyAsync(pts1, o1, 3 * a1 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                     hipMemcpyAsync(conf1, o1 + 3 * a1, a1 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                     hipMemcpyAsync(pts2, o1 + 4 * a1, 3 * a2 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                     hipMemcpyAsync(conf2, o1 + 4 * a1 + 3 * a2, a2 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess;
-            if (ok) { ++m->graph_replays; return D3R_OK; }
-            return D3R_ERR_LAUNCH;
-        }
-        if (ge->seen < 1000) ++ge->seen;
-    }
-    forward_impl(m, m->ws, m->ws_bytes, phases, img1, img2, nimg1, nimg, feat, B, d0, d1, pts1, conf1, pts2, conf2, st, &rc);
-    return rc;
+    int rc = D3R_OK;
+    if (graph_forward(m, k, st, &rc)) return rc;
+    return forward(m, k, st);
 }
 
 extern "C" long d3r_model_graph_replays(const d3r_model* m) { return m ? m->graph_replays : -1; }
 
+// B pairs of two image sizes with their outputs; packed: one [B][H][W][8] payload (pts1 xyz, conf1, pts2 xyz, conf2 per pixel)
+static Call pair_call(const d3r_model* m, int phases, int B, int H1, int W1, int H2, int W2, float* pts1, float* conf1, float* pts2, float* conf2, bool packed = false) {
+    Call k;
+    k.phases = phases; k.B = B; k.d[0] = side_dim(H1, W1, m->cfg.patch_size); k.d[1] = side_dim(H2, W2, m->cfg.patch_size);
+    k.pts[0] = pts1; k.conf[0] = conf1; k.pts[1] = pts2; k.conf[1] = conf2;
+    if (packed) k.pstride = k.cstride = 8;
+    return k;
+}
+static int run_forward(d3r_model* m, Call k, const float* img1, const float* img2, void* stream) {
+    k.img1 = img1; k.img2 = img2; k.nimg1 = k.B; k.nimg = 2 * k.B;
+    return run_phases(m, k, (hipStream_t)stream);
+}
+static int run_decode(d3r_model* m, Call k, const void* feat, void* stream) {
+    k.feat = const_cast<void*>(feat);
+    return run_phases(m, k, (hipStream_t)stream);
+}
+
 extern "C" int d3r_model_forward(d3r_model* m, const float* img1, const float* img2, int B, int H, int W, float* pts1, float* conf1,
                                  float* pts2, float* conf2, void* stream) {
     if (!m || !img1 || !img2 || B <= 0 || !pts1 || !conf1 || !pts2 || !conf2) return D3R_ERR_INVALID;
-    return run_phases(m, PH_ENCODE | PH_DECODE, img1, img2, B, 2 * B, nullptr, B, H, W, H, W, pts1, conf1, pts2, conf2, (hipStream_t)stream);
+    return run_forward(m, pair_call(m, PH_ENCODE | PH_DECODE, B, H, W, H, W, pts1, conf1, pts2, conf2), img1, img2, stream);
 }
 
 extern "C" int d3r_model_forward_mixed(d3r_model* m, const float* img1, int H1, int W1, const float* img2, int H2, int W2, int B, float* pts1,
                                        float* conf1, float* pts2, float* conf2, void* stream) {
     if (!m || !img1 || !img2 || B <= 0 || !pts1 || !conf1 || !pts2 || !conf2) return D3R_ERR_INVALID;
-    return run_phases(m, PH_ENCODE | PH_DECODE, img1, img2, B, 2 * B, nullptr, B, H1, W1, H2, W2, pts1, conf1, pts2, conf2, (hipStream_t)stream);
+    return run_forward(m, pair_call(m, PH_ENCODE | PH_DECODE, B, H1, W1, H2, W2, pts1, conf1, pts2, conf2), img1, img2, stream);
 }
 
 extern "C" int d3r_model_forward_packed(d3r_model* m, const float* img1, const float* img2, int B, int H, int W, float* out8, void* stream) {
     if (!m || !img1 || !img2 || B <= 0 || !out8) return D3R_ERR_INVALID;
-    m->out_pstride = 8; m->out_cstride = 8;
-    const int rc = run_phases(m, PH_ENCODE | PH_DECODE, img1, img2, B, 2 * B, nullptr, B, H, W, H, W, out8, out8 + 3, out8 + 4, out8 + 7, (hipStream_t)stream);
-    m->out_pstride = 3; m->out_cstride = 1;
-    return rc;
+    return run_forward(m, pair_call(m, PH_ENCODE | PH_DECODE, B, H, W, H, W, out8, out8 + 3, out8 + 4, out8 + 7, true), img1, img2, stream);
 }
 
 extern "C" size_t d3r_model_feature_bytes(const d3r_model* m, int H, int W) {
@@ -1251,19 +1210,18 @@ extern "C" size_t d3r_model_feature_bytes(const d3r_model* m, int H, int W) {
 
 extern "C" int d3r_model_encode(d3r_model* m, const float* img, int n, int H, int W, void* feat_out, void* stream) {
     if (!m || !img || n <= 0 || !feat_out) return D3R_ERR_INVALID;
-    return run_phases(m, PH_ENCODE, img, nullptr, n, n, feat_out, 0, H, W, H, W, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    Call k = pair_call(m, PH_ENCODE, 0, H, W, H, W, nullptr, nullptr, nullptr, nullptr);
+    k.img1 = img; k.nimg1 = k.nimg = n; k.feat = feat_out;
+    return run_phases(m, k, (hipStream_t)stream);
 }
 
 extern "C" int d3r_model_decode(d3r_model* m, const void* feat, int B, int H, int W, float* pts1, float* conf1, float* pts2, float* conf2,
                                 void* stream) {
     if (!m || !feat || B <= 0 || !pts1 || !conf1 || !pts2 || !conf2) return D3R_ERR_INVALID;
-    return run_phases(m, PH_DECODE, nullptr, nullptr, 0, 0, const_cast<void*>(feat), B, H, W, H, W, pts1, conf1, pts2, conf2, (hipStream_t)stream);
+    return run_decode(m, pair_call(m, PH_DECODE, B, H, W, H, W, pts1, conf1, pts2, conf2), feat, stream);
 }
 
 extern "C" int d3r_model_decode_packed(d3r_model* m, const void* feat, int B, int H, int W, float* out8, void* stream) {
     if (!m || !feat || B <= 0 || !out8) return D3R_ERR_INVALID;
-    m->out_pstride = 8; m->out_cstride = 8;
-    const int rc = run_phases(m, PH_DECODE, nullptr, nullptr, 0, 0, const_cast<void*>(feat), B, H, W, H, W, out8, out8 + 3, out8 + 4, out8 + 7, (hipStream_t)stream);
-    m->out_pstride = 3; m->out_cstride = 1;
-    return rc;
+    return run_decode(m, pair_call(m, PH_DECODE, B, H, W, H, W, out8, out8 + 3, out8 + 4, out8 + 7, true), feat, stream);
 }

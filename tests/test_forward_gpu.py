@@ -742,3 +742,26 @@ def test_layernorm_statistics_in_the_consumer_prologue_are_bit_identical(gpu, mo
         eng._destroy_engine()
     for a, b in zip(outs['0'], outs['1000000']):
         assert all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize('case', range(10))
+def test_engine_schedule_matches_recorded(gpu, case):
+    """Launch order and workspace size of the engine's forward, which no output comparison sees: for ten small calls (default switches, ln_finalize launched,
+    LayerNorm kernels, two view sizes, two head chunks, fp32 / bf16 / fp16f8, the linear head, encode then decode) a fresh engine grows its workspace by exactly the
+    recorded bytes and, profiled, enqueues exactly the recorded list of (kind, M, N, K). tests/golden/engine_schedule.json was recorded by
+    tools/make_engine_schedule_golden.py BEFORE the forward was split into layout, blocks and launch helpers (csrc/engine.hip)."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location('make_engine_schedule_golden', os.path.join(os.path.dirname(GOLD), os.pardir, 'tools', 'make_engine_schedule_golden.py'))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    table = json.load(open(os.path.join(GOLD, 'engine_schedule.json')))
+    assert table['cases'] == gen.CASES and len(table['recorded']) == 10
+    want, got = table['recorded'][case], gen.run_case(gen.CASES[case], gpu)
+    assert [r['call'] for r in got] == [r['call'] for r in want]
+    for w, g in zip(want, got):
+        print(f"[{gen.CASES[case]['name']}] {g['call']}: workspace {g['workspace_bytes']} bytes (recorded {w['workspace_bytes']}), {len(g['launches'])} launches (recorded {len(w['launches'])})")
+        assert len(w['launches']) >= 14          # the encoder alone, two blocks deep
+        assert g['workspace_bytes'] == w['workspace_bytes']
+        first = next((i for i, (a, b) in enumerate(zip(w['launches'], g['launches'])) if a != b), None)
+        assert first is None and len(g['launches']) == len(w['launches']), (first, w['launches'][first] if first is not None else None, g['launches'][first] if first is not None else None)
