@@ -11,7 +11,13 @@ query, idx = -1 and d2 = +inf. The kernels give what an fp32 brute force over al
 A uniform grid with cells as large as max_dist would make every query walk thousands of points when the clouds are much denser than
 max_dist, so the search runs as a radius ladder: r_k = min(r_0 4^k, max_dist), each pass on a grid of cell r_k and only for the queries no
 earlier pass resolved. A neighbour found within r_k is the global nearest and all its ties lie within r_k, so the ladder's result is the
-single search's at max_dist."""
+single search's at max_dist.
+
+    d2, idx = k_nearest(query, ref, k, max_dist)            # the k nearest, rows sorted by (d2, index): csrc/cloud_knn.hip, d3r_cloud_knn
+
+The same grid and ladder carry the k nearest neighbours, and three consumers of their rows: `knn_mean_distances` with `outlier_threshold`
+(statistical outlier removal), `cloud_normals` and `orient_normals`; viz.FusedCloud.estimate_normals / remove_outliers and
+scene.fuse(normals=..., outliers=...) are built of them."""
 import ctypes as C
 import math
 
@@ -23,6 +29,12 @@ from ._lib import check, current_stream, lib, ptr
 
 MAX_THRESHOLDS = 8      # D3R_CLOUD_MAX_THRESHOLDS
 LADDER_STEP = 4.0
+MAX_K = 32              # D3R_CLOUD_MAX_K
+# the ladder of `k_nearest`: a rung walks about 27 cells of side r, on a surface sampled at spacing v about 9 r^2 / v^2 points, and resolves
+# a query once k points lie within r, about r >= v sqrt(k / pi). A step of 4 from r_0 = 2 v jumps from 36 to 576 points for the queries
+# the first rung leaves open (most of them at k = 16, which needs 2.3 v); a step of 2 looks at 144 (tools/cloud_normals_speed.py).
+KNN_LADDER_STEP = 2.0
+KNN_CELL_FACTOR = 1.0   # cell = factor r of a rung of `k_nearest`; exactness does not depend on it (tools/cloud_normals_speed.py measures 1 and 1/2)
 
 
 def _radius_f32(x, what):
@@ -40,6 +52,14 @@ def default_r0(ref, max_dist):
     """the first radius of the ladder: twice the reference cloud's voxel size when it is a FusedCloud with one, else max_dist / 16"""
     voxel = getattr(ref, 'voxel_size', None)
     return 2.0 * voxel if voxel is not None and math.isfinite(voxel) and voxel > 0 else float(max_dist) / 16
+
+
+def default_knn_r0(ref, k, max_dist):
+    """the first radius of the ladder of `k_nearest`: for a FusedCloud with a voxel size v, v max(2, sqrt(k)) -- a surface sampled at
+    spacing v holds about pi r^2 / v^2 points within r, so r = v sqrt(k) expects pi k of them (measured on the 12.6 M-point cloud of
+    tools/cloud_normals_speed.py at k = 16: 0.4 % of the rows are full at 2 v, 86 % at 4 v); else max_dist / 16"""
+    voxel = getattr(ref, 'voxel_size', None)
+    return voxel * max(2.0, math.sqrt(k)) if voxel is not None and math.isfinite(voxel) and voxel > 0 else float(max_dist) / 16
 
 
 def _device_of(*clouds):
@@ -61,12 +81,12 @@ def _points(cloud, device, what):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
-def ladder_radii(r0, max_dist):
-    """r_k = min(r_0 4^k, max_dist) as float32; the last is exactly max_dist"""
+def ladder_radii(r0, max_dist, step=LADDER_STEP):
+    """r_k = min(r_0 step^k, max_dist) as float32, step = 4 unless given; the last is exactly max_dist"""
     r0, max_dist = _radius_f32(r0, 'r0'), _radius_f32(max_dist, 'max_dist')
     out, k = [], 0
     while True:
-        r = np.float32(min(float(r0) * LADDER_STEP ** k, float(max_dist)))
+        r = np.float32(min(float(r0) * step ** k, float(max_dist)))
         if not r < max_dist:
             return out + [max_dist]
         out.append(r)
@@ -134,6 +154,133 @@ def nearest_in_cloud(query, ref, max_dist, r0=None, to_host=True, evals=None):
     if to_host:
         return d2.cpu().numpy(), idx.cpu().numpy()
     return d2, idx
+
+
+@torch.no_grad()
+def k_nearest(query, ref, k, max_dist, exclude_self=False, r0=None, to_host=True, evals=None, step=KNN_LADDER_STEP, cell_factor=KNN_CELL_FACTOR):
+    """(d2, idx) of the k nearest neighbours of every query point in `ref` within max_dist: d2 (N, k) float32, idx (N, k) int32. DEFINED
+    without a grid (include/dust3r_hip.h, d3r_cloud_knn): the candidates of a query with three finite coordinates are the finite reference
+    points with fp32 d2 <= max_dist^2; exclude_self drops the candidate whose INDEX is the query's (query is ref, or a cloud of equal length:
+    a duplicate at another index stays); the row holds the k smallest (d2, index) pairs in ascending lexicographic order, padded with
+    (+inf, -1). Bit for bit what an fp32 brute force with np.lexsort gives. 1 <= k <= 32. The search is the radius ladder of
+    `nearest_in_cloud` with r_j = min(r_0 step^j, max_dist): a query is resolved once its LAST column is found -- every point within r_j was
+    looked at, so k candidates within r_j are the k smallest at any larger radius -- and each rung overwrites the rows still open. r0: the
+    first radius, default `default_knn_r0`; evals as for `nearest_in_cloud`; cell_factor: the cells of a rung are cell_factor r_j wide (speed
+    only). One host synchronisation (the reference cloud's bounds)."""
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f'k_nearest: k = {k} outside [1, {MAX_K}]')
+    max_dist = _radius_f32(max_dist, 'max_dist')
+    _lib.require_device()
+    device = _device_of(query, ref)
+    if r0 is None:
+        r0 = default_knn_r0(ref, k, max_dist)
+    radii = ladder_radii(min(float(_radius_f32(r0, 'r0')), float(max_dist)), max_dist, step=step)
+    Q = _points(query, device, 'query')
+    R = Q if query is ref else _points(ref, device, 'ref')
+    nq, nr = len(Q), len(R)
+    if exclude_self and nq != nr:
+        raise ValueError(f'k_nearest: exclude_self needs query is ref, or clouds of equal length; got {nq} and {nr} points')
+    d2 = torch.full((nq, k), float('inf'), dtype=torch.float32, device=device)
+    idx = torch.full((nq, k), -1, dtype=torch.int32, device=device)
+    if nq > 0 and nr > 0:
+        with torch.cuda.device(device):
+            lo, hi, n_valid = _bounds(R, device)
+            if n_valid > 0:
+                size = int(lib.d3r_cloud_grid_workspace_bytes(nr, nq))
+                if size == 0:
+                    raise ValueError(f'k_nearest: clouds of {nq} and {nr} points are too large')
+                work = torch.empty(size, dtype=torch.uint8, device=device)
+                lo_c = (C.c_float * 3)(*lo.tolist())
+                for j, r in enumerate(radii):
+                    cell, bits = grid_cell(lo, hi, _radius_f32(float(r) * cell_factor, 'cell'))
+                    bits_c = (C.c_int * 3)(*bits)
+                    check(lib.d3r_cloud_grid_build(nr, ptr(R), lo_c, float(cell), bits_c, ptr(work), current_stream()), 'cloud_grid_build')
+                    check(lib.d3r_cloud_knn(nr, nq, ptr(Q), k, float(r), lo_c, float(cell), bits_c, int(bool(exclude_self)), int(j > 0), ptr(d2), ptr(idx),
+                                            ptr(evals), ptr(work), current_stream()), 'cloud_knn')
+    if to_host:
+        return d2.cpu().numpy(), idx.cpu().numpy()
+    return d2, idx
+
+
+@torch.no_grad()
+def knn_mean_distances(d2, idx):
+    """Of the rows of `k_nearest` (device tensors (N, k)): mean (N,) float32 = the mean distance to the k neighbours (fp64 sum of IEEE square
+    roots in column order, one rounding), NaN where fewer than k were found; count (1,) int64 = the full rows; sums (2,) float64 = the sum
+    of their means and of the means' squares. d3r_cloud_knn_distances; device tensors, no synchronisation."""
+    _lib.require_device()
+    device = d2.device
+    n, k = d2.shape
+    mean = torch.full((n,), float('nan'), dtype=torch.float32, device=device)
+    count = torch.zeros((1,), dtype=torch.int64, device=device)
+    sums = torch.zeros((2,), dtype=torch.float64, device=device)
+    if n > 0:
+        with torch.cuda.device(device):
+            work = torch.empty(int(lib.d3r_cloud_knn_distances_workspace_bytes(n)), dtype=torch.uint8, device=device)
+            check(lib.d3r_cloud_knn_distances(n, k, ptr(d2.contiguous()), ptr(idx.contiguous()), ptr(mean), ptr(count), ptr(sums), ptr(work),
+                                              current_stream()), 'cloud_knn_distances')
+    return mean, count, sums
+
+
+def outlier_threshold(count, sum_mean, sum_mean2, std_ratio):
+    """mean + std_ratio std of `count` mean neighbour distances from their sum and their sum of squares, host fp64. The std is the sample's
+    (count - 1 in the denominator, as Open3D's remove_statistical_outlier; a variance that rounds below zero counts as zero; 0 for fewer
+    than two values). NaN when count is 0: no point is kept then."""
+    count, s1, s2 = int(count), float(sum_mean), float(sum_mean2)
+    if count <= 0:
+        return float('nan')
+    mean = s1 / count
+    var = max(s2 - count * mean * mean, 0.0) / (count - 1) if count > 1 else 0.0
+    return mean + float(std_ratio) * math.sqrt(var)
+
+
+@torch.no_grad()
+def cloud_normals(points, ref, idx, min_neighbors=3):
+    """(normals (N, 3) float32, curvature (N,) float32) of `points` from the neighbour rows idx (N, k) into `ref`, on the device: per point
+    the fp64 scatter matrix of the point and its found neighbours, the unit eigenvector of its smallest eigenvalue l0 (the first component
+    of largest magnitude positive) and l0 / (l0 + l1 + l2); the zero normal and NaN with fewer than min_neighbors. d3r_cloud_normals."""
+    _lib.require_device()
+    device = idx.device
+    P = _points(points, device, 'points')
+    R = P if points is ref else _points(ref, device, 'ref')
+    n, k = idx.shape
+    if len(P) != n:
+        raise ValueError(f'cloud_normals: {len(P)} points, {n} neighbour rows')
+    normals = torch.zeros((n, 3), dtype=torch.float32, device=device)
+    curvature = torch.full((n,), float('nan'), dtype=torch.float32, device=device)
+    if n > 0 and len(R) > 0:
+        with torch.cuda.device(device):
+            check(lib.d3r_cloud_normals(n, ptr(P), len(R), ptr(R), k, ptr(idx.contiguous()), int(min_neighbors), ptr(normals), ptr(curvature),
+                                        current_stream()), 'cloud_normals')
+    return normals, curvature
+
+
+@torch.no_grad()
+def orient_normals(points, normals, depth, conf, intrinsics, cam2world, heights, widths, tol=0.05):
+    """`normals` (N, 3) float32 on the device, oriented IN PLACE towards the cameras that see each point; returns n_seen (N,) int32, the
+    views in which the point is visible. depth, conf: a scene's padded (n, row) stacks (utils/padded.py), intrinsics (n, 3, 3), cam2world
+    (n, 4, 4), heights / widths the int32 shape tables. A view sees a point when it projects in front of the camera onto a pixel whose depth
+    agrees within tol (relative); the vote is the confidence-weighted sum of the cosines to the seeing cameras, over all cameras with weight
+    1 when none sees it. d3r_cloud_orient_normals."""
+    from .utils.geometry import inv
+    _lib.require_device()
+    device = normals.device
+    P = _points(points, device, 'points')
+    n, n_views = len(P), len(depth)
+    if normals.shape != (n, 3) or normals.dtype != torch.float32 or not normals.is_contiguous():
+        raise ValueError(f'orient_normals: normals must be a contiguous float32 ({n}, 3) tensor')
+    n_seen = torch.zeros((n,), dtype=torch.int32, device=device)
+    if n > 0:
+        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()      # noqa: E731
+        depth, conf, cam2world = f32(depth), f32(conf), f32(cam2world)
+        if depth.shape != conf.shape or depth.ndim != 2:
+            raise ValueError(f'orient_normals: depth {tuple(depth.shape)} and conf {tuple(conf.shape)} must be the same (n, row) stacks')
+        centers = cam2world[:, :3, 3].contiguous()
+        with torch.cuda.device(device):
+            check(lib.d3r_cloud_orient_normals(n, ptr(P), ptr(normals), ptr(n_seen), n_views, ptr(depth), ptr(conf), ptr(f32(intrinsics)),
+                                               ptr(f32(inv(cam2world))), ptr(centers), ptr(heights), ptr(widths), depth.shape[1], float(tol),
+                                               current_stream()), 'cloud_orient_normals')
+    return n_seen
 
 
 @torch.no_grad()

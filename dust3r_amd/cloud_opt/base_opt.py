@@ -347,13 +347,16 @@ class BasePCOptimizer(nn.Module):
         return res
 
     @torch.no_grad()
-    def fuse(self, voxel_size=None, min_count=1, weights='conf', to_host=True):
+    def fuse(self, voxel_size=None, min_count=1, weights='conf', to_host=True, normals=False, outliers=None, k=16):
         """The scene as ONE point cloud (new; the reference exports every masked pixel of every view): the masked points of all views
         (`get_masks()` at the scene's current min_conf_thr, as the GLB export) binned into voxels of `voxel_size` and averaged per voxel,
         weighted by the images' confidences (weights='conf') or equally (weights=None); `viz.fuse_points` on the scene's padded stacks,
         csrc/fuse.hip. voxel_size=None: the median pixel footprint (`viz.default_voxel_size`: median depth / focal; a ValueError when it is
         not a positive number -- NaN depth maps or focals -- while the scene has valid points: give a voxel_size then). min_count: voxels of
-        fewer points are dropped. Returns a `viz.FusedCloud` (`.save_ply(path)`; `export.write_colmap` takes it)."""
+        fewer points are dropped. outliers=std_ratio: statistical outlier removal on the fused cloud first (`FusedCloud.remove_outliers`
+        over k neighbours); normals=True: then normals from k neighbours, turned towards the cameras of this scene that see each point
+        (`FusedCloud.estimate_normals(scene=self)`; csrc/cloud_knn.hip). Returns a `viz.FusedCloud` (`.save_ply(path)`;
+        `export.write_colmap` takes it)."""
         if self.imgs is None:
             raise ValueError('fuse needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
         if self.device.type != 'cuda':
@@ -364,8 +367,13 @@ class BasePCOptimizer(nn.Module):
         if voxel_size is None:       # evaluated once the bounds pass has found a valid point
             def voxel_size():
                 return default_voxel_size(self.get_depthmaps(raw=True), [h * w for h, w in self.imshapes], self.get_focals())
-        return fuse_points(self.imgs, self.get_pts3d(raw=True), self.get_masks(raw=True), self._im_conf if weights == 'conf' else None, voxel_size,
-                           self.device, min_count=min_count, to_host=to_host)
+        cloud = fuse_points(self.imgs, self.get_pts3d(raw=True), self.get_masks(raw=True), self._im_conf if weights == 'conf' else None, voxel_size,
+                            self.device, min_count=min_count, to_host=to_host)
+        if outliers is not None:
+            cloud, _ = cloud.remove_outliers(k=k, std_ratio=outliers)
+        if normals:
+            cloud = cloud.estimate_normals(k=k, scene=self)
+        return cloud
 
     @torch.no_grad()
     def show(self, show_pw_cams=False, show_pw_pts3d=False, cam_size=None, cam_colors=None, **kw):

@@ -12,27 +12,21 @@
 //                            cloud_query_kernel   one thread per query, in that order: the lanes of a wave walk the same runs
 //   d3r_cloud_distance_stats cloud_stats_kernel / cloud_stats_final_kernel   per-workgroup partials, then one workgroup in index order
 // As in fuse.hip: no atomics, no kernel waits on another workgroup, no scratch; the same bytes on every run. A cell that holds most of
-// the cloud is walked point by point by every query near it: slow, not wrong.
+// the cloud is walked point by point by every query near it: slow, not wrong. The workspace layout, the checks of cell and radius and the
+// padded cell range's arithmetic are in cloud_grid.hpp, shared with cloud_knn.hip (the k nearest neighbours on the same grid).
 #include "../../include/dust3r_hip.h"
 #include "common.hpp"
 #include "scene_common.hpp"
 #include "fuse_grid.hpp"
+#include "cloud_grid.hpp"
 
 namespace d3r {
 namespace cloud {
 
 using namespace d3r::fuse;
 
-constexpr int QT = 256;                 // threads of the per-point kernels
 constexpr int STAT_BLOCKS = 1024;       // grid cap of the statistics pass = the partials of the final pass
 constexpr int STAT_I = 2 + D3R_CLOUD_MAX_THRESHOLDS, STAT_D = 2;
-
-__global__ __launch_bounds__(64) void cloud_shape_kernel(int* __restrict__ shape, int n) {
-    if (threadIdx.x == 0) {
-        shape[0] = 1;
-        shape[1] = n;
-    }
-}
 
 // sorted pair i -> (point, original index)
 __global__ __launch_bounds__(QT) void cloud_gather_kernel(const float* __restrict__ pts, const int* __restrict__ idx, const int* __restrict__ n_dev, int cap,
@@ -72,18 +66,6 @@ __global__ __launch_bounds__(QT) void cloud_init_kernel(int n, int only_unresolv
         }
     }
 }
-
-// the next fp32 above x (nextafterf(x, +inf)): +inf and NaN stay
-D3R_DEV float next_up(float x) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, x);
-    if (x != x || u == 0x7F800000u) return x;
-    if ((u & 0x7FFFFFFFu) == 0u) return __builtin_bit_cast(float, 1u);
-    return __builtin_bit_cast(float, (u & 0x80000000u) ? u - 1u : u + 1u);
-}
-D3R_DEV float next_down(float x) { return -next_up(-x); }
-
-// floorf((x - lo_c) / cell), before the clamp
-D3R_DEV float axis_f(float x, const KeyParams& k, int c) { return floorf(__fdiv_rn(__fsub_rn(x, k.lo[c]), k.voxel)); }
 
 struct QueryArgs {
     KeyParams key;
@@ -252,48 +234,6 @@ __global__ __launch_bounds__(QT) void cloud_stats_final_kernel(int n_parts, cons
         for (int k = 0; k < STAT_D; ++k) sums_out[k] = sd[k];
     }
 }
-
-struct CloudWorkspace {
-    int* shape;             // [4]: the reference cloud as a view of 1 x n_ref, the query cloud as one of 1 x n_query
-    FuseWorkspace ref;      // stages 1-3 on the reference cloud; its n_dev = (valid points N, cells M) stays for the queries
-    float4* pts4;           // [n_ref]: the valid reference points in cell order, w = the original index
-    uint64_t* cell_key;     // [n_ref]
-    int* cell_start;        // [n_ref + 1]
-    FuseWorkspace qry;      // stages 1-2 on the queries
-    uint8_t* mask;          // [n_query]: only_unresolved
-    size_t bytes;
-};
-
-static CloudWorkspace cloud_workspace(void* base, int n_ref, int n_query) {
-    CloudWorkspace w;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* r = p ? p + off : nullptr;
-        off += align256(bytes);
-        return r;
-    };
-    w.shape = (int*)take(4 * sizeof(int));
-    w.ref = fuse_workspace(take(0), 1, n_ref, n_ref);
-    off += w.ref.bytes;
-    w.pts4 = (float4*)take((size_t)n_ref * sizeof(float4));
-    w.cell_key = (uint64_t*)take((size_t)n_ref * sizeof(uint64_t));
-    w.cell_start = (int*)take(((size_t)n_ref + 1) * sizeof(int));
-    w.qry = fuse_workspace(take(0), 1, n_query, n_query);
-    off += w.qry.bytes;
-    w.mask = (uint8_t*)take((size_t)n_query);
-    w.bytes = off;
-    return w;
-}
-
-static bool cloud_cell_ok(float cell) { return cell > 0.f && cell <= 3.0e38f; }
-// r r must be a normal fp32 number: a subnormal or zero r2 accepts d2 = 0 from coordinates far beyond r (their squares flush), an infinite
-// one accepts every point -- in both cases d2 <= r2 no longer bounds the coordinates by r', which is what the cell range rests on
-static bool cloud_radius_ok(float r) {
-    const float r2 = r * r;                                             // host code of a file built without contraction: one fp32 product
-    return r > 0.f && r2 >= 1.17549435e-38f && r2 <= 3.4028234e38f;
-}
-static int cloud_blocks(long long n) { return fuse_blocks(fuse_tiles(n, QT)); }
 
 }  // namespace cloud
 }  // namespace d3r

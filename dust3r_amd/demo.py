@@ -13,7 +13,8 @@ The function users call, `get_reconstructed_scene` (dust3r/demo.py:135-186): fil
 compute_global_alignment -> get_3D_model_from_scene, and the rgb / depth / confidence gallery it returns (`scene_gallery`: one GPU call
 for all images, csrc/gallery.hip, no matplotlib). `scenegraph_options` is the rule of set_scenegraph_options as plain data, and
 `python -m dust3r_amd.demo` the command line in place of the gradio page; its --fuse / --ply / --colmap (new) also write the fused cloud of
-`scene.fuse()` as scene.ply and as a COLMAP model (`write_fused`, dust3r_amd/export.py)."""
+`scene.fuse()` as scene.ply and as a COLMAP model (`write_fused`, dust3r_amd/export.py); --fuse_normals / --fuse_outliers add normals and
+statistical outlier removal."""
 import argparse
 import copy
 import json
@@ -360,7 +361,16 @@ def get_args_parser():
                              '(default: the median pixel footprint)')
     parser.add_argument('--ply', action='store_true', default=False, help='write the fused cloud as outdir/scene.ply (implies --fuse)')
     parser.add_argument('--colmap', action='store_true', default=False, help='write the fused cloud, cameras and images as a COLMAP model in outdir/colmap (implies --fuse)')
+    parser.add_argument('--fuse_normals', action='store_true', default=False,
+                        help='estimate normals of the fused cloud, turned towards the cameras, and write them into scene.ply (implies --fuse)')
+    parser.add_argument('--fuse_outliers', type=float, default=None, metavar='STD_RATIO',
+                        help='statistical outlier removal on the fused cloud: drop points whose mean neighbour distance exceeds mean + STD_RATIO std (implies --fuse)')
     return parser
+
+
+def wants_fuse(args):
+    """--ply, --colmap, --fuse_normals and --fuse_outliers imply --fuse"""
+    return args.fuse is not None or args.ply or args.colmap or args.fuse_normals or args.fuse_outliers is not None
 
 
 def clamp_scenegraph(num_files, winsize, refid, scenegraph_type):
@@ -403,14 +413,15 @@ def write_cameras(outdir, scene):
     return name
 
 
-def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, ply=True, colmap=False):
+def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, ply=True, colmap=False, normals=False, outliers=None):
     """outdir/scene.ply and / or outdir/colmap of the scene's fused cloud (scene.fuse; export.write_ply / write_colmap), with the mask of
-    get_3D_model_from_scene: min_conf_thr through the scene's confidence transform, the sky on request. Returns the file names."""
+    get_3D_model_from_scene: min_conf_thr through the scene's confidence transform, the sky on request; normals / outliers as for scene.fuse.
+    Returns the file names."""
     from .export import write_colmap
     if mask_sky:
         scene = scene.mask_sky()
     scene.min_conf_thr = float(scene.conf_trf(torch.tensor(min_conf_thr)))
-    cloud = scene.fuse(voxel_size=voxel_size or None)
+    cloud = scene.fuse(voxel_size=voxel_size or None, normals=normals, outliers=outliers)
     written = []
     if ply:
         written.append(cloud.save_ply(os.path.join(outdir, 'scene.ply')))
@@ -435,9 +446,9 @@ def main(argv=None):
     if args.turntable > 0:
         written += render_turntable(os.path.join(args.outdir, 'turntable'), scene, n_frames=args.turntable, min_conf_thr=args.min_conf_thr,
                                     mask_sky=args.mask_sky, clean_depth=args.clean_depth, transparent_cams=args.transparent_cams, silent=args.silent)
-    if args.fuse is not None or args.ply or args.colmap:
+    if wants_fuse(args):
         written += write_fused(args.outdir, scene, voxel_size=args.fuse, min_conf_thr=args.min_conf_thr, mask_sky=args.mask_sky,
-                               ply=args.ply or not args.colmap, colmap=args.colmap)
+                               ply=args.ply or not args.colmap, colmap=args.colmap, normals=args.fuse_normals, outliers=args.fuse_outliers)
     if not args.silent:
         print('(wrote', len(written), 'files to', args.outdir, ')')
     return 0

@@ -1,7 +1,7 @@
 """File formats other tools read, for the fused cloud of `scene.fuse()` (viz.FusedCloud): binary PLY, and a COLMAP model (sparse/0 +
 images/, the layout Gaussian-splatting trainers take). Host only: struct and numpy; bulk bytes go out through memoryview, as in glb.py.
 
-Out of scope: normals, meshing, TSDF fusion, 2-D tracks in the COLMAP model (every image has no 2-D points, every point an empty track),
+Out of scope: meshing, TSDF fusion, normals in the COLMAP model, 2-D tracks in the COLMAP model (every image has no 2-D points, every point an empty track),
 ASCII PLY."""
 import os
 import struct
@@ -10,6 +10,7 @@ import numpy as np
 
 _PLY_VERTEX = [('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
 _PLY_TYPES = {'<f4': 'float', 'u1': 'uchar', '<i4': 'int'}
+_PLY_NORMAL = [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]       # directly after z, where MeshLab, Open3D and Poisson reconstruction expect them
 _PLY_OPTIONAL = {'confidence': '<f4', 'count': '<i4'}
 
 CAMERA_MODEL_PINHOLE = 1        # COLMAP's model id of PINHOLE (fx, fy, cx, cy)
@@ -27,13 +28,20 @@ def _rgb_rows(colors, n):
 
 
 # ---- PLY ------------------------------------------------------------------------------------------------------------------------------
-def write_ply(path, positions, colors, weight=None, count=None):
-    """Binary little-endian PLY: per vertex `float x y z`, `uchar red green blue`, then `float confidence` (weight) and `int count` when
-    given. positions (M, 3), colors (M, 3) or (M, 4) (alpha dropped), weight (M,), count (M,). Returns the path."""
+def write_ply(path, positions, colors, weight=None, count=None, normals=None):
+    """Binary little-endian PLY: per vertex `float x y z`, `float nx ny nz` when normals are given, `uchar red green blue`, then
+    `float confidence` (weight) and `int count` when given. positions (M, 3), colors (M, 3) or (M, 4) (alpha dropped), weight (M,),
+    count (M,), normals (M, 3). Without normals the file is the one the four-argument call writes. Returns the path."""
     positions = np.asarray(_host(positions), dtype=np.float32).reshape(-1, 3)
     colors = _rgb_rows(colors, len(positions))
     fields = list(_PLY_VERTEX)
     extra = {}
+    if normals is not None:
+        normals = np.asarray(_host(normals), dtype=np.float32)
+        if normals.shape != positions.shape:
+            raise ValueError(f'write_ply: {len(positions)} positions, normals of shape {normals.shape}')
+        fields[3:3] = _PLY_NORMAL
+        extra.update(nx=normals[:, 0], ny=normals[:, 1], nz=normals[:, 2])
     for name, arr in (('confidence', weight), ('count', count)):
         if arr is not None:
             extra[name] = np.asarray(_host(arr)).reshape(-1)
@@ -55,7 +63,7 @@ def write_ply(path, positions, colors, weight=None, count=None):
 
 def read_ply(path):
     """Reads the dialect `write_ply` writes (binary little-endian, one vertex element, the properties above in that order): a dict of
-    positions (M, 3) float32, colors (M, 3) uint8 and, when present, confidence (M,) float32 and count (M,) int32."""
+    positions (M, 3) float32, colors (M, 3) uint8 and, when present, normals (M, 3) float32, confidence (M,) float32 and count (M,) int32."""
     with open(path, 'rb') as f:
         raw = f.read()
     end = raw.find(b'end_header\n')
@@ -72,6 +80,8 @@ def read_ply(path):
     names = {v: k for k, v in _PLY_TYPES.items()}
     fields = [(name, names[t]) for t, name in props]
     want = list(_PLY_VERTEX) + [(k, v) for k, v in _PLY_OPTIONAL.items() if k in dict(fields)]
+    if 'nx' in dict(fields):
+        want[3:3] = _PLY_NORMAL
     if fields != want:
         raise ValueError(f'{path}: vertex properties {props} are not the ones write_ply writes')
     dtype = np.dtype(fields)
@@ -81,6 +91,8 @@ def read_ply(path):
     rows = np.frombuffer(body, dtype=dtype)
     out = dict(positions=np.stack([rows['x'], rows['y'], rows['z']], axis=1) if n else np.zeros((0, 3), np.float32),
                colors=np.stack([rows['red'], rows['green'], rows['blue']], axis=1) if n else np.zeros((0, 3), np.uint8))
+    if 'nx' in rows.dtype.names:
+        out['normals'] = np.stack([rows['nx'], rows['ny'], rows['nz']], axis=1) if n else np.zeros((0, 3), np.float32)
     for name in _PLY_OPTIONAL:
         if name in rows.dtype.names:
             out[name] = rows[name].copy()

@@ -9,6 +9,8 @@
 - the fused cloud (new): `fuse_points` merges the views' pointmaps into one voxel-fused, weighted cloud (csrc/fuse.hip, C ABI
   `d3r_fuse_bounds` / `d3r_fuse_voxels`), a `FusedCloud`; dust3r_amd/export.py writes it as PLY or as a COLMAP model.
 The interactive viewers (a window, show_raw_pointcloud*) are not mirrored."""
+import math
+
 import numpy as np
 import torch
 
@@ -151,19 +153,87 @@ class FusedCloud:
     with to_host=False. voxel_size, origin (3,) float32 (the minimum of the fused points: voxel (i, j, k) starts at origin + voxel_size (i, j,
     k)) and bounds = (min, max) of the fused points, (+inf, -inf) for an empty cloud."""
 
-    def __init__(self, positions, colors, weight, count, voxel_size, bounds):
+    def __init__(self, positions, colors, weight, count, voxel_size, bounds, normals=None, curvature=None):
         self.positions, self.colors, self.weight, self.count = positions, colors, weight, count
         self.voxel_size = float(voxel_size)
         self.bounds = bounds
         self.origin = bounds[0]
+        self.normals, self.curvature = normals, curvature      # (M, 3) float32 and (M,) float32 of `estimate_normals`, else None
 
     def __len__(self):
         return len(self.positions)
 
     def save_ply(self, path):
-        """Binary little-endian PLY with the per-point confidence (= weight) and count (export.write_ply)."""
+        """Binary little-endian PLY with the per-point confidence (= weight) and count, and the normals when the cloud has them
+        (export.write_ply)."""
         from .export import write_ply
-        return write_ply(path, *(_to_numpy(a) for a in (self.positions, self.colors, self.weight, self.count)))
+        return write_ply(path, *(_to_numpy(a) for a in (self.positions, self.colors, self.weight, self.count)),
+                         normals=None if self.normals is None else _to_numpy(self.normals))
+
+    def _neighbour_radius(self, max_dist):
+        """max_dist of the neighbour searches: 8 voxels unless given. A surface sampled at spacing v holds about pi r^2 / v^2 points within
+        r, so 16 neighbours lie within about 2.3 v: the default leaves a factor of three."""
+        if max_dist is not None:
+            return float(max_dist)
+        if not (math.isfinite(self.voxel_size) and self.voxel_size > 0):
+            raise ValueError(f'the cloud has no voxel size ({self.voxel_size!r}): give max_dist')
+        return 8.0 * self.voxel_size
+
+    @torch.no_grad()
+    def estimate_normals(self, k=16, max_dist=None, scene=None, tol=0.05, min_neighbors=3):
+        """A new cloud with `normals` (M, 3) float32 and `curvature` (M,) float32, on the GPU (csrc/cloud_knn.hip): per point the k nearest
+        other points within max_dist (default 8 voxels; cloud_metrics.k_nearest, exact), the fp64 scatter matrix of the point and those
+        neighbours, the unit eigenvector of its smallest eigenvalue l0, curvature = l0 / (l0 + l1 + l2). A point with fewer than
+        min_neighbors neighbours gets the zero normal and NaN. Without a scene the sign makes the component of largest magnitude positive;
+        with a scene (the aligned scene the cloud was fused from) every normal is turned towards the cameras that see its point:
+        visible = it projects onto a pixel whose depth agrees within tol (relative); the vote is weighted by the pixels' confidences, and
+        falls back to all cameras for a point no view sees (cloud_metrics.orient_normals). Arrays come back where this cloud's are."""
+        from .cloud_metrics import _device_of, _points, cloud_normals, default_knn_r0, k_nearest, orient_normals
+        on_device = isinstance(self.positions, torch.Tensor)
+        device = scene.device if scene is not None and not on_device else _device_of(self)
+        P = _points(self, device, 'cloud')
+        normals = torch.zeros((len(P), 3), dtype=torch.float32, device=device)
+        curvature = torch.full((len(P),), float('nan'), dtype=torch.float32, device=device)
+        if len(P) > 0:
+            radius = self._neighbour_radius(max_dist)
+            _, idx = k_nearest(P, P, k, radius, exclude_self=True, r0=min(default_knn_r0(self, k, radius), radius), to_host=False)
+            normals, curvature = cloud_normals(P, P, idx, min_neighbors=min_neighbors)
+            if scene is not None:
+                heights, widths, _ = scene._shape_tables
+                orient_normals(P, normals, scene.get_depthmaps(raw=True), scene._im_conf, scene.get_intrinsics(), scene.get_im_poses(), heights, widths,
+                               tol=tol)
+        if not on_device:
+            normals, curvature = normals.cpu().numpy(), curvature.cpu().numpy()
+        return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=normals, curvature=curvature)
+
+    @torch.no_grad()
+    def remove_outliers(self, k=16, std_ratio=2.0, max_dist=None):
+        """(cloud, keep): statistical outlier removal on the GPU. Per point the mean distance to its k nearest other points within max_dist
+        (default 8 voxels); a point is kept when it HAS k neighbours within max_dist and its mean is <= mean + std_ratio std of those
+        means (cloud_metrics.outlier_threshold: host fp64 from three sums reduced on the device; the fp32 means widened to fp64 for the
+        comparison). Open3D's remove_statistical_outlier with the search truncated at max_dist: a point with fewer than k neighbours
+        there is an outlier. keep: (M,) bool. Normals and curvature, when present, are carried along. One host synchronisation more
+        than `k_nearest` (the three sums)."""
+        from .cloud_metrics import _device_of, _points, default_knn_r0, k_nearest, knn_mean_distances, outlier_threshold
+        on_device = isinstance(self.positions, torch.Tensor)
+        device = _device_of(self)
+        P = _points(self, device, 'cloud')
+        keep = torch.zeros((len(P),), dtype=torch.bool, device=device)
+        if len(P) > 0:
+            radius = self._neighbour_radius(max_dist)
+            d2, idx = k_nearest(P, P, k, radius, exclude_self=True, r0=min(default_knn_r0(self, k, radius), radius), to_host=False)
+            mean, count, sums = knn_mean_distances(d2, idx)
+            packed = torch.cat([count.double(), sums]).cpu().tolist()      # one read-back (the count is exact in fp64 below 2^53)
+            threshold = outlier_threshold(int(packed[0]), packed[1], packed[2], std_ratio)
+            keep = mean.double() <= threshold                              # NaN (fewer than k neighbours, or no full row at all): dropped
+        fields = [self.positions, self.colors, self.weight, self.count, self.normals, self.curvature]
+        if on_device:
+            out = [None if a is None else a[keep] for a in fields]
+            mask = keep
+        else:
+            mask = keep.cpu().numpy()
+            out = [None if a is None else a[mask] for a in fields]
+        return FusedCloud(*out[:4], voxel_size=self.voxel_size, bounds=self.bounds, normals=out[4], curvature=out[5]), mask
 
     def distance_to(self, other, max_dist, to_host=True):
         """(d2, idx) of every point of this cloud in `other` (a FusedCloud or (N, 3) points) within max_dist: squared distances (+inf where

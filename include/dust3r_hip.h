@@ -503,6 +503,50 @@ size_t d3r_cloud_distance_stats_workspace_bytes(int n);
 int d3r_cloud_distance_stats(int n, const float* query, const float* d2, const int* idx, int n_tau, const float* tau, long long* counts_out,
                              double* sums_out, void* workspace, void* stream);
 
+/* The k nearest neighbours of every point, and what the fused cloud needs of them: mean neighbour distances (statistical outlier removal),
+ * normals, their orientation by the scene's cameras (new; csrc/cloud_knn.hip). Clouds, validity, d2, r, lo, cell, bits and the workspace
+ * are those of d3r_cloud_grid_build / d3r_cloud_nearest above; the grid is built by d3r_cloud_grid_build, unchanged.
+ * d3r_cloud_knn: 1 <= k <= D3R_CLOUD_MAX_K. THE RESULT, stated without the grid: the CANDIDATES of a valid query q are the valid reference
+ *   points g with d2(q, R_g) <= r2 = r r (fp32); with exclude_self != 0 the candidate g == q is dropped -- by index only: a duplicate of the
+ *   query at another index stays. Row q of d2_out [n_query][k] and idx_out [n_query][k] holds the k smallest pairs (d2, g) in lexicographic
+ *   order, ascending; a row of fewer candidates is padded with (+inf, -1); an invalid query gets a fully padded row. This is what an fp32
+ *   brute force over all pairs gives, bit for bit. Each thread owns one query, in the order of the queries' cells, and keeps its sorted list
+ *   in registers (8, 16 or 32 slots by k; insertion is an unrolled compare-and-shift, the last slot the pruning bound).
+ *   only_unresolved = 0: every row is written. only_unresolved != 0: the rows whose LAST column holds an index >= 0 on entry are kept and
+ *   their queries are not searched; the other rows are overwritten. Sound for a radius ladder: every point with d2 <= r2 is looked at, so
+ *   k candidates within r are the k smallest of any larger radius. evals (optional, DEVICE int [n_query]): += the distances evaluated.
+ * d3r_cloud_knn_distances: over the rows of d2 / idx [n][k] as written above. mean_out [n] fp32: the fp64 sum, in column order, of
+ *   sqrt((double)d2) (IEEE) over the row's found neighbours, divided by their number and rounded once; NaN when fewer than k were found.
+ *   count_out [1] DEVICE int64 = the rows with all k found; sums_out [2] DEVICE fp64 = { sum of (double)mean_out, sum of its squares } over
+ *   those rows. Per-workgroup partials of a fixed launch shape, then one workgroup in index order. workspace:
+ *   d3r_cloud_knn_distances_workspace_bytes(n) bytes of DEVICE memory.
+ * d3r_cloud_normals: points [n][3], ref [n_ref][3], idx [n][k] rows of ref (an index outside [0, n_ref) counts as not found). The SAMPLE of
+ *   a point is the point itself followed by its found neighbours in column order. With fewer than min_neighbors (>= 2; 3 is usual) found:
+ *   the normal (0, 0, 0) and the curvature NaN. Otherwise, in fp64: the mean, the 3 x 3 scatter matrix about it, its eigenvalues l0 <= l1 <=
+ *   l2 by cyclic Jacobi (a fixed number of sweeps over named scalars) and the unit eigenvector of l0. normals_out [n][3] fp32, signed so that
+ *   the first component of largest magnitude is positive; curvature_out [n] fp32 = l0 / (l0 + l1 + l2).
+ * d3r_cloud_orient_normals: normals [n][3] oriented in place by a visibility vote over n_views cameras; n_seen [n] int32 = the views in
+ *   which the point is visible. depth, conf [n_views][max_area], intrinsics [n_views][9], world2cam [n_views][16], img_h / img_w as for
+ *   d3r_clean_pointcloud (a scene's padded stacks), centers [n_views][3] the camera centres, all DEVICE. A thread owns one point and walks
+ *   the views in order; it projects with the arithmetic of clean_pointcloud: per row ((m0 x + m1 y) + m2 z) + m3, then the intrinsics' rows,
+ *   every operation a separate IEEE fp32 rounding, pixel = rint of the fp32 quotient (half to even). View v is VISIBLE when pz > 0, the
+ *   pixel lies inside the view, and |pz - depth_v[pixel]| <= tol depth_v[pixel] (fp32). The vote s = sum over the visible views, in order,
+ *   of w_v dot(n, (c_v - p) / |c_v - p|) in fp64, w_v = conf_v[pixel] (a point AT a centre gives 0); when no view is visible the same sum
+ *   over all views with weight 1. The normal is negated when s < 0. 0 <= tol < 1.
+ * No atomics, no waiting between workgroups, no scratch. D3R_ERR_INVALID on NULL, sizes or k out of range and on what d3r_cloud_nearest
+ * refuses; nothing is launched then. No allocation, no synchronisation. */
+#define D3R_CLOUD_MAX_K 32
+int d3r_cloud_knn(int n_ref, int n_query, const float* query, int k, float r, const float* lo, float cell, const int* bits, int exclude_self,
+                  int only_unresolved, float* d2_out, int* idx_out, int* evals, void* workspace, void* stream);
+size_t d3r_cloud_knn_distances_workspace_bytes(int n);
+int d3r_cloud_knn_distances(int n, int k, const float* d2, const int* idx, float* mean_out, long long* count_out, double* sums_out, void* workspace,
+                            void* stream);
+int d3r_cloud_normals(int n, const float* points, int n_ref, const float* ref, int k, const int* idx, int min_neighbors, float* normals_out,
+                      float* curvature_out, void* stream);
+int d3r_cloud_orient_normals(int n, const float* points, float* normals, int* n_seen, int n_views, const float* depth, const float* conf,
+                             const float* intrinsics, const float* world2cam, const float* centers, const int* img_h_dev, const int* img_w_dev,
+                             int max_area, float tol, void* stream);
+
 /* The depth / confidence gallery of the demo (the end of get_reconstructed_scene, dust3r/demo.py:168-184) for n images in one call.
  * depth, conf [n][max_area] DEVICE fp32 (a scene's padded stacks), npix_dev [n] DEVICE int: the pixel count of each image (a count that is
  * negative or above max_area makes its image empty); what lies behind a count is neither read into a result nor written. table [257][4]
