@@ -96,6 +96,9 @@ def _load():
         'd3r_conv2d_nhwc_x': (i, [vp, vp, fp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, i, vp, i, vp]),
         'd3r_convt_gemm': (i, [vp, vp, fp, vp, i, i, i, i, i, i, i, i, i, vp]),
         'd3r_conv_head4': (i, [vp, vp, fp, fp, fp, fp, fp, i, i, i, i, i, i, i, i, i, i, i, f, f, vp, i, vp]),
+        'd3r_up2_conv_head4': (i, [vp, vp, vp, fp, fp, fp, fp, fp, i, i, i, i, i, i, i, i, i, i, f, f, vp, i, vp]),
+        'd3r_up2_conv_route': (i, [i, i, i, i, i, i, i, i]),
+        'd3r_up2_conv2d_nhwc_x': (i, [vp, vp, vp, fp, vp, i, i, i, i, i, i, i, i, vp, i, vp]),
         'd3r_head_final': (i, [vp, i, fp, fp, fp, fp, C.c_size_t, i, i, i, i, f, f, i, vp]),
         'd3r_linear_head_post': (i, [fp, fp, fp, i, i, i, i, i, i, i, i, f, f, vp]),
         'd3r_attention': (i, [vp, vp, vp, vp, i, i, i, i, i, f, i, vp]),

@@ -157,6 +157,55 @@ extern "C" int d3r_conv_head4(const void* in, const void* wgt, const float* bias
     return rc_of(launch_gemm(dtype, p, plan, (hipStream_t)stream));
 }
 
+// x2 bilinear map of `src` + d3r_conv_head4 on it: ONE launch where the plan has it (engine.hip conv_up2_head4: the map is never stored), else the two launches of
+// today through `map`. Both built by the parameter builders the engine uses (kernels.hpp).
+static GemmParams up2_head4_capi_params(const void* src, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B, int Hi,
+                                        int Wi, int cstride, int cin_pad, int Cout, int pstride, int conf_stride, const void* zero_page) {
+    GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, wgt, bias, cin_pad, Cout, zero_page);
+    p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = conf_stride; p.res1 = w4; p.res2 = b4;
+    return p;
+}
+// the typed-store form (engine.hip conv_up2): d3r_conv2d_nhwc_x's launch without residuals or ReLU copy
+static GemmParams up2_conv_capi_params(const void* src, const void* wgt, const float* bias, void* out, int B, int Hi, int Wi, int cstride, int cin_pad, int Cout, int ldo,
+                                       int flags, const void* zero_page) {
+    GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, wgt, bias, cin_pad, Cout, zero_page);
+    p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.ldr = ldo; p.ldo2 = ldo;
+    return p;
+}
+extern "C" int d3r_up2_conv_route(int dtype, int B, int Hi, int Wi, int cstride, int cin_pad, int Cout, int head4) {
+    if (!conv_dtype(dtype) || B <= 0 || Hi <= 0 || Wi <= 0 || Cout <= 0 || cin_pad <= 0 || cstride < cin_pad) return D3R_ERR_INVALID;
+    const GemmParams p = head4 ? up2_head4_capi_params(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, cstride, cin_pad, Cout, 3, 1, nullptr)
+                               : up2_conv_capi_params(nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, cstride, cin_pad, Cout, rup(Cout, 8), 0, nullptr);
+    return gemm_plan_for(p, dtype).up2 ? 1 : 0;
+}
+extern "C" int d3r_up2_conv2d_nhwc_x(const void* src, void* map, const void* wgt, const float* bias, void* out, int B, int Hi, int Wi, int cstride, int cin_pad, int Cout,
+                                     int ldo, int flags, const void* zero_page, int dtype, void* stream) {
+    if (!src || !wgt || !out || !zero_page || !conv_dtype(dtype) || B <= 0 || Hi <= 0 || Wi <= 0 || Cout <= 0) return D3R_ERR_INVALID;
+    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || cstride < cin_pad || cstride % 8 != 0 || Cout % 4 != 0 || ldo < Cout || (flags & ~(GF_RELU | GF_NOWIDE))) return D3R_ERR_INVALID;
+    GemmParams p = up2_conv_capi_params(src, wgt, bias, out, B, Hi, Wi, cstride, cin_pad, Cout, ldo, flags, zero_page);
+    const GemmPlan plan = gemm_plan_for(p, dtype);
+    if (plan.up2) return rc_of(launch_gemm(dtype, p, plan, (hipStream_t)stream));
+    if (!map) return D3R_ERR_INVALID;
+    const int rc = rc_of(launch_upsample2x(dtype, src, map, nullptr, B, Hi, Wi, cstride, cstride, 2 * Hi, 2 * Wi, (hipStream_t)stream));
+    if (rc != D3R_OK) return rc;
+    return d3r_conv2d_nhwc_x(map, wgt, bias, out, nullptr, nullptr, nullptr, B, 2 * Hi, 2 * Wi, cstride, cin_pad, Cout, Cout, ldo, 3, 1, 1, flags, zero_page, dtype, stream);
+}
+extern "C" int d3r_up2_conv_head4(const void* src, void* map, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B,
+                                  int Hi, int Wi, int cstride, int cin_pad, int Cout, int pstride, int conf_stride, int depth_mode, int conf_mode, float conf_vmin,
+                                  float conf_vmax, const void* zero_page, int dtype, void* stream) {
+    if (!src || !wgt || !w4 || !b4 || !pts || !conf || !zero_page || !conv_dtype(dtype) || B <= 0 || Hi <= 0 || Wi <= 0 || Cout <= 0) return D3R_ERR_INVALID;
+    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || cstride < cin_pad || cstride % 8 != 0 || pstride < 3 || conf_stride < 1) return D3R_ERR_INVALID;
+    GemmParams p = up2_head4_capi_params(src, wgt, bias, w4, b4, pts, conf, B, Hi, Wi, cstride, cin_pad, Cout, pstride, conf_stride, zero_page);
+    if (!post_mode(p.post, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
+    const GemmPlan plan = gemm_plan_for(p, dtype);
+    if (plan.up2) return rc_of(launch_gemm(dtype, p, plan, (hipStream_t)stream));
+    if (!map) return D3R_ERR_INVALID;
+    const int rc = rc_of(launch_upsample2x(dtype, src, map, nullptr, B, Hi, Wi, cstride, cstride, 2 * Hi, 2 * Wi, (hipStream_t)stream));
+    if (rc != D3R_OK) return rc;
+    return d3r_conv_head4(map, wgt, bias, w4, b4, pts, conf, B, 2 * Hi, 2 * Wi, cstride, cin_pad, Cout, 3, pstride, conf_stride, depth_mode, conf_mode, conf_vmin, conf_vmax,
+                          zero_page, dtype, stream);
+}
+
 extern "C" int d3r_head_final(const void* feat, int C, const float* w4, const float* b4, float* pts, float* conf, size_t npix, int pstride, int conf_stride,
                               int depth_mode, int conf_mode, float conf_vmin, float conf_vmax, int dtype, void* stream) {
     PostMode pm;

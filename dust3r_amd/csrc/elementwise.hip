@@ -277,19 +277,32 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const void* __restrict_
 // index o is o (n - 1) / (2 n - 1): outputs 2 c and 2 c + 1 need input columns {x0, x0 + 1} and {x0', x0' + 1} with x0' = x0 or x0 + 1, so a
 // 2 x 2 output block reads a 3 x 3 input neighbourhood: 18 loads per 8 stores instead of 32 per 8. Every output pixel is evaluated with the
 // expression of the one-pixel kernel (rows interpolated along x, then along y).
+// The quad kernel's interpolation arithmetic. Split-fp16 (PIN): the shared, pinned forms of kernels.hpp up2_* -- the convolution that interpolates this map on the
+// fly (gemm_up2.hip, split-fp16 only) must reproduce it bit for bit. Every other precision keeps the plain, contractable expressions it has always had: hipcc
+// compiles them differently per instantiation (all fmas in bf16 / fp16 / fp32), and pinning the split-fp16 forms there would move those outputs.
+template <bool PIN> struct Up2Quad {
+    static D3R_DEV void src(float scale, int o, int& i0, float& l, float& h) {
+        if constexpr (PIN) up2_src(scale, o, i0, l, h);
+        else { const float f = scale * (float)o; i0 = (int)f; l = f - (float)i0; h = 1.f - l; }
+    }
+    static D3R_DEV float lerp(float h, float a, float l, float b) { if constexpr (PIN) return up2_lerp(h, a, l, b); else return h * a + l * b; }
+    static D3R_DEV float lerp_rev(float h, float a, float l, float b) { if constexpr (PIN) return up2_lerp_rev(h, a, l, b); else return h * a + l * b; }
+    static D3R_DEV float lerp_rr(float h, float a, float l, float b) { if constexpr (PIN) return up2_lerp_rr(h, a, l, b); else return h * a + l * b; }
+};
 template <int DT, bool NT>
 __global__ __launch_bounds__(256) void upsample2x_quad_kernel(const void* __restrict__ in, void* __restrict__ out, void* __restrict__ out_relu,
                                                               int Hi, int Wi, int C, int cstride, int Ho, int Wo) {
     const int cn = C / 8;
     const int hp = (Ho + 1) / 2, wp = (Wo + 1) / 2;
     const int b = blockIdx.x / hp, r = blockIdx.x - b * hp;
-    const float sh = Hi > 1 ? (float)(Hi - 1) / (float)(2 * Hi - 1) : 0.f;
-    const float sw = Wi > 1 ? (float)(Wi - 1) / (float)(2 * Wi - 1) : 0.f;
+    using Q = Up2Quad<DT == D3R_F16X3>;
+    const float sh = up2_scale(Hi), sw = up2_scale(Wi);
     // the two output rows of this block
     const int oyA = 2 * r, oyB = min(2 * r + 1, Ho - 1);
-    const float fyA = sh * (float)oyA, fyB = sh * (float)oyB;
-    const int yb = (int)fyA, y0B = (int)fyB;
-    const float lyA = fyA - (float)yb, hyA = 1.f - lyA, lyB = fyB - (float)y0B, hyB = 1.f - lyB;
+    int yb, y0B;
+    float lyA, hyA, lyB, hyB;
+    Q::src(sh, oyA, yb, lyA, hyA);
+    Q::src(sh, oyB, y0B, lyB, hyB);
     const bool offY = y0B > yb;                                   // row B starts one input row further down
     const int ry0 = yb, ry1 = min(yb + 1, Hi - 1), ry2 = min(yb + 2, Hi - 1);
     const size_t row[3] = {((size_t)b * Hi + ry0) * Wi, ((size_t)b * Hi + ry1) * Wi, ((size_t)b * Hi + ry2) * Wi};
@@ -299,9 +312,10 @@ __global__ __launch_bounds__(256) void upsample2x_quad_kernel(const void* __rest
     for (int i = threadIdx.x; i < items; i += 256) {
         const int cpair = i / cn, c = (i - cpair * cn) * 8;
         const int oxA = 2 * cpair, oxB = min(2 * cpair + 1, Wo - 1);
-        const float fxA = sw * (float)oxA, fxB = sw * (float)oxB;
-        const int xb = (int)fxA, x0B = (int)fxB;
-        const float lxA = fxA - (float)xb, hxA = 1.f - lxA, lxB = fxB - (float)x0B, hxB = 1.f - lxB;
+        int xb, x0B;
+        float lxA, hxA, lxB, hxB;
+        Q::src(sw, oxA, xb, lxA, hxA);
+        Q::src(sw, oxB, x0B, lxB, hxB);
         const bool offX = x0B > xb;
         const int cx0 = xb, cx1 = min(xb + 1, Wi - 1), cx2 = min(xb + 2, Wi - 1);
         // rows interpolated along x at the two output columns: hA[r][k], hB[r][k]
@@ -314,20 +328,20 @@ __global__ __launch_bounds__(256) void upsample2x_quad_kernel(const void* __rest
             load8<DT>(in, (row[rr] + cx2) * (size_t)cstride + c, v2);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                hA[rr][k] = hxA * v0[k] + lxA * v1[k];
+                hA[rr][k] = rr == 0 ? Q::lerp_rev(hxA, v0[k], lxA, v1[k]) : Q::lerp(hxA, v0[k], lxA, v1[k]);      // kernels.hpp: which output takes which form
                 const float b0 = offX ? v1[k] : v0[k], b1 = offX ? v2[k] : v1[k];
-                hB[rr][k] = hxB * b0 + lxB * b1;
+                hB[rr][k] = Q::lerp(hxB, b0, lxB, b1);
             }
         }
         float oAA[8], oAB[8], oBA[8], oBB[8];      // (row, column)
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            oAA[k] = hyA * hA[0][k] + lyA * hA[1][k];
-            oAB[k] = hyA * hB[0][k] + lyA * hB[1][k];
+            oAA[k] = Q::lerp_rr(hyA, hA[0][k], lyA, hA[1][k]);
+            oAB[k] = Q::lerp(hyA, hB[0][k], lyA, hB[1][k]);
             const float a0 = offY ? hA[1][k] : hA[0][k], a1 = offY ? hA[2][k] : hA[1][k];
             const float b0 = offY ? hB[1][k] : hB[0][k], b1 = offY ? hB[2][k] : hB[1][k];
-            oBA[k] = hyB * a0 + lyB * a1;
-            oBB[k] = hyB * b0 + lyB * b1;
+            oBA[k] = Q::lerp(hyB, a0, lyB, a1);
+            oBB[k] = Q::lerp(hyB, b0, lyB, b1);
         }
         const bool haveXB = 2 * cpair + 1 < Wo;
         auto put = [&](size_t orow, int ox, const float (&o)[8]) __attribute__((always_inline)) {

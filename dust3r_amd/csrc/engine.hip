@@ -476,6 +476,47 @@ bool conv_head4(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, co
     return true;
 }
 
+// The same launch reading the x2 bilinear map of `src` (B, Hi, Wi) without the map in memory (AMODE_CONV_UP2, gemm_up2.hip). up2_head4_params with null
+// operands is what head_upfused asks the plan about: the layout (which then takes no map from the arena) and the launch decide by the same predicate.
+GemmParams up2_head4_params(const d3r_model* m, const void* src, int B, int Hi, int Wi, int cstride, const ConvW& w, const float* w4, const float* b4,
+                            float* pts, float* conf, int pstride, int cstride_conf) {
+    GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, w.w, w.b, w.cin_pad, w.Cout, m->zero_page);
+    p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = cstride_conf; p.res1 = w4; p.res2 = b4; p.post = m->post;
+    return p;
+}
+// The typed-store form (head.0 on the x2 map of refinenet-0's output): conv() without residuals
+GemmParams up2_conv_params(const d3r_model* m, const void* src, int B, int Hi, int Wi, int cstride, const ConvW& w, void* out, int ldo, int flags) {
+    GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, w.w, w.b, w.cin_pad, w.Cout, m->zero_page);
+    p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.ldr = ldo; p.ldo2 = ldo;
+    return p;
+}
+// Which of the head's two x2 maps are interpolated inside the convolution that reads them. D3R_HEAD_UPFUSE=0: neither (the two-kernel routes: test A/B);
+// the last convolution's route also needs its fused tail (D3R_HEAD_FUSE).
+bool up2_switch_on(const d3r_model* m) {
+    const char* u = getenv("D3R_HEAD_UPFUSE");
+    return m->dt == D3R_F16X3 && !(u && u[0] == '0');
+}
+bool head_upfused(const d3r_model* m, const ConvW& w, int B, int Hi, int Wi, int cstride) {      // head.2 + tail on the x2 map of head.0's output
+    const char* e = getenv("D3R_HEAD_FUSE");
+    if (!up2_switch_on(m) || w.k != 3 || (e && e[0] == '0')) return false;
+    return gemm_plan_for(up2_head4_params(m, nullptr, B, Hi, Wi, cstride, w, nullptr, nullptr, nullptr, nullptr, 3, 1), m->dt).up2;
+}
+bool head0_upfused(const d3r_model* m, const ConvW& w, int B, int Hi, int Wi, int cstride, int ldo) {      // head.0 on the x2 map of refinenet-0's output
+    if (!up2_switch_on(m) || w.k != 3) return false;
+    return gemm_plan_for(up2_conv_params(m, nullptr, B, Hi, Wi, cstride, w, nullptr, ldo, 0), m->dt).up2;
+}
+void conv_up2(Ctx& c, const void* src, int B, int Hi, int Wi, int cstride, const ConvW& w, void* out, int ldo, int flags) {
+    GemmParams p = up2_conv_params(c.m, src, B, Hi, Wi, cstride, w, out, ldo, flags);
+    const GemmPlan plan = gemm_plan_for(p, c.m->dt);
+    launch(c, c.m->dt, p, PRF_CONV, w.Cout, w.k * w.k * w.Cin, false, &plan);
+}
+void conv_up2_head4(Ctx& c, const void* src, int B, int Hi, int Wi, int cstride, const ConvW& w, const float* w4, const float* b4,
+                    float* pts, float* conf, int pstride, int cstride_conf) {
+    GemmParams p = up2_head4_params(c.m, src, B, Hi, Wi, cstride, w, w4, b4, pts, conf, pstride, cstride_conf);
+    const GemmPlan plan = gemm_plan_for(p, c.m->dt);
+    launch(c, c.m->dt, p, PRF_CONV, w.Cout, w.k * w.k * w.Cin, false, &plan);
+}
+
 struct Arena {
     char* base; size_t off = 0, cap;
     Arena(void* b, size_t c) : base((char*)b), cap(c) {}
@@ -729,7 +770,7 @@ Dims dims_of(const d3r_model* m, const Call& k) {
 // ---- workspace layouts: ONE sequence of takes per arena. On Arena(nullptr, 0) it sizes the arena, on the real base it yields the pointers. ----
 struct DptGrid { int H[4], W[4]; };       // the four reassembled maps of a th x tw token grid
 DptGrid dpt_grid(int th, int tw) { return DptGrid{{4 * th, 2 * th, th, (th - 1) / 2 + 1}, {4 * tw, 2 * tw, tw, (tw - 1) / 2 + 1}}; }
-struct DptBufs { void *cmap[4], *t1, *r[4], *rr[4], *tA, *tB, *tC, *up[4], *h0, *h1, *h2; };      // up[lvl]: refinenet lvl's upsampled output
+struct DptBufs { void *cmap[4], *t1, *r[4], *rr[4], *tA, *tB, *tC, *up[4], *h0, *h1, *h2; bool fuse_up0, fuse_h1; };      // fuse_*: that x2 map is interpolated inside its consumer and has no buffer      // up[lvl]: refinenet lvl's upsampled output
 DptBufs dpt_layout(const d3r_model* m, const DptHead& D, Arena& ar, int B, int th, int tw) {
     const size_t eb = dt_bytes(m->dt), px8 = (size_t)B * 8 * th * 8 * tw;
     const DptGrid g = dpt_grid(th, tw);
@@ -738,9 +779,12 @@ DptBufs dpt_layout(const d3r_model* m, const DptHead& D, Arena& ar, int B, int t
     b.t1 = ar.take((size_t)B * th * tw * 768 * eb);
     for (int i = 0; i < 4; ++i) { b.r[i] = ar.take((size_t)B * g.H[i] * g.W[i] * 256 * eb); b.rr[i] = ar.take((size_t)B * g.H[i] * g.W[i] * 256 * eb); }
     for (void** t : {&b.tA, &b.tB, &b.tC}) *t = ar.take((size_t)B * g.H[0] * g.W[0] * 256 * eb);
+    // the two large x2 maps (refinenet-0's output: 1.6 GB per head at 32 pairs; head.0's: 3.2 GB) only where their consumers do not interpolate them themselves
+    b.fuse_up0 = head0_upfused(m, D.head0, B, g.H[0], g.W[0], 256, 128);
+    b.fuse_h1 = head_upfused(m, D.head2, B, 8 * th, 8 * tw, 128);
     for (int lvl = 3; lvl >= 0; --lvl)      // dpt_head.py:57 crops refinenet4's output to layer 3's size
-        b.up[lvl] = ar.take((size_t)B * (lvl == 3 ? g.H[2] : 2 * g.H[lvl]) * (lvl == 3 ? g.W[2] : 2 * g.W[lvl]) * 256 * eb);
-    b.h0 = ar.take(px8 * 128 * eb); b.h1 = ar.take(4 * px8 * 128 * eb); b.h2 = ar.take(4 * px8 * 128 * eb);
+        b.up[lvl] = lvl == 0 && b.fuse_up0 ? nullptr : ar.take((size_t)B * (lvl == 3 ? g.H[2] : 2 * g.H[lvl]) * (lvl == 3 ? g.W[2] : 2 * g.W[lvl]) * 256 * eb);
+    b.h0 = ar.take(px8 * 128 * eb); b.h1 = b.fuse_h1 ? nullptr : ar.take(4 * px8 * 128 * eb); b.h2 = ar.take(4 * px8 * 128 * eb);
     return b;
 }
 
@@ -778,12 +822,16 @@ Workspace ws_layout(const d3r_model* m, const Call& k, const Dims& d, Arena& ar)
         w.e = take_fold(ar, d.Me, d.Ge);
         for (int b = 0; b < 2; ++b) { w.fr[b] = ar.take((size_t)d.M2d * d.Cd * eb); w.l[b] = take_fold(ar, d.M2d, d.Gd); w.s[b] = take_fold(ar, d.Mmax, d.Gd); }
     }
-    for (int s = 0; s < 2 && m->cfg.head_type == 1 && d.do_dec; ++s) {      // both sides' arenas hold a chunk of the larger view
-        Arena sub(nullptr, 0);
-        dpt_layout(m, m->dpt[0], sub, d.chunk, k.d[s].th, k.d[s].tw);
-        const size_t a = ((sub.off + 255) & ~(size_t)255) + 256;
-        w.head_bytes = a > w.head_bytes ? a : w.head_bytes;
-    }
+    // both sides' arenas hold a chunk of the larger view -- a full chunk or the call's last, smaller one: with fewer pixel tiles the head may keep the x2 map
+    // that a full chunk does not take (head_upfused), so the smaller chunk is laid out too
+    for (int s = 0; s < 2 && m->cfg.head_type == 1 && d.do_dec; ++s)
+        for (int nb : {d.chunk, d.chunk > 0 ? k.B % d.chunk : 0}) {
+            if (nb <= 0) continue;
+            Arena sub(nullptr, 0);
+            dpt_layout(m, m->dpt[0], sub, nb, k.d[s].th, k.d[s].tw);
+            const size_t a = ((sub.off + 255) & ~(size_t)255) + 256;
+            w.head_bytes = a > w.head_bytes ? a : w.head_bytes;
+        }
     for (int s = 0; s < 2; ++s) w.head_arena[s] = ar.take(w.head_bytes);
     w.bytes = ar.off + 256;
     return w;
@@ -873,12 +921,16 @@ void run_dpt(Ctx& c, const DptHead& D, Arena ar, const Call& k, const void* cons
         conv(c, b.tA, B, H, W, 256, R.r2c2, 1, 1, o, 256, 0, m->cfg.dpt_skip_relu_inplace ? skip_relu : skip);
         // out_conv (1x1) commutes with the bilinear upsampling (both linear, weights sum to 1): run it at low resolution
         plain_linear(c, R.outc, NormIn{o}, 256, B * H * W, EPI_T, b.tA, 256);
+        if (lvl == 0 && b.fuse_up0) break;      // head.0 below interpolates this level's x2 map itself
         D3R_OTHER(launch_upsample2x(m->dt, b.tA, b.up[lvl], nullptr, B, H, W, 256, 256, lvl == 3 ? g.H[2] : 2 * H, lvl == 3 ? g.W[2] : 2 * W, c.st));
         path = b.up[lvl];
     }
     // head: 3x3 256->128, x2, 3x3 128->128 + ReLU, 1x1 128->4 + postprocess
     const int H8 = 8 * th, W8 = 8 * tw;
-    conv(c, path, B, H8, W8, 256, D.head0, 1, 1, b.h0, 128, 0);
+    if (b.fuse_up0) conv_up2(c, b.tA, B, g.H[0], g.W[0], 256, D.head0, b.h0, 128, 0);
+    else conv(c, path, B, H8, W8, 256, D.head0, 1, 1, b.h0, 128, 0);
+    // Split-fp16, whole 16 x 32 tiles of output pixels, a tile per CU: the x2 map is interpolated inside the last convolution (with the fused tail below), never stored
+    if (b.fuse_h1) { conv_up2_head4(c, b.h0, B, H8, W8, 128, D.head2, D.head4_w, D.head4_b, pts, conf, k.pstride, k.cstride); return; }
     D3R_OTHER(launch_upsample2x(m->dt, b.h0, b.h1, nullptr, B, H8, W8, 128, 128, 2 * H8, 2 * W8, c.st));
     // Split-fp16, enough pixels for the 512 x 128 tile (every wave then holds all 128 channels of its 64 pixels): the 1x1 convolution and
     // the postprocess run in the epilogue of the last 3x3 convolution, on its fp32 accumulators -- the 128-channel full-resolution map
@@ -1019,11 +1071,13 @@ int forward(d3r_model* m, const Call& k, hipStream_t st) {
     const Dims d = dims_of(m, k);
     Fwd F{m, k, d, ws_layout(m, k, d, ar), Ctx{m, st, D3R_OK, st}};
     if (!m->ws || F.w.bytes > ar.cap) return D3R_ERR_ALLOC;
-    for (int s = 0; s < 2 && F.w.head_bytes; ++s) {
-        Arena sub(F.w.head_arena[s], F.w.head_bytes);
-        dpt_layout(m, m->dpt[s], sub, d.chunk, k.d[s].th, k.d[s].tw);
-        if (sub.off > sub.cap) return D3R_ERR_ALLOC;
-    }
+    for (int s = 0; s < 2 && F.w.head_bytes; ++s)
+        for (int nb : {d.chunk, d.chunk > 0 ? k.B % d.chunk : 0}) {
+            if (nb <= 0) continue;
+            Arena sub(F.w.head_arena[s], F.w.head_bytes);
+            dpt_layout(m, m->dpt[s], sub, nb, k.d[s].th, k.d[s].tw);
+            if (sub.off > sub.cap) return D3R_ERR_ALLOC;
+        }
     Ctx& c = F.c;
     F.two = m->two_streams && !m->prof_on && m->side != nullptr;
     F.S[0] = st; F.S[1] = F.two ? m->side : st;

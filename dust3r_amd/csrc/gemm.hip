@@ -42,6 +42,7 @@
 #include <atomic>
 
 #include "kernels.hpp"
+#include "gemm_head4.hpp"
 
 namespace d3r {
 
@@ -790,64 +791,11 @@ __global__ __launch_bounds__(CF::NT, CF::MINW) void gemm_kernel(GemmParams p) {
     // ---- fused DPT head tail (EPI_HEAD4, kernels.hpp): this wave holds every output channel of its FJ x 16 rows --------------
     if constexpr (DT == D3R_F16X3 && CF::NWI == 1 && FI == 8) {
         if (p.epi == EPI_HEAD4) {
-            const float* hw = reinterpret_cast<const float*>(p.res1);
-            const float* hb = reinterpret_cast<const float*>(p.res2);
-            const float* bsrc = p.bias ? p.bias : hw;
-            const int C = p.n_store;
-            const bool has_bias = p.bias != nullptr;
-            const float floor_v = (p.flags & GF_RELU) ? 0.f : -3.0e38f;
-            float part[FJ][4];
-#pragma unroll
-            for (int fj = 0; fj < FJ; ++fj) part[fj][0] = part[fj][1] = part[fj][2] = part[fj][3] = 0.f;
-            // 1x1 weights and bias of fragment column fi: requested one fragment ahead (double buffered); the fence keeps hipcc from hoisting
-            // all 40 loads (160 registers next to the 128 accumulators) to the top
-            float4 wb[2][5];
-            auto request = [&](int fi, float4 (&d)[5]) __attribute__((always_inline)) {
-                const int n = fi * 16 + i4;                     // n0 == 0: one tile spans the channels
-                const int nc = min(n, C - 4);                   // channels >= C: zero accumulators (padded weight rows), zero 1x1 weights
-                d[4] = *reinterpret_cast<const float4*>(bsrc + nc);
-#pragma unroll
-                for (int o = 0; o < 4; ++o) d[o] = *reinterpret_cast<const float4*>(hw + (size_t)o * C + nc);
-            };
-            request(0, wb[0]);
-#pragma unroll
-            for (int fi = 0; fi < FI; ++fi) {
-                if (fi + 1 < FI) request(fi + 1, wb[(fi + 1) & 1]);
-                const float live = fi * 16 + i4 < C ? 1.f : 0.f;
-                const float4 bt = wb[fi & 1][4];
-                const float4 bi = make_float4(has_bias ? bt.x : 0.f, has_bias ? bt.y : 0.f, has_bias ? bt.z : 0.f, has_bias ? bt.w : 0.f);
-                float4 w4[4];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    const float4 t = wb[fi & 1][o];
-                    w4[o] = make_float4(t.x * live, t.y * live, t.z * live, t.w * live);
-                }
-#pragma unroll
-                for (int fj = 0; fj < FJ; ++fj) {
-                    const f32x4_t a = acc[fi][fj];
-                    // ReLU as a select-free maximum (a branch here splits the block and the register allocator spills around it)
-                    const float v0 = fmaxf(a[0] + bi.x, floor_v), v1 = fmaxf(a[1] + bi.y, floor_v), v2 = fmaxf(a[2] + bi.z, floor_v), v3 = fmaxf(a[3] + bi.w, floor_v);
-#pragma unroll
-                    for (int o = 0; o < 4; ++o)
-                        part[fj][o] = fmaf(v3, w4[o].w, fmaf(v2, w4[o].z, fmaf(v1, w4[o].y, fmaf(v0, w4[o].x, part[fj][o]))));
-                }
-                asm volatile("" ::: "memory");
-            }
-            // the four lane groups hold four quarters of a row's channels: add them up; lane group g then owns the rows of fragment g
-            const int g = lane >> 4;
-            float r4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int fj = 0; fj < FJ; ++fj)
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    const float t = rows_sum4(part[fj][o]);
-                    r4[o] = (fj == g) ? t : r4[o];
-                }
-            static_assert(FJ == 4, "one row fragment per lane group");
-            const int m = m0 + wj * (FJ * 16) + g * 16 + jl;
+            float r4[4];
+            head4_tail<FI, FJ>(p, acc, lane, r4);      // gemm_head4.hpp, shared with conv_up2_kernel
+            const int m = m0 + wj * (FJ * 16) + (lane >> 4) * 16 + jl;
             if (m < p.M)
-                postprocess_store(r4[0] + hb[0], r4[1] + hb[1], r4[2] + hb[2], r4[3] + hb[3], reinterpret_cast<float*>(p.out),
-                                  reinterpret_cast<float*>(p.out2), (size_t)m, p.ldo, p.ldo2, p.post);
+                postprocess_store(r4[0], r4[1], r4[2], r4[3], reinterpret_cast<float*>(p.out), reinterpret_cast<float*>(p.out2), (size_t)m, p.ldo, p.ldo2, p.post);
             return;
         }
     }
@@ -1572,6 +1520,7 @@ GemmEnv gemm_env() {
     if (const char* e = getenv("D3R_GEMM_PERSIST")) env.persist = e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1);
     if (const char* e = getenv("D3R_GEMM_T128W8")) env.t128w8 = atol(e);
     if (const char* e = getenv("D3R_GEMM_NOWIDE")) env.nowide = e[0] == '1';
+    if (const char* e = getenv("D3R_UP2_MIN_TILES")) env.up2_min_tiles = atol(e);      // tests: the fused x2 + convolution launch on fewer tiles than compute units
     return env;
 }
 
@@ -1588,6 +1537,7 @@ static bool gemm_args_ok(const GemmParams& p, int dt) {
     const int kt = 128 / (int)dt_bytes(dt);
     if (p.M <= 0 || p.n_pad % 128 != 0 || p.n_store > p.n_pad || p.K % kt != 0 || p.K <= 0) return false;
     if (p.amode == AMODE_CONV && (p.Cin % kt != 0 || p.zero_page == nullptr)) return false;
+    if (p.amode != AMODE_LINEAR && p.amode != AMODE_CONV && p.amode != AMODE_CONV_UP2) return false;
     if (p.epi == EPI_HEADS && p.head_c % 128 != 0 && p.head_c < (1 << 29)) return false;
     if (p.epi == EPI_HEAD4 && (p.n_store > 128 || p.n_store % 4 != 0 || !p.res1 || !p.res2 || !p.out || !p.out2)) return false;
     // folded LayerNorm (kernels.hpp): statistics come out of the wide fp32 epilogue only; the consumer side exists for split-fp16 operands, typed / GELU / head outputs
@@ -1611,6 +1561,8 @@ static hipError_t run_plan(int dt, const GemmParams& p_in, const GemmPlan& plan,
     p.flags |= plan.flags;
     p.splitk = plan.splitk;
     if (plan.cfg == GEMM_CFG_P4) return launch_gemm_p4(p, s);
+    // x2 bilinear map + convolution: the fused kernel where the plan has it, else nothing (the caller asked the plan first and took the two-kernel route)
+    if (p.amode == AMODE_CONV_UP2) return plan.up2 && conv_up2_fused(p, dt, gemm_env(), device_cus()) ? launch_conv_up2(p, s) : hipErrorInvalidValue;
     // the fused head tail needs a wave to hold every output channel of its rows: waves stacked along m, 128 columns per wave
     if (p.epi == EPI_HEAD4 && (dt != D3R_F16X3 || !(plan.cfg == GEMM_CFG_512x128 || plan.cfg == GEMM_CFG_256x128R))) return hipErrorInvalidValue;
 #ifdef D3R_GEMM_ONLY_DT      // development builds (-DD3R_GEMM_ONLY_DT=4): one precision mode only, a tenth of the compile time

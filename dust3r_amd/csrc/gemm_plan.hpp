@@ -10,13 +10,31 @@ struct GemmEnv {             // read by gemm_env() (gemm.hip), once per launch o
     int persist = -1;        // D3R_GEMM_PERSIST: -1 the heuristic decides, 0 never, 1 every eligible launch on the persistent kernel
     long t128w8 = 1100;      // D3R_GEMM_T128W8: 128 x 128 launches of fewer tiles run on eight waves (0 = never)
     bool nowide = false;     // D3R_GEMM_NOWIDE=1
+    long up2_min_tiles = -1; // D3R_UP2_MIN_TILES (tests): fewest pixel tiles of a fused x2 + convolution launch; -1 = one per compute unit
 };
 struct GemmPlan {
     int cfg = GEMM_CFG_128;  // GEMM_CFG_*, GEMM_CFG_P4 included, already mapped onto the shapes the operand type has: what profiles and host queries report
     bool w8 = false;         // cfg == GEMM_CFG_128 on EIGHT waves (include/dust3r_hip.h: D3R_TILE_128W8)
     int splitk = 1;          // blocks per tile along K (GemmParams::splitk of the launch)
     int flags = 0;           // what the launch ORs into p.flags
+    bool up2 = false;        // an AMODE_CONV_UP2 launch runs fused (gemm_up2.hip); false: there is no such launch, the caller materialises the map
 };
+
+// x2 bilinear map + 3x3 convolution in one launch (AMODE_CONV_UP2, gemm_up2.hip): split-fp16, whole 16 x 32 tiles of output pixels, whole 32-channel K slices,
+// one wave per 64 pixels holding all <= 128 output channels, the fused head tail or a typed store as the epilogue,
+// and at least one tile per compute unit -- below that the 512-pixel tiles leave CUs idle that the two-kernel route's smaller tiles fill.
+constexpr int UP2_TILE_H = 16, UP2_TILE_W = 32;
+inline bool conv_up2_fused(const GemmParams& p, int dt, const GemmEnv& env, int cus) {
+    if (dt != D3R_F16X3 || p.amode != AMODE_CONV_UP2) return false;
+    // epilogues: the fused head tail, or a typed store (bias, ReLU) of whole 8-channel groups without residuals or a ReLU copy
+    if (p.epi == EPI_T) { if (p.res1 || p.res2 || p.out2 || p.ldo % 8 != 0 || p.n_store % 8 != 0 || p.ldo < p.n_store || (p.flags & ~(GF_RELU | GF_NTSTORE | GF_NOWIDE))) return false; }
+    else if (p.epi != EPI_HEAD4) return false;
+    if (p.ksize != 3 || p.stride != 1 || p.pad != 1 || p.Hout != p.Hin || p.Wout != p.Win || (p.Hin & 1) || (p.Win & 1)) return false;
+    if (p.Hin % UP2_TILE_H != 0 || p.Win % UP2_TILE_W != 0 || p.Cin <= 0 || p.Cin % 32 != 0 || p.cstride % 8 != 0 || p.cstride < p.Cin) return false;
+    if (p.n_store > 128 || p.n_store % 4 != 0 || p.n_pad < 128 || p.K != 9 * p.Cin) return false;
+    const long tiles = (long)(p.M / (p.Hin * p.Win)) * (p.Hin / UP2_TILE_H) * (p.Win / UP2_TILE_W);
+    return tiles >= (env.up2_min_tiles >= 0 ? env.up2_min_tiles : (long)cus);
+}
 
 // tracing: a trace buffer (gemm_set_trace) is attached to this launch
 inline GemmPlan gemm_plan(const GemmParams& p, int dt, const GemmEnv& env, int cus, bool tracing) {
@@ -27,6 +45,11 @@ inline GemmPlan gemm_plan(const GemmParams& p, int dt, const GemmEnv& env, int c
     plan.flags |= GF_NTSTORE;      // wide epilogues store with the non-temporal policy (measured +3..10 % on isolated GEMMs, +1 % on the forward)
     const bool nowide = (p.flags | plan.flags) & GF_NOWIDE;
     tracing = tracing || p.trace;
+    if (p.amode == AMODE_CONV_UP2) {      // one shape, or no launch at all
+        plan.cfg = GEMM_CFG_512x128;
+        plan.up2 = !tracing && p.force_cfg < 0 && env.forced_cfg < 0 && conv_up2_fused(p, dt, env, cus);
+        return plan;
+    }
 
     // ---- persistent kernel (gemm_p4.hip) for this launch? Measured on MI355X inside the 32-pair forward (tools/launch_table.py, profiles/r06_*): it wins where the
     // epilogue is a large share of a tile's life and the tiles fill whole rounds of the CUs -- fc1 + GELU 395 -> 427 (encoder) / 363 -> 398 TFLOP/s (decoder),

@@ -5,7 +5,9 @@
 namespace d3r {
 
 // ------------------------------------------------------------------------------ GEMM / conv
-enum { AMODE_LINEAR = 0, AMODE_CONV = 1 };
+// AMODE_CONV_UP2 (split-fp16): Conv2d(3x3, stride 1, pad 1) whose input is the x2 bilinear map (align_corners = True, no crop) of `act`, a low-resolution NHWC map of
+// Hin / 2 x Win / 2 pixels -- Hin, Win, Hout, Wout and M describe the convolution on the map, which is never materialised (gemm_up2.hip; conv_up2_fused below decides)
+enum { AMODE_LINEAR = 0, AMODE_CONV = 1, AMODE_CONV_UP2 = 2 };
 enum { EPI_T = 0, EPI_F32 = 1, EPI_GELU = 2, EPI_HEADS = 3, EPI_CONVT = 4, EPI_HEAD4 = 5 };
 // EPI_HEAD4 (split-fp16, tiles whose waves hold all <= 128 output channels of their rows: the 512 x 128 / 256 x 128 R shapes): the DPT head's
 // tail fused into its last 3x3 convolution -- bias, ReLU (GF_RELU), Conv2d(C, 4, 1) on the fp32 accumulators, postprocess, store of
@@ -72,6 +74,8 @@ void gemm_set_trace(unsigned long long* buf, size_t capacity_blocks);
 // gemm_p4.hip: the persistent split-fp16 kernel whose epilogue runs under the next tile's K loop (tile configuration 10 in profiles)
 bool gemm_p4_eligible(const GemmParams& p, int dt);
 hipError_t launch_gemm_p4(const GemmParams& p, hipStream_t s);
+// gemm_up2.hip: AMODE_CONV_UP2 launches on 16 x 32 pixel tiles (eight waves of 128 (n) x 64 (m), profiled as tile configuration 3)
+hipError_t launch_conv_up2(const GemmParams& p, hipStream_t s);
 }  // namespace d3r
 #include "gemm_plan.hpp"      // GemmEnv, GemmPlan, gemm_plan(): the dispatch decision, pure
 namespace d3r {
@@ -102,6 +106,14 @@ inline GemmParams conv_gemm_params(const void* in, int B, int Hin, int Win, int 
     p.Hout = (Hin + 2 * pad - k) / stride + 1; p.Wout = (Win + 2 * pad - k) / stride + 1;
     p.M = B * p.Hout * p.Wout; p.K = k * k * cin_pad; p.n_pad = (Cout + 127) / 128 * 128; p.n_rows = (Cout + 255) / 256 * 256; p.n_store = Cout;
     p.zero_page = zero_page;
+    return p;
+}
+// The same 3x3 convolution (stride 1, pad 1) reading the x2 bilinear map of the low-resolution map `src` (B, Hi, Wi) without materialising it: AMODE_CONV_UP2.
+// Whether such a launch exists is the plan's answer (GemmPlan::up2, gemm_plan.hpp conv_up2_fused); where it does not, the caller runs launch_upsample2x and
+// conv_gemm_params on the map.
+inline GemmParams conv_up2_gemm_params(const void* src, int B, int Hi, int Wi, int cstride, const void* wgt, const float* bias, int cin_pad, int Cout, const void* zero_page) {
+    GemmParams p = conv_gemm_params(src, B, 2 * Hi, 2 * Wi, cstride, wgt, bias, cin_pad, Cout, 3, 1, 1, zero_page);
+    p.amode = AMODE_CONV_UP2;
     return p;
 }
 // head4_tile: the plan of an EPI_HEAD4 launch -- 512 x 128 where the heuristic picks it, else the FORCED 256 x 128 R (p.force_cfg is set) -- or false when
@@ -191,6 +203,47 @@ D3R_DEV void ln_quad_sums(const float4& v, float& sm, float& sq) {
     const float xx = v.x * v.x, yy = v.y * v.y, zz = v.z * v.z, ww = v.w * v.w;
     sm = (v.x + v.y) + (v.z + v.w);
     sq = (xx + yy) + (zz + ww);
+}
+// x2 bilinear map (align_corners = True, ATen's source index): the arithmetic shared by upsample2x_quad_kernel (elementwise.hip) and the convolution that interpolates its
+// own A operand (gemm_up2.hip), which must reproduce the materialised map bit for bit. Under -ffp-contract=fast hipcc contracts `h*a + l*b` differently from context to
+// context -- and, after SLP vectorisation, from one output of the quad kernel to the next -- so every product and fma is written out, with contraction OFF, in the form the
+// stand-alone kernel compiled to before the arithmetic was shared (read from its gfx950 disassembly and confirmed on an MI355X against an fp32 emulation of every
+// candidate form, element by element; its outputs did not move):
+//   up2_scale    the source step of an axis of n input samples
+//   up2_src      output index o -> first source sample i0, weights (h, l) of samples i0 and min(i0 + 1, n - 1); the product is rounded before the subtraction
+//   up2_lerp     h a + l b as fma(h, a, round(l b)): v_mul_f32 + v_fmac_f32, the form of every interpolation but the two below
+//   up2_lerp_rev fma(l, b, round(h a)): the x interpolation of the FIRST source row of a quad (a 2 x 2 block of map pixels on even coordinates) at its EVEN column --
+//                the vectoriser packed rows 0 and 1 of that column into one v_pk_mul_f32 / v_pk_fma_f32 pair with the operands of row 0 crossed
+//   up2_lerp_rr  round(h a) + round(l b): the y interpolation of the pixel on even row AND even column (v_pk_mul_f32 + v_add_f32)
+// up2_pixel_forms states which pixel takes which: a map pixel (oy, ox) with first source row y0 interpolates its top source row with up2_lerp_rev iff ox is even and
+// that row is row 0 of its quad (oy even, or oy odd and row oy - 1 starts at the same source row), and its two rows with up2_lerp_rr iff oy and ox are even.
+D3R_DEV float up2_scale(int n) { return n > 1 ? (float)(n - 1) / (float)(2 * n - 1) : 0.f; }
+D3R_DEV void up2_src(float scale, int o, int& i0, float& l, float& h) {
+#pragma clang fp contract(off)
+    const float f = scale * (float)o;
+    i0 = (int)f;
+    l = f - (float)i0;
+    h = 1.f - l;
+}
+D3R_DEV float up2_lerp(float h, float a, float l, float b) {
+#pragma clang fp contract(off)
+    const float t = l * b;
+    return __builtin_fmaf(h, a, t);
+}
+D3R_DEV float up2_lerp_rev(float h, float a, float l, float b) {
+#pragma clang fp contract(off)
+    const float t = h * a;
+    return __builtin_fmaf(l, b, t);
+}
+D3R_DEV void up2_pixel_forms(int oy, int ox, int y0, int y0_prev_row, bool& top_rev, bool& y_rr) {
+    const bool ecol = !(ox & 1), erow = !(oy & 1);
+    top_rev = ecol && (erow || y0 == y0_prev_row);
+    y_rr = ecol && erow;
+}
+D3R_DEV float up2_lerp_rr(float h, float a, float l, float b) {
+#pragma clang fp contract(off)
+    const float s = h * a, t = l * b;
+    return s + t;
 }
 template <int TPR> D3R_DEV void ln_row_stats(const float2* __restrict__ pr, int G, int sub, float inv_c, float eps, float& rstd, float& nmr) {
     static_assert(TPR == 1 || TPR == 2 || TPR == 4, "threads per row");

@@ -111,15 +111,16 @@ def linear_x3(act, weight, bias=None, epilogue='store', residual=None):
     return out if epi == 1 else unpack_x3(out)
 
 
-def upsample2x_x3(x, out_hw=None):
-    """`upsample2x_nhwc` on split-fp16 maps: x (B,H,W,C) fp32, C % 8 == 0, packed along the channel axis; fp32 result."""
+def upsample2x_x3(x, out_hw=None, rows=False):
+    """`upsample2x_nhwc` on split-fp16 maps: x (B,H,W,C) fp32, C % 8 == 0, packed along the channel axis; fp32 result, or -- rows=True -- the split rows
+    (B,Ho,Wo,2C) fp16 exactly as the kernel stored them (unpacking to fp32 and packing again may re-split a value into another (hi, lo) pair)."""
     _lib.require_device()
     B, H, W, Cc = x.shape
     Ho, Wo = out_hw if out_hw is not None else (2 * H, 2 * W)
     xp = pack_x3(x)
     out = torch.empty((B, Ho, Wo, 2 * Cc), dtype=torch.float16, device=x.device)
     check(lib.d3r_upsample2x_nhwc(ptr(xp), ptr(out), B, H, W, Cc, Ho, Wo, _lib.DTYPE_F16X3, current_stream()), 'upsample2x(x3)')
-    return unpack_x3(out)
+    return out if rows else unpack_x3(out)
 
 
 def _e4m3(x):
@@ -354,23 +355,28 @@ def pack_convt_bias_device(b, k, cout_pad=None):
 
 
 def conv2d_nhwc_x(x, wp, bias, Cout, k, stride=1, pad=0, cin_pad=None, relu=False, nowide=False, res1=None, res2=None, relu_copy=False, n_store=None, ldo=None,
-                  dtype='fp16x3'):
+                  dtype='fp16x3', x_rows=False, out_rows=None):
     """d3r_conv2d_nhwc_x (the engine's conv()): x (B, H, W, cstride) of which the first cin_pad channels are read, wp from pack_conv_weight_device, bias (Cout,) or None;
     res1 / res2 (B, Ho, Wo, ldo). Returns (B, Ho, Wo, ldo) [, its ReLU copy]."""
     _lib.require_device()
     B, H, W, cstride = x.shape
+    if x_rows:      # x: the split-fp16 storage rows of another kernel (upsample2x_x3(rows=True)), handed over untouched
+        assert dtype == 'fp16x3' and x.dtype == torch.float16 and cstride % 2 == 0
+        cstride //= 2
     cin_pad = cin_pad or cstride
     n_store = Cout if n_store is None else n_store
     ldo = n_store if ldo is None else ldo
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    xr = to_rows(x, dtype)
+    xr = x.contiguous() if x_rows else to_rows(x, dtype)
     bp = None if bias is None else pad_rows(bias.float())
-    out = to_rows(torch.zeros((B, Ho, Wo, ldo), dtype=torch.float32, device=x.device), dtype)
+    out = out_rows if out_rows is not None else to_rows(torch.zeros((B, Ho, Wo, ldo), dtype=torch.float32, device=x.device), dtype)
     out2 = torch.zeros_like(out) if relu_copy else None
     r1, r2 = (None if r is None else to_rows(r, dtype) for r in (res1, res2))
     flags = (_lib.CONV_RELU if relu else 0) | (_lib.CONV_NOWIDE if nowide else 0)
     check(lib.d3r_conv2d_nhwc_x(ptr(xr), ptr(wp), ptr(bp), ptr(out), ptr(r1), ptr(r2), ptr(out2), B, H, W, cstride, cin_pad, Cout, n_store, ldo, k, stride, pad, flags,
                                 ptr(_zero_page(x.device)), _lib.DTYPES[dtype], current_stream()), f'conv2d_nhwc_x({dtype})')
+    if out_rows is not None:      # the caller's storage rows, as stored
+        return out
     return (from_rows(out, dtype), from_rows(out2, dtype)) if relu_copy else from_rows(out, dtype)
 
 
@@ -406,14 +412,18 @@ def _head_views(npix, strides, pts, conf):
     return pts.as_strided((npix, 3), (ps, 1)), conf.as_strided((npix,), (cs,))
 
 
-def conv_head4(x, wp, bias, w4, b4, Cout, post=('exp', 'exp', 1.0, float('inf')), strides=(3, 1), cin_pad=None, k=3, dtype='fp16x3', pts=None, conf=None):
-    """d3r_conv_head4 (the engine's conv_head4(): 3x3 conv + ReLU + 1x1 conv to 4 + postprocess in one launch): x (B, H, W, cstride), w4 (4, Cout), b4 (4,).
+def conv_head4(x, wp, bias, w4, b4, Cout, post=('exp', 'exp', 1.0, float('inf')), strides=(3, 1), cin_pad=None, k=3, dtype='fp16x3', pts=None, conf=None, x_rows=False):
+    """d3r_conv_head4 (the engine's conv_head4(): 3x3 conv + ReLU + 1x1 conv to 4 + postprocess in one launch): x (B, H, W, cstride), w4 (4, Cout), b4 (4,);
+    x_rows=True: x is already the split-fp16 rows (B, H, W, 2 cstride) of another kernel (upsample2x_x3(rows=True)), handed over untouched.
     Returns (launched, pts (B*H*W, 3), conf (B*H*W,)); launched False = the entry point declined and wrote nothing."""
     _lib.require_device()
     B, H, W, cstride = x.shape
+    if x_rows:
+        assert dtype == 'fp16x3' and x.dtype == torch.float16 and cstride % 2 == 0
+        cstride //= 2
     npix = B * H * W
     pts, conf = _head_outputs(npix, strides, pts, conf, x.device)
-    xr = to_rows(x, dtype)
+    xr = x.contiguous() if x_rows else to_rows(x, dtype)
     bp = None if bias is None else pad_rows(bias.float())
     w4, b4 = w4.float().contiguous(), b4.float().contiguous()
     rc = lib.d3r_conv_head4(ptr(xr), ptr(wp), ptr(bp), ptr(w4), ptr(b4), ptr(pts), ptr(conf), B, H, W, cstride,
@@ -421,6 +431,53 @@ def conv_head4(x, wp, bias, w4, b4, Cout, post=('exp', 'exp', 1.0, float('inf'))
     if rc != _lib.DECLINED:
         check(rc, f'conv_head4({dtype})')
     return (rc == 0,) + _head_views(npix, strides, pts, conf)
+
+
+def up2_conv_route(B, Hi, Wi, Cin, Cout, cstride=None, dtype='fp16x3', head4=True):
+    """d3r_up2_conv_route (host only): True = up2_conv_head4 (head4=False: up2_conv2d_nhwc_x) interpolates the x2 map inside the convolution, False = it runs the two launches."""
+    rc = lib.d3r_up2_conv_route(_lib.DTYPES[dtype], B, Hi, Wi, cstride or Cin, Cin, Cout, int(head4))
+    if rc not in (0, 1):
+        check(rc, f'up2_conv_route({dtype})')
+    return rc == 1
+
+
+def _up2_scratch(fused, B, Hi, Wi, cstride, dtype, device):
+    """the map the two-launch route goes through; None where the one-launch route runs (the entry points accept NULL there)"""
+    return None if fused else to_rows(torch.zeros((B, 2 * Hi, 2 * Wi, cstride), dtype=torch.float32, device=device), dtype)
+
+
+def up2_conv_head4(x, wp, bias, w4, b4, Cout, post=('exp', 'exp', 1.0, float('inf')), strides=(3, 1), cin_pad=None, dtype='fp16x3', pts=None, conf=None):
+    """d3r_up2_conv_head4: conv_head4 (3x3) on the x2 bilinear map of x (B, Hi, Wi, cstride), in one launch where up2_conv_route says so, else through a scratch map.
+    Returns (launched, pts (B*2Hi*2Wi, 3), conf (B*2Hi*2Wi,))."""
+    _lib.require_device()
+    B, Hi, Wi, cstride = x.shape
+    npix = B * 4 * Hi * Wi
+    pts, conf = _head_outputs(npix, strides, pts, conf, x.device)
+    xr = to_rows(x, dtype)
+    scratch = _up2_scratch(up2_conv_route(B, Hi, Wi, cin_pad or cstride, Cout, cstride, dtype), B, Hi, Wi, cstride, dtype, x.device)
+    bp = None if bias is None else pad_rows(bias.float())
+    w4, b4 = w4.float().contiguous(), b4.float().contiguous()
+    rc = lib.d3r_up2_conv_head4(ptr(xr), ptr(scratch), ptr(wp), ptr(bp), ptr(w4), ptr(b4), ptr(pts), ptr(conf), B, Hi, Wi, cstride, cin_pad or cstride, Cout,
+                                strides[0], strides[1], *_post_args(post), ptr(_zero_page(x.device)), _lib.DTYPES[dtype], current_stream())
+    if rc != _lib.DECLINED:
+        check(rc, f'up2_conv_head4({dtype})')
+    return (rc == 0,) + _head_views(npix, strides, pts, conf)
+
+
+def up2_conv2d_nhwc_x(x, wp, bias, Cout, relu=False, cin_pad=None, dtype='fp16x3', out_rows=None, ldo=None):
+    """d3r_up2_conv2d_nhwc_x: conv2d_nhwc_x (3x3, stride 1, pad 1) on the x2 bilinear map of x (B, Hi, Wi, cstride). out_rows: the storage rows (B, 2Hi, 2Wi, ldo) to
+    write into (split-fp16: an fp16 tensor of 2 ldo per pixel), e.g. pre-filled with sentinels. Returns the storage rows."""
+    _lib.require_device()
+    B, Hi, Wi, cstride = x.shape
+    ldo = Cout if ldo is None else ldo
+    xr = to_rows(x, dtype)
+    if out_rows is None:
+        out_rows = to_rows(torch.zeros((B, 2 * Hi, 2 * Wi, ldo), dtype=torch.float32, device=x.device), dtype)
+    scratch = _up2_scratch(up2_conv_route(B, Hi, Wi, cin_pad or cstride, Cout, cstride, dtype, head4=False) and ldo % 8 == 0, B, Hi, Wi, cstride, dtype, x.device)
+    bp = None if bias is None else pad_rows(bias.float())
+    check(lib.d3r_up2_conv2d_nhwc_x(ptr(xr), ptr(scratch), ptr(wp), ptr(bp), ptr(out_rows), B, Hi, Wi, cstride, cin_pad or cstride, Cout, ldo,
+                                    _lib.CONV_RELU if relu else 0, ptr(_zero_page(x.device)), _lib.DTYPES[dtype], current_stream()), f'up2_conv2d_nhwc_x({dtype})')
+    return out_rows
 
 
 def head_final(feat, w4, b4, post=('exp', 'exp', 1.0, float('inf')), strides=(3, 1), dtype='fp16x3', pts=None, conf=None):

@@ -173,6 +173,20 @@ int d3r_convt_gemm(const void* act, const void* wgt, const float* bias, void* ou
 int d3r_conv_head4(const void* in, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B, int Hin,
                    int Win, int cstride, int cin_pad, int Cout, int ksize, int pstride, int conf_stride, int depth_mode, int conf_mode,
                    float conf_vmin, float conf_vmax, const void* zero_page, int dtype, void* stream);
+/* d3r_up2_conv_head4 (split-fp16): d3r_conv_head4 with ksize 3 on the x2 bilinear map (align_corners, no crop) of the low-resolution map src [B][Hi][Wi][cstride].
+ *   Where d3r_up2_conv_route answers 1 -- split-fp16, 2 Hi % 16 == 0, 2 Wi % 32 == 0, cin_pad % 32 == 0, Cout <= 128 and Cout % 4 == 0, at least one 16 x 32 tile of
+ *   output pixels per compute unit (D3R_UP2_MIN_TILES moves that floor: tests) -- the map is interpolated inside the convolution, in ONE launch, and `map` is not
+ *   touched (it may be NULL). Everywhere else the entry point runs d3r_upsample2x_nhwc into map [B][2 Hi][2 Wi][cstride] and d3r_conv_head4 on it, whose
+ *   D3R_DECLINED it passes on. Both routes give the same bits.
+ * d3r_up2_conv_route: host only, no launch; head4 = 1 asks about d3r_up2_conv_head4, 0 about d3r_up2_conv2d_nhwc_x: 1 = the one-launch route, 0 = the two launches; D3R_ERR_INVALID for arguments the entry point refuses. */
+int d3r_up2_conv_head4(const void* src, void* map, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B,
+                       int Hi, int Wi, int cstride, int cin_pad, int Cout, int pstride, int conf_stride, int depth_mode, int conf_mode, float conf_vmin,
+                       float conf_vmax, const void* zero_page, int dtype, void* stream);
+int d3r_up2_conv_route(int dtype, int B, int Hi, int Wi, int cstride, int cin_pad, int Cout, int head4);
+/* d3r_up2_conv2d_nhwc_x: the same for d3r_conv2d_nhwc_x (ksize 3, stride 1, pad 1; bias, D3R_CONV_RELU; no residuals, no ReLU copy; n_store = Cout) on the x2 map of src:
+ *   out [B][2 Hi][2 Wi][ldo] in `dtype`. One launch where d3r_up2_conv_route(..., head4 = 0) answers 1 (additionally Cout % 8 == 0 and ldo % 8 == 0), else through `map`. */
+int d3r_up2_conv2d_nhwc_x(const void* src, void* map, const void* wgt, const float* bias, void* out, int B, int Hi, int Wi, int cstride, int cin_pad, int Cout,
+                          int ldo, int flags, const void* zero_page, int dtype, void* stream);
 int d3r_head_final(const void* feat, int C, const float* w4, const float* b4, float* pts, float* conf, size_t npix, int pstride, int conf_stride,
                    int depth_mode, int conf_mode, float conf_vmin, float conf_vmax, int dtype, void* stream);
 int d3r_linear_head_post(const float* feat, float* pts, float* conf, int B, int th, int tw, int ps, int pstride, int conf_stride, int depth_mode,
@@ -294,7 +308,7 @@ size_t d3r_model_device_bytes(const d3r_model* m);
 #define D3R_MODEL_OPT_GRAPH_MAX_PAIRS 3 /* n > 0: whole forwards (d3r_model_forward / _mixed / _packed) of at most n pairs are replayed as a hipGraph
                                          * from the third call with the same (B, image sizes, output layout) on: ~700 launches become one
                                          * graph launch + input / output copies through engine-owned staging buffers (bit-identical results).
-                                         * The D3R_* environment probes that change the launch plan (D3R_GEMM_*, D3R_HEAD_FUSE, D3R_ATTN_*) are read when a graph is CAPTURED: set them before
+                                         * The D3R_* environment probes that change the launch plan (D3R_GEMM_*, D3R_HEAD_FUSE, D3R_HEAD_UPFUSE, D3R_ATTN_*) are read when a graph is CAPTURED: set them before
                                          * the first captured call (a captured graph replays the plan it was captured with).
                                          * DEFAULT 0 = off (or D3R_GRAPH_MAX_PAIRS at create): measured on MI355X, one 512x384 pair per call
                                          * took 14.83 ms replayed vs 14.86 ms eager (before the small-problem GEMM tile: 10.4 ms now) -- the one-pair forward is bound by the dependent chain of
