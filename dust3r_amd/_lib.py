@@ -89,6 +89,10 @@ def _load():
         'd3r_rope_table': (i, [fp, i, f, f, vp]),
         'd3r_linear_heads': (i, [vp, vp, fp, i, i, i, i, ip, vp, i, i, i, i, fp, i, fp, fp, fp, fp, f, fp, C.c_size_t, vp, i, i, vp]),
         'd3r_linear_heads_tile_config': (i, [i, i, i, i, ip, i, i, i, i, i, i]),
+        'd3r_ln_finalize': (i, [fp, i, i, f, fp, fp, vp]),
+        'd3r_ln_fold_pack': (i, [fp, fp, fp, fp, vp, fp, fp, i, i, i, vp]),
+        'd3r_linear_ln': (i, [vp, vp, fp, vp, i, i, i, i, fp, fp, fp, fp, f, vp]),
+        'd3r_layernorm_x3rows': (i, [vp, fp, fp, vp, i, i, f, vp]),
         'd3r_conv2d_nhwc': (i, [vp, vp, fp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, vp, i, vp]),
         'd3r_conv_k_slice_major': (i, []),
         'd3r_pack_conv_weight': (i, [fp, vp, i, i, i, i, i, i, i, vp]),

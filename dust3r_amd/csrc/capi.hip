@@ -82,6 +82,38 @@ extern "C" int d3r_linear_heads_tile_config(int M, int K, int n_regions, int hea
     return plan.w8 ? D3R_TILE_128W8 : plan.cfg;
 }
 
+// ---- The folded-LayerNorm chain alone, for the kernel tests: the launches the engine makes between a typed-residual GEMM (d3r_linear_x3res,
+// the producer of the partial sums) and the GEMM that consumes the statistics. d3r_linear_heads above is the consumer with the head-scatter epilogue.
+extern "C" int d3r_ln_finalize(const float* part, int rows, int C, float eps, float* rstd, float* nmr, void* stream) {
+    if (!part || !rstd || !nmr || rows <= 0 || C <= 0 || C % 32 != 0 || C > 2048) return D3R_ERR_INVALID;
+    return rc_of(launch_ln_finalize(part, rows, C, eps, rstd, nmr, (hipStream_t)stream));
+}
+
+// What finalize_fold (engine.hip) runs for one matrix, through the same function: split-fp16 is the only layout a fold engine packs.
+extern "C" int d3r_ln_fold_pack(const float* W, const float* gamma, const float* beta, const float* bias_in, void* dst_rows, float* colsum, float* bias_out, int N,
+                                int K, int dtype, void* stream) {
+    if (!W || !gamma || !beta || !dst_rows || !colsum || !bias_out || N <= 0 || K <= 0 || K % 8 != 0 || dtype != D3R_F16X3) return D3R_ERR_INVALID;
+    return rc_of(launch_ln_fold_pack(dtype, W, gamma, beta, bias_in, dst_rows, colsum, bias_out, N, K, (hipStream_t)stream));
+}
+
+// d3r_linear (split-fp16, typed store or GELU) as the consumer of a folded LayerNorm: the ln_* fields exactly as d3r_linear_heads fills them.
+extern "C" int d3r_linear_ln(const void* act_rows, const void* wgt, const float* bias_fold, void* out, int M, int N, int K, int epilogue, float* ln_rstd,
+                             float* ln_nmr, const float* ln_colsum, const float* ln_part_in, float ln_eps, void* stream) {
+    if (!act_rows || !wgt || !out || !ln_rstd || !ln_nmr || !ln_colsum || M <= 0 || N <= 0 || N % 8 != 0 || K <= 0 || (epilogue != 0 && epilogue != 2)) return D3R_ERR_INVALID;
+    if (ln_part_in && (K % 32 != 0 || K > 2048)) return D3R_ERR_INVALID;
+    GemmParams p = linear_gemm_params(act_rows, K, wgt, bias_fold, M, N, K);
+    p.epi = epilogue == 2 ? EPI_GELU : EPI_T;
+    p.out = out; p.ldo = N;
+    p.ln_rstd = ln_rstd; p.ln_nmr = ln_nmr; p.ln_colsum = ln_colsum; p.ln_part_in = ln_part_in; p.ln_eps = ln_eps; p.ln_inv_c = 1.0f / (float)K;
+    return rc_of(launch_gemm(D3R_F16X3, p, (hipStream_t)stream));
+}
+
+// enc_norm / dec_norm of a folded-LayerNorm engine: LayerNorm from split-fp16 rows into split-fp16 rows
+extern "C" int d3r_layernorm_x3rows(const void* rows, const float* gamma, const float* beta, void* out_rows, int M, int C, float eps, void* stream) {
+    if (!rows || !gamma || !beta || !out_rows || M <= 0 || C <= 0 || C % 8 != 0 || C > 2048) return D3R_ERR_INVALID;
+    return rc_of(launch_layernorm_x3in(rows, gamma, beta, out_rows, M, C, eps, (hipStream_t)stream));
+}
+
 extern "C" int d3r_conv_k_slice_major(void) { return 1; }
 
 extern "C" int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bias, void* out, const void* res1, const void* res2, void* out_relu_copy,

@@ -1096,16 +1096,22 @@ int forward(d3r_model* m, const Call& k, hipStream_t st) {
 // bias or its LayerNorm's vectors were loaded, and it needs ALL of its weight tensors staged for that (projk | projv: both). A vector-only update of a
 // matrix whose staging copy is gone cannot be folded: D3R_ERR_STATE until that matrix's weights are loaded again (include/dust3r_hip.h, d3r_model_load_tensor);
 // the other matrices are unaffected.
+// The two launches of one matrix (kernels.hpp launch_ln_fold_pack): here so that the kernel tests (capi.hip d3r_ln_fold_pack) run what finalize_fold runs.
+hipError_t d3r::launch_ln_fold_pack(int dt, const float* W, const float* gamma, const float* beta, const float* bias_in, void* dst, float* colsum, float* bias_out, int N, int K,
+                                    hipStream_t s) {
+    PackParams pp;
+    pp.src = W; pp.numel = (size_t)N * K; pp.dst = dst; pp.dst_cols = K; pp.kind = PACK_MAT; pp.cols = K; pp.row_off = 0;
+    pp.kscale = gamma;
+    const hipError_t e = launch_pack_weight(dt, pp, s);
+    return e != hipSuccess ? e : launch_ln_fold_vectors(dt, W, gamma, beta, bias_in, colsum, bias_out, N, K, s);
+}
+
 static int finalize_fold(d3r_model* m) {
     if (!m->ln_fold || !m->fold_dirty) return D3R_OK;
     for (Lin* L : m->fold_lins) if (L->fold_dirty && (!L->w32 || L->have_mask != L->want_mask)) return D3R_ERR_STATE;
     for (Lin* L : m->fold_lins) {
         if (!L->fold_dirty) continue;
-        PackParams pp;
-        pp.src = L->w32; pp.numel = (size_t)L->N * L->K; pp.dst = L->w; pp.dst_cols = L->K; pp.kind = PACK_MAT; pp.cols = L->K; pp.row_off = 0;
-        pp.kscale = L->ln->g;
-        if (launch_pack_weight(L->dt, pp, nullptr) != hipSuccess) return D3R_ERR_LAUNCH;
-        if (launch_ln_fold_vectors(L->dt, L->w32, L->ln->g, L->ln->b, L->b, L->ln_s, L->b_fold, L->N, L->K, nullptr) != hipSuccess) return D3R_ERR_LAUNCH;
+        if (launch_ln_fold_pack(L->dt, L->w32, L->ln->g, L->ln->b, L->b, L->w, L->ln_s, L->b_fold, L->N, L->K, nullptr) != hipSuccess) return D3R_ERR_LAUNCH;
     }
     if (hipDeviceSynchronize() != hipSuccess) return D3R_ERR_LAUNCH;
     for (Lin* L : m->fold_lins) {

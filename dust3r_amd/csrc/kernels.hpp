@@ -183,6 +183,11 @@ struct PackParams {
     const float* kscale = nullptr;   // PACK_MAT: multiply column k of the source by kscale[k] before the conversion (LayerNorm gamma folded into the weights)
 };
 hipError_t launch_pack_weight(int dt, const PackParams& p, hipStream_t s);
+// The load-time fold of ONE nn.Linear behind a LayerNorm, built in one place (engine.hip) for the engine (finalize_fold) and for the kernel-level C ABI
+// (capi.hip d3r_ln_fold_pack): W [N][K] fp32 packed as W diag(gamma) into the rows of `dst` (PACK_MAT with kscale = gamma; K columns per row, padding rows
+// zeroed by the caller), then launch_ln_fold_vectors.
+hipError_t launch_ln_fold_pack(int dt, const float* W, const float* gamma, const float* beta, const float* bias_in, void* dst, float* colsum, float* bias_out, int N, int K,
+                               hipStream_t s);
 hipError_t launch_pack_convt_bias(const float* src, float* dst, int cout, int cout_pad, int taps, hipStream_t s);
 
 // ------------------------------------------------------------------------------ aligner

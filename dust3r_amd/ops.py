@@ -111,6 +111,65 @@ def linear_x3(act, weight, bias=None, epilogue='store', residual=None):
     return out if epi == 1 else unpack_x3(out)
 
 
+def ln_finalize(part, C, eps=1e-6, rstd=None, nmr=None):
+    """d3r_ln_finalize: part (rows, C // 32, 2) fp32, the (sum, sum of squares) pairs of linear_x3res -> (rstd, nmr) fp32. rstd / nmr: the CALLER's arrays of at
+    least `rows` elements (what the launch leaves untouched stays visible); None: allocated here."""
+    _lib.require_device()
+    rows = part.shape[0]
+    assert part.dtype == torch.float32 and part.shape == (rows, C // 32, 2)
+    rstd = torch.empty(rows, dtype=torch.float32, device=part.device) if rstd is None else rstd
+    nmr = torch.empty(rows, dtype=torch.float32, device=part.device) if nmr is None else nmr
+    assert rstd.numel() >= rows and nmr.numel() >= rows and rstd.dtype == nmr.dtype == torch.float32
+    check(lib.d3r_ln_finalize(ptr(part), rows, C, float(eps), ptr(rstd), ptr(nmr), current_stream()), 'ln_finalize')
+    return rstd, nmr
+
+
+def ln_fold_pack(W, gamma, beta, bias=None, dtype='fp16x3'):
+    """d3r_ln_fold_pack, the load-time fold of nn.Linear(W (N, K), bias) behind LayerNorm(gamma, beta): returns (rows, colsum, bias_fold) as the consumer launches
+    take them -- rows fp16 (round_up(N, 256), 2 K) zeroed HERE before the launch (rows >= N must come back zero), colsum / bias_fold fp32 of round_up(N, 256)
+    elements pre-filled with zero (elements >= N likewise)."""
+    _lib.require_device()
+    N, K = W.shape
+    n_rows = (N + 255) // 256 * 256
+    rows = torch.zeros((n_rows, 2 * K), dtype=torch.float16, device=W.device)
+    colsum = torch.zeros(n_rows, dtype=torch.float32, device=W.device)
+    bias_fold = torch.zeros(n_rows, dtype=torch.float32, device=W.device)
+    W, gamma, beta = W.float().contiguous(), gamma.float().contiguous(), beta.float().contiguous()
+    bias = None if bias is None else bias.float().contiguous()
+    check(lib.d3r_ln_fold_pack(ptr(W), ptr(gamma), ptr(beta), ptr(bias), ptr(rows), ptr(colsum), ptr(bias_fold), N, K, _lib.DTYPES[dtype], current_stream()),
+          'ln_fold_pack')
+    return rows, colsum, bias_fold
+
+
+def linear_ln(act_rows, wgt_rows, bias_fold, N, epilogue, rstd, nmr, colsum, part_in=None, eps=1e-6, out=None):
+    """d3r_linear_ln, the plain consumer of a folded LayerNorm: act_rows fp16 (M, 2 K) split-fp16 rows, wgt_rows / bias_fold / colsum as ln_fold_pack returns
+    them (round_up(N, 256) rows), epilogue 'store' | 'gelu'. rstd / nmr fp32 (M,) are read, or -- part_in (M, K // 32, 2) given -- WRITTEN by the launch.
+    out: the caller's fp16 destination of at least M * 2 N elements (nothing here fills it); None: allocated here. Returns the stored rows, fp16 (M, 2 N)."""
+    _lib.require_device()
+    M, K = act_rows.shape[0], act_rows.shape[1] // 2
+    assert act_rows.dtype == wgt_rows.dtype == torch.float16 and wgt_rows.shape == ((N + 255) // 256 * 256, 2 * K)
+    assert colsum.numel() >= wgt_rows.shape[0] and (bias_fold is None or bias_fold.numel() >= wgt_rows.shape[0])
+    assert rstd.numel() >= M and nmr.numel() >= M and rstd.dtype == nmr.dtype == colsum.dtype == torch.float32
+    assert part_in is None or (part_in.dtype == torch.float32 and part_in.shape == (M, K // 32, 2))
+    out = torch.empty(M * 2 * N, dtype=torch.float16, device=act_rows.device) if out is None else out
+    assert out.dtype == torch.float16 and out.numel() >= M * 2 * N
+    check(lib.d3r_linear_ln(ptr(act_rows), ptr(wgt_rows), ptr(bias_fold), ptr(out), M, N, K, {'store': 0, 'gelu': 2}[epilogue], ptr(rstd), ptr(nmr), ptr(colsum),
+                            ptr(part_in), float(eps), current_stream()), 'linear_ln')
+    return out[:M * 2 * N].view(M, 2 * N)
+
+
+def layernorm_x3rows(rows, gamma, beta, eps=1e-6, out=None):
+    """d3r_layernorm_x3rows: LayerNorm from split-fp16 rows fp16 (M, 2 C) into split-fp16 rows (the enc_norm / dec_norm launch of a fold engine). out: the caller's
+    fp16 destination of at least M * 2 C elements; None: allocated here. Returns the stored rows, fp16 (M, 2 C)."""
+    _lib.require_device()
+    M, C2 = rows.shape
+    assert rows.dtype == torch.float16
+    out = torch.empty(M * C2, dtype=torch.float16, device=rows.device) if out is None else out
+    assert out.dtype == torch.float16 and out.numel() >= M * C2
+    check(lib.d3r_layernorm_x3rows(ptr(rows), ptr(gamma), ptr(beta), ptr(out), M, C2 // 2, float(eps), current_stream()), 'layernorm_x3rows')
+    return out[:M * C2].view(M, C2)
+
+
 def upsample2x_x3(x, out_hw=None, rows=False):
     """`upsample2x_nhwc` on split-fp16 maps: x (B,H,W,C) fp32, C % 8 == 0, packed along the channel axis; fp32 result, or -- rows=True -- the split rows
     (B,Ho,Wo,2C) fp16 exactly as the kernel stored them (unpacking to fp32 and packing again may re-split a value into another (hi, lo) pair)."""

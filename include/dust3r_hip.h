@@ -121,6 +121,26 @@ int d3r_linear_heads(const void* act, const void* wgt, const float* bias, int M,
 #define D3R_TILE_128W8 12
 int d3r_linear_heads_tile_config(int M, int K, int n_regions, int head_c, const int* kinds, int heads, int ntok, int tok_w, int ldv, int max_pos, int dtype);
 
+/* ---- The folded-LayerNorm chain alone (croco Block / DecoderBlock: norm1 / norm2 / norm3 / norm_y in front of an nn.Linear), exported so that
+ * the kernel tests can pin each launch against fp64 (the engine makes the same launches from C++). The producer is d3r_linear_x3res above; d3r_linear_heads
+ * is the consumer with the head-scatter epilogue. */
+/* part [rows][C / 32][2] = (sum, sum of squares) pairs of d3r_linear_x3res -> rstd[m] = 1 / sqrt(max(E[x^2] - mean^2, 0) + eps), nmr[m] = fp32(-mean) * rstd[m]
+ * (fp64 sums in a fixed order). C % 32 == 0, C <= 2048. Nothing past rows is written. */
+int d3r_ln_finalize(const float* part, int rows, int C, float eps, float* rstd, float* nmr, void* stream);
+/* The load-time fold of one nn.Linear W [N][K] fp32 (bias_in [N] or NULL) behind LayerNorm(gamma, beta): dst_rows = split-fp16 rows of W diag(gamma) -- the
+ * caller zeroes dst_rows, round_up(N, 256) rows of K; rows >= N are not written --, colsum[n] = sum_k of the ROUNDED row n, bias_out[n] = bias_in[n] + sum_k
+ * beta_k W_nk (fp64 sums, one rounding). K % 8 == 0; dtype must be D3R_DTYPE_F16X3 (the only layout a fold engine packs): anything else is D3R_ERR_INVALID. */
+int d3r_ln_fold_pack(const float* W, const float* gamma, const float* beta, const float* bias_in, void* dst_rows, float* colsum, float* bias_out, int N, int K,
+                     int dtype, void* stream);
+/* d3r_linear in split-fp16 as the CONSUMER of a folded LayerNorm: out [M][N] split-fp16 rows = epilogue(rstd_m (act_rows . wgt^T - mean_m colsum_n) + bias_fold_n),
+ * epilogue 0 store | 2 GELU(erf); wgt = d3r_ln_fold_pack's rows, bias_fold (NULL: none) and ln_colsum hold round_up(N, 256) floats. ln_rstd / ln_nmr [M] are
+ * read -- or, with ln_part_in != NULL ([M][K / 32][2], K % 32 == 0, K <= 2048), formed by the launch with d3r_ln_finalize's arithmetic (eps = ln_eps, 1 / K as the
+ * mean's factor) and WRITTEN. N % 8 == 0. D3R_ERR_INVALID: a NULL operand or statistic, another epilogue, these shape rules. */
+int d3r_linear_ln(const void* act_rows, const void* wgt, const float* bias_fold, void* out, int M, int N, int K, int epilogue, float* ln_rstd, float* ln_nmr,
+                  const float* ln_colsum, const float* ln_part_in, float ln_eps, void* stream);
+/* LayerNorm(eps) from split-fp16 rows [M][C] into split-fp16 rows (enc_norm / dec_norm of a fold engine: the residual stream is typed). C % 8 == 0, C <= 2048. */
+int d3r_layernorm_x3rows(const void* rows, const float* gamma, const float* beta, void* out_rows, int M, int C, float eps, void* stream);
+
 /* 2-D convolution, NHWC, as implicit GEMM: in [B][Hin][Win][Cin] dtype, wgt [round_up(Cout,256)][k*k*Cin] dtype;
  * out [B][Hout][Wout][Cout] dtype = [relu](conv + bias + res1 + res2)   (DPT head convs, dust3r/heads/dpt_head.py:34-65).
  * K order of a weight row: with S = 128 / sizeof(dtype) channels per K step (Cin % S == 0),
