@@ -362,19 +362,19 @@ D3R_DEV void modular_image_step(const SmallView& s, int i, float (&Q)[7], float 
         const double gy = -(10.0 / Fy) * ((double)R[1] * RI[12] + (double)R[4] * RI[13] + (double)R[7] * RI[14]);
         if (s.g_pp) { s.g_pp[i * 2] = (float)gx; s.g_pp[i * 2 + 1] = (float)gy; }
         if (s.update && tpp) {
-            pp0 = adam_update(pp0, (float)gx, s.pp_m[i * 2], s.pp_v[i * 2], s.adam);
-            pp1 = adam_update(pp1, (float)gy, s.pp_m[i * 2 + 1], s.pp_v[i * 2 + 1], s.adam);
+            pp0 = adam_update_unfused(pp0, (float)gx, s.pp_m[i * 2], s.pp_v[i * 2], s.adam);
+            pp1 = adam_update_unfused(pp1, (float)gy, s.pp_m[i * 2 + 1], s.pp_v[i * 2 + 1], s.adam);
             s.im_pp[i * 2] = pp0; s.im_pp[i * 2 + 1] = pp1;
         }
     }
     if (s.update && tp)
         for (int k = 0; k < 7; ++k) {
-            Q[k] = adam_update(Q[k], (float)gQ[k], s.imp_m[i * 7 + k], s.imp_v[i * 7 + k], s.adam);
+            Q[k] = adam_update_unfused(Q[k], (float)gQ[k], s.imp_m[i * 7 + k], s.imp_v[i * 7 + k], s.adam);
             s.im_poses[i * 7 + k] = Q[k];
         }
     if (s.update && tf) {
         for (int k = 0; k < s.nfoc; ++k) {
-            fo[k] = adam_update(fo[k], (float)gf[k], s.foc_m[i * s.nfoc + k], s.foc_v[i * s.nfoc + k], s.adam);
+            fo[k] = adam_update_unfused(fo[k], (float)gf[k], s.foc_m[i * s.nfoc + k], s.foc_v[i * s.nfoc + k], s.adam);
             s.im_focals[i * s.nfoc + k] = fo[k];
         }
         if (s.nfoc == 1) fo[1] = fo[0];
@@ -387,8 +387,8 @@ D3R_DEV void modular_image_derived(const SmallView& s, int i, const float (&Q)[7
     quat_to_rotmat(Q, D);
     D[9] = signed_expm1f(Q[4]); D[10] = signed_expm1f(Q[5]); D[11] = signed_expm1f(Q[6]);
     D[12] = expf(fo[0] / s.focal_break);
-    D[13] = 0.5f * (float)s.img_w[i] + 10.f * pp0;
-    D[14] = 0.5f * (float)s.img_h[i] + 10.f * pp1;
+    D[13] = principal_point_px(s.img_w[i], pp0);
+    D[14] = principal_point_px(s.img_h[i], pp1);
     D[15] = expf(fo[1] / s.focal_break);
     float4* dst = reinterpret_cast<float4*>(s.d_img + i * 16);
     for (int k = 0; k < 4; ++k) dst[k] = make_float4(D[4 * k], D[4 * k + 1], D[4 * k + 2], D[4 * k + 3]);
@@ -482,12 +482,12 @@ __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
                 const double g0 = gA[0] + gA[1], g1 = gA[2];
                 if (s.g_pa) { s.g_pa[e * 2] = (float)g0; s.g_pa[e * 2 + 1] = (float)g1; }
                 if (s.update && s.opt_adapt) {
-                    s.pw_adaptors[e * 2] = adam_update(a0, (float)g0, s.pa_m[e * 2], s.pa_v[e * 2], s.adam);
-                    s.pw_adaptors[e * 2 + 1] = adam_update(a1, (float)g1, s.pa_m[e * 2 + 1], s.pa_v[e * 2 + 1], s.adam);
+                    s.pw_adaptors[e * 2] = adam_update_unfused(a0, (float)g0, s.pa_m[e * 2], s.pa_v[e * 2], s.adam);
+                    s.pw_adaptors[e * 2 + 1] = adam_update_unfused(a1, (float)g1, s.pa_m[e * 2 + 1], s.pa_v[e * 2 + 1], s.adam);
                 }
             }
             if (s.update)
-                for (int k = 0; k < 8; ++k) P[k] = adam_update(P[k], (float)gP[k], s.pw_m[e * 8 + k], s.pw_v[e * 8 + k], s.adam);
+                for (int k = 0; k < 8; ++k) P[k] = adam_update_unfused(P[k], (float)gP[k], s.pw_m[e * 8 + k], s.pw_v[e * 8 + k], s.adam);
         }
         // image poses / focals
         for (int i = tid; i < s.n; i += 256) {
@@ -510,9 +510,9 @@ __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
                 for (int k = 0; k < 7; ++k) s.g_imp[i * 7 + k] = (float)gP[k];
             if (s.g_foc) s.g_foc[i] = (float)gf;
             if (s.update && s.opt_poses)
-                for (int k = 0; k < 7; ++k) P[k] = adam_update(P[k], (float)gP[k], s.imp_m[i * 7 + k], s.imp_v[i * 7 + k], s.adam);
+                for (int k = 0; k < 7; ++k) P[k] = adam_update_unfused(P[k], (float)gP[k], s.imp_m[i * 7 + k], s.imp_v[i * 7 + k], s.adam);
             const float focal_param_old = s.im_focals[i];
-            if (s.update && s.opt_focals) s.im_focals[i] = adam_update(s.im_focals[i], (float)gf, s.foc_m[i], s.foc_v[i], s.adam);
+            if (s.update && s.opt_focals) s.im_focals[i] = adam_update_unfused(s.im_focals[i], (float)gf, s.foc_m[i], s.foc_v[i], s.adam);
             if (s.g_pp || (s.update && s.opt_pp)) {
                 // principal point (optimizer.py:141-142: pp = (W/2, H/2) + 10 im_pp): dX/dppx = -exp(d)/F R[:,0], so
                 // dL/d im_pp = -(10 / F) (R^T S)_{0,1} with S = sum_p g_p exp(d_p), the record's last three sums
@@ -522,8 +522,8 @@ __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
                 const double gy = -(10.0 / F) * ((double)R[1] * S0 + (double)R[4] * S1 + (double)R[7] * S2);
                 if (s.g_pp) { s.g_pp[i * 2] = (float)gx; s.g_pp[i * 2 + 1] = (float)gy; }
                 if (s.update && s.opt_pp) {
-                    s.im_pp[i * 2] = adam_update(s.im_pp[i * 2], (float)gx, s.pp_m[i * 2], s.pp_v[i * 2], s.adam);
-                    s.im_pp[i * 2 + 1] = adam_update(s.im_pp[i * 2 + 1], (float)gy, s.pp_m[i * 2 + 1], s.pp_v[i * 2 + 1], s.adam);
+                    s.im_pp[i * 2] = adam_update_unfused(s.im_pp[i * 2], (float)gx, s.pp_m[i * 2], s.pp_v[i * 2], s.adam);
+                    s.im_pp[i * 2 + 1] = adam_update_unfused(s.im_pp[i * 2 + 1], (float)gy, s.pp_m[i * 2 + 1], s.pp_v[i * 2 + 1], s.adam);
                 }
             }
         }
@@ -561,8 +561,8 @@ __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
         D[10] = signed_expm1f(P[5]);
         D[11] = signed_expm1f(P[6]);
         D[12] = expf(s.im_focals[i] / s.focal_break);
-        D[13] = 0.5f * (float)s.img_w[i] + 10.f * s.im_pp[i * 2];
-        D[14] = 0.5f * (float)s.img_h[i] + 10.f * s.im_pp[i * 2 + 1];
+        D[13] = principal_point_px(s.img_w[i], s.im_pp[i * 2]);
+        D[14] = principal_point_px(s.img_h[i], s.im_pp[i * 2 + 1]);
         D[15] = 0.f;
     }
 }
@@ -677,15 +677,15 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
                 const double g0 = gA[0] + gA[1], g1 = gA[2];
                 if (s.g_pa) { s.g_pa[e * 2] = (float)g0; s.g_pa[e * 2 + 1] = (float)g1; }
                 if (s.update && s.opt_adapt) {
-                    ad0 = adam_update(ad0, (float)g0, am[0], av[0], s.adam);
-                    ad1 = adam_update(ad1, (float)g1, am[1], av[1], s.adam);
+                    ad0 = adam_update_unfused(ad0, (float)g0, am[0], av[0], s.adam);
+                    ad1 = adam_update_unfused(ad1, (float)g1, am[1], av[1], s.adam);
                     *reinterpret_cast<float2*>(s.pw_adaptors + e * 2) = make_float2(ad0, ad1);
                     s.pa_m[e * 2] = am[0]; s.pa_m[e * 2 + 1] = am[1]; s.pa_v[e * 2] = av[0]; s.pa_v[e * 2 + 1] = av[1];
                 }
             }
             if (s.update) {
 #pragma unroll
-                for (int k = 0; k < 8; ++k) P[k] = adam_update(P[k], (float)gP[k], pm[k], pv[k], s.adam);
+                for (int k = 0; k < 8; ++k) P[k] = adam_update_unfused(P[k], (float)gP[k], pm[k], pv[k], s.adam);
                 float4* d = reinterpret_cast<float4*>(s.pw_poses + e * 8);
                 d[0] = make_float4(P[0], P[1], P[2], P[3]); d[1] = make_float4(P[4], P[5], P[6], P[7]);
                 float4* dm = reinterpret_cast<float4*>(s.pw_m + e * 8);
@@ -710,8 +710,8 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
                 const double gy = -(10.0 / F) * ((double)R2[1] * RI[12] + (double)R2[4] * RI[13] + (double)R2[7] * RI[14]);
                 if (s.g_pp) { s.g_pp[i * 2] = (float)gx; s.g_pp[i * 2 + 1] = (float)gy; }
                 if (s.update && s.opt_pp) {
-                    pp0 = adam_update(pp0, (float)gx, ppm[0], ppv[0], s.adam);
-                    pp1 = adam_update(pp1, (float)gy, ppm[1], ppv[1], s.adam);
+                    pp0 = adam_update_unfused(pp0, (float)gx, ppm[0], ppv[0], s.adam);
+                    pp1 = adam_update_unfused(pp1, (float)gy, ppm[1], ppv[1], s.adam);
                     s.im_pp[i * 2] = pp0; s.im_pp[i * 2 + 1] = pp1;
                     s.pp_m[i * 2] = ppm[0]; s.pp_m[i * 2 + 1] = ppm[1]; s.pp_v[i * 2] = ppv[0]; s.pp_v[i * 2 + 1] = ppv[1];
                 }
@@ -719,12 +719,12 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
             if (s.update && s.opt_poses) {
 #pragma unroll
                 for (int k = 0; k < 7; ++k) {
-                    Q[k] = adam_update(Q[k], (float)gQ[k], qm[k], qv[k], s.adam);
+                    Q[k] = adam_update_unfused(Q[k], (float)gQ[k], qm[k], qv[k], s.adam);
                     s.im_poses[i * 7 + k] = Q[k]; s.imp_m[i * 7 + k] = qm[k]; s.imp_v[i * 7 + k] = qv[k];
                 }
             }
             if (s.update && s.opt_focals) {
-                foc = adam_update(foc, (float)gf, fm, fv, s.adam);
+                foc = adam_update_unfused(foc, (float)gf, fm, fv, s.adam);
                 s.im_focals[i] = foc; s.foc_m[i] = fm; s.foc_v[i] = fv;
             }
         }
@@ -750,8 +750,8 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
         quat_to_rotmat(Q, D);
         D[9] = signed_expm1f(Q[4]); D[10] = signed_expm1f(Q[5]); D[11] = signed_expm1f(Q[6]);
         D[12] = expf(foc / s.focal_break);
-        D[13] = 0.5f * (float)iw + 10.f * pp0;
-        D[14] = 0.5f * (float)ih + 10.f * pp1;
+        D[13] = principal_point_px(iw, pp0);
+        D[14] = principal_point_px(ih, pp1);
         D[15] = 0.f;
         float4* dst = reinterpret_cast<float4*>(s.d_img + i * 16);
 #pragma unroll

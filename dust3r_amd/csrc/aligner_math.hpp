@@ -24,8 +24,14 @@ namespace d3r {
 
 struct Quat { float x, y, z, w; };
 
-// roma.unitquat_to_rotmat on the normalised quaternion (XYZW); R row-major [9]
+// roma.unitquat_to_rotmat on the normalised quaternion (XYZW); R row-major [9].
+// Contraction is switched OFF: under -ffp-contract=fast hipcc fuses `q0*q0 + q1*q1` and `1 - 2*(yy + zz)` in one kernel and not in another, and the pose /
+// focal step has two kernels (one edge per thread, strided loop) whose derived matrices must not depend on which of them ran: a last-bit difference there is
+// enough for Adam (beta2 = 0.9) to move single log-depths by 1e-3 of a step within 10 iterations (tests/test_aligner_options_gpu.py).
 D3R_HD void quat_to_rotmat(const float q[4], float R[9]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     const float x = q[0] / n, y = q[1] / n, z = q[2] / n, w = q[3] / n;
     const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, xw = x * w, yw = y * w, zw = z * w;
@@ -97,6 +103,24 @@ D3R_HD float adam_update(float p, float g, float& m, float& v, const AdamCoef& c
     v = v * c.b2 + (1.f - c.b2) * g * g;
     const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
     return p - c.step_size * (m / denom);
+}
+// The same update with every product and sum rounded on its own (contraction OFF), for the pose / focal step: its two kernels must move a parameter to the
+// same bits (see quat_to_rotmat). The main kernel keeps adam_update for the log-depths: it is one kernel, and VALU-bound.
+D3R_HD float adam_update_unfused(float p, float g, float& m, float& v, const AdamCoef& c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    m = m + (g - m) * (1.f - c.b1);
+    v = v * c.b2 + (1.f - c.b2) * g * g;
+    const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+    return p - c.step_size * (m / denom);
+}
+// Principal point in pixels, (size / 2) + 10 im_pp (optimizer.py:141-142), rounded the same way by every kernel that forms it
+D3R_HD float principal_point_px(int size, float pp) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return 0.5f * (float)size + 10.f * pp;
 }
 
 // ---- small-parameter chain rules ----------------------------------------------------------------

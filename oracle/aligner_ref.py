@@ -15,6 +15,15 @@ reference files and by tests/golden/aligner_*.pt generated from them).
 
 The state is held as plain tensors with the reference's `state_dict(trainable=True)` key names
 (pw_poses, pw_adaptors, im_poses, im_depthmaps, im_focals, im_pp).
+
+Options restated besides the defaults, each pinned against the unmodified reference class by
+tests/golden/aligner_pco_options.pt (tools/make_pco_golden.py; tests/test_oracle_pins.py):
+  dist='l2', conf='sqrt' | 'id' | 'm1'      commons.py:62-76, base_opt.py:77
+  norm_pw_scale=False                        what preset_pose leaves (optimizer.py:80-81): no scale normalisation in get_pw_scale
+                                             (base_opt.py:178-184), no centring of the adaptors (base_opt.py:143-148)
+  load_state(frozen=('im_poses', ...))       preset_pose / preset_focal over all images (optimizer.py:80,91)
+  images of several sizes                    predictions given as per-edge lists: the ParameterStack(fill=max_area) path
+                                             (optimizer.py:37-61,214-237), see _init_per_image_shapes
 """
 import math
 import os
@@ -44,38 +53,83 @@ def linear_schedule(t, lr_start, lr_end):
 
 class AlignerRef:
     def __init__(self, dust3r_output, dist='l1', conf='log', base_scale=0.5, pw_break=20, focal_break=20,
-                 dtype=torch.float32):
+                 dtype=torch.float32, norm_pw_scale=True):
         v1, v2, p1, p2 = [dust3r_output[k] for k in ('view1', 'view2', 'pred1', 'pred2')]
         self.edges = [(int(i), int(j)) for i, j in zip(v1['idx'], v2['idx'])]
         self.n_imgs = max(max(e) for e in self.edges) + 1
         E = len(self.edges)
-        pi, pj = p1['pts3d'].cpu(), p2['pts3d_in_other_view'].cpu()
-        H, W = pi.shape[1:3]
-        self.H, self.W, self.A = H, W, H * W
         self.dtype = dtype
         self.dist = dist
         trf = dict(log=torch.log, sqrt=torch.sqrt, m1=lambda x: x - 1, id=lambda x: x, none=lambda x: x)[conf]
-        self.pred_i = pi.reshape(E, self.A, 3).to(dtype)
-        self.pred_j = pj.reshape(E, self.A, 3).to(dtype)
-        self.weight_i = trf(p1['conf'].cpu().float()).reshape(E, self.A).to(dtype)
-        self.weight_j = trf(p2['conf'].cpu().float()).reshape(E, self.A).to(dtype)
         self.ei = torch.tensor([i for i, j in self.edges])
         self.ej = torch.tensor([j for i, j in self.edges])
         self.base_scale, self.pw_break, self.focal_break = base_scale, pw_break, focal_break
-        self.norm_pw_scale = True
-        vs, us = torch.meshgrid(torch.arange(H, dtype=dtype), torch.arange(W, dtype=dtype), indexing='ij')
-        self.grid = torch.stack((us, vs), dim=-1).reshape(1, self.A, 2)      # xy_grid(W,H): [...,0]=col
-        self.pp0 = torch.tensor([W / 2, H / 2], dtype=dtype)
-        self.total_area_i = self.total_area_j = E * self.A
+        self.norm_pw_scale = bool(norm_pw_scale)           # False: what preset_pose leaves behind (optimizer.py:80-81)
+        if isinstance(p1['pts3d'], (list, tuple)):
+            self._init_per_image_shapes(p1, p2, trf)
+        else:
+            pi, pj = p1['pts3d'].cpu(), p2['pts3d_in_other_view'].cpu()
+            H, W = pi.shape[1:3]
+            self.H, self.W, self.A = H, W, H * W
+            self.imshapes = [(H, W)] * self.n_imgs
+            self.pred_i = pi.reshape(E, self.A, 3).to(dtype)
+            self.pred_j = pj.reshape(E, self.A, 3).to(dtype)
+            self.weight_i = trf(p1['conf'].cpu().float()).reshape(E, self.A).to(dtype)
+            self.weight_j = trf(p2['conf'].cpu().float()).reshape(E, self.A).to(dtype)
+            vs, us = torch.meshgrid(torch.arange(H, dtype=dtype), torch.arange(W, dtype=dtype), indexing='ij')
+            self.grid = torch.stack((us, vs), dim=-1).reshape(1, self.A, 2)      # xy_grid(W,H): [...,0]=col
+            self.pp0 = torch.tensor([W / 2, H / 2], dtype=dtype)
+            self.total_area_i = self.total_area_j = E * self.A
         self.params = None
 
+    def _init_per_image_shapes(self, p1, p2, trf):
+        """Images of several sizes: the predictions are per-edge lists of (H_i, W_i, ...) tensors. Restates the reference's
+        ParameterStack(fill=max_area) path (optimizer.py:37-61, 214-237): every per-pixel stack is ravelled and zero-padded to the
+        largest area -- predictions, weights (so the padding carries zero weight) and the pixel grid (so the padding sits at pixel
+        (0, 0)) --, the image centre pp0 is per image, and each side's sum is divided by the sum of that side's image areas."""
+        dtype, E = self.dtype, len(self.edges)
+        shapes = [None] * self.n_imgs
+        for e, (i, j) in enumerate(self.edges):                                 # commons.py get_imshapes
+            for img, t in ((i, p1['pts3d'][e]), (j, p2['pts3d_in_other_view'][e])):
+                hw = tuple(int(x) for x in t.shape[:2])
+                assert shapes[img] in (None, hw), f'incompatible shapes for image {img}'
+                shapes[img] = hw
+        self.imshapes = shapes
+        areas = [h * w for h, w in shapes]
+        self.A = max(areas)
+        self.H = self.W = None
+
+        def stack(seq, tail, f=lambda x: x):
+            out = torch.zeros((len(seq), self.A) + tail, dtype=dtype)
+            for k, t in enumerate(seq):
+                t = f(t.cpu().float())
+                out[k, :t.shape[0] * t.shape[1]] = t.reshape((-1,) + tail).to(dtype)
+            return out
+        self.pred_i, self.pred_j = stack(p1['pts3d'], (3,)), stack(p2['pts3d_in_other_view'], (3,))
+        self.weight_i, self.weight_j = stack(p1['conf'], (), trf), stack(p2['conf'], (), trf)
+        grids = []
+        for H, W in shapes:
+            vs, us = torch.meshgrid(torch.arange(H, dtype=dtype), torch.arange(W, dtype=dtype), indexing='ij')
+            grids.append(torch.stack((us, vs), dim=-1))
+        self.grid = stack(grids, (2,))                                           # (n, A, 2)
+        self.pp0 = torch.tensor([(W / 2, H / 2) for H, W in shapes], dtype=dtype)  # (n, 2)
+        self.total_area_i = sum(areas[i] for i, j in self.edges)
+        self.total_area_j = sum(areas[j] for i, j in self.edges)
+
     # ------------------------------------------------------------------ state
-    def load_state(self, state, optimize_pp=False, allow_pw_adaptors=False):
+    def load_state(self, state, optimize_pp=False, allow_pw_adaptors=False, frozen=()):
+        """`frozen`: parameter groups taken out of the optimisation besides the two switches -- 'im_poses' is what preset_pose over
+        all images leaves (optimizer.py:80; pass norm_pw_scale=False to the constructor with it, :81), 'im_focals' what
+        preset_focal does (:91). The values themselves come with `state`."""
         # optimizer.py:34: im_pp.requires_grad_(optimize_pp); base_opt.py:92: pw_adaptors.requires_grad_(allow_pw_adaptors)
-        frozen = tuple(k for k, on in (('pw_adaptors', allow_pw_adaptors), ('im_pp', optimize_pp)) if not on)
-        self.params = {k: state[k].detach().clone().to(self.dtype).requires_grad_(k not in frozen)
+        frozen = tuple(frozen) + tuple(k for k, on in (('pw_adaptors', allow_pw_adaptors), ('im_pp', optimize_pp)) if not on)
+        self.params = {k: state[k].detach().clone().to(self.dtype).reshape(self._shape_of(k)).requires_grad_(k not in frozen)
                        for k in ('pw_poses', 'pw_adaptors', 'im_poses', 'im_depthmaps', 'im_focals', 'im_pp')}
         return self
+
+    def _shape_of(self, k):
+        E, n = len(self.edges), self.n_imgs
+        return dict(pw_poses=(E, 8), pw_adaptors=(E, 2), im_poses=(n, 7), im_depthmaps=(n, self.A), im_focals=(n, 1), im_pp=(n, 2))[k]
 
     def state(self):
         return {k: v.detach().clone() for k, v in self.params.items()}
@@ -110,7 +164,8 @@ class AlignerRef:
         cam = torch.cat((depth * (self.grid - pp) / f, depth), dim=-1)       # (n,A,3)
         return cam @ Ri.transpose(1, 2) + Ti[:, None, :]
 
-    def loss(self):
+    def _distances(self):
+        """Per edge and pixel, the distance between the image's point and the aligned pairwise point, both sides: 2 x (E, A)."""
         p = self.params
         Re, Te = self._poses(p['pw_poses'])
         sc = self.pw_scale().view(-1, 1, 1)
@@ -129,7 +184,20 @@ class AlignerRef:
         else:
             di = (X[self.ei] - ai).square().sum(dim=-1)
             dj = (X[self.ej] - aj).square().sum(dim=-1)
+        return di, dj
+
+    def loss(self):
+        di, dj = self._distances()
         return (di * self.weight_i).sum() / self.total_area_i + (dj * self.weight_j).sum() / self.total_area_j
+
+    def edge_mean_loss(self):
+        """The same distances under BasePCOptimizer.forward's weighting (base_opt.py:246-273, the Modular scene's loss): per edge the MEAN
+        over each side's image, averaged over the edges. Equal to loss() when all images have one area; with several areas it is the
+        other weighting a PointCloudOptimizer result must be told apart from."""
+        di, dj = self._distances()
+        areas = torch.tensor([h * w for h, w in self.imshapes], dtype=self.dtype)
+        per_edge = (di * self.weight_i).sum(dim=1) / areas[self.ei] + (dj * self.weight_j).sum(dim=1) / areas[self.ej]
+        return per_edge.sum() / len(self.edges)
 
     # ------------------------------------------------------------------ loop
     def run(self, niter=300, lr=0.01, schedule='cosine', lr_min=1e-6, callback=None, total=None, start=0):

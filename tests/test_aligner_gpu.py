@@ -300,6 +300,17 @@ def test_preset_pose_and_focal_freeze_parameters(gpu):
     scene.preset_focal([gt['focal']] * 4)
     scene.preset_pose([gt['cam2world'][i] for i in range(4)])
     f0, p0 = scene.im_focals.data.clone(), scene.im_poses.data.clone()
+    # the loss and gradients of the preset scene (norm_pw_scale False, optimizer.py:80-81) against fp64 autograd at the same state
+    from oracle.aligner_ref import AlignerRef
+    assert scene.norm_pw_scale is False
+    state = {k: getattr(scene, k).detach().cpu().clone() for k in ('pw_poses', 'pw_adaptors', 'im_poses', 'im_depthmaps', 'im_focals', 'im_pp')}
+    loss_ref, g_ref = AlignerRef(out, dtype=torch.float64, norm_pw_scale=False).load_state(state).grads()
+    loss, g = scene.loss_and_grads()
+    assert abs(float(loss) / loss_ref - 1) < 1e-5
+    for k in ('pw_poses', 'im_poses', 'im_depthmaps', 'im_focals'):
+        err = rel(g[k].reshape(g_ref[k].shape), g_ref[k])
+        print(k, err)
+        assert err < 5e-5, (k, err)
     scene.compute_global_alignment(init=None, niter=10, schedule='cosine', lr=0.01)
     assert torch.equal(scene.im_focals.data, f0) and torch.equal(scene.im_poses.data, p0)
 

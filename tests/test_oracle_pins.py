@@ -91,6 +91,68 @@ def test_aligner_oracle_against_reference_golden():
     assert float((al.focals().detach().flatten() / g['focals'].flatten() - 1).abs().max()) < 5e-3
 
 
+def pco_case_oracle(case, dtype=torch.float32, **override):
+    """AlignerRef in the setting of one case of tests/golden/aligner_pco_options.pt, at the case's state. `override`: constructor
+    keywords that replace the case's (the GPU tests evaluate the same state under the defaults to show that an option acts)."""
+    from dust3r_amd.synthetic import synthetic_mixed_scene
+    out = synthetic_mixed_scene(**case['scene_args']) if case['scene'] == 'synthetic_mixed_scene' else synthetic_scene(**case['scene_args'])[0]
+    kw = {k: v for k, v in case['kw'].items() if k in ('dist', 'conf')} | dict(norm_pw_scale=case['norm_pw_scale']) | override
+    frozen = tuple(k for k in ('im_poses', 'im_focals') if k not in case['trainable'])
+    al = AlignerRef(out, dtype=dtype, **kw)
+    return al.load_state(case['state'], frozen=frozen, optimize_pp='im_pp' in case['trainable'], allow_pw_adaptors='pw_adaptors' in case['trainable']), out
+
+
+def test_aligner_oracle_options_against_reference_golden():
+    """AlignerRef in fp32 against the unmodified reference PointCloudOptimizer in every setting recorded by tools/make_pco_golden.py
+    (dist='l2', conf='sqrt' | 'id' | 'm1', every pose / focal preset, images of two areas, 138 edge sides on one image), at the bars of
+    test_aligner_oracle_against_reference_golden: loss, the gradient of every trainable group (and no other), the first 10 losses."""
+    g = _g('aligner_pco_options.pt')
+    assert [c['name'] for c in g['cases']] == ['l2', 'conf_sqrt', 'conf_id', 'conf_m1', 'preset_all', 'preset_pose_only', 'preset_all_adaptors',
+                                               'mixed_sizes', 'mixed_sizes_l2', 'oneref_70']
+    for case in g['cases']:
+        al, _ = pco_case_oracle(case)
+        loss0, grads = al.grads()
+        assert abs(loss0 - case['loss']) < 1e-6 * abs(case['loss']) + 1e-7, (case['name'], loss0, case['loss'])
+        assert sorted(grads) == sorted(case['grads']) == sorted(case['trainable'])
+        worst = 0.0
+        for k, ref in case['grads'].items():
+            err = float((grads[k] - ref).abs().max() / ref.abs().max())
+            worst = max(worst, err)
+            assert err < 2e-4, (case['name'], k, err)
+        losses = al.run(niter=case['niter'])
+        lerr = float((torch.tensor(losses[:10]) / case['losses'][:10] - 1).abs().max())
+        print(f'{case["name"]:18s} loss {abs(loss0 / case["loss"] - 1):.1e}  gradients {worst:.1e}  first 10 losses {lerr:.1e}')
+        assert lerr < 1e-4, (case['name'], lerr)
+        st = al.state()
+        for k in ('im_poses', 'im_focals', 'im_pp', 'pw_adaptors'):
+            if k not in case['trainable']:
+                assert torch.equal(st[k], case['state'][k]), (case['name'], k)          # frozen groups did not move
+    presets = {c['name']: c for c in g['cases'] if c['preset']}
+    assert presets['preset_all']['trainable'] == ['pw_poses', 'im_depthmaps'] and not presets['preset_all']['norm_pw_scale']
+    assert presets['preset_pose_only']['trainable'] == ['pw_poses', 'im_depthmaps', 'im_focals'] and not presets['preset_pose_only']['norm_pw_scale']
+    assert presets['preset_all_adaptors']['trainable'] == ['pw_poses', 'pw_adaptors', 'im_depthmaps'] and not presets['preset_all_adaptors']['norm_pw_scale']
+    assert float(presets['preset_all_adaptors']['state']['pw_adaptors'].abs().min()) > 0
+
+
+def test_aligner_oracle_edge_mean_weighting_against_reference_golden():
+    """AlignerRef.edge_mean_loss() -- the weighting the mixed-size PointCloudOptimizer tests must tell their result apart from -- against the
+    unmodified reference ModularPointCloudOptimizer on images of two areas (aligner_modular_grads.pt, 'mixed_sizes'), and the distance of
+    the two weightings at that state."""
+    from dust3r_amd.synthetic import synthetic_mixed_scene
+    case = next(c for c in _g('aligner_modular_grads.pt')['cases'] if c['name'] == 'mixed_sizes')
+    al = AlignerRef(synthetic_mixed_scene(**case['scene_args']))
+    n, st = al.n_imgs, case['state']
+    depth = torch.zeros((n, al.A))
+    for i, (h, w) in enumerate(al.imshapes):
+        depth[i, :h * w] = st[f'im_depthmaps.{i}'].flatten()
+    al.load_state(dict(pw_poses=st['pw_poses'], pw_adaptors=st['pw_adaptors'], im_depthmaps=depth,
+                       **{k: torch.stack([st[f'{k}.{i}'] for i in range(n)]) for k in ('im_poses', 'im_focals', 'im_pp')}))
+    with torch.no_grad():
+        mean, area = float(al.edge_mean_loss()), float(al.loss())
+    assert abs(mean - case['loss']) < 1e-6 * abs(case['loss']) + 1e-7, (mean, case['loss'])
+    assert abs(area / mean - 1) > 1e-2
+
+
 def test_forward_oracle_equals_live_reference():
     """The oracle against the unmodified reference model on the same weights and views (tests/golden/reference_pins.pt `forward`): the same module tree
     (state-dict keys) and the same outputs. The ops and their order are the reference's, but a stored vector only matches bit for bit at the thread count
