@@ -12,9 +12,13 @@
 //                            (32 B per edge-pixel, the algorithmic minimum of SURVEY.md 8(d))
 //                            and the depth gradient needs no atomics.
 //   2. aligner_reduce_kernel fixed-order fp64 reduction of the partials (deterministic).
-//   3. aligner_small_kernel  chain rule to (quaternion, log-translation, log-scale, log-focal),
-//                            Adam on those few thousand parameters, loss bookkeeping, and the
-//                            derived matrices (M_e, R_i, T_i, F_i) for the next iteration.
+//   3. the pose / focal step chain rule to (quaternion, log-translation, log-scale, log-focal, principal point,
+//                            adaptors), Adam on those few thousand parameters, loss bookkeeping, and the derived
+//                            matrices (M_e, R_i, T_i, F_i) for the next iteration. One workgroup, two kernels:
+//                            aligner_small1_kernel (one edge and one image per thread, operands in registers) up to
+//                            1024 edges / images, aligner_small_kernel (strided loops) for any size. They differ in
+//                            how items map to threads and how three sums cross the block; what is done to an edge or
+//                            an image is ONE set of functions that both kernels and both scenes call.
 #include "aligner_math.hpp"
 #include "kernels.hpp"
 
@@ -338,71 +342,188 @@ struct SmallView {
     int nfoc;
 };
 
-// ---- the Modular scene's image step (reference modular_optimizer.py) ---------------------------------------------------------------
-// Q, fo (nfoc focal parameters; fo[1] = fo[0] when nfoc == 1), pp0 / pp1: the values the main pass took its gradients at, updated in place
-// (and stored) where trainable. A frozen entry is skipped whole -- no update, its moments stay zero -- which is torch.optim.Adam without that
-// parameter (`_no_grad` takes it out of the optimiser). Gradients are exported for every image.
-D3R_DEV void modular_image_step(const SmallView& s, int i, float (&Q)[7], float (&fo)[2], float& pp0, float& pp1, const double (&RI)[15]) {
-    float R[9];
-    quat_to_rotmat(Q, R);
-    double gQ[7], gf[2];
-    image_chain(Q, R, s.focal_break, RI, RI + 9, gQ, gf[0]);
-    if (s.nfoc == 2) focal_xy_grads(R, s.focal_break, RI, gf[0], gf[1]);
-    const bool tp = s.opt_poses && (!s.tr_pose || s.tr_pose[i]);
-    const bool tf = s.opt_focals && (!s.tr_foc || s.tr_foc[i]);
-    const bool tpp = s.opt_pp && (!s.tr_pp || s.tr_pp[i]);
-    if (s.g_imp)
-        for (int k = 0; k < 7; ++k) s.g_imp[i * 7 + k] = (float)gQ[k];
-    if (s.g_foc)
-        for (int k = 0; k < s.nfoc; ++k) s.g_foc[i * s.nfoc + k] = (float)gf[k];
-    if (s.g_pp || (s.update && tpp)) {
-        // pp = (W/2, H/2) + 10 im_pp: dL/d im_pp = -(10 / Fx) (R^T S)_0, -(10 / Fy) (R^T S)_1 at the focals the gradients were taken at
-        const double Fx = exp((double)fo[0] / (double)s.focal_break), Fy = exp((double)fo[1] / (double)s.focal_break);
-        const double gx = -(10.0 / Fx) * ((double)R[0] * RI[12] + (double)R[3] * RI[13] + (double)R[6] * RI[14]);
-        const double gy = -(10.0 / Fy) * ((double)R[1] * RI[12] + (double)R[4] * RI[13] + (double)R[7] * RI[14]);
-        if (s.g_pp) { s.g_pp[i * 2] = (float)gx; s.g_pp[i * 2 + 1] = (float)gy; }
-        if (s.update && tpp) {
-            pp0 = adam_update_unfused(pp0, (float)gx, s.pp_m[i * 2], s.pp_v[i * 2], s.adam);
-            pp1 = adam_update_unfused(pp1, (float)gy, s.pp_m[i * 2 + 1], s.pp_v[i * 2 + 1], s.adam);
-            s.im_pp[i * 2] = pp0; s.im_pp[i * 2 + 1] = pp1;
+// ---- the pose / focal step: what a thread holds of one image and of one edge, and ONE body per item ---------------------------------
+// Everything done to an item is written once, here, so the fp32 the next main pass reads cannot depend on which step kernel ran. MOD = the
+// Modular scene (reference modular_optimizer.py): nfoc = 1 or 2 focal parameters per image and per-image trainability; PointCloudOptimizer's
+// step is that step with nfoc = 1 and no masks (Fy = Fx: the same bits on both axes). Every index into these arrays is a compile-time
+// constant after unrolling: a run-time index would put the struct in scratch.
+struct ImageRegs {
+    float Q[7], fo[2], pp[2];                           // fo: the x and y focal parameters (fo[1] = fo[0] when nfoc == 1)
+    float qm[7], qv[7], fm[2], fv[2], ppm[2], ppv[2];   // Adam moments of the three groups (loaded when s.update)
+    int w, h;
+};
+struct EdgeRegs {
+    float P[8], ad[2];                                  // pairwise pose, the two adaptors
+    float pm[8], pv[8], am[2], av[2];                   // their Adam moments (loaded when s.update)
+};
+
+// One parameter group of an item (rows of K floats at `off`; the first n <= K are in use): the gradient is exported, and where the group
+// is trained Adam runs on the registers and the values are stored with their moments. k < n inside the unrolled loop, not a loop to n,
+// which would index the registers at run time.
+template <int K>
+D3R_DEV void group_step(const SmallView& s, bool train, int off, int n, const double (&g)[K], float* g_out, float (&p)[K], float (&m)[K], float (&v)[K],
+                        float* p_out, float* m_out, float* v_out) {
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (k < n) {
+            if (g_out) g_out[off + k] = (float)g[k];
+            if (s.update && train) {
+                p[k] = adam_update_unfused(p[k], (float)g[k], m[k], v[k], s.adam);
+                p_out[off + k] = p[k]; m_out[off + k] = m[k]; v_out[off + k] = v[k];
+            }
         }
-    }
-    if (s.update && tp)
-        for (int k = 0; k < 7; ++k) {
-            Q[k] = adam_update_unfused(Q[k], (float)gQ[k], s.imp_m[i * 7 + k], s.imp_v[i * 7 + k], s.adam);
-            s.im_poses[i * 7 + k] = Q[k];
-        }
-    if (s.update && tf) {
-        for (int k = 0; k < s.nfoc; ++k) {
-            fo[k] = adam_update_unfused(fo[k], (float)gf[k], s.foc_m[i * s.nfoc + k], s.foc_v[i * s.nfoc + k], s.adam);
-            s.im_focals[i * s.nfoc + k] = fo[k];
-        }
-        if (s.nfoc == 1) fo[1] = fo[0];
+}
+
+template <bool MOD>
+D3R_DEV void load_image(const SmallView& s, int i, ImageRegs& r) {
+    const int nf = MOD ? s.nfoc : 1;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) r.Q[k] = s.im_poses[i * 7 + k];
+    r.fo[0] = s.im_focals[i * nf]; r.fo[1] = s.im_focals[i * nf + nf - 1];
+    r.pp[0] = s.im_pp[i * 2]; r.pp[1] = s.im_pp[i * 2 + 1];
+    r.w = s.img_w[i]; r.h = s.img_h[i];
+    if (s.update) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) { r.qm[k] = s.imp_m[i * 7 + k]; r.qv[k] = s.imp_v[i * 7 + k]; }
+        r.fm[0] = s.foc_m[i * nf]; r.fm[1] = s.foc_m[i * nf + nf - 1];
+        r.fv[0] = s.foc_v[i * nf]; r.fv[1] = s.foc_v[i * nf + nf - 1];
+        if (s.opt_pp) { r.ppm[0] = s.pp_m[i * 2]; r.ppm[1] = s.pp_m[i * 2 + 1]; r.ppv[0] = s.pp_v[i * 2]; r.ppv[1] = s.pp_v[i * 2 + 1]; }
     }
 }
 
-// derived record of image i for the next main pass: R(9) T(3) Fx ppx ppy Fy
-D3R_DEV void modular_image_derived(const SmallView& s, int i, const float (&Q)[7], const float (&fo)[2], float pp0, float pp1) {
+// Image i's step from its reduced record RI = G (9) | sum g (3) | S = sum g exp(d) (3). r holds the values the main pass took its gradients
+// at; each trainable group is updated in place and stored with its moments. A frozen entry is skipped whole -- no update, its moments stay
+// zero -- which is torch.optim.Adam without that parameter (`_no_grad` takes it out of the optimiser). Gradients are exported for every image.
+template <bool MOD>
+D3R_DEV void image_step(const SmallView& s, int i, ImageRegs& r, const double (&RI)[15]) {
+    const int nf = MOD ? s.nfoc : 1;
+    float R[9];
+    quat_to_rotmat(r.Q, R);
+    double gQ[7], gf[2];
+    image_chain(r.Q, R, s.focal_break, RI, RI + 9, gQ, gf[0]);
+    if (nf == 2) focal_xy_grads(R, s.focal_break, RI, gf[0], gf[1]);
+    const bool tp = s.opt_poses && (!MOD || !s.tr_pose || s.tr_pose[i]);
+    const bool tf = s.opt_focals && (!MOD || !s.tr_foc || s.tr_foc[i]);
+    const bool tpp = s.opt_pp && (!MOD || !s.tr_pp || s.tr_pp[i]);
+    if (s.g_pp || (s.update && tpp)) {
+        // principal point (optimizer.py:141-142: pp = (W/2, H/2) + 10 im_pp): dX/dppx = -exp(d)/Fx R[:,0], so dL/d im_pp =
+        // -(10 / Fx) (R^T S)_0, -(10 / Fy) (R^T S)_1 at the focals the gradients were taken at
+        const double Fx = exp((double)r.fo[0] / (double)s.focal_break), Fy = exp((double)r.fo[1] / (double)s.focal_break);
+        const double gx = -(10.0 / Fx) * ((double)R[0] * RI[12] + (double)R[3] * RI[13] + (double)R[6] * RI[14]);
+        const double gy = -(10.0 / Fy) * ((double)R[1] * RI[12] + (double)R[4] * RI[13] + (double)R[7] * RI[14]);
+        const double gpp[2] = {gx, gy};
+        group_step(s, tpp, i * 2, 2, gpp, s.g_pp, r.pp, r.ppm, r.ppv, s.im_pp, s.pp_m, s.pp_v);
+    }
+    group_step(s, tp, i * 7, 7, gQ, s.g_imp, r.Q, r.qm, r.qv, s.im_poses, s.imp_m, s.imp_v);
+    group_step(s, tf, i * nf, nf, gf, s.g_foc, r.fo, r.fm, r.fv, s.im_focals, s.foc_m, s.foc_v);
+    if (nf == 1) r.fo[1] = r.fo[0];
+}
+
+// derived record of image i for the next main pass: R(9) T(3) Fx ppx ppy Fy (Fy: the Modular scene only, 0 otherwise)
+template <bool MOD>
+D3R_DEV void image_derived(const SmallView& s, int i, const ImageRegs& r) {
     float D[16];
-    quat_to_rotmat(Q, D);
-    D[9] = signed_expm1f(Q[4]); D[10] = signed_expm1f(Q[5]); D[11] = signed_expm1f(Q[6]);
-    D[12] = expf(fo[0] / s.focal_break);
-    D[13] = principal_point_px(s.img_w[i], pp0);
-    D[14] = principal_point_px(s.img_h[i], pp1);
-    D[15] = expf(fo[1] / s.focal_break);
+    quat_to_rotmat(r.Q, D);
+    D[9] = signed_expm1f(r.Q[4]); D[10] = signed_expm1f(r.Q[5]); D[11] = signed_expm1f(r.Q[6]);
+    D[12] = expf(r.fo[0] / s.focal_break);
+    D[13] = principal_point_px(r.w, r.pp[0]);
+    D[14] = principal_point_px(r.h, r.pp[1]);
+    D[15] = MOD ? expf(r.fo[1] / s.focal_break) : 0.f;
     float4* dst = reinterpret_cast<float4*>(s.d_img + i * 16);
+#pragma unroll
     for (int k = 0; k < 4; ++k) dst[k] = make_float4(D[4 * k], D[4 * k + 1], D[4 * k + 2], D[4 * k + 3]);
 }
 
-D3R_DEV void modular_load_image(const SmallView& s, int i, float (&Q)[7], float (&fo)[2], float& pp0, float& pp1) {
-    for (int k = 0; k < 7; ++k) Q[k] = s.im_poses[i * 7 + k];
-    fo[0] = s.im_focals[i * s.nfoc];
-    fo[1] = s.im_focals[i * s.nfoc + s.nfoc - 1];
-    pp0 = s.im_pp[i * 2]; pp1 = s.im_pp[i * 2 + 1];
+// a row of 8 floats (a pairwise pose or its moments) as two float4
+D3R_DEV void load8(const float* p, float (&d)[8]) {
+    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+    d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+}
+
+D3R_DEV void load_edge(const SmallView& s, int e, EdgeRegs& r) {
+    load8(s.pw_poses + e * 8, r.P);
+    const float2 a2 = *reinterpret_cast<const float2*>(s.pw_adaptors + e * 2);
+    r.ad[0] = a2.x; r.ad[1] = a2.y;
+    if (s.update) {
+        load8(s.pw_m + e * 8, r.pm);
+        load8(s.pw_v + e * 8, r.pv);
+        if (s.opt_adapt) { r.am[0] = s.pa_m[e * 2]; r.am[1] = s.pa_m[e * 2 + 1]; r.av[0] = s.pa_v[e * 2]; r.av[1] = s.pa_v[e * 2 + 1]; }
+    }
+}
+
+// GM = dL/dM_e (3x4), both sides of edge e summed; returns the edge's loss
+D3R_DEV double load_edge_sums(const SmallView& s, int e, double (&GM)[12]) {
+    const double* r0 = s.red_edge + (size_t)(2 * e) * PW;
+    const double* r1 = r0 + PW;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) GM[k] = r0[k] + r1[k];
+    return r0[12] + r1[12];
 }
 
 D3R_DEV float pw_scale_factor(const SmallView& s, double mean_p7) {
     return s.norm_pw_scale ? expf(logf(s.base_scale) - (float)mean_p7) : 1.0f;
+}
+
+// pairwise adaptors (base_opt.py:143-149): adapt = exp((A - mean A) / pw_break) with A = (a0, a0, a1); fp32, as the main pass uses them
+D3R_DEV float adaptor_mean(const SmallView& s, const float (&ad)[2]) { return s.norm_pw_scale ? (2.f * ad[0] + ad[1]) / 3.f : 0.f; }
+D3R_DEV void adaptor_factors(const SmallView& s, const float (&ad)[2], float (&f)[3]) {
+    const float mean = adaptor_mean(s, ad);
+    f[0] = f[1] = expf((ad[0] - mean) / s.pw_break);
+    f[2] = expf((ad[1] - mean) / s.pw_break);
+}
+// M_e[r][c] = s~ R[r][c] adapt_c, so dL/d adapt_c = s~ sum_r GM[r][c] R[r][c]; then through the exp and the mean-centring to (a0, a1)
+D3R_DEV void adaptor_grads(const SmallView& s, const EdgeRegs& r, float nf, const double (&GM)[12], double (&g)[2]) {
+    float R[9];
+    quat_to_rotmat(r.P, R);
+    const float mean = adaptor_mean(s, r.ad);
+    const double ad[3] = {exp((double)(r.ad[0] - mean) / s.pw_break), exp((double)(r.ad[0] - mean) / s.pw_break), exp((double)(r.ad[1] - mean) / s.pw_break)};
+    const double st = exp((double)r.P[7]) * (double)nf;
+    double gA[3], tot = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        double gc = 0.0;
+        for (int k = 0; k < 3; ++k) gc += GM[k * 4 + c] * (double)R[k * 3 + c];
+        gA[c] = gc * st * ad[c] / (double)s.pw_break;      // dL/d((A_c - mean) / b) chain through exp
+        tot += gA[c];
+    }
+    if (s.norm_pw_scale)
+        for (int c = 0; c < 3; ++c) gA[c] -= tot / 3.0;
+    g[0] = gA[0] + gA[1]; g[1] = gA[2];
+}
+
+// chain rule at the parameters the main pass used: gP[0:7] = dL/dP_e[0:7], gP[7] = dL/ds~_e * s~_e (before the coupling through the mean of P7)
+D3R_DEV void edge_grads(const SmallView& s, const EdgeRegs& r, float nf, const double (&GM)[12], double (&gP)[8]) {
+    float R[9], adapt[3];
+    quat_to_rotmat(r.P, R);
+    const float st = expf(r.P[7]) * nf;
+    adaptor_factors(s, r.ad, adapt);
+    double gs;
+    edge_chain(r.P, R, st, adapt, GM, gP, gs);
+    gP[7] = gs * (double)st;
+}
+
+D3R_DEV bool adaptor_grads_wanted(const SmallView& s) { return s.g_pa || (s.update && s.opt_adapt); }
+
+// Edge e's update from the complete gradient of P_e[0:8] (scale coupling included): the adaptors (GM is read only when
+// adaptor_grads_wanted), then the pose
+D3R_DEV void edge_update(const SmallView& s, int e, EdgeRegs& r, const double (&gP)[8], float nf, const double (&GM)[12]) {
+    if (adaptor_grads_wanted(s)) {
+        double gA[2];
+        adaptor_grads(s, r, nf, GM, gA);      // at the pose the main pass used: before its update below
+        group_step(s, s.opt_adapt != 0, e * 2, 2, gA, s.g_pa, r.ad, r.am, r.av, s.pw_adaptors, s.pa_m, s.pa_v);
+    }
+    group_step(s, true, e * 8, 8, gP, s.g_pw, r.P, r.pm, r.pv, s.pw_poses, s.pw_m, s.pw_v);
+}
+
+// derived M_e = [s~ R diag(adapt) | s~ T] for the next main pass; nf from the mean of P7 AFTER the update
+D3R_DEV void edge_derived(const SmallView& s, int e, const EdgeRegs& r, float nf) {
+    float R[9], ad[3];
+    quat_to_rotmat(r.P, R);
+    const float st = expf(r.P[7]) * nf;
+    adaptor_factors(s, r.ad, ad);
+    float4* M = reinterpret_cast<float4*>(s.d_edge + e * 12);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        M[k] = make_float4(st * R[k * 3] * ad[0], st * R[k * 3 + 1] * ad[1], st * R[k * 3 + 2] * ad[2], st * signed_expm1f(r.P[4 + k]));
 }
 
 // fixed-order block sum (256 threads): wave butterfly in fp64, then the four wave totals in wave order
@@ -415,8 +536,10 @@ D3R_DEV double block_sum_f64(double v, double* sh4) {
     return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
 }
 
+// ---- the step in strided loops: any E, n --------------------------------------------------------------------------------------------
 // single workgroup; E and n are a few hundred at most per call site (E <= 600). Every sum over edges is
-// a block reduction (thread t owns edges t, t+256, ...): no thread-0 serial chains of dependent L2 loads.
+// a block reduction (thread t owns edges t, t+256, ...): no thread-0 serial chains of dependent L2 loads. Items are loaded inside the
+// loops, and the gradient of P_e crosses the block sum of the scale coupling through s.scratch.
 template <bool MOD>
 __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
     __shared__ double sh4[4];
@@ -427,105 +550,37 @@ __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
         for (int e = tid; e < s.E; e += 256) acc += (double)s.pw_poses[e * 8 + 7];
         const double mean7 = block_sum_f64(acc, sh4) / (double)s.E;
         const float nf = pw_scale_factor(s, mean7);
-        // pass 1: dL/ds~_e * s~_e (kept in scratch) and its sum over edges; loss = sum of the per-side partials
+        // pass 1: the gradient of P_e (kept in scratch; slot 7 = dL/ds~_e * s~_e) and the sums over edges of slot 7 and of the loss
         double gsum = 0.0, lsum = 0.0;
         for (int e = tid; e < s.E; e += 256) {
-            const float* P = s.pw_poses + e * 8;
-            float R[9];
-            quat_to_rotmat(P, R);
-            const float st = expf(P[7]) * nf;
-            float adapt[3];
-            {
-                const float a0 = s.pw_adaptors[e * 2], a1 = s.pw_adaptors[e * 2 + 1];
-                const float mean = s.norm_pw_scale ? (2.f * a0 + a1) / 3.f : 0.f;
-                adapt[0] = adapt[1] = expf((a0 - mean) / s.pw_break);
-                adapt[2] = expf((a1 - mean) / s.pw_break);
-            }
-            double GM[12], gP[7], gs;
-            for (int k = 0; k < 12; ++k) GM[k] = s.red_edge[(size_t)(2 * e) * PW + k] + s.red_edge[(size_t)(2 * e + 1) * PW + k];
-            edge_chain(P, R, st, adapt, GM, gP, gs);
-            for (int k = 0; k < 7; ++k) s.scratch[(size_t)e * 8 + k] = gP[k];   // reused by pass 2 (same thread, same e)
-            s.scratch[(size_t)e * 8 + 7] = gs * (double)st;
-            gsum += gs * (double)st;
-            lsum += s.red_edge[(size_t)(2 * e) * PW + 12] + s.red_edge[(size_t)(2 * e + 1) * PW + 12];
+            EdgeRegs r;
+            double GM[12], gP[8];
+            load_edge(s, e, r);
+            const double lside = load_edge_sums(s, e, GM);
+            edge_grads(s, r, nf, GM, gP);
+            for (int k = 0; k < 8; ++k) s.scratch[(size_t)e * 8 + k] = gP[k];   // reused by pass 2 (same thread, same e)
+            gsum += gP[7];
+            lsum += lside;
         }
         const double sum_gs = block_sum_f64(gsum, sh4);
         const double loss = block_sum_f64(lsum, sh4);
         if (tid == 0 && s.loss_hist) s.loss_hist[s.iter] = (float)loss;
-        // pass 2: the scale gradient needs the sum over ALL edges (norm_pw_scale couples them); then Adam on pairwise poses
+        // pass 2: the scale gradient needs the sum over ALL edges (norm_pw_scale couples them); then the update
         for (int e = tid; e < s.E; e += 256) {
-            float* P = s.pw_poses + e * 8;
-            double gP[8];
-            for (int k = 0; k < 7; ++k) gP[k] = s.scratch[(size_t)e * 8 + k];
-            gP[7] = s.scratch[(size_t)e * 8 + 7] - (s.norm_pw_scale ? sum_gs / (double)s.E : 0.0);
-            if (s.g_pw)
-                for (int k = 0; k < 8; ++k) s.g_pw[e * 8 + k] = (float)gP[k];
-            if (s.g_pa || (s.update && s.opt_adapt)) {
-                // pairwise adaptors (base_opt.py:143-149: adapt = exp((A - mean A) / pw_break), A = (a0, a0, a1)): M_e[r][c] =
-                // s~ R[r][c] adapt_c, so dL/d adapt_c = s~ sum_r GM[r][c] R[r][c]; then through exp and the mean-centring
-                float R[9];
-                quat_to_rotmat(P, R);
-                const float a0 = s.pw_adaptors[e * 2], a1 = s.pw_adaptors[e * 2 + 1];
-                const float mean = s.norm_pw_scale ? (2.f * a0 + a1) / 3.f : 0.f;
-                const double ad[3] = {exp((double)(a0 - mean) / s.pw_break), exp((double)(a0 - mean) / s.pw_break), exp((double)(a1 - mean) / s.pw_break)};
-                const double st = exp((double)P[7]) * (double)nf;
-                double gA[3], tot = 0.0;
-                for (int c = 0; c < 3; ++c) {
-                    double gc = 0.0;
-                    for (int r = 0; r < 3; ++r)
-                        gc += (s.red_edge[(size_t)(2 * e) * PW + r * 4 + c] + s.red_edge[(size_t)(2 * e + 1) * PW + r * 4 + c]) * (double)R[r * 3 + c];
-                    gA[c] = gc * st * ad[c] / (double)s.pw_break;      // dL/d((A_c - mean) / b) chain through exp
-                    tot += gA[c];
-                }
-                if (s.norm_pw_scale)
-                    for (int c = 0; c < 3; ++c) gA[c] -= tot / 3.0;
-                const double g0 = gA[0] + gA[1], g1 = gA[2];
-                if (s.g_pa) { s.g_pa[e * 2] = (float)g0; s.g_pa[e * 2 + 1] = (float)g1; }
-                if (s.update && s.opt_adapt) {
-                    s.pw_adaptors[e * 2] = adam_update_unfused(a0, (float)g0, s.pa_m[e * 2], s.pa_v[e * 2], s.adam);
-                    s.pw_adaptors[e * 2 + 1] = adam_update_unfused(a1, (float)g1, s.pa_m[e * 2 + 1], s.pa_v[e * 2 + 1], s.adam);
-                }
-            }
-            if (s.update)
-                for (int k = 0; k < 8; ++k) P[k] = adam_update_unfused(P[k], (float)gP[k], s.pw_m[e * 8 + k], s.pw_v[e * 8 + k], s.adam);
+            EdgeRegs r;
+            double GM[12], gP[8];
+            load_edge(s, e, r);
+            if (adaptor_grads_wanted(s)) load_edge_sums(s, e, GM);
+            for (int k = 0; k < 8; ++k) gP[k] = s.scratch[(size_t)e * 8 + k];
+            if (s.norm_pw_scale) gP[7] -= sum_gs / (double)s.E;
+            edge_update(s, e, r, gP, nf, GM);
         }
-        // image poses / focals
         for (int i = tid; i < s.n; i += 256) {
-            if constexpr (MOD) {
-                float Q[7], fo[2], pp0, pp1;
-                double RI[15];
-                modular_load_image(s, i, Q, fo, pp0, pp1);
-                for (int k = 0; k < 15; ++k) RI[k] = s.red_img[(size_t)i * PW + k];
-                modular_image_step(s, i, Q, fo, pp0, pp1, RI);
-                continue;
-            }
-            float* P = s.im_poses + i * 7;
-            float R[9];
-            quat_to_rotmat(P, R);
-            double G[9], GT[3], gP[7], gf;
-            for (int k = 0; k < 9; ++k) G[k] = s.red_img[(size_t)i * PW + k];
-            for (int k = 0; k < 3; ++k) GT[k] = s.red_img[(size_t)i * PW + 9 + k];
-            image_chain(P, R, s.focal_break, G, GT, gP, gf);
-            if (s.g_imp)
-                for (int k = 0; k < 7; ++k) s.g_imp[i * 7 + k] = (float)gP[k];
-            if (s.g_foc) s.g_foc[i] = (float)gf;
-            if (s.update && s.opt_poses)
-                for (int k = 0; k < 7; ++k) P[k] = adam_update_unfused(P[k], (float)gP[k], s.imp_m[i * 7 + k], s.imp_v[i * 7 + k], s.adam);
-            const float focal_param_old = s.im_focals[i];
-            if (s.update && s.opt_focals) s.im_focals[i] = adam_update_unfused(s.im_focals[i], (float)gf, s.foc_m[i], s.foc_v[i], s.adam);
-            if (s.g_pp || (s.update && s.opt_pp)) {
-                // principal point (optimizer.py:141-142: pp = (W/2, H/2) + 10 im_pp): dX/dppx = -exp(d)/F R[:,0], so
-                // dL/d im_pp = -(10 / F) (R^T S)_{0,1} with S = sum_p g_p exp(d_p), the record's last three sums
-                const double F = exp((double)focal_param_old / (double)s.focal_break);   // the focal the gradients were taken at
-                const double S0 = s.red_img[(size_t)i * PW + 12], S1 = s.red_img[(size_t)i * PW + 13], S2 = s.red_img[(size_t)i * PW + 14];
-                const double gx = -(10.0 / F) * ((double)R[0] * S0 + (double)R[3] * S1 + (double)R[6] * S2);
-                const double gy = -(10.0 / F) * ((double)R[1] * S0 + (double)R[4] * S1 + (double)R[7] * S2);
-                if (s.g_pp) { s.g_pp[i * 2] = (float)gx; s.g_pp[i * 2 + 1] = (float)gy; }
-                if (s.update && s.opt_pp) {
-                    s.im_pp[i * 2] = adam_update_unfused(s.im_pp[i * 2], (float)gx, s.pp_m[i * 2], s.pp_v[i * 2], s.adam);
-                    s.im_pp[i * 2 + 1] = adam_update_unfused(s.im_pp[i * 2 + 1], (float)gy, s.pp_m[i * 2 + 1], s.pp_v[i * 2 + 1], s.adam);
-                }
-            }
+            ImageRegs r;
+            double RI[15];
+            load_image<MOD>(s, i, r);
+            for (int k = 0; k < 15; ++k) RI[k] = s.red_img[(size_t)i * PW + k];
+            image_step<MOD>(s, i, r, RI);
         }
         __syncthreads();   // the updated P7 values are read by other threads below
     }
@@ -534,39 +589,16 @@ __global__ __launch_bounds__(256) void aligner_small_kernel(SmallView s) {
     for (int e = tid; e < s.E; e += 256) acc2 += (double)s.pw_poses[e * 8 + 7];
     const float nf = pw_scale_factor(s, block_sum_f64(acc2, sh4) / (double)s.E);
     for (int e = tid; e < s.E; e += 256) {
-        const float* P = s.pw_poses + e * 8;
-        float R[9];
-        quat_to_rotmat(P, R);
-        const float st = expf(P[7]) * nf;
-        const float a0 = s.pw_adaptors[e * 2], a1 = s.pw_adaptors[e * 2 + 1];
-        const float mean = s.norm_pw_scale ? (2.f * a0 + a1) / 3.f : 0.f;
-        const float ad[3] = {expf((a0 - mean) / s.pw_break), expf((a0 - mean) / s.pw_break), expf((a1 - mean) / s.pw_break)};
-        float* M = s.d_edge + e * 12;
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) M[r * 4 + c] = st * R[r * 3 + c] * ad[c];
-            M[r * 4 + 3] = st * signed_expm1f(P[4 + r]);
-        }
+        EdgeRegs r;
+        load_edge(s, e, r);
+        edge_derived(s, e, r, nf);
     }
     for (int i = tid; i < s.n; i += 256) {
-        if constexpr (MOD) {
-            float Q[7], fo[2], pp0, pp1;
-            modular_load_image(s, i, Q, fo, pp0, pp1);
-            modular_image_derived(s, i, Q, fo, pp0, pp1);
-            continue;
-        }
-        const float* P = s.im_poses + i * 7;
-        float* D = s.d_img + i * 16;
-        quat_to_rotmat(P, D);
-        D[9] = signed_expm1f(P[4]);
-        D[10] = signed_expm1f(P[5]);
-        D[11] = signed_expm1f(P[6]);
-        D[12] = expf(s.im_focals[i] / s.focal_break);
-        D[13] = principal_point_px(s.img_w[i], s.im_pp[i * 2]);
-        D[14] = principal_point_px(s.img_h[i], s.im_pp[i * 2 + 1]);
-        D[15] = 0.f;
+        ImageRegs r;
+        load_image<MOD>(s, i, r);
+        image_derived<MOD>(s, i, r);
     }
 }
-
 
 // ---- the same step with ONE edge and ONE image per thread (E, n <= NT) ----------------------------------------------------------
 // The generic kernel above walks edges in strided loops, so everything that crosses a block sum goes through memory (scratch, the
@@ -600,181 +632,49 @@ __global__ __launch_bounds__(NT) void aligner_small1_kernel(SmallView s) {
     const int e = he ? tid : 0, i = hi ? tid : 0;
 
     // ---- one batch of loads ------------------------------------------------------------------------------------------------
-    float P[8], ad0, ad1, pm[8], pv[8], am[2], av[2];
-    double GM[12], lside = 0.0;
-    {
-        const float4 p0 = *reinterpret_cast<const float4*>(s.pw_poses + e * 8), p1 = *reinterpret_cast<const float4*>(s.pw_poses + e * 8 + 4);
-        P[0] = p0.x; P[1] = p0.y; P[2] = p0.z; P[3] = p0.w; P[4] = p1.x; P[5] = p1.y; P[6] = p1.z; P[7] = p1.w;
-        const float2 a2 = *reinterpret_cast<const float2*>(s.pw_adaptors + e * 2);
-        ad0 = a2.x; ad1 = a2.y;
-    }
-    if (s.update) {
-        const float4 m0 = *reinterpret_cast<const float4*>(s.pw_m + e * 8), m1 = *reinterpret_cast<const float4*>(s.pw_m + e * 8 + 4);
-        const float4 v0 = *reinterpret_cast<const float4*>(s.pw_v + e * 8), v1 = *reinterpret_cast<const float4*>(s.pw_v + e * 8 + 4);
-        pm[0] = m0.x; pm[1] = m0.y; pm[2] = m0.z; pm[3] = m0.w; pm[4] = m1.x; pm[5] = m1.y; pm[6] = m1.z; pm[7] = m1.w;
-        pv[0] = v0.x; pv[1] = v0.y; pv[2] = v0.z; pv[3] = v0.w; pv[4] = v1.x; pv[5] = v1.y; pv[6] = v1.z; pv[7] = v1.w;
-        if (s.opt_adapt) { am[0] = s.pa_m[e * 2]; am[1] = s.pa_m[e * 2 + 1]; av[0] = s.pa_v[e * 2]; av[1] = s.pa_v[e * 2 + 1]; }
-    }
-    if (grads) {
-        const double* r0 = s.red_edge + (size_t)(2 * e) * PW;
-        const double* r1 = r0 + PW;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) GM[k] = r0[k] + r1[k];
-        lside = r0[12] + r1[12];
-    }
-    float Q[7], foc, pp0, pp1, qm[7], qv[7], fm = 0.f, fv = 0.f, ppm[2], ppv[2];
-    double RI[15];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) Q[k] = s.im_poses[i * 7 + k];
-    foc = s.im_focals[i];
-    pp0 = s.im_pp[i * 2]; pp1 = s.im_pp[i * 2 + 1];
-    float fo[2] = {foc, foc};   // MOD: x and y focal parameters
-    if constexpr (MOD) { fo[0] = s.im_focals[i * s.nfoc]; fo[1] = s.im_focals[i * s.nfoc + s.nfoc - 1]; }
-    const int iw = s.img_w[i], ih = s.img_h[i];
-    if (s.update) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) { qm[k] = s.imp_m[i * 7 + k]; qv[k] = s.imp_v[i * 7 + k]; }
-        fm = s.foc_m[i]; fv = s.foc_v[i];
-        if (s.opt_pp) { ppm[0] = s.pp_m[i * 2]; ppm[1] = s.pp_m[i * 2 + 1]; ppv[0] = s.pp_v[i * 2]; ppv[1] = s.pp_v[i * 2 + 1]; }
-    }
+    EdgeRegs er;
+    ImageRegs ir;
+    double GM[12], RI[15], lside = 0.0;
+    load_edge(s, e, er);
+    if (grads) lside = load_edge_sums(s, e, GM);
+    load_image<MOD>(s, i, ir);
     if (grads) {
 #pragma unroll
         for (int k = 0; k < 15; ++k) RI[k] = s.red_img[(size_t)i * PW + k];
     }
 
     if (grads) {
-        // ---- edges: chain rule at the parameters the main pass used ----------------------------------------------------------
-        double v3[3] = {he ? (double)P[7] : 0.0, 0.0, 0.0};
+        // mean of P7 BEFORE the update defines the s~ the gradients were taken at
+        double v3[3] = {he ? (double)er.P[7] : 0.0, 0.0, 0.0};
         block_sum3_f64<NT>(v3, sh);
         const float nf = pw_scale_factor(s, v3[0] / (double)s.E);
-        float R[9];
-        quat_to_rotmat(P, R);
-        const float st = expf(P[7]) * nf;
-        const float amean = s.norm_pw_scale ? (2.f * ad0 + ad1) / 3.f : 0.f;
-        const float adapt[3] = {expf((ad0 - amean) / s.pw_break), expf((ad0 - amean) / s.pw_break), expf((ad1 - amean) / s.pw_break)};
-        double gP[8], gs;
-        edge_chain(P, R, st, adapt, GM, gP, gs);
-        gP[7] = gs * (double)st;
+        double gP[8];
+        edge_grads(s, er, nf, GM, gP);
         double w3[3] = {he ? gP[7] : 0.0, he ? lside : 0.0, 0.0};
         block_sum3_f64<NT>(w3, sh);
         if (tid == 0 && s.loss_hist) s.loss_hist[s.iter] = (float)w3[1];
         if (s.norm_pw_scale) gP[7] -= w3[0] / (double)s.E;
-        if (he) {
-            if (s.g_pw)
-                for (int k = 0; k < 8; ++k) s.g_pw[e * 8 + k] = (float)gP[k];
-            if (s.g_pa || (s.update && s.opt_adapt)) {
-                const double ad[3] = {exp((double)(ad0 - amean) / s.pw_break), exp((double)(ad0 - amean) / s.pw_break), exp((double)(ad1 - amean) / s.pw_break)};
-                const double std_ = exp((double)P[7]) * (double)nf;
-                double gA[3], tot = 0.0;
-                for (int c = 0; c < 3; ++c) {
-                    double gc = 0.0;
-                    for (int r = 0; r < 3; ++r) gc += GM[r * 4 + c] * (double)R[r * 3 + c];
-                    gA[c] = gc * std_ * ad[c] / (double)s.pw_break;
-                    tot += gA[c];
-                }
-                if (s.norm_pw_scale)
-                    for (int c = 0; c < 3; ++c) gA[c] -= tot / 3.0;
-                const double g0 = gA[0] + gA[1], g1 = gA[2];
-                if (s.g_pa) { s.g_pa[e * 2] = (float)g0; s.g_pa[e * 2 + 1] = (float)g1; }
-                if (s.update && s.opt_adapt) {
-                    ad0 = adam_update_unfused(ad0, (float)g0, am[0], av[0], s.adam);
-                    ad1 = adam_update_unfused(ad1, (float)g1, am[1], av[1], s.adam);
-                    *reinterpret_cast<float2*>(s.pw_adaptors + e * 2) = make_float2(ad0, ad1);
-                    s.pa_m[e * 2] = am[0]; s.pa_m[e * 2 + 1] = am[1]; s.pa_v[e * 2] = av[0]; s.pa_v[e * 2 + 1] = av[1];
-                }
-            }
-            if (s.update) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) P[k] = adam_update_unfused(P[k], (float)gP[k], pm[k], pv[k], s.adam);
-                float4* d = reinterpret_cast<float4*>(s.pw_poses + e * 8);
-                d[0] = make_float4(P[0], P[1], P[2], P[3]); d[1] = make_float4(P[4], P[5], P[6], P[7]);
-                float4* dm = reinterpret_cast<float4*>(s.pw_m + e * 8);
-                dm[0] = make_float4(pm[0], pm[1], pm[2], pm[3]); dm[1] = make_float4(pm[4], pm[5], pm[6], pm[7]);
-                float4* dv = reinterpret_cast<float4*>(s.pw_v + e * 8);
-                dv[0] = make_float4(pv[0], pv[1], pv[2], pv[3]); dv[1] = make_float4(pv[4], pv[5], pv[6], pv[7]);
-            }
-        }
-        // ---- images ------------------------------------------------------------------------------------------------------------
-        if (MOD && hi) modular_image_step(s, i, Q, fo, pp0, pp1, RI);
-        if (!MOD && hi) {
-            float R2[9];
-            quat_to_rotmat(Q, R2);
-            double gQ[7], gf;
-            image_chain(Q, R2, s.focal_break, RI, RI + 9, gQ, gf);
-            if (s.g_imp)
-                for (int k = 0; k < 7; ++k) s.g_imp[i * 7 + k] = (float)gQ[k];
-            if (s.g_foc) s.g_foc[i] = (float)gf;
-            if (s.g_pp || (s.update && s.opt_pp)) {
-                const double F = exp((double)foc / (double)s.focal_break);   // the focal the gradients were taken at
-                const double gx = -(10.0 / F) * ((double)R2[0] * RI[12] + (double)R2[3] * RI[13] + (double)R2[6] * RI[14]);
-                const double gy = -(10.0 / F) * ((double)R2[1] * RI[12] + (double)R2[4] * RI[13] + (double)R2[7] * RI[14]);
-                if (s.g_pp) { s.g_pp[i * 2] = (float)gx; s.g_pp[i * 2 + 1] = (float)gy; }
-                if (s.update && s.opt_pp) {
-                    pp0 = adam_update_unfused(pp0, (float)gx, ppm[0], ppv[0], s.adam);
-                    pp1 = adam_update_unfused(pp1, (float)gy, ppm[1], ppv[1], s.adam);
-                    s.im_pp[i * 2] = pp0; s.im_pp[i * 2 + 1] = pp1;
-                    s.pp_m[i * 2] = ppm[0]; s.pp_m[i * 2 + 1] = ppm[1]; s.pp_v[i * 2] = ppv[0]; s.pp_v[i * 2 + 1] = ppv[1];
-                }
-            }
-            if (s.update && s.opt_poses) {
-#pragma unroll
-                for (int k = 0; k < 7; ++k) {
-                    Q[k] = adam_update_unfused(Q[k], (float)gQ[k], qm[k], qv[k], s.adam);
-                    s.im_poses[i * 7 + k] = Q[k]; s.imp_m[i * 7 + k] = qm[k]; s.imp_v[i * 7 + k] = qv[k];
-                }
-            }
-            if (s.update && s.opt_focals) {
-                foc = adam_update_unfused(foc, (float)gf, fm, fv, s.adam);
-                s.im_focals[i] = foc; s.foc_m[i] = fm; s.foc_v[i] = fv;
-            }
-        }
+        if (hi) image_step<MOD>(s, i, ir, RI);
+        if (he) edge_update(s, e, er, gP, nf, GM);
     }
     // ---- derived quantities for the next main pass, from the registers ---------------------------------------------------------
-    double u3[3] = {he ? (double)P[7] : 0.0, 0.0, 0.0};
+    double u3[3] = {he ? (double)er.P[7] : 0.0, 0.0, 0.0};
     block_sum3_f64<NT>(u3, sh);
     const float nf2 = pw_scale_factor(s, u3[0] / (double)s.E);
-    if (he) {
-        float R[9];
-        quat_to_rotmat(P, R);
-        const float st = expf(P[7]) * nf2;
-        const float mean = s.norm_pw_scale ? (2.f * ad0 + ad1) / 3.f : 0.f;
-        const float ad[3] = {expf((ad0 - mean) / s.pw_break), expf((ad0 - mean) / s.pw_break), expf((ad1 - mean) / s.pw_break)};
-        float4* M = reinterpret_cast<float4*>(s.d_edge + e * 12);
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            M[r] = make_float4(st * R[r * 3] * ad[0], st * R[r * 3 + 1] * ad[1], st * R[r * 3 + 2] * ad[2], st * signed_expm1f(P[4 + r]));
-    }
-    if (MOD && hi) modular_image_derived(s, i, Q, fo, pp0, pp1);
-    if (!MOD && hi) {
-        float D[16];
-        quat_to_rotmat(Q, D);
-        D[9] = signed_expm1f(Q[4]); D[10] = signed_expm1f(Q[5]); D[11] = signed_expm1f(Q[6]);
-        D[12] = expf(foc / s.focal_break);
-        D[13] = principal_point_px(iw, pp0);
-        D[14] = principal_point_px(ih, pp1);
-        D[15] = 0.f;
-        float4* dst = reinterpret_cast<float4*>(s.d_img + i * 16);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = make_float4(D[4 * k], D[4 * k + 1], D[4 * k + 2], D[4 * k + 3]);
-    }
+    if (he) edge_derived(s, e, er, nf2);
+    if (hi) image_derived<MOD>(s, i, ir);
 }
 
-template <bool MOD>
-static void launch_small(const SmallView& s, hipStream_t st, bool generic) {
-    // generic (D3R_ALIGNER_OPT_GENERIC_SMALL) pins the strided-loop kernel, which takes any E, n: parity tests run both
-    const int need = s.E > s.n ? s.E : s.n;
-    if (!generic && need <= 256) hipLaunchKernelGGL((aligner_small1_kernel<256, MOD>), dim3(1), dim3(256), 0, st, s);
-    else if constexpr (!MOD) {
-        if (!generic && need <= 1024) hipLaunchKernelGGL((aligner_small1_kernel<1024, MOD>), dim3(1), dim3(1024), 0, st, s);
-        else hipLaunchKernelGGL(aligner_small_kernel<MOD>, dim3(1), dim3(256), 0, st, s);
-    } else {
-        // the Modular scene above 256 edges / images takes the strided-loop kernel: at 1024 threads (128 VGPRs) the one-edge-per-thread form spills
-        hipLaunchKernelGGL(aligner_small_kernel<MOD>, dim3(1), dim3(256), 0, st, s);
-    }
-}
+// need = max(E, n) picks the kernel: one edge / image per thread at 256 threads, at 1024 threads (PointCloudOptimizer only: capped at 128
+// VGPRs that form spills, and the Modular step is the larger one), the strided loops above that. generic (D3R_ALIGNER_OPT_GENERIC_SMALL)
+// pins the strided loops, which take any E, n: parity tests run both.
 static void launch_small(const SmallView& s, hipStream_t st, bool generic, bool modular) {
-    if (modular) launch_small<true>(s, st, generic);
-    else launch_small<false>(s, st, generic);
+    const int need = s.E > s.n ? s.E : s.n;
+    void (*kernel)(SmallView) = modular ? aligner_small_kernel<true> : aligner_small_kernel<false>;
+    int nt = 256;
+    if (!generic && need <= 256) kernel = modular ? aligner_small1_kernel<256, true> : aligner_small1_kernel<256, false>;
+    else if (!generic && need <= 1024 && !modular) { kernel = aligner_small1_kernel<1024, false>; nt = 1024; }
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(nt), 0, st, s);
 }
 
 }  // namespace d3r

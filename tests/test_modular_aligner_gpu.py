@@ -196,7 +196,8 @@ def test_compute_global_alignment_mst_entry_point(gpu):
 
 
 def test_pose_step_kernels_agree_modular(gpu):
-    """The one-image-per-thread and strided-loop pose / focal steps in the Modular configuration (fx_and_fy, optimize_pp, partial masks)."""
+    """The one-image-per-thread and strided-loop pose / focal steps in the Modular configuration (fx_and_fy, optimize_pp, partial masks).
+    As in test_pose_step_kernels_agree the two runs end on the same bits: the same last loss, torch.equal on every entry of the state."""
     from dust3r_amd._lib import check, lib
     from dust3r_amd.cloud_opt.base_opt import global_alignment_loop
     g = _gold('aligner_modular_trace.pt')
@@ -220,6 +221,9 @@ def test_pose_step_kernels_agree_modular(gpu):
         assert rel(g0[k], g1[k]) < 1e-5, k
     for k in s0:
         assert rel(s0[k], s1[k]) < 1e-5, k
+    assert e0 == e1, (e0, e1)
+    for k in s0:
+        assert torch.equal(s0[k], s1[k]), k
     assert torch.equal(s0['im_pp.3'], s1['im_pp.3']) and not torch.equal(s0['im_pp.0'], pp[0].to(s0['im_pp.0'].device))
 
 

@@ -137,9 +137,10 @@ def test_global_aligner_accepts_reference_state(trace):
 
 def test_aligner_kernel_registers_and_scratch():
     """aligner.hip's resource report (dust3r_amd/build.py writes it next to the object when it compiles the file; build() runs before the suite).
-    The PointCloudOptimizer instances keep the registers they had before the Modular scene was added (main 126 / 122 VGPRs, one-edge-per-thread
-    step 210 at 256 threads and 128 + 392 B/lane of scratch at 1024 -- that spill predates the Modular scene --, strided step 135); the Modular
-    instances use no scratch, and the Modular scene has no 1024-thread step (it takes the strided kernel above 256 edges / images)."""
+    The PointCloudOptimizer main kernels keep the registers they had before the Modular scene was added (126 / 122 VGPRs). The step kernels, whose
+    per-edge and per-image bodies both scenes share: one edge per thread 226 VGPRs at 256 threads and 128 + 388 B/lane of scratch at 1024 (the
+    spill predates the Modular scene, then 392 B/lane), strided loops 159. The Modular instances use no scratch, and the Modular scene has no
+    1024-thread step (it takes the strided kernel above 256 edges / images)."""
     from dust3r_amd.build import CSRC
     rep = os.path.join(CSRC, 'aligner.resources.txt')
     assert os.path.exists(rep), f'{rep} is missing: build() writes it'
@@ -153,8 +154,8 @@ def test_aligner_kernel_registers_and_scratch():
             if m and cur is not None:
                 cur[key] = int(m.group(1))
     pco = {'_ZN3d3r19aligner_main_kernelILb1ELb0EEEvNS_11AlignerViewE': (126, 0), '_ZN3d3r19aligner_main_kernelILb0ELb0EEEvNS_11AlignerViewE': (122, 0),
-           '_ZN3d3r21aligner_small1_kernelILi256ELb0EEEvNS_9SmallViewE': (210, 0), '_ZN3d3r21aligner_small1_kernelILi1024ELb0EEEvNS_9SmallViewE': (128, 392),
-           '_ZN3d3r20aligner_small_kernelILb0EEEvNS_9SmallViewE': (135, 0)}
+           '_ZN3d3r21aligner_small1_kernelILi256ELb0EEEvNS_9SmallViewE': (226, 0), '_ZN3d3r21aligner_small1_kernelILi1024ELb0EEEvNS_9SmallViewE': (128, 388),
+           '_ZN3d3r20aligner_small_kernelILb0EEEvNS_9SmallViewE': (159, 0)}
     for k, (vgpr, scratch) in pco.items():
         assert (info[k]['vgpr'], info[k]['scratch']) == (vgpr, scratch), (k, info[k])
     modular = [k for k in info if re.search(r'aligner_(main|small1?)_kernel', k) and 'Lb1EEEv' in k]     # MOD = true is the last template argument
