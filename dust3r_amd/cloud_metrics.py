@@ -17,7 +17,14 @@ single search's at max_dist.
 
 The same grid and ladder carry the k nearest neighbours, and three consumers of their rows: `knn_mean_distances` with `outlier_threshold`
 (statistical outlier removal), `cloud_normals` and `orient_normals`; viz.FusedCloud.estimate_normals / remove_outliers and
-scene.fuse(normals=..., outliers=...) are built of them."""
+scene.fuse(normals=..., outliers=...) are built of them.
+
+    reg = register_clouds(src, dst, max_dist)               # Sim(3) ICP of src onto dst: csrc/cloud_icp.hip, d3r_cloud_transform / d3r_cloud_icp_sums
+
+The same nearest neighbour carries the registration of one cloud onto another: per iteration the source is moved by the
+current similarity, every moved point finds its nearest reference point on grids that are built once per stage, one kernel gates the pairs
+and reduces them to 18 (point to point) or 36 (point to plane) fp64 sums, and the host solves for the update in fp64."""
+import collections
 import ctypes as C
 import math
 
@@ -362,3 +369,281 @@ def cloud_metrics(pred, gt, max_dist, thresholds, to_host=True, r0=None, details
     k = 2 + MAX_THRESHOLDS
     cut = lambda o: (packed[o:o + k].long(), packed[o + k:o + k + 2], packed[o + k + 2:o + k + 3])      # noqa: E731
     return compose_metrics(_side(*cut(0), len(thresholds)), _side(*cut(k + 3), len(thresholds)), thresholds)
+
+
+# ---- registration: Sim(3) ICP ------------------------------------------------------------------------------------------
+ICP_POINT_SUMS, ICP_PLANE_SUMS = 18, 36         # the lengths of sums_out of d3r_cloud_icp_sums
+ICP_SINGULAR = 1e-12                            # a system whose smallest eigenvalue (singular value) is below this times its largest is singular
+METRICS = {'point': 0, 'plane': 1}
+
+Registration = collections.namedtuple('Registration', 'similarity scale rmse n_pairs n_valid iterations converged reason history')
+Registration.__doc__ = """The result of `register_clouds`: similarity (4, 4) float64 [s R | t] that takes src onto dst, its scale, rmse and n_pairs
+of the last measured iteration (the residual of the metric: distances for 'point', plane distances for 'plane'), n_valid = the finite source
+points, iterations (all stages), converged (the LAST stage met the tolerance), reason (why it ended), history = [(stage, n_pairs, rmse)]."""
+
+
+def similarity_parts(S):
+    """(M (12,) float32 = [A | t] row-major, R (9,) float32, scale) of a 4x4 similarity [s R | t; 0 0 0 1], what d3r_cloud_transform takes.
+    ValueError unless S is finite, its last row (0, 0, 0, 1) and its 3x3 block a positive multiple of a rotation (to 1e-6)."""
+    S = np.asarray(S, np.float64)
+    if S.shape != (4, 4) or not np.isfinite(S).all() or not np.array_equal(S[3], [0, 0, 0, 1]):
+        raise ValueError(f'expected a finite (4, 4) similarity with last row (0, 0, 0, 1), got {S!r}')
+    A = S[:3, :3]
+    det = np.linalg.det(A)
+    if not det > 0:
+        raise ValueError(f'the 3 x 3 block of a similarity has a positive determinant, got {det!r}')
+    scale = float(np.cbrt(det))
+    R = A / scale
+    if not np.abs(R @ R.T - np.eye(3)).max() <= 1e-6:
+        raise ValueError('the 3 x 3 block is not a multiple of a rotation')
+    return np.concatenate([A, S[:3, 3:4]], axis=1).astype(np.float32).reshape(12), R.astype(np.float32).reshape(9), scale
+
+
+def exp_so3(w):
+    """Rodrigues' formula, fp64: the rotation by |w| about w"""
+    w = np.asarray(w, np.float64)
+    t = float(np.linalg.norm(w))
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    a, b = (1 - t * t / 6, 0.5 - t * t / 24) if t < 1e-4 else (math.sin(t) / t, (1 - math.cos(t)) / (t * t))
+    return np.eye(3) + a * K + b * (K @ K)
+
+
+def _about_centre(A, v, centre):
+    """the 4x4 map p -> c + A (p - c) + v"""
+    out = np.eye(4)
+    out[:3, :3] = A
+    out[:3, 3] = centre + v - A @ centre
+    return out
+
+
+def icp_update_point(sums, centre, with_scale=True):
+    """(delta (4, 4) or None, rmse, reason) from the 18 sums of the point metric about `centre`: weighted Umeyama of the 17 moments
+    (bootstrap.similarity_from_moments; with_scale=False: its rotation with scale 1), delta = p -> c + s R (p - c - mx) + my.
+    None with a reason when fewer than 3 pairs or the source pairs do not span a plane."""
+    from .cloud_opt.bootstrap import similarity_from_moments
+    m = np.asarray(sums, np.float64)
+    n = m[0]
+    rmse = math.sqrt(max(m[17], 0.0) / n) if n > 0 else float('nan')
+    if n < 3:
+        return None, rmse, f'{int(n)} pairs, 3 needed'
+    mx, my = m[1:4] / n, m[4:7] / n
+    cov = (m[7:16].reshape(3, 3) / n).T - np.outer(my, mx)
+    var = m[16] / n - mx @ mx
+    sv = np.linalg.svd(cov, compute_uv=False)
+    if not (var > 0 and np.isfinite(sv).all() and sv[1] > ICP_SINGULAR * max(sv[0], var)):
+        return None, rmse, 'singular system: the pairs do not fix a rotation'
+    T = similarity_from_moments(m[:17])
+    s = float(np.cbrt(np.linalg.det(T[:3, :3])))
+    if not (np.isfinite(T).all() and s > 0):
+        return None, rmse, 'singular system: no finite similarity'
+    A = T[:3, :3] if with_scale else T[:3, :3] / s
+    return _about_centre(A, my - A @ mx, np.asarray(centre, np.float64)), rmse, None
+
+
+def plane_system(sums, with_scale=True):
+    """(H, g, sum e e) of the 36 sums of the plane metric: H the symmetric 7 x 7 matrix of sum J J^T (its 28 upper-triangle entries
+    row-major), g = sum J e; without scale their first six rows and columns"""
+    m = np.asarray(sums, np.float64)
+    k = 7 if with_scale else 6
+    H = np.zeros((7, 7))
+    H[np.triu_indices(7)] = m[:28]
+    H = H + np.triu(H, 1).T
+    return H[:k, :k], m[28:28 + k], float(m[35])
+
+
+def icp_update_plane(sums, n_pairs, centre, with_scale=True):
+    """(delta (4, 4) or None, rmse, reason) from the 36 sums of the plane metric about `centre`: the minimiser x = (omega, v, sigma) of
+    sum (e + J x)^2, H x = -g (`plane_system`; 6 unknowns without scale), delta = [e^sigma Exp(omega) | c + v - e^sigma Exp(omega) c].
+    Solved after a symmetric diagonal scaling; None with a reason when there are fewer pairs than unknowns or the scaled system's smallest
+    eigenvalue is below 1e-12 of its largest."""
+    H, g, see = plane_system(sums, with_scale)
+    k = len(g)
+    rmse = math.sqrt(max(see, 0.0) / n_pairs) if n_pairs > 0 else float('nan')
+    if n_pairs < k:
+        return None, rmse, f'{int(n_pairs)} pairs, {k} needed'
+    d = np.sqrt(np.diag(H))
+    if not (np.isfinite(H).all() and np.isfinite(g).all() and (d > 0).all()):
+        return None, rmse, 'singular system: a zero or non-finite diagonal'
+    Hs = H / np.outer(d, d)
+    ev = np.linalg.eigvalsh(Hs)
+    if not ev[0] > ICP_SINGULAR * ev[-1]:
+        return None, rmse, 'singular system: the planes do not fix every unknown'
+    x = np.linalg.solve(Hs, -g / d) / d
+    A = (math.exp(x[6]) if k == 7 else 1.0) * exp_so3(x[:3])
+    return _about_centre(A, x[3:6], np.asarray(centre, np.float64)), rmse, None
+
+
+def icp_update(metric, sums, n_pairs, centre, with_scale=True):
+    """(delta or None, rmse, reason) of one iteration from what d3r_cloud_icp_sums reduced; metric 'point' or 'plane'"""
+    if metric == 'point':
+        return icp_update_point(sums, centre, with_scale)
+    return icp_update_plane(sums, n_pairs, centre, with_scale)
+
+
+def _normals_of(cloud, device):
+    n = getattr(cloud, 'normals', None)
+    if n is None:
+        return None
+    t = n if isinstance(n, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(n, dtype=np.float32)))
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+@torch.no_grad()
+def transform_points(points, S, normals=None):
+    """points (N, 3) moved by the similarity S, and normals rotated by its rotation, on the device (d3r_cloud_transform): fp32, row r =
+    ((A_r0 x + A_r1 y) + A_r2 z) + t_r with [A | t] = float32(S). Device tensors; (moved, rotated normals or None)."""
+    M, R, _ = similarity_parts(S)
+    _lib.require_device()
+    device = _device_of(points)
+    P = _points(points, device, 'points')
+    out = torch.empty_like(P)
+    N_in = None if normals is None else _points(normals, device, 'normals')
+    if N_in is not None and len(N_in) != len(P):
+        raise ValueError(f'transform_points: {len(P)} points, {len(N_in)} normals')
+    N_out = None if N_in is None else torch.empty_like(N_in)
+    if len(P) > 0:
+        with torch.cuda.device(device):
+            check(lib.d3r_cloud_transform(len(P), ptr(P), (C.c_float * 12)(*M.tolist()), ptr(out), ptr(N_in), (C.c_float * 9)(*R.tolist()), ptr(N_out),
+                                          current_stream()), 'cloud_transform')
+    return out, N_out
+
+
+@torch.no_grad()
+def icp_sums(moved, ref, d2, idx, metric, gate, centre, ref_normals=None, moved_normals=None, cos_min=None, want_used=False):
+    """d3r_cloud_icp_sums on device tensors: (count (1,) int64, sums (18 or 36,) float64, used (N,) uint8 or None), no synchronisation"""
+    _lib.require_device()
+    device = moved.device
+    n = len(moved)
+    count = torch.zeros((1,), dtype=torch.int64, device=device)
+    sums = torch.zeros((ICP_PLANE_SUMS if METRICS[metric] else ICP_POINT_SUMS,), dtype=torch.float64, device=device)
+    used = torch.zeros((n,), dtype=torch.uint8, device=device) if want_used else None
+    if n > 0 and len(ref) > 0:
+        with torch.cuda.device(device):
+            work = torch.empty(int(lib.d3r_cloud_icp_sums_workspace_bytes(n)), dtype=torch.uint8, device=device)
+            check(lib.d3r_cloud_icp_sums(n, ptr(moved), ptr(moved_normals), len(ref), ptr(ref), ptr(ref_normals), ptr(d2), ptr(idx), METRICS[metric],
+                                         float(gate), 0.0 if cos_min is None else float(cos_min), (C.c_float * 3)(*[float(c) for c in centre]),
+                                         ptr(count), ptr(sums), ptr(used), ptr(work), current_stream()), 'cloud_icp_sums')
+    return count, sums, used
+
+
+class _ReferenceGrids:
+    """The grids of one ladder over a reference cloud that does not move: rung k in a workspace of its own, built once (kept) or before
+    every search (rebuild=True: what `nearest_in_cloud` does in one workspace; the same bytes, tests compare the two)."""
+
+    def __init__(self, R, lo, hi, radii, n_query, rebuild=False):
+        self.R, self.radii, self.rebuild, self.n_query = R, radii, rebuild, n_query
+        self.lo_c = (C.c_float * 3)(*lo.tolist())
+        size = int(lib.d3r_cloud_grid_workspace_bytes(len(R), n_query))
+        if size == 0:
+            raise ValueError(f'register_clouds: clouds of {n_query} and {len(R)} points are too large')
+        self.rungs = []
+        for r in radii:
+            cell, bits = grid_cell(lo, hi, r)
+            rung = (float(r), float(cell), (C.c_int * 3)(*bits), torch.empty(size, dtype=torch.uint8, device=R.device))
+            self.rungs.append(rung)
+            if not rebuild:
+                self._build(rung)
+
+    def _build(self, rung):
+        r, cell, bits_c, work = rung
+        check(lib.d3r_cloud_grid_build(len(self.R), ptr(self.R), self.lo_c, cell, bits_c, ptr(work), current_stream()), 'cloud_grid_build')
+
+    def nearest(self, Q, d2, idx):
+        """the ladder of `nearest_in_cloud` for the queries Q (at most n_query) into d2 / idx"""
+        for k, rung in enumerate(self.rungs):
+            if self.rebuild:
+                self._build(rung)
+            r, cell, bits_c, work = rung
+            check(lib.d3r_cloud_nearest(len(self.R), len(Q), ptr(Q), r, self.lo_c, cell, bits_c, int(k > 0), ptr(d2), ptr(idx), None, ptr(work),
+                                        current_stream()), 'cloud_nearest')
+
+
+@torch.no_grad()
+def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plane', max_iters=30, tol=1e-6, cos_min=None, r0=None, centre=None,
+                    _rebuild_grids=False):
+    """Sim(3) ICP of the cloud src onto the cloud dst on the GPU: a `Registration` whose similarity S takes src into dst's frame.
+    src, dst: (N, 3) arrays, tensors or FusedClouds. max_dist: the pair gate, a float or a coarse-to-fine sequence of floats, each a stage
+    of at most max_iters iterations that starts where the last ended. init: the (4, 4) similarity to start from (identity). with_scale=False
+    keeps the scale of init. metric: 'plane' (point to plane; the normals of dst: its own when it is a FusedCloud with normals, else PCA
+    normals of k_nearest(k=16) within 8 voxels, or within the largest max_dist for a cloud without a voxel size) or 'point'. cos_min: pairs
+    whose normals (src's rotated by S, dst's) have a cosine below it are dropped; needs normals on both clouds. r0: the first radius of the
+    nearest-neighbour ladder (default as `nearest_in_cloud`). centre (3,): the point the sums are taken about, default the middle of dst's
+    bounds. One iteration: d3r_cloud_transform of src by float32(S), the ladder of d3r_cloud_nearest on grids built once per stage (dst does
+    not move), d3r_cloud_icp_sums, ONE read-back of at most 37 numbers, `icp_update` in fp64 on the host, S <- delta S. A stage ends when
+    |rmse - rmse_prev| <= tol rmse (the update of that iteration is not applied: rmse and n_pairs are those of the returned S) or at
+    max_iters. ValueError when the first iteration has no pair; later, fewer pairs than unknowns or a singular system end the loop with
+    converged=False and a reason."""
+    if metric not in METRICS:
+        raise ValueError(f"register_clouds: metric is 'point' or 'plane', got {metric!r}")
+    stages = [max_dist] if np.ndim(max_dist) == 0 else list(max_dist)
+    if not stages or int(max_iters) < 1:
+        raise ValueError('register_clouds: max_dist is empty or max_iters < 1')
+    stages = [_radius_f32(g, 'max_dist') for g in stages]
+    S = np.eye(4) if init is None else np.array(init, np.float64)
+    similarity_parts(S)
+    _lib.require_device()
+    device = _device_of(src, dst)
+    P, Q = _points(src, device, 'src'), _points(dst, device, 'dst')
+    n = len(P)
+    if n == 0 or len(Q) == 0:
+        raise ValueError(f'register_clouds: clouds of {n} and {len(Q)} points')
+    src_normals = _normals_of(src, device) if cos_min is not None else None
+    dst_normals = _normals_of(dst, device) if metric == 'plane' or cos_min is not None else None
+    if cos_min is not None and (src_normals is None or dst_normals is None):
+        raise ValueError('register_clouds: cos_min needs normals on both clouds (FusedCloud.estimate_normals)')
+    history, reason, converged, rmse, n_pairs, iterations = [], None, False, float('nan'), 0, 0
+    with torch.cuda.device(device):
+        lo, hi, n_ref_valid = _bounds(Q, device)
+        if n_ref_valid == 0:
+            raise ValueError('register_clouds: dst has no finite point')
+        if metric == 'plane' and dst_normals is None:
+            voxel = getattr(dst, 'voxel_size', None)
+            radius = 8.0 * voxel if voxel is not None and math.isfinite(voxel) and voxel > 0 else float(max(stages))
+            _, nbr = k_nearest(Q, Q, 16, radius, exclude_self=True, r0=min(default_knn_r0(dst, 16, radius), radius), to_host=False)
+            dst_normals, _ = cloud_normals(Q, Q, nbr)
+        n_valid = int(torch.isfinite(P).all(dim=1).sum())
+        c = (0.5 * (lo.astype(np.float64) + hi.astype(np.float64))).astype(np.float32) if centre is None else np.asarray(centre, np.float32).reshape(3)
+        if not np.isfinite(c).all():
+            raise ValueError(f'register_clouds: centre {c!r} is not finite')
+        c64 = c.astype(np.float64)
+        moved, moved_normals = torch.empty_like(P), None if src_normals is None else torch.empty_like(src_normals)
+        d2 = torch.empty((n,), dtype=torch.float32, device=device)
+        idx = torch.empty((n,), dtype=torch.int32, device=device)
+        count = torch.zeros((1,), dtype=torch.int64, device=device)
+        sums = torch.zeros((ICP_PLANE_SUMS if METRICS[metric] else ICP_POINT_SUMS,), dtype=torch.float64, device=device)
+        work = torch.empty(int(lib.d3r_cloud_icp_sums_workspace_bytes(n)), dtype=torch.uint8, device=device)
+        centre_c = (C.c_float * 3)(*c.tolist())
+        for stage, gate in enumerate(stages):
+            first = default_r0(dst, gate) if r0 is None else r0
+            grids = _ReferenceGrids(Q, lo, hi, ladder_radii(min(float(_radius_f32(first, 'r0')), float(gate)), gate), n, rebuild=_rebuild_grids)
+            prev, converged = None, False
+            for it in range(int(max_iters)):
+                M, R, _ = similarity_parts(S)
+                check(lib.d3r_cloud_transform(n, ptr(P), (C.c_float * 12)(*M.tolist()), ptr(moved), ptr(src_normals), (C.c_float * 9)(*R.tolist()),
+                                              ptr(moved_normals), current_stream()), 'cloud_transform')
+                grids.nearest(moved, d2, idx)
+                check(lib.d3r_cloud_icp_sums(n, ptr(moved), ptr(moved_normals), len(Q), ptr(Q), ptr(dst_normals), ptr(d2), ptr(idx), METRICS[metric],
+                                             float(gate), 0.0 if cos_min is None else float(cos_min), centre_c, ptr(count), ptr(sums), None, ptr(work),
+                                             current_stream()), 'cloud_icp_sums')
+                host = torch.cat([count.double(), sums]).cpu().numpy()          # the iteration's one read-back (the count is exact in fp64)
+                pairs = int(host[0])
+                if pairs == 0 and not history:
+                    raise ValueError(f'register_clouds: no source point has a neighbour within {float(gate)!r} at the initial similarity')
+                delta, now, why = icp_update(metric, host[1:], pairs, c64, with_scale)
+                iterations += 1
+                n_pairs, rmse = pairs, now
+                history.append((stage, pairs, now))
+                if delta is None:
+                    reason = why
+                    break
+                if prev is not None and abs(now - prev) <= tol * now:
+                    converged, reason = True, 'converged'
+                    break
+                prev = now
+                S = delta @ S
+            else:
+                reason = f'max_iters = {int(max_iters)} reached in stage {stage}'
+            if delta is None:
+                break
+    scale = similarity_parts(S)[2]
+    return Registration(S, scale, rmse, n_pairs, n_valid, iterations, converged, reason, history)

@@ -14,7 +14,8 @@ evaluation is out of scope (ranks would add their per-pair sums and counts, see 
 scores an aligned SCENE against ground-truth views (new; the reference has no such code): the scene is registered to the ground truth, both
 sides are voxel-fused at one voxel size and the two clouds are compared by `dust3r_amd.cloud_metrics` (accuracy, completeness, Chamfer,
 precision / recall / F-score), all on the GPU. `python -m dust3r_amd.evaluation PRED.ply GT.ply --max-dist D` does the last step on two
-PLY files."""
+PLY files; with --register the predicted cloud is first registered onto the other by Sim(3) ICP (cloud_metrics.register_clouds), which
+`evaluate_scene(refine='icp')` does after its own alignment."""
 import json
 import math
 import sys
@@ -89,16 +90,24 @@ def pose_errors(pred_c2w, gt_c2w):
 
 
 @torch.no_grad()
-def evaluate_scene(scene, gt_views, align='points', voxel_size=None, max_dist=None, thresholds=None, return_details=False):
+def evaluate_scene(scene, gt_views, align='points', voxel_size=None, max_dist=None, thresholds=None, return_details=False, refine=None,
+                   refine_kw=None):
     """The cloud metrics of an aligned scene against ground truth. gt_views: per image a dict with `pts3d` (H, W, 3) world points,
     `valid_mask` (H, W) and optionally `camera_pose` (4, 4) cam-to-world (the keys of dust3r_amd.datasets).
     1. the similarity S that takes the scene into the ground truth's frame. align='points': one weighted Umeyama over all pixels valid on
        both sides (the scene's mask and finite point, the ground truth's valid_mask and finite point; weight 1, the others zeroed with
        weight 0) -- the 17 moments per image by d3r_similarity_moments, added in fp64 on the host, finished by
        bootstrap.similarity_from_moments. align='poses': bootstrap.align_pose_sets of the scene's poses onto the camera_poses. None: identity.
+       A (4, 4) array: that similarity.
     2. both sides through viz.fuse_points at one voxel_size (default: the scene's default_voxel_size times the scale of S): the scene's
        masked points, moved by S, weighted by confidence; the ground truth's valid points weighted by ones.
     3. cloud_metrics(pred cloud, gt cloud, max_dist, thresholds); defaults thresholds = (1, 2, 4) voxel_size, max_dist = 16 voxel_size.
+    refine='icp': after step 2 the scene's cloud is registered onto the ground truth's by cloud_metrics.register_clouds(pred_cloud, gt_cloud,
+    **refine_kw) (default max_dist: this call's; the plane metric takes the normals of the ground-truth cloud), the result is composed into
+    S, the scene is moved by the refined S and fused again at the unchanged voxel size, and step 3 scores that cloud. The refinement is
+    ACCEPTED when it lowers `overall` (the Chamfer distance it exists to reduce); otherwise everything is that of the first alignment, so
+    refining never reports a worse overall. `scale` and the pose errors are those of the S that was kept; the details gain `registration`
+    and `refined` (whether it was accepted). None: no refinement.
     With camera_pose in every view: ate_rmse and rot_err_mean_deg / rot_err_max_deg of the scene's poses moved by S (fp64, host).
     return_details: (metrics, details) with every stage's output: similarity (4, 4), scale, pred_pts / gt_pts / pred_mask / gt_mask
     (the padded stacks that were fused), pred_cloud / gt_cloud, d2_pred / idx_pred / d2_gt / idx_gt, voxel_size, max_dist, thresholds."""
@@ -107,8 +116,11 @@ def evaluate_scene(scene, gt_views, align='points', voxel_size=None, max_dist=No
     from .cloud_opt.bootstrap import align_pose_sets, similarity_from_moments, split_similarity
     from .utils.padded import pad_views
     from .viz import default_voxel_size, fuse_points
-    if align not in ('points', 'poses', None):
-        raise ValueError(f"evaluate_scene: align is 'points', 'poses' or None, got {align!r}")
+    given = None if align is None or isinstance(align, str) else np.array(align, np.float64)
+    if given is None and align not in ('points', 'poses', None):
+        raise ValueError(f"evaluate_scene: align is 'points', 'poses' or None (or a (4, 4) similarity), got {align!r}")
+    if refine not in ('icp', None):
+        raise ValueError(f"evaluate_scene: refine is 'icp' or None, got {refine!r}")
     if scene.device.type != 'cuda':
         raise _lib.D3RError('evaluate_scene runs on the GPU (dust3r_amd has no CPU execution path)')
     _lib.require_device()
@@ -126,7 +138,11 @@ def evaluate_scene(scene, gt_views, align='points', voxel_size=None, max_dist=No
     has_poses = all(v.get('camera_pose') is not None for v in gt_views)
     gt_poses = np.stack([np.asarray(torch.as_tensor(v['camera_pose']).detach().cpu(), np.float64) for v in gt_views]) if has_poses else None
     poses = scene.get_im_poses().detach().double().cpu().numpy()
-    if align == 'points':
+    if given is not None:
+        from .cloud_metrics import similarity_parts
+        similarity_parts(given)
+        S = given
+    elif align == 'points':
         both = pred_mask & gt_mask & torch.isfinite(pred).all(dim=-1) & torch.isfinite(gt).all(dim=-1)
         wgt = both.float().contiguous()
         moments = _stack_moments(torch.where(both[..., None], pred, 0.0).contiguous(), torch.where(both[..., None], gt, 0.0).contiguous(), wgt, areas)
@@ -139,9 +155,11 @@ def evaluate_scene(scene, gt_views, align='points', voxel_size=None, max_dist=No
         S = align_pose_sets(poses, gt_poses)
     else:
         S = np.eye(4)
+    def move(S):
+        A = torch.tensor(S[:3, :3], dtype=torch.float32, device=dev)
+        return (pred @ A.T + torch.tensor(S[:3, 3], dtype=torch.float32, device=dev)).contiguous()
     scale, R, t = split_similarity(S)
-    A = torch.tensor(S[:3, :3], dtype=torch.float32, device=dev)
-    aligned = (pred @ A.T + torch.tensor(S[:3, 3], dtype=torch.float32, device=dev)).contiguous() if align is not None else pred
+    aligned = move(S) if align is not None else pred
     if voxel_size is None:
         voxel_size = default_voxel_size(scene.get_depthmaps(raw=True), areas, scene.get_focals()) * scale
     thresholds = [k * voxel_size for k in (1, 2, 4)] if thresholds is None else list(thresholds)
@@ -150,6 +168,19 @@ def evaluate_scene(scene, gt_views, align='points', voxel_size=None, max_dist=No
     gt_cloud = fuse_points(scene.imgs, gt, gt_mask, None, voxel_size, dev, to_host=False)
     details = {}
     metrics = cloud_metrics(pred_cloud, gt_cloud, max_dist, thresholds, details=details)
+    if refine == 'icp':
+        from .cloud_metrics import register_clouds
+        registration = register_clouds(pred_cloud, gt_cloud, **dict(dict(max_dist=max_dist), **(refine_kw or {})))
+        S_new = registration.similarity @ S
+        moved = move(S_new)
+        cloud_new = fuse_points(scene.imgs, moved, pred_mask, scene._im_conf, voxel_size, dev, to_host=False)
+        details_new = {}
+        metrics_new = cloud_metrics(cloud_new, gt_cloud, max_dist, thresholds, details=details_new)
+        accepted = metrics_new['overall'] < metrics['overall']             # False for a NaN on either side: the first alignment stays
+        if accepted:
+            S, aligned, pred_cloud, metrics, details = S_new, moved, cloud_new, metrics_new, details_new
+            scale, R, t = split_similarity(S)
+        details.update(registration=registration, refined=accepted)
     metrics.update(voxel_size=float(voxel_size), max_dist=float(max_dist), scale=scale)
     if has_poses:
         moved = poses.copy()
@@ -164,20 +195,46 @@ def evaluate_scene(scene, gt_views, align='points', voxel_size=None, max_dist=No
 
 
 def main(argv=None):
-    """python -m dust3r_amd.evaluation PRED.ply GT.ply --max-dist D [--thresholds T ...]: the dict of cloud_metrics as one JSON line"""
+    """python -m dust3r_amd.evaluation PRED.ply GT.ply --max-dist D [--thresholds T ...]: the dict of cloud_metrics as one JSON line.
+    --register [--init FILE] [--rigid] [--metric point|plane] [--register-dist D1 D2 ...]: PRED is first registered onto GT by
+    cloud_metrics.register_clouds (stages --register-dist, default 4 D, 2 D, D) and moved; the line gains similarity (4 x 4, row-major
+    lists), registration_rmse and registration_pairs."""
+    args = parse_args(argv)
+    from .cloud_metrics import cloud_metrics
+    from .export import read_ply
+    clouds = [read_ply(p)['positions'] for p in (args.pred, args.gt)]
+    thresholds = [args.max_dist / 16, args.max_dist / 8, args.max_dist / 4] if args.thresholds is None else args.thresholds
+    if not args.register:
+        print(json.dumps(cloud_metrics(clouds[0], clouds[1], args.max_dist, thresholds)))
+        return 0
+    from .cloud_metrics import register_clouds, transform_points
+    init = None if args.init is None else np.loadtxt(args.init, dtype=np.float64).reshape(4, 4)
+    stages = [4 * args.max_dist, 2 * args.max_dist, args.max_dist] if args.register_dist is None else args.register_dist
+    reg = register_clouds(clouds[0], clouds[1], stages, init=init, with_scale=not args.rigid, metric=args.metric)
+    moved, _ = transform_points(clouds[0], reg.similarity)
+    out = cloud_metrics(moved, clouds[1], args.max_dist, thresholds)
+    out.update(similarity=reg.similarity.tolist(), registration_rmse=reg.rmse, registration_pairs=reg.n_pairs)
+    print(json.dumps(out))
+    return 0
+
+
+def parse_args(argv=None):
+    """the command line of `main`"""
     import argparse
     parser = argparse.ArgumentParser(prog='python -m dust3r_amd.evaluation', description='cloud-to-cloud metrics of two PLY files on the GPU')
     parser.add_argument('pred')
     parser.add_argument('gt')
     parser.add_argument('--max-dist', type=float, required=True, help='distances beyond it are outliers')
     parser.add_argument('--thresholds', type=float, nargs='*', default=None, help='precision / recall distances (default: max-dist / 16, / 8, / 4)')
+    parser.add_argument('--register', action='store_true', help='register PRED onto GT by Sim(3) ICP before scoring')
+    parser.add_argument('--init', default=None, help='a text file with the 4 x 4 similarity the registration starts from')
+    parser.add_argument('--rigid', action='store_true', help='keep the scale of --init (no scale unknown)')
+    parser.add_argument('--metric', choices=('point', 'plane'), default='plane', help='the residual of the registration')
+    parser.add_argument('--register-dist', type=float, nargs='+', default=None, help='the pair gates of the stages, coarse to fine (default: 4, 2, 1 max-dist)')
     args = parser.parse_args(argv)
-    from .cloud_metrics import cloud_metrics
-    from .export import read_ply
-    clouds = [read_ply(p)['positions'] for p in (args.pred, args.gt)]
-    thresholds = [args.max_dist / 16, args.max_dist / 8, args.max_dist / 4] if args.thresholds is None else args.thresholds
-    print(json.dumps(cloud_metrics(clouds[0], clouds[1], args.max_dist, thresholds)))
-    return 0
+    if not args.register and (args.init is not None or args.rigid or args.register_dist is not None or args.metric != 'plane'):
+        parser.error('--init, --rigid, --metric and --register-dist need --register')
+    return args
 
 
 if __name__ == '__main__':

@@ -235,6 +235,27 @@ class FusedCloud:
             out = [None if a is None else a[mask] for a in fields]
         return FusedCloud(*out[:4], voxel_size=self.voxel_size, bounds=self.bounds, normals=out[4], curvature=out[5]), mask
 
+    @torch.no_grad()
+    def transform(self, S):
+        """A new cloud moved by the (4, 4) similarity S = [s R | t]: the positions by d3r_cloud_transform (fp32, cloud_metrics.transform_points),
+        the normals rotated by R and not renormalised; colours, weights, counts and curvature are kept, voxel_size is multiplied by s and
+        the bounds are those of the moved points. The voxel keys are not recomputed: the points keep their order. Arrays come back where
+        this cloud's are."""
+        from .cloud_metrics import _bounds, _device_of, similarity_parts, transform_points
+        scale = similarity_parts(S)[2]
+        on_device = isinstance(self.positions, torch.Tensor)
+        device = _device_of(self)
+        positions, normals, bounds = self.positions, self.normals, self.bounds
+        if len(self) > 0:
+            positions, normals = transform_points(self.positions, S, normals=self.normals)
+            with torch.cuda.device(device):
+                lo, hi, n_valid = _bounds(positions, device)
+            bounds = (lo, hi) if n_valid > 0 else self.bounds
+            if not on_device:
+                positions, normals = positions.cpu().numpy(), None if normals is None else normals.cpu().numpy()
+        return FusedCloud(positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size * scale, bounds=bounds, normals=normals,
+                          curvature=self.curvature)
+
     def distance_to(self, other, max_dist, to_host=True):
         """(d2, idx) of every point of this cloud in `other` (a FusedCloud or (N, 3) points) within max_dist: squared distances (+inf where
         there is none) and rows of `other` (-1); cloud_metrics.nearest_in_cloud on the GPU."""

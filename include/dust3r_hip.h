@@ -581,6 +581,35 @@ int d3r_cloud_orient_normals(int n, const float* points, float* normals, int* n_
                              const float* intrinsics, const float* world2cam, const float* centers, const int* img_h_dev, const int* img_w_dev,
                              int max_area, float tol, void* stream);
 
+/* Cloud registration (new; csrc/cloud_icp.hip): what one iteration of Sim(3) ICP needs besides d3r_cloud_nearest. Clouds and validity as
+ * above; every array DEVICE unless it says HOST (HOST arrays are read during the call).
+ * d3r_cloud_transform: M [12] HOST fp32 = [A | t] row-major, A = s R, every entry finite. out [n][3]: out_r = ((A_r0 x + A_r1 y) + A_r2 z)
+ *   + t_r, every operation a separate IEEE fp32 rounding (the row product of d3r_clean_pointcloud). A row with a non-finite coordinate gives
+ *   a row of three non-finite coordinates. normals_in / normals_out [n][3], both or neither: m_r = (R_r0 n_x + R_r1 n_y) + R_r2 n_z with
+ *   R [9] HOST fp32 row-major, finite (needed only with normals); not renormalised. out may be pts, normals_out may be normals_in.
+ * d3r_cloud_icp_sums: moved [n][3] the transformed source, moved_normals [n][3] or NULL, ref [n_ref][3], ref_normals [n_ref][3] (may be
+ *   NULL when metric = 0 and moved_normals is NULL), d2 [n] / idx [n] as d3r_cloud_nearest wrote them for `moved` in `ref`, metric 0 =
+ *   point to point, 1 = point to plane, gate > 0 with a finite fp32 square, cos_min (not NaN; ignored when moved_normals is NULL),
+ *   centre [3] HOST fp32, finite. Row i is USED when 0 <= idx[i] < n_ref, d2[i] <= gate gate (fp32 product), the point moved_i and the point
+ *   q = ref[idx[i]] are valid, for metric 1 the normal n = ref_normals[idx[i]] is finite and not (0, 0, 0), and, with moved_normals m,
+ *   ((m_x n_x + m_y n_y) + m_z n_z) >= cos_min in fp32, every operation rounded on its own. Per used row, in fp64 from the fp32 inputs:
+ *   a = moved_i - centre, y = q - centre, d = a - y, e = (n_x d_x + n_y d_y) + n_z d_z; sums of three terms are (t0 + t1) + t2.
+ *   count_out [1] DEVICE int64 = the used rows; used_out [n] DEVICE uint8 (optional) = the used mask; sums_out DEVICE fp64:
+ *   metric 0, [18]: { W = count, sum a [3], sum y [3], sum a_i y_j [3][3] row-major, sum |a|^2, sum |d|^2 }: the 17 moments of
+ *     d3r_similarity_moments with weight 1, x = a, then the squared residual.
+ *   metric 1, [36]: with J = (a_y n_z - a_z n_y, a_z n_x - a_x n_z, a_x n_y - a_y n_x, n_x, n_y, n_z, a . n): the 28 entries J_r J_c, r <= c,
+ *     of the upper triangle of sum J J^T row-major, then sum J_r e [7], then sum e e.
+ *   Each sum is the fp64 sum of the stated terms over the used rows in a fixed order: the same bytes on every run, within
+ *   2 (n - 1) 2^-53 sum |term| of any other order. workspace: d3r_cloud_icp_sums_workspace_bytes(n) bytes of DEVICE memory (0 for n <= 0).
+ * No atomics, no waiting between workgroups, no scratch. D3R_ERR_INVALID on NULL, non-positive sizes, a non-finite M, R or centre, a
+ * metric, gate or cos_min out of range, normals given on one side only; nothing is launched then. No allocation, no synchronisation. */
+int d3r_cloud_transform(int n, const float* pts, const float* M, float* out, const float* normals_in, const float* R, float* normals_out,
+                        void* stream);
+size_t d3r_cloud_icp_sums_workspace_bytes(int n);
+int d3r_cloud_icp_sums(int n, const float* moved, const float* moved_normals, int n_ref, const float* ref, const float* ref_normals, const float* d2,
+                       const int* idx, int metric, float gate, float cos_min, const float* centre, long long* count_out, double* sums_out,
+                       uint8_t* used_out, void* workspace, void* stream);
+
 /* The depth / confidence gallery of the demo (the end of get_reconstructed_scene, dust3r/demo.py:168-184) for n images in one call.
  * depth, conf [n][max_area] DEVICE fp32 (a scene's padded stacks), npix_dev [n] DEVICE int: the pixel count of each image (a count that is
  * negative or above max_area makes its image empty); what lies behind a count is neither read into a result nor written. table [257][4]
