@@ -106,6 +106,7 @@ def _load():
         'd3r_head_final': (i, [vp, i, fp, fp, fp, fp, C.c_size_t, i, i, i, i, f, f, i, vp]),
         'd3r_linear_head_post': (i, [fp, fp, fp, i, i, i, i, i, i, i, i, f, f, vp]),
         'd3r_attention': (i, [vp, vp, vp, vp, i, i, i, i, i, f, i, vp]),
+        'd3r_attention_rows': (i, [vp, vp, vp, vp, i, i, i, i, i, f, i, i, vp]),
         'd3r_upsample2x_nhwc': (i, [vp, vp, i, i, i, i, i, i, i, vp]),
         'd3r_gemm_set_trace': (i, [vp, C.c_size_t]),
         'd3r_gemm_tile_config': (i, [i, i, i, i, i, i]),

@@ -262,6 +262,16 @@ extern "C" int d3r_attention(const void* q, const void* k, const void* vt, void*
     return rc_of(launch_attention(dtype, a, (hipStream_t)stream));
 }
 
+// d3r_attention with the layout of the output rows named: `out_rows` is the dtype id of the GEMM that reads them (the engine's proj launch), so a
+// split-fp16 attention can be asked for the fp16 + fp8 activation rows its kernels store for the fp16f8 / fp16x2f8 modes.
+extern "C" int d3r_attention_rows(const void* q, const void* k, const void* vt, void* out, int B, int H, int Nq, int Nk, int ldv, float scale, int dtype,
+                                  int out_rows, void* stream) {
+    if (!q || !k || !vt || !out || out_rows < D3R_BF16 || out_rows > D3R_F16X2F8) return D3R_ERR_INVALID;
+    AttnParams a;
+    a.q = q; a.k = k; a.vt = vt; a.out = out; a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.ldv = ldv; a.scale = scale; a.out_dt = out_rows;
+    return rc_of(launch_attention(dtype, a, (hipStream_t)stream));
+}
+
 extern "C" int d3r_upsample2x_nhwc(const void* in, void* out, int B, int Hi, int Wi, int C, int Ho, int Wo, int dtype, void* stream) {
     if (!in || !out) return D3R_ERR_INVALID;
     return rc_of(launch_upsample2x(dtype, in, out, nullptr, B, Hi, Wi, C, C, Ho, Wo, (hipStream_t)stream));

@@ -573,9 +573,10 @@ def attention(q, k, vt, Nk=None, scale=0.125):
     return out
 
 
-def attention_x3(q, k, v, scale=0.125):
+def attention_x3(q, k, v, scale=0.125, out_rows='fp16x3'):
     """`attention` in the split-fp16 precision mode: q (B,H,Nq,64), k, v (B,H,Nk,64) fp32 are packed to the x3 row layout (q, k per
-    token; v transposed to (B,H,64,ldv) with the keys zero padded to a multiple of 64), the (B,Nq,H*64) result comes back as fp32."""
+    token; v transposed to (B,H,64,ldv) with the keys zero padded to a multiple of 64), the (B,Nq,H*64) result comes back as fp32.
+    out_rows='fp16f8' (or 'fp16x2f8'): the kernel stores the fp16 + fp8 activation rows of those GEMM modes (d3r_attention_rows), decoded here."""
     _lib.require_device()
     B, H, Nq, D = q.shape
     Nk = k.shape[2]
@@ -584,9 +585,14 @@ def attention_x3(q, k, v, scale=0.125):
     vt = torch.zeros((B, H, 64, ldv), dtype=torch.float32, device=q.device)
     vt[..., :Nk] = v.float().transpose(-1, -2)
     qp, kp, vp = pack_x3(q), pack_x3(k), pack_x3(vt)
-    out = torch.empty((B, Nq, H * 64 * 2), dtype=torch.float16, device=q.device)
-    check(lib.d3r_attention(ptr(qp), ptr(kp), ptr(vp), ptr(out), B, H, Nq, Nk, ldv, scale, _lib.DTYPE_F16X3, current_stream()), 'attention(x3)')
-    return unpack_x3(out)
+    if _lib.DTYPES[out_rows] == _lib.DTYPE_F16X3:
+        out = torch.empty((B, Nq, H * 64 * 2), dtype=torch.float16, device=q.device)
+        check(lib.d3r_attention(ptr(qp), ptr(kp), ptr(vp), ptr(out), B, H, Nq, Nk, ldv, scale, _lib.DTYPE_F16X3, current_stream()), 'attention(x3)')
+        return unpack_x3(out)
+    out = torch.empty((B, Nq, H * 64 * 4), dtype=torch.uint8, device=q.device)
+    check(lib.d3r_attention_rows(ptr(qp), ptr(kp), ptr(vp), ptr(out), B, H, Nq, Nk, ldv, scale, _lib.DTYPE_F16X3, _lib.DTYPES[out_rows], current_stream()),
+          f'attention(x3 -> {out_rows})')
+    return unpack_f8(out)
 
 
 def upsample2x_nhwc(x, out_hw=None):

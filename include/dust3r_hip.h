@@ -216,6 +216,11 @@ int d3r_linear_head_post(const float* feat, float* pts, float* conf, int B, int 
  * out [B][Nq][H*64]; all `dtype`   (croco Attention / CrossAttention core) */
 int d3r_attention(const void* q, const void* k, const void* vt, void* out, int B, int H, int Nq, int Nk, int ldv, float scale,
                   int dtype, void* stream);
+/* d3r_attention with the layout of the output rows named: out_rows is a D3R_DTYPE_* id, `dtype` itself or -- dtype D3R_DTYPE_F16X3 only --
+ * D3R_DTYPE_F16F8 / D3R_DTYPE_F16X2F8: out holds the fp16 + fp8 activation rows [B][Nq][H*64 * 4 bytes] that a proj GEMM of that mode reads.
+ * Any other pair is D3R_ERR_INVALID. */
+int d3r_attention_rows(const void* q, const void* k, const void* vt, void* out, int B, int H, int Nq, int Nk, int ldv, float scale,
+                       int dtype, int out_rows, void* stream);
 
 /* F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) on NHWC, output cropped to (Ho, Wo) */
 int d3r_upsample2x_nhwc(const void* in, void* out, int B, int Hi, int Wi, int C, int Ho, int Wo, int dtype, void* stream);

@@ -24,6 +24,7 @@ int main(void) {
       if (d3r_aligner_reduced_sums(NULL, &sums, &count) != D3R_ERR_INVALID) { printf("FAIL aligner_reduced_sums(NULL)\n"); ++fails; } }
     if (d3r_aligner_read_losses(NULL, 1, NULL, NULL) != D3R_ERR_INVALID) { printf("FAIL aligner_read_losses(NULL)\n"); ++fails; }
     if (d3r_layernorm(NULL, NULL, NULL, NULL, 1, 64, 1e-6f, D3R_DTYPE_F32, NULL) != D3R_ERR_INVALID) { printf("FAIL layernorm(NULL)\n"); ++fails; }
+    if (d3r_attention_rows(NULL, NULL, NULL, NULL, 1, 1, 1, 1, 64, 0.125f, D3R_DTYPE_F16X3, D3R_DTYPE_F16F8, NULL) != D3R_ERR_INVALID) { printf("FAIL attention_rows(NULL)\n"); ++fails; }
     /* the host-only gradient self test runs without a device: one edge between two 2x2 images */
     {
         const int ei[1] = {0}, ej[1] = {1};
