@@ -347,7 +347,7 @@ class BasePCOptimizer(nn.Module):
         return res
 
     @torch.no_grad()
-    def fuse(self, voxel_size=None, min_count=1, weights='conf', to_host=True, normals=False, outliers=None, k=16):
+    def fuse(self, voxel_size=None, min_count=1, weights='conf', to_host=True, normals=False, outliers=None, k=16, tracks=False, max_reproj_error=None):
         """The scene as ONE point cloud (new; the reference exports every masked pixel of every view): the masked points of all views
         (`get_masks()` at the scene's current min_conf_thr, as the GLB export) binned into voxels of `voxel_size` and averaged per voxel,
         weighted by the images' confidences (weights='conf') or equally (weights=None); `viz.fuse_points` on the scene's padded stacks,
@@ -355,8 +355,10 @@ class BasePCOptimizer(nn.Module):
         not a positive number -- NaN depth maps or focals -- while the scene has valid points: give a voxel_size then). min_count: voxels of
         fewer points are dropped. outliers=std_ratio: statistical outlier removal on the fused cloud first (`FusedCloud.remove_outliers`
         over k neighbours); normals=True: then normals from k neighbours, turned towards the cameras of this scene that see each point
-        (`FusedCloud.estimate_normals(scene=self)`; csrc/cloud_knn.hip). Returns a `viz.FusedCloud` (`.save_ply(path)`;
-        `export.write_colmap` takes it)."""
+        (`FusedCloud.estimate_normals(scene=self)`; csrc/cloud_knn.hip). tracks=True: last, on the final points, the 2-D tracks -- which
+        pixel of which image observes each point, by projection within one voxel_size -- as `cloud.tracks` (`FusedCloud.build_tracks`;
+        csrc/tracks.hip), observations landing more than max_reproj_error pixels off dropped; `export.write_colmap` then writes POINTS2D
+        and tracks. Returns a `viz.FusedCloud` (`.save_ply(path)`; `export.write_colmap` takes it)."""
         if self.imgs is None:
             raise ValueError('fuse needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
         if self.device.type != 'cuda':
@@ -373,6 +375,8 @@ class BasePCOptimizer(nn.Module):
             cloud, _ = cloud.remove_outliers(k=k, std_ratio=outliers)
         if normals:
             cloud = cloud.estimate_normals(k=k, scene=self)
+        if tracks:
+            cloud = cloud.build_tracks(self, max_error=max_reproj_error, weights=weights)
         return cloud
 
     @torch.no_grad()

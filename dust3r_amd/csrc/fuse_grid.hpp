@@ -277,26 +277,33 @@ static inline bool fuse_key_params(const float* lo, float voxel, const int* bits
     return true;
 }
 
+// Stage 2 on the stream, on buffers of the caller's (tracks.hip sorts its observations by view with it): the *n_dev (at most capacity)
+// pairs of keys[cur] / idx[cur] sorted stably by bits [0, total_bits) of the key, pass k by bits [4 k, 4 k + 4), ping-pong between the two
+// buffers; hist: [16][ceil(capacity / (SUB NT))]. Returns the buffer the sort ends in (cur itself for total_bits <= 0).
+static inline int fuse_sort_pairs(uint64_t* const (&keys)[2], int* const (&idx)[2], int* hist, const int* n_dev, int capacity, int total_bits, int cur,
+                                  hipStream_t st) {
+    const int ts = (int)fuse_tiles(capacity, SUB * NT);
+    for (int shift = 0; shift < total_bits; shift += DIGIT_BITS, cur ^= 1) {
+        hipLaunchKernelGGL(fuse_hist_kernel, dim3(fuse_blocks(ts)), dim3(NT), 0, st, keys[cur], n_dev, capacity, shift, ts, hist);
+        hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(NT), 0, st, hist, ts * DIGITS, (int*)nullptr);
+        hipLaunchKernelGGL(fuse_scatter_kernel, dim3(fuse_blocks(ts)), dim3(NT), 0, st, keys[cur], idx[cur], n_dev, capacity, shift, ts, hist, keys[cur ^ 1],
+                           idx[cur ^ 1]);
+    }
+    return cur;
+}
+
 // Stages 1 and 2 on the stream: a (pts, mask, weight, img_h, img_w, row, key set by the caller) keyed and compacted into w, then sorted.
 // Returns the buffer the sort ends in: w.keys[cur] / w.idx[cur] hold the w.n_dev[0] sorted pairs.
 static inline int fuse_key_and_sort(FlagArgs& a, const FuseWorkspace& w, int n_views, int capacity, int total_bits, hipStream_t st) {
     const int tpv = (int)fuse_tiles(a.row, NT);
     const long long t1 = (long long)n_views * tpv;
-    const int ts = (int)fuse_tiles(capacity, SUB * NT);
     a.tiles_per_view = tpv; a.sorted = nullptr; a.n_dev = w.n_dev; a.cap = capacity;
     // 1. key and compact
     hipLaunchKernelGGL((fuse_flag_kernel<KEYS, false>), dim3(fuse_blocks(t1)), dim3(NT), 0, st, a, t1, w.tile_cnt, w.keys[0], w.idx[0]);
     hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(NT), 0, st, w.tile_cnt, (int)t1, w.n_dev);
     hipLaunchKernelGGL((fuse_flag_kernel<KEYS, true>), dim3(fuse_blocks(t1)), dim3(NT), 0, st, a, t1, w.tile_cnt, w.keys[0], w.idx[0]);
     // 2. the sort: pass k orders by bits [4 k, 4 k + 4) of the key
-    int cur = 0;
-    for (int shift = 0; shift < total_bits; shift += DIGIT_BITS, cur ^= 1) {
-        hipLaunchKernelGGL(fuse_hist_kernel, dim3(fuse_blocks(ts)), dim3(NT), 0, st, w.keys[cur], w.n_dev, capacity, shift, ts, w.hist);
-        hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(NT), 0, st, w.hist, ts * DIGITS, (int*)nullptr);
-        hipLaunchKernelGGL(fuse_scatter_kernel, dim3(fuse_blocks(ts)), dim3(NT), 0, st, w.keys[cur], w.idx[cur], w.n_dev, capacity, shift, ts, w.hist,
-                           w.keys[cur ^ 1], w.idx[cur ^ 1]);
-    }
-    return cur;
+    return fuse_sort_pairs(w.keys, w.idx, w.hist, w.n_dev, capacity, total_bits, 0, st);
 }
 
 // Stage 3 on the stream: the segment heads of the sorted keys w.keys[cur], into the index buffer the sort left free (returned); their

@@ -361,6 +361,11 @@ def get_args_parser():
                              '(default: the median pixel footprint)')
     parser.add_argument('--ply', action='store_true', default=False, help='write the fused cloud as outdir/scene.ply (implies --fuse)')
     parser.add_argument('--colmap', action='store_true', default=False, help='write the fused cloud, cameras and images as a COLMAP model in outdir/colmap (implies --fuse)')
+    parser.add_argument('--colmap_tracks', action='store_true', default=False,
+                        help='with --colmap: also write the 2-D tracks (POINTS2D per image, the track and mean reprojection error per point; '
+                             'FusedCloud.build_tracks) and their statistics into cameras.json under "tracks"')
+    parser.add_argument('--max_reproj_error', type=float, default=None, metavar='PX',
+                        help='with --colmap_tracks: drop observations whose projection lands more than PX pixels from the observing pixel')
     parser.add_argument('--fuse_normals', action='store_true', default=False,
                         help='estimate normals of the fused cloud, turned towards the cameras, and write them into scene.ply (implies --fuse)')
     parser.add_argument('--fuse_outliers', type=float, default=None, metavar='STD_RATIO',
@@ -413,26 +418,40 @@ def write_cameras(outdir, scene):
     return name
 
 
-def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, ply=True, colmap=False, normals=False, outliers=None):
+def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, ply=True, colmap=False, normals=False, outliers=None, tracks=False,
+                max_reproj_error=None):
     """outdir/scene.ply and / or outdir/colmap of the scene's fused cloud (scene.fuse; export.write_ply / write_colmap), with the mask of
-    get_3D_model_from_scene: min_conf_thr through the scene's confidence transform, the sky on request; normals / outliers as for scene.fuse.
+    get_3D_model_from_scene: min_conf_thr through the scene's confidence transform, the sky on request; normals / outliers / tracks /
+    max_reproj_error as for scene.fuse. With tracks, their `stats()` are added to outdir/cameras.json (when it is there) under "tracks".
     Returns the file names."""
     from .export import write_colmap
     if mask_sky:
         scene = scene.mask_sky()
     scene.min_conf_thr = float(scene.conf_trf(torch.tensor(min_conf_thr)))
-    cloud = scene.fuse(voxel_size=voxel_size or None, normals=normals, outliers=outliers)
+    cloud = scene.fuse(voxel_size=voxel_size or None, normals=normals, outliers=outliers, tracks=tracks, max_reproj_error=max_reproj_error)
     written = []
     if ply:
         written.append(cloud.save_ply(os.path.join(outdir, 'scene.ply')))
     if colmap:
         written += write_colmap(os.path.join(outdir, 'colmap'), scene, cloud)
+    cameras = os.path.join(outdir, 'cameras.json')
+    if tracks and os.path.isfile(cameras):
+        with open(cameras) as f:
+            doc = json.load(f)
+        doc['tracks'] = cloud.tracks.stats()
+        with open(cameras, 'w') as f:
+            json.dump(doc, f, indent=1)
     return written
 
 
 def main(argv=None):
     from .model import AsymmetricCroCo3DStereo
-    args = get_args_parser().parse_args(argv)
+    parser = get_args_parser()
+    args = parser.parse_args(argv)
+    if args.colmap_tracks and not args.colmap:
+        parser.error('--colmap_tracks needs --colmap')
+    if args.max_reproj_error is not None and not args.colmap_tracks:
+        parser.error('--max_reproj_error needs --colmap_tracks')
     files = _input_files(args.images)
     if not files:
         raise SystemExit(f'no image in {args.images}')
@@ -448,7 +467,8 @@ def main(argv=None):
                                     mask_sky=args.mask_sky, clean_depth=args.clean_depth, transparent_cams=args.transparent_cams, silent=args.silent)
     if wants_fuse(args):
         written += write_fused(args.outdir, scene, voxel_size=args.fuse, min_conf_thr=args.min_conf_thr, mask_sky=args.mask_sky,
-                               ply=args.ply or not args.colmap, colmap=args.colmap, normals=args.fuse_normals, outliers=args.fuse_outliers)
+                               ply=args.ply or not args.colmap, colmap=args.colmap, normals=args.fuse_normals, outliers=args.fuse_outliers,
+                               tracks=args.colmap_tracks, max_reproj_error=args.max_reproj_error)
     if not args.silent:
         print('(wrote', len(written), 'files to', args.outdir, ')')
     return 0

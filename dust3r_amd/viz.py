@@ -153,12 +153,13 @@ class FusedCloud:
     with to_host=False. voxel_size, origin (3,) float32 (the minimum of the fused points: voxel (i, j, k) starts at origin + voxel_size (i, j,
     k)) and bounds = (min, max) of the fused points, (+inf, -inf) for an empty cloud."""
 
-    def __init__(self, positions, colors, weight, count, voxel_size, bounds, normals=None, curvature=None):
+    def __init__(self, positions, colors, weight, count, voxel_size, bounds, normals=None, curvature=None, tracks=None):
         self.positions, self.colors, self.weight, self.count = positions, colors, weight, count
         self.voxel_size = float(voxel_size)
         self.bounds = bounds
         self.origin = bounds[0]
         self.normals, self.curvature = normals, curvature      # (M, 3) float32 and (M,) float32 of `estimate_normals`, else None
+        self.tracks = tracks                                   # the `CloudTracks` of `build_tracks`, else None
 
     def __len__(self):
         return len(self.positions)
@@ -187,7 +188,8 @@ class FusedCloud:
         min_neighbors neighbours gets the zero normal and NaN. Without a scene the sign makes the component of largest magnitude positive;
         with a scene (the aligned scene the cloud was fused from) every normal is turned towards the cameras that see its point:
         visible = it projects onto a pixel whose depth agrees within tol (relative); the vote is weighted by the pixels' confidences, and
-        falls back to all cameras for a point no view sees (cloud_metrics.orient_normals). Arrays come back where this cloud's are."""
+        falls back to all cameras for a point no view sees (cloud_metrics.orient_normals). Arrays come back where this cloud's are. The
+        points are the same ones, so the cloud's tracks, when it has them, are kept."""
         from .cloud_metrics import _device_of, _points, cloud_normals, default_knn_r0, k_nearest, orient_normals
         on_device = isinstance(self.positions, torch.Tensor)
         device = scene.device if scene is not None and not on_device else _device_of(self)
@@ -204,7 +206,8 @@ class FusedCloud:
                                tol=tol)
         if not on_device:
             normals, curvature = normals.cpu().numpy(), curvature.cpu().numpy()
-        return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=normals, curvature=curvature)
+        return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=normals, curvature=curvature,
+                          tracks=self.tracks)
 
     @torch.no_grad()
     def remove_outliers(self, k=16, std_ratio=2.0, max_dist=None):
@@ -213,7 +216,8 @@ class FusedCloud:
         means (cloud_metrics.outlier_threshold: host fp64 from three sums reduced on the device; the fp32 means widened to fp64 for the
         comparison). Open3D's remove_statistical_outlier with the search truncated at max_dist: a point with fewer than k neighbours
         there is an outlier. keep: (M,) bool. Normals and curvature, when present, are carried along. One host synchronisation more
-        than `k_nearest` (the three sums)."""
+        than `k_nearest` (the three sums). Tracks are DROPPED (they index the points before the removal): call `build_tracks` on the
+        result, as `scene.fuse(tracks=True)` does."""
         from .cloud_metrics import _device_of, _points, default_knn_r0, k_nearest, knn_mean_distances, outlier_threshold
         on_device = isinstance(self.positions, torch.Tensor)
         device = _device_of(self)
@@ -240,7 +244,7 @@ class FusedCloud:
         """A new cloud moved by the (4, 4) similarity S = [s R | t]: the positions by d3r_cloud_transform (fp32, cloud_metrics.transform_points),
         the normals rotated by R and not renormalised; colours, weights, counts and curvature are kept, voxel_size is multiplied by s and
         the bounds are those of the moved points. The voxel keys are not recomputed: the points keep their order. Arrays come back where
-        this cloud's are."""
+        this cloud's are. The result has no tracks: the scene's cameras no longer see the moved points where the tracks say."""
         from .cloud_metrics import _bounds, _device_of, similarity_parts, transform_points
         scale = similarity_parts(S)[2]
         on_device = isinstance(self.positions, torch.Tensor)
@@ -261,6 +265,28 @@ class FusedCloud:
         there is none) and rows of `other` (-1); cloud_metrics.nearest_in_cloud on the GPU."""
         from .cloud_metrics import nearest_in_cloud
         return nearest_in_cloud(self, other, max_dist, to_host=to_host)
+
+    @torch.no_grad()
+    def build_tracks(self, scene, max_dist=None, max_error=None, weights='conf'):
+        """A new cloud carrying `.tracks` (a `CloudTracks`): which pixel of which image of `scene` (the aligned scene the cloud was fused
+        from) observes each point, by projection (`cloud_tracks`; csrc/tracks.hip). max_dist: how far from the point the observing pixel's
+        own 3-D point may lie, default the cloud's voxel_size; max_error: observations whose projection lands farther than this many
+        pixels from the chosen pixel are dropped (default: none is). weights: 'conf' or None as given to `scene.fuse()`, so that the
+        same pixels count as valid. The tracks' arrays come back where this cloud's are."""
+        if weights not in ('conf', None):
+            raise ValueError(f"build_tracks: weights is 'conf' or None, got {weights!r}")
+        if max_dist is None:
+            if not (math.isfinite(self.voxel_size) and self.voxel_size > 0):
+                if len(self) > 0:
+                    raise ValueError(f'the cloud has no voxel size ({self.voxel_size!r}): give max_dist')
+                max_dist = 0.0
+            else:
+                max_dist = self.voxel_size
+        tracks = cloud_tracks(self.positions, scene.get_pts3d(raw=True), scene.get_masks(raw=True), scene._im_conf if weights == 'conf' else None,
+                              scene.get_intrinsics(), scene.get_im_poses(), scene.imshapes, max_dist, max_error=max_error, device=scene.device,
+                              to_host=not isinstance(self.positions, torch.Tensor))
+        return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=self.normals,
+                          curvature=self.curvature, tracks=tracks)
 
 
 def check_voxel_size(voxel_size):
@@ -365,6 +391,166 @@ def fuse_points(imgs, pts3d, masks, weights, voxel_size, device, min_count=1, to
         if to_host:
             out = [t.cpu().numpy() for t in out]
     return FusedCloud(*out, voxel_size=voxel, bounds=(lo, hi))
+
+
+# ---- 2-D tracks of a cloud -------------------------------------------------------------------------------------------------------------
+class CloudTracks:
+    """The observations of a cloud's M points in the n images of a scene (`cloud_tracks`; include/dust3r_hip.h, d3r_cloud_tracks_count /
+    d3r_cloud_tracks_fill, has the definition). T observations, numpy arrays, or torch tensors on the device with to_host=False:
+    point_offsets (M + 1,) int32: point j owns observations [point_offsets[j], point_offsets[j + 1]), its TRACK, in ascending view order;
+    view (T,) int32, pixel (T,) int32 (e = y W_view + x), err2 (T,) float64 (the squared distance in pixels between the point's projection
+    and that pixel); image_offsets (n + 1,) int32 and image_obs (T,) int32: image v's 2-D points are the observations
+    image_obs[image_offsets[v] : image_offsets[v + 1]], in ascending point index; point2d (T,) int32: the position of observation k inside
+    its image's list. shapes: the images' (H, W)."""
+
+    def __init__(self, point_offsets, view, pixel, point2d, err2, image_offsets, image_obs, shapes):
+        self.point_offsets, self.view, self.pixel, self.point2d, self.err2 = point_offsets, view, pixel, point2d, err2
+        self.image_offsets, self.image_obs = image_offsets, image_obs
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+
+    def __len__(self):
+        return len(self.view)
+
+    @property
+    def n_points(self):
+        return len(self.point_offsets) - 1
+
+    @property
+    def lengths(self):
+        """(M,) the track length of every point"""
+        return self.point_offsets[1:] - self.point_offsets[:-1]
+
+    @property
+    def point_index(self):
+        """(T,) the point of every observation"""
+        if isinstance(self.view, torch.Tensor):
+            return torch.repeat_interleave(torch.arange(self.n_points, device=self.view.device), self.lengths.long())
+        return np.repeat(np.arange(self.n_points), self.lengths)
+
+    def xy(self):
+        """(T, 2) the pixel (x, y) of every observation, the integers COLMAP's POINTS2D get (same dtype as `pixel`)"""
+        if isinstance(self.view, torch.Tensor):
+            widths = torch.tensor([w for _, w in self.shapes], dtype=self.pixel.dtype, device=self.pixel.device)[self.view.long()]
+            return torch.stack([self.pixel % widths, torch.div(self.pixel, widths, rounding_mode='floor')], dim=1)
+        widths = np.array([w for _, w in self.shapes], dtype=self.pixel.dtype)[self.view]
+        return np.stack([self.pixel % widths, self.pixel // widths], axis=1) if len(widths) else np.zeros((0, 2), self.pixel.dtype)
+
+    def point_error(self):
+        """(M,) float64: the mean over a point's track of sqrt(err2), COLMAP's per-point error in pixels; -1 for a point without an
+        observation. numpy: the sums run in track order (np.bincount); tensors: differences of one cumulative sum (deterministic on
+        the device, where an index_add would not be), which may differ from the former in the last bits."""
+        lengths = self.lengths
+        if isinstance(self.view, torch.Tensor):
+            run = torch.cat([torch.zeros(1, dtype=torch.float64, device=self.err2.device), torch.cumsum(torch.sqrt(self.err2), 0)])
+            sums = run[self.point_offsets[1:].long()] - run[self.point_offsets[:-1].long()]
+            return torch.where(lengths > 0, sums / lengths.clamp(min=1), torch.full_like(sums, -1.0))
+        sums = np.bincount(self.point_index, weights=np.sqrt(self.err2), minlength=self.n_points)
+        return np.where(lengths > 0, sums / np.maximum(lengths, 1), -1.0)
+
+    def stats(self):
+        """dict of plain numbers: observations, mean_track_length (over all points), unobserved (the share of points without an
+        observation), mean_error / median_error (sqrt(err2) over the observations, pixels; None without observations) and
+        observations_per_image (a list)."""
+        err = np.sqrt(_to_numpy(self.err2))
+        lengths = _to_numpy(self.lengths)
+        per_image = np.diff(_to_numpy(self.image_offsets)).tolist()
+        m = max(self.n_points, 1)
+        return dict(observations=int(len(err)), mean_track_length=float(len(err) / m), unobserved=float((lengths == 0).sum() / m),
+                    mean_error=float(err.mean()) if len(err) else None, median_error=float(np.median(err)) if len(err) else None,
+                    observations_per_image=[int(v) for v in per_image])
+
+
+def track_cameras(intrinsics, cam2world):
+    """(n, 16) float64, per view what the tracks project with: the world-to-camera rows R (9, row-major) and t (3) of `export.colmap_pose`
+    (the pose exactly as the COLMAP model holds it), then fx, fy, cx, cy of the (n, 3, 3) intrinsics."""
+    from .export import colmap_pose, quat_to_rotmat
+    K = np.asarray(_to_numpy(intrinsics), dtype=np.float64).reshape(-1, 3, 3)
+    c2w = np.asarray(_to_numpy(cam2world), dtype=np.float64).reshape(-1, 4, 4)
+    if len(K) != len(c2w):
+        raise ValueError(f'track_cameras: {len(K)} intrinsics, {len(c2w)} poses')
+    table = np.empty((len(K), 16), dtype=np.float64)
+    for i in range(len(K)):
+        q, t = colmap_pose(c2w[i])
+        table[i, :9], table[i, 9:12] = quat_to_rotmat(q).reshape(9), t
+        table[i, 12:] = K[i, 0, 0], K[i, 1, 1], K[i, 0, 2], K[i, 1, 2]
+    return table
+
+
+@torch.no_grad()
+def cloud_tracks(positions, pts3d, masks, weights, intrinsics, cam2world, shapes, max_dist, max_error=None, device=None, to_host=True, timing=None):
+    """The 2-D tracks of a cloud in the views it was fused from, on the GPU (csrc/tracks.hip): point j is observed in view v at the pixel,
+    among the 3 x 3 around its rounded projection, whose own 3-D point is valid (the rule of `fuse_points`) and nearest to it within
+    max_dist; the observation carries the squared distance in pixels between the projection and that pixel, and is dropped when that
+    exceeds max_error^2. By projection, not voxel membership: at the default voxel size nearly every voxel holds one pixel, so membership
+    tracks would have length 1. include/dust3r_hip.h (d3r_cloud_tracks_count) states the rule operation by operation;
+    tests/test_tracks_cpu.py restates it in numpy, and the two agree bit for bit.
+
+    positions (M, 3) float32, array or tensor. pts3d, masks, weights: per view the (H, W, 3) / (H, W) maps, or the ready padded stacks of a
+    scene; weights may be None. intrinsics (n, 3, 3), cam2world (n, 4, 4) (`track_cameras`), shapes: the views' (H, W). max_dist >= 0,
+    squared in float32. Returns a `CloudTracks`. One host synchronisation: the number of observations, to size the outputs. timing
+    (optional): a dict that receives the device milliseconds of the two calls under 'count' and 'fill' (tools/tracks_speed.py)."""
+    _lib.require_device()
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    n = len(shapes)
+    if n == 0 or len(pts3d) != n or len(masks) != n or (weights is not None and len(weights) != n):
+        raise ValueError(f'cloud_tracks: {n} shapes, {len(pts3d)} pointmaps, {len(masks)} masks, {None if weights is None else len(weights)} weight maps')
+    with np.errstate(over='ignore'):
+        r = np.float32(max_dist)
+        r2 = r * r
+    if not (np.isfinite(r2) and r >= 0):
+        raise ValueError(f'cloud_tracks: max_dist = {max_dist!r} must be >= 0 with a finite float32 square')
+    if max_error is not None and not float(max_error) >= 0:
+        raise ValueError(f'cloud_tracks: max_error = {max_error!r} must be >= 0')
+    from .cloud_metrics import _points
+    P = _points(positions, device, 'cloud_tracks')
+    m = len(P)
+    row = next((x.shape[1] for x, nd in ((pts3d, 3), (masks, 2), (weights, 2)) if isinstance(x, torch.Tensor) and x.ndim == nd), None)
+    pts = pad_views(pts3d, device, torch.float32, (3,), row, shapes, 'cloud_tracks: pointmap')
+    mask = pad_views(masks, device, torch.uint8, (), row, shapes, 'cloud_tracks: mask')
+    wgt = None if weights is None else pad_views(weights, device, torch.float32, (), row, shapes, 'cloud_tracks: weight')
+    row = pts.shape[1]
+    if n * row >= 2 ** 31:
+        raise ValueError(f'cloud_tracks: {n} rows of {row} do not fit 31-bit pixel indices (fewer views per call)')
+    cams = torch.from_numpy(track_cameras(intrinsics, cam2world)).to(device)
+    if len(cams) != n:
+        raise ValueError(f'cloud_tracks: {n} shapes, {len(cams)} cameras')
+    hs, ws, _ = shape_tables(shapes, device)
+    thr = (0, 0.0) if max_error is None else (1, float(max_error) ** 2)
+    point_off = torch.zeros((m + 1,), dtype=torch.int32, device=device)
+    seen = torch.empty((max(m, 1), (n + 31) // 32), dtype=torch.int32, device=device)      # one bit per (point, view), from the first pass to the second
+    total = 0
+    with torch.cuda.device(device):
+        events = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing is not None else None
+        args = (n, ptr(pts), ptr(mask), ptr(wgt), ptr(hs), ptr(ws), row, m, ptr(P), ptr(cams), float(r2), thr[0], thr[1])
+        if m > 0:
+            total_dev = torch.empty((1,), dtype=torch.int64, device=device)
+            if events:
+                events[0].record()
+            check(lib.d3r_cloud_tracks_count(*args, ptr(point_off), ptr(seen), ptr(total_dev), current_stream()), 'cloud_tracks_count')
+            if events:
+                events[1].record()
+            total = int(total_dev.cpu())
+            if total >= 2 ** 31:
+                raise ValueError(f'cloud_tracks: {total} observations do not fit 31-bit indices (fewer points or views per call)')
+        cap = max(total, 1)
+        view, pixel, point2d, image_obs = (torch.empty((cap,), dtype=torch.int32, device=device) for _ in range(4))
+        err2 = torch.empty((cap,), dtype=torch.float64, device=device)
+        image_off = torch.zeros((n + 1,), dtype=torch.int32, device=device)
+        if m > 0:
+            work = torch.empty(int(lib.d3r_cloud_tracks_workspace_bytes(cap)), dtype=torch.uint8, device=device)
+            if events:
+                events[2].record()
+            check(lib.d3r_cloud_tracks_fill(*args, ptr(point_off), ptr(seen), total, cap, ptr(view), ptr(pixel), ptr(err2), ptr(point2d), ptr(image_off), ptr(image_obs),
+                                            ptr(work), current_stream()), 'cloud_tracks_fill')
+            if events:
+                events[3].record()
+                events[3].synchronize()
+                timing['count'], timing['fill'] = events[0].elapsed_time(events[1]), events[2].elapsed_time(events[3])
+        out = [point_off, view[:total], pixel[:total], point2d[:total], err2[:total], image_off, image_obs[:total]]
+        if to_host:
+            out = [t.cpu().numpy() for t in out]
+    return CloudTracks(*out, shapes=shapes)
 
 
 def _rot_z(deg):

@@ -615,6 +615,49 @@ int d3r_cloud_icp_sums(int n, const float* moved, const float* moved_normals, in
                        const int* idx, int metric, float gate, float cos_min, const float* centre, long long* count_out, double* sums_out,
                        uint8_t* used_out, void* workspace, void* stream);
 
+/* 2-D tracks of a cloud in the views of a scene (new; csrc/tracks.hip): which pixel of which view observes each point, by projection.
+ * pts [n][row][3], mask [n][row], weight [n][row] or NULL, img_h / img_w [n]: the scene's stacks as for d3r_fuse_bounds (n * row <= 2^31 - 1,
+ * 1 <= n <= 65535; what lies behind a view's h w elements is never read; a view whose h w exceeds row is empty). positions [M][3] DEVICE
+ * fp32, 1 <= M <= 2^31 - 2. cams [n][16] DEVICE fp64: per view the world-to-camera rows R (9, row-major), t (3), then fx, fy, cx, cy.
+ * r2 a finite fp32 >= 0 (the squared search distance, formed by the caller as the fp32 product max_dist max_dist); has_thr != 0: thr2 >= 0
+ * (the squared error threshold, fp64).
+ * THE RULE for point c = (x, y, z) and view v; every fp64 and fp32 operation is rounded on its own (no contraction), in the order written:
+ *   1. X_r = ((R[r][0] x + R[r][1] y) + R[r][2] z) + t[r] in fp64, x, y, z widened exactly. Rejected unless X_2 > 0 (a NaN is rejected).
+ *   2. u = fx (X_0 / X_2) + cx, w = fy (X_1 / X_2) + cy; iu = floor(u + 0.5), iw = floor(w + 0.5). Rejected unless 0 <= iu < W_v and
+ *      0 <= iw < H_v, compared in fp64 before any conversion to int.
+ *   3. The candidates are the pixels (iu + a, iw + b), a, b in {-1, 0, 1}, that lie inside the image, are VALID (d3r_fuse_bounds: mask
+ *      nonzero, finite point, finite weight > 0 when weights are given) and whose point p has fp32 d2 = (dx dx + dy dy) + dz dz <= r2,
+ *      dx = p_x - x, ....
+ *   4. The candidate of least d2 is chosen; among equal d2 the lowest pixel index e = y W_v + x.
+ *   5. No candidate: no observation. Otherwise the observation is (v, e) with e2 = (u - x) (u - x) + (w - y) (w - y) in fp64, (x, y) the
+ *      chosen pixel; with has_thr it is dropped when e2 > thr2.
+ *   The 2-D point of an observation is the pixel (x, y) itself, in the convention of the PINHOLE parameters (fx, fy, cx, cy) given: no
+ *   half-pixel shift is applied on either side.
+ * d3r_cloud_tracks_count: point_off_out [M + 1] DEVICE int32 = the exclusive scan of the points' observation counts (point_off[M] = T mod
+ *   2^32), seen_out [M][ceil(n / 32)] DEVICE uint32: bit v & 31 of word v >> 5 of row j is set when view v observes point j, total_out [1]
+ *   DEVICE int64 = T, summed in 64 bits. The caller reads T back, sizes the outputs and calls
+ * d3r_cloud_tracks_fill with the SAME inputs, point_off and seen as written (the second pass walks only the views whose bit is set, so it
+ *   costs what the observations cost, not what the M n pairs cost), total = T and capacity >= max(T, 1) rows in every output:
+ *   view_out, pixel_out [capacity] int32 and err2_out [capacity] fp64: observation k in [point_off[j], point_off[j + 1]) belongs to point
+ *     j; a point's observations are in ascending view order;
+ *   image_obs_out [capacity] int32: the observations ordered by view, then by k (a stable radix sort over bit_length(n - 1) bits: inside
+ *     an image ascending point index); image_off_out [n + 1] int32: image v owns image_obs[image_off[v], image_off[v + 1]);
+ *   point2d_out [capacity] int32: point2d[k] = the position of observation k inside its image's list.
+ *   Two points may claim one pixel: two entries. The first T rows are written. workspace: d3r_cloud_tracks_workspace_bytes(capacity) bytes
+ *   of DEVICE memory (0 for capacity <= 0).
+ * One writer per output slot: no atomics, no waiting between workgroups, no scratch; integer results and fp64 + * / floor only, so the
+ * same bytes on every run and the bytes of the numpy restatement (tests/test_tracks_cpu.py). D3R_ERR_INVALID on NULL, n outside
+ * [1, 65535], n * row > 2^31 - 1, M <= 0, a negative or non-finite r2, a negative or NaN thr2, total < 0, total > capacity or
+ * total > 2^31 - 1; nothing is launched then. No allocation, no synchronisation. */
+size_t d3r_cloud_tracks_workspace_bytes(int capacity);
+int d3r_cloud_tracks_count(int n_views, const float* pts, const uint8_t* mask, const float* weight, const int* img_h_dev, const int* img_w_dev, int row,
+                           int n_points, const float* positions, const double* cams_dev, float r2, int has_thr, double thr2, int* point_off_out,
+                           uint32_t* seen_out, long long* total_out, void* stream);
+int d3r_cloud_tracks_fill(int n_views, const float* pts, const uint8_t* mask, const float* weight, const int* img_h_dev, const int* img_w_dev, int row,
+                          int n_points, const float* positions, const double* cams_dev, float r2, int has_thr, double thr2, const int* point_off,
+                          const uint32_t* seen, long long total, int capacity, int* view_out, int* pixel_out, double* err2_out, int* point2d_out, int* image_off_out,
+                          int* image_obs_out, void* workspace, void* stream);
+
 /* The depth / confidence gallery of the demo (the end of get_reconstructed_scene, dust3r/demo.py:168-184) for n images in one call.
  * depth, conf [n][max_area] DEVICE fp32 (a scene's padded stacks), npix_dev [n] DEVICE int: the pixel count of each image (a count that is
  * negative or above max_area makes its image empty); what lies behind a count is neither read into a result nor written. table [257][4]
