@@ -1,6 +1,6 @@
 """Cloud-to-cloud metrics on the GPU (new; the reference's paper reports them, its code has none): accuracy, completeness, overall (Chamfer),
-precision / recall / F-score at a distance, of one cloud against another -- csrc/cloud_nn.hip, C ABI `d3r_cloud_grid_build` /
-`d3r_cloud_nearest` / `d3r_cloud_distance_stats` (include/dust3r_hip.h).
+precision / recall / F-score at a distance, of one cloud against another -- csrc/cloud_nn.hip (the grid, the statistics) and
+csrc/cloud_knn.hip (the search), C ABI `d3r_cloud_grid_build` / `d3r_cloud_nearest` / `d3r_cloud_distance_stats` (include/dust3r_hip.h).
 
     d2, idx = nearest_in_cloud(query, ref, max_dist)        # the truncated exact nearest neighbour of every query point
     m = cloud_metrics(pred, gt, max_dist, thresholds)       # the dict of the metrics
@@ -127,6 +127,62 @@ def _bounds(pts, device):
     return b[:3].copy(), b[3:].copy(), int(host[3])
 
 
+class _ReferenceGrids:
+    """The radius ladder over a reference cloud R that does not move, and the only caller of d3r_cloud_grid_build / d3r_cloud_nearest /
+    d3r_cloud_knn: rung j searches at radii[j] on a grid of cell cell_factor radii[j], from the second on only for the queries still open.
+    k: None for the nearest neighbour (d2 / idx (N,)), else the k nearest (N, k), with exclude_self; evals as `nearest_in_cloud`'s.
+    rebuild=False: a workspace per rung, its grid built once here (`register_clouds`: many searches on the same grids). rebuild=True: ONE
+    workspace, every rung's grid built in it before its search (one search; the same bytes, tests compare the two)."""
+
+    def __init__(self, R, lo, hi, radii, n_query, rebuild=False, k=None, exclude_self=False, cell_factor=1.0, evals=None):
+        self.R, self.rebuild, self.k, self.exclude_self, self.evals = R, rebuild, k, bool(exclude_self), evals
+        self.lo_c = (C.c_float * 3)(*lo.tolist())
+        size = int(lib.d3r_cloud_grid_workspace_bytes(len(R), n_query))
+        if size == 0:
+            raise ValueError(f'clouds of {n_query} and {len(R)} points are too large')
+        work = torch.empty(size, dtype=torch.uint8, device=R.device) if rebuild else None
+        self.rungs = []
+        for r in radii:
+            cell, bits = grid_cell(lo, hi, _radius_f32(float(r) * cell_factor, 'cell'))
+            rung = (float(r), float(cell), (C.c_int * 3)(*bits), work if rebuild else torch.empty(size, dtype=torch.uint8, device=R.device))
+            self.rungs.append(rung)
+            if not rebuild:
+                self._build(rung)
+
+    def _build(self, rung):
+        r, cell, bits_c, work = rung
+        check(lib.d3r_cloud_grid_build(len(self.R), ptr(self.R), self.lo_c, cell, bits_c, ptr(work), current_stream()), 'cloud_grid_build')
+
+    def search(self, Q, d2, idx):
+        """the ladder for the queries Q (at most n_query) into d2 / idx"""
+        for j, rung in enumerate(self.rungs):
+            if self.rebuild:
+                self._build(rung)
+            r, cell, bits_c, work = rung
+            out = (ptr(d2), ptr(idx), ptr(self.evals), ptr(work), current_stream())
+            if self.k is None:
+                check(lib.d3r_cloud_nearest(len(self.R), len(Q), ptr(Q), r, self.lo_c, cell, bits_c, int(j > 0), *out), 'cloud_nearest')
+            else:
+                check(lib.d3r_cloud_knn(len(self.R), len(Q), ptr(Q), self.k, r, self.lo_c, cell, bits_c, int(self.exclude_self), int(j > 0), *out),
+                      'cloud_knn')
+
+
+def _ladder_search(Q, R, radii, k, to_host, **how):
+    """(d2, idx) of one ladder of the device clouds Q in R: what `nearest_in_cloud` (k None) and `k_nearest` return; `how` as _ReferenceGrids"""
+    nq, device = len(Q), Q.device
+    shape = (nq,) if k is None else (nq, k)
+    d2 = torch.full(shape, float('inf'), dtype=torch.float32, device=device)
+    idx = torch.full(shape, -1, dtype=torch.int32, device=device)
+    if nq > 0 and len(R) > 0:
+        with torch.cuda.device(device):
+            lo, hi, n_valid = _bounds(R, device)
+            if n_valid > 0:
+                _ReferenceGrids(R, lo, hi, radii, nq, rebuild=True, k=k, **how).search(Q, d2, idx)
+    if to_host:
+        return d2.cpu().numpy(), idx.cpu().numpy()
+    return d2, idx
+
+
 @torch.no_grad()
 def nearest_in_cloud(query, ref, max_dist, r0=None, to_host=True, evals=None):
     """(d2, idx) of every query point in `ref` within max_dist, as defined at the top: d2 (N,) float32 squared distances (+inf where none),
@@ -140,27 +196,7 @@ def nearest_in_cloud(query, ref, max_dist, r0=None, to_host=True, evals=None):
         r0 = default_r0(ref, max_dist)
     radii = ladder_radii(min(float(_radius_f32(r0, 'r0')), float(max_dist)), max_dist)
     Q, R = _points(query, device, 'query'), _points(ref, device, 'ref')
-    nq, nr = len(Q), len(R)
-    d2 = torch.full((nq,), float('inf'), dtype=torch.float32, device=device)
-    idx = torch.full((nq,), -1, dtype=torch.int32, device=device)
-    if nq > 0 and nr > 0:
-        with torch.cuda.device(device):
-            lo, hi, n_valid = _bounds(R, device)
-            if n_valid > 0:
-                size = int(lib.d3r_cloud_grid_workspace_bytes(nr, nq))
-                if size == 0:
-                    raise ValueError(f'nearest_in_cloud: clouds of {nq} and {nr} points are too large')
-                work = torch.empty(size, dtype=torch.uint8, device=device)
-                lo_c = (C.c_float * 3)(*lo.tolist())
-                for k, r in enumerate(radii):
-                    cell, bits = grid_cell(lo, hi, r)
-                    bits_c = (C.c_int * 3)(*bits)
-                    check(lib.d3r_cloud_grid_build(nr, ptr(R), lo_c, float(cell), bits_c, ptr(work), current_stream()), 'cloud_grid_build')
-                    check(lib.d3r_cloud_nearest(nr, nq, ptr(Q), float(r), lo_c, float(cell), bits_c, int(k > 0), ptr(d2), ptr(idx), ptr(evals),
-                                                ptr(work), current_stream()), 'cloud_nearest')
-    if to_host:
-        return d2.cpu().numpy(), idx.cpu().numpy()
-    return d2, idx
+    return _ladder_search(Q, R, radii, None, to_host, evals=evals)
 
 
 @torch.no_grad()
@@ -185,29 +221,9 @@ def k_nearest(query, ref, k, max_dist, exclude_self=False, r0=None, to_host=True
     radii = ladder_radii(min(float(_radius_f32(r0, 'r0')), float(max_dist)), max_dist, step=step)
     Q = _points(query, device, 'query')
     R = Q if query is ref else _points(ref, device, 'ref')
-    nq, nr = len(Q), len(R)
-    if exclude_self and nq != nr:
-        raise ValueError(f'k_nearest: exclude_self needs query is ref, or clouds of equal length; got {nq} and {nr} points')
-    d2 = torch.full((nq, k), float('inf'), dtype=torch.float32, device=device)
-    idx = torch.full((nq, k), -1, dtype=torch.int32, device=device)
-    if nq > 0 and nr > 0:
-        with torch.cuda.device(device):
-            lo, hi, n_valid = _bounds(R, device)
-            if n_valid > 0:
-                size = int(lib.d3r_cloud_grid_workspace_bytes(nr, nq))
-                if size == 0:
-                    raise ValueError(f'k_nearest: clouds of {nq} and {nr} points are too large')
-                work = torch.empty(size, dtype=torch.uint8, device=device)
-                lo_c = (C.c_float * 3)(*lo.tolist())
-                for j, r in enumerate(radii):
-                    cell, bits = grid_cell(lo, hi, _radius_f32(float(r) * cell_factor, 'cell'))
-                    bits_c = (C.c_int * 3)(*bits)
-                    check(lib.d3r_cloud_grid_build(nr, ptr(R), lo_c, float(cell), bits_c, ptr(work), current_stream()), 'cloud_grid_build')
-                    check(lib.d3r_cloud_knn(nr, nq, ptr(Q), k, float(r), lo_c, float(cell), bits_c, int(bool(exclude_self)), int(j > 0), ptr(d2), ptr(idx),
-                                            ptr(evals), ptr(work), current_stream()), 'cloud_knn')
-    if to_host:
-        return d2.cpu().numpy(), idx.cpu().numpy()
-    return d2, idx
+    if exclude_self and len(Q) != len(R):
+        raise ValueError(f'k_nearest: exclude_self needs query is ref, or clouds of equal length; got {len(Q)} and {len(R)} points')
+    return _ladder_search(Q, R, radii, k, to_host, exclude_self=exclude_self, cell_factor=cell_factor, evals=evals)
 
 
 @torch.no_grad()
@@ -526,38 +542,6 @@ def icp_sums(moved, ref, d2, idx, metric, gate, centre, ref_normals=None, moved_
     return count, sums, used
 
 
-class _ReferenceGrids:
-    """The grids of one ladder over a reference cloud that does not move: rung k in a workspace of its own, built once (kept) or before
-    every search (rebuild=True: what `nearest_in_cloud` does in one workspace; the same bytes, tests compare the two)."""
-
-    def __init__(self, R, lo, hi, radii, n_query, rebuild=False):
-        self.R, self.radii, self.rebuild, self.n_query = R, radii, rebuild, n_query
-        self.lo_c = (C.c_float * 3)(*lo.tolist())
-        size = int(lib.d3r_cloud_grid_workspace_bytes(len(R), n_query))
-        if size == 0:
-            raise ValueError(f'register_clouds: clouds of {n_query} and {len(R)} points are too large')
-        self.rungs = []
-        for r in radii:
-            cell, bits = grid_cell(lo, hi, r)
-            rung = (float(r), float(cell), (C.c_int * 3)(*bits), torch.empty(size, dtype=torch.uint8, device=R.device))
-            self.rungs.append(rung)
-            if not rebuild:
-                self._build(rung)
-
-    def _build(self, rung):
-        r, cell, bits_c, work = rung
-        check(lib.d3r_cloud_grid_build(len(self.R), ptr(self.R), self.lo_c, cell, bits_c, ptr(work), current_stream()), 'cloud_grid_build')
-
-    def nearest(self, Q, d2, idx):
-        """the ladder of `nearest_in_cloud` for the queries Q (at most n_query) into d2 / idx"""
-        for k, rung in enumerate(self.rungs):
-            if self.rebuild:
-                self._build(rung)
-            r, cell, bits_c, work = rung
-            check(lib.d3r_cloud_nearest(len(self.R), len(Q), ptr(Q), r, self.lo_c, cell, bits_c, int(k > 0), ptr(d2), ptr(idx), None, ptr(work),
-                                        current_stream()), 'cloud_nearest')
-
-
 @torch.no_grad()
 def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plane', max_iters=30, tol=1e-6, cos_min=None, r0=None, centre=None,
                     _rebuild_grids=False):
@@ -621,7 +605,7 @@ def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plan
                 M, R, _ = similarity_parts(S)
                 check(lib.d3r_cloud_transform(n, ptr(P), (C.c_float * 12)(*M.tolist()), ptr(moved), ptr(src_normals), (C.c_float * 9)(*R.tolist()),
                                               ptr(moved_normals), current_stream()), 'cloud_transform')
-                grids.nearest(moved, d2, idx)
+                grids.search(moved, d2, idx)
                 check(lib.d3r_cloud_icp_sums(n, ptr(moved), ptr(moved_normals), len(Q), ptr(Q), ptr(dst_normals), ptr(d2), ptr(idx), METRICS[metric],
                                              float(gate), 0.0 if cos_min is None else float(cos_min), centre_c, ptr(count), ptr(sums), None, ptr(work),
                                              current_stream()), 'cloud_icp_sums')

@@ -1,6 +1,7 @@
-// dust3r_amd -- what cloud_nn.hip (the nearest neighbour) and cloud_knn.hip (the k nearest) share of the grid of d3r_cloud_grid_build: the
-// layout of its workspace, the checks of the cell size and the radius, the padded cell range's arithmetic and the 1 x n shape table.
-// Moved here from cloud_nn.hip with the same text; as in fuse_grid.hpp every kernel is static, so each file launches its own copy.
+// dust3r_amd -- what cloud_nn.hip (the grid, the distance statistics), cloud_knn.hip (the search on the grid) and cloud_icp.hip (the
+// registration's sums) share: the layout of the grid's workspace, the checks of the cell size and the radius, the padded cell range's
+// arithmetic, the 1 x n shape table, and the ordered fp64 / int64 sum of all three: the workgroup's sum, the final kernel over the
+// per-workgroup partials and the partials' layout. As in fuse_grid.hpp every kernel is static, so each file launches its own copy.
 #pragma once
 #include "common.hpp"
 #include "scene_common.hpp"
@@ -73,6 +74,79 @@ static inline bool cloud_radius_ok(float r) {
     return r > 0.f && r2 >= 1.17549435e-38f && r2 <= 3.4028234e38f;
 }
 static inline int cloud_blocks(long long n) { return fuse_blocks(fuse_tiles(n, QT)); }
+
+// ---- the ordered sum: ND doubles and NI int64s per thread -> per workgroup -> one row -------------------------------------------------------
+constexpr int SUM_PARTS = 1024;         // grid cap of a pass that leaves partials = the rows the final kernel reads
+
+// The workgroup's totals of sd / si, column k written to out_d[k] / out_i[k]: the wave's sums by an xor butterfly 32..1, then column k by
+// thread k over the waves 0..3 in order. A fixed shape: the same bytes whatever the run. Once per kernel (it owns its LDS).
+template <int ND, int NI>
+D3R_DEV void cloud_block_sum(double (&sd)[ND], long long (&si)[NI], double* out_d, long long* out_i) {
+    static_assert(ND <= QT && NI <= QT, "one thread per column");
+    __shared__ double lds_d[QT / 64 * ND];
+    __shared__ long long lds_i[QT / 64 * NI];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k) sd[k] += __shfl_xor(sd[k], o);
+#pragma unroll
+        for (int k = 0; k < NI; ++k) si[k] += __shfl_xor(si[k], o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k) lds_d[wave * ND + k] = sd[k];
+#pragma unroll
+        for (int k = 0; k < NI; ++k) lds_i[wave * NI + k] = si[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < ND) {
+        double t = lds_d[threadIdx.x];
+        for (int w = 1; w < QT / 64; ++w) t += lds_d[w * ND + threadIdx.x];
+        out_d[threadIdx.x] = t;
+    }
+    if (threadIdx.x < NI) {
+        long long c = lds_i[threadIdx.x];
+        for (int w = 1; w < QT / 64; ++w) c += lds_i[w * NI + threadIdx.x];
+        out_i[threadIdx.x] = c;
+    }
+}
+
+// one workgroup adds the partials: thread t the rows t, t + QT, ... in index order, then the workgroup's sum
+template <int ND, int NI>
+static __global__ __launch_bounds__(QT) void cloud_sums_final_kernel(int n_parts, const double* __restrict__ part_d, const long long* __restrict__ part_i,
+                                                                    long long* __restrict__ counts_out, double* __restrict__ sums_out) {
+    double sd[ND];
+    long long si[NI];
+#pragma unroll
+    for (int k = 0; k < ND; ++k) sd[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) si[k] = 0;
+    for (int b = threadIdx.x; b < n_parts; b += QT) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k) sd[k] += part_d[(size_t)b * ND + k];
+#pragma unroll
+        for (int k = 0; k < NI; ++k) si[k] += part_i[(size_t)b * NI + k];
+    }
+    cloud_block_sum<ND, NI>(sd, si, sums_out, counts_out);
+}
+
+struct SumParts {
+    int parts;              // the workgroups of the pass over n rows
+    double* d;              // [parts][nd]
+    long long* i;           // [parts][ni]
+    size_t bytes;
+};
+
+static inline SumParts cloud_sum_parts(void* base, int n, int nd, int ni) {
+    SumParts p;
+    p.parts = std::min(cloud_blocks(n), SUM_PARTS);
+    const size_t d_bytes = align256((size_t)p.parts * nd * sizeof(double));
+    p.d = (double*)base;
+    p.i = base ? (long long*)((char*)base + d_bytes) : nullptr;
+    p.bytes = d_bytes + align256((size_t)p.parts * ni * sizeof(long long));
+    return p;
+}
 
 }  // namespace cloud
 }  // namespace d3r

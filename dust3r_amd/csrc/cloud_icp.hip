@@ -1,8 +1,8 @@
 // dust3r_amd -- cloud registration (new; the reference has none): what one iteration of Sim(3) ICP does on the device besides the nearest
-// neighbour search of cloud_nn.hip (dust3r_amd/cloud_metrics.py, register_clouds).
+// neighbour search of cloud_knn.hip (dust3r_amd/cloud_metrics.py, register_clouds).
 //   d3r_cloud_transform    cloud_transform_kernel            p' = A p + t per point, m = R n per normal, one thread per row
 //   d3r_cloud_icp_sums     cloud_icp_sums_kernel<METRIC>     the gates of every row and the fp64 sums of the used rows: per-workgroup partials
-//                          cloud_icp_final_kernel<METRIC>    one workgroup adds the partials in index order
+//                          cloud_sums_final_kernel<18|36, 1> one workgroup adds the partials in index order (cloud_grid.hpp)
 // METRIC 0 (point to point): the 17 moments of bootstrap.hip's layout and the squared residual, 18 sums. METRIC 1 (point to plane): the
 // upper triangle of sum J J^T, sum J e and sum e e, 36 sums. One instance per metric: neither carries the other's accumulators.
 // As in cloud_nn.hip: no atomics, no kernel waits on another workgroup, no scratch; partial b holds the rows b QT + thread + k gridDim QT,
@@ -19,7 +19,6 @@ namespace cloud {
 
 using namespace d3r::fuse;
 
-constexpr int ICP_BLOCKS = 1024;        // grid cap of the sums pass = the partials of the final pass
 constexpr int ICP_POINT = 18, ICP_PLANE = 36;
 template <int METRIC> struct IcpSums { static constexpr int N = METRIC ? ICP_PLANE : ICP_POINT; };
 
@@ -68,43 +67,13 @@ struct IcpArgs {
     uint8_t* used_out;                  // optional
 };
 
-// the wave's sums by a butterfly of fixed shape, then column k by thread k over the waves in order: the workgroup's totals go to out[k]
-template <int NS>
-D3R_DEV void icp_block_sum(double (&s)[NS], long long cnt, double* lds_d, long long* lds_i, double* out_d, long long* out_i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) s[k] += __shfl_xor(s[k], o);
-        cnt += __shfl_xor(cnt, o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) lds_d[wave * NS + k] = s[k];
-        lds_i[wave] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        double t = lds_d[threadIdx.x];
-        for (int w = 1; w < QT / 64; ++w) t += lds_d[w * NS + threadIdx.x];
-        out_d[threadIdx.x] = t;
-    }
-    if (threadIdx.x == 0) {
-        long long c = lds_i[0];
-        for (int w = 1; w < QT / 64; ++w) c += lds_i[w];
-        *out_i = c;
-    }
-}
-
 template <int METRIC>
 __global__ __launch_bounds__(QT) void cloud_icp_sums_kernel(const IcpArgs a, double* __restrict__ part_d, long long* __restrict__ part_i) {
     constexpr int NS = IcpSums<METRIC>::N;
-    __shared__ double lds_d[QT / 64 * NS];
-    __shared__ long long lds_i[QT / 64];
     double s[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) s[k] = 0.0;
-    long long cnt = 0;
+    long long cnt[1] = {0};
     const double cx = (double)a.centre[0], cy = (double)a.centre[1], cz = (double)a.centre[2];
     for (long long i = (long long)blockIdx.x * QT + threadIdx.x; i < a.n; i += (long long)gridDim.x * QT) {
         const int g = a.idx[i];
@@ -129,7 +98,7 @@ __global__ __launch_bounds__(QT) void cloud_icp_sums_kernel(const IcpArgs a, dou
         }
         if (a.used_out) a.used_out[i] = used;
         if (!used) continue;
-        cnt += 1;
+        cnt[0] += 1;
         const double ax = (double)px - cx, ay = (double)py - cy, az = (double)pz - cz;
         const double yx = (double)qx - cx, yy = (double)qy - cy, yz = (double)qz - cz;
         const double dx = ax - yx, dy = ay - yy, dz = az - yz;
@@ -159,28 +128,9 @@ __global__ __launch_bounds__(QT) void cloud_icp_sums_kernel(const IcpArgs a, dou
             s[35] += e * e;
         }
     }
-    icp_block_sum<NS>(s, cnt, lds_d, lds_i, part_d + (size_t)blockIdx.x * NS, part_i + blockIdx.x);
+    cloud_block_sum<NS, 1>(s, cnt, part_d + (size_t)blockIdx.x * NS, part_i + blockIdx.x);
 }
 
-template <int METRIC>
-__global__ __launch_bounds__(QT) void cloud_icp_final_kernel(int n_parts, const double* __restrict__ part_d, const long long* __restrict__ part_i,
-                                                            long long* __restrict__ count_out, double* __restrict__ sums_out) {
-    constexpr int NS = IcpSums<METRIC>::N;
-    __shared__ double lds_d[QT / 64 * NS];
-    __shared__ long long lds_i[QT / 64];
-    double s[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) s[k] = 0.0;
-    long long cnt = 0;
-    for (int b = threadIdx.x; b < n_parts; b += QT) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) s[k] += part_d[(size_t)b * NS + k];
-        cnt += part_i[b];
-    }
-    icp_block_sum<NS>(s, cnt, lds_d, lds_i, sums_out, count_out);
-}
-
-static inline int icp_parts(int n) { return std::min(cloud_blocks(n), ICP_BLOCKS); }
 static inline bool all_finite(const float* v, int n) {
     for (int k = 0; k < n; ++k)
         if (!(v[k] >= -3.4028234e38f && v[k] <= 3.4028234e38f)) return false;
@@ -189,11 +139,9 @@ static inline bool all_finite(const float* v, int n) {
 
 template <int METRIC>
 static void icp_launch(const IcpArgs& a, long long* count_out, double* sums_out, void* workspace, hipStream_t st) {
-    const int parts = icp_parts(a.n);
-    double* part_d = (double*)workspace;
-    long long* part_i = (long long*)((char*)workspace + align256((size_t)parts * ICP_PLANE * sizeof(double)));
-    hipLaunchKernelGGL(cloud_icp_sums_kernel<METRIC>, dim3(parts), dim3(QT), 0, st, a, part_d, part_i);
-    hipLaunchKernelGGL(cloud_icp_final_kernel<METRIC>, dim3(1), dim3(QT), 0, st, parts, part_d, part_i, count_out, sums_out);
+    const SumParts p = cloud_sum_parts(workspace, a.n, ICP_PLANE, 1);        // as d3r_cloud_icp_sums_workspace_bytes, which does not know the metric
+    hipLaunchKernelGGL(cloud_icp_sums_kernel<METRIC>, dim3(p.parts), dim3(QT), 0, st, a, p.d, p.i);
+    hipLaunchKernelGGL((cloud_sums_final_kernel<IcpSums<METRIC>::N, 1>), dim3(1), dim3(QT), 0, st, p.parts, p.d, p.i, count_out, sums_out);
 }
 
 }  // namespace cloud
@@ -215,8 +163,7 @@ extern "C" int d3r_cloud_transform(int n, const float* pts, const float* M, floa
 
 extern "C" size_t d3r_cloud_icp_sums_workspace_bytes(int n) {
     if (n <= 0) return 0;
-    const size_t parts = (size_t)icp_parts(n);
-    return align256(parts * ICP_PLANE * sizeof(double)) + align256(parts * sizeof(long long));
+    return cloud_sum_parts(nullptr, n, ICP_PLANE, 1).bytes;
 }
 
 extern "C" int d3r_cloud_icp_sums(int n, const float* moved, const float* moved_normals, int n_ref, const float* ref, const float* ref_normals,

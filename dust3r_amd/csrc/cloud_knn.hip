@@ -1,13 +1,17 @@
-// dust3r_amd -- the k nearest neighbours of every point of a cloud on the grid of d3r_cloud_grid_build (cloud_nn.hip, cloud_grid.hpp), and
+// dust3r_amd -- the search on the grid of d3r_cloud_grid_build (cloud_nn.hip, cloud_grid.hpp) for both of its entry points, the k nearest
+// neighbours of every point of a cloud (d3r_cloud_knn) and the nearest one (d3r_cloud_nearest, the same search at k = 1), and
 // the three kernels that consume them: mean neighbour distances (statistical outlier removal), normals, the orientation of the normals by
-// the scene's cameras (new; the reference has none; dust3r_amd/cloud_metrics.py k_nearest, viz.FusedCloud.estimate_normals / remove_outliers).
-// The contract does not mention the grid (include/dust3r_hip.h): the candidates of a valid query are the valid reference points with fp32
-// d2 <= r2 (the query's own index left out with exclude_self), and its row holds the k smallest (d2, index) pairs in lexicographic order,
-// padded with (+inf, -1). The grid only limits which points are LOOKED AT, and the looked-at set holds every point with d2 <= r2.
+// the scene's cameras (new; the reference has none; dust3r_amd/cloud_metrics.py nearest_in_cloud / k_nearest, viz.FusedCloud.estimate_normals /
+// remove_outliers). The contract does not mention the grid (include/dust3r_hip.h): the candidates of a valid query are the valid reference
+// points with fp32 d2 <= r2 (the query's own index left out with exclude_self), and its row holds the k smallest (d2, index) pairs in
+// lexicographic order, padded with (+inf, -1); the nearest neighbour, the lowest index among the points of minimal d2 when that minimum is
+// <= r2, is the row of one column. The grid only limits which points are LOOKED AT, and the looked-at set holds every point with d2 <= r2
+// ("Cloud metrics"). A cell that holds most of the cloud is walked point by point by every query near it: slow, not wrong.
 //   d3r_cloud_knn             cloud_knn_init_kernel      every row padded, or, with only_unresolved, the mask idx[q][k - 1] < 0 of the open rows
-//                             stages 1-2 of fuse_grid.hpp on the queries with the grid's own key: the queries in the order of their cells
-//                             cloud_knn_kernel<8|16|32>  one thread per query, in that order; the sorted list lives in registers
-//   d3r_cloud_knn_distances   cloud_knn_mean_kernel / cloud_knn_mean_final_kernel   the row means; per-workgroup partials, then one workgroup
+//   d3r_cloud_nearest         stages 1-2 of fuse_grid.hpp on the queries with the grid's own key: the queries in the order of their cells
+//                             cloud_knn_kernel<1|8|16|32>   one thread per query, in that order: the lanes of a wave walk the same runs; the
+//                                                        sorted list lives in registers
+//   d3r_cloud_knn_distances   cloud_knn_mean_kernel / cloud_sums_final_kernel<2, 1>   the row means; per-workgroup partials, then one workgroup
 //   d3r_cloud_normals         cloud_normals_kernel       fp64 scatter matrix of the point and its neighbours, cyclic Jacobi on named scalars
 //   d3r_cloud_orient_normals  cloud_orient_kernel        one thread per point walks the views in order: projection in fp32, the vote in fp64
 // As in fuse.hip and cloud_nn.hip: no atomics, no kernel waits on another workgroup, no scratch; the same bytes on every run. The list is
@@ -22,7 +26,6 @@
 namespace d3r {
 namespace cloud {
 
-constexpr int KNN_STAT_BLOCKS = 1024;   // grid cap of the mean pass = the partials of its final pass
 constexpr int JACOBI_SWEEPS = 8;        // cyclic Jacobi on 3 x 3 converges quadratically: 4-5 sweeps reach fp64 rounding, 8 leave a margin
 constexpr int NO_INDEX = 0x7FFFFFFF;    // the index of an empty list slot: above every real one, so (inf, NO_INDEX) sorts last
 
@@ -81,7 +84,8 @@ __global__ __launch_bounds__(QT) void cloud_knn_kernel(const KnnArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float lo = next_down(__fsub_rn(pa[c], rp)), hi = next_up(__fadd_rn(pa[c], rp));
-            // as in cloud_query_kernel: an interval that ends below cell 0 or starts above the last cell holds no reference point
+            // every reference point has 0 <= floorf(.) <= qmax (lo = the bounds' minimum, bits from their extent) and floorf(.) is monotone:
+            // an interval that ends below cell 0 or starts above the last cell holds none
             outside = outside || axis_f(hi, a.key, c) < 0.f || axis_f(lo, a.key, c) > (float)a.key.qmax[c];
             c0[c] = axis_q(lo, a.key, c);
             c1[c] = axis_q(hi, a.key, c);
@@ -143,38 +147,9 @@ __global__ __launch_bounds__(QT) void cloud_knn_kernel(const KnnArgs a) {
 // ---- mean neighbour distance ------------------------------------------------------------------------------------------------------------
 constexpr int MEAN_D = 2, MEAN_I = 1;
 
-// the wave's sums by butterflies, then thread 0 over the waves in order: the workgroup's totals, valid in thread 0 (cloud_nn.hip's pattern)
-D3R_DEV void mean_block_sum(double (&sd)[MEAN_D], long long (&si)[MEAN_I], double* lds_d, long long* lds_i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < MEAN_D; ++k) sd[k] += __shfl_xor(sd[k], o);
-#pragma unroll
-        for (int k = 0; k < MEAN_I; ++k) si[k] += __shfl_xor(si[k], o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < MEAN_D; ++k) lds_d[wave * MEAN_D + k] = sd[k];
-#pragma unroll
-        for (int k = 0; k < MEAN_I; ++k) lds_i[wave * MEAN_I + k] = si[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < QT / 64; ++w) {
-#pragma unroll
-            for (int k = 0; k < MEAN_D; ++k) sd[k] += lds_d[w * MEAN_D + k];
-#pragma unroll
-            for (int k = 0; k < MEAN_I; ++k) si[k] += lds_i[w * MEAN_I + k];
-        }
-    }
-}
-
 // mean_out[q], and partial b = the sums over the full rows q = b QT + thread + j gridDim QT: a fixed set in a fixed order, whatever the run
 __global__ __launch_bounds__(QT) void cloud_knn_mean_kernel(int n, int k, const float* __restrict__ d2, const int* __restrict__ idx, float* __restrict__ mean_out,
                                                            double* __restrict__ part_d, long long* __restrict__ part_i) {
-    __shared__ double lds_d[QT / 64 * MEAN_D];
-    __shared__ long long lds_i[QT / 64 * MEAN_I];
     double sd[MEAN_D] = {0.0, 0.0};
     long long si[MEAN_I] = {0};
     for (long long q = (long long)blockIdx.x * QT + threadIdx.x; q < n; q += (long long)gridDim.x * QT) {
@@ -195,31 +170,7 @@ __global__ __launch_bounds__(QT) void cloud_knn_mean_kernel(int n, int k, const 
             sd[1] += __dmul_rn(m, m);
         }
     }
-    mean_block_sum(sd, si, lds_d, lds_i);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < MEAN_D; ++j) part_d[(size_t)blockIdx.x * MEAN_D + j] = sd[j];
-        part_i[blockIdx.x] = si[0];
-    }
-}
-
-__global__ __launch_bounds__(QT) void cloud_knn_mean_final_kernel(int n_parts, const double* __restrict__ part_d, const long long* __restrict__ part_i,
-                                                                 long long* __restrict__ count_out, double* __restrict__ sums_out) {
-    __shared__ double lds_d[QT / 64 * MEAN_D];
-    __shared__ long long lds_i[QT / 64 * MEAN_I];
-    double sd[MEAN_D] = {0.0, 0.0};
-    long long si[MEAN_I] = {0};
-    for (int b = threadIdx.x; b < n_parts; b += QT) {
-#pragma unroll
-        for (int j = 0; j < MEAN_D; ++j) sd[j] += part_d[(size_t)b * MEAN_D + j];
-        si[0] += part_i[b];
-    }
-    mean_block_sum(sd, si, lds_d, lds_i);
-    if (threadIdx.x == 0) {
-        count_out[0] = si[0];
-#pragma unroll
-        for (int j = 0; j < MEAN_D; ++j) sums_out[j] = sd[j];
-    }
+    cloud_block_sum<MEAN_D, MEAN_I>(sd, si, part_d + (size_t)blockIdx.x * MEAN_D, part_i + (size_t)blockIdx.x * MEAN_I);
 }
 
 // ---- normals ----------------------------------------------------------------------------------------------------------------------------
@@ -364,8 +315,6 @@ __global__ __launch_bounds__(QT) void cloud_orient_kernel(const OrientArgs a) {
     }
 }
 
-static int knn_parts(int n) { return std::min(cloud_blocks(n), KNN_STAT_BLOCKS); }
-
 }  // namespace cloud
 }  // namespace d3r
 
@@ -392,27 +341,31 @@ extern "C" int d3r_cloud_knn(int n_ref, int n_query, const float* query, int k, 
     qa.query = query; qa.order = w.qry.idx[cur]; qa.n_query_dev = w.qry.n_dev; qa.cap_query = n_query;
     qa.d2_out = d2_out; qa.idx_out = idx_out; qa.evals = evals;
     const dim3 grid(cloud_blocks(n_query)), block(QT);
-    if (k <= 8) hipLaunchKernelGGL(cloud_knn_kernel<8>, grid, block, 0, st, qa);
+    if (k == 1) hipLaunchKernelGGL(cloud_knn_kernel<1>, grid, block, 0, st, qa);
+    else if (k <= 8) hipLaunchKernelGGL(cloud_knn_kernel<8>, grid, block, 0, st, qa);
     else if (k <= 16) hipLaunchKernelGGL(cloud_knn_kernel<16>, grid, block, 0, st, qa);
     else hipLaunchKernelGGL(cloud_knn_kernel<32>, grid, block, 0, st, qa);
     return rc_of(hipGetLastError());
 }
 
+// the first column of the search at k = 1: the smallest (d2, index) pair among those with d2 <= r2; outputs (n,) are rows of one column
+extern "C" int d3r_cloud_nearest(int n_ref, int n_query, const float* query, float r, const float* lo, float cell, const int* bits, int only_unresolved,
+                                 float* d2_out, int* idx_out, int* evals, void* workspace, void* stream) {
+    return d3r_cloud_knn(n_ref, n_query, query, 1, r, lo, cell, bits, 0, only_unresolved, d2_out, idx_out, evals, workspace, stream);
+}
+
 extern "C" size_t d3r_cloud_knn_distances_workspace_bytes(int n) {
     if (n <= 0) return 0;
-    const size_t parts = (size_t)knn_parts(n);
-    return align256(parts * MEAN_D * sizeof(double)) + align256(parts * MEAN_I * sizeof(long long));
+    return cloud_sum_parts(nullptr, n, MEAN_D, MEAN_I).bytes;
 }
 
 extern "C" int d3r_cloud_knn_distances(int n, int k, const float* d2, const int* idx, float* mean_out, long long* count_out, double* sums_out,
                                        void* workspace, void* stream) {
     if (n <= 0 || k < 1 || k > D3R_CLOUD_MAX_K || !d2 || !idx || !mean_out || !count_out || !sums_out || !workspace) return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const int parts = knn_parts(n);
-    double* part_d = (double*)workspace;
-    long long* part_i = (long long*)((char*)workspace + align256((size_t)parts * MEAN_D * sizeof(double)));
-    hipLaunchKernelGGL(cloud_knn_mean_kernel, dim3(parts), dim3(QT), 0, st, n, k, d2, idx, mean_out, part_d, part_i);
-    hipLaunchKernelGGL(cloud_knn_mean_final_kernel, dim3(1), dim3(QT), 0, st, parts, part_d, part_i, count_out, sums_out);
+    const SumParts p = cloud_sum_parts(workspace, n, MEAN_D, MEAN_I);
+    hipLaunchKernelGGL(cloud_knn_mean_kernel, dim3(p.parts), dim3(QT), 0, st, n, k, d2, idx, mean_out, p.d, p.i);
+    hipLaunchKernelGGL((cloud_sums_final_kernel<MEAN_D, MEAN_I>), dim3(1), dim3(QT), 0, st, p.parts, p.d, p.i, count_out, sums_out);
     return rc_of(hipGetLastError());
 }
 

@@ -1,6 +1,6 @@
 // dust3r_amd -- the voxel grid that fuse.hip (scene.fuse()) and cloud_nn.hip (cloud-to-cloud nearest neighbours) share: stages 1-3 of
 // d3r_fuse_voxels, moved here with the same arithmetic and launch sequence. What differs from the code as it stood in fuse.hip: valid_at
-// takes a NULL mask; key_of is written on axis_q (one axis of the key, the same three operations), which the query kernel of cloud_nn.hip
+// takes a NULL mask; key_of is written on axis_q (one axis of the key, the same three operations), which the search kernel of cloud_knn.hip
 // needs on its own; every kernel, the template included, is static, so each file that includes this header has and launches its OWN
 // copies under its own host stubs -- nothing is merged across the two objects, whatever flags they are built with.
 // Inputs are padded stacks (utils/padded.py): view v is elements [0, h w) of row v, flat index g = v row + e; a flat cloud of n points is

@@ -502,7 +502,7 @@ int d3r_fuse_voxels(int n_views, const float* pts, const uint8_t* mask, const fl
                     const int* img_w_dev, int row, const float* lo, float voxel, const int* bits, int capacity, float* positions_out,
                     uint32_t* colors_out, float* weight_out, int* count_out, long long* totals_out, void* workspace, void* stream);
 
-/* Cloud-to-cloud metrics (new; csrc/cloud_nn.hip): the truncated exact nearest neighbour of every point of a query cloud in a reference
+/* Cloud-to-cloud metrics (new; csrc/cloud_nn.hip, the search in csrc/cloud_knn.hip): the truncated exact nearest neighbour of every point of a query cloud in a reference
  * cloud, and the sums and counts of the distances. ref [n_ref][3] and query [n_query][3] DEVICE fp32, 1 <= n <= 2^31 - 1. A point is VALID
  * when its three coordinates are finite. d2(q, p) = (dx dx + dy dy) + dz dz with dx = q_x - p_x, ..., every operation a separate IEEE
  * fp32 rounding (no contraction). r a positive fp32 whose square r2 = r r (fp32) is a NORMAL number, about 1.1e-19 <= r <= 1.8e19: with a
@@ -522,7 +522,8 @@ int d3r_fuse_voxels(int n_views, const float* pts, const uint8_t* mask, const fl
  *   and bits are the ones stated above. The queries are processed in the order of their own cell keys; results go to their original rows.
  *   only_unresolved = 0: every row of d2_out / idx_out is written. only_unresolved != 0: the rows with idx_out[q] >= 0 on entry are kept
  *   and their queries are not searched (the radius ladder of dust3r_amd/cloud_metrics.py); the other rows are written.
- *   evals (optional, DEVICE int [n_query]): evals[q] += the distances evaluated for q in this call.
+ *   evals (optional, DEVICE int [n_query]): evals[q] += the distances evaluated for q in this call. The call IS d3r_cloud_knn (below) at
+ *   k = 1, exclude_self = 0: the smallest (d2, index) pair is the lowest index of minimal d2.
  *   workspace: d3r_cloud_grid_workspace_bytes(n_ref, n_query) bytes of DEVICE memory (0 for invalid sizes), n_query the largest query
  *   cloud asked of this grid (the build itself does not depend on it).
  * d3r_cloud_distance_stats: over rows q < n of d2 / idx as written above, tau [n_tau] a HOST array, 0 <= n_tau <= D3R_CLOUD_MAX_THRESHOLDS,
@@ -550,7 +551,7 @@ int d3r_cloud_distance_stats(int n, const float* query, const float* d2, const i
  *   query at another index stays. Row q of d2_out [n_query][k] and idx_out [n_query][k] holds the k smallest pairs (d2, g) in lexicographic
  *   order, ascending; a row of fewer candidates is padded with (+inf, -1); an invalid query gets a fully padded row. This is what an fp32
  *   brute force over all pairs gives, bit for bit. Each thread owns one query, in the order of the queries' cells, and keeps its sorted list
- *   in registers (8, 16 or 32 slots by k; insertion is an unrolled compare-and-shift, the last slot the pruning bound).
+ *   in registers (1, 8, 16 or 32 slots by k; insertion is an unrolled compare-and-shift, the last slot the pruning bound).
  *   only_unresolved = 0: every row is written. only_unresolved != 0: the rows whose LAST column holds an index >= 0 on entry are kept and
  *   their queries are not searched; the other rows are overwritten. Sound for a radius ladder: every point with d2 <= r2 is looked at, so
  *   k candidates within r are the k smallest of any larger radius. evals (optional, DEVICE int [n_query]): += the distances evaluated.

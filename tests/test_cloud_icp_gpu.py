@@ -364,6 +364,6 @@ def test_resource_report_has_no_scratch():
         pytest.skip('no cloud_icp.resources.txt: the library was not built by dust3r_amd/build.py')
     report = open(path).read()
     kernels = re.findall(r'Function Name: (\S+)', report)
-    new = [k for k in kernels if 'cloud_icp' in k or 'cloud_transform' in k]
-    assert len(new) == 5 and sum('cloud_icp_sums_kernel' in k for k in new) == 2 and sum('cloud_icp_final_kernel' in k for k in new) == 2
+    new = [k for k in kernels if 'cloud_icp' in k or 'cloud_transform' in k or 'cloud_sums_final' in k]
+    assert len(new) == 5 and sum('cloud_icp_sums_kernel' in k for k in new) == 2 and sum('cloud_sums_final_kernel' in k for k in new) == 2
     assert re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', report) == ['0'] * len(kernels)

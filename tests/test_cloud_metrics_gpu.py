@@ -433,5 +433,5 @@ def test_resource_report_has_no_scratch():
     report = open(path).read()
     kernels = re.findall(r'Function Name: (\S+)', report)
     new = [k for k in kernels if 'cloud_' in k]
-    assert len(new) == 7 and len(kernels) == 14 and all('cloud_' in k or 'fuse_' in k for k in kernels)
+    assert len(new) == 5 and len(kernels) == 12 and sum('cloud_sums_final_kernel' in k for k in new) == 1 and all('cloud_' in k or 'fuse_' in k for k in kernels)
     assert re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', report) == ['0'] * len(kernels)

@@ -30,9 +30,9 @@ STAGES = ('bounds', 'key+compact', 'sort', 'heads', 'gather+cells', 'init', 'que
 
 
 def stage_of(name):
-    """the stage a kernel of csrc/cloud_nn.hip / fuse_grid.hpp belongs to, from its (mangled or demangled) name; None for other kernels"""
+    """the stage a kernel of csrc/cloud_nn.hip / cloud_knn.hip / fuse_grid.hpp belongs to, from its (mangled or demangled) name; None for other kernels"""
     for key, stage in (('fuse_bounds', 'bounds'), ('fuse_hist', 'sort'), ('fuse_scatter', 'sort'), ('cloud_gather', 'gather+cells'),
-                       ('cloud_cells', 'gather+cells'), ('cloud_init', 'init'), ('cloud_shape', 'init'), ('cloud_query', 'query'), ('fuse_scan', 'scan')):
+                       ('cloud_cells', 'gather+cells'), ('cloud_knn_init', 'init'), ('cloud_shape', 'init'), ('cloud_knn_kernel', 'query'), ('fuse_scan', 'scan')):
         if key in name:
             return stage
     if 'fuse_flag' in name:
@@ -41,7 +41,7 @@ def stage_of(name):
 
 
 def summarise(path):
-    """Groups the dispatches of a kernel trace into calls (a call starts at fuse_bounds_kernel; only those that reach cloud_query_kernel count)
+    """Groups the dispatches of a kernel trace into calls (a call starts at fuse_bounds_kernel; only those that reach cloud_knn_kernel count)
     and stages (a scan belongs to the stage of the kernel before it). Prints the median over the calls of every stage."""
     rows = [r for r in csv.DictReader(open(path)) if stage_of(r['Kernel_Name'])]
     rows.sort(key=lambda r: int(r['Start_Timestamp']))

@@ -100,7 +100,7 @@ def main():
         radii = ladder_radii(min(default_r0(dst, gate), float(gate)), gate)
         build_ms = device_ms(lambda: _ReferenceGrids(Q, lo, hi, radii, m), reps=3, warm=1)
         grids = _ReferenceGrids(Q, lo, hi, radii, m)
-        nearest_ms = device_ms(lambda: grids.nearest(moved, d2, idx))
+        nearest_ms = device_ms(lambda: grids.search(moved, d2, idx))
         row = dict(row='iteration', views=n, voxel_size=float(voxel), n_src=m, n_ref=mr, gate_voxels=round(float(gate) / voxel, 2), rungs=[float(r) for r in radii],
                    grid_build_once_ms=round(build_ms, 3), transform_ms=round(transform_ms, 3), nearest_ms=round(nearest_ms, 3))
         for metric in ('point', 'plane'):
