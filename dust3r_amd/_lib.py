@@ -242,5 +242,10 @@ def ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def workspace(nbytes, device):
+    """The uninitialised device buffer of a call's `workspace` argument: nbytes as its *_workspace_bytes export gives it."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
 def current_stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -119,7 +119,7 @@ def _bounds(pts, device):
     ones = torch.ones((n,), dtype=torch.uint8, device=device)
     h, w = torch.ones((1,), dtype=torch.int32, device=device), torch.full((1,), n, dtype=torch.int32, device=device)
     small = torch.empty((4,), dtype=torch.int64, device=device)
-    work = torch.empty(max(1, int(lib.d3r_fuse_bounds_workspace_bytes(1, n))), dtype=torch.uint8, device=device)
+    work = _lib.workspace(max(1, lib.d3r_fuse_bounds_workspace_bytes(1, n)), device)
     check(lib.d3r_fuse_bounds(1, ptr(pts), ptr(ones), None, ptr(h), ptr(w), n, ptr(small.view(torch.float32)), ptr(small[3:]), ptr(work),
                               current_stream()), 'fuse_bounds')
     host = small.cpu()
@@ -140,7 +140,7 @@ class _ReferenceGrids:
         size = int(lib.d3r_cloud_grid_workspace_bytes(len(R), n_query))
         if size == 0:
             raise ValueError(f'clouds of {n_query} and {len(R)} points are too large')
-        work = torch.empty(size, dtype=torch.uint8, device=R.device) if rebuild else None
+        work = _lib.workspace(size, R.device) if rebuild else None
         self.rungs = []
         for r in radii:
             cell, bits = grid_cell(lo, hi, _radius_f32(float(r) * cell_factor, 'cell'))
@@ -239,7 +239,7 @@ def knn_mean_distances(d2, idx):
     sums = torch.zeros((2,), dtype=torch.float64, device=device)
     if n > 0:
         with torch.cuda.device(device):
-            work = torch.empty(int(lib.d3r_cloud_knn_distances_workspace_bytes(n)), dtype=torch.uint8, device=device)
+            work = _lib.workspace(lib.d3r_cloud_knn_distances_workspace_bytes(n), device)
             check(lib.d3r_cloud_knn_distances(n, k, ptr(d2.contiguous()), ptr(idx.contiguous()), ptr(mean), ptr(count), ptr(sums), ptr(work),
                                               current_stream()), 'cloud_knn_distances')
     return mean, count, sums
@@ -324,11 +324,11 @@ def distance_stats(points, d2, idx, thresholds):
     median = torch.full((1,), float('nan'), dtype=torch.float64, device=device)
     if n > 0:
         with torch.cuda.device(device):
-            work = torch.empty(int(lib.d3r_cloud_distance_stats_workspace_bytes(n)), dtype=torch.uint8, device=device)
+            work = _lib.workspace(lib.d3r_cloud_distance_stats_workspace_bytes(n), device)
             check(lib.d3r_cloud_distance_stats(n, ptr(points), ptr(d2), ptr(idx), len(tau), (C.c_float * max(len(tau), 1))(*tau), ptr(counts), ptr(sums),
                                                ptr(work), current_stream()), 'cloud_distance_stats')
             found = (idx >= 0).to(torch.uint8)
-            work = torch.empty(int(lib.d3r_pair_criterion_workspace_bytes(1, n)), dtype=torch.uint8, device=device)
+            work = _lib.workspace(lib.d3r_pair_criterion_workspace_bytes(1, n), device)
             check(lib.d3r_masked_median(1, n, ptr(d2), None, ptr(found), None, ptr(median), ptr(work), current_stream()), 'masked_median')
     return counts, sums, median
 
@@ -535,7 +535,7 @@ def icp_sums(moved, ref, d2, idx, metric, gate, centre, ref_normals=None, moved_
     used = torch.zeros((n,), dtype=torch.uint8, device=device) if want_used else None
     if n > 0 and len(ref) > 0:
         with torch.cuda.device(device):
-            work = torch.empty(int(lib.d3r_cloud_icp_sums_workspace_bytes(n)), dtype=torch.uint8, device=device)
+            work = _lib.workspace(lib.d3r_cloud_icp_sums_workspace_bytes(n), device)
             check(lib.d3r_cloud_icp_sums(n, ptr(moved), ptr(moved_normals), len(ref), ptr(ref), ptr(ref_normals), ptr(d2), ptr(idx), METRICS[metric],
                                          float(gate), 0.0 if cos_min is None else float(cos_min), (C.c_float * 3)(*[float(c) for c in centre]),
                                          ptr(count), ptr(sums), ptr(used), ptr(work), current_stream()), 'cloud_icp_sums')
@@ -595,7 +595,7 @@ def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plan
         idx = torch.empty((n,), dtype=torch.int32, device=device)
         count = torch.zeros((1,), dtype=torch.int64, device=device)
         sums = torch.zeros((ICP_PLANE_SUMS if METRICS[metric] else ICP_POINT_SUMS,), dtype=torch.float64, device=device)
-        work = torch.empty(int(lib.d3r_cloud_icp_sums_workspace_bytes(n)), dtype=torch.uint8, device=device)
+        work = _lib.workspace(lib.d3r_cloud_icp_sums_workspace_bytes(n), device)
         centre_c = (C.c_float * 3)(*c.tolist())
         for stage, gate in enumerate(stages):
             first = default_r0(dst, gate) if r0 is None else r0

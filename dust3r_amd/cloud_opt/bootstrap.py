@@ -96,7 +96,7 @@ class PairMaps:
         npix_d = self._i32(npix)
         out = torch.empty((n, 17), dtype=torch.float64, device=self.dev)
         with torch.cuda.device(self.dev):
-            ws = torch.empty(int(lib.d3r_similarity_moments_workspace(n, max(npix))), dtype=torch.uint8, device=self.dev)
+            ws = _lib.workspace(lib.d3r_similarity_moments_workspace(n, max(npix)), self.dev)
             check(lib.d3r_similarity_moments(n, ptr(src), ptr(tgt), ptr(wgt), ptr(npix_d), max(npix), ptr(ws), ptr(out), current_stream()),
                   'similarity_moments')
         return out.cpu().numpy()
@@ -382,7 +382,7 @@ def solve_pnp_batch(dev, jobs, iterations=10, reproj_err=5.0, seed=0, refine_ite
     poses = np.stack([hyp[a, best[a]].reshape(3, 4) for a in range(n)]).astype(np.float64)
     best_count = counts[np.arange(n), best]
 
-    ws = torch.empty(int(lib.d3r_pnp_workspace(n)), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(lib.d3r_pnp_workspace(n), dev)
     sums = torch.empty((n, nv), dtype=torch.float64, device=dev)
 
     def gn_sums(P):

@@ -20,35 +20,16 @@
 // Sums are accumulated in fp32 per lane over at most 8 points, then in fp64 across lanes / workgroups in a fixed order (deterministic).
 #include "../../include/dust3r_hip.h"
 #include "kernels.hpp"
+#include "reduce.hpp"
 
 namespace d3r {
 
-D3R_DEV double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// Block-wide fixed-order sum of NV doubles per thread; result valid in thread 0 (returned in v[]). red: NW * NV doubles of LDS.
+// Block-wide fixed-order sum of NV doubles per thread (reduce.hpp); result valid in thread 0 (returned in v[]). red: NT / 64 * NV doubles of
+// LDS; the trailing barrier lets the caller reuse red. The combine starts from wave 0's value, not from 0.0: the same bits, because every
+// accumulator starts at +0.0 and an IEEE sum is -0.0 only when both operands are, so no wave's value is -0.0.
 template <int NV, int NT>
 D3R_DEV void block_sum_f64(double (&v)[NV], double* red) {
-    constexpr int NW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = wave_sum_f64(v[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[wave * NV + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            double s = 0.0;
-            for (int w = 0; w < NW; ++w) s += red[w * NV + k];
-            v[k] = s;
-        }
-    }
+    block_reduce_gather<NT, false>(v, red, Sum());
     __syncthreads();
 }
 
@@ -253,7 +234,7 @@ __global__ __launch_bounds__(256) void pnp_score_kernel(const PnpJob* jobs, cons
     for (int h = 0; h < PNP_MAXH; ++h) {
         int s = local[h];
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);      // not reduce.hpp's wave_reduce: at 256 VGPRs the kernel then spills
         if ((threadIdx.x & 63) == 0 && s) atomicAdd(&cnt[h], s);      // integer adds: order independent
     }
     __syncthreads();

@@ -1,7 +1,7 @@
 // dust3r_amd -- what cloud_nn.hip (the grid, the distance statistics), cloud_knn.hip (the search on the grid) and cloud_icp.hip (the
 // registration's sums) share: the layout of the grid's workspace, the checks of the cell size and the radius, the padded cell range's
-// arithmetic, the 1 x n shape table, and the ordered fp64 / int64 sum of all three: the workgroup's sum, the final kernel over the
-// per-workgroup partials and the partials' layout. As in fuse_grid.hpp every kernel is static, so each file launches its own copy.
+// arithmetic, the 1 x n shape table, and the ordered fp64 / int64 sum of all three: the workgroup's sum (reduce.hpp's reduction, whose
+// header states the order), the final kernel over the per-workgroup partials and the partials' layout. As in fuse_grid.hpp every kernel is static, so each file launches its own copy.
 #pragma once
 #include "common.hpp"
 #include "scene_common.hpp"
@@ -46,23 +46,17 @@ struct CloudWorkspace {
 
 static inline CloudWorkspace cloud_workspace(void* base, int n_ref, int n_query) {
     CloudWorkspace w;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* r = p ? p + off : nullptr;
-        off += align256(bytes);
-        return r;
-    };
-    w.shape = (int*)take(4 * sizeof(int));
-    w.ref = fuse_workspace(take(0), 1, n_ref, n_ref);
-    off += w.ref.bytes;
-    w.pts4 = (float4*)take((size_t)n_ref * sizeof(float4));
-    w.cell_key = (uint64_t*)take((size_t)n_ref * sizeof(uint64_t));
-    w.cell_start = (int*)take(((size_t)n_ref + 1) * sizeof(int));
-    w.qry = fuse_workspace(take(0), 1, n_query, n_query);
-    off += w.qry.bytes;
-    w.mask = (uint8_t*)take((size_t)n_query);
-    w.bytes = off;
+    Carver c(base);
+    w.shape = c.take<int>(4);
+    w.ref = fuse_workspace(c.take<char>(0), 1, n_ref, n_ref);
+    c.bytes += w.ref.bytes;
+    w.pts4 = c.take<float4>(n_ref);
+    w.cell_key = c.take<uint64_t>(n_ref);
+    w.cell_start = c.take<int>((size_t)n_ref + 1);
+    w.qry = fuse_workspace(c.take<char>(0), 1, n_query, n_query);
+    c.bytes += w.qry.bytes;
+    w.mask = c.take<uint8_t>(n_query);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -73,43 +67,23 @@ static inline bool cloud_radius_ok(float r) {
     const float r2 = r * r;                                             // host code of files built without contraction: one fp32 product
     return r > 0.f && r2 >= 1.17549435e-38f && r2 <= 3.4028234e38f;
 }
-static inline int cloud_blocks(long long n) { return fuse_blocks(fuse_tiles(n, QT)); }
+static inline int cloud_blocks(long long n) { return blocks_of(tiles_of(n, QT), MAX_BLOCKS); }
 
 // ---- the ordered sum: ND doubles and NI int64s per thread -> per workgroup -> one row -------------------------------------------------------
 constexpr int SUM_PARTS = 1024;         // grid cap of a pass that leaves partials = the rows the final kernel reads
 
-// The workgroup's totals of sd / si, column k written to out_d[k] / out_i[k]: the wave's sums by an xor butterfly 32..1, then column k by
-// thread k over the waves 0..3 in order. A fixed shape: the same bytes whatever the run. Once per kernel (it owns its LDS).
+// The workgroup's totals of sd / si, column k written to out_d[k] / out_i[k] by thread k: reduce.hpp's workgroup reduction of both types
+// behind one barrier. A fixed shape: the same bytes whatever the run. Once per kernel (it owns its LDS).
 template <int ND, int NI>
 D3R_DEV void cloud_block_sum(double (&sd)[ND], long long (&si)[NI], double* out_d, long long* out_i) {
     static_assert(ND <= QT && NI <= QT, "one thread per column");
     __shared__ double lds_d[QT / 64 * ND];
     __shared__ long long lds_i[QT / 64 * NI];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < ND; ++k) sd[k] += __shfl_xor(sd[k], o);
-#pragma unroll
-        for (int k = 0; k < NI; ++k) si[k] += __shfl_xor(si[k], o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < ND; ++k) lds_d[wave * ND + k] = sd[k];
-#pragma unroll
-        for (int k = 0; k < NI; ++k) lds_i[wave * NI + k] = si[k];
-    }
+    block_reduce_stage(si, lds_i, Sum());                                // the integers first: after the 18 fp64 columns, cloud_icp_sums_kernel<0> needs 82 VGPRs for 80
+    block_reduce_stage(sd, lds_d, Sum());
     __syncthreads();
-    if (threadIdx.x < ND) {
-        double t = lds_d[threadIdx.x];
-        for (int w = 1; w < QT / 64; ++w) t += lds_d[w * ND + threadIdx.x];
-        out_d[threadIdx.x] = t;
-    }
-    if (threadIdx.x < NI) {
-        long long c = lds_i[threadIdx.x];
-        for (int w = 1; w < QT / 64; ++w) c += lds_i[w * NI + threadIdx.x];
-        out_i[threadIdx.x] = c;
-    }
+    if (threadIdx.x < ND) out_d[threadIdx.x] = block_reduce_column<QT, ND>(lds_d, threadIdx.x, Sum());
+    if (threadIdx.x < NI) out_i[threadIdx.x] = block_reduce_column<QT, NI>(lds_i, threadIdx.x, Sum());
 }
 
 // one workgroup adds the partials: thread t the rows t, t + QT, ... in index order, then the workgroup's sum
@@ -140,11 +114,11 @@ struct SumParts {
 
 static inline SumParts cloud_sum_parts(void* base, int n, int nd, int ni) {
     SumParts p;
+    Carver c(base);
     p.parts = std::min(cloud_blocks(n), SUM_PARTS);
-    const size_t d_bytes = align256((size_t)p.parts * nd * sizeof(double));
-    p.d = (double*)base;
-    p.i = base ? (long long*)((char*)base + d_bytes) : nullptr;
-    p.bytes = d_bytes + align256((size_t)p.parts * ni * sizeof(long long));
+    p.d = c.take<double>((size_t)p.parts * nd);
+    p.i = c.take<long long>((size_t)p.parts * ni);
+    p.bytes = c.bytes;
     return p;
 }
 

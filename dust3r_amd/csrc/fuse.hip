@@ -36,64 +36,22 @@ __global__ __launch_bounds__(NT) void fuse_bounds_kernel(const float* __restrict
     const size_t base = (size_t)v * row;
     float b[6];
     bounds_init(b);
-    int cnt = 0;
+    int cnt[1] = {0};
     for (long long e = (long long)blockIdx.x * NT + threadIdx.x; e < area; e += (long long)gridDim.x * NT) {
         if (valid_at(pts, mask, weight, base + e)) {
             bounds_add(b, pts + 3 * (base + e));
-            ++cnt;
+            ++cnt[0];
         }
     }
     const size_t part = (size_t)v * gridDim.x + blockIdx.x;
     block_bounds(b, lds_b, partials + part * 6);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < WAVES; ++w) s += wave_cnt[w];
-        part_cnt[part] = s;
-    }
+    block_reduce_gather<NT, false>(cnt, wave_cnt, Sum());
+    if (threadIdx.x == 0) part_cnt[part] = cnt[0];
 }
 
 __global__ __launch_bounds__(256) void fuse_bounds_final_kernel(int n_parts, const float* __restrict__ partials, const int* __restrict__ part_cnt,
                                                                float* __restrict__ bounds_out, long long* __restrict__ count_out) {
-    __shared__ float lds[4][6];
-    __shared__ long long lds_n[4];
-    float b[6];
-    bounds_init(b);
-    long long n = 0;
-    for (int i = threadIdx.x; i < n_parts; i += 256) {
-        const float* p = partials + (size_t)i * 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            b[c] = fminf(b[c], p[c]);
-            b[3 + c] = fmaxf(b[3 + c], p[3 + c]);
-        }
-        n += part_cnt[i];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            const float t = __shfl_xor(b[c], o);
-            b[c] = c < 3 ? fminf(b[c], t) : fmaxf(b[c], t);
-        }
-        n += __shfl_xor(n, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) lds[threadIdx.x >> 6][c] = b[c];
-        lds_n[threadIdx.x >> 6] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x;
-        float r = lds[0][c];
-        for (int w = 1; w < 4; ++w) r = c < 3 ? fminf(r, lds[w][c]) : fmaxf(r, lds[w][c]);
-        bounds_out[c] = r;
-    }
-    if (threadIdx.x == 6) *count_out = lds_n[0] + lds_n[1] + lds_n[2] + lds_n[3];
+    bounds_final<true>(n_parts, partials, part_cnt, bounds_out, count_out);
 }
 
 // voxel j = the sorted pairs [starts[j], starts[j + 1]) (the last: up to N), walked in order
@@ -137,12 +95,16 @@ __global__ __launch_bounds__(256) void fuse_reduce_kernel(const int* __restrict_
 }  // namespace fuse
 }  // namespace d3r
 
+using namespace d3r;
 using namespace d3r::fuse;
 
 extern "C" size_t d3r_fuse_bounds_workspace_bytes(int n_views, int row) {
     if (n_views <= 0 || row <= 0) return 0;
-    const size_t parts = (size_t)n_views * fuse_blocks(fuse_tiles(row, NT));
-    return align256(parts * 6 * sizeof(float)) + align256(parts * sizeof(int));
+    const size_t parts = (size_t)n_views * blocks_of(tiles_of(row, NT), MAX_BLOCKS);
+    Carver c(nullptr);                                                  // as d3r_fuse_bounds carves it
+    c.take<float>(parts * 6);
+    c.take<int>(parts);
+    return c.bytes;
 }
 
 extern "C" int d3r_fuse_bounds(int n_views, const float* pts, const uint8_t* mask, const float* weight, const int* img_h_dev, const int* img_w_dev, int row,
@@ -151,10 +113,11 @@ extern "C" int d3r_fuse_bounds(int n_views, const float* pts, const uint8_t* mas
         !bounds_out || !count_out || !workspace)
         return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const int bx = fuse_blocks(fuse_tiles(row, NT));
+    const int bx = blocks_of(tiles_of(row, NT), MAX_BLOCKS);
     const size_t parts = (size_t)n_views * bx;
-    float* partials = (float*)workspace;
-    int* part_cnt = (int*)((char*)workspace + align256(parts * 6 * sizeof(float)));
+    Carver c(workspace);
+    float* partials = c.take<float>(parts * 6);
+    int* part_cnt = c.take<int>(parts);
     hipLaunchKernelGGL(fuse_bounds_kernel, dim3(bx, n_views), dim3(NT), 0, st, pts, mask, weight, img_h_dev, img_w_dev, row, partials, part_cnt);
     hipLaunchKernelGGL(fuse_bounds_final_kernel, dim3(1), dim3(256), 0, st, (int)parts, partials, part_cnt, bounds_out, count_out);
     return rc_of(hipGetLastError());
@@ -182,7 +145,7 @@ extern "C" int d3r_fuse_voxels(int n_views, const float* pts, const uint8_t* mas
     const int cur = fuse_key_and_sort(a, w, n_views, capacity, total_bits, st);
     const int* starts = fuse_segment_heads(a, w, cur, capacity, st);
     // 4. reduce
-    hipLaunchKernelGGL(fuse_reduce_kernel, dim3(fuse_blocks(fuse_tiles(capacity, 256))), dim3(256), 0, st, w.idx[cur], starts, w.n_dev, w.n_dev + 1, capacity,
+    hipLaunchKernelGGL(fuse_reduce_kernel, dim3(blocks_of(tiles_of(capacity, 256), MAX_BLOCKS)), dim3(256), 0, st, w.idx[cur], starts, w.n_dev, w.n_dev + 1, capacity,
                        pts, weight, rgb, rgb_is_u8, positions_out, colors_out, weight_out, count_out, totals_out);
     return rc_of(hipGetLastError());
 }

@@ -13,7 +13,8 @@
 //      fuse_scatter_kernel (rank inside the tile from wave ballots, tiles in order)
 //   3. segment heads: key[i] != key[i - 1], compacted with the pattern of stage 1 (fuse_flag_kernel<HEADS, ...>)
 // No kernel waits on another workgroup: every scan over tiles is a launch of its own (ONE workgroup, chunks in order), there is no
-// atomic, no look-back, no grid barrier. Integer placement only: the same bytes on every run.
+// atomic, no look-back, no grid barrier. Integer placement only: the same bytes on every run. The workspace's carving and the grid
+// arithmetic (tiles_of / blocks_of, capped at MAX_BLOCKS here) are reduce.hpp's.
 #pragma once
 #include <algorithm>
 #include "common.hpp"
@@ -71,6 +72,8 @@ static __global__ __launch_bounds__(NT) void fuse_scan_kernel(int* __restrict__ 
     for (int base = 0; base < L; base += NT) {
         const int i = base + threadIdx.x;
         const int x = i < L ? a[i] : 0;
+        // reduce.hpp's wave_scan_inclusive, written out: through the call the compiler orders the same instructions differently, and every
+        // grid build and d3r_fuse_voxels measured 0.5 % slower (this kernel runs once per sort pass)
         int inc = x;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -223,8 +226,6 @@ static __global__ __launch_bounds__(NT) void fuse_scatter_kernel(const uint64_t*
     }
 }
 
-static inline long long fuse_tiles(long long n, int per) { return (n + per - 1) / per; }
-static inline int fuse_blocks(long long tiles) { return (int)std::max(1LL, std::min(tiles, (long long)MAX_BLOCKS)); }
 
 struct FuseWorkspace {
     int* tile_cnt;          // [max(n tiles_per_view, ceil(cap / NT))]: the tile counts of stage 1, then of stage 3
@@ -237,30 +238,22 @@ struct FuseWorkspace {
 
 static inline FuseWorkspace fuse_workspace(void* base, int n_views, int row, int cap) {
     FuseWorkspace w;
-    char* p = (char*)base;
-    const long long t1 = (long long)n_views * fuse_tiles(row, NT), t3 = fuse_tiles(cap, NT), ts = fuse_tiles(cap, SUB * NT);
-    const size_t sizes[7] = {(size_t)std::max(t1, t3) * sizeof(int), (size_t)ts * DIGITS * sizeof(int), 2 * sizeof(int), (size_t)cap * sizeof(uint64_t),
-                             (size_t)cap * sizeof(uint64_t), (size_t)cap * sizeof(int), (size_t)cap * sizeof(int)};
-    void* ptrs[7];
-    size_t off = 0;
-    for (int i = 0; i < 7; ++i) {
-        ptrs[i] = p ? p + off : nullptr;
-        off += align256(sizes[i]);
-    }
-    w.tile_cnt = (int*)ptrs[0];
-    w.hist = (int*)ptrs[1];
-    w.n_dev = (int*)ptrs[2];
-    w.keys[0] = (uint64_t*)ptrs[3];
-    w.keys[1] = (uint64_t*)ptrs[4];
-    w.idx[0] = (int*)ptrs[5];
-    w.idx[1] = (int*)ptrs[6];
-    w.bytes = off;
+    Carver c(base);
+    const long long t1 = (long long)n_views * tiles_of(row, NT), t3 = tiles_of(cap, NT), ts = tiles_of(cap, SUB * NT);
+    w.tile_cnt = c.take<int>((size_t)std::max(t1, t3));
+    w.hist = c.take<int>((size_t)ts * DIGITS);
+    w.n_dev = c.take<int>(2);
+    w.keys[0] = c.take<uint64_t>(cap);
+    w.keys[1] = c.take<uint64_t>(cap);
+    w.idx[0] = c.take<int>(cap);
+    w.idx[1] = c.take<int>(cap);
+    w.bytes = c.bytes;
     return w;
 }
 
 static inline bool fuse_shape_ok(int n_views, int row, int capacity) {
     return n_views > 0 && n_views <= 65535 && row > 0 && (long long)n_views * row <= 2147483647LL && capacity > 0 &&
-           (long long)n_views * fuse_tiles(row, NT) <= 2147483647LL / DIGITS;
+           (long long)n_views * tiles_of(row, NT) <= 2147483647LL / DIGITS;
 }
 
 // lo, voxel and bits into the key's parameters; false when a bit count is outside [1, 21] or lo is not finite. *total_bits: their sum
@@ -282,11 +275,11 @@ static inline bool fuse_key_params(const float* lo, float voxel, const int* bits
 // buffers; hist: [16][ceil(capacity / (SUB NT))]. Returns the buffer the sort ends in (cur itself for total_bits <= 0).
 static inline int fuse_sort_pairs(uint64_t* const (&keys)[2], int* const (&idx)[2], int* hist, const int* n_dev, int capacity, int total_bits, int cur,
                                   hipStream_t st) {
-    const int ts = (int)fuse_tiles(capacity, SUB * NT);
+    const int ts = (int)tiles_of(capacity, SUB * NT);
     for (int shift = 0; shift < total_bits; shift += DIGIT_BITS, cur ^= 1) {
-        hipLaunchKernelGGL(fuse_hist_kernel, dim3(fuse_blocks(ts)), dim3(NT), 0, st, keys[cur], n_dev, capacity, shift, ts, hist);
+        hipLaunchKernelGGL(fuse_hist_kernel, dim3(blocks_of(ts, MAX_BLOCKS)), dim3(NT), 0, st, keys[cur], n_dev, capacity, shift, ts, hist);
         hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(NT), 0, st, hist, ts * DIGITS, (int*)nullptr);
-        hipLaunchKernelGGL(fuse_scatter_kernel, dim3(fuse_blocks(ts)), dim3(NT), 0, st, keys[cur], idx[cur], n_dev, capacity, shift, ts, hist, keys[cur ^ 1],
+        hipLaunchKernelGGL(fuse_scatter_kernel, dim3(blocks_of(ts, MAX_BLOCKS)), dim3(NT), 0, st, keys[cur], idx[cur], n_dev, capacity, shift, ts, hist, keys[cur ^ 1],
                            idx[cur ^ 1]);
     }
     return cur;
@@ -295,13 +288,13 @@ static inline int fuse_sort_pairs(uint64_t* const (&keys)[2], int* const (&idx)[
 // Stages 1 and 2 on the stream: a (pts, mask, weight, img_h, img_w, row, key set by the caller) keyed and compacted into w, then sorted.
 // Returns the buffer the sort ends in: w.keys[cur] / w.idx[cur] hold the w.n_dev[0] sorted pairs.
 static inline int fuse_key_and_sort(FlagArgs& a, const FuseWorkspace& w, int n_views, int capacity, int total_bits, hipStream_t st) {
-    const int tpv = (int)fuse_tiles(a.row, NT);
+    const int tpv = (int)tiles_of(a.row, NT);
     const long long t1 = (long long)n_views * tpv;
     a.tiles_per_view = tpv; a.sorted = nullptr; a.n_dev = w.n_dev; a.cap = capacity;
     // 1. key and compact
-    hipLaunchKernelGGL((fuse_flag_kernel<KEYS, false>), dim3(fuse_blocks(t1)), dim3(NT), 0, st, a, t1, w.tile_cnt, w.keys[0], w.idx[0]);
+    hipLaunchKernelGGL((fuse_flag_kernel<KEYS, false>), dim3(blocks_of(t1, MAX_BLOCKS)), dim3(NT), 0, st, a, t1, w.tile_cnt, w.keys[0], w.idx[0]);
     hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(NT), 0, st, w.tile_cnt, (int)t1, w.n_dev);
-    hipLaunchKernelGGL((fuse_flag_kernel<KEYS, true>), dim3(fuse_blocks(t1)), dim3(NT), 0, st, a, t1, w.tile_cnt, w.keys[0], w.idx[0]);
+    hipLaunchKernelGGL((fuse_flag_kernel<KEYS, true>), dim3(blocks_of(t1, MAX_BLOCKS)), dim3(NT), 0, st, a, t1, w.tile_cnt, w.keys[0], w.idx[0]);
     // 2. the sort: pass k orders by bits [4 k, 4 k + 4) of the key
     return fuse_sort_pairs(w.keys, w.idx, w.hist, w.n_dev, capacity, total_bits, 0, st);
 }
@@ -309,12 +302,12 @@ static inline int fuse_key_and_sort(FlagArgs& a, const FuseWorkspace& w, int n_v
 // Stage 3 on the stream: the segment heads of the sorted keys w.keys[cur], into the index buffer the sort left free (returned); their
 // number -> w.n_dev[1]
 static inline int* fuse_segment_heads(FlagArgs& a, const FuseWorkspace& w, int cur, int capacity, hipStream_t st) {
-    const long long t3 = fuse_tiles(capacity, NT);
+    const long long t3 = tiles_of(capacity, NT);
     int* starts = w.idx[cur ^ 1];
     a.sorted = w.keys[cur];
-    hipLaunchKernelGGL((fuse_flag_kernel<HEADS, false>), dim3(fuse_blocks(t3)), dim3(NT), 0, st, a, t3, w.tile_cnt, (uint64_t*)nullptr, starts);
+    hipLaunchKernelGGL((fuse_flag_kernel<HEADS, false>), dim3(blocks_of(t3, MAX_BLOCKS)), dim3(NT), 0, st, a, t3, w.tile_cnt, (uint64_t*)nullptr, starts);
     hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(NT), 0, st, w.tile_cnt, (int)t3, w.n_dev + 1);
-    hipLaunchKernelGGL((fuse_flag_kernel<HEADS, true>), dim3(fuse_blocks(t3)), dim3(NT), 0, st, a, t3, w.tile_cnt, (uint64_t*)nullptr, starts);
+    hipLaunchKernelGGL((fuse_flag_kernel<HEADS, true>), dim3(blocks_of(t3, MAX_BLOCKS)), dim3(NT), 0, st, a, t3, w.tile_cnt, (uint64_t*)nullptr, starts);
     return starts;
 }
 

@@ -17,6 +17,7 @@
 // the sum of the affine map separately, so no FMA may be formed from them.
 #include "../../include/dust3r_hip.h"
 #include "common.hpp"
+#include "reduce.hpp"
 #include "gallery_math.hpp"
 
 namespace d3r {
@@ -32,32 +33,16 @@ D3R_DEV int npix_of(const int* __restrict__ npix, unsigned img, int max_area) {
     return a >= 0 && a <= max_area ? a : 0;
 }
 
-// the workgroup's maxima -> every thread (red: 2 * NT / 64 floats of LDS)
-D3R_DEV void block_max2(float& a, float& b, float (*red)[NT / 64]) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a = nan_max(a, __shfl_xor(a, o));
-        b = nan_max(b, __shfl_xor(b, o));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = a;
-        red[1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    a = red[0][0];
-    b = red[1][0];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) {
-        a = nan_max(a, red[0][w]);
-        b = nan_max(b, red[1][w]);
-    }
+// the workgroup's maxima -> every thread (red: 2 * NT / 64 floats of LDS), in the order of reduce.hpp
+D3R_DEV void block_max2(float (&m)[2], float* red) {
+    block_reduce_gather<NT, true>(m, red, [](float a, float b, int) { return nan_max(a, b); });
 }
 
 __global__ __launch_bounds__(NT) void gallery_max_kernel(const float* __restrict__ depth, const float* __restrict__ conf, const int* __restrict__ npix,
                                                          int n_imgs, int max_area, float* __restrict__ partials) {
-    __shared__ float red[2][NT / 64];
+    __shared__ float red[2 * NT / 64];
     const unsigned vpr = (unsigned)max_area / VEC, total = (unsigned)n_imgs * vpr;      // groups per row, groups in all (< 2^31: checked by the host)
-    float md = -__builtin_huge_valf(), mc = -__builtin_huge_valf();
+    float m[2] = {-__builtin_huge_valf(), -__builtin_huge_valf()};                      // depth, confidence
     for (unsigned g = blockIdx.x * NT + threadIdx.x; g < total; g += gridDim.x * NT) {
         const unsigned img = g / vpr;
         const int p = (int)(g - img * vpr) * VEC, a = npix_of(npix, img, max_area);
@@ -68,15 +53,15 @@ __global__ __launch_bounds__(NT) void gallery_max_kernel(const float* __restrict
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             if (p + k < a) {
-                md = nan_max(md, dv[k]);
-                mc = nan_max(mc, cv[k]);
+                m[0] = nan_max(m[0], dv[k]);
+                m[1] = nan_max(m[1], cv[k]);
             }
         }
     }
-    block_max2(md, mc, red);
+    block_max2(m, red);
     if (threadIdx.x == 0) {
-        partials[blockIdx.x] = md;
-        partials[gridDim.x + blockIdx.x] = mc;
+        partials[blockIdx.x] = m[0];
+        partials[gridDim.x + blockIdx.x] = m[1];
     }
 }
 
@@ -90,14 +75,15 @@ __global__ __launch_bounds__(NT) void gallery_image_kernel(const float* __restri
                                                            const float4* __restrict__ table, float* __restrict__ depth_img, float4* __restrict__ conf_img,
                                                            float* __restrict__ maxima_out) {
     __shared__ float4 lut[LUT_ROWS];
-    __shared__ float red[2][NT / 64];
+    __shared__ float red[2 * NT / 64];
     for (int i = threadIdx.x; i < LUT_ROWS; i += NT) lut[i] = table[i];
-    float dmax = -__builtin_huge_valf(), cmax = -__builtin_huge_valf();
+    float m[2] = {-__builtin_huge_valf(), -__builtin_huge_valf()};
     for (int i = threadIdx.x; i < n_parts; i += NT) {
-        dmax = nan_max(dmax, partials[i]);
-        cmax = nan_max(cmax, partials[n_parts + i]);
+        m[0] = nan_max(m[0], partials[i]);
+        m[1] = nan_max(m[1], partials[n_parts + i]);
     }
-    block_max2(dmax, cmax, red);                           // its barrier also publishes lut
+    block_max2(m, red);                                    // its barrier also publishes lut
+    const float dmax = m[0], cmax = m[1];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         maxima_out[0] = dmax;
         maxima_out[1] = cmax;
@@ -139,7 +125,7 @@ static bool gallery_shape_ok(int n_imgs, int max_area) {
 
 static int gallery_blocks(int n_imgs, int max_area) {
     const long long groups = (long long)n_imgs * (max_area / VEC);
-    return (int)std::min<long long>((groups + NT - 1) / NT, MAX_BLOCKS);
+    return d3r::blocks_of(d3r::tiles_of(groups, NT), MAX_BLOCKS);
 }
 
 extern "C" void d3r_scene_gallery_launch_bound(int* max_blocks, int* threads, int* pixels_per_thread) {

@@ -17,6 +17,7 @@
 // Non-finite values at VALID pixels are outside the contract (a NaN would be keyed like a large number).
 #include "../../include/dust3r_hip.h"
 #include "common.hpp"
+#include "reduce.hpp"
 #include <algorithm>
 
 namespace d3r {
@@ -138,19 +139,6 @@ template <bool VEC> D3R_DEV void store_f4(float* base, int p0, int N, const floa
     }
 }
 
-// sum over the workgroup in a fixed order: shuffle tree inside a wave, then the waves in order. Every thread calls it; thread 0 holds the result.
-D3R_DEV double block_sum(double v, double* lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < NT / 64; ++w) r += lds[w];
-    return r;
-}
-
 D3R_DEV void hist_add(uint32_t* lh, int s, uint32_t key, uint32_t prefix, uint32_t hmask, int shift, uint32_t bmask) {
     if ((key & hmask) == prefix) atomicAdd(&lh[s * BINS + ((key >> shift) & bmask)], 1u);
 }
@@ -169,7 +157,7 @@ __global__ __launch_bounds__(NT) void pass_kernel(const Args a) {
     constexpr int S = MODE == M_SEL_CENTER ? 6 : (SELECT ? 2 : 0);
     constexpr int C = S / 2;                   // selections per side
     __shared__ uint32_t lh[SELECT ? S * BINS : 1];
-    __shared__ double red[NT / 64];
+    __shared__ double red[NT / 64 * 3];
     const int b = blockIdx.y, v = blockIdx.z, N = a.N;
     const float* gt = (v ? a.gt2 : a.gt1) + (size_t)b * N * 3;
     const float* pr = (v ? a.pr2 : a.pr1) + (size_t)b * N * 3;
@@ -260,8 +248,12 @@ __global__ __launch_bounds__(NT) void pass_kernel(const Args a) {
         hist_flush(lh, a.hist + (size_t)b * MAXSEL * BINS, S * BINS);
     } else {
         double* part = a.partial + (((size_t)b * 2 + v) * MAXGX + blockIdx.x) * 4;
-        const double r0 = block_sum(acc0, red), r1 = block_sum(acc1, red), r2 = block_sum(acc2, red);
-        if (threadIdx.x == 0) { part[0] = r0; part[1] = r1; part[2] = r2; part[3] = 0.0; }
+        // The workgroup's three sums in reduce.hpp's fixed order, in thread 0: bit for bit what a __shfl_down ladder 32..1 read in lane 0 (the
+        // butterfly's tree for lane 0) and a combine started from 0.0 give, since every accumulator starts at +0.0 and an IEEE sum is -0.0
+        // only when both operands are.
+        double acc[3] = {acc0, acc1, acc2};
+        block_reduce_gather<NT, false>(acc, red, Sum());
+        if (threadIdx.x == 0) { part[0] = acc[0]; part[1] = acc[1]; part[2] = acc[2]; part[3] = 0.0; }
     }
 }
 
@@ -393,15 +385,27 @@ __global__ void drop_gt_norm_kernel(double* out, int B) {
 
 using namespace d3r::losses;
 
-static size_t hist_bytes(int B) { return align256((size_t)B * MAXSEL * BINS * sizeof(uint32_t)); }
-static size_t sel_bytes(int B) { return align256((size_t)B * MAXSEL * 2 * sizeof(uint32_t)); }
-static size_t partial_bytes(int B) { return align256((size_t)B * 2 * MAXGX * 4 * sizeof(double)); }
+struct LossWorkspace {
+    uint32_t *hist, *sel;   // [B][MAXSEL][BINS], [B][MAXSEL][2]: zeroed at the start of a call, `clear` bytes from hist
+    double* partial;        // [B][2][MAXGX][4]
+    size_t clear, bytes;
+};
+static LossWorkspace loss_workspace(void* base, int B) {
+    LossWorkspace w;
+    d3r::Carver c(base);
+    w.hist = c.take<uint32_t>((size_t)B * MAXSEL * BINS);
+    w.sel = c.take<uint32_t>((size_t)B * MAXSEL * 2);
+    w.clear = c.bytes;
+    w.partial = c.take<double>((size_t)B * 2 * MAXGX * 4);
+    w.bytes = c.bytes;
+    return w;
+}
 static int grid_x(int N) { return (int)std::min<long long>(((long long)N + NT * 4 - 1) / (NT * 4), MAXGX); }
 static bool aligned(const void* p, size_t a) { return ((size_t)p % a) == 0; }
 
 extern "C" size_t d3r_pair_criterion_workspace_bytes(int B, int N) {
     if (B <= 0 || N <= 0) return 0;
-    return hist_bytes(B) + sel_bytes(B) + partial_bytes(B);
+    return loss_workspace(nullptr, B).bytes;
 }
 
 extern "C" int d3r_pair_criterion_passes(const d3r_criterion_opts* o) {
@@ -444,16 +448,15 @@ extern "C" int d3r_pair_criterion(int B, int N, const float* gt_pts1, const floa
     a.gt1 = gt_pts1; a.gt2 = gt_pts2; a.pr1 = pr_pts1; a.pr2 = pr_pts2; a.pose = inv_pose1; a.m1 = valid1; a.m2 = valid2;
     a.conf1 = o->use_conf ? conf1 : nullptr; a.conf2 = o->use_conf ? conf2 : nullptr;
     a.out = out;
-    a.hist = (uint32_t*)workspace;
-    a.sel = (uint32_t*)((char*)workspace + hist_bytes(B));
-    a.partial = (double*)((char*)workspace + hist_bytes(B) + sel_bytes(B));
+    const LossWorkspace w = loss_workspace(workspace, B);
+    a.hist = w.hist; a.sel = w.sel; a.partial = w.partial;
     a.map1 = map1; a.map2 = map2;
     a.N = N; a.norm_mode = o->norm_mode; a.has_clip = o->has_dist_clip; a.clip = o->dist_clip; a.alpha = o->use_conf ? o->alpha : 0.f;
     a.apply = 0u; a.digit = 0;
     // 16-byte loads: every pair's rows start on 16 bytes (masks: 4) when N % 4 == 0 and the tensors do
     bool vec = N % 4 == 0 && aligned(gt_pts1, 16) && aligned(pr_pts1, 16) && aligned(valid1, 4) && aligned(gt_pts2, 16) && aligned(pr_pts2, 16) &&
                aligned(valid2, 4) && aligned(conf1, 16) && aligned(conf2, 16) && aligned(map1, 16) && aligned(map2, 16);
-    if (hipMemsetAsync(a.hist, 0, hist_bytes(B) + sel_bytes(B), st) != hipSuccess) return D3R_ERR_LAUNCH;
+    if (hipMemsetAsync(w.hist, 0, w.clear, st) != hipSuccess) return D3R_ERR_LAUNCH;
     const int gx = grid_x(N);
     const bool norm = o->norm_mode != D3R_NORM_NONE, norm_gt = norm && !o->gt_scale;
 
@@ -486,9 +489,9 @@ extern "C" int d3r_masked_median(int B, int N, const float* vals1, const float* 
                                  void* workspace, void* stream) {
     if (B <= 0 || B > 65535 || N <= 0 || N > (1 << 28) || !vals1 || !out || !workspace) return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    uint32_t* hist = (uint32_t*)workspace;
-    uint32_t* sel = (uint32_t*)((char*)workspace + hist_bytes(B));
-    if (hipMemsetAsync(hist, 0, hist_bytes(B) + sel_bytes(B), st) != hipSuccess) return D3R_ERR_LAUNCH;
+    const LossWorkspace w = loss_workspace(workspace, B);
+    uint32_t *hist = w.hist, *sel = w.sel;
+    if (hipMemsetAsync(hist, 0, w.clear, st) != hipSuccess) return D3R_ERR_LAUNCH;
     const bool vec = N % 4 == 0 && aligned(vals1, 16) && aligned(vals2, 16) && aligned(mask1, 4) && aligned(mask2, 4);
     const dim3 grid(grid_x(N), B, vals2 ? 2 : 1);
     for (int d = 0; d < 3; ++d) {

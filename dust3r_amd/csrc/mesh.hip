@@ -78,12 +78,7 @@ __global__ __launch_bounds__(64) void mesh_scan_tiles_kernel(const int* __restri
     for (int t0 = 0; t0 < tiles; t0 += 64) {
         const int t = t0 + lane;
         const int u = t < tiles ? c[2 * t] : 0, l = t < tiles ? c[2 * t + 1] : 0;
-        int iu = u, il = l;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int a = __shfl_up(iu, o), b = __shfl_up(il, o);
-            if (lane >= o) { iu += a; il += b; }
-        }
+        const int iu = wave_scan_inclusive(u, lane), il = wave_scan_inclusive(l, lane);
         if (t < tiles) {
             c[2 * t] = run_u + iu - u;
             c[2 * t + 1] = run_l + il - l;
@@ -110,12 +105,7 @@ __global__ __launch_bounds__(64) void mesh_scan_views_kernel(int n_views, const 
             f = PC ? (long long)view_tot[2 * v] : 2 * ((long long)view_tot[2 * v] + view_tot[2 * v + 1]);
             a = area_of(img_h[v], img_w[v], max_area);
         }
-        long long fi = f, ai = a;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long x = __shfl_up(fi, o), y = __shfl_up(ai, o);
-            if (lane >= o) { fi += x; ai += y; }
-        }
+        const long long fi = wave_scan_inclusive(f, lane), ai = wave_scan_inclusive(a, lane);
         if (v < n_views) {
             view_off[v] = run_f + fi - f;
             vert_off[v] = run_v + ai - a;
@@ -229,46 +219,18 @@ __global__ __launch_bounds__(NT) void mesh_color_kernel(const float* __restrict_
 }
 
 __global__ __launch_bounds__(256) void mesh_bounds_kernel(int n_parts, const float* __restrict__ partials, float* __restrict__ bounds_out) {
-    __shared__ float lds[4][6];
-    float b[6];
-    bounds_init(b);
-    for (int i = threadIdx.x; i < n_parts; i += 256) {
-        const float* p = partials + (size_t)i * 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            b[c] = fminf(b[c], p[c]);
-            b[3 + c] = fmaxf(b[3 + c], p[3 + c]);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            const float t = __shfl_xor(b[c], o);
-            b[c] = c < 3 ? fminf(b[c], t) : fmaxf(b[c], t);
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) lds[threadIdx.x >> 6][c] = b[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x;
-        float r = lds[0][c];
-        for (int w = 1; w < 4; ++w) r = c < 3 ? fminf(r, lds[w][c]) : fmaxf(r, lds[w][c]);
-        bounds_out[c] = r;
-    }
+    bounds_final<false>(n_parts, partials, nullptr, bounds_out, nullptr);
 }
 
 }  // namespace mesh
 }  // namespace d3r
 
+using namespace d3r;
 using namespace d3r::mesh;
 
 // grid.x of every tile / pixel launch, and the tiles a view can have: a 512 x 384 view has 192 tiles; grid-stride beyond 1024
-static int mesh_tiles(int max_area) { return (int)(((long long)max_area + NT - 1) / NT); }
-static int mesh_blocks(int max_area) { return std::min(mesh_tiles(max_area), 1024); }
+static int mesh_tiles(int max_area) { return (int)tiles_of(max_area, NT); }
+static int mesh_blocks(int max_area) { return blocks_of(mesh_tiles(max_area), 1024); }
 
 struct MeshWorkspace {
     int* tile_cnt;          // [n][max_tiles][2]
@@ -281,22 +243,13 @@ struct MeshWorkspace {
 
 static MeshWorkspace mesh_workspace(void* base, int n_views, int max_area) {
     MeshWorkspace w;
-    char* p = (char*)base;
-    const size_t sizes[5] = {(size_t)n_views * mesh_tiles(max_area) * 2 * sizeof(int), (size_t)n_views * 2 * sizeof(int),
-                             (size_t)n_views * sizeof(long long), (size_t)n_views * sizeof(long long),
-                             (size_t)n_views * mesh_blocks(max_area) * 6 * sizeof(float)};
-    void* ptrs[5];
-    size_t off = 0;
-    for (int i = 0; i < 5; ++i) {
-        ptrs[i] = p ? p + off : nullptr;
-        off += align256(sizes[i]);
-    }
-    w.tile_cnt = (int*)ptrs[0];
-    w.view_tot = (int*)ptrs[1];
-    w.view_off = (long long*)ptrs[2];
-    w.vert_off = (long long*)ptrs[3];
-    w.partials = (float*)ptrs[4];
-    w.bytes = off;
+    Carver c(base);
+    w.tile_cnt = c.take<int>((size_t)n_views * mesh_tiles(max_area) * 2);
+    w.view_tot = c.take<int>((size_t)n_views * 2);
+    w.view_off = c.take<long long>(n_views);
+    w.vert_off = c.take<long long>(n_views);
+    w.partials = c.take<float>((size_t)n_views * mesh_blocks(max_area) * 6);
+    w.bytes = c.bytes;
     return w;
 }
 

@@ -20,6 +20,7 @@
 // Kernel boundaries give the visibility between phases.
 #include "../../include/dust3r_hip.h"
 #include "common.hpp"
+#include "scene_common.hpp"
 
 namespace d3r {
 namespace sky {
@@ -59,8 +60,7 @@ D3R_DEV bool pixel_color(const void* rgb, int is_u8, size_t p) {
     return sky_color(to_u8(q[0]), to_u8(q[1]), to_u8(q[2]));
 }
 
-// an image's pixel count; 0 (the image is treated as empty) when its size is negative or does not fit its row of max_area
-D3R_DEV int area_of(int H, int W, int max_area) { return H >= 0 && W >= 0 && (long long)H * W <= max_area ? H * W : 0; }
+using scene::area_of;        // an image's pixel count, 0 when its size is negative or does not fit its row: shared with mesh.hip and fuse.hip
 
 __global__ __launch_bounds__(256) void sky_color_kernel(const void* __restrict__ rgb, int is_u8, const int* __restrict__ img_h,
                                                         const int* __restrict__ img_w, int max_area, uint8_t* __restrict__ out) {
@@ -257,8 +257,7 @@ __global__ __launch_bounds__(256) void sky_amax_kernel(const int* __restrict__ i
     int best = 0;
     for (int p = blockIdx.x * 256 + threadIdx.x; p < area; p += gridDim.x * 256)
         if (labels[base + p] == p) best = max(best, areas[base + p]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
+    best = wave_reduce(best, [](int a, int b) { return max(a, b); });
     if ((threadIdx.x & 63) == 0 && best > 0) atomicMax(amax + img, best);
 }
 
@@ -285,7 +284,7 @@ extern "C" size_t d3r_segment_sky_workspace_bytes(int n_imgs, int max_area) {
 }
 
 // grid.x of the pixel kernels: enough workgroups for a 512 x 384 image at 4 pixels per thread, grid-stride beyond
-static int pixel_blocks(int max_area) { return (int)std::min<long long>(((long long)max_area + 1023) / 1024, 1024); }
+static int pixel_blocks(int max_area) { return d3r::blocks_of(d3r::tiles_of(max_area, 1024), 1024); }
 
 extern "C" int d3r_sky_color_mask(int n_imgs, const void* rgb, int rgb_is_u8, const int* img_h_dev, const int* img_w_dev, int max_area,
                                   uint8_t* mask_out, void* stream) {

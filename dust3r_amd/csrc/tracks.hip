@@ -144,17 +144,10 @@ __global__ __launch_bounds__(WALK_NT) void tracks_walk_kernel(const WalkArgs a, 
 // *total_out = the sum of cnt[0, L) in 64 bits, one workgroup, a fixed order (integers: any order gives the same)
 __global__ __launch_bounds__(NT) void tracks_total_kernel(const int* __restrict__ cnt, int L, long long* __restrict__ total_out) {
     __shared__ long long wave_sums[WAVES];
-    long long s = 0;
-    for (long long i = threadIdx.x; i < L; i += NT) s += cnt[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int w = 0; w < WAVES; ++w) t += wave_sums[w];
-        *total_out = t;
-    }
+    long long s[1] = {0};
+    for (long long i = threadIdx.x; i < L; i += NT) s[0] += cnt[i];
+    block_reduce_gather<NT, false>(s, wave_sums, Sum());
+    if (threadIdx.x == 0) *total_out = s[0];
 }
 
 // sorted [T]: the views of the observations in image order. Thread k' <= T: the views (sorted[k' - 1], sorted[k']] start at k' (k' = T: the
@@ -188,20 +181,12 @@ struct TracksWorkspace {
 
 static inline TracksWorkspace tracks_workspace(void* base, int cap) {
     TracksWorkspace w;
-    char* p = (char*)base;
-    const size_t sizes[4] = {(size_t)cap * sizeof(uint64_t), (size_t)cap * sizeof(uint64_t), (size_t)cap * sizeof(int),
-                             (size_t)fuse_tiles(cap, SUB * NT) * DIGITS * sizeof(int)};
-    void* ptrs[4];
-    size_t off = 0;
-    for (int i = 0; i < 4; ++i) {
-        ptrs[i] = p ? p + off : nullptr;
-        off += align256(sizes[i]);
-    }
-    w.keys[0] = (uint64_t*)ptrs[0];
-    w.keys[1] = (uint64_t*)ptrs[1];
-    w.idx = (int*)ptrs[2];
-    w.hist = (int*)ptrs[3];
-    w.bytes = off;
+    Carver c(base);
+    w.keys[0] = c.take<uint64_t>(cap);
+    w.keys[1] = c.take<uint64_t>(cap);
+    w.idx = c.take<int>(cap);
+    w.hist = c.take<int>((size_t)tiles_of(cap, SUB * NT) * DIGITS);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -230,6 +215,7 @@ static inline int bit_length(unsigned x) {
 }  // namespace tracks
 }  // namespace d3r
 
+using namespace d3r;
 using namespace d3r::tracks;
 
 extern "C" size_t d3r_cloud_tracks_workspace_bytes(int capacity) {
@@ -245,7 +231,7 @@ extern "C" int d3r_cloud_tracks_count(int n_views, const float* pts, const uint8
         !seen_out || !total_out)
         return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL((tracks_walk_kernel<false>), dim3(fuse_blocks(fuse_tiles(n_points, WALK_NT))), dim3(WALK_NT), 0, st, a, point_off_out, seen_out, 0,
+    hipLaunchKernelGGL((tracks_walk_kernel<false>), dim3(blocks_of(tiles_of(n_points, WALK_NT), MAX_BLOCKS)), dim3(WALK_NT), 0, st, a, point_off_out, seen_out, 0,
                        (int*)nullptr, (int*)nullptr, (double*)nullptr, (uint64_t*)nullptr, (int*)nullptr);
     hipLaunchKernelGGL(tracks_total_kernel, dim3(1), dim3(NT), 0, st, point_off_out, n_points, total_out);
     hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(NT), 0, st, point_off_out, n_points + 1, (int*)nullptr);
@@ -270,10 +256,10 @@ extern "C" int d3r_cloud_tracks_fill(int n_views, const float* pts, const uint8_
     int* const idx[2] = {image_obs_out, w.idx};
     const int start = passes & 1;
     const int* n_dev = point_off + n_points;                           // T, as the count pass left it
-    hipLaunchKernelGGL((tracks_walk_kernel<true>), dim3(fuse_blocks(fuse_tiles(n_points, WALK_NT))), dim3(WALK_NT), 0, st, a, (int*)point_off, (uint32_t*)seen, capacity, view_out,
+    hipLaunchKernelGGL((tracks_walk_kernel<true>), dim3(blocks_of(tiles_of(n_points, WALK_NT), MAX_BLOCKS)), dim3(WALK_NT), 0, st, a, (int*)point_off, (uint32_t*)seen, capacity, view_out,
                        pixel_out, err2_out, keys[start], idx[start]);
     const int cur = fuse_sort_pairs(keys, idx, w.hist, n_dev, capacity, bits, start, st);      // cur == 0
-    const int blocks = fuse_blocks(fuse_tiles((long long)capacity + 1, WALK_NT));
+    const int blocks = blocks_of(tiles_of((long long)capacity + 1, WALK_NT), MAX_BLOCKS);
     hipLaunchKernelGGL(tracks_image_off_kernel, dim3(blocks), dim3(WALK_NT), 0, st, keys[cur], n_dev, capacity, n_views, image_off_out);
     hipLaunchKernelGGL(tracks_point2d_kernel, dim3(blocks), dim3(WALK_NT), 0, st, keys[cur], idx[cur], n_dev, capacity, n_views, image_off_out, point2d_out);
     return rc_of(hipGetLastError());

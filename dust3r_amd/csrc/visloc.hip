@@ -33,6 +33,7 @@
 // Every quantity of a job depends only on that job's record: the same bits whether it runs alone or in any batch.
 #include "../../include/dust3r_hip.h"
 #include "common.hpp"
+#include "reduce.hpp"
 #include "visloc_math.hpp"
 
 namespace d3r {
@@ -354,7 +355,7 @@ __global__ __launch_bounds__(64) void pnp_lm_init_kernel(int n_jobs, int max_poi
 // per chunk: the Gauss-Newton sums of the reprojection error at the trial pose over the best hypothesis's inliers. Parameters: a
 // rotation increment w and a translation increment d of the camera-frame point, x' = x + w x x + d (left perturbation).
 __global__ __launch_bounds__(PT) void pnp_lm_kernel(const d3r_pnp_ransac_job* __restrict__ jobs, int max_points, void* workspace) {
-    __shared__ double red[PT / 64][NSUM];
+    __shared__ double red[PT / 64 * (NSUM - 2)];
     const int j = blockIdx.y;
     const PnpWs w = pnp_ws(workspace, j, max_points);
     const d3r_pnp_ransac_job J = jobs[j];
@@ -396,19 +397,9 @@ __global__ __launch_bounds__(PT) void pnp_lm_kernel(const d3r_pnp_ransac_job* __
         for (int r = 0; r < 6; ++r) s[21 + r] += ju[r] * ru + jv[r] * rv;
         s[27] += ru * ru + rv * rv;
     }
-    // fixed-order reduction: wave butterflies, then the 4 waves in order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int k = 0; k < NSUM - 2; ++k) {
-        double v = s[k];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NSUM - 2) {
-        double v = 0.0;
-        for (int wv = 0; wv < PT / 64; ++wv) v += red[wv][threadIdx.x];
-        w.partial[(size_t)blockIdx.x * NSUM + threadIdx.x] = v;
-    }
+    // fixed-order reduction (reduce.hpp): wave butterflies, then column k by thread k over the 4 waves in order. The per-thread sums start
+    // at +0.0, so no wave's value is -0.0 and starting from wave 0's value gives the bits of starting from 0.0
+    block_reduce_columns<PT, NSUM - 2>(s, red, Sum(), w.partial + (size_t)blockIdx.x * NSUM);
 }
 
 // x' = exp([w]) x + d applied to the pose: R' = exp([w]) R, t' = exp([w]) t + d

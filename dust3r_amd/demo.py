@@ -255,7 +255,7 @@ def gallery_images(depth, conf, npix):
     depth_img = torch.empty((n, row), dtype=torch.float32, device=device)
     conf_img = torch.empty((n, row, 4), dtype=torch.float32, device=device)
     maxima = torch.empty((2,), dtype=torch.float32, device=device)
-    work = torch.empty(max(1, int(_lib.lib.d3r_scene_gallery_workspace_bytes(n, row))), dtype=torch.uint8, device=device)
+    work = _lib.workspace(max(1, _lib.lib.d3r_scene_gallery_workspace_bytes(n, row)), device)
     with torch.cuda.device(device):
         _lib.check(_lib.lib.d3r_scene_gallery(n, _lib.ptr(depth), _lib.ptr(conf), _lib.ptr(npix), row, _lib.ptr(_device_table(device)), _lib.ptr(depth_img),
                                               _lib.ptr(conf_img), _lib.ptr(maxima), _lib.ptr(work), _lib.current_stream()), 'scene_gallery')

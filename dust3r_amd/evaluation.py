@@ -63,7 +63,7 @@ def _stack_moments(src, tgt, wgt, areas):
     """(17,) weighted Umeyama moments of the padded stacks src -> tgt (n, row, 3) with weights (n, row): one d3r_similarity_moments job per
     view (its h w elements), added in fp64 on the host (the moments are additive). Rows of pad_views / a scene are multiples of 4
     elements, so every row starts on 16 bytes, as the kernel's float4 loads need."""
-    from ._lib import check, current_stream, lib, ptr
+    from ._lib import check, current_stream, lib, ptr, workspace
     n, dev = len(areas), src.device
     addrs = [[t.data_ptr() + i * t.stride(0) * 4 for i in range(n)] for t in (src, tgt, wgt)]
     if not all(a % 16 == 0 for table in addrs for a in table):
@@ -72,7 +72,7 @@ def _stack_moments(src, tgt, wgt, areas):
     npix = torch.tensor(areas, dtype=torch.int32).to(dev)
     out = torch.empty((n, 17), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        ws = torch.empty(int(lib.d3r_similarity_moments_workspace(n, max(areas))), dtype=torch.uint8, device=dev)
+        ws = workspace(lib.d3r_similarity_moments_workspace(n, max(areas)), dev)
         check(lib.d3r_similarity_moments(n, ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), ptr(npix), max(areas), ptr(ws), ptr(out), current_stream()),
               'similarity_moments')
     return out.cpu().numpy().sum(axis=0)

@@ -81,7 +81,7 @@ def pair_criterion(gt_pts1, gt_pts2, inv_pose1, valid1, valid2, pr_pts1, pr_pts2
     map1 = torch.empty((B, N), dtype=torch.float32, device=dev) if maps else None
     map2 = torch.empty((B, N), dtype=torch.float32, device=dev) if maps and g2 is not None else None
     with torch.cuda.device(dev):
-        work = torch.empty(int(lib.d3r_pair_criterion_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
+        work = _lib.workspace(lib.d3r_pair_criterion_workspace_bytes(B, N), dev)
         check(lib.d3r_pair_criterion(B, N, ptr(g1), ptr(g2), ptr(pose), ptr(m1), ptr(m2), ptr(p1), ptr(p2), ptr(c1), ptr(c2), C.byref(opts),
                                      ptr(stats), ptr(map1), ptr(map2), ptr(work), current_stream()), 'pair_criterion')
     return stats, map1, map2
@@ -112,7 +112,7 @@ def masked_median(vals1, vals2=None, mask1=None, mask2=None):
     m2 = _mask(mask2, v2, dev) if (mask2 is not None and v2 is not None) else None
     out = torch.empty(B, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        work = torch.empty(int(lib.d3r_pair_criterion_workspace_bytes(B, v1.shape[1])), dtype=torch.uint8, device=dev)
+        work = _lib.workspace(lib.d3r_pair_criterion_workspace_bytes(B, v1.shape[1]), dev)
         check(lib.d3r_masked_median(B, v1.shape[1], ptr(v1), ptr(v2), ptr(m1), ptr(m2), ptr(out), ptr(work), current_stream()), 'masked_median')
     return out.float()
 

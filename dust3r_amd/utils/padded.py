@@ -1,6 +1,7 @@
 """The padded layout: per-view maps of different sizes as rows of one tensor -- what every batched scene kernel takes (d3r_clean_pointcloud,
 d3r_segment_sky, d3r_scene_mesh, d3r_scene_gallery) and what a scene keeps (`_im_conf`, `_flat_im_depthmaps`, `get_depthmaps(raw=True)`,
-`get_pts3d(raw=True)`). This module is the one place that pads, slices back and builds the shape tables. The contract:
+`get_pts3d(raw=True)`). This module is the one place that pads, slices back and builds the shape tables; `viz.ingest_views` is the one
+ingestion built on it (images, pointmaps, masks and weights of a batched scene call, lists or ready stacks, to stacks and tables). The contract:
 - a stack is a contiguous (n, row, *tail) tensor; view i of shape (h, w) is `stack[i, :h * w]` in raster order;
 - row >= every h * w; the rows made here and the scene's are multiples of 4 (the float4 loads of d3r_scene_gallery need that; an explicit
   `row` is taken as given: the mesh and sky kernels take any), and the base address is 16-byte aligned (as every tensor torch allocates);

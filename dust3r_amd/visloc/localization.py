@@ -79,7 +79,7 @@ def match_pairs(pairs, conf_thr, device=None):
     n = len(jobs)
     with torch.cuda.device(dev):
         rec = _records(jobs, MatchJob, dev)
-        work = torch.empty(int(lib.d3r_match_pairs_workspace(n, max_pixels)), dtype=torch.uint8, device=dev)
+        work = _lib.workspace(lib.d3r_match_pairs_workspace(n, max_pixels), dev)
         counts = torch.empty(n, dtype=torch.int32, device=dev)
         out = torch.empty((n, max_pixels, 2), dtype=torch.int32, device=dev)
         check(lib.d3r_match_pairs(n, ptr(rec), max_pixels, ptr(work), ptr(counts), ptr(out), current_stream()), 'match_pairs')
@@ -152,7 +152,7 @@ def run_pnp_batch(jobs, mode='cv2', seed=0, device=None, return_inliers=False, r
         params = PnpRansacParams(max(r.max_iters for r in recs), max(r.n for r in recs))
         with torch.cuda.device(dev):
             rec = _records(recs, PnpRansacJob, dev)
-            work = torch.empty(int(lib.d3r_pnp_ransac_workspace(m, params.max_points)), dtype=torch.uint8, device=dev)
+            work = _lib.workspace(lib.d3r_pnp_ransac_workspace(m, params.max_points), dev)
             poses = torch.empty((m, 12), dtype=torch.float64, device=dev)
             inl = torch.empty(m, dtype=torch.int32, device=dev)
             status = torch.empty(m, dtype=torch.int32, device=dev)

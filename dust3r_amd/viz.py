@@ -37,24 +37,52 @@ def _as_hwc(image):
     return t
 
 
+def _tensor(x):
+    return x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+
+
+def _images(imgs, name, floats='float'):
+    """H x W x 3 tensors, all uint8 or all float32 (floats='float': any floating dtype, converted; 'float32': only that): images, is_u8, shapes"""
+    images = [_tensor(im) for im in imgs]
+    if floats == 'float':
+        images = [im.float() if im.is_floating_point() and im.dtype != torch.float32 else im for im in images]
+    images = [_as_hwc(im) for im in images]
+    is_u8 = bool(images) and images[0].dtype == torch.uint8
+    if any((im.dtype == torch.uint8) != is_u8 for im in images):
+        raise TypeError(f'{name}: mix of uint8 and {floats} images')
+    return images, is_u8, [tuple(im.shape[:2]) for im in images]
+
+
+def ingest_views(imgs, pts3d, masks, weights, device, name, shapes=None):
+    """The one ingestion of scene_mesh_batch, fuse_points and cloud_tracks: (pts, mask, wgt, rgb, is_u8, shapes, row, hs, ws), the padded
+    stacks of utils/padded.py on `device` and the int32 shape tables. imgs None: no rgb / is_u8, and `shapes` gives the views' (H, W);
+    weights None: no wgt. A ready stack among pts3d, masks, weights sets the rows of all. Every error carries `name`, the caller's."""
+    images = is_u8 = rgb = None
+    if imgs is not None:
+        images, is_u8, shapes = _images(imgs, name)
+    row = next((x.shape[1] for x, nd in ((pts3d, 3), (masks, 2), (weights, 2)) if isinstance(x, torch.Tensor) and x.ndim == nd), None)
+    pts = pad_views(pts3d, device, torch.float32, (3,), row, shapes, f'{name}: pointmap')
+    mask = pad_views(masks, device, torch.uint8, (), row, shapes, f'{name}: mask')
+    wgt = None if weights is None else pad_views(weights, device, torch.float32, (), row, shapes, f'{name}: weight')
+    if images is not None:
+        rgb = pad_views(images, device, torch.uint8 if is_u8 else torch.float32, (3,), row, shapes, f'{name}: image')
+    return (pts, mask, wgt, rgb, is_u8, shapes, pts.shape[1]) + shape_tables(shapes, device)[:2]
+
+
 @torch.no_grad()
 def segment_sky_batch(images, device):
     """Sky masks of a list of H x W x 3 RGB images (numpy arrays or tensors, all uint8 or all float32 in [0, 1]; sizes may differ), computed
     in one batched call on `device`: a list of (H, W) torch.bool tensors on that device."""
     _lib.require_device()
-    arrays = [_as_hwc(im) for im in images]
+    arrays, is_u8, shapes = _images(images, 'segment_sky_batch', floats='float32')
     if not arrays:
         return []
-    is_u8 = arrays[0].dtype == torch.uint8
-    if any((a.dtype == torch.uint8) != is_u8 for a in arrays):
-        raise TypeError('segment_sky_batch: mix of uint8 and float32 images')
     device = torch.device(device)
-    shapes = [a.shape[:2] for a in arrays]
     rgb = pad_views(arrays, device, torch.uint8 if is_u8 else torch.float32, tail=(3,))
     n, max_area = rgb.shape[:2]
     hs, ws, _ = shape_tables(shapes, device)
     masks = torch.empty((n, max_area), dtype=torch.bool, device=device)
-    work = torch.empty(int(lib.d3r_segment_sky_workspace_bytes(n, max_area)), dtype=torch.uint8, device=device)
+    work = _lib.workspace(lib.d3r_segment_sky_workspace_bytes(n, max_area), device)
     with torch.cuda.device(device):
         check(lib.d3r_segment_sky(n, ptr(rgb), int(is_u8), ptr(hs), ptr(ws), max_area, ptr(masks), ptr(work), current_stream()), 'segment_sky')
     return split_views(masks, shapes)
@@ -67,10 +95,6 @@ def segment_sky(image):
 
 
 # ---- GLB export geometry -----------------------------------------------------------------------------------------------------------
-def _tensor(x):
-    return x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-
-
 @torch.no_grad()
 def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False, to_host=True):
     """The geometry of the demo's GLB export for all views in one GPU call (csrc/mesh.hip).
@@ -97,30 +121,17 @@ def scene_mesh_batch(imgs, pts3d, masks, device, as_pointcloud=False, to_host=Tr
         raise ValueError(f'scene_mesh_batch: {len(imgs)} images, {len(pts3d)} pointmaps, {n} masks')
     if n == 0:
         raise ValueError('scene_mesh_batch: no views')
-    images = [_tensor(im) for im in imgs[:n]]
-    images = [im.float() if im.is_floating_point() and im.dtype != torch.float32 else im for im in images]
-    images = [_as_hwc(im) for im in images]
-    is_u8 = images[0].dtype == torch.uint8
-    if any((im.dtype == torch.uint8) != is_u8 for im in images):
-        raise TypeError('scene_mesh_batch: mix of uint8 and float images')
-    shapes = [tuple(im.shape[:2]) for im in images]
+    pts, mask, _, rgb, is_u8, shapes, max_area, hs, ws = ingest_views(imgs[:n], pts3d, masks, None, device, 'scene_mesh_batch')
     areas = [h * w for h, w in shapes]
     n_vert = sum(areas)
     if n_vert >= 2 ** 32:
         raise ValueError(f'scene_mesh_batch: {n_vert} vertices do not fit uint32 indices (as_pointcloud=True or fewer views)')
-    # a ready stack among the inputs sets the rows of all three
-    row = next((x.shape[1] for x, nd in ((pts3d, 3), (masks, 2)) if isinstance(x, torch.Tensor) and x.ndim == nd), None)
-    pts = pad_views(pts3d, device, torch.float32, (3,), row, shapes, 'scene_mesh_batch: pointmap')
-    mask = pad_views(masks, device, torch.uint8, (), row, shapes, 'scene_mesh_batch: mask')
-    rgb = pad_views(images, device, torch.uint8 if is_u8 else torch.float32, (3,), row, shapes, 'scene_mesh_batch: image')
-    max_area = pts.shape[1]
-    hs, ws, _ = shape_tables(shapes, device)
     n_faces = sum(4 * (h - 1) * (w - 1) for h, w in shapes if h > 1 and w > 1)
     faces = None if as_pointcloud else torch.empty((max(n_faces, 1), 3), dtype=torch.int32, device=device)
     points = torch.empty((n_vert, 3), dtype=torch.float32, device=device) if as_pointcloud else None
     colors = torch.empty((n_vert,), dtype=torch.int32, device=device)
     small = torch.empty((n + 3,), dtype=torch.int64, device=device)       # counts [n] int64, then bounds [6] fp32: one read-back
-    work = torch.empty(int(lib.d3r_scene_mesh_workspace_bytes(n, max_area)), dtype=torch.uint8, device=device)
+    work = _lib.workspace(lib.d3r_scene_mesh_workspace_bytes(n, max_area), device)
     with torch.cuda.device(device):
         check(lib.d3r_scene_mesh(n, ptr(pts), ptr(mask), ptr(rgb), int(is_u8), ptr(hs), ptr(ws), max_area, int(bool(as_pointcloud)), ptr(faces),
                                  ptr(points), ptr(colors), ptr(small), ptr(small[n:].view(torch.float32)), ptr(work), current_stream()), 'scene_mesh')
@@ -340,25 +351,11 @@ def fuse_points(imgs, pts3d, masks, weights, voxel_size, device, min_count=1, to
         raise ValueError(f'fuse_points: {len(imgs)} images, {len(pts3d)} pointmaps, {n} masks, {None if weights is None else len(weights)} weight maps')
     if n == 0:
         raise ValueError('fuse_points: no views')
-    images = [_tensor(im) for im in imgs[:n]]
-    images = [im.float() if im.is_floating_point() and im.dtype != torch.float32 else im for im in images]
-    images = [_as_hwc(im) for im in images]
-    is_u8 = images[0].dtype == torch.uint8
-    if any((im.dtype == torch.uint8) != is_u8 for im in images):
-        raise TypeError('fuse_points: mix of uint8 and float images')
-    shapes = [tuple(im.shape[:2]) for im in images]
-    # a ready stack among the inputs sets the rows of all four
-    row = next((x.shape[1] for x, nd in ((pts3d, 3), (masks, 2), (weights, 2)) if isinstance(x, torch.Tensor) and x.ndim == nd), None)
-    pts = pad_views(pts3d, device, torch.float32, (3,), row, shapes, 'fuse_points: pointmap')
-    mask = pad_views(masks, device, torch.uint8, (), row, shapes, 'fuse_points: mask')
-    wgt = None if weights is None else pad_views(weights, device, torch.float32, (), row, shapes, 'fuse_points: weight')
-    rgb = pad_views(images, device, torch.uint8 if is_u8 else torch.float32, (3,), row, shapes, 'fuse_points: image')
-    row = pts.shape[1]
+    pts, mask, wgt, rgb, is_u8, _, row, hs, ws = ingest_views(imgs[:n], pts3d, masks, weights, device, 'fuse_points')
     if n * row >= 2 ** 31:
         raise ValueError(f'fuse_points: {n} rows of {row} do not fit 31-bit pixel indices (fewer views per call)')
-    hs, ws, _ = shape_tables(shapes, device)
     small = torch.empty((4,), dtype=torch.int64, device=device)           # bounds [6] fp32, then the count: one read-back
-    work = torch.empty(max(1, int(lib.d3r_fuse_bounds_workspace_bytes(n, row))), dtype=torch.uint8, device=device)
+    work = _lib.workspace(max(1, lib.d3r_fuse_bounds_workspace_bytes(n, row)), device)
     with torch.cuda.device(device):
         check(lib.d3r_fuse_bounds(n, ptr(pts), ptr(mask), ptr(wgt), ptr(hs), ptr(ws), row, ptr(small.view(torch.float32)), ptr(small[3:]), ptr(work),
                                   current_stream()), 'fuse_bounds')
@@ -376,7 +373,7 @@ def fuse_points(imgs, pts3d, masks, weights, voxel_size, device, min_count=1, to
                 voxel = check_voxel_size(voxel_size())
             bits = fuse_key_bits(lo, hi, voxel)                            # raises before anything else is launched
             totals = torch.empty((2,), dtype=torch.int64, device=device)
-            work = torch.empty(int(lib.d3r_fuse_voxels_workspace_bytes(n, row, cap)), dtype=torch.uint8, device=device)
+            work = _lib.workspace(lib.d3r_fuse_voxels_workspace_bytes(n, row, cap), device)
             check(lib.d3r_fuse_voxels(n, ptr(pts), ptr(mask), ptr(wgt), ptr(rgb), int(is_u8), ptr(hs), ptr(ws), row, (C.c_float * 3)(*lo.tolist()),
                                       float(voxel), (C.c_int * 3)(*bits), cap, ptr(positions), ptr(colors), ptr(weight), ptr(count), ptr(totals),
                                       ptr(work), current_stream()), 'fuse_voxels')
@@ -505,17 +502,12 @@ def cloud_tracks(positions, pts3d, masks, weights, intrinsics, cam2world, shapes
     from .cloud_metrics import _points
     P = _points(positions, device, 'cloud_tracks')
     m = len(P)
-    row = next((x.shape[1] for x, nd in ((pts3d, 3), (masks, 2), (weights, 2)) if isinstance(x, torch.Tensor) and x.ndim == nd), None)
-    pts = pad_views(pts3d, device, torch.float32, (3,), row, shapes, 'cloud_tracks: pointmap')
-    mask = pad_views(masks, device, torch.uint8, (), row, shapes, 'cloud_tracks: mask')
-    wgt = None if weights is None else pad_views(weights, device, torch.float32, (), row, shapes, 'cloud_tracks: weight')
-    row = pts.shape[1]
+    pts, mask, wgt, _, _, _, row, hs, ws = ingest_views(None, pts3d, masks, weights, device, 'cloud_tracks', shapes)
     if n * row >= 2 ** 31:
         raise ValueError(f'cloud_tracks: {n} rows of {row} do not fit 31-bit pixel indices (fewer views per call)')
     cams = torch.from_numpy(track_cameras(intrinsics, cam2world)).to(device)
     if len(cams) != n:
         raise ValueError(f'cloud_tracks: {n} shapes, {len(cams)} cameras')
-    hs, ws, _ = shape_tables(shapes, device)
     thr = (0, 0.0) if max_error is None else (1, float(max_error) ** 2)
     point_off = torch.zeros((m + 1,), dtype=torch.int32, device=device)
     seen = torch.empty((max(m, 1), (n + 31) // 32), dtype=torch.int32, device=device)      # one bit per (point, view), from the first pass to the second
@@ -538,7 +530,7 @@ def cloud_tracks(positions, pts3d, masks, weights, intrinsics, cam2world, shapes
         err2 = torch.empty((cap,), dtype=torch.float64, device=device)
         image_off = torch.zeros((n + 1,), dtype=torch.int32, device=device)
         if m > 0:
-            work = torch.empty(int(lib.d3r_cloud_tracks_workspace_bytes(cap)), dtype=torch.uint8, device=device)
+            work = _lib.workspace(lib.d3r_cloud_tracks_workspace_bytes(cap), device)
             if events:
                 events[2].record()
             check(lib.d3r_cloud_tracks_fill(*args, ptr(point_off), ptr(seen), total, cap, ptr(view), ptr(pixel), ptr(err2), ptr(point2d), ptr(image_off), ptr(image_obs),
