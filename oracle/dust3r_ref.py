@@ -187,8 +187,13 @@ class DUSt3RRef(CroCoNet):
         assert torch.as_tensor(shape1)[0:1].allclose(torch.as_tensor(shape1)), 'true_shape must be all identical'
         hw1 = tuple(int(v) for v in torch.as_tensor(shape1)[0].tolist())
         hw2 = tuple(int(v) for v in torch.as_tensor(shape2)[0].tolist())
-        res1 = self.downstream_head1([t.float() for t in dec1], hw1)
-        res2 = self.downstream_head2([t.float() for t in dec2], hw2)
+        return self.heads(dec1, dec2, hw1, hw2)
+
+    def heads(self, dec1, dec2, hw1, hw2):                                         # model.py:193-197, 208-210
+        # the reference casts the tokens to fp32 (`tok.float()`, autocast off); a .double() copy of this oracle (oracle/stage_ref.py) keeps its own type
+        dt = next(self.downstream_head1.parameters()).dtype
+        res1 = self.downstream_head1([t.to(dt) for t in dec1], hw1)
+        res2 = self.downstream_head2([t.to(dt) for t in dec2], hw2)
         res2['pts3d_in_other_view'] = res2.pop('pts3d')
         return res1, res2
 
