@@ -23,7 +23,12 @@ scene.fuse(normals=..., outliers=...) are built of them.
 
 The same nearest neighbour carries the registration of one cloud onto another: per iteration the source is moved by the
 current similarity, every moved point finds its nearest reference point on grids that are built once per stage, one kernel gates the pairs
-and reduces them to 18 (point to point) or 36 (point to plane) fp64 sums, and the host solves for the update in fp64."""
+and reduces them to 18 (point to point) or 36 (point to plane) fp64 sums, and the host solves for the update in fp64.
+
+    res = cluster_points(points, eps, min_points)           # DBSCAN: labels, sizes, n_neighbors, core: csrc/cloud_cluster.hip, d3r_cloud_cluster
+
+On the same grid, built on the cloud itself with cells of eps: density clustering, defined without the grid and without any visiting
+order; viz.FusedCloud.cluster / keep_clusters and scene.fuse(clusters=..., keep_largest=...) are built of it."""
 import collections
 import ctypes as C
 import math
@@ -304,6 +309,65 @@ def orient_normals(points, normals, depth, conf, intrinsics, cam2world, heights,
                                                ptr(f32(inv(cam2world))), ptr(centers), ptr(heights), ptr(widths), depth.shape[1], float(tol),
                                                current_stream()), 'cloud_orient_normals')
     return n_seen
+
+
+# ---- density clustering ------------------------------------------------------------------------------------------------
+Clusters = collections.namedtuple('Clusters', 'labels sizes n_neighbors core')
+Clusters.__doc__ = """The result of `cluster_points`: labels (N,) int32, the cluster of every point, -1 for noise; sizes (C,) int32, the members of
+cluster 0 .. C - 1, never increasing; n_neighbors (N,) int32, the points within eps, the point itself included; core (N,) bool."""
+
+
+def _min_points(min_points):
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or min_points < 1 or min_points >= 2 ** 31:
+        raise ValueError(f'min_points = {min_points!r} must be an int >= 1')
+    return int(min_points)
+
+
+@torch.no_grad()
+def cluster_points(points, eps, min_points=10, to_host=True, evals=None, stage_events=None):
+    """`Clusters` of the (N, 3) points (an array, a tensor or a FusedCloud): DBSCAN on the GPU (csrc/cloud_cluster.hip, d3r_cloud_cluster),
+    DEFINED without a grid (include/dust3r_hip.h). A point is valid when its coordinates are finite. The neighbours of a valid point are
+    the valid points with fp32 d2 <= eps^2 (fp32), THE POINT ITSELF INCLUDED: scikit-learn's convention for min_samples (Open3D's
+    cluster_dbscan counts the same way). A point with at least min_points neighbours is core; the clusters are the connected components
+    of the core points under d2 <= eps^2, each rooted at its lowest index. A valid non-core point with a core neighbour is a border point
+    and takes the cluster of the core neighbour with the smallest (d2, index) pair: unlike textbook DBSCAN, where a border point between
+    two clusters goes to whichever reaches it first, the assignment does not depend on any visiting order. Everything else is noise, label
+    -1. Clusters are numbered by decreasing size, ties by ascending root. Exactly what an fp32 brute force over all pairs gives; the same
+    bytes on every run. Two host synchronisations: the cloud's bounds (for the grid of cell eps), then the number of clusters.
+    to_host=False: device tensors. evals: an int32 device tensor (N,) that accumulates the distance evaluations of the counting walk;
+    stage_events: four torch.cuda.Event (or None), each recorded once before so that its handle exists, recorded again after the count,
+    the components, the border walk and the numbering (tools/cloud_cluster_speed.py)."""
+    eps = _radius_f32(eps, 'eps')
+    min_points = _min_points(min_points)
+    _lib.require_device()
+    device = _device_of(points)
+    P = _points(points, device, 'points')
+    n = len(P)
+    labels = torch.full((n,), -1, dtype=torch.int32, device=device)
+    n_neighbors = torch.zeros((n,), dtype=torch.int32, device=device)
+    core = torch.zeros((n,), dtype=torch.uint8, device=device)
+    sizes = torch.zeros((0,), dtype=torch.int32, device=device)
+    if n > 0:
+        with torch.cuda.device(device):
+            lo, hi, n_valid = _bounds(P, device)
+            if n_valid > 0:
+                cell, bits = grid_cell(lo, hi, eps)
+                lo_c, bits_c = (C.c_float * 3)(*lo.tolist()), (C.c_int * 3)(*bits)
+                grid_bytes, own_bytes = int(lib.d3r_cloud_grid_workspace_bytes(n, 1)), int(lib.d3r_cloud_cluster_workspace_bytes(n))
+                if grid_bytes == 0 or own_bytes == 0:
+                    raise ValueError(f'a cloud of {n} points is too large')
+                grid, work = _lib.workspace(grid_bytes, device), _lib.workspace(own_bytes, device)
+                all_sizes = torch.empty((n,), dtype=torch.int32, device=device)
+                n_clusters = torch.zeros((1,), dtype=torch.int32, device=device)
+                events = None
+                if stage_events is not None:
+                    events = (C.c_void_p * 4)(*[None if e is None else e.cuda_event for e in stage_events])
+                check(lib.d3r_cloud_grid_build(n, ptr(P), lo_c, float(cell), bits_c, ptr(grid), current_stream()), 'cloud_grid_build')
+                check(lib.d3r_cloud_cluster(n, float(eps), min_points, lo_c, float(cell), bits_c, ptr(labels), ptr(all_sizes), ptr(n_clusters),
+                                            ptr(n_neighbors), ptr(core), ptr(evals), events, ptr(grid), ptr(work), current_stream()), 'cloud_cluster')
+                sizes = all_sizes[:int(n_clusters.cpu())].clone()            # the one read-back of the clustering
+    out = Clusters(labels, sizes, n_neighbors, core.bool())
+    return Clusters(*(t.cpu().numpy() for t in out)) if to_host else out
 
 
 @torch.no_grad()

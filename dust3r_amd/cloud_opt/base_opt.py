@@ -347,14 +347,17 @@ class BasePCOptimizer(nn.Module):
         return res
 
     @torch.no_grad()
-    def fuse(self, voxel_size=None, min_count=1, weights='conf', to_host=True, normals=False, outliers=None, k=16, tracks=False, max_reproj_error=None):
+    def fuse(self, voxel_size=None, min_count=1, weights='conf', to_host=True, normals=False, outliers=None, k=16, tracks=False, max_reproj_error=None,
+             clusters=None, keep_largest=None):
         """The scene as ONE point cloud (new; the reference exports every masked pixel of every view): the masked points of all views
         (`get_masks()` at the scene's current min_conf_thr, as the GLB export) binned into voxels of `voxel_size` and averaged per voxel,
         weighted by the images' confidences (weights='conf') or equally (weights=None); `viz.fuse_points` on the scene's padded stacks,
         csrc/fuse.hip. voxel_size=None: the median pixel footprint (`viz.default_voxel_size`: median depth / focal; a ValueError when it is
         not a positive number -- NaN depth maps or focals -- while the scene has valid points: give a voxel_size then). min_count: voxels of
         fewer points are dropped. outliers=std_ratio: statistical outlier removal on the fused cloud first (`FusedCloud.remove_outliers`
-        over k neighbours); normals=True: then normals from k neighbours, turned towards the cameras of this scene that see each point
+        over k neighbours); clusters=True, or a dict of eps / min_points: then density clustering (`FusedCloud.cluster`; csrc/cloud_cluster.hip),
+        the cloud carries `.labels` and `.cluster_sizes`; keep_largest=N (implies clusters): only the N largest clusters stay
+        (`FusedCloud.keep_clusters`), which drops the dense floaters the outlier removal keeps; normals=True: then normals from k neighbours, turned towards the cameras of this scene that see each point
         (`FusedCloud.estimate_normals(scene=self)`; csrc/cloud_knn.hip). tracks=True: last, on the final points, the 2-D tracks -- which
         pixel of which image observes each point, by projection within one voxel_size -- as `cloud.tracks` (`FusedCloud.build_tracks`;
         csrc/tracks.hip), observations landing more than max_reproj_error pixels off dropped; `export.write_colmap` then writes POINTS2D
@@ -365,6 +368,11 @@ class BasePCOptimizer(nn.Module):
             raise _lib.D3RError('fuse runs on the GPU (dust3r_amd has no CPU execution path)')
         if weights not in ('conf', None):
             raise ValueError(f"fuse: weights is 'conf' or None, got {weights!r}")
+        if keep_largest is not None and not clusters:
+            clusters = True
+        cluster_args = dict(clusters) if isinstance(clusters, dict) else {}
+        if set(cluster_args) - {'eps', 'min_points'}:
+            raise ValueError(f"fuse: clusters is True or a dict of 'eps' / 'min_points', got {clusters!r}")
         from ..viz import default_voxel_size, fuse_points
         if voxel_size is None:       # evaluated once the bounds pass has found a valid point
             def voxel_size():
@@ -373,6 +381,10 @@ class BasePCOptimizer(nn.Module):
                             self.device, min_count=min_count, to_host=to_host)
         if outliers is not None:
             cloud, _ = cloud.remove_outliers(k=k, std_ratio=outliers)
+        if clusters:
+            cloud = cloud.cluster(**cluster_args)
+            if keep_largest is not None:
+                cloud, _ = cloud.keep_clusters(largest=keep_largest)
         if normals:
             cloud = cloud.estimate_normals(k=k, scene=self)
         if tracks:

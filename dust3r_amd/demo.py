@@ -14,7 +14,7 @@ compute_global_alignment -> get_3D_model_from_scene, and the rgb / depth / confi
 for all images, csrc/gallery.hip, no matplotlib). `scenegraph_options` is the rule of set_scenegraph_options as plain data, and
 `python -m dust3r_amd.demo` the command line in place of the gradio page; its --fuse / --ply / --colmap (new) also write the fused cloud of
 `scene.fuse()` as scene.ply and as a COLMAP model (`write_fused`, dust3r_amd/export.py); --fuse_normals / --fuse_outliers add normals and
-statistical outlier removal."""
+statistical outlier removal, --fuse_clusters / --fuse_keep_largest density clustering and the removal of all but the largest clusters."""
 import argparse
 import copy
 import json
@@ -370,12 +370,18 @@ def get_args_parser():
                         help='estimate normals of the fused cloud, turned towards the cameras, and write them into scene.ply (implies --fuse)')
     parser.add_argument('--fuse_outliers', type=float, default=None, metavar='STD_RATIO',
                         help='statistical outlier removal on the fused cloud: drop points whose mean neighbour distance exceeds mean + STD_RATIO std (implies --fuse)')
+    parser.add_argument('--fuse_clusters', type=float, nargs='?', const=0.0, default=None, metavar='EPS_IN_VOXELS',
+                        help='density clustering (DBSCAN) of the fused cloud: scene.ply gets an int label per point, cameras.json the cluster sizes; '
+                             'EPS_IN_VOXELS: the neighbourhood radius in voxels (default 2.5) (implies --fuse)')
+    parser.add_argument('--fuse_keep_largest', type=int, default=None, metavar='N',
+                        help='keep only the N largest clusters of the fused cloud, which drops dense floaters (implies --fuse_clusters and --fuse)')
     return parser
 
 
 def wants_fuse(args):
-    """--ply, --colmap, --fuse_normals and --fuse_outliers imply --fuse"""
-    return args.fuse is not None or args.ply or args.colmap or args.fuse_normals or args.fuse_outliers is not None
+    """--ply, --colmap, --fuse_normals, --fuse_outliers, --fuse_clusters and --fuse_keep_largest imply --fuse"""
+    return (args.fuse is not None or args.ply or args.colmap or args.fuse_normals or args.fuse_outliers is not None or args.fuse_clusters is not None or
+            args.fuse_keep_largest is not None)
 
 
 def clamp_scenegraph(num_files, winsize, refid, scenegraph_type):
@@ -419,26 +425,42 @@ def write_cameras(outdir, scene):
 
 
 def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, ply=True, colmap=False, normals=False, outliers=None, tracks=False,
-                max_reproj_error=None):
+                max_reproj_error=None, clusters=None, keep_largest=None):
     """outdir/scene.ply and / or outdir/colmap of the scene's fused cloud (scene.fuse; export.write_ply / write_colmap), with the mask of
     get_3D_model_from_scene: min_conf_thr through the scene's confidence transform, the sky on request; normals / outliers / tracks /
     max_reproj_error as for scene.fuse. With tracks, their `stats()` are added to outdir/cameras.json (when it is there) under "tracks".
+    clusters: None, or the eps of `FusedCloud.cluster` in voxels (0: its default); keep_largest=N keeps the N largest clusters (and implies
+    clusters). The cluster count and the ten largest sizes are added to cameras.json under "clusters"; scene.ply gets an `int label`.
     Returns the file names."""
     from .export import write_colmap
     if mask_sky:
         scene = scene.mask_sky()
     scene.min_conf_thr = float(scene.conf_trf(torch.tensor(min_conf_thr)))
-    cloud = scene.fuse(voxel_size=voxel_size or None, normals=normals, outliers=outliers, tracks=tracks, max_reproj_error=max_reproj_error)
+    voxel_size, cluster_args = voxel_size or None, None
+    if clusters is not None or keep_largest is not None:
+        cluster_args = True
+        if clusters:                 # eps in voxels: the voxel size has to be known before the call
+            if voxel_size is None:
+                from .viz import default_voxel_size
+                voxel_size = default_voxel_size(scene.get_depthmaps(raw=True), [h * w for h, w in scene.imshapes], scene.get_focals())
+            if math.isfinite(voxel_size) and voxel_size > 0:             # else: a scene without a valid point, which scene.fuse handles
+                cluster_args = dict(eps=float(clusters) * voxel_size)
+    cloud = scene.fuse(voxel_size=voxel_size, normals=normals, outliers=outliers, tracks=tracks, max_reproj_error=max_reproj_error, clusters=cluster_args,
+                       keep_largest=keep_largest)
     written = []
     if ply:
         written.append(cloud.save_ply(os.path.join(outdir, 'scene.ply')))
     if colmap:
         written += write_colmap(os.path.join(outdir, 'colmap'), scene, cloud)
     cameras = os.path.join(outdir, 'cameras.json')
-    if tracks and os.path.isfile(cameras):
+    if (tracks or cluster_args is not None) and os.path.isfile(cameras):
         with open(cameras) as f:
             doc = json.load(f)
-        doc['tracks'] = cloud.tracks.stats()
+        if tracks:
+            doc['tracks'] = cloud.tracks.stats()
+        if cluster_args is not None:
+            sizes = [int(s) for s in (cloud.cluster_sizes.tolist() if cloud.cluster_sizes is not None else [])]
+            doc['clusters'] = dict(count=len(sizes), largest=sizes[:10], kept=None if keep_largest is None else min(int(keep_largest), len(sizes)))
         with open(cameras, 'w') as f:
             json.dump(doc, f, indent=1)
     return written
@@ -468,7 +490,8 @@ def main(argv=None):
     if wants_fuse(args):
         written += write_fused(args.outdir, scene, voxel_size=args.fuse, min_conf_thr=args.min_conf_thr, mask_sky=args.mask_sky,
                                ply=args.ply or not args.colmap, colmap=args.colmap, normals=args.fuse_normals, outliers=args.fuse_outliers,
-                               tracks=args.colmap_tracks, max_reproj_error=args.max_reproj_error)
+                               tracks=args.colmap_tracks, max_reproj_error=args.max_reproj_error, clusters=args.fuse_clusters,
+                               keep_largest=args.fuse_keep_largest)
     if not args.silent:
         print('(wrote', len(written), 'files to', args.outdir, ')')
     return 0

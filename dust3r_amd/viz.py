@@ -7,7 +7,8 @@
 - `SceneViz` (viz.py:119-209) as a HEADLESS viewer: the same `add_pointcloud` / `add_camera` / `add_cameras`, and `render` / `show` that draw
   the scene into images with the rasteriser of csrc/render.hip (`render_batch`, C ABI `d3r_render_*`) instead of opening a window.
 - the fused cloud (new): `fuse_points` merges the views' pointmaps into one voxel-fused, weighted cloud (csrc/fuse.hip, C ABI
-  `d3r_fuse_bounds` / `d3r_fuse_voxels`), a `FusedCloud`; dust3r_amd/export.py writes it as PLY or as a COLMAP model.
+  `d3r_fuse_bounds` / `d3r_fuse_voxels`), a `FusedCloud`; dust3r_amd/export.py writes it as PLY or as a COLMAP model. Its `cluster` /
+  `keep_clusters` separate the scene from dense floaters (DBSCAN, csrc/cloud_cluster.hip); `label_colors` paints the clusters.
 The interactive viewers (a window, show_raw_pointcloud*) are not mirrored."""
 import math
 
@@ -162,15 +163,18 @@ class FusedCloud:
     """The voxel-fused cloud of `fuse_points` / `scene.fuse()`: positions (M, 3) float32, colors (M, 3) uint8, weight (M,) float32 (the summed
     weights of a voxel's points), count (M,) int32 (their number), in ascending voxel-key order; numpy arrays, or torch tensors on the device
     with to_host=False. voxel_size, origin (3,) float32 (the minimum of the fused points: voxel (i, j, k) starts at origin + voxel_size (i, j,
-    k)) and bounds = (min, max) of the fused points, (+inf, -inf) for an empty cloud."""
+    k)) and bounds = (min, max) of the fused points, (+inf, -inf) for an empty cloud. After `cluster`: labels (M,) int32, the cluster of every
+    point (-1 = noise), and cluster_sizes (C,) int32; they follow the points through estimate_normals, build_tracks, remove_outliers,
+    keep_clusters and transform."""
 
-    def __init__(self, positions, colors, weight, count, voxel_size, bounds, normals=None, curvature=None, tracks=None):
+    def __init__(self, positions, colors, weight, count, voxel_size, bounds, normals=None, curvature=None, tracks=None, labels=None, cluster_sizes=None):
         self.positions, self.colors, self.weight, self.count = positions, colors, weight, count
         self.voxel_size = float(voxel_size)
         self.bounds = bounds
         self.origin = bounds[0]
         self.normals, self.curvature = normals, curvature      # (M, 3) float32 and (M,) float32 of `estimate_normals`, else None
         self.tracks = tracks                                   # the `CloudTracks` of `build_tracks`, else None
+        self.labels, self.cluster_sizes = labels, cluster_sizes    # (M,) int32 (-1 = noise) and (C,) int32 of `cluster`, else None
 
     def __len__(self):
         return len(self.positions)
@@ -180,7 +184,7 @@ class FusedCloud:
         (export.write_ply)."""
         from .export import write_ply
         return write_ply(path, *(_to_numpy(a) for a in (self.positions, self.colors, self.weight, self.count)),
-                         normals=None if self.normals is None else _to_numpy(self.normals))
+                         normals=None if self.normals is None else _to_numpy(self.normals), labels=None if self.labels is None else _to_numpy(self.labels))
 
     def _neighbour_radius(self, max_dist):
         """max_dist of the neighbour searches: 8 voxels unless given. A surface sampled at spacing v holds about pi r^2 / v^2 points within
@@ -190,6 +194,79 @@ class FusedCloud:
         if not (math.isfinite(self.voxel_size) and self.voxel_size > 0):
             raise ValueError(f'the cloud has no voxel size ({self.voxel_size!r}): give max_dist')
         return 8.0 * self.voxel_size
+
+    def _subset(self, keep):
+        """(cloud, mask) of the points where the device bool tensor `keep` is set: normals, curvature and labels are carried along
+        (cluster_sizes too: they still describe the labels), tracks are not. The mask comes back where this cloud's arrays are."""
+        fields = [self.positions, self.colors, self.weight, self.count, self.normals, self.curvature, self.labels]
+        mask = keep if isinstance(self.positions, torch.Tensor) else keep.cpu().numpy()
+        out = [None if a is None else a[mask] for a in fields]
+        return FusedCloud(*out[:4], voxel_size=self.voxel_size, bounds=self.bounds, normals=out[4], curvature=out[5], labels=out[6],
+                          cluster_sizes=self.cluster_sizes), mask
+
+    @torch.no_grad()
+    def cluster(self, eps=None, min_points=10):
+        """A new cloud carrying `.labels` (M,) int32 and `.cluster_sizes` (C,) int32: DBSCAN on the GPU (cloud_metrics.cluster_points,
+        which has the definition; csrc/cloud_cluster.hip). Label -1 is noise, cluster 0 the largest. eps: the neighbourhood radius,
+        default 2.5 voxels. A surface sampled at spacing v holds about pi r^2 / v^2 points within r, so about pi 2.5^2 = 20 within
+        2.5 v: twice the default min_points of 10, which leaves room for thinner sampling, while a floater has to come within 2.5
+        voxels of the surface to be joined to it. (The room is needed: the voxel size is the MEDIAN pixel footprint, and the 12.6 M-point
+        cloud of tools/cloud_cluster_speed.py has 11 neighbours on average, not 20) ValueError for a cloud without a
+        voxel size when eps is not given, unless it is empty. The points are the same ones: normals and tracks are kept. Arrays come
+        back where this cloud's are."""
+        from .cloud_metrics import _min_points, _radius_f32, cluster_points
+        _min_points(min_points)
+        if eps is None:
+            if not (math.isfinite(self.voxel_size) and self.voxel_size > 0):
+                if len(self) > 0:
+                    raise ValueError(f'the cloud has no voxel size ({self.voxel_size!r}): give eps')
+                eps = 1.0                                                  # an empty cloud: any radius gives the same nothing
+            else:
+                eps = 2.5 * self.voxel_size
+        _radius_f32(eps, 'eps')
+        res = cluster_points(self, eps, min_points=min_points, to_host=not isinstance(self.positions, torch.Tensor))
+        return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=self.normals,
+                          curvature=self.curvature, tracks=self.tracks, labels=res.labels, cluster_sizes=res.sizes)
+
+    def keep_clusters(self, largest=None, min_size=None, labels=None):
+        """(cloud, keep) of a clustered cloud (`cluster`), like `remove_outliers`: the points of the chosen clusters, keep (M,) bool.
+        Exactly one selector: largest=N, the N largest clusters (labels 0 .. N - 1: the numbering is by decreasing size); min_size=S,
+        the clusters of at least S points; labels=[...], those clusters. Noise is never kept. Normals, curvature and labels are carried
+        along, cluster_sizes stays as it was (the labels are not renumbered). Tracks are DROPPED, as in `remove_outliers`: they index
+        the points before the removal; call `build_tracks` on the result."""
+        if sum(x is not None for x in (largest, min_size, labels)) != 1:
+            raise ValueError('keep_clusters: give exactly one of largest, min_size, labels')
+        if self.labels is None or self.cluster_sizes is None:
+            raise ValueError('keep_clusters: the cloud has no labels: call cluster() first')
+        n_clusters = len(self.cluster_sizes)
+        is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, bool)      # noqa: E731
+        if largest is not None:
+            if not is_int(largest) or largest < 0:
+                raise ValueError(f'keep_clusters: largest = {largest!r} must be an int >= 0')
+            chosen = np.arange(n_clusters) < largest
+        elif min_size is not None:
+            if not is_int(min_size) or min_size < 1:
+                raise ValueError(f'keep_clusters: min_size = {min_size!r} must be an int >= 1')
+            chosen = _to_numpy(self.cluster_sizes) >= min_size
+        else:
+            wanted = np.asarray(list(labels))
+            if wanted.size and (wanted.dtype.kind not in 'iu' or wanted.min() < 0 or wanted.max() >= n_clusters):
+                raise ValueError(f'keep_clusters: labels {list(labels)!r} are not clusters 0 .. {n_clusters - 1}')
+            chosen = np.zeros(n_clusters, bool)
+            chosen[wanted.astype(np.int64)] = True
+        own = self.labels if isinstance(self.labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(self.labels))
+        table = torch.from_numpy(np.concatenate([chosen, [False]])).to(own.device)           # the last entry answers label -1
+        return self._subset(table[own.long()])
+
+    def colored_by_label(self):
+        """A new cloud whose colours are `label_colors` of its labels (what save_ply, SceneViz and the renderer then draw)"""
+        if self.labels is None:
+            raise ValueError('colored_by_label: the cloud has no labels: call cluster() first')
+        colors = label_colors(self.labels)
+        if isinstance(self.colors, torch.Tensor):
+            colors = torch.from_numpy(colors).to(self.colors.device)
+        return FusedCloud(self.positions, colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=self.normals,
+                          curvature=self.curvature, tracks=self.tracks, labels=self.labels, cluster_sizes=self.cluster_sizes)
 
     @torch.no_grad()
     def estimate_normals(self, k=16, max_dist=None, scene=None, tol=0.05, min_neighbors=3):
@@ -218,7 +295,7 @@ class FusedCloud:
         if not on_device:
             normals, curvature = normals.cpu().numpy(), curvature.cpu().numpy()
         return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=normals, curvature=curvature,
-                          tracks=self.tracks)
+                          tracks=self.tracks, labels=self.labels, cluster_sizes=self.cluster_sizes)
 
     @torch.no_grad()
     def remove_outliers(self, k=16, std_ratio=2.0, max_dist=None):
@@ -226,7 +303,7 @@ class FusedCloud:
         (default 8 voxels); a point is kept when it HAS k neighbours within max_dist and its mean is <= mean + std_ratio std of those
         means (cloud_metrics.outlier_threshold: host fp64 from three sums reduced on the device; the fp32 means widened to fp64 for the
         comparison). Open3D's remove_statistical_outlier with the search truncated at max_dist: a point with fewer than k neighbours
-        there is an outlier. keep: (M,) bool. Normals and curvature, when present, are carried along. One host synchronisation more
+        there is an outlier. keep: (M,) bool. Normals, curvature and cluster labels, when present, are carried along. One host synchronisation more
         than `k_nearest` (the three sums). Tracks are DROPPED (they index the points before the removal): call `build_tracks` on the
         result, as `scene.fuse(tracks=True)` does."""
         from .cloud_metrics import _device_of, _points, default_knn_r0, k_nearest, knn_mean_distances, outlier_threshold
@@ -241,14 +318,7 @@ class FusedCloud:
             packed = torch.cat([count.double(), sums]).cpu().tolist()      # one read-back (the count is exact in fp64 below 2^53)
             threshold = outlier_threshold(int(packed[0]), packed[1], packed[2], std_ratio)
             keep = mean.double() <= threshold                              # NaN (fewer than k neighbours, or no full row at all): dropped
-        fields = [self.positions, self.colors, self.weight, self.count, self.normals, self.curvature]
-        if on_device:
-            out = [None if a is None else a[keep] for a in fields]
-            mask = keep
-        else:
-            mask = keep.cpu().numpy()
-            out = [None if a is None else a[mask] for a in fields]
-        return FusedCloud(*out[:4], voxel_size=self.voxel_size, bounds=self.bounds, normals=out[4], curvature=out[5]), mask
+        return self._subset(keep)
 
     @torch.no_grad()
     def transform(self, S):
@@ -269,7 +339,7 @@ class FusedCloud:
             if not on_device:
                 positions, normals = positions.cpu().numpy(), None if normals is None else normals.cpu().numpy()
         return FusedCloud(positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size * scale, bounds=bounds, normals=normals,
-                          curvature=self.curvature)
+                          curvature=self.curvature, labels=self.labels, cluster_sizes=self.cluster_sizes)
 
     def distance_to(self, other, max_dist, to_host=True):
         """(d2, idx) of every point of this cloud in `other` (a FusedCloud or (N, 3) points) within max_dist: squared distances (+inf where
@@ -297,7 +367,21 @@ class FusedCloud:
                               scene.get_intrinsics(), scene.get_im_poses(), scene.imshapes, max_dist, max_error=max_error, device=scene.device,
                               to_host=not isinstance(self.positions, torch.Tensor))
         return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=self.normals,
-                          curvature=self.curvature, tracks=tracks)
+                          curvature=self.curvature, tracks=tracks, labels=self.labels, cluster_sizes=self.cluster_sizes)
+
+
+LABEL_PALETTE = np.array([(31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103, 189), (140, 86, 75), (227, 119, 194), (188, 189, 34),
+                          (23, 190, 207), (174, 199, 232), (255, 187, 120), (152, 223, 138), (255, 152, 150), (197, 176, 213), (196, 156, 148),
+                          (247, 182, 210), (219, 219, 141), (158, 218, 229), (57, 59, 121), (132, 60, 57)], np.uint8)
+LABEL_NOISE_COLOR = (128, 128, 128)
+
+
+def label_colors(labels):
+    """(n, 3) uint8 colours of cluster labels: a fixed palette of 20 by label mod 20, grey for noise (label < 0). Host arithmetic."""
+    labels = _to_numpy(labels).astype(np.int64).reshape(-1)
+    out = LABEL_PALETTE[np.mod(labels, len(LABEL_PALETTE))]
+    out[labels < 0] = LABEL_NOISE_COLOR
+    return out
 
 
 def check_voxel_size(voxel_size):

@@ -616,6 +616,37 @@ int d3r_cloud_icp_sums(int n, const float* moved, const float* moved_normals, in
                        const int* idx, int metric, float gate, float cos_min, const float* centre, long long* count_out, double* sums_out,
                        uint8_t* used_out, void* workspace, void* stream);
 
+/* Density clustering of a cloud (DBSCAN; new; csrc/cloud_cluster.hip). points [n][3] DEVICE fp32, 1 <= n <= 2^31 - 1; eps a positive fp32
+ * whose square eps2 = eps eps (fp32) is a normal number; min_points >= 1. Validity and d2 are those of the cloud metrics above: a point is
+ * VALID when its three coordinates are finite; d2 = (dx dx + dy dy) + dz dz, every operation its own fp32 rounding.
+ * THE RESULT, stated without the grid:
+ *   1. Neighbours. N(i) = the valid j with d2(i, j) <= eps2, i itself included. n_neighbors_out[i] = |N(i)|, 0 for an invalid point.
+ *   2. Core. i is core when it is valid and n_neighbors_out[i] >= min_points. core_out[i] = 1 or 0.
+ *   3. Clusters. The connected components of the graph on the core points with an edge wherever d2 <= eps2. A component's ROOT is its
+ *      lowest point index.
+ *   4. Border. A valid point that is not core and has a core point in N(i) belongs to the cluster of the core neighbour with the smallest
+ *      (d2, index) pair -- whatever the order in which points are visited.
+ *   5. Noise. Every other point: label -1.
+ *   6. Numbering. Clusters are numbered 0 .. C - 1 by decreasing size (core and border members), ties by ascending root.
+ *      labels_out [n] int32; sizes_out [n] int32, of which the first C are written; n_clusters_out [1] int32 = C. All DEVICE.
+ *   Nothing in 1-6 depends on the order of threads: two runs give the same bytes, a brute force over all pairs the same integers.
+ * The grid: d3r_cloud_grid_build of the same n points into grid_workspace (d3r_cloud_grid_workspace_bytes(n, 1) bytes), with the lo, cell
+ *   and bits given here again; cell = eps is usual, exactness does not depend on it. Every walk covers the padded cell range of
+ *   d3r_cloud_nearest at r = eps, so it looks at every point with d2 <= eps2. One thread per valid point, in cell order, walks its range
+ *   three times at most: to count, to unite (core points), to pick its core neighbour (the others). The components are a lock-free
+ *   union-find on the point indices: parent[x] <= x, only ever lowered, by an atomic compare-and-swap on a root or an atomic minimum, to a
+ *   member of x's own component; no workgroup waits for another, and every loop is bounded by a strictly decreasing index. The numbering
+ *   sorts (root, point) and then (n - size, cluster) with the stable radix sort of d3r_fuse_voxels over bit_length(n - 1) bits each.
+ *   evals (optional, DEVICE int [n]): += the distances point i evaluated in its counting walk. stage_events (optional, HOST array of four
+ *   hipEvent_t, each may be NULL): recorded on the stream after the count, the components, the border walk and the numbering.
+ *   workspace: d3r_cloud_cluster_workspace_bytes(n) bytes of DEVICE memory (0 for an invalid n).
+ * No scratch. D3R_ERR_INVALID on NULL, n or min_points out of range and on what d3r_cloud_grid_build / d3r_cloud_nearest refuse; nothing is
+ * launched then. No allocation, no synchronisation: the caller reads C back to know how many sizes were written. */
+size_t d3r_cloud_cluster_workspace_bytes(int n);
+int d3r_cloud_cluster(int n, float eps, int min_points, const float* lo, float cell, const int* bits, int* labels_out, int* sizes_out,
+                      int* n_clusters_out, int* n_neighbors_out, uint8_t* core_out, int* evals, void* const* stage_events, void* grid_workspace,
+                      void* workspace, void* stream);
+
 /* 2-D tracks of a cloud in the views of a scene (new; csrc/tracks.hip): which pixel of which view observes each point, by projection.
  * pts [n][row][3], mask [n][row], weight [n][row] or NULL, img_h / img_w [n]: the scene's stacks as for d3r_fuse_bounds (n * row <= 2^31 - 1,
  * 1 <= n <= 65535; what lies behind a view's h w elements is never read; a view whose h w exceeds row is empty). positions [M][3] DEVICE
