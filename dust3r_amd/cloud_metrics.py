@@ -137,7 +137,8 @@ class _ReferenceGrids:
     d3r_cloud_knn: rung j searches at radii[j] on a grid of cell cell_factor radii[j], from the second on only for the queries still open.
     k: None for the nearest neighbour (d2 / idx (N,)), else the k nearest (N, k), with exclude_self; evals as `nearest_in_cloud`'s.
     rebuild=False: a workspace per rung, its grid built once here (`register_clouds`: many searches on the same grids). rebuild=True: ONE
-    workspace, every rung's grid built in it before its search (one search; the same bytes, tests compare the two)."""
+    workspace, every rung's grid built in it before its search (one search; the same bytes, tests compare the two). `cluster_points` takes
+    a single rung (radii = [eps], rebuild=False) and hands that grid to d3r_cloud_cluster: it never searches."""
 
     def __init__(self, R, lo, hi, radii, n_query, rebuild=False, k=None, exclude_self=False, cell_factor=1.0, evals=None):
         self.R, self.rebuild, self.k, self.exclude_self, self.evals = R, rebuild, k, bool(exclude_self), evals
@@ -351,19 +352,18 @@ def cluster_points(points, eps, min_points=10, to_host=True, evals=None, stage_e
         with torch.cuda.device(device):
             lo, hi, n_valid = _bounds(P, device)
             if n_valid > 0:
-                cell, bits = grid_cell(lo, hi, eps)
-                lo_c, bits_c = (C.c_float * 3)(*lo.tolist()), (C.c_int * 3)(*bits)
-                grid_bytes, own_bytes = int(lib.d3r_cloud_grid_workspace_bytes(n, 1)), int(lib.d3r_cloud_cluster_workspace_bytes(n))
-                if grid_bytes == 0 or own_bytes == 0:
+                own_bytes = int(lib.d3r_cloud_cluster_workspace_bytes(n))
+                if own_bytes == 0:
                     raise ValueError(f'a cloud of {n} points is too large')
-                grid, work = _lib.workspace(grid_bytes, device), _lib.workspace(own_bytes, device)
+                grids = _ReferenceGrids(P, lo, hi, [eps], 1)                 # one rung: the grid of cell eps, built here
+                _, cell, bits_c, grid = grids.rungs[0]
+                work = _lib.workspace(own_bytes, device)
                 all_sizes = torch.empty((n,), dtype=torch.int32, device=device)
                 n_clusters = torch.zeros((1,), dtype=torch.int32, device=device)
                 events = None
                 if stage_events is not None:
                     events = (C.c_void_p * 4)(*[None if e is None else e.cuda_event for e in stage_events])
-                check(lib.d3r_cloud_grid_build(n, ptr(P), lo_c, float(cell), bits_c, ptr(grid), current_stream()), 'cloud_grid_build')
-                check(lib.d3r_cloud_cluster(n, float(eps), min_points, lo_c, float(cell), bits_c, ptr(labels), ptr(all_sizes), ptr(n_clusters),
+                check(lib.d3r_cloud_cluster(n, float(eps), min_points, grids.lo_c, cell, bits_c, ptr(labels), ptr(all_sizes), ptr(n_clusters),
                                             ptr(n_neighbors), ptr(core), ptr(evals), events, ptr(grid), ptr(work), current_stream()), 'cloud_cluster')
                 sizes = all_sizes[:int(n_clusters.cpu())].clone()            # the one read-back of the clustering
     out = Clusters(labels, sizes, n_neighbors, core.bool())

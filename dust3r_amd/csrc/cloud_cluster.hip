@@ -3,14 +3,14 @@
 // keep_clusters). The contract does not mention the grid (include/dust3r_hip.h): neighbours are the valid points with fp32 d2 <= eps2, the
 // point itself included; core points have min_points of them; clusters are the connected components of the core graph, rooted at their
 // lowest index; a border point goes to the core neighbour of smallest (d2, index); clusters are numbered by decreasing size, ties by root.
-// The grid only limits which points are LOOKED AT, with the padded cell range of cloud_knn_kernel.
+// The grid only limits which points are LOOKED AT: every walk is cloud_grid.hpp's cloud_walk, the search's own.
 //   cluster_init_kernel       every point: parent = itself, no neighbours, not core
 //   cluster_count_kernel      one thread per valid point in cell order walks its range: n_neighbors, the core flag
 //   cluster_union_kernel      a core point walks again: every core neighbour of lower index is united with it, lock-free (below)
 //   cluster_flatten_kernel    root of every core point; -1 for the others
 //   cluster_border_kernel     a valid non-core point walks: the root of the core neighbour of minimal (d2 bits, index) key
-//   cluster_flag_kernel       the labelled points compacted as (root, point), fuse_sort_pairs by root, fuse_segment_heads: one segment per
-//   cluster_keys_kernel       cluster; (n - size, cluster) sorted stably by the first: decreasing size, equal sizes keep ascending roots
+//   fuse_flag_kernel<ROOTS>   the labelled points compacted as (root, point), fuse_sort_pairs by root, fuse_segment_heads: one segment per
+//   cluster_keys_kernel       cluster (fuse_grid.hpp); (n - size, cluster) sorted stably by the first: decreasing size, equal sizes keep ascending roots
 //   cluster_rank_kernel / cluster_label_kernel   sizes in rank order, root -> rank, rank -> labels
 // THE UNION-FIND is the only place in the cloud code where workgroups touch the same words. parent[x] <= x always, == x exactly for a
 // root, and it is only ever lowered (atomicCAS on a root, atomicMin when a find halves a path) to a member of x's own component. No
@@ -26,62 +26,6 @@
 namespace d3r {
 namespace cloud {
 
-struct WalkArgs {
-    KeyParams key;
-    float r;
-    const float4* pts4;                 // the grid: the valid points in cell order, w = the original index
-    const uint64_t* cell_key;
-    const int* cell_start;
-    const int* n_dev;                   // [2]: the valid points N, the cells M
-    int cap;
-};
-
-// cloud_knn.hip's key of the pair (d2, g): d2's bits above g, whose unsigned order is the pair's lexicographic order (0 <= d2 <= +inf, g >= 0)
-D3R_DEV uint64_t cluster_pair_key(float d2, int g) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)g; }
-
-// The walk of cloud_knn_kernel for the point (ax, ay, az): per axis the cells from q(next_down(a - r')) to q(next_up(a + r')), r' = r (1 +
-// 2^-10); per (z, y) row one binary search and one run of points. f(i, d2, v) for EVERY looked-at point i (sorted position) -- the caller
-// tests d2 <= r2. Returns the distances evaluated.
-template <class F>
-D3R_DEV int cluster_walk(const WalkArgs& a, int M, float ax, float ay, float az, F&& f) {
-    const float rp = __fmul_rn(a.r, 1.0009765625f);
-    const float pa[3] = {ax, ay, az};
-    int c0[3], c1[3];
-    bool outside = false;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float lo = next_down(__fsub_rn(pa[c], rp)), hi = next_up(__fadd_rn(pa[c], rp));
-        outside = outside || axis_f(hi, a.key, c) < 0.f || axis_f(lo, a.key, c) > (float)a.key.qmax[c];
-        c0[c] = axis_q(lo, a.key, c);
-        c1[c] = axis_q(hi, a.key, c);
-    }
-    if (outside) return 0;
-    int evals = 0, from = 0;
-    for (int z = c0[2]; z <= c1[2]; ++z) {
-        for (int y = c0[1]; y <= c1[1]; ++y) {
-            const uint64_t row = ((uint64_t)y << a.key.shift[1]) | ((uint64_t)z << a.key.shift[2]);
-            const uint64_t k_lo = row | (uint64_t)c0[0], k_hi = row | (uint64_t)c1[0];
-            int l = from, h = M;                                           // the first cell with key >= k_lo
-            while (l < h) {
-                const int m = l + ((h - l) >> 1);
-                if (a.cell_key[m] < k_lo) l = m + 1; else h = m;
-            }
-            int j = l;
-            while (j < M && a.cell_key[j] <= k_hi) ++j;
-            from = j;
-            if (j == l) continue;
-            const int s = a.cell_start[l], e = a.cell_start[j];
-            for (int i = s; i < e; ++i) {
-                const float4 v = a.pts4[i];
-                const float dx = __fsub_rn(ax, v.x), dy = __fsub_rn(ay, v.y), dz = __fsub_rn(az, v.z);
-                f(i, __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)), v);
-            }
-            evals += e - s;
-        }
-    }
-    return evals;
-}
-
 __global__ __launch_bounds__(QT) void cluster_init_kernel(int n, int* __restrict__ parent, int* __restrict__ n_neighbors, uint8_t* __restrict__ core) {
     for (long long g = (long long)blockIdx.x * QT + threadIdx.x; g < n; g += (long long)gridDim.x * QT) {
         parent[g] = (int)g;
@@ -90,7 +34,7 @@ __global__ __launch_bounds__(QT) void cluster_init_kernel(int n, int* __restrict
     }
 }
 
-__global__ __launch_bounds__(QT) void cluster_count_kernel(const WalkArgs a, int min_points, int* __restrict__ n_neighbors, uint8_t* __restrict__ core,
+__global__ __launch_bounds__(QT) void cluster_count_kernel(const GridWalk a, int min_points, int* __restrict__ n_neighbors, uint8_t* __restrict__ core,
                                                           uint8_t* __restrict__ core_sorted, int* __restrict__ evals) {
     const int N = count_of(a.n_dev, a.cap), M = count_of(a.n_dev + 1, a.cap);
     const float r2 = __fmul_rn(a.r, a.r);
@@ -98,7 +42,7 @@ __global__ __launch_bounds__(QT) void cluster_count_kernel(const WalkArgs a, int
         const float4 p = a.pts4[t];
         const int g = __float_as_int(p.w);
         int cnt = 0;
-        const int ev = cluster_walk(a, M, p.x, p.y, p.z, [&](int, float d2, const float4&) { cnt += d2 <= r2; });
+        const int ev = cloud_walk(a, M, p.x, p.y, p.z, [&](int, float d2, const float4&) { cnt += d2 <= r2; });
         const bool is_core = cnt >= min_points;
         n_neighbors[g] = cnt;
         core[g] = is_core;
@@ -141,14 +85,14 @@ D3R_DEV void cluster_unite(int* parent, int a, int b) {
     }
 }
 
-__global__ __launch_bounds__(QT) void cluster_union_kernel(const WalkArgs a, const uint8_t* __restrict__ core_sorted, int* parent) {
+__global__ __launch_bounds__(QT) void cluster_union_kernel(const GridWalk a, const uint8_t* __restrict__ core_sorted, int* parent) {
     const int N = count_of(a.n_dev, a.cap), M = count_of(a.n_dev + 1, a.cap);
     const float r2 = __fmul_rn(a.r, a.r);
     for (long long t = (long long)blockIdx.x * QT + threadIdx.x; t < N; t += (long long)gridDim.x * QT) {
         if (!core_sorted[t]) continue;
         const float4 p = a.pts4[t];
         const int g = __float_as_int(p.w);
-        cluster_walk(a, M, p.x, p.y, p.z, [&](int i, float d2, const float4& v) {
+        cloud_walk(a, M, p.x, p.y, p.z, [&](int i, float d2, const float4& v) {
             const int h = __float_as_int(v.w);
             if (d2 <= r2 && h < g && core_sorted[i]) cluster_unite(parent, g, h);
         });
@@ -172,16 +116,16 @@ __global__ __launch_bounds__(QT) void cluster_flatten_kernel(int n, const int* _
 }
 
 // root is read at core points and written at non-core points only
-__global__ __launch_bounds__(QT) void cluster_border_kernel(const WalkArgs a, const uint8_t* __restrict__ core_sorted, int* root) {
+__global__ __launch_bounds__(QT) void cluster_border_kernel(const GridWalk a, const uint8_t* __restrict__ core_sorted, int* root) {
     const int N = count_of(a.n_dev, a.cap), M = count_of(a.n_dev + 1, a.cap);
     const float r2 = __fmul_rn(a.r, a.r);
     for (long long t = (long long)blockIdx.x * QT + threadIdx.x; t < N; t += (long long)gridDim.x * QT) {
         if (core_sorted[t]) continue;
         const float4 p = a.pts4[t];
-        const uint64_t none = cluster_pair_key(__builtin_huge_valf(), 0x7FFFFFFF);
+        const uint64_t none = pair_key(__builtin_huge_valf(), NO_INDEX);
         uint64_t best = none;
-        cluster_walk(a, M, p.x, p.y, p.z, [&](int i, float d2, const float4& v) {
-            const uint64_t cand = cluster_pair_key(d2, __float_as_int(v.w));
+        cloud_walk(a, M, p.x, p.y, p.z, [&](int i, float d2, const float4& v) {
+            const uint64_t cand = pair_key(d2, __float_as_int(v.w));
             if (d2 <= r2 && core_sorted[i] && cand < best) best = cand;
         });
         if (best != none) root[__float_as_int(p.w)] = root[(int)(uint32_t)best];
@@ -189,28 +133,6 @@ __global__ __launch_bounds__(QT) void cluster_border_kernel(const WalkArgs a, co
 }
 
 // ---- numbering -----------------------------------------------------------------------------------------------------------------------------
-// the compaction of fuse_flag_kernel for the flag root[g] >= 0: tile counts (PLACE = false), then, with the counts scanned, (root, g) in index order
-template <bool PLACE>
-__global__ __launch_bounds__(NT) void cluster_flag_kernel(int n, const int* __restrict__ root, long long n_tiles, int* __restrict__ tile_cnt,
-                                                         uint64_t* __restrict__ keys, int* __restrict__ idx) {
-    __shared__ int wave_sums[WAVES];
-    for (long long T = blockIdx.x; T < n_tiles; T += gridDim.x) {
-        const long long g = T * NT + threadIdx.x;
-        const bool flag = g < n && root[g] >= 0;
-        int total;
-        const int pos = block_scan_1024(flag, wave_sums, &total);
-        if (!PLACE) {
-            if (threadIdx.x == 0) tile_cnt[T] = total;
-        } else if (flag) {
-            const long long o = (long long)tile_cnt[T] + pos;
-            if (o < n) {
-                keys[o] = (uint64_t)root[g];
-                idx[o] = (int)g;
-            }
-        }
-    }
-}
-
 // cluster c = segment c of the pairs sorted by root: the key n - size (0 <= key < n), so an ascending stable sort gives decreasing sizes
 __global__ __launch_bounds__(QT) void cluster_keys_kernel(int n, const int* __restrict__ starts, const int* __restrict__ n_dev, uint64_t* __restrict__ ckeys,
                                                          int* __restrict__ cidx) {
@@ -269,12 +191,6 @@ static inline ClusterWorkspace cluster_workspace(void* base, int n) {
     return w;
 }
 
-static inline int bit_length(unsigned v) {
-    int b = 0;
-    for (; v; v >>= 1) ++b;
-    return b;
-}
-
 }  // namespace cloud
 }  // namespace d3r
 
@@ -291,7 +207,7 @@ extern "C" int d3r_cloud_cluster(int n, float eps, int min_points, const float* 
     if (!fuse_shape_ok(1, n, n) || !lo || !bits || !labels_out || !sizes_out || !n_clusters_out || !n_neighbors_out || !core_out || !grid_workspace ||
         !workspace || !cloud_radius_ok(eps) || !cloud_cell_ok(cell) || min_points < 1)
         return D3R_ERR_INVALID;
-    WalkArgs a;
+    GridWalk a;
     int total_bits = 0;
     if (!fuse_key_params(lo, cell, bits, &a.key, &total_bits)) return D3R_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
@@ -314,14 +230,14 @@ extern "C" int d3r_cloud_cluster(int n, float eps, int min_points, const float* 
     mark(2);
     // numbering: (root, point) of the labelled points, sorted by root; one segment per cluster
     const long long tiles = d3r::tiles_of(n, NT);
-    hipLaunchKernelGGL((cluster_flag_kernel<false>), dim3(d3r::blocks_of(tiles, MAX_BLOCKS)), dim3(NT), 0, st, n, w.root, tiles, w.f.tile_cnt, w.f.keys[0], w.f.idx[0]);
+    const dim3 tile_grid(d3r::blocks_of(tiles, MAX_BLOCKS));
+    FlagArgs fa = {};                                                      // ROOTS and HEADS read root, n_dev, cap and the sorted keys only
+    fa.root = w.root; fa.n_dev = w.f.n_dev; fa.cap = n;
+    hipLaunchKernelGGL((fuse_flag_kernel<ROOTS, false>), tile_grid, dim3(NT), 0, st, fa, tiles, w.f.tile_cnt, w.f.keys[0], w.f.idx[0]);
     hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(NT), 0, st, w.f.tile_cnt, (int)tiles, w.f.n_dev);
-    hipLaunchKernelGGL((cluster_flag_kernel<true>), dim3(d3r::blocks_of(tiles, MAX_BLOCKS)), dim3(NT), 0, st, n, w.root, tiles, w.f.tile_cnt, w.f.keys[0], w.f.idx[0]);
+    hipLaunchKernelGGL((fuse_flag_kernel<ROOTS, true>), tile_grid, dim3(NT), 0, st, fa, tiles, w.f.tile_cnt, w.f.keys[0], w.f.idx[0]);
     const int index_bits = bit_length((unsigned)(n - 1));
     const int cur = fuse_sort_pairs(w.f.keys, w.f.idx, w.f.hist, w.f.n_dev, n, index_bits, 0, st);
-    FlagArgs fa;
-    fa.pts = nullptr; fa.mask = nullptr; fa.weight = nullptr; fa.img_h = nullptr; fa.img_w = nullptr; fa.row = n; fa.tiles_per_view = 0; fa.key = a.key;
-    fa.n_dev = w.f.n_dev; fa.cap = n;
     const int* starts = fuse_segment_heads(fa, w.f, cur, n, st);
     // the clusters by (n - size), stable: equal sizes stay in ascending root order
     hipLaunchKernelGGL(cluster_keys_kernel, grid, block, 0, st, n, starts, w.f.n_dev, w.ckeys[0], w.cidx[0]);

@@ -1,7 +1,9 @@
-// dust3r_amd -- what cloud_nn.hip (the grid, the distance statistics), cloud_knn.hip (the search on the grid) and cloud_icp.hip (the
-// registration's sums) share: the layout of the grid's workspace, the checks of the cell size and the radius, the padded cell range's
-// arithmetic, the 1 x n shape table, and the ordered fp64 / int64 sum of all three: the workgroup's sum (reduce.hpp's reduction, whose
-// header states the order), the final kernel over the per-workgroup partials and the partials' layout. As in fuse_grid.hpp every kernel is static, so each file launches its own copy.
+// dust3r_amd -- what cloud_nn.hip (the grid, the distance statistics), cloud_knn.hip (the search on the grid), cloud_icp.hip (the
+// registration's sums) and cloud_cluster.hip (the density clustering) share: the layout of the grid's workspace, the checks of the cell
+// size and the radius, the 1 x n shape table, THE WALK of a point's padded cell range over the grid (GridWalk / cloud_walk: the one text
+// that the search and the three clustering kernels run, and that the exactness argument of DESIGN.md 4.12 rests on), the (d2, index) pair
+// as one 64-bit key, and the ordered fp64 / int64 sum: the workgroup's sum (reduce.hpp's reduction, whose header states the order), the
+// final kernel over the per-workgroup partials and the partials' layout. As in fuse_grid.hpp every kernel is static, so each file launches its own copy.
 #pragma once
 #include "common.hpp"
 #include "scene_common.hpp"
@@ -68,6 +70,69 @@ static inline bool cloud_radius_ok(float r) {
     return r > 0.f && r2 >= 1.17549435e-38f && r2 <= 3.4028234e38f;
 }
 static inline int cloud_blocks(long long n) { return blocks_of(tiles_of(n, QT), MAX_BLOCKS); }
+
+// ---- the walk ----------------------------------------------------------------------------------------------------------------------------
+constexpr int NO_INDEX = 0x7FFFFFFF;    // the index of an empty slot: above every real one, so (inf, NO_INDEX) sorts last
+
+// The pair (d2, g) as one 64-bit key, d2's bits above g: d2 is a sum of squares, so +0 <= d2 <= +inf and never NaN for finite coordinates,
+// and the bits of such floats order as unsigned integers; g >= 0. Lexicographic (d2, g) order is the unsigned order of the keys: one
+// comparison per candidate. The empty slot (+inf, NO_INDEX) is above every pair a walk accepts (d2 <= r2 < inf).
+D3R_DEV uint64_t pair_key(float d2, int g) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)g; }
+
+struct GridWalk {
+    KeyParams key;
+    float r;
+    const float4* pts4;                 // the grid: the valid points in cell order, w = the original index
+    const uint64_t* cell_key;
+    const int* cell_start;
+    const int* n_dev;                   // [2]: the valid points N, the cells M
+    int cap;
+};
+
+// The walk for the point (ax, ay, az) over the M cells: per axis the cells from q(next_down(a - r')) to q(next_up(a + r')), r' = r (1 +
+// 2^-10); per (z, y) row one binary search and one run of points. f(i, d2, v) for EVERY looked-at point i (sorted position), d2 in fp32 with
+// every operation rounded on its own -- the caller tests d2 <= r2. Returns the distances evaluated.
+template <class F>
+D3R_DEV int cloud_walk(const GridWalk& a, int M, float ax, float ay, float az, F&& f) {
+    const float rp = __fmul_rn(a.r, 1.0009765625f);
+    const float pa[3] = {ax, ay, az};
+    int c0[3], c1[3];
+    bool outside = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float lo = next_down(__fsub_rn(pa[c], rp)), hi = next_up(__fadd_rn(pa[c], rp));
+        // every grid point has 0 <= floorf(.) <= qmax (lo = the bounds' minimum, bits from their extent) and floorf(.) is monotone: an
+        // interval that ends below cell 0 or starts above the last cell holds none
+        outside = outside || axis_f(hi, a.key, c) < 0.f || axis_f(lo, a.key, c) > (float)a.key.qmax[c];
+        c0[c] = axis_q(lo, a.key, c);
+        c1[c] = axis_q(hi, a.key, c);
+    }
+    if (outside) return 0;
+    int evals = 0, from = 0;                                               // the rows come in ascending key order: each search starts where the last ended
+    for (int z = c0[2]; z <= c1[2]; ++z) {
+        for (int y = c0[1]; y <= c1[1]; ++y) {
+            const uint64_t row = ((uint64_t)y << a.key.shift[1]) | ((uint64_t)z << a.key.shift[2]);
+            const uint64_t k_lo = row | (uint64_t)c0[0], k_hi = row | (uint64_t)c1[0];
+            int l = from, h = M;                                           // the first cell with key >= k_lo
+            while (l < h) {
+                const int m = l + ((h - l) >> 1);
+                if (a.cell_key[m] < k_lo) l = m + 1; else h = m;
+            }
+            int j = l;
+            while (j < M && a.cell_key[j] <= k_hi) ++j;                   // at most c1 - c0 + 1 cells: one run of points
+            from = j;
+            if (j == l) continue;
+            const int s = a.cell_start[l], e = a.cell_start[j];
+            for (int i = s; i < e; ++i) {
+                const float4 v = a.pts4[i];
+                const float dx = __fsub_rn(ax, v.x), dy = __fsub_rn(ay, v.y), dz = __fsub_rn(az, v.z);
+                f(i, __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)), v);
+            }
+            evals += e - s;
+        }
+    }
+    return evals;
+}
 
 // ---- the ordered sum: ND doubles and NI int64s per thread -> per workgroup -> one row -------------------------------------------------------
 constexpr int SUM_PARTS = 1024;         // grid cap of a pass that leaves partials = the rows the final kernel reads

@@ -6,7 +6,8 @@
 // points with fp32 d2 <= r2 (the query's own index left out with exclude_self), and its row holds the k smallest (d2, index) pairs in
 // lexicographic order, padded with (+inf, -1); the nearest neighbour, the lowest index among the points of minimal d2 when that minimum is
 // <= r2, is the row of one column. The grid only limits which points are LOOKED AT, and the looked-at set holds every point with d2 <= r2
-// ("Cloud metrics"). A cell that holds most of the cloud is walked point by point by every query near it: slow, not wrong.
+// ("Cloud metrics"): the walk itself is cloud_grid.hpp's cloud_walk, which the clustering runs too. A cell that holds most of
+// the cloud is walked point by point by every query near it: slow, not wrong.
 //   d3r_cloud_knn             cloud_knn_init_kernel      every row padded, or, with only_unresolved, the mask idx[q][k - 1] < 0 of the open rows
 //   d3r_cloud_nearest         stages 1-2 of fuse_grid.hpp on the queries with the grid's own key: the queries in the order of their cells
 //                             cloud_knn_kernel<1|8|16|32>   one thread per query, in that order: the lanes of a wave walk the same runs; the
@@ -27,7 +28,6 @@ namespace d3r {
 namespace cloud {
 
 constexpr int JACOBI_SWEEPS = 8;        // cyclic Jacobi on 3 x 3 converges quadratically: 4-5 sweeps reach fp64 rounding, 8 leave a margin
-constexpr int NO_INDEX = 0x7FFFFFFF;    // the index of an empty list slot: above every real one, so (inf, NO_INDEX) sorts last
 
 // a fresh call: every row (+inf, -1). only_unresolved: the rows stay, mask[q] = the row is still short of k neighbours
 __global__ __launch_bounds__(QT) void cloud_knn_init_kernel(int n, int k, int only_unresolved, float* __restrict__ d2_out, int* __restrict__ idx_out,
@@ -45,14 +45,8 @@ __global__ __launch_bounds__(QT) void cloud_knn_init_kernel(int n, int k, int on
 }
 
 struct KnnArgs {
-    KeyParams key;
-    float r;
+    GridWalk grid;                      // the reference cloud's grid and the radius (cloud_grid.hpp)
     int k, exclude_self;
-    const float4* pts4;                 // the grid
-    const uint64_t* cell_key;
-    const int* cell_start;
-    const int* n_ref_dev;               // [2]: the valid reference points N, the cells M
-    int cap_ref;
     const float* query;
     const int* order;                   // the valid (and open) queries in the order of their cells
     const int* n_query_dev;
@@ -62,73 +56,30 @@ struct KnnArgs {
     int* evals;                         // optional: += the distances this query evaluated
 };
 
-// The pair (d2, g) as one 64-bit key, d2's bits above g: d2 is a sum of squares, so +0 <= d2 <= +inf and never NaN for finite coordinates,
-// and the bits of such floats order as unsigned integers; g >= 0. Lexicographic (d2, g) order is the unsigned order of the keys: one
-// comparison per list slot. The empty slot (+inf, NO_INDEX) is above every pair the kernel accepts (d2 <= r2 < inf).
-D3R_DEV uint64_t pair_key(float d2, int g) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)g; }
-
 // K list slots, k <= K columns written. Slot K - 1 is the pruning bound.
 template <int K>
 __global__ __launch_bounds__(QT) void cloud_knn_kernel(const KnnArgs a) {
-    const int M = count_of(a.n_ref_dev + 1, a.cap_ref);
+    const int M = count_of(a.grid.n_dev + 1, a.grid.cap);
     const int Nq = count_of(a.n_query_dev, a.cap_query);
-    const float r2 = __fmul_rn(a.r, a.r);
-    const float rp = __fmul_rn(a.r, 1.0009765625f);                     // r (1 + 2^-10)
+    const float r2 = __fmul_rn(a.grid.r, a.grid.r);
     for (long long t = (long long)blockIdx.x * QT + threadIdx.x; t < Nq; t += (long long)gridDim.x * QT) {
         const int q = a.order[t];
         const float* p = a.query + 3 * (size_t)q;
-        const float ax = p[0], ay = p[1], az = p[2];
-        const float pa[3] = {ax, ay, az};
-        int c0[3], c1[3];
-        bool outside = false;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float lo = next_down(__fsub_rn(pa[c], rp)), hi = next_up(__fadd_rn(pa[c], rp));
-            // every reference point has 0 <= floorf(.) <= qmax (lo = the bounds' minimum, bits from their extent) and floorf(.) is monotone:
-            // an interval that ends below cell 0 or starts above the last cell holds none
-            outside = outside || axis_f(hi, a.key, c) < 0.f || axis_f(lo, a.key, c) > (float)a.key.qmax[c];
-            c0[c] = axis_q(lo, a.key, c);
-            c1[c] = axis_q(hi, a.key, c);
-        }
         uint64_t list[K];
 #pragma unroll
         for (int j = 0; j < K; ++j) list[j] = pair_key(__builtin_huge_valf(), NO_INDEX);
         const int self = a.exclude_self ? q : -1;
-        int evals = 0;
-        if (!outside) {
-            int from = 0;                                                  // the rows come in ascending key order: each search starts where the last ended
-            for (int z = c0[2]; z <= c1[2]; ++z) {
-                for (int y = c0[1]; y <= c1[1]; ++y) {
-                    const uint64_t row = ((uint64_t)y << a.key.shift[1]) | ((uint64_t)z << a.key.shift[2]);
-                    const uint64_t k_lo = row | (uint64_t)c0[0], k_hi = row | (uint64_t)c1[0];
-                    int l = from, h = M;                                   // the first cell with key >= k_lo
-                    while (l < h) {
-                        const int m = l + ((h - l) >> 1);
-                        if (a.cell_key[m] < k_lo) l = m + 1; else h = m;
-                    }
-                    int j = l;
-                    while (j < M && a.cell_key[j] <= k_hi) ++j;           // at most c1 - c0 + 1 cells: one run of points
-                    from = j;
-                    if (j == l) continue;
-                    const int s = a.cell_start[l], e = a.cell_start[j];
-                    for (int i = s; i < e; ++i) {
-                        const float4 v = a.pts4[i];
-                        const float dx = __fsub_rn(ax, v.x), dy = __fsub_rn(ay, v.y), dz = __fsub_rn(az, v.z);
-                        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-                        const int g = __float_as_int(v.w);
-                        const uint64_t cand = pair_key(d2, g);
-                        if (d2 <= r2 && g != self && cand < list[K - 1]) {
-                            // slot j takes its left neighbour when the candidate sorts before that one, else the candidate when it sorts
-                            // before slot j itself; from the right, so every read sees the old list. Static indices only.
+        const int evals = cloud_walk(a.grid, M, p[0], p[1], p[2], [&](int, float d2, const float4& v) {
+            const int g = __float_as_int(v.w);
+            const uint64_t cand = pair_key(d2, g);
+            if (d2 <= r2 && g != self && cand < list[K - 1]) {
+                // slot j takes its left neighbour when the candidate sorts before that one, else the candidate when it sorts before slot j
+                // itself; from the right, so every read sees the old list. Static indices only.
 #pragma unroll
-                            for (int j2 = K - 1; j2 > 0; --j2) list[j2] = cand < list[j2 - 1] ? list[j2 - 1] : (cand < list[j2] ? cand : list[j2]);
-                            list[0] = cand < list[0] ? cand : list[0];
-                        }
-                    }
-                    evals += e - s;
-                }
+                for (int j = K - 1; j > 0; --j) list[j] = cand < list[j - 1] ? list[j - 1] : (cand < list[j] ? cand : list[j]);
+                list[0] = cand < list[0] ? cand : list[0];
             }
-        }
+        });
         float* d2_row = a.d2_out + (size_t)q * a.k;
         int* idx_row = a.idx_out + (size_t)q * a.k;
 #pragma unroll
@@ -336,8 +287,8 @@ extern "C" int d3r_cloud_knn(int n_ref, int n_query, const float* query, int k, 
     a.pts = query; a.mask = only_unresolved ? w.mask : nullptr; a.weight = nullptr; a.img_h = w.shape + 2; a.img_w = w.shape + 3;
     a.row = n_query;
     const int cur = fuse_key_and_sort(a, w.qry, 1, n_query, total_bits, st);
-    qa.key = a.key; qa.r = r; qa.k = k; qa.exclude_self = exclude_self != 0;
-    qa.pts4 = w.pts4; qa.cell_key = w.cell_key; qa.cell_start = w.cell_start; qa.n_ref_dev = w.ref.n_dev; qa.cap_ref = n_ref;
+    qa.grid.key = a.key; qa.grid.r = r; qa.k = k; qa.exclude_self = exclude_self != 0;
+    qa.grid.pts4 = w.pts4; qa.grid.cell_key = w.cell_key; qa.grid.cell_start = w.cell_start; qa.grid.n_dev = w.ref.n_dev; qa.grid.cap = n_ref;
     qa.query = query; qa.order = w.qry.idx[cur]; qa.n_query_dev = w.qry.n_dev; qa.cap_query = n_query;
     qa.d2_out = d2_out; qa.idx_out = idx_out; qa.evals = evals;
     const dim3 grid(cloud_blocks(n_query)), block(QT);

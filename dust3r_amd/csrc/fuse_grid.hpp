@@ -99,7 +99,8 @@ static __global__ __launch_bounds__(NT) void fuse_scan_kernel(int* __restrict__ 
 // the flagged elements placed in order (PLACE = true).
 //   KEYS:  element = pixel e = t NT + thread of view v, T = v tiles_per_view + t; flag = valid; places (key, g) into keys / idx
 //   HEADS: element = sorted pair i = T NT + thread; flag = i < N and (i == 0 or key[i] != key[i - 1]); places i into idx
-enum { KEYS = 0, HEADS = 1 };
+//   ROOTS: element = point i = T NT + thread; flag = i < cap and root[i] >= 0; places (root[i], i) into keys / idx (cloud_cluster.hip)
+enum { KEYS = 0, HEADS = 1, ROOTS = 2 };
 struct FlagArgs {
     const float* pts;
     const uint8_t* mask;
@@ -110,6 +111,7 @@ struct FlagArgs {
     const uint64_t* sorted;             // HEADS: the sorted keys
     const int* n_dev;
     int cap;
+    const int* root;                    // ROOTS: the cluster root of every point, -1 for none. Last: the fields above keep their offsets
 };
 
 template <int WHAT, bool PLACE>
@@ -128,7 +130,7 @@ static __global__ __launch_bounds__(NT) void fuse_flag_kernel(const FlagArgs a, 
             flag = e < area_of(a.img_h[v], a.img_w[v], a.row) && valid_at(a.pts, a.mask, a.weight, g);
         } else {
             i = T * NT + threadIdx.x;
-            flag = i < N && (i == 0 || a.sorted[i] != a.sorted[i - 1]);
+            flag = WHAT == HEADS ? i < N && (i == 0 || a.sorted[i] != a.sorted[i - 1]) : i < a.cap && a.root[i] >= 0;
         }
         int total;
         const int pos = block_scan_1024(flag, wave_sums, &total);
@@ -141,6 +143,7 @@ static __global__ __launch_bounds__(NT) void fuse_flag_kernel(const FlagArgs a, 
                     keys[o] = key_of(a.pts + 3 * g, a.key);
                     idx[o] = (int)g;
                 } else {
+                    if (WHAT == ROOTS) keys[o] = (uint64_t)a.root[i];
                     idx[o] = (int)i;
                 }
             }
@@ -268,6 +271,13 @@ static inline bool fuse_key_params(const float* lo, float voxel, const int* bits
     }
     key->voxel = voxel;
     return true;
+}
+
+// the bits of x: what a sort by an index below n needs, bit_length(n - 1)
+static inline int bit_length(unsigned x) {
+    int b = 0;
+    for (; x; x >>= 1) ++b;
+    return b;
 }
 
 // Stage 2 on the stream, on buffers of the caller's (tracks.hip sorts its observations by view with it): the *n_dev (at most capacity)

@@ -206,12 +206,6 @@ static inline bool tracks_walk_args(WalkArgs* a, int n_views, const float* pts, 
     return true;
 }
 
-static inline int bit_length(unsigned x) {
-    int b = 0;
-    for (; x; x >>= 1) ++b;
-    return b;
-}
-
 }  // namespace tracks
 }  // namespace d3r
 

@@ -176,6 +176,14 @@ class FusedCloud:
         self.tracks = tracks                                   # the `CloudTracks` of `build_tracks`, else None
         self.labels, self.cluster_sizes = labels, cluster_sizes    # (M,) int32 (-1 = noise) and (C,) int32 of `cluster`, else None
 
+    PER_POINT = ('positions', 'colors', 'weight', 'count', 'normals', 'curvature', 'labels')      # one row per point: what a subset masks
+
+    def _with(self, **changes):
+        """A new cloud with this cloud's fields, the named ones replaced: a deriving method says only what it changes. The attributes ARE the
+        constructor's arguments, plus origin, which follows bounds."""
+        fields = {name: value for name, value in vars(self).items() if name != 'origin'}
+        return FusedCloud(**dict(fields, **changes))
+
     def __len__(self):
         return len(self.positions)
 
@@ -198,11 +206,9 @@ class FusedCloud:
     def _subset(self, keep):
         """(cloud, mask) of the points where the device bool tensor `keep` is set: normals, curvature and labels are carried along
         (cluster_sizes too: they still describe the labels), tracks are not. The mask comes back where this cloud's arrays are."""
-        fields = [self.positions, self.colors, self.weight, self.count, self.normals, self.curvature, self.labels]
         mask = keep if isinstance(self.positions, torch.Tensor) else keep.cpu().numpy()
-        out = [None if a is None else a[mask] for a in fields]
-        return FusedCloud(*out[:4], voxel_size=self.voxel_size, bounds=self.bounds, normals=out[4], curvature=out[5], labels=out[6],
-                          cluster_sizes=self.cluster_sizes), mask
+        rows = {name: getattr(self, name) for name in self.PER_POINT}
+        return self._with(tracks=None, **{name: a[mask] for name, a in rows.items() if a is not None}), mask
 
     @torch.no_grad()
     def cluster(self, eps=None, min_points=10):
@@ -225,8 +231,7 @@ class FusedCloud:
                 eps = 2.5 * self.voxel_size
         _radius_f32(eps, 'eps')
         res = cluster_points(self, eps, min_points=min_points, to_host=not isinstance(self.positions, torch.Tensor))
-        return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=self.normals,
-                          curvature=self.curvature, tracks=self.tracks, labels=res.labels, cluster_sizes=res.sizes)
+        return self._with(labels=res.labels, cluster_sizes=res.sizes)
 
     def keep_clusters(self, largest=None, min_size=None, labels=None):
         """(cloud, keep) of a clustered cloud (`cluster`), like `remove_outliers`: the points of the chosen clusters, keep (M,) bool.
@@ -265,8 +270,7 @@ class FusedCloud:
         colors = label_colors(self.labels)
         if isinstance(self.colors, torch.Tensor):
             colors = torch.from_numpy(colors).to(self.colors.device)
-        return FusedCloud(self.positions, colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=self.normals,
-                          curvature=self.curvature, tracks=self.tracks, labels=self.labels, cluster_sizes=self.cluster_sizes)
+        return self._with(colors=colors)
 
     @torch.no_grad()
     def estimate_normals(self, k=16, max_dist=None, scene=None, tol=0.05, min_neighbors=3):
@@ -294,8 +298,7 @@ class FusedCloud:
                                tol=tol)
         if not on_device:
             normals, curvature = normals.cpu().numpy(), curvature.cpu().numpy()
-        return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=normals, curvature=curvature,
-                          tracks=self.tracks, labels=self.labels, cluster_sizes=self.cluster_sizes)
+        return self._with(normals=normals, curvature=curvature)
 
     @torch.no_grad()
     def remove_outliers(self, k=16, std_ratio=2.0, max_dist=None):
@@ -338,8 +341,7 @@ class FusedCloud:
             bounds = (lo, hi) if n_valid > 0 else self.bounds
             if not on_device:
                 positions, normals = positions.cpu().numpy(), None if normals is None else normals.cpu().numpy()
-        return FusedCloud(positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size * scale, bounds=bounds, normals=normals,
-                          curvature=self.curvature, labels=self.labels, cluster_sizes=self.cluster_sizes)
+        return self._with(positions=positions, normals=normals, voxel_size=self.voxel_size * scale, bounds=bounds, tracks=None)
 
     def distance_to(self, other, max_dist, to_host=True):
         """(d2, idx) of every point of this cloud in `other` (a FusedCloud or (N, 3) points) within max_dist: squared distances (+inf where
@@ -366,8 +368,7 @@ class FusedCloud:
         tracks = cloud_tracks(self.positions, scene.get_pts3d(raw=True), scene.get_masks(raw=True), scene._im_conf if weights == 'conf' else None,
                               scene.get_intrinsics(), scene.get_im_poses(), scene.imshapes, max_dist, max_error=max_error, device=scene.device,
                               to_host=not isinstance(self.positions, torch.Tensor))
-        return FusedCloud(self.positions, self.colors, self.weight, self.count, voxel_size=self.voxel_size, bounds=self.bounds, normals=self.normals,
-                          curvature=self.curvature, tracks=tracks, labels=self.labels, cluster_sizes=self.cluster_sizes)
+        return self._with(tracks=tracks)
 
 
 LABEL_PALETTE = np.array([(31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103, 189), (140, 86, 75), (227, 119, 194), (188, 189, 34),

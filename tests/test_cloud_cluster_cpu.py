@@ -245,6 +245,42 @@ def test_fused_cloud_carries_labels_where_the_points_stay():
     assert plain.labels is None and plain.cluster_sizes is None
 
 
+FIELDS = ('positions', 'colors', 'weight', 'count', 'voxel_size', 'bounds', 'normals', 'curvature', 'tracks', 'labels', 'cluster_sizes')
+
+
+def test_derived_clouds_keep_carry_or_drop_every_field():
+    """every deriving method that runs without a GPU, on a cloud with ALL eleven fields set, field by field as the docstrings say: kept (the
+    same object), carried along (the masked rows) or dropped (None); origin follows bounds"""
+    import inspect
+    from dust3r_amd.viz import FusedCloud
+    assert tuple(inspect.signature(FusedCloud.__init__).parameters)[1:] == FIELDS
+    assert set(FusedCloud.PER_POINT) == {'positions', 'colors', 'weight', 'count', 'normals', 'curvature', 'labels'}
+    rng = np.random.default_rng(4)
+    labels, sizes, tracks = np.array([0, 0, 0, 1, 1, -1, 2, 0, 1, 2, -1, 0], np.int32), np.array([5, 3, 2], np.int32), object()
+    cloud = _fused(normals=rng.random((12, 3)).astype(F32), curvature=rng.random(12).astype(F32), tracks=tracks, labels=labels, cluster_sizes=sizes)
+    assert all(getattr(cloud, name) is not None for name in FIELDS) and cloud.origin is cloud.bounds[0]
+
+    coloured = cloud.colored_by_label()                                    # the same points: only the colours are new
+    assert coloured is not cloud and coloured.colors is not cloud.colors and coloured.colors.shape == (12, 3)
+    for name in FIELDS:
+        if name != 'colors':
+            assert getattr(coloured, name) is getattr(cloud, name) or name == 'voxel_size' and coloured.voxel_size == cloud.voxel_size, name
+    assert coloured.origin is cloud.bounds[0]
+
+    kept, keep = cloud.keep_clusters(largest=1)                            # a subset: rows carried along, tracks dropped, the rest kept
+    assert np.array_equal(keep, labels == 0) and len(kept) == 5
+    for name in FusedCloud.PER_POINT:
+        assert np.array_equal(getattr(kept, name), getattr(cloud, name)[keep]) and getattr(kept, name).dtype == getattr(cloud, name).dtype, name
+    assert kept.tracks is None and kept.cluster_sizes is sizes and kept.bounds is cloud.bounds and kept.origin is cloud.bounds[0]
+    assert kept.voxel_size == cloud.voxel_size
+    for name in FIELDS:                                                    # and the cloud it came from is as it was
+        assert getattr(cloud, name) is not None, name
+    assert cloud.tracks is tracks and cloud.labels is labels
+
+    bare, _ = _fused(labels=labels, cluster_sizes=sizes).keep_clusters(min_size=3)      # what the cloud does not have stays None
+    assert bare.normals is None and bare.curvature is None and bare.tracks is None and len(bare.labels) == 8
+
+
 # ---- 3. PLY ----------------------------------------------------------------------------------------------------------------------------------
 def test_ply_with_labels_round_trips(tmp_path):
     from dust3r_amd.export import read_ply, write_ply
@@ -347,7 +383,8 @@ def test_resource_report_has_no_scratch():
     report = open(path).read()
     kernels = re.findall(r'Function Name: (\S+)', report)
     new = [k for k in kernels if 'cluster_' in k]
-    assert len(new) == 10 and sum('cluster_flag_kernel' in k for k in new) == 2 and all('cluster_' in k or 'cloud_' in k or 'fuse_' in k for k in kernels)
+    assert len(new) == 8 and all('cluster_' in k or 'cloud_' in k or 'fuse_' in k for k in kernels)
+    assert sum('fuse_flag_kernel' in k for k in kernels) == 6             # KEYS, HEADS and ROOTS, counting and placing (fuse_grid.hpp)
     for name in ('cluster_count_kernel', 'cluster_union_kernel', 'cluster_border_kernel', 'cluster_flatten_kernel'):
         assert sum(name in k for k in new) == 1
     assert re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', report) == ['0'] * len(kernels)

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from test_cloud_cluster_cpu import PARAMS, SCENE, partition_of, restated_dbscan, scene_restated
+from test_cloud_metrics_cpu import lattice_case, restated_grid_nearest
 
 pytestmark = pytest.mark.gpu
 
@@ -191,7 +192,65 @@ def test_ranges_that_leave_the_grid(gpu):
     _same(_run(far, 0.06, 3), restated_dbscan(far, 0.06, 3))
 
 
-# ---- 4. through the API -------------------------------------------------------------------------------------------------------------------
+# ---- 4. one walk: the search and the clustering look at the same points --------------------------------------------------------------------
+def walk_cloud(r):
+    """(308, 3) float32: the reference lattice of test_cloud_metrics_cpu.lattice_case (spacing r, side 6, with its 20 duplicates) plus its
+    72 queries one and two spacings outside every face, so that the padded ranges of the inner points are cut at those of the outer ones
+    and those of the outer ones leave the grid; a NaN, a +inf and a -inf row"""
+    Q, R = lattice_case(np.random.default_rng(21), r, 0.0, side=6)
+    assert len(Q) == 30 + 12 * (12 + 6) + 30 + 20                          # lattice_case's layout: per (axis, k) 12 displaced sites, then 6 beyond the face
+    beyond = Q[30:30 + 12 * 18].reshape(12, 18, 3)[:, 12:].reshape(-1, 3)
+    P = np.concatenate([R, beyond]).astype(F32)
+    P[3, 0], P[100, 1], P[-1, 2] = np.nan, np.inf, -np.inf
+    return P
+
+
+@pytest.mark.parametrize('factor', [0.5, 1.0, 2.0])
+def test_search_and_clustering_walk_the_same_points(gpu, factor):
+    """d3r_cloud_nearest, d3r_cloud_knn and d3r_cloud_cluster on ONE grid of the cloud, the cloud as its own queries: per point the same
+    number of distance evaluations, that of the numpy restatement of the walk, and zero at the non-finite rows; and the clustering's
+    n_neighbors is the number of columns a 32-column search fills (every point here has fewer than 32 neighbours: on a lattice of spacing r
+    the sites within r are the point's own and its six axis neighbours, each held once or a few times)."""
+    import ctypes as C
+    from dust3r_amd._lib import check, current_stream, lib, ptr
+    from dust3r_amd.cloud_metrics import _bounds
+    from dust3r_amd.viz import fuse_key_bits
+    for r in (0.25, 1e-3):
+        P = walk_cloud(r)
+        n, bad = len(P), ~np.isfinite(P).all(axis=1)
+        assert bad.sum() == 3
+        cell = np.float32(r) * np.float32(factor)
+        want_evals = restated_grid_nearest(P, P, r, cell)[2]
+        want_count = restated_dbscan(P, r, 1).n_neighbors                   # the fp32 brute force over all pairs
+        assert want_count.max() < 32 and want_count[~bad].min() >= 1 and (want_evals[bad] == 0).all() and (want_evals[~bad] >= want_count[~bad]).all()
+        Pd = torch.from_numpy(P).to(gpu)
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=gpu)      # noqa: E731
+        with torch.cuda.device(gpu):
+            lo, hi, n_valid = _bounds(Pd, gpu)
+            assert n_valid == n - 3
+            lo_c, bits_c = (C.c_float * 3)(*lo.tolist()), (C.c_int * 3)(*fuse_key_bits(lo, hi, cell))
+            grid = torch.empty(int(lib.d3r_cloud_grid_workspace_bytes(n, n)), dtype=torch.uint8, device=gpu)
+            work = torch.empty(int(lib.d3r_cloud_cluster_workspace_bytes(n)), dtype=torch.uint8, device=gpu)
+            where = (lo_c, float(cell), bits_c)
+            check(lib.d3r_cloud_grid_build(n, ptr(Pd), *where, ptr(grid), current_stream()), 'build')
+            ev_nearest, ev_knn, ev_cluster = i32(n), i32(n), i32(n)
+            d2 = {k: torch.empty((n, k), device=gpu) for k in (1, 8, 32)}
+            idx = {k: i32(n, k) for k in (1, 8, 32)}
+            radius, stream = float(np.float32(r)), current_stream()
+            check(lib.d3r_cloud_nearest(n, n, ptr(Pd), radius, *where, 0, ptr(d2[1]), ptr(idx[1]), ptr(ev_nearest), ptr(grid), stream), 'nearest')
+            check(lib.d3r_cloud_knn(n, n, ptr(Pd), 8, radius, *where, 0, 0, ptr(d2[8]), ptr(idx[8]), ptr(ev_knn), ptr(grid), stream), 'knn')
+            check(lib.d3r_cloud_knn(n, n, ptr(Pd), 32, radius, *where, 0, 0, ptr(d2[32]), ptr(idx[32]), None, ptr(grid), stream), 'knn at k = 32')
+            labels, sizes, n_clusters, n_neighbors, core = i32(n), i32(n), i32(1), i32(n), torch.zeros((n,), dtype=torch.uint8, device=gpu)
+            check(lib.d3r_cloud_cluster(n, radius, 4, *where, ptr(labels), ptr(sizes), ptr(n_clusters), ptr(n_neighbors), ptr(core), ptr(ev_cluster), None,
+                                        ptr(grid), ptr(work), stream), 'cluster')
+        ev_nearest, ev_knn, ev_cluster = (t.cpu().numpy() for t in (ev_nearest, ev_knn, ev_cluster))
+        assert np.array_equal(ev_nearest, ev_knn) and np.array_equal(ev_knn, ev_cluster), r
+        assert np.array_equal(ev_cluster, want_evals) and (ev_cluster[bad] == 0).all() and ev_cluster.max() > 0, r
+        filled = torch.isfinite(d2[32]).sum(dim=1).cpu().numpy()
+        assert np.array_equal(n_neighbors.cpu().numpy(), filled) and np.array_equal(filled, want_count), r
+
+
+# ---- 5. through the API -------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def scene(gpu):
     from test_fuse_gpu import _scene
