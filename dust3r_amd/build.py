@@ -7,14 +7,15 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['gemm.hip', 'gemm_p4.hip', 'gemm_up2.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'sky.hip', 'visloc.hip', 'mesh.hip', 'fuse.hip', 'cloud_nn.hip', 'cloud_knn.hip', 'cloud_icp.hip', 'cloud_cluster.hip', 'tracks.hip', 'gallery.hip', 'render.hip', 'losses.hip', 'views.hip', 'engine.hip', 'capi.hip']
-HEADERS = ['common.hpp', 'reduce.hpp', 'scene_common.hpp', 'kernels.hpp', 'gemm_plan.hpp', 'gemm_head4.hpp', 'aligner_math.hpp', 'visloc_math.hpp', 'views_math.hpp', 'gallery_math.hpp', 'fuse_grid.hpp', 'cloud_grid.hpp', os.path.join('..', '..', 'include', 'dust3r_hip.h')]
+SOURCES = ['gemm.hip', 'gemm_p4.hip', 'gemm_p4_heads.hip', 'gemm_up2.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'sky.hip', 'visloc.hip', 'mesh.hip', 'fuse.hip', 'cloud_nn.hip', 'cloud_knn.hip', 'cloud_icp.hip', 'cloud_cluster.hip', 'tracks.hip', 'gallery.hip', 'render.hip', 'losses.hip', 'views.hip', 'engine.hip', 'capi.hip']
+HEADERS = ['common.hpp', 'reduce.hpp', 'scene_common.hpp', 'kernels.hpp', 'gemm_plan.hpp', 'gemm_p4.hpp', 'gemm_head4.hpp', 'aligner_math.hpp', 'visloc_math.hpp', 'views_math.hpp', 'gallery_math.hpp', 'fuse_grid.hpp', 'cloud_grid.hpp', os.path.join('..', '..', 'include', 'dust3r_hip.h')]
 LIB = os.path.join(CSRC, 'libdust3r_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-inline-asm']
 # attention.hip: no SLP vectorisation -- its scalar-VALU softmax slices (attention_x3_kernel<..., SC = true>) must stay v_fma_f32 / v_add_f32
 # pairs; hipcc -O3 re-packs adjacent scalar fp32 operations into v_pk_* (an anti-lever beside MFMAs, MI355X_MICROARCH.md). The packed
 # variants of the same kernel use explicit 2-vectors and are not affected.
 EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'gemm_p4.hip': ['-fno-slp-vectorize', '-Rpass-analysis=kernel-resource-usage'],     # gemm_p4.hip: its drain's scalar GELU pieces sit between MFMAs too
+               'gemm_p4_heads.hip': ['-fno-slp-vectorize', '-Rpass-analysis=kernel-resource-usage'],      # the same kernel body: the same flags
                'gemm_up2.hip': ['-Rpass-analysis=kernel-resource-usage'],     # gemm_up2.hip: its report shows the fused x2 + convolution kernel keeps its accumulators in registers (tests read it)
                'aligner.hip': ['-Rpass-analysis=kernel-resource-usage'],      # aligner.hip: its report pins the registers / scratch of every aligner kernel (tests read it)
                'sky.hip': ['-Rpass-analysis=kernel-resource-usage'],          # sky.hip: its report shows the segmentation kernels use no scratch (tests read it)

@@ -454,6 +454,25 @@ void gemm_heads(Ctx& c, const Lin& L, const NormIn& in, int M, int C, int heads,
     const Region r[3] = {r0, r1, r2};
     for (int i = 0; i < 3; ++i) { p.head_kind[i] = r[i].kind; p.head_dst[i] = r[i].dst; }
     p.heads = heads; p.ntok = d.N; p.tok_w = d.tw; p.ldv = d.ldv; p.rope_table = c.m->rope_table;
+    // q | k | v whose q | k prefix the plan puts on the persistent kernel (gemm_p4.hip: its drain rotates, it has no V^T): two launches on the same rows and statistics,
+    // q | k there and V -- weight rows, bias and column sums from row 2 C on -- where a [vt] launch goes. Every element is computed as in the single launch.
+    if (r0.kind == HEAD_ROPE && r1.kind == HEAD_ROPE && r2.kind == HEAD_VT && L.N == 3 * C && L.dt == D3R_F16X3) {
+        GemmParams qk = p;
+        qk.n_store = qk.n_pad = 2 * C; qk.head_kind[2] = 0; qk.head_dst[2] = nullptr;
+        const GemmPlan plan = gemm_plan_for(qk, L.dt);
+        if (plan.cfg == GEMM_CFG_P4) {        // (C % 128 == 0 there)
+            launch(c, L.dt, qk, PRF_GEMM, 2 * C, L.K, false, &plan);
+            GemmParams v = p;
+            v.wgt = reinterpret_cast<const char*>(p.wgt) + (size_t)2 * C * L.K * dt_bytes(L.dt);
+            if (v.bias) v.bias += 2 * C;
+            if (v.ln_colsum) v.ln_colsum += 2 * C;
+            v.n_store = v.n_pad = C; v.n_rows = p.n_rows - 2 * C;
+            v.head_kind[0] = HEAD_VT; v.head_dst[0] = r2.dst;
+            for (int i = 1; i < 3; ++i) { v.head_kind[i] = 0; v.head_dst[i] = nullptr; }
+            launch(c, L.dt, v, PRF_GEMM, C, L.K);
+            return;
+        }
+    }
     launch(c, L.dt, p, PRF_GEMM, L.N, L.K);
 }
 

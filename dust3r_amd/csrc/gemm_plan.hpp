@@ -60,7 +60,12 @@ inline GemmPlan gemm_plan(const GemmParams& p, int dt, const GemmEnv& env, int c
         const long tiles = (long)(p.M / 256) * (p.n_store / 128);
         const long rounds = (tiles + cus - 1) / cus;
         // the last round at least ~half full on average: >= 88 % of the tile slots used
-        if (env.persist == 1 || (tiles >= cus && tiles * 100 >= rounds * cus * 88 && !(p.epi == EPI_F32 && p.K > 1024))) {
+        // Attention projections (EPI_HEADS; eligible: rotated regions only): the q | k launch the engine splits off a q | k | v projection (engine.hip gemm_heads), and only
+        // where it fills its rounds almost exactly (>= 95 % of the slots: the encoder's 49152 x 2048 = 3072 tiles = 12 rounds). The split costs the V launch the rounds it
+        // shared with q | k: the decoder's V alone (N = 768) fills rounds on no kernel, its q | k 90 % -- not split, not measured. One-region launches (the
+        // cross-attention q) stay on the one-tile-per-block kernels as recorded (tests/golden/gemm_plan_table.json).
+        const bool heads_ok = p.epi != EPI_HEADS || (p.n_store == 2 * p.head_c && tiles * 100 >= rounds * cus * 95);
+        if (env.persist == 1 || (tiles >= cus && tiles * 100 >= rounds * cus * 88 && !(p.epi == EPI_F32 && p.K > 1024) && heads_ok)) {
             plan.cfg = GEMM_CFG_P4;
             return plan;
         }

@@ -74,6 +74,7 @@ void gemm_set_trace(unsigned long long* buf, size_t capacity_blocks);
 // gemm_p4.hip: the persistent split-fp16 kernel whose epilogue runs under the next tile's K loop (tile configuration 10 in profiles)
 bool gemm_p4_eligible(const GemmParams& p, int dt);
 hipError_t launch_gemm_p4(const GemmParams& p, hipStream_t s);
+hipError_t launch_gemm_p4_heads(const GemmParams& p, hipStream_t s);      // gemm_p4_heads.hip: its EPI_HEADS launches (every region HEAD_ROPE)
 // gemm_up2.hip: AMODE_CONV_UP2 launches on 16 x 32 pixel tiles (eight waves of 128 (n) x 64 (m), profiled as tile configuration 3)
 hipError_t launch_conv_up2(const GemmParams& p, hipStream_t s);
 }  // namespace d3r

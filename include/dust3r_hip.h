@@ -117,7 +117,10 @@ int d3r_linear_heads(const void* act, const void* wgt, const float* bias, int M,
  * D3R_GEMM_NOWIDE and D3R_GEMM_T128W8 applied -- a pinned configuration that is infeasible for the launch is IGNORED, and this is how a caller sees it.
  * D3R_TILE_128W8: the 128x128 tile on eight waves (split-fp16 launches of fewer than D3R_GEMM_T128W8 = 1100 tiles). Feasible for a heads launch:
  * 0 and 8 (8: split-fp16 only); 1 when head_c % 256 == 0; 2 and 3 for bf16 / fp16 when ntok % 64 == 0 and D3R_GEMM_NOWIDE is not set (only then is V^T
- * transposed in the staging tile; every other V^T route swaps the MFMA operand roles and needs a square tile); never 7, 9, 11. */
+ * transposed in the staging tile; every other V^T route swaps the MFMA operand roles and needs a square tile); never 7, 9, 11.
+ * 10 (the persistent kernel, split-fp16): launches whose regions are all HEAD_ROPE, with head_c % 128 == 0, ntok % 16 == 0, a token grid of at most 64 x 64, whole
+ * 256 x 128 tiles (at least 8), K % 32 == 0 and K >= 576 -- by default only the two-region q | k launch whose tiles fill whole rounds of the compute units (>= 95 % of
+ * the slots; the engine then issues V as a launch of its own), under D3R_GEMM_PERSIST=1 every such launch; never with D3R_GEMM_PERSIST=0, D3R_GEMM_NOWIDE or a pin. */
 #define D3R_TILE_128W8 12
 int d3r_linear_heads_tile_config(int M, int K, int n_regions, int head_c, const int* kinds, int heads, int ntok, int tok_w, int ldv, int max_pos, int dtype);
 
