@@ -168,6 +168,12 @@ def _load():
         'd3r_cloud_icp_sums': (i, [i, fp, fp, i, fp, fp, fp, ip, i, f, f, C.POINTER(C.c_float), vp, vp, vp, vp, vp]),
         'd3r_cloud_cluster_workspace_bytes': (C.c_size_t, [i]),
         'd3r_cloud_cluster': (i, [i, f, i, C.POINTER(C.c_float), f, C.POINTER(C.c_int), ip, ip, ip, ip, vp, ip, C.POINTER(vp), vp, vp, vp]),
+        'd3r_cloud_grid_heads': (i, [i, ip, ip, vp, vp]),
+        'd3r_cloud_spfh': (i, [i, fp, fp, i, ip, vp, vp]),
+        'd3r_cloud_fpfh': (i, [i, i, ip, fp, vp, fp, vp]),
+        'd3r_feature_nearest': (i, [i, fp, i, fp, fp, ip, vp]),
+        'd3r_sim3_ransac_workspace_bytes': (C.c_size_t, [i, i]),
+        'd3r_sim3_ransac': (i, [i, fp, fp, C.c_ulonglong, i, f, C.c_double, i, vp, vp, vp, vp]),
         'd3r_cloud_tracks_workspace_bytes': (C.c_size_t, [i]),
         'd3r_cloud_tracks_count': (i, [i, fp, vp, fp, ip, ip, i, i, fp, vp, f, i, C.c_double, ip, vp, vp, vp]),
         'd3r_cloud_tracks_fill': (i, [i, fp, vp, fp, ip, ip, i, i, fp, vp, f, i, C.c_double, ip, vp, C.c_longlong, i, ip, ip, vp, ip, ip, ip, vp, vp]),

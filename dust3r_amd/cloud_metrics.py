@@ -28,7 +28,14 @@ and reduces them to 18 (point to point) or 36 (point to plane) fp64 sums, and th
     res = cluster_points(points, eps, min_points)           # DBSCAN: labels, sizes, n_neighbors, core: csrc/cloud_cluster.hip, d3r_cloud_cluster
 
 On the same grid, built on the cloud itself with cells of eps: density clustering, defined without the grid and without any visiting
-order; viz.FusedCloud.cluster / keep_clusters and scene.fuse(clusters=..., keep_largest=...) are built of it."""
+order; viz.FusedCloud.cluster / keep_clusters and scene.fuse(clusters=..., keep_largest=...) are built of it.
+
+    res = global_registration(src, dst)                     # a coarse Sim(3) from nothing: csrc/cloud_features.hip
+
+The similarity `register_clouds` starts from, when nobody has one: `grid_subsample` at a cell relative to each cloud's
+own size, FPFH descriptors of the k nearest neighbours (`spfh_counts`, `fpfh_features`), exhaustive mutual matching in 33 dimensions
+(`feature_nearest`, `match_features`) and a Sim(3) RANSAC over the matches (`sim3_ransac`); `register_clouds(..., init='global')` chains
+the two."""
 import collections
 import ctypes as C
 import math
@@ -608,7 +615,7 @@ def icp_sums(moved, ref, d2, idx, metric, gate, centre, ref_normals=None, moved_
 
 @torch.no_grad()
 def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plane', max_iters=30, tol=1e-6, cos_min=None, r0=None, centre=None,
-                    _rebuild_grids=False):
+                    _rebuild_grids=False, global_kw=None, details=None):
     """Sim(3) ICP of the cloud src onto the cloud dst on the GPU: a `Registration` whose similarity S takes src into dst's frame.
     src, dst: (N, 3) arrays, tensors or FusedClouds. max_dist: the pair gate, a float or a coarse-to-fine sequence of floats, each a stage
     of at most max_iters iterations that starts where the last ended. init: the (4, 4) similarity to start from (identity). with_scale=False
@@ -620,13 +627,26 @@ def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plan
     not move), d3r_cloud_icp_sums, ONE read-back of at most 37 numbers, `icp_update` in fp64 on the host, S <- delta S. A stage ends when
     |rmse - rmse_prev| <= tol rmse (the update of that iteration is not applied: rmse and n_pairs are those of the returned S) or at
     max_iters. ValueError when the first iteration has no pair; later, fewer pairs than unknowns or a singular system end the loop with
-    converged=False and a reason."""
+    converged=False and a reason. init='global': the loop starts from `global_registration(src, dst, with_scale=with_scale, **global_kw)`
+    (DESIGN.md, 4.17), so src may be rotated, moved and scaled by anything; ValueError with its reason when it finds no similarity. The
+    `Registration` is the same tuple; the `GlobalRegistration` is put into `details` (a dict, optional) under 'global'."""
     if metric not in METRICS:
         raise ValueError(f"register_clouds: metric is 'point' or 'plane', got {metric!r}")
     stages = [max_dist] if np.ndim(max_dist) == 0 else list(max_dist)
     if not stages or int(max_iters) < 1:
         raise ValueError('register_clouds: max_dist is empty or max_iters < 1')
     stages = [_radius_f32(g, 'max_dist') for g in stages]
+    if isinstance(init, str):
+        if init != 'global':
+            raise ValueError(f"register_clouds: init is a (4, 4) similarity, None or 'global', got {init!r}")
+        found = global_registration(src, dst, **dict(dict(with_scale=with_scale), **(global_kw or {})))
+        if details is not None:
+            details['global'] = found
+        if found.similarity is None:
+            raise ValueError(f'register_clouds: the global registration found no similarity: {found.reason}')
+        init = found.similarity
+    elif global_kw is not None:
+        raise ValueError("register_clouds: global_kw needs init='global'")
     S = np.eye(4) if init is None else np.array(init, np.float64)
     similarity_parts(S)
     _lib.require_device()
@@ -695,3 +715,312 @@ def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plan
                 break
     scale = similarity_parts(S)[2]
     return Registration(S, scale, rmse, n_pairs, n_valid, iterations, converged, reason, history)
+
+
+# ---- global registration: FPFH features and Sim(3) RANSAC --------------------------------------------------------------
+FEATURE_DIM, SPFH_ROW, FEATURE_BINS = 33, 36, 11        # the row of d3r_cloud_fpfh, of d3r_cloud_spfh, the bins of one pair feature
+MAX_HYPOTHESES = 1 << 23                                # D3R_SIM3_MAX_HYPOTHESES
+FEATURE_CELL = 0.1                                      # the default feature cell, in units of `cloud_size`
+FEATURE_KNN_RADIUS = 8.0                                # the descriptor's neighbours lie within this many feature cells
+NORMALS_K = 16                                          # the neighbours of the PCA normals of a cloud that has none
+
+GlobalRegistration = collections.namedtuple('GlobalRegistration', 'similarity scale n_features n_matches n_inliers n_valid best_hypothesis mirrored reason')
+GlobalRegistration.__doc__ = """The result of `global_registration`: similarity (4, 4) float64 [s R | t] that takes src onto dst (None when none was
+found, with the reason), its scale, n_features = (source, destination) feature points, n_matches = the mutual matches RANSAC saw, n_inliers =
+the matches within thr of the returned similarity, n_valid = the hypotheses that passed the edge-ratio test, best_hypothesis = the winner's
+index, mirrored = whether the run with the source descriptors of reversed normals won, reason (None on success)."""
+
+
+@torch.no_grad()
+def grid_subsample(points, cell, to_host=True):
+    """indices (M,) int32: of every occupied cell of the grid of d3r_cloud_grid_build at `cell` (origin = the minimum of the finite points)
+    the LOWEST original index among the cell's finite points, in ascending cell-key order (z, then y, then x). d3r_cloud_grid_heads on
+    the grid's workspace. ValueError when the extent does not fit 21 bits per axis at that cell. Two host synchronisations (the bounds,
+    the count)."""
+    cell = _radius_f32(cell, 'cell')
+    _lib.require_device()
+    device = _device_of(points)
+    P = _points(points, device, 'points')
+    n = len(P)
+    out = torch.empty((0,), dtype=torch.int32, device=device)
+    if n > 0:
+        with torch.cuda.device(device):
+            lo, hi, n_valid = _bounds(P, device)
+            if n_valid > 0:
+                grids = _ReferenceGrids(P, lo, hi, [cell], 1)                # one rung: the grid of that cell, built here
+                _, used_cell, _, work = grids.rungs[0]
+                if used_cell != float(cell):
+                    raise ValueError(f'grid_subsample: cell = {float(cell)!r} is too small for the extent of the cloud')
+                heads = torch.empty((n,), dtype=torch.int32, device=device)
+                count = torch.zeros((1,), dtype=torch.int32, device=device)
+                check(lib.d3r_cloud_grid_heads(n, ptr(heads), ptr(count), ptr(work), current_stream()), 'cloud_grid_heads')
+                out = heads[:int(count.cpu())].clone()
+    return out.cpu().numpy() if to_host else out
+
+
+@torch.no_grad()
+def cloud_size(points):
+    """(size, centroid (3,) float64) of the finite points: size = sqrt(trace of their fp64 covariance), the RMS distance from the centroid.
+    (nan, None) for a cloud without a finite point. One host synchronisation."""
+    P = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32)))
+    V = P[torch.isfinite(P).all(dim=1)].double()
+    if len(V) == 0:
+        return float('nan'), None
+    c = V.mean(dim=0)
+    host = torch.cat([((V - c) ** 2).sum(dim=1).mean().reshape(1), c]).cpu().numpy()
+    return math.sqrt(float(host[0])), host[1:]
+
+
+@torch.no_grad()
+def feature_cloud(cloud, normals=None, cell=None):
+    """(positions (M, 3), normals (M, 3), cell, indices (M,) int32) on the device: the cloud `grid_subsample`d at `cell` (default
+    FEATURE_CELL = 0.1 `cloud_size`: relative to the cloud's own size, which makes what follows independent of its unknown scale) and
+    the normals at those points. Normals: `normals` when given, else the cloud's own (a FusedCloud with normals), both TAKEN AS CONSISTENTLY
+    ORIENTED; else PCA normals of the whole cloud (NORMALS_K = 16 neighbours within 4 cells) turned so that (p - c) . n >= 0 about the
+    feature points' centroid c. That orientation suits object-like scans seen from outside; inconsistently oriented normals defeat the
+    descriptor."""
+    _lib.require_device()
+    device = _device_of(cloud)
+    P = _points(cloud, device, 'cloud')
+    if len(P) == 0:
+        raise ValueError('feature_cloud: the cloud is empty')
+    if cell is None:
+        size, _ = cloud_size(P)
+        if not (math.isfinite(size) and size > 0):
+            raise ValueError(f'feature_cloud: the cloud has no extent (size {size!r}): give cell')
+        cell = FEATURE_CELL * size
+    cell = _radius_f32(cell, 'cell')
+    own = normals if normals is not None else getattr(cloud, 'normals', None)
+    if own is not None:
+        own = _points(own, device, 'normals')
+        if len(own) != len(P):
+            raise ValueError(f'feature_cloud: {len(P)} points, {len(own)} normals')
+    idx = grid_subsample(P, cell, to_host=False)
+    F = P[idx.long()].contiguous()
+    if own is not None:
+        return F, own[idx.long()].contiguous(), float(cell), idx
+    radius = 4.0 * float(cell)
+    _, nbr = k_nearest(P, P, NORMALS_K, radius, exclude_self=True, r0=min(float(cell), radius), to_host=False)
+    N, _ = cloud_normals(P, P, nbr)
+    N = N[idx.long()]
+    c = F.double().mean(dim=0)
+    outward = ((F.double() - c) * N.double()).sum(dim=1) >= 0
+    return F, torch.where(outward[:, None], N, -N).contiguous(), float(cell), idx
+
+
+@torch.no_grad()
+def spfh_counts(points, normals, idx):
+    """counts (N, 36) uint8 of d3r_cloud_spfh (include/dust3r_hip.h has the definition): per point the 3 x 11 histogram of (alpha, phi,
+    theta) over its neighbour rows idx (N, k) -- rows of `k_nearest(points, points, k, ..., exclude_self=True)` -- the pairs counted, two
+    zero bytes. Device tensors, no synchronisation."""
+    _lib.require_device()
+    device = idx.device
+    P, N = _points(points, device, 'points'), _points(normals, device, 'normals')
+    n, k = idx.shape
+    if len(P) != n or len(N) != n:
+        raise ValueError(f'spfh_counts: {len(P)} points, {len(N)} normals, {n} neighbour rows')
+    counts = torch.zeros((n, SPFH_ROW), dtype=torch.uint8, device=device)
+    if n > 0:
+        with torch.cuda.device(device):
+            check(lib.d3r_cloud_spfh(n, ptr(P), ptr(N), k, ptr(idx.contiguous()), ptr(counts), current_stream()), 'cloud_spfh')
+    return counts
+
+
+@torch.no_grad()
+def fpfh_features(d2, idx, counts):
+    """features (N, 33) float32 of d3r_cloud_fpfh: the point's own histogram plus its neighbours', weighted by normalised 1 / d2, each
+    third scaled to sum 100; fp64 in column order. d2, idx (N, k) the rows of `k_nearest`, counts (N, 36) of `spfh_counts`."""
+    _lib.require_device()
+    device = idx.device
+    n, k = idx.shape
+    if d2.shape != idx.shape or counts.shape != (n, SPFH_ROW) or counts.dtype != torch.uint8:
+        raise ValueError(f'fpfh_features: d2 {tuple(d2.shape)}, idx {tuple(idx.shape)}, counts {tuple(counts.shape)} {counts.dtype}')
+    out = torch.zeros((n, FEATURE_DIM), dtype=torch.float32, device=device)
+    if n > 0:
+        with torch.cuda.device(device):
+            check(lib.d3r_cloud_fpfh(n, k, ptr(idx.contiguous()), ptr(d2.contiguous()), ptr(counts.contiguous()), ptr(out), current_stream()), 'cloud_fpfh')
+    return out
+
+
+@torch.no_grad()
+def cloud_features(points, normals, cell, k=MAX_K):
+    """FPFH features (N, 33) float32 of the feature points: `k_nearest` (k neighbours within FEATURE_KNN_RADIUS = 8 cells, exclude_self),
+    `spfh_counts`, `fpfh_features`. Device tensors."""
+    radius = FEATURE_KNN_RADIUS * float(cell)
+    d2, idx = k_nearest(points, points, k, radius, exclude_self=True, r0=min(float(cell) * max(2.0, math.sqrt(k)), radius), to_host=False)
+    return fpfh_features(d2, idx, spfh_counts(points, normals, idx))
+
+
+def mirror_features(features):
+    """the features of the same cloud with every normal negated: a pair's (alpha, phi, theta) becomes (alpha, -phi, -theta), so the phi
+    and theta thirds are read in reverse bin order and the alpha third is unchanged. A tensor or an array (N, 33)."""
+    b = FEATURE_BINS
+    flip = (lambda t: t.flip(1)) if isinstance(features, torch.Tensor) else (lambda t: t[:, ::-1])
+    cat = torch.cat if isinstance(features, torch.Tensor) else np.concatenate
+    return cat([features[:, :b], flip(features[:, b:2 * b]), flip(features[:, 2 * b:])], 1)
+
+
+@torch.no_grad()
+def feature_nearest(fa, fb):
+    """(d2 (Na,) float32, idx (Na,) int32) of every row of fa among the rows of fb, both (N, 33) float32 on the device: the lowest index of
+    minimal fp32 squared distance, summed in column order (d3r_feature_nearest: exhaustive and exact); (+inf, -1) for a row with a
+    non-finite value and when fb has no finite row."""
+    _lib.require_device()
+    device = fa.device
+    for f in (fa, fb):
+        if f.ndim != 2 or f.shape[1] != FEATURE_DIM or f.dtype != torch.float32:
+            raise ValueError(f'feature_nearest: expected (N, {FEATURE_DIM}) float32 features, got {tuple(f.shape)} {f.dtype}')
+    d2 = torch.full((len(fa),), float('inf'), dtype=torch.float32, device=device)
+    idx = torch.full((len(fa),), -1, dtype=torch.int32, device=device)
+    if len(fa) > 0 and len(fb) > 0:
+        with torch.cuda.device(device):
+            check(lib.d3r_feature_nearest(len(fa), ptr(fa.contiguous()), len(fb), ptr(fb.contiguous()), ptr(d2), ptr(idx), current_stream()), 'feature_nearest')
+    return d2, idx
+
+
+@torch.no_grad()
+def match_features(fa, fb, mutual=True):
+    """(ia, ib) int64 device tensors: row ia[m] of fa matches row ib[m] of fb. `feature_nearest` from fa to fb; mutual=True keeps i <-> j
+    only when i is also the nearest of j among fa (a second call the other way), in ascending i."""
+    _, ab = feature_nearest(fa, fb)
+    ia = torch.nonzero(ab >= 0).reshape(-1)
+    ib = ab[ia].long()
+    if mutual and len(ia) > 0:
+        _, ba = feature_nearest(fb, fa)
+        keep = ba[ib].long() == ia
+        ia, ib = ia[keep], ib[keep]
+    return ia, ib
+
+
+def _ransac_args(n_hyp, thr, ratio_min):
+    if isinstance(n_hyp, bool) or not isinstance(n_hyp, (int, np.integer)) or not 1 <= n_hyp <= MAX_HYPOTHESES:
+        raise ValueError(f'n_hyp = {n_hyp!r} must be an int in [1, {MAX_HYPOTHESES}]')
+    with np.errstate(over='ignore'):
+        t = np.float32(thr)
+        ok = t > 0 and np.isfinite(t * t)
+    if not ok:
+        raise ValueError(f'thr = {thr!r} must be a positive float32 with a finite square')
+    if not 0 < float(ratio_min) <= 1:
+        raise ValueError(f'ratio_min = {ratio_min!r} must lie in (0, 1]')
+    return int(n_hyp), float(t), float(ratio_min)
+
+
+@torch.no_grad()
+def sim3_ransac(p, q, n_hyp, thr, ratio_min=0.9, with_scale=True, seed=0):
+    """(best (15,) float64, inliers (n,) uint8) device tensors of d3r_sim3_ransac over the correspondences p[i] <-> q[i] ((n, 3) float32,
+    n >= 3): best = (h or -1, inlier count, valid hypotheses, the 12 entries of S = [s R | t] row-major). Hypothesis h: three
+    correspondences drawn by (seed, h), rejected unless the three edge-length ratios agree within ratio_min, the similarity of the two
+    triangles in fp64; scored in fp32 as `transform_points` then d2 <= thr^2; the largest count wins, then the lowest h. n_hyp is fixed (no
+    adaptive stopping); the same seed gives the same bytes. No synchronisation."""
+    n_hyp, thr, ratio_min = _ransac_args(n_hyp, thr, ratio_min)
+    _lib.require_device()
+    device = _device_of(p, q)
+    P, Q = _points(p, device, 'p'), _points(q, device, 'q')
+    n = len(P)
+    if n < 3 or len(Q) != n:
+        raise ValueError(f'sim3_ransac: {n} and {len(Q)} points; at least 3 correspondences')
+    best = torch.zeros((15,), dtype=torch.float64, device=device)
+    inliers = torch.zeros((n,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        work = _lib.workspace(lib.d3r_sim3_ransac_workspace_bytes(n, n_hyp), device)
+        check(lib.d3r_sim3_ransac(n, ptr(P), ptr(Q), int(seed) & (2 ** 64 - 1), n_hyp, thr, ratio_min, int(bool(with_scale)), ptr(best), ptr(inliers),
+                                  ptr(work), current_stream()), 'sim3_ransac')
+    return best, inliers
+
+
+def similarity_inliers(S, p, q, thr):
+    """(n,) bool on the host: the inlier test of d3r_sim3_ransac for the similarity S (4, 4) over p <-> q (n, 3) float32 arrays: p' by the
+    fp32 row product of `transform_points`, fp32 d2 <= thr^2, both points finite."""
+    M = np.asarray(S, np.float64)[:3, :4].astype(np.float32)
+    p, q = np.asarray(p, np.float32), np.asarray(q, np.float32)
+    with np.errstate(invalid='ignore', over='ignore'):
+        moved = np.stack([((M[r, 0] * p[:, 0] + M[r, 1] * p[:, 1]) + M[r, 2] * p[:, 2]) + M[r, 3] for r in range(3)], axis=1)
+        d = moved - q
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        t = np.float32(thr)
+        return np.isfinite(p).all(axis=1) & np.isfinite(q).all(axis=1) & (d2 <= t * t)
+
+
+def refine_on_inliers(S, p, q, thr, with_scale=True, rounds=3):
+    """(S, inliers (n,) bool): at most `rounds` rounds of Umeyama over the inlier set of S, host fp64 (`icp_update_point` on the 18 sums of
+    the inlier pairs about their destination centroid). A round is kept only when its inlier count does not drop."""
+    S = np.array(S, np.float64)
+    inl = similarity_inliers(S, p, q, thr)
+    p64, q64 = np.asarray(p, np.float64), np.asarray(q, np.float64)
+    for _ in range(rounds):
+        y = q64[inl]
+        c = y.mean(axis=0)
+        a = p64[inl] @ S[:3, :3].T + S[:3, 3] - c
+        y = y - c
+        sums = np.concatenate([[len(a)], a.sum(axis=0), y.sum(axis=0), (a[:, :, None] * y[:, None, :]).sum(axis=0).reshape(9), [(a * a).sum()],
+                               [((a - y) ** 2).sum()]])
+        delta, _, _ = icp_update_point(sums, c, with_scale)
+        if delta is None:
+            break
+        S_new = delta @ S
+        inl_new = similarity_inliers(S_new, p, q, thr)
+        if inl_new.sum() < inl.sum():
+            break
+        same = np.array_equal(inl_new, inl)
+        S, inl = S_new, inl_new
+        if same:
+            break
+    return S, inl
+
+
+@torch.no_grad()
+def global_registration(src, dst, src_normals=None, dst_normals=None, cell=None, k=MAX_K, n_hyp=65536, thr=None, ratio_min=0.9, with_scale=True,
+                        seed=0, try_mirrored=True, to_host=True):
+    """Global (initialisation-free) registration of the cloud src onto the cloud dst on the GPU: a `GlobalRegistration` whose similarity
+    takes src into dst's frame from ANY relative rotation, translation and (with_scale) scale -- the coarse similarity `register_clouds`
+    needs (DESIGN.md, 4.17). src, dst: (N, 3) arrays, tensors or FusedClouds.
+    1. `feature_cloud` of both sides: cell = None takes 0.1 of each cloud's own size, a float is the cell of BOTH clouds (then they
+       must share a scale), a pair is (source cell, destination cell). Normals: src_normals / dst_normals, else the clouds' own, else oriented PCA normals (see `feature_cloud`:
+       that orientation suits object-like scans; inconsistently oriented normals defeat the descriptor).
+    2. `cloud_features` on each: k nearest neighbours, SPFH, FPFH.
+    3. `match_features`: mutual nearest neighbours in the 33-dimensional feature space, exhaustive.
+    4. `sim3_ransac` over the matches, thr defaulting to half the destination's feature cell, n_hyp hypotheses, the given seed.
+       try_mirrored: a second match and RANSAC with `mirror_features` of the source -- the descriptors the source would have with every
+       normal negated -- covers a cloud whose normals point the other way; the higher inlier count wins, ties go to the unmirrored run.
+    5. `refine_on_inliers`: at most three rounds of Umeyama over the inliers, fp64 on the host; the matches are read back once for it.
+    Fewer than 3 matches, or no hypothesis with 3 inliers, gives similarity=None with a reason, not an exception. The result is host
+    data whatever to_host says (the argument exists for symmetry with the other calls of this module)."""
+    n_hyp, _, ratio_min = _ransac_args(n_hyp, 1.0 if thr is None else thr, ratio_min)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f'global_registration: k = {k} outside [1, {MAX_K}]')
+    _lib.require_device()
+    device = _device_of(src, dst)
+    with torch.cuda.device(device):
+        cells = (cell, cell) if cell is None or np.ndim(cell) == 0 else tuple(cell)
+        Ps, Ns, cell_s, _ = feature_cloud(_as_cloud(src, device), src_normals, cells[0])
+        Pd, Nd, cell_d, _ = feature_cloud(_as_cloud(dst, device), dst_normals, cells[1])
+        n_features = (len(Ps), len(Pd))
+        thr = 0.5 * cell_d if thr is None else thr
+        fail = lambda why, n_matches=0, n_valid=0: GlobalRegistration(None, float('nan'), n_features, n_matches, 0, n_valid, -1, False, why)      # noqa: E731
+        Fs, Fd = cloud_features(Ps, Ns, cell_s, k), cloud_features(Pd, Nd, cell_d, k)
+        runs = []
+        for mirrored in ([False, True] if try_mirrored else [False]):
+            ia, ib = match_features(mirror_features(Fs) if mirrored else Fs, Fd)
+            if len(ia) < 3:
+                runs.append((None, None, None, len(ia)))
+                continue
+            p, q = Ps[ia].contiguous(), Pd[ib].contiguous()
+            best, _ = sim3_ransac(p, q, n_hyp, thr, ratio_min, with_scale, seed)
+            runs.append((best.cpu().numpy(), p, q, len(ia)))
+        counts = [-1 if b is None else (int(b[1]) if b[0] >= 0 else 0) for b, _, _, _ in runs]
+        w = int(np.argmax(counts))                                          # the first of equal counts: the unmirrored run
+        best, p, q, n_matches = runs[w]
+        if best is None:
+            return fail(f'{max(r[3] for r in runs)} mutual matches, 3 needed', max(r[3] for r in runs))
+        if best[0] < 0:
+            return fail(f'no hypothesis of {n_hyp} ({int(best[2])} valid) has 3 inliers within {float(thr)!r}', n_matches, int(best[2]))
+        S0 = np.eye(4)
+        S0[:3, :4] = best[3:].reshape(3, 4)
+        S, inl = refine_on_inliers(S0, p.cpu().numpy(), q.cpu().numpy(), thr, with_scale)        # the one read-back of the matches
+    return GlobalRegistration(S, similarity_parts(S)[2], n_features, n_matches, int(inl.sum()), int(best[2]), int(best[0]), bool(w), None)
+
+
+def _as_cloud(cloud, device):
+    """a FusedCloud as it is (its normals and positions are read by name), anything else as device points"""
+    return cloud if hasattr(cloud, 'positions') else _points(cloud, device, 'cloud')

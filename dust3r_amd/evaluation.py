@@ -198,11 +198,15 @@ def main(argv=None):
     """python -m dust3r_amd.evaluation PRED.ply GT.ply --max-dist D [--thresholds T ...]: the dict of cloud_metrics as one JSON line.
     --register [--init FILE] [--rigid] [--metric point|plane] [--register-dist D1 D2 ...]: PRED is first registered onto GT by
     cloud_metrics.register_clouds (stages --register-dist, default 4 D, 2 D, D) and moved; the line gains similarity (4 x 4, row-major
-    lists), registration_rmse and registration_pairs."""
+    lists), registration_rmse and registration_pairs. --global [--feature-cell C] [--ransac-iters H] [--seed S] (with --register, instead of
+    --init): the registration starts from cloud_metrics.global_registration -- FPFH features, exhaustive matching and a Sim(3) RANSAC of H
+    hypotheses, with the PLY files' normals when they have them -- so PRED may be rotated and scaled by anything; the line gains
+    global_similarity, global_inliers and global_matches."""
     args = parse_args(argv)
     from .cloud_metrics import cloud_metrics
     from .export import read_ply
-    clouds = [read_ply(p)['positions'] for p in (args.pred, args.gt)]
+    plys = [read_ply(p) for p in (args.pred, args.gt)]
+    clouds = [p['positions'] for p in plys]
     thresholds = [args.max_dist / 16, args.max_dist / 8, args.max_dist / 4] if args.thresholds is None else args.thresholds
     if not args.register:
         print(json.dumps(cloud_metrics(clouds[0], clouds[1], args.max_dist, thresholds)))
@@ -210,10 +214,19 @@ def main(argv=None):
     from .cloud_metrics import register_clouds, transform_points
     init = None if args.init is None else np.loadtxt(args.init, dtype=np.float64).reshape(4, 4)
     stages = [4 * args.max_dist, 2 * args.max_dist, args.max_dist] if args.register_dist is None else args.register_dist
-    reg = register_clouds(clouds[0], clouds[1], stages, init=init, with_scale=not args.rigid, metric=args.metric)
+    details = {}
+    if args.global_register:
+        init = 'global'
+        global_kw = dict(src_normals=plys[0].get('normals'), dst_normals=plys[1].get('normals'), cell=args.feature_cell, n_hyp=args.ransac_iters,
+                         seed=args.seed)
+    reg = register_clouds(clouds[0], clouds[1], stages, init=init, with_scale=not args.rigid, metric=args.metric,
+                          global_kw=global_kw if args.global_register else None, details=details)
     moved, _ = transform_points(clouds[0], reg.similarity)
     out = cloud_metrics(moved, clouds[1], args.max_dist, thresholds)
     out.update(similarity=reg.similarity.tolist(), registration_rmse=reg.rmse, registration_pairs=reg.n_pairs)
+    if args.global_register:
+        g = details['global']
+        out.update(global_similarity=g.similarity.tolist(), global_inliers=g.n_inliers, global_matches=g.n_matches)
     print(json.dumps(out))
     return 0
 
@@ -231,9 +244,18 @@ def parse_args(argv=None):
     parser.add_argument('--rigid', action='store_true', help='keep the scale of --init (no scale unknown)')
     parser.add_argument('--metric', choices=('point', 'plane'), default='plane', help='the residual of the registration')
     parser.add_argument('--register-dist', type=float, nargs='+', default=None, help='the pair gates of the stages, coarse to fine (default: 4, 2, 1 max-dist)')
+    parser.add_argument('--global', dest='global_register', action='store_true',
+                        help='start the registration from a global one (FPFH features, Sim(3) RANSAC): no --init needed')
+    parser.add_argument('--feature-cell', type=float, default=None, help='the cell of the feature clouds of --global (default: 0.1 of each cloud\'s size)')
+    parser.add_argument('--ransac-iters', type=int, default=65536, help='the hypotheses of the RANSAC of --global')
+    parser.add_argument('--seed', type=int, default=0, help='the seed of the RANSAC of --global')
     args = parser.parse_args(argv)
     if not args.register and (args.init is not None or args.rigid or args.register_dist is not None or args.metric != 'plane'):
         parser.error('--init, --rigid, --metric and --register-dist need --register')
+    if args.global_register and (not args.register or args.init is not None):
+        parser.error('--global needs --register and excludes --init')
+    if not args.global_register and (args.feature_cell is not None or args.ransac_iters != 65536 or args.seed != 0):
+        parser.error('--feature-cell, --ransac-iters and --seed need --global')
     return args
 
 

@@ -343,6 +343,19 @@ class FusedCloud:
                 positions, normals = positions.cpu().numpy(), None if normals is None else normals.cpu().numpy()
         return self._with(positions=positions, normals=normals, voxel_size=self.voxel_size * scale, bounds=bounds, tracks=None)
 
+    @torch.no_grad()
+    def feature_cloud(self, cell=None):
+        """(positions (F, 3), normals (F, 3)) float32: the points a global registration describes (cloud_metrics.feature_cloud, which has
+        the definition): of every occupied cell of a grid of side `cell` the point of lowest index, in cell order. cell: default 0.1 of the
+        cloud's size, sqrt(trace of the fp64 covariance of its finite points) -- relative to the cloud itself, so the same fraction of any
+        rescaled copy. The normals are the cloud's own when it has them (taken as consistently oriented: `estimate_normals(scene=...)`),
+        else PCA normals turned away from the feature points' centroid. Arrays come back where this cloud's are."""
+        from .cloud_metrics import feature_cloud
+        positions, normals, _, _ = feature_cloud(self, cell=cell)
+        if not isinstance(self.positions, torch.Tensor):
+            positions, normals = positions.cpu().numpy(), normals.cpu().numpy()
+        return positions, normals
+
     def distance_to(self, other, max_dist, to_host=True):
         """(d2, idx) of every point of this cloud in `other` (a FusedCloud or (N, 3) points) within max_dist: squared distances (+inf where
         there is none) and rows of `other` (-1); cloud_metrics.nearest_in_cloud on the GPU."""

@@ -650,6 +650,57 @@ int d3r_cloud_cluster(int n, float eps, int min_points, const float* lo, float c
                       int* n_clusters_out, int* n_neighbors_out, uint8_t* core_out, int* evals, void* const* stage_events, void* grid_workspace,
                       void* workspace, void* stream);
 
+/* Global (initialisation-free) registration of two clouds (new; csrc/cloud_features.hip): descriptors, their exhaustive matching and a
+ * Sim(3) RANSAC over the matches (dust3r_amd/cloud_metrics.py, global_registration). Every array DEVICE; validity and the fp32 d2 of points
+ * as in the cloud metrics above; every fp32 and fp64 operation below is rounded on its own (no contraction), in the order written; a dot
+ * product of three terms is (t0 + t1) + t2 and a cross product's component is one difference of two products.
+ * d3r_cloud_grid_heads: after d3r_cloud_grid_build of n_ref points into `workspace`: indices_out [n_ref] int32, of which the first M are
+ *   written = per occupied cell, in ascending order of the cells' keys, the LOWEST original index among the cell's valid points;
+ *   count_out [1] int32 = M. (The grid is sorted stably from index order, so this is the first point of every cell.)
+ * d3r_cloud_spfh: points, normals [n][3] fp32; idx [n][k] rows of d3r_cloud_knn with exclude_self (-1 padded), 1 <= k <= D3R_CLOUD_MAX_K.
+ *   counts_out [n][36] uint8, 4-byte aligned: 3 x 11 bin counts (alpha, phi, theta), the number m of pairs counted, two zero bytes.
+ *   Per neighbour q of p, fp32: d = q - p, dist = sqrt(d . d), dn = d / dist; u = n_p, phi = u . dn; c = dn x u, v = c / sqrt(c . c);
+ *   w = u x v; alpha = v . n_q; theta = atan2f(w . n_q, u . n_q). bin(x; lo, hi) = floorf((x - lo) / (hi - lo) * 11) clamped to [0, 10] (a
+ *   NaN gives 0), over [-1, 1], [-1, 1] and [-pi, pi] (pi the fp32 nearest to it). The pair is SKIPPED when idx is outside [0, n), either
+ *   point is invalid, either normal is non-finite or (0, 0, 0), dist is not > 0 or sqrt(c . c) is not > 0. A point that is itself invalid
+ *   or has such a normal counts no pair. Only atan2f is not an IEEE operation: a sample within its error of a bin edge may land on either side.
+ * d3r_cloud_fpfh: idx, d2 [n][k] the rows of d3r_cloud_knn, counts [n][36] as written above. features_out [n][33] fp32. In fp64, with S(x)_b
+ *   the count of bin b of point x and m_x its pairs-counted byte: neighbour column j CONTRIBUTES when 0 <= idx_j < n, d2_j > 0 and
+ *   m_{q_j} > 0; w_j = 1 / (double)d2_j; W = sum of w_j over the contributing columns in column order, from 0;
+ *     F_b = S(p)_b / m_p (0 when m_p = 0), then for every contributing column in order F_b += (w_j / W) * (S(q_j)_b / m_{q_j});
+ *   per third f of the 33 bins s_f = the sum of its 11 values in bin order; out_b = (float)((F_b * 100) / s_f), 0 when s_f is not > 0.
+ *   The weights are normalised: scaling the cloud (every d2 by a common factor) leaves the feature unchanged up to rounding.
+ * d3r_feature_nearest: a [n_a][33], b [n_b][33] fp32. THE RESULT: for a row of a with 33 finite values, idx_out = the lowest index among
+ *   the all-finite rows of b that minimise d2 = (...((e_0 e_0 + e_1 e_1) + e_2 e_2) ... + e_32 e_32), e_c = a_c - b_c in fp32, and d2_out =
+ *   that minimum (which may be +inf); for any other row of a, and when no row of b is all finite, idx_out = -1 and d2_out = +inf. What an
+ *   fp32 loop over all pairs and the 33 columns gives, bit for bit; the search is exhaustive.
+ * d3r_sim3_ransac: p, q [n_corr][3] fp32 correspondences (p_i <-> q_i), n_corr >= 3, 1 <= n_hyp <= D3R_SIM3_MAX_HYPOTHESES, thr > 0 with a
+ *   finite fp32 square, 0 < ratio_min <= 1, with_scale 0 or 1. HYPOTHESIS h: the first three distinct values among draw(c) =
+ *   ((mix64(mix64(seed ^ 0xD1B54A32D192ED03 (h + 1)) + c) >> 32) n_corr) >> 32, c = 0 .. 63 (the sampler of d3r_pnp_ransac), pick the
+ *   correspondences 0, 1, 2; fewer than three: invalid. In fp64 from the fp32 inputs: the lengths lp_e, lq_e of the edges 0-1, 1-2, 2-0
+ *   on each side (sqrt((x x + y y) + z z)); r_e = lq_e / lp_e. INVALID unless every lp_e > 0, min r >= ratio_min max r, and with
+ *   with_scale = 0 min r >= ratio_min and max r <= 1 / ratio_min. s = ((lq_0 + lq_1) + lq_2) / ((lp_0 + lp_1) + lp_2), or 1 when
+ *   with_scale = 0. Frames on each side: e1 = (x1 - x0) / |x1 - x0|, e3 = e1 x (x2 - x0) normalised, e2 = e3 x e1; invalid when a norm is not
+ *   > 0. R_rc = (Fq_r0 Fp_c0 + Fq_r1 Fp_c1) + Fq_r2 Fp_c2 with F_rk = component r of e_(k+1); A = s R; mean_c = ((x0_c + x1_c) + x2_c) / 3;
+ *   t_r = meanq_r - ((A_r0 meanp_0 + A_r1 meanp_1) + A_r2 meanp_2); S = [A | t], invalid unless its 12 entries are finite and s > 0.
+ *   SCORE: with [A | t] = float32(S), p' = the row product of d3r_cloud_transform, d2(p', q) in fp32; correspondence i is an INLIER when
+ *   p_i and q_i are valid and d2 <= thr thr (fp32 product). THE WINNER: the valid hypothesis with the largest inlier count, among equals
+ *   the lowest h. best_out [15] fp64 = { h, or -1 when no valid hypothesis has at least 3 inliers; its count (0 with -1); the number of
+ *   valid hypotheses; the 12 entries of S row-major (0 with -1) }; inliers_out [n_corr] uint8 = the winner's mask (0 with -1). n_hyp is
+ *   fixed: no adaptive stopping. One thread per hypothesis; a scoring kernel with the rows of 256 hypotheses in LDS that skips invalid
+ *   ones; one workgroup selects. Integer atomic additions of counts only: the same seed gives the same bytes. workspace:
+ *   d3r_sim3_ransac_workspace_bytes(n_corr, n_hyp) bytes (0 for invalid sizes).
+ * No floating-point atomics, no waiting between workgroups, no scratch. D3R_ERR_INVALID on NULL, sizes, k, thr, ratio_min or with_scale out
+ * of range, counts not 4-byte aligned; nothing is launched then. No allocation, no synchronisation. */
+#define D3R_SIM3_MAX_HYPOTHESES (1 << 23)
+int d3r_cloud_grid_heads(int n_ref, int* indices_out, int* count_out, void* workspace, void* stream);
+int d3r_cloud_spfh(int n, const float* points, const float* normals, int k, const int* idx, uint8_t* counts_out, void* stream);
+int d3r_cloud_fpfh(int n, int k, const int* idx, const float* d2, const uint8_t* counts, float* features_out, void* stream);
+int d3r_feature_nearest(int n_a, const float* a, int n_b, const float* b, float* d2_out, int* idx_out, void* stream);
+size_t d3r_sim3_ransac_workspace_bytes(int n_corr, int n_hyp);
+int d3r_sim3_ransac(int n_corr, const float* p, const float* q, unsigned long long seed, int n_hyp, float thr, double ratio_min, int with_scale,
+                    double* best_out, uint8_t* inliers_out, void* workspace, void* stream);
+
 /* 2-D tracks of a cloud in the views of a scene (new; csrc/tracks.hip): which pixel of which view observes each point, by projection.
  * pts [n][row][3], mask [n][row], weight [n][row] or NULL, img_h / img_w [n]: the scene's stacks as for d3r_fuse_bounds (n * row <= 2^31 - 1,
  * 1 <= n <= 65535; what lies behind a view's h w elements is never read; a view whose h w exceeds row is empty). positions [M][3] DEVICE

@@ -1,0 +1,548 @@
+"""Global cloud registration (FPFH features, Sim(3) RANSAC) without a GPU: the numpy restatements that tests/test_cloud_global_gpu.py holds
+csrc/cloud_features.hip and cloud_metrics.global_registration against, pinned here against the truth on a synthetic scene.
+Every restatement follows the definition of its export in include/dust3r_hip.h, operation for operation:
+- `restated_grid_heads`: the fp32 cell key of d3r_cloud_grid_build, the first index of every key by np.unique.
+- `restated_knn`: an fp32 brute force over all pairs, rows sorted by (d2, index).
+- `restated_spfh`: float32 numpy, every operation one rounding; only arctan2 is not an IEEE operation, so the function also FLAGS the rows
+  with a sample within 1e-4 of a bin width of a bin edge (in fp64), where the device's atan2f may legitimately land on the other side.
+- `restated_fpfh`: fp64, the sums in column and bin order.
+- `restated_feature_nearest`: a float32 loop over the 33 columns.
+- `restated_ransac`: the sampler in uint64 arithmetic, the hypotheses in fp64 in the header's operation order, the scores in float32.
+- `restated_global`: the composition, with an Umeyama on the inlier pairs that does not go through the product's sums.
+The scene: a bumpy closed surface without symmetry (14 Gaussian bumps on an ellipsoid; on a smooth ellipsoid the descriptor has nothing to
+hold on to), destination 6000 points, source 5000 fresh samples plus 250 uniform outliers, moved by the inverse of a similarity of 140
+degrees and scale 2.7."""
+import math
+
+import numpy as np
+import pytest
+
+from dust3r_amd.cloud_metrics import (FEATURE_CELL, FEATURE_KNN_RADIUS, GlobalRegistration, global_registration, grid_cell, grid_subsample,
+                                      match_features, mirror_features, refine_on_inliers, sim3_ransac, similarity_inliers)      # what this file is about
+from test_cloud_icp_cpu import STAGES, pca_normals, restated_register, restated_transform, restated_update, similarity, similarity_distance
+
+F32 = np.float32
+BINS, DIM = 11, 33
+PI_F = F32(np.pi)
+EDGE_MARGIN = 1e-4          # of a bin width: a sample closer than this to a bin edge flags its row
+
+
+# ---- restatements ------------------------------------------------------------------------------------------------------------------------
+def _finite_rows(P):
+    return np.isfinite(P).all(axis=1)
+
+
+def restated_grid_heads(P, cell):
+    """indices (M,) int32: the lowest index of every occupied cell, ascending cell key"""
+    P = np.asarray(P, F32)
+    ok = _finite_rows(P)
+    if not ok.any():
+        return np.zeros((0,), np.int32)
+    lo, hi = P[ok].min(axis=0), P[ok].max(axis=0)
+    used, bits = grid_cell(lo, hi, F32(cell))
+    assert used == F32(cell)
+    q = np.floor((P[ok] - lo) / F32(cell))
+    assert q.dtype == F32
+    q = q.astype(np.int64)
+    key = q[:, 0] | (q[:, 1] << bits[0]) | (q[:, 2] << (bits[0] + bits[1]))
+    _, first = np.unique(key, return_index=True)
+    return np.flatnonzero(ok)[first].astype(np.int32)
+
+
+def restated_knn(P, k, max_dist, chunk=512):
+    """(d2 (n, k) float32, idx (n, k) int32) of every point among the others: d3r_cloud_knn with exclude_self, by brute force"""
+    P = np.asarray(P, F32)
+    n = len(P)
+    ok = _finite_rows(P)
+    r2 = F32(max_dist) * F32(max_dist)
+    d2_out, idx_out = np.full((n, k), np.inf, F32), np.full((n, k), -1, np.int32)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for s in range(0, n, chunk):
+            d = P[s:s + chunk, None, :] - P[None, :, :]
+            m = d * d
+            d2 = (m[:, :, 0] + m[:, :, 1]) + m[:, :, 2]
+            assert d2.dtype == F32
+            bad = ~ok[None, :] | ~ok[s:s + chunk, None] | ~(d2 <= r2)
+            bad[np.arange(len(d2)), np.arange(s, s + len(d2))] = True
+            d2 = np.where(bad, F32(np.inf), d2)
+            order = np.argsort(d2, axis=1, kind='stable')[:, :k]              # ties by index
+            got = np.take_along_axis(d2, order, axis=1)
+            cols = min(k, n)
+            d2_out[s:s + chunk, :cols] = got
+            idx_out[s:s + chunk, :cols] = np.where(np.isfinite(got), order, -1)
+    return d2_out, idx_out
+
+
+def _dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def _normal_ok(N):
+    return _finite_rows(N) & (N != 0).any(axis=1)
+
+
+def _bins(x, lo, width):
+    """(bin, distance of the sample from the nearest bin edge in bin widths, fp64)"""
+    t = ((x - lo) / width) * F32(BINS)
+    assert t.dtype == F32
+    b = np.fmin(np.fmax(np.floor(t), F32(0)), F32(BINS - 1)).astype(np.int64)
+    t64 = (x.astype(np.float64) - float(lo)) / float(width) * BINS
+    return b, np.abs(t64 - np.rint(t64))
+
+
+def restated_spfh(P, N, idx):
+    """(counts (n, 36) uint8, flagged (n,) bool): d3r_cloud_spfh in float32, and the rows with a sample within EDGE_MARGIN of a bin edge"""
+    P, N, idx = np.asarray(P, F32), np.asarray(N, F32), np.asarray(idx, np.int64)
+    n, k = idx.shape
+    inside = (idx >= 0) & (idx < n)
+    g = np.where(inside, idx, 0)
+    point_ok = _finite_rows(P) & _normal_ok(N)
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        ok = inside & point_ok[:, None] & point_ok[g]
+        u, nq = np.broadcast_to(N[:, None, :], (n, k, 3)), N[g]
+        d = P[g] - P[:, None, :]
+        dist = np.sqrt(_dot(d, d))
+        ok &= dist > 0
+        dn = d / dist[..., None]
+        phi = _dot(u, dn)
+        c = _cross(dn, u)
+        cn = np.sqrt(_dot(c, c))
+        ok &= cn > 0
+        v = c / cn[..., None]
+        w = _cross(u, v)
+        alpha = _dot(v, nq)
+        theta = np.arctan2(_dot(w, nq), _dot(u, nq))
+        assert all(x.dtype == F32 for x in (alpha, phi, theta))
+        binned = [_bins(alpha, F32(-1), F32(2)), _bins(phi, F32(-1), F32(2)), _bins(theta, -PI_F, PI_F - (-PI_F))]
+    counts = np.zeros((n, 36), np.int64)
+    flagged = np.zeros(n, bool)
+    rows = np.arange(n)
+    for f, (b, edge) in enumerate(binned):
+        flagged |= (ok & (edge < EDGE_MARGIN)).any(axis=1)
+        for j in range(k):
+            r = rows[ok[:, j]]
+            counts[r, f * BINS + b[r, j]] += 1
+    counts[:, DIM] = ok.sum(axis=1)
+    return counts.astype(np.uint8), flagged
+
+
+def restated_fpfh(idx, d2, counts):
+    """features (n, 33) float32: d3r_cloud_fpfh in fp64, column by column"""
+    idx, d2, counts = np.asarray(idx, np.int64), np.asarray(d2, F32), np.asarray(counts, np.uint8)
+    n, k = idx.shape
+    S, m = counts[:, :DIM].astype(np.float64), counts[:, DIM].astype(np.float64)
+    inside = (idx >= 0) & (idx < n)
+    g = np.where(inside, idx, 0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        contributes = inside & (d2 > 0) & (m[g] > 0)
+        w = 1.0 / d2.astype(np.float64)
+        W = np.zeros(n)
+        for j in range(k):
+            W = np.where(contributes[:, j], W + w[:, j], W)
+        acc = np.where(m[:, None] > 0, S / m[:, None], 0.0)
+        for j in range(k):
+            term = (w[:, j] / W)[:, None] * (S[g[:, j]] / m[g[:, j]][:, None])
+            acc = np.where(contributes[:, j, None], acc + term, acc)
+        out = np.zeros((n, DIM), F32)
+        for f in range(3):
+            block = acc[:, f * BINS:(f + 1) * BINS]
+            s = block[:, 0]
+            for b in range(1, BINS):
+                s = s + block[:, b]
+            out[:, f * BINS:(f + 1) * BINS] = np.where(s[:, None] > 0, (block * 100.0) / s[:, None], 0.0).astype(F32)
+    return out
+
+
+def restated_feature_nearest(A, B):
+    """(d2 (na,) float32, idx (na,) int32): a float32 loop over the 33 columns, the lowest index of the minimum"""
+    A, B = np.asarray(A, F32), np.asarray(B, F32)
+    d2_out, idx_out = np.full(len(A), np.inf, F32), np.full(len(A), -1, np.int32)
+    rows = np.flatnonzero(_finite_rows(A))
+    cand = np.flatnonzero(_finite_rows(B))
+    if len(rows) == 0 or len(cand) == 0:
+        return d2_out, idx_out
+    a, b = A[rows], B[cand]
+    with np.errstate(over='ignore'):
+        d2 = None
+        for c in range(DIM):
+            e = a[:, None, c] - b[None, :, c]
+            d2 = e * e if d2 is None else d2 + e * e
+    assert d2.dtype == F32
+    j = np.argmin(d2, axis=1)                                                     # the first of equal minima
+    d2_out[rows], idx_out[rows] = d2[np.arange(len(rows)), j], cand[j]
+    return d2_out, idx_out
+
+
+def restated_match(fa, fb):
+    """(ia, ib): the mutual nearest neighbours, ascending ia"""
+    _, ab = restated_feature_nearest(fa, fb)
+    _, ba = restated_feature_nearest(fb, fa)
+    ia = np.flatnonzero(ab >= 0)
+    ib = ab[ia].astype(np.int64)
+    keep = ba[ib] == ia
+    return ia[keep], ib[keep]
+
+
+U64 = np.uint64
+
+
+def mix64(x):
+    x = x + U64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> U64(30))) * U64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> U64(27))) * U64(0x94D049BB133111EB)
+    return x ^ (x >> U64(31))
+
+
+def draw_index(seed, h, c, n):
+    """visloc_math.hpp's draw_index for an array h of hypotheses"""
+    with np.errstate(over='ignore'):
+        r = mix64(mix64(U64(seed) ^ (U64(0xD1B54A32D192ED03) * (h.astype(U64) + U64(1)))) + U64(c))
+        return (((r >> U64(32)) * U64(n)) >> U64(32)).astype(np.int64)
+
+
+def restated_samples(seed, n_hyp, n):
+    """(H, 3) int64: the first three distinct draws of every hypothesis, -1 where 64 draws did not give them"""
+    h = np.arange(n_hyp)
+    pick = np.full((n_hyp, 3), -1, np.int64)
+    for c in range(64):
+        k = draw_index(seed, h, c, n)
+        i0, i1, i2 = pick[:, 0].copy(), pick[:, 1].copy(), pick[:, 2].copy()
+        fresh = (k != i0) & (k != i1)
+        pick[:, 0] = np.where(i0 < 0, k, i0)
+        pick[:, 1] = np.where((i0 >= 0) & (i1 < 0) & fresh, k, i1)
+        pick[:, 2] = np.where((i1 >= 0) & (i2 < 0) & fresh, k, i2)
+    return pick
+
+
+def _frame(x0, x1, x2):
+    """visloc_math.hpp's triangle_frame for stacks: (F (H, 3, 3) with F[:, r, k] = component r of axis k, ok)"""
+    d3 = lambda a, b: a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2]      # noqa: E731
+    e1 = x1 - x0
+    n1 = np.sqrt(d3(e1, e1))
+    e1 = e1 / n1[:, None]
+    e3 = _cross(e1, x2 - x0)
+    n3 = np.sqrt(d3(e3, e3))
+    e3 = e3 / n3[:, None]
+    e2 = _cross(e3, e1)
+    return np.stack([e1, e2, e3], axis=2), (n1 > 0) & (n3 > 0)
+
+
+def restated_hypotheses(p, q, seed, n_hyp, ratio_min, with_scale):
+    """(S (H, 12) float64, valid (H,) bool) of d3r_sim3_ransac's hypotheses"""
+    p, q = np.asarray(p, F32).astype(np.float64), np.asarray(q, F32).astype(np.float64)
+    pick = restated_samples(seed, n_hyp, len(p))
+    ok = pick[:, 2] >= 0
+    i = np.where(pick < 0, 0, pick)
+    P, Q = [p[i[:, c]] for c in range(3)], [q[i[:, c]] for c in range(3)]
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        def length(a, b):
+            d = b - a
+            return np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        lp = [length(P[0], P[1]), length(P[1], P[2]), length(P[2], P[0])]
+        lq = [length(Q[0], Q[1]), length(Q[1], Q[2]), length(Q[2], Q[0])]
+        ok &= (lp[0] > 0) & (lp[1] > 0) & (lp[2] > 0)
+        r = [lq[e] / lp[e] for e in range(3)]
+        rmin, rmax = np.fmin(r[0], np.fmin(r[1], r[2])), np.fmax(r[0], np.fmax(r[1], r[2]))
+        ok &= rmin >= ratio_min * rmax
+        if not with_scale:
+            ok &= (rmin >= ratio_min) & (rmax <= 1.0 / ratio_min)
+        s = ((lq[0] + lq[1]) + lq[2]) / ((lp[0] + lp[1]) + lp[2]) if with_scale else np.ones(n_hyp)
+        Fp, okp = _frame(*P)
+        Fq, okq = _frame(*Q)
+        ok &= okp & okq
+        mp, mq = ((P[0] + P[1]) + P[2]) / 3.0, ((Q[0] + Q[1]) + Q[2]) / 3.0
+        S = np.zeros((n_hyp, 12))
+        for rr in range(3):
+            for c in range(3):
+                S[:, rr * 4 + c] = s * ((Fq[:, rr, 0] * Fp[:, c, 0] + Fq[:, rr, 1] * Fp[:, c, 1]) + Fq[:, rr, 2] * Fp[:, c, 2])
+            S[:, rr * 4 + 3] = mq[:, rr] - ((S[:, rr * 4] * mp[:, 0] + S[:, rr * 4 + 1] * mp[:, 1]) + S[:, rr * 4 + 2] * mp[:, 2])
+        ok &= (np.abs(S) <= 1e300).all(axis=1) & (s > 0)
+    return np.where(ok[:, None], S, 0.0), ok
+
+
+def restated_d2(M, p, q):
+    """fp32 squared distances of the rows [A | t] = M (12,) float32 applied to p, from q"""
+    d = restated_transform(p, M) - q
+    return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+
+
+def restated_ransac(p, q, seed, n_hyp, thr, ratio_min=0.9, with_scale=True):
+    """dict(h, count, n_valid, S (12,), inliers (n,) bool, margin): d3r_sim3_ransac. margin = how close, relative to thr^2, the winner's
+    nearest correspondence lies to the gate (a count that differed on a device would have to show a row there)"""
+    p, q = np.asarray(p, F32), np.asarray(q, F32)
+    S, valid = restated_hypotheses(p, q, seed, n_hyp, ratio_min, with_scale)
+    live = _finite_rows(p) & _finite_rows(q)
+    thr2 = F32(thr) * F32(thr)
+    counts = np.full(n_hyp, -1, np.int64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for h in np.flatnonzero(valid):
+            counts[h] = (live & (restated_d2(S[h].astype(F32), p, q) <= thr2)).sum()
+        h = int(np.argmax(counts)) if valid.any() else -1                          # the first of equal counts
+        if h < 0 or counts[h] < 3:
+            return dict(h=-1, count=0, n_valid=int(valid.sum()), S=np.zeros(12), inliers=np.zeros(len(p), bool), margin=float('inf'))
+        d2 = restated_d2(S[h].astype(F32), p, q)
+        inliers = live & (d2 <= thr2)
+        margin = float(np.nanmin(np.abs(d2[live].astype(np.float64) - float(thr2)))) / float(thr2)
+    return dict(h=h, count=int(counts[h]), n_valid=int(valid.sum()), S=S[h], inliers=inliers, margin=margin)
+
+
+def restated_size(P):
+    V = np.asarray(P, F32)[_finite_rows(P)].astype(np.float64)
+    return math.sqrt(((V - V.mean(axis=0)) ** 2).sum(axis=1).mean())
+
+
+def restated_feature_cloud(P, normals=None, cell=None):
+    """(positions, normals, cell): the grid heads at cell = 0.1 size and the normals there; without normals, PCA normals (k = 16) of the
+    whole cloud turned away from the feature points' centroid"""
+    P = np.asarray(P, F32)
+    cell = F32(FEATURE_CELL * restated_size(P) if cell is None else cell)
+    idx = restated_grid_heads(P, cell)
+    F = P[idx]
+    if normals is not None:
+        return F, np.asarray(normals, F32)[idx], float(cell)
+    N = pca_normals(P, k=16)[idx]
+    c = F.astype(np.float64).mean(axis=0)
+    outward = ((F.astype(np.float64) - c) * N.astype(np.float64)).sum(axis=1) >= 0
+    return F, np.where(outward[:, None], N, -N), float(cell)
+
+
+def restated_features(F, N, cell, k=32):
+    """(features, d2, idx, counts, flagged) of a feature cloud"""
+    d2, idx = restated_knn(F, k, FEATURE_KNN_RADIUS * cell)
+    counts, flagged = restated_spfh(F, N, idx)
+    return restated_fpfh(idx, d2, counts), d2, idx, counts, flagged
+
+
+def restated_refine(S, p, q, thr, with_scale=True, rounds=3):
+    """at most three rounds of Umeyama over the inliers, a round kept only when the count does not drop"""
+    S = np.array(S, np.float64)
+    thr2 = F32(thr) * F32(thr)
+    count = lambda T: restated_d2(T[:3, :4].astype(F32).reshape(12), p, q) <= thr2      # noqa: E731
+    inl = count(S)
+    for _ in range(rounds):
+        a = p[inl].astype(np.float64) @ S[:3, :3].T + S[:3, 3]
+        A, v = restated_update('point', a, q[inl].astype(np.float64), None, with_scale)
+        D = np.eye(4)
+        D[:3, :3], D[:3, 3] = A, v
+        T = D @ S
+        now = count(T)
+        if now.sum() < inl.sum():
+            break
+        same = np.array_equal(now, inl)
+        S, inl = T, now
+        if same:
+            break
+    return S, inl
+
+
+def restated_global(src, dst, n_hyp=65536, seed=0, ratio_min=0.9, with_scale=True, src_normals=None, dst_normals=None, mirrored=False):
+    """dict(S, n_features, n_matches, ransac, n_inliers, p, q, thr): `global_registration` in numpy (one run, mirrored or not)"""
+    Ps, Ns, cell_s = restated_feature_cloud(src, src_normals)
+    Pd, Nd, cell_d = restated_feature_cloud(dst, dst_normals)
+    fs, fd = restated_features(Ps, Ns, cell_s)[0], restated_features(Pd, Nd, cell_d)[0]
+    ia, ib = restated_match(mirror_features(fs) if mirrored else fs, fd)
+    p, q, thr = Ps[ia], Pd[ib], 0.5 * cell_d
+    best = restated_ransac(p, q, seed, n_hyp, thr, ratio_min, with_scale)
+    S0 = np.eye(4)
+    S0[:3, :4] = best['S'].reshape(3, 4)
+    S, inl = restated_refine(S0, p, q, thr, with_scale)
+    return dict(S=S, n_features=(len(Ps), len(Pd)), n_matches=len(ia), ransac=best, n_inliers=int(inl.sum()), p=p, q=q, thr=thr, ia=ia, ib=ib)
+
+
+# ---- the scene ---------------------------------------------------------------------------------------------------------------------------
+TRUTH = similarity((-2, 1, 0.5), 140.0, 2.7, (3, -5, 1.5))
+KINDS = ('full', 'partial', 'noisy')
+
+
+def _bumps():
+    rng = np.random.default_rng(7)
+    c = rng.standard_normal((14, 3))
+    c /= np.linalg.norm(c, axis=1, keepdims=True)
+    a = rng.uniform(0.15, 0.45, 14) * rng.choice([-1, 1], 14)
+    sigma = rng.uniform(0.15, 0.4, 14)
+    return c, a, sigma
+
+
+def bumpy(rng, n):
+    """(points (n, 3) float64, directions u): u r(u) (1, 0.8, 0.6), r = 1 + sum_j a_j exp(-|u - c_j|^2 / sigma_j^2)"""
+    c, a, sigma = _bumps()
+    u = rng.standard_normal((n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    r = 1 + (a * np.exp(-((u[:, None, :] - c[None]) ** 2).sum(axis=2) / sigma ** 2)).sum(axis=1)
+    return u * r[:, None] * np.array([1.0, 0.8, 0.6]), u
+
+
+_SCENES = {}
+
+
+def scene(kind):
+    """(src, dst) float32 of a case: 'full', 'partial' (the samples with u_x + 0.3 u_y > -0.2, about 70 %) or 'noisy' (0.005 Gaussian noise
+    on the samples); the outliers follow the samples; src is moved by the inverse of TRUTH. One generator, the destination first."""
+    if not _SCENES:
+        rng = np.random.default_rng(20240611)
+        dst = bumpy(rng, 6000)[0].astype(F32)
+        clean, u = bumpy(rng, 5000)
+        outliers = rng.uniform(-1.5, 1.5, (250, 3))
+        noise = rng.normal(0.0, 0.005, (5000, 3))
+        keep = u[:, 0] + 0.3 * u[:, 1] > -0.2
+        inv = np.linalg.inv(TRUTH)
+        for name, pts in (('full', clean), ('partial', clean[keep]), ('noisy', clean + noise)):
+            pts = np.concatenate([pts, outliers])
+            _SCENES[name] = ((pts @ inv[:3, :3].T + inv[:3, 3]).astype(F32), dst)
+    return _SCENES[kind]
+
+
+_GLOBAL, _DST_NORMALS = {}, {}
+
+
+def restated_case(kind):
+    """`restated_global` of a case, computed once and shared with the GPU tests"""
+    if kind not in _GLOBAL:
+        _GLOBAL[kind] = restated_global(*scene(kind))
+    return _GLOBAL[kind]
+
+
+def dst_normals():
+    if not _DST_NORMALS:
+        _DST_NORMALS['n'] = pca_normals(scene('full')[1])
+    return _DST_NORMALS['n']
+
+
+GLOBAL_BAR = (5.0, 0.03)            # degrees, relative scale: inside the 8 degrees / 8 % from which the ICP tests are shown to converge
+# kind -> the bars of restated global + restated ICP (stages 0.3 / 0.1 / 0.03) against the truth: (degrees, relative scale), twice what the
+# committed restatement reaches (0.00287 deg / 2.53e-4, 0.0189 deg / 1.79e-4, 0.0379 deg / 4.25e-4; the test prints them, DESIGN.md 4.17 lists them)
+REFINED_BARS = {'full': (0.0058, 5.1e-4), 'partial': (0.038, 3.6e-4), 'noisy': (0.076, 8.5e-4)}
+
+
+# ---- 1. the restatement against the truth ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('kind', KINDS)
+def test_restated_global_is_near_the_truth(kind):
+    g = restated_case(kind)
+    ang, ds, _ = similarity_distance(g['S'], TRUTH)
+    print(f"{kind}: features {g['n_features']}, matches {g['n_matches']}, valid {g['ransac']['n_valid']}, best {g['ransac']['count']}, "
+          f"refined {g['n_inliers']} inliers, {ang:.3g} deg, scale {ds:.3g}")
+    assert g['ransac']['h'] >= 0
+    assert ang <= GLOBAL_BAR[0] and ds <= GLOBAL_BAR[1]
+
+
+@pytest.mark.parametrize('kind', KINDS)
+def test_restated_icp_converges_from_the_restated_global_result(kind):
+    src, dst = scene(kind)
+    S, history, converged = restated_register(src, dst, dst_normals(), STAGES, init=restated_case(kind)['S'])
+    ang, ds, _ = similarity_distance(S, TRUTH)
+    print(f'{kind}: after ICP {ang:.3g} deg, scale {ds:.3g}, {len(history)} iterations')
+    assert converged
+    assert ang <= REFINED_BARS[kind][0] and ds <= REFINED_BARS[kind][1]
+
+
+# ---- 2. the mirror identity --------------------------------------------------------------------------------------------------------------
+def test_features_of_negated_normals_are_the_bin_reversed_features():
+    F, N, cell = restated_feature_cloud(scene('full')[1])
+    f = restated_features(F, N, cell)[0]
+    g = restated_features(F, -N, cell)[0]
+    assert np.array_equal(g, mirror_features(f))
+    assert not np.array_equal(g, f)
+
+
+def test_restated_samples_are_distinct_and_reproducible():
+    a, b = restated_samples(5, 1000, 7), restated_samples(5, 1000, 7)
+    assert np.array_equal(a, b) and (a >= 0).all() and (a < 7).all()
+    assert (a[:, 0] != a[:, 1]).all() and (a[:, 0] != a[:, 2]).all() and (a[:, 1] != a[:, 2]).all()
+    assert not np.array_equal(a, restated_samples(6, 1000, 7))
+    assert (restated_samples(0, 50, 3) >= 0).all()                               # three correspondences: every draw set is a permutation
+
+
+def test_restated_ransac_recovers_a_planted_similarity():
+    rng = np.random.default_rng(11)
+    p = rng.standard_normal((60, 3)).astype(F32)
+    T = similarity((1, -1, 2), 75.0, 1.7, (0.5, 2.0, -1.0))
+    q = (p.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(F32)
+    q[40:] = rng.uniform(-4, 4, (20, 3)).astype(F32)                             # a third of the correspondences are wrong
+    best = restated_ransac(p, q, 3, 512, 0.01)
+    S = np.eye(4)
+    S[:3, :4] = best['S'].reshape(3, 4)
+    ang, ds, dt = similarity_distance(S, T)
+    assert best['count'] == 40 and best['inliers'][:40].all() and not best['inliers'][40:].any()
+    assert ang < 1e-3 and ds < 1e-5 and dt < 1e-4
+    rigid = restated_ransac(p, q, 3, 512, 0.01, with_scale=False)
+    assert rigid['h'] == -1 and rigid['n_valid'] == 0                            # scale 1.7 is outside [0.9, 1 / 0.9]
+    Sr, inl = refine_on_inliers(S, p, q, 0.01)
+    assert inl.sum() == 40 and np.array_equal(inl, similarity_inliers(Sr, p, q, 0.01))
+    assert similarity_distance(Sr, T)[0] <= ang + 1e-9
+
+
+# ---- 3. arguments ------------------------------------------------------------------------------------------------------------------------
+def test_host_entry_points_check_their_arguments_before_the_device():
+    P = np.zeros((4, 3), F32)
+    for kw in (dict(n_hyp=0), dict(n_hyp=2 ** 23 + 1), dict(n_hyp=1.5), dict(thr=0.0), dict(thr=float('nan')), dict(ratio_min=0.0),
+               dict(ratio_min=1.5), dict(k=0), dict(k=33)):
+        with pytest.raises(ValueError):
+            global_registration(P, P, **kw)
+    for kw in (dict(n_hyp=0), dict(thr=-1.0), dict(thr=1e30), dict(ratio_min=2.0)):
+        with pytest.raises(ValueError):
+            sim3_ransac(P, P, **dict(dict(n_hyp=16, thr=0.1), **kw))
+    with pytest.raises(ValueError):
+        grid_subsample(P, 0.0)
+    assert GlobalRegistration._fields == ('similarity', 'scale', 'n_features', 'n_matches', 'n_inliers', 'n_valid', 'best_hypothesis', 'mirrored', 'reason')
+    f = np.arange(2 * DIM, dtype=F32).reshape(2, DIM)
+    m = mirror_features(f)
+    assert np.array_equal(m[:, :BINS], f[:, :BINS]) and np.array_equal(m[:, BINS:2 * BINS], f[:, BINS:2 * BINS][:, ::-1])
+    assert np.array_equal(mirror_features(m), f)
+    assert match_features.__doc__ and 'mutual' in match_features.__doc__
+
+
+def test_register_clouds_checks_the_global_arguments_before_the_device():
+    from dust3r_amd.cloud_metrics import register_clouds
+    P = np.zeros((4, 3), F32)
+    for kw in (dict(init='local'), dict(global_kw={}), dict(init=np.eye(4), global_kw=dict(seed=1)), dict(init='global', global_kw=dict(n_hyp=0))):
+        with pytest.raises(ValueError):
+            register_clouds(P, P, 1.0, **kw)
+
+
+def test_exports_refuse_bad_arguments_without_a_launch():
+    import ctypes as C
+    from dust3r_amd._lib import EXPORTED, lib
+    assert {'d3r_cloud_grid_heads', 'd3r_cloud_spfh', 'd3r_cloud_fpfh', 'd3r_feature_nearest', 'd3r_sim3_ransac',
+            'd3r_sim3_ransac_workspace_bytes'} <= set(EXPORTED)
+    wb = lib.d3r_sim3_ransac_workspace_bytes
+    assert wb(2, 16) == 0 and wb(3, 0) == 0 and wb(3, 2 ** 23 + 1) == 0 and wb(3, 1) >= 12 * 8 + 12 * 4 + 8
+    assert wb(3, 4096) == wb(100000, 4096) and wb(3, 2 ** 20) >= 2 ** 20 * (12 * 8 + 12 * 4 + 8)
+    one, odd = C.c_void_p(256), C.c_void_p(258)                                       # never dereferenced: every call below is refused first
+    assert lib.d3r_cloud_grid_heads(0, one, one, one, None) == -1
+    for args in ((4, None, one, one), (4, one, None, one), (4, one, one, None)):
+        assert lib.d3r_cloud_grid_heads(*args, None) == -1
+    spfh = lambda **kw: lib.d3r_cloud_spfh(*[dict(dict(n=4, p=one, nrm=one, k=8, idx=one, out=one, stream=None), **kw)[a]      # noqa: E731
+                                             for a in ('n', 'p', 'nrm', 'k', 'idx', 'out', 'stream')])
+    for kw in (dict(n=0), dict(p=None), dict(nrm=None), dict(k=0), dict(k=33), dict(idx=None), dict(out=None), dict(out=odd)):
+        assert spfh(**kw) == -1, kw
+    fpfh = lambda **kw: lib.d3r_cloud_fpfh(*[dict(dict(n=4, k=8, idx=one, d2=one, counts=one, out=one, stream=None), **kw)[a]      # noqa: E731
+                                             for a in ('n', 'k', 'idx', 'd2', 'counts', 'out', 'stream')])
+    for kw in (dict(n=0), dict(k=0), dict(k=33), dict(idx=None), dict(d2=None), dict(counts=None), dict(counts=odd), dict(out=None)):
+        assert fpfh(**kw) == -1, kw
+    near = lambda **kw: lib.d3r_feature_nearest(*[dict(dict(na=4, a=one, nb=4, b=one, d2=one, idx=one, stream=None), **kw)[a]      # noqa: E731
+                                                  for a in ('na', 'a', 'nb', 'b', 'd2', 'idx', 'stream')])
+    for kw in (dict(na=0), dict(nb=0), dict(a=None), dict(b=None), dict(d2=None), dict(idx=None)):
+        assert near(**kw) == -1, kw
+    ransac = lambda **kw: lib.d3r_sim3_ransac(*[dict(dict(n=4, p=one, q=one, seed=0, n_hyp=16, thr=0.1, ratio=0.9, scale=1, best=one, inl=one, work=one,      # noqa: E731
+                                                          stream=None), **kw)[a]
+                                                for a in ('n', 'p', 'q', 'seed', 'n_hyp', 'thr', 'ratio', 'scale', 'best', 'inl', 'work', 'stream')])
+    for kw in (dict(n=2), dict(p=None), dict(q=None), dict(n_hyp=0), dict(n_hyp=2 ** 23 + 1), dict(thr=0.0), dict(thr=float('nan')), dict(thr=1e30),
+               dict(ratio=0.0), dict(ratio=1.01), dict(ratio=float('nan')), dict(scale=2), dict(best=None), dict(inl=None), dict(work=None)):
+        assert ransac(**kw) == -1, kw
+
+
+def test_command_line_arguments():
+    from dust3r_amd.evaluation import parse_args
+    a = parse_args(['p.ply', 'g.ply', '--max-dist', '0.5', '--register'])
+    assert not a.global_register and a.feature_cell is None and a.ransac_iters == 65536 and a.seed == 0
+    a = parse_args(['p.ply', 'g.ply', '--max-dist', '0.5', '--register', '--global', '--feature-cell', '0.2', '--ransac-iters', '4096', '--seed', '7'])
+    assert a.register and a.global_register and a.feature_cell == 0.2 and a.ransac_iters == 4096 and a.seed == 7 and a.init is None
+    for bad in (['--global'], ['--register', '--global', '--init', 'S.txt'], ['--register', '--seed', '3'], ['--register', '--feature-cell', '0.1'],
+                ['--register', '--ransac-iters', '100']):
+        with pytest.raises(SystemExit):
+            parse_args(['p.ply', 'g.ply', '--max-dist', '0.5'] + bad)
