@@ -193,6 +193,7 @@ def _load():
         'd3r_selftest_p3p_host': (i, [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
         'd3r_selftest_p3p_roots_host': (i, [vp, vp, vp, vp]),
         'd3r_selftest_ransac_iters_host': (i, [C.c_double, C.c_double, i, i]),
+        'd3r_selftest_draw_distinct_host': (i, [C.c_ulonglong, i, i, i, ip]),
         'd3r_row_means': (i, [fp, i, i, i, fp, vp]),
         'd3r_similarity_moments_workspace': (C.c_size_t, [i, i]),
         'd3r_similarity_moments': (i, [i, vp, vp, vp, ip, i, vp, vp, vp]),

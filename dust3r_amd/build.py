@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 SOURCES = ['gemm.hip', 'gemm_p4.hip', 'gemm_p4_heads.hip', 'gemm_up2.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'sky.hip', 'visloc.hip', 'mesh.hip', 'fuse.hip', 'cloud_nn.hip', 'cloud_knn.hip', 'cloud_icp.hip', 'cloud_cluster.hip', 'cloud_features.hip', 'tracks.hip', 'gallery.hip', 'render.hip', 'losses.hip', 'views.hip', 'engine.hip', 'capi.hip']
-HEADERS = ['common.hpp', 'reduce.hpp', 'scene_common.hpp', 'kernels.hpp', 'gemm_plan.hpp', 'gemm_p4.hpp', 'gemm_head4.hpp', 'aligner_math.hpp', 'visloc_math.hpp', 'views_math.hpp', 'gallery_math.hpp', 'fuse_grid.hpp', 'cloud_grid.hpp', os.path.join('..', '..', 'include', 'dust3r_hip.h')]
+HEADERS = ['common.hpp', 'reduce.hpp', 'scene_common.hpp', 'kernels.hpp', 'gemm_plan.hpp', 'gemm_p4.hpp', 'gemm_head4.hpp', 'aligner_math.hpp', 'visloc_math.hpp', 'ransac.hpp', 'views_math.hpp', 'gallery_math.hpp', 'fuse_grid.hpp', 'cloud_grid.hpp', os.path.join('..', '..', 'include', 'dust3r_hip.h')]
 LIB = os.path.join(CSRC, 'libdust3r_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-inline-asm']
 # attention.hip: no SLP vectorisation -- its scalar-VALU softmax slices (attention_x3_kernel<..., SC = true>) must stay v_fma_f32 / v_add_f32

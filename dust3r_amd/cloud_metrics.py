@@ -67,18 +67,24 @@ def _radius_f32(x, what):
     return v
 
 
+def _voxel_of(cloud):
+    """the voxel size of a cloud if it has a usable one (a FusedCloud's, finite and positive), else None"""
+    voxel = getattr(cloud, 'voxel_size', None)
+    return voxel if voxel is not None and math.isfinite(voxel) and voxel > 0 else None
+
+
 def default_r0(ref, max_dist):
     """the first radius of the ladder: twice the reference cloud's voxel size when it is a FusedCloud with one, else max_dist / 16"""
-    voxel = getattr(ref, 'voxel_size', None)
-    return 2.0 * voxel if voxel is not None and math.isfinite(voxel) and voxel > 0 else float(max_dist) / 16
+    voxel = _voxel_of(ref)
+    return 2.0 * voxel if voxel is not None else float(max_dist) / 16
 
 
 def default_knn_r0(ref, k, max_dist):
     """the first radius of the ladder of `k_nearest`: for a FusedCloud with a voxel size v, v max(2, sqrt(k)) -- a surface sampled at
     spacing v holds about pi r^2 / v^2 points within r, so r = v sqrt(k) expects pi k of them (measured on the 12.6 M-point cloud of
     tools/cloud_normals_speed.py at k = 16: 0.4 % of the rows are full at 2 v, 86 % at 4 v); else max_dist / 16"""
-    voxel = getattr(ref, 'voxel_size', None)
-    return voxel * max(2.0, math.sqrt(k)) if voxel is not None and math.isfinite(voxel) and voxel > 0 else float(max_dist) / 16
+    voxel = _voxel_of(ref)
+    return voxel * max(2.0, math.sqrt(k)) if voxel is not None else float(max_dist) / 16
 
 
 def _device_of(*clouds):
@@ -178,6 +184,15 @@ class _ReferenceGrids:
             else:
                 check(lib.d3r_cloud_knn(len(self.R), len(Q), ptr(Q), self.k, r, self.lo_c, cell, bits_c, int(self.exclude_self), int(j > 0), *out),
                       'cloud_knn')
+
+
+def _single_grid(P, cell):
+    """(grids, used_cell, bits_c, work): ONE grid of the device cloud P, built here at `cell` (`grid_cell`); None without a finite point. One host sync."""
+    lo, hi, n_valid = _bounds(P, P.device)
+    if n_valid == 0:
+        return None
+    grids = _ReferenceGrids(P, lo, hi, [cell], 1)
+    return (grids,) + grids.rungs[0][1:]
 
 
 def _ladder_search(Q, R, radii, k, to_host, **how):
@@ -357,13 +372,12 @@ def cluster_points(points, eps, min_points=10, to_host=True, evals=None, stage_e
     sizes = torch.zeros((0,), dtype=torch.int32, device=device)
     if n > 0:
         with torch.cuda.device(device):
-            lo, hi, n_valid = _bounds(P, device)
-            if n_valid > 0:
+            single = _single_grid(P, eps)
+            if single is not None:
+                grids, cell, bits_c, grid = single
                 own_bytes = int(lib.d3r_cloud_cluster_workspace_bytes(n))
                 if own_bytes == 0:
                     raise ValueError(f'a cloud of {n} points is too large')
-                grids = _ReferenceGrids(P, lo, hi, [eps], 1)                 # one rung: the grid of cell eps, built here
-                _, cell, bits_c, grid = grids.rungs[0]
                 work = _lib.workspace(own_bytes, device)
                 all_sizes = torch.empty((n,), dtype=torch.int32, device=device)
                 n_clusters = torch.zeros((1,), dtype=torch.int32, device=device)
@@ -575,19 +589,25 @@ def _normals_of(cloud, device):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _pca_normals(P, k, radius, r0):
+    """PCA normals (N, 3) of the device cloud P, which has none: `cloud_normals` over its k nearest within radius, the ladder from r0"""
+    _, nbr = k_nearest(P, P, k, radius, exclude_self=True, r0=min(r0, radius), to_host=False)
+    return cloud_normals(P, P, nbr)[0]
+
+
 @torch.no_grad()
-def transform_points(points, S, normals=None):
+def transform_points(points, S, normals=None, out=None, normals_out=None):
     """points (N, 3) moved by the similarity S, and normals rotated by its rotation, on the device (d3r_cloud_transform): fp32, row r =
-    ((A_r0 x + A_r1 y) + A_r2 z) + t_r with [A | t] = float32(S). Device tensors; (moved, rotated normals or None)."""
+    ((A_r0 x + A_r1 y) + A_r2 z) + t_r with [A | t] = float32(S). Device tensors; (moved, rotated normals or None): out / normals_out when given."""
     M, R, _ = similarity_parts(S)
     _lib.require_device()
     device = _device_of(points)
     P = _points(points, device, 'points')
-    out = torch.empty_like(P)
+    out = torch.empty_like(P) if out is None else out
     N_in = None if normals is None else _points(normals, device, 'normals')
     if N_in is not None and len(N_in) != len(P):
         raise ValueError(f'transform_points: {len(P)} points, {len(N_in)} normals')
-    N_out = None if N_in is None else torch.empty_like(N_in)
+    N_out = None if N_in is None else torch.empty_like(N_in) if normals_out is None else normals_out
     if len(P) > 0:
         with torch.cuda.device(device):
             check(lib.d3r_cloud_transform(len(P), ptr(P), (C.c_float * 12)(*M.tolist()), ptr(out), ptr(N_in), (C.c_float * 9)(*R.tolist()), ptr(N_out),
@@ -596,17 +616,18 @@ def transform_points(points, S, normals=None):
 
 
 @torch.no_grad()
-def icp_sums(moved, ref, d2, idx, metric, gate, centre, ref_normals=None, moved_normals=None, cos_min=None, want_used=False):
-    """d3r_cloud_icp_sums on device tensors: (count (1,) int64, sums (18 or 36,) float64, used (N,) uint8 or None), no synchronisation"""
+def icp_sums(moved, ref, d2, idx, metric, gate, centre, ref_normals=None, moved_normals=None, cos_min=None, want_used=False, out=None):
+    """d3r_cloud_icp_sums on device tensors: (count (1,) int64, sums (18 or 36,) float64, used (N,) uint8 or None), no synchronisation.
+    out: (count, sums, workspace of d3r_cloud_icp_sums_workspace_bytes(N)) to use instead of allocating them."""
     _lib.require_device()
     device = moved.device
     n = len(moved)
-    count = torch.zeros((1,), dtype=torch.int64, device=device)
-    sums = torch.zeros((ICP_PLANE_SUMS if METRICS[metric] else ICP_POINT_SUMS,), dtype=torch.float64, device=device)
+    count, sums, work = out or (torch.zeros((1,), dtype=torch.int64, device=device),
+                                torch.zeros((ICP_PLANE_SUMS if METRICS[metric] else ICP_POINT_SUMS,), dtype=torch.float64, device=device), None)
     used = torch.zeros((n,), dtype=torch.uint8, device=device) if want_used else None
     if n > 0 and len(ref) > 0:
         with torch.cuda.device(device):
-            work = _lib.workspace(lib.d3r_cloud_icp_sums_workspace_bytes(n), device)
+            work = _lib.workspace(lib.d3r_cloud_icp_sums_workspace_bytes(n), device) if work is None else work
             check(lib.d3r_cloud_icp_sums(n, ptr(moved), ptr(moved_normals), len(ref), ptr(ref), ptr(ref_normals), ptr(d2), ptr(idx), METRICS[metric],
                                          float(gate), 0.0 if cos_min is None else float(cos_min), (C.c_float * 3)(*[float(c) for c in centre]),
                                          ptr(count), ptr(sums), ptr(used), ptr(work), current_stream()), 'cloud_icp_sums')
@@ -665,10 +686,9 @@ def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plan
         if n_ref_valid == 0:
             raise ValueError('register_clouds: dst has no finite point')
         if metric == 'plane' and dst_normals is None:
-            voxel = getattr(dst, 'voxel_size', None)
-            radius = 8.0 * voxel if voxel is not None and math.isfinite(voxel) and voxel > 0 else float(max(stages))
-            _, nbr = k_nearest(Q, Q, 16, radius, exclude_self=True, r0=min(default_knn_r0(dst, 16, radius), radius), to_host=False)
-            dst_normals, _ = cloud_normals(Q, Q, nbr)
+            voxel = _voxel_of(dst)
+            radius = 8.0 * voxel if voxel is not None else float(max(stages))
+            dst_normals = _pca_normals(Q, 16, radius, default_knn_r0(dst, 16, radius))
         n_valid = int(torch.isfinite(P).all(dim=1).sum())
         c = (0.5 * (lo.astype(np.float64) + hi.astype(np.float64))).astype(np.float32) if centre is None else np.asarray(centre, np.float32).reshape(3)
         if not np.isfinite(c).all():
@@ -680,19 +700,14 @@ def register_clouds(src, dst, max_dist, init=None, with_scale=True, metric='plan
         count = torch.zeros((1,), dtype=torch.int64, device=device)
         sums = torch.zeros((ICP_PLANE_SUMS if METRICS[metric] else ICP_POINT_SUMS,), dtype=torch.float64, device=device)
         work = _lib.workspace(lib.d3r_cloud_icp_sums_workspace_bytes(n), device)
-        centre_c = (C.c_float * 3)(*c.tolist())
         for stage, gate in enumerate(stages):
             first = default_r0(dst, gate) if r0 is None else r0
             grids = _ReferenceGrids(Q, lo, hi, ladder_radii(min(float(_radius_f32(first, 'r0')), float(gate)), gate), n, rebuild=_rebuild_grids)
             prev, converged = None, False
             for it in range(int(max_iters)):
-                M, R, _ = similarity_parts(S)
-                check(lib.d3r_cloud_transform(n, ptr(P), (C.c_float * 12)(*M.tolist()), ptr(moved), ptr(src_normals), (C.c_float * 9)(*R.tolist()),
-                                              ptr(moved_normals), current_stream()), 'cloud_transform')
+                transform_points(P, S, src_normals, out=moved, normals_out=moved_normals)
                 grids.search(moved, d2, idx)
-                check(lib.d3r_cloud_icp_sums(n, ptr(moved), ptr(moved_normals), len(Q), ptr(Q), ptr(dst_normals), ptr(d2), ptr(idx), METRICS[metric],
-                                             float(gate), 0.0 if cos_min is None else float(cos_min), centre_c, ptr(count), ptr(sums), None, ptr(work),
-                                             current_stream()), 'cloud_icp_sums')
+                icp_sums(moved, Q, d2, idx, metric, gate, c, dst_normals, moved_normals, cos_min, out=(count, sums, work))
                 host = torch.cat([count.double(), sums]).cpu().numpy()          # the iteration's one read-back (the count is exact in fp64)
                 pairs = int(host[0])
                 if pairs == 0 and not history:
@@ -745,10 +760,9 @@ def grid_subsample(points, cell, to_host=True):
     out = torch.empty((0,), dtype=torch.int32, device=device)
     if n > 0:
         with torch.cuda.device(device):
-            lo, hi, n_valid = _bounds(P, device)
-            if n_valid > 0:
-                grids = _ReferenceGrids(P, lo, hi, [cell], 1)                # one rung: the grid of that cell, built here
-                _, used_cell, _, work = grids.rungs[0]
+            single = _single_grid(P, cell)
+            if single is not None:
+                _, used_cell, _, work = single
                 if used_cell != float(cell):
                     raise ValueError(f'grid_subsample: cell = {float(cell)!r} is too small for the extent of the cloud')
                 heads = torch.empty((n,), dtype=torch.int32, device=device)
@@ -800,9 +814,7 @@ def feature_cloud(cloud, normals=None, cell=None):
     if own is not None:
         return F, own[idx.long()].contiguous(), float(cell), idx
     radius = 4.0 * float(cell)
-    _, nbr = k_nearest(P, P, NORMALS_K, radius, exclude_self=True, r0=min(float(cell), radius), to_host=False)
-    N, _ = cloud_normals(P, P, nbr)
-    N = N[idx.long()]
+    N = _pca_normals(P, NORMALS_K, radius, float(cell))[idx.long()]
     c = F.double().mean(dim=0)
     outward = ((F.double() - c) * N.double()).sum(dim=1) >= 0
     return F, torch.where(outward[:, None], N, -N).contiguous(), float(cell), idx

@@ -5,19 +5,20 @@
 //   d3r_cloud_spfh         cloud_spfh_kernel          per point the 3 x 11 histogram of its pair features (alpha, phi, theta), one thread per point
 //   d3r_cloud_fpfh         cloud_fpfh_kernel          per point the distance-weighted sum of its neighbours' histograms, fp64, one thread per point
 //   d3r_feature_nearest    feature_nearest_kernel     exhaustive nearest row of b for every row of a in 33 dimensions: THE HOT KERNEL
-//   d3r_sim3_ransac        sim3_hyp_kernel            one thread per hypothesis: counter-based sample of 3 correspondences, fp64 similarity
-//                          sim3_score_kernel          grid (correspondence chunk, round of RND hypotheses): rows in LDS, ballots and popcounts
+//   d3r_sim3_ransac        sim3_hyp_kernel            one thread per hypothesis: counter-based sample of 3 correspondences (ransac.hpp), fp64 similarity
+//                          sim3_score_kernel          grid (correspondence chunk, round of RND hypotheses): ransac.hpp's round scorer
 //                          sim3_select_kernel         one workgroup: the largest count, then the lowest hypothesis
 //                          sim3_mask_kernel           the winner's inlier mask
 // No floating-point atomics, no kernel waits on another workgroup, no scratch. The only atomics are integer additions of inlier counts
 // (sim3_score_kernel), whose result does not depend on their order: the same bytes on every run. Built without contraction: every
-// product and sum below is one IEEE rounding, which is what the numpy restatements compute.
+// product and sum below is one IEEE rounding, which is what the numpy restatements compute; the fp32 3-vector arithmetic is fuse_grid.hpp's.
 #include "../../include/dust3r_hip.h"
 #include "common.hpp"
 #include "scene_common.hpp"
 #include "fuse_grid.hpp"
 #include "cloud_grid.hpp"
-#include "visloc_math.hpp"
+#include "ransac.hpp"
+#include "visloc_math.hpp"      // triangle_frame: the Sim(3) hypothesis is the motion between the frames of its two sampled triangles
 
 namespace d3r {
 namespace cloud {
@@ -39,11 +40,6 @@ __global__ __launch_bounds__(QT) void cloud_grid_heads_kernel(const float4* __re
 
 // ---- 2. SPFH ----------------------------------------------------------------------------------------------------------------------------
 constexpr int BINS = 11, FEAT = 3 * BINS, SPFH_ROW = 36;                  // 33 counts, the pairs counted, two zero bytes
-
-D3R_DEV float dot3f(float ax, float ay, float az, float bx, float by, float bz) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
-}
-D3R_DEV bool normal_ok(float x, float y, float z) { return finite_f(x) && finite_f(y) && finite_f(z) && (x != 0.f || y != 0.f || z != 0.f); }
 
 // floorf((x - lo) / width 11) clamped to [0, 10]; a NaN lands in bin 0
 D3R_DEV int bin11(float x, float lo, float width) {
@@ -69,7 +65,7 @@ __global__ __launch_bounds__(QT) void cloud_spfh_kernel(int n, const float* __re
         const float* p = pts + 3 * (size_t)i;
         const float* u = normals + 3 * (size_t)i;
         const float px = p[0], py = p[1], pz = p[2], ux = u[0], uy = u[1], uz = u[2];
-        const bool own = finite_f(px) && finite_f(py) && finite_f(pz) && normal_ok(ux, uy, uz);
+        const bool own = finite3(px, py, pz) && normal_ok(ux, uy, uz);
         Hist11 h[3];
         uint32_t m = 0;
         for (int j = 0; j < k; ++j) {
@@ -78,23 +74,23 @@ __global__ __launch_bounds__(QT) void cloud_spfh_kernel(int n, const float* __re
             const float* q = pts + 3 * (size_t)g;
             const float* nq = normals + 3 * (size_t)g;
             const float qx = q[0], qy = q[1], qz = q[2], nx = nq[0], ny = nq[1], nz = nq[2];
-            if (!(finite_f(qx) && finite_f(qy) && finite_f(qz) && normal_ok(nx, ny, nz))) continue;
+            if (!(finite3(qx, qy, qz) && normal_ok(nx, ny, nz))) continue;
             const float dx = __fsub_rn(qx, px), dy = __fsub_rn(qy, py), dz = __fsub_rn(qz, pz);
-            const float dist = __fsqrt_rn(dot3f(dx, dy, dz, dx, dy, dz));
+            const float dist = __fsqrt_rn(dist2(dx, dy, dz));
             if (!(dist > 0.f)) continue;
             const float ex = __fdiv_rn(dx, dist), ey = __fdiv_rn(dy, dist), ez = __fdiv_rn(dz, dist);      // dn
-            const float phi = dot3f(ux, uy, uz, ex, ey, ez);
+            const float phi = row3(ux, uy, uz, ex, ey, ez);
             // v = dn x u, normalised
             float vx = __fsub_rn(__fmul_rn(ey, uz), __fmul_rn(ez, uy)), vy = __fsub_rn(__fmul_rn(ez, ux), __fmul_rn(ex, uz)),
                   vz = __fsub_rn(__fmul_rn(ex, uy), __fmul_rn(ey, ux));
-            const float vn = __fsqrt_rn(dot3f(vx, vy, vz, vx, vy, vz));
+            const float vn = __fsqrt_rn(dist2(vx, vy, vz));
             if (!(vn > 0.f)) continue;
             vx = __fdiv_rn(vx, vn); vy = __fdiv_rn(vy, vn); vz = __fdiv_rn(vz, vn);
             // w = u x v
             const float wx = __fsub_rn(__fmul_rn(uy, vz), __fmul_rn(uz, vy)), wy = __fsub_rn(__fmul_rn(uz, vx), __fmul_rn(ux, vz)),
                         wz = __fsub_rn(__fmul_rn(ux, vy), __fmul_rn(uy, vx));
-            const float alpha = dot3f(vx, vy, vz, nx, ny, nz);
-            const float theta = atan2f(dot3f(wx, wy, wz, nx, ny, nz), dot3f(ux, uy, uz, nx, ny, nz));
+            const float alpha = row3(vx, vy, vz, nx, ny, nz);
+            const float theta = atan2f(row3(wx, wy, wz, nx, ny, nz), row3(ux, uy, uz, nx, ny, nz));
             h[0].add(bin11(alpha, -1.f, 2.f));
             h[1].add(bin11(phi, -1.f, 2.f));
             h[2].add(bin11(theta, -PI_F, __fsub_rn(PI_F, -PI_F)));
@@ -302,13 +298,8 @@ __global__ __launch_bounds__(RND) void sim3_hyp_kernel(const Sim3Args a, const S
     const int h = blockIdx.x * RND + threadIdx.x;
     if (h >= a.n_hyp) return;
     w.counts[h] = 0;
-    int i0 = -1, i1 = -1, i2 = -1;
-    for (int c = 0; c < 64 && i2 < 0; ++c) {
-        const int k = vl::draw_index(a.seed, h, c, a.n);
-        if (k == i0 || k == i1) continue;
-        if (i0 < 0) i0 = k; else if (i1 < 0) i1 = k; else i2 = k;
-    }
-    bool ok = i2 >= 0;
+    int i[3];
+    bool ok = ransac::draw_distinct(a.seed, h, a.n, i);
     double S[12];
 #pragma unroll
     for (int c = 0; c < 12; ++c) S[c] = 0.0;
@@ -316,8 +307,8 @@ __global__ __launch_bounds__(RND) void sim3_hyp_kernel(const Sim3Args a, const S
         double P[3][3], Q[3][3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            P[0][c] = (double)a.p[(size_t)i0 * 3 + c]; P[1][c] = (double)a.p[(size_t)i1 * 3 + c]; P[2][c] = (double)a.p[(size_t)i2 * 3 + c];
-            Q[0][c] = (double)a.q[(size_t)i0 * 3 + c]; Q[1][c] = (double)a.q[(size_t)i1 * 3 + c]; Q[2][c] = (double)a.q[(size_t)i2 * 3 + c];
+            P[0][c] = (double)a.p[(size_t)i[0] * 3 + c]; P[1][c] = (double)a.p[(size_t)i[1] * 3 + c]; P[2][c] = (double)a.p[(size_t)i[2] * 3 + c];
+            Q[0][c] = (double)a.q[(size_t)i[0] * 3 + c]; Q[1][c] = (double)a.q[(size_t)i[1] * 3 + c]; Q[2][c] = (double)a.q[(size_t)i[2] * 3 + c];
         }
         // the edges 0-1, 1-2, 2-0
         const double lp[3] = {len3(P[0], P[1]), len3(P[1], P[2]), len3(P[2], P[0])}, lq[3] = {len3(Q[0], Q[1]), len3(Q[1], Q[2]), len3(Q[2], Q[0])};
@@ -358,34 +349,19 @@ __global__ __launch_bounds__(RND) void sim3_hyp_kernel(const Sim3Args a, const S
 
 // p' = float32(S) p by the row product of d3r_cloud_transform, d2 to q as in the cloud metrics
 D3R_DEV bool sim3_inlier(const float* m, float px, float py, float pz, float qx, float qy, float qz, float thr2) {
-    const float x = __fadd_rn(dot3f(m[0], m[1], m[2], px, py, pz), m[3]);
-    const float y = __fadd_rn(dot3f(m[4], m[5], m[6], px, py, pz), m[7]);
-    const float z = __fadd_rn(dot3f(m[8], m[9], m[10], px, py, pz), m[11]);
-    const float dx = __fsub_rn(x, qx), dy = __fsub_rn(y, qy), dz = __fsub_rn(z, qz);
-    return dot3f(dx, dy, dz, dx, dy, dz) <= thr2;                        // false for a NaN
-}
-
-D3R_DEV bool pair_finite(const float* p, const float* q) {
-    return finite_f(p[0]) && finite_f(p[1]) && finite_f(p[2]) && finite_f(q[0]) && finite_f(q[1]) && finite_f(q[2]);
+    const float x = affine_row(m, px, py, pz), y = affine_row(m + 4, px, py, pz), z = affine_row(m + 8, px, py, pz);
+    return dist2(__fsub_rn(x, qx), __fsub_rn(y, qy), __fsub_rn(z, qz)) <= thr2;          // false for a NaN
 }
 
 __global__ __launch_bounds__(SPT) void sim3_score_kernel(const Sim3Args a, const Sim3Ws w) {
-    __shared__ float rows[RND][12];
-    __shared__ int valid[RND];
-    __shared__ int cnt[RND];
     __shared__ int any_valid;
-    const int h0 = blockIdx.y * RND, p0 = blockIdx.x * SCHUNK;
+    const int h0 = blockIdx.y * RND, p0 = blockIdx.x * SCHUNK, n_slots = min(RND, a.n_hyp - h0);
     if (threadIdx.x == 0) any_valid = 0;
     __syncthreads();
-    for (int t = threadIdx.x; t < RND; t += SPT) {
-        const int v = h0 + t < a.n_hyp ? w.valid[h0 + t] : 0;
-        valid[t] = v;
-        cnt[t] = 0;
-        if (v) any_valid = 1;                                             // every writer stores the same value
-    }
+    for (int t = threadIdx.x; t < n_slots; t += SPT)
+        if (w.valid[h0 + t]) any_valid = 1;                               // every writer stores the same value
     __syncthreads();
     if (!any_valid) return;
-    for (int t = threadIdx.x; t < RND * 12; t += SPT) rows[t / 12][t % 12] = h0 + t / 12 < a.n_hyp ? w.rows[(size_t)h0 * 12 + t] : 0.f;
     float px[SPL], py[SPL], pz[SPL], qx[SPL], qy[SPL], qz[SPL];
     bool live[SPL];
 #pragma unroll
@@ -394,21 +370,13 @@ __global__ __launch_bounds__(SPT) void sim3_score_kernel(const Sim3Args a, const
         const int j = i < a.n ? i : 0;
         const float* p = a.p + (size_t)j * 3;
         const float* q = a.q + (size_t)j * 3;
-        live[k] = i < a.n && pair_finite(p, q);
+        live[k] = i < a.n && finite3(p) && finite3(q);
         px[k] = p[0]; py[k] = p[1]; pz[k] = p[2];
         qx[k] = q[0]; qy[k] = q[1]; qz[k] = q[2];
     }
-    __syncthreads();
-    for (int h = 0; h < RND; ++h) {
-        if (!valid[h]) continue;                                          // the same for every lane
-        int c = 0;
-#pragma unroll
-        for (int k = 0; k < SPL; ++k) c += __popcll(__ballot(live[k] && sim3_inlier(rows[h], px[k], py[k], pz[k], qx[k], qy[k], qz[k], a.thr2)));
-        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&cnt[h], c);
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < RND; t += SPT)
-        if (cnt[t]) atomicAdd(&w.counts[h0 + t], cnt[t]);
+    ransac::score_round<SPT, SPL, RND>(w.rows + (size_t)h0 * 12, w.valid + h0, n_slots, w.counts + h0, [&](const float* row, int k) {
+        return live[k] && sim3_inlier(row, px[k], py[k], pz[k], qx[k], qy[k], qz[k], a.thr2);
+    });
 }
 
 // (count, lowest h) as one key: the larger key wins
@@ -459,7 +427,7 @@ __global__ __launch_bounds__(QT) void sim3_mask_kernel(const Sim3Args a, const S
     for (long long i = (long long)blockIdx.x * QT + threadIdx.x; i < a.n; i += (long long)gridDim.x * QT) {
         const float* p = a.p + (size_t)i * 3;
         const float* q = a.q + (size_t)i * 3;
-        inliers_out[i] = found && pair_finite(p, q) && sim3_inlier(m, p[0], p[1], p[2], q[0], q[1], q[2], a.thr2);
+        inliers_out[i] = found && finite3(p) && finite3(q) && sim3_inlier(m, p[0], p[1], p[2], q[0], q[1], q[2], a.thr2);
     }
 }
 

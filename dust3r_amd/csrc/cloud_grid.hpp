@@ -126,7 +126,7 @@ D3R_DEV int cloud_walk(const GridWalk& a, int M, float ax, float ay, float az, F
             for (int i = s; i < e; ++i) {
                 const float4 v = a.pts4[i];
                 const float dx = __fsub_rn(ax, v.x), dy = __fsub_rn(ay, v.y), dz = __fsub_rn(az, v.z);
-                f(i, __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)), v);
+                f(i, dist2(dx, dy, dz), v);
             }
             evals += e - s;
         }

@@ -31,11 +31,6 @@ struct TransformArgs {
     float* normals_out;
 };
 
-// ((a0 x + a1 y) + a2 z), every operation its own rounding
-D3R_DEV float row3(float a0, float a1, float a2, float x, float y, float z) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(a0, x), __fmul_rn(a1, y)), __fmul_rn(a2, z));
-}
-
 // out may be pts and normals_out may be normals_in: a thread reads its row before it writes it
 __global__ __launch_bounds__(QT) void cloud_transform_kernel(const TransformArgs a) {
     for (long long i = (long long)blockIdx.x * QT + threadIdx.x; i < a.n; i += (long long)gridDim.x * QT) {
@@ -43,13 +38,13 @@ __global__ __launch_bounds__(QT) void cloud_transform_kernel(const TransformArgs
         const float x = p[0], y = p[1], z = p[2];
         float* o = a.out + 3 * (size_t)i;
 #pragma unroll
-        for (int r = 0; r < 3; ++r) o[r] = __fadd_rn(row3(a.m[4 * r], a.m[4 * r + 1], a.m[4 * r + 2], x, y, z), a.m[4 * r + 3]);
+        for (int r = 0; r < 3; ++r) o[r] = affine_row(a.m + 4 * r, x, y, z);
         if (a.normals_in) {
             const float* q = a.normals_in + 3 * (size_t)i;
             const float nx = q[0], ny = q[1], nz = q[2];
             float* m = a.normals_out + 3 * (size_t)i;
 #pragma unroll
-            for (int r = 0; r < 3; ++r) m[r] = row3(a.r[3 * r], a.r[3 * r + 1], a.r[3 * r + 2], nx, ny, nz);
+            for (int r = 0; r < 3; ++r) m[r] = row3(a.r + 3 * r, nx, ny, nz);
         }
     }
 }
@@ -80,21 +75,21 @@ __global__ __launch_bounds__(QT) void cloud_icp_sums_kernel(const IcpArgs a, dou
         bool used = g >= 0 && g < a.n_ref && a.d2[i] <= a.gate2;
         const float* p = a.moved + 3 * (size_t)i;
         const float px = p[0], py = p[1], pz = p[2];
-        used = used && finite_f(px) && finite_f(py) && finite_f(pz);
+        used = used && finite3(px, py, pz);
         float qx = 0.f, qy = 0.f, qz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
         if (used) {
             const float* q = a.ref + 3 * (size_t)g;
             qx = q[0]; qy = q[1]; qz = q[2];
-            used = finite_f(qx) && finite_f(qy) && finite_f(qz);
+            used = finite3(qx, qy, qz);
         }
         if (used && (METRIC == 1 || a.moved_normals)) {
             const float* nr = a.ref_normals + 3 * (size_t)g;
             nx = nr[0]; ny = nr[1]; nz = nr[2];
-            if (METRIC == 1) used = finite_f(nx) && finite_f(ny) && finite_f(nz) && (nx != 0.f || ny != 0.f || nz != 0.f);
+            if (METRIC == 1) used = normal_ok(nx, ny, nz);
         }
         if (used && a.moved_normals) {
             const float* m = a.moved_normals + 3 * (size_t)i;
-            used = row3(m[0], m[1], m[2], nx, ny, nz) >= a.cos_min;           // a NaN cosine fails
+            used = row3(m, nx, ny, nz) >= a.cos_min;           // a NaN cosine fails
         }
         if (a.used_out) a.used_out[i] = used;
         if (!used) continue;

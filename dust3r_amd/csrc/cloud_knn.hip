@@ -222,12 +222,6 @@ struct OrientArgs {
     const int *Hs, *Ws;
 };
 
-// row r of a 3 x 4 / 3 x 3 product as clean_pointcloud_kernel writes it, left to right, every operation rounded on its own
-D3R_DEV float row4(const float* M, float x, float y, float z) {
-    return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(M[0], x), __fmul_rn(M[1], y)), __fmul_rn(M[2], z)), M[3]);
-}
-D3R_DEV float row3(const float* M, float x, float y, float z) { return __fadd_rn(__fadd_rn(__fmul_rn(M[0], x), __fmul_rn(M[1], y)), __fmul_rn(M[2], z)); }
-
 __global__ __launch_bounds__(QT) void cloud_orient_kernel(const OrientArgs a) {
     for (long long q = (long long)blockIdx.x * QT + threadIdx.x; q < a.n; q += (long long)gridDim.x * QT) {
         const float* X = a.points + 3 * (size_t)q;
@@ -243,7 +237,8 @@ __global__ __launch_bounds__(QT) void cloud_orient_kernel(const OrientArgs a) {
             const double cosine = len > 0.0 ? (nx * dx + ny * dy + nz * dz) / len : 0.0;      // a point at the centre has no direction: no vote
             s_all += cosine;
             const float* M = a.w2c + 16 * v;
-            const float px = row4(M, x, y, z), py = row4(M + 4, x, y, z), pz = row4(M + 8, x, y, z);
+            // rows of the 3 x 4 / 3 x 3 products as clean_pointcloud_kernel writes them, left to right (fuse_grid.hpp)
+            const float px = affine_row(M, x, y, z), py = affine_row(M + 4, x, y, z), pz = affine_row(M + 8, x, y, z);
             if (!(pz > 0.f)) continue;
             const float* Kv = a.K + 9 * v;
             const float ku = row3(Kv, px, py, pz), kv = row3(Kv + 3, px, py, pz), kw = row3(Kv + 6, px, py, pz);

@@ -65,8 +65,7 @@ __global__ __launch_bounds__(QT) void cloud_stats_kernel(const StatArgs a, doubl
     for (long long q = (long long)blockIdx.x * QT + threadIdx.x; q < a.n; q += (long long)gridDim.x * QT) {
         bool valid = true;
         if (a.query) {
-            const float* p = a.query + 3 * (size_t)q;
-            valid = finite_f(p[0]) && finite_f(p[1]) && finite_f(p[2]);
+            valid = finite3(a.query + 3 * (size_t)q);
         }
         si[0] += valid;
         if (a.idx[q] < 0) continue;

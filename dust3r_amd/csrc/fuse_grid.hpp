@@ -32,11 +32,24 @@ constexpr int MAX_BLOCKS = 2048;        // grid cap of the tile kernels (grid-st
 
 D3R_DEV bool finite_f(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7F800000u) != 0x7F800000u; }
 
+// ---- the fp32 3-vector arithmetic of the cloud kernels, each operation rounded on its own whatever the including file's flags: a point has
+// three finite coordinates, a usable normal is finite and not zero
+D3R_DEV bool finite3(float x, float y, float z) { return finite_f(x) && finite_f(y) && finite_f(z); }
+D3R_DEV bool finite3(const float* p) { return finite_f(p[0]) && finite_f(p[1]) && finite_f(p[2]); }      // reads p[1], p[2] only as far as needed
+D3R_DEV bool normal_ok(float x, float y, float z) { return finite3(x, y, z) && (x != 0.f || y != 0.f || z != 0.f); }
+// ((a0 x + a1 y) + a2 z); a row [a0 a1 a2 t] of an affine map adds t last
+D3R_DEV float row3(float a0, float a1, float a2, float x, float y, float z) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(a0, x), __fmul_rn(a1, y)), __fmul_rn(a2, z));
+}
+D3R_DEV float row3(const float* a, float x, float y, float z) { return row3(a[0], a[1], a[2], x, y, z); }
+D3R_DEV float affine_row(const float* m, float x, float y, float z) { return __fadd_rn(row3(m, x, y, z), m[3]); }
+// the squared length (dx dx + dy dy) + dz dz of a difference
+D3R_DEV float dist2(float dx, float dy, float dz) { return row3(dx, dy, dz, dx, dy, dz); }
+
 // mask == nullptr: every element passes it (a flat cloud)
 D3R_DEV bool valid_at(const float* pts, const uint8_t* mask, const float* weight, size_t g) {
     if (mask && !mask[g]) return false;
-    const float* p = pts + 3 * g;
-    if (!(finite_f(p[0]) && finite_f(p[1]) && finite_f(p[2]))) return false;
+    if (!finite3(pts + 3 * g)) return false;
     if (!weight) return true;
     const float w = weight[g];
     return finite_f(w) && w > 0.f;

@@ -7,6 +7,8 @@
 //           0, 1, ..., NT / 64 - 1 in ascending order, starting from wave 0's value.
 // `op` is the caller's: op(a, b) for a wave, op(a, b, k) with the column k for a workgroup (the bounds take a minimum in columns 0-2 and a
 // maximum in 3-5). NaN behaviour is therefore the op's, nothing here adds any. Header-only and D3R_DEV: each object keeps its own copies.
+// Defined once in the same way, next to what they serve: the fp32 3-vector arithmetic and the finite / usable-normal tests of the cloud
+// kernels (fuse_grid.hpp), the sampler and the round scorer of the two RANSACs (ransac.hpp).
 #pragma once
 #include <algorithm>
 #include "common.hpp"
@@ -77,13 +79,13 @@ template <class T> D3R_DEV T wave_scan_inclusive(T v, int lane) {
     return v;
 }
 
-// ---- host: a workspace carved into 256-byte aligned arrays, in the order of the calls. A null base gives null pointers and the same bytes,
-// which is how every *_workspace_bytes export sizes what its call carves.
+// ---- a workspace carved into 256-byte aligned arrays, in the order of the calls. A null base gives null pointers and the same bytes,
+// which is how every *_workspace_bytes export sizes what its call carves. Host code, and the kernels of visloc.hip that carve their job's record.
 struct Carver {
     char* base;
     size_t bytes = 0;
-    explicit Carver(void* b) : base((char*)b) {}
-    template <class T> T* take(size_t count) {
+    __host__ __device__ explicit Carver(void* b) : base((char*)b) {}
+    template <class T> __host__ __device__ T* take(size_t count) {
         T* r = base ? (T*)(base + bytes) : nullptr;
         bytes += align256(count * sizeof(T));
         return r;

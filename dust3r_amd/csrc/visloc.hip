@@ -16,11 +16,11 @@
 // d3r_pnp_ransac: PnP-RANSAC with full intrinsics for many jobs (queries) in one call, no host synchronisation inside:
 //   pnp_init_kernel        per-job state (iteration budget, best support)
 //   per round of RND hypotheses:
-//     pnp_hyp_kernel       one lane per hypothesis: counter-based sample (seed, hypothesis) -> 4 distinct points, fp64 P3P on the
-//                          first three, the root that best reprojects the fourth; written as fp32 rows pre-scaled by fx / fy
-//     pnp_score_kernel     grid (point chunk, job): the round's hypotheses in LDS, 4 points per lane; a point is an inlier when it
-//                          is in front of the camera and ex^2 + ey^2 <= thr^2 z^2 (the squared pixel error against the squared
-//                          threshold, multiplied through by z^2). Wave counts come from ballots; integer atomics, order-free.
+//     pnp_hyp_kernel       one lane per hypothesis: counter-based sample (seed, hypothesis) -> 4 distinct points (ransac.hpp), fp64 P3P
+//                          on the first three, the root that best reprojects the fourth; written as fp32 rows pre-scaled by fx / fy
+//     pnp_score_kernel     grid (point chunk, job): ransac.hpp's round scorer (hypotheses in LDS, 4 points per lane, ballots, integer atomics);
+//                          a point is an inlier when it is in front of the camera and ex^2 + ey^2 <= thr^2 z^2 (the squared pixel error
+//                          against the squared threshold, multiplied through by z^2).
 //     pnp_select_kernel    the round's best hypothesis (largest support, then lowest index) replaces the job's best when its support
 //                          is strictly larger and updates the budget (RANSACUpdateNumIters); the job is done once the rounds so far
 //                          cover the budget. The budget is checked between rounds, so every job scores at least one full round.
@@ -34,6 +34,7 @@
 #include "../../include/dust3r_hip.h"
 #include "common.hpp"
 #include "reduce.hpp"
+#include "ransac.hpp"
 #include "visloc_math.hpp"
 
 namespace d3r {
@@ -46,15 +47,14 @@ constexpr int QPL = 4;          // queries per lane
 constexpr int QTILE = QT * QPL; // queries per workgroup
 constexpr int RTILE = 1024;     // other-side points per LDS tile
 
-__host__ __device__ inline size_t match_pair_bytes(int max_pixels) {
-    return 2 * ((size_t)max_pixels * (sizeof(float4) + 2 * sizeof(int))) + 16;
-}
-
 // per pair, inside the workspace (stride = max_pixels): pts[2] float4, then per side pix, nn int32, then count[2]. Addressed by
 // arithmetic on `side` (a per-workgroup value): an array of pointers indexed by it would go to scratch.
+__host__ __device__ inline size_t pix_offset(int max_pixels, int side) { return 2 * (size_t)max_pixels * sizeof(float4) + (size_t)(2 * side) * max_pixels * sizeof(int); }
+// a pair's record ends 16 bytes behind the start of its last field, count[2] (where the pix of a third side would start)
+__host__ __device__ inline size_t match_pair_bytes(int max_pixels) { return pix_offset(max_pixels, 2) + 16; }
 D3R_DEV char* match_base(void* workspace, int pair, int max_pixels) { return (char*)workspace + (size_t)pair * match_pair_bytes(max_pixels); }
 D3R_DEV float4* ws_pts(char* base, int max_pixels, int side) { return (float4*)base + (size_t)side * max_pixels; }
-D3R_DEV int* ws_pix(char* base, int max_pixels, int side) { return (int*)(base + 2 * (size_t)max_pixels * sizeof(float4)) + (size_t)(2 * side) * max_pixels; }
+D3R_DEV int* ws_pix(char* base, int max_pixels, int side) { return (int*)(base + pix_offset(max_pixels, side)); }
 D3R_DEV int* ws_nn(char* base, int max_pixels, int side) { return ws_pix(base, max_pixels, side) + max_pixels; }
 D3R_DEV int* ws_count(char* base, int max_pixels) { return ws_pix(base, max_pixels, 2); }
 
@@ -187,31 +187,27 @@ struct PnpWs {
     int* hyp_valid;             // [RND]
     int* counts;                // [RND]
     double* partial;            // [chunks][NSUM]
+    size_t bytes;
 };
 
 __host__ __device__ inline int pnp_chunks(int max_points) { return (max_points + CHUNK - 1) / CHUNK; }
-__host__ __device__ inline size_t pnp_job_bytes(int max_points) {
-    size_t b = (sizeof(PnpState) + 255) / 256 * 256;
-    b += (size_t)RND * 12 * sizeof(double) + (size_t)RND * 12 * sizeof(float) + 2 * (size_t)RND * sizeof(int);
-    b += (size_t)pnp_chunks(max_points) * NSUM * sizeof(double);
-    return (b + 255) / 256 * 256;
+
+// one job's record carved at base; a null base gives its size (every array is a multiple of 256 bytes, the state is padded to one)
+__host__ __device__ inline PnpWs pnp_job(void* base, int max_points) {
+    PnpWs w;
+    Carver c(base);
+    w.st = c.take<PnpState>(1);
+    w.hyp_pose = c.take<double>((size_t)RND * 12);
+    w.hyp_rows = c.take<float>((size_t)RND * 12);
+    w.hyp_valid = c.take<int>(RND);
+    w.counts = c.take<int>(RND);
+    w.partial = c.take<double>((size_t)pnp_chunks(max_points) * NSUM);
+    w.bytes = c.bytes;
+    return w;
 }
 
 D3R_DEV PnpWs pnp_ws(void* workspace, int job, int max_points) {
-    char* base = (char*)workspace + (size_t)job * pnp_job_bytes(max_points);
-    PnpWs w;
-    w.st = (PnpState*)base;
-    base += (sizeof(PnpState) + 255) / 256 * 256;
-    w.hyp_pose = (double*)base;
-    base += (size_t)RND * 12 * sizeof(double);
-    w.hyp_rows = (float*)base;
-    base += (size_t)RND * 12 * sizeof(float);
-    w.hyp_valid = (int*)base;
-    base += (size_t)RND * sizeof(int);
-    w.counts = (int*)base;
-    base += (size_t)RND * sizeof(int);
-    w.partial = (double*)base;
-    return w;
+    return pnp_job((char*)workspace + (size_t)job * pnp_job(nullptr, max_points).bytes, max_points);
 }
 
 // fp32 rows {fx R0, fx t0, fy R1, fy t1, R2, t2} of a world -> camera pose: x = rows0 . (X, 1), y = rows1 . (X, 1), z = rows2 . (X, 1)
@@ -257,8 +253,8 @@ __global__ __launch_bounds__(RND) void pnp_hyp_kernel(const d3r_pnp_ransac_job* 
     w.counts[hl] = 0;
     int valid = 0;
     if (h < niters) {
-        int idx[4];
-        if (draw_sample(J.seed, h, J.n, idx)) {
+        int idx[MODEL_POINTS];
+        if (ransac::draw_distinct(J.seed, h, J.n, idx)) {
             double uv[4][2], X[4][3], pose[12];
             for (int i = 0; i < 4; ++i) {
                 uv[i][0] = J.pts2d[(size_t)idx[i] * 2];
@@ -280,16 +276,11 @@ __global__ __launch_bounds__(RND) void pnp_hyp_kernel(const d3r_pnp_ransac_job* 
 }
 
 __global__ __launch_bounds__(PT) void pnp_score_kernel(const d3r_pnp_ransac_job* __restrict__ jobs, int max_points, void* workspace) {
-    __shared__ float rows[RND][12];
-    __shared__ int valid[RND];
-    __shared__ int cnt[RND];
     const int j = blockIdx.y;
     const PnpWs w = pnp_ws(workspace, j, max_points);
     const d3r_pnp_ransac_job J = jobs[j];
     const int p0 = blockIdx.x * CHUNK;
     if (w.st->done || p0 >= J.n) return;
-    for (int t = threadIdx.x; t < RND * 12; t += PT) rows[t / 12][t % 12] = w.hyp_rows[t];
-    for (int t = threadIdx.x; t < RND; t += PT) { valid[t] = w.hyp_valid[t]; cnt[t] = 0; }
     float X[PPL], Y[PPL], Z[PPL], a[PPL], b[PPL];
     bool live[PPL];
 #pragma unroll
@@ -302,17 +293,8 @@ __global__ __launch_bounds__(PT) void pnp_score_kernel(const d3r_pnp_ransac_job*
         b[k] = J.pts2d[(size_t)q * 2 + 1] - J.cy;
     }
     const float thr2 = J.thr * J.thr;
-    __syncthreads();
-    for (int h = 0; h < RND; ++h) {
-        if (!valid[h]) continue;
-        int c = 0;
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) c += __popcll(__ballot(live[k] && is_inlier(rows[h], X[k], Y[k], Z[k], a[k], b[k], thr2)));
-        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&cnt[h], c);
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < RND; t += PT)
-        if (cnt[t]) atomicAdd(&w.counts[t], cnt[t]);
+    ransac::score_round<PT, PPL, RND>(w.hyp_rows, w.hyp_valid, RND, w.counts,
+                                      [&](const float* row, int k) { return live[k] && is_inlier(row, X[k], Y[k], Z[k], a[k], b[k], thr2); });
 }
 
 __global__ __launch_bounds__(64) void pnp_select_kernel(const d3r_pnp_ransac_job* __restrict__ jobs, int max_points, void* workspace, int round) {
@@ -547,7 +529,7 @@ extern "C" int d3r_match_pairs(int n_pairs, const d3r_match_job* jobs, int max_p
 
 extern "C" size_t d3r_pnp_ransac_workspace(int n_jobs, int max_points) {
     if (n_jobs <= 0 || max_points <= 0) return 0;
-    return (size_t)n_jobs * pnp_job_bytes(max_points);
+    return (size_t)n_jobs * pnp_job(nullptr, max_points).bytes;
 }
 
 extern "C" int d3r_pnp_ransac(int n_jobs, const d3r_pnp_ransac_job* jobs, const d3r_pnp_ransac_params* params, void* workspace,
@@ -599,4 +581,11 @@ extern "C" int d3r_selftest_p3p_roots_host(const double* f, const double* X, dou
 
 extern "C" int d3r_selftest_ransac_iters_host(double confidence, double ep, int model_points, int max_iters) {
     return ransac_update_num_iters(confidence, ep, model_points, max_iters);
+}
+
+// host-only: ransac.hpp's first k distinct draws of hypothesis h (k = 3 or 4) into idx_out[k]; 1 when 64 draws gave them, -1 for another k
+extern "C" int d3r_selftest_draw_distinct_host(unsigned long long seed, int h, int n, int k, int* idx_out) {
+    if (k == 3) return d3r::ransac::draw_distinct(seed, h, n, *(int(*)[3])idx_out) ? 1 : 0;
+    if (k == 4) return d3r::ransac::draw_distinct(seed, h, n, *(int(*)[4])idx_out) ? 1 : 0;
+    return -1;
 }

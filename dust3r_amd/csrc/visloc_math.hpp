@@ -1,6 +1,7 @@
-// dust3r_amd -- host/device math of the visual-localization kernels (csrc/visloc.hip): the counter-based sampler, the real roots of
-// polynomials up to degree 4, the P3P minimal solver and OpenCV's RANSAC stopping rule. Everything is fp64 and written once for both
-// sides, so the CPU test-suite checks the solver through d3r_selftest_p3p_host before any kernel runs.
+// dust3r_amd -- host/device math of the visual-localization kernels (csrc/visloc.hip): the real roots of polynomials up to degree 4, the
+// P3P minimal solver with its triangle frame (which the Sim(3) hypotheses of cloud_features.hip use too) and OpenCV's RANSAC stopping
+// rule. Everything is fp64 and written once for both sides, so the CPU test-suite checks the solver through d3r_selftest_p3p_host before
+// any kernel runs. The sampler is ransac.hpp's.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -13,33 +14,6 @@
 
 namespace d3r {
 namespace vl {
-
-// splitmix64 finaliser: a bijective 64-bit mix, the counter-based generator's only state is its argument
-D3R_HD uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// the c-th draw of hypothesis h of a job keyed by `seed`: uniform in [0, n) (multiply-high, bias < n / 2^32)
-D3R_HD int draw_index(uint64_t seed, int h, int c, int n) {
-    const uint64_t r = mix64(mix64(seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(h + 1))) + (uint64_t)c);
-    return (int)(((r >> 32) * (uint64_t)n) >> 32);
-}
-
-// four distinct indices in [0, n), n >= 4; false if 64 draws did not give them (never at the sizes RANSAC meets). Written with
-// constant array indices only, so that nothing lands in scratch on the GPU.
-D3R_HD bool draw_sample(uint64_t seed, int h, int n, int idx[4]) {
-    int i0 = -1, i1 = -1, i2 = -1, i3 = -1;
-    for (int c = 0; c < 64 && i3 < 0; ++c) {
-        const int k = draw_index(seed, h, c, n);
-        if (k == i0 || k == i1 || k == i2) continue;
-        if (i0 < 0) i0 = k; else if (i1 < 0) i1 = k; else if (i2 < 0) i2 = k; else i3 = k;
-    }
-    idx[0] = i0; idx[1] = i1; idx[2] = i2; idx[3] = i3;
-    return i3 >= 0;
-}
 
 // ---- real roots of polynomials up to degree 4, in increasing order -------------------------------------------------------------
 // Coefficients c[0..4] ascending, zero above the degree. Degree 2 in closed form; degrees 3 and 4 bracket one root in each

@@ -878,10 +878,13 @@ int d3r_pnp_ransac(int n_jobs, const d3r_pnp_ransac_job* jobs, const d3r_pnp_ran
 /* Host-only self tests of the shared visloc math (no GPU touched; all pointers HOST). d3r_selftest_p3p_host: P3P on 3 of 4 pixel /
  * world correspondences, the 4th picking the root; pose_out [12] world -> camera; returns 1 when a pose was found.
  * d3r_selftest_p3p_roots_host: every P3P solution for 3 unit bearings f [3][3] and world points X [3][3] (R_out [4][9], t_out [4][3]);
- * returns their number. d3r_selftest_ransac_iters_host: the stopping rule. */
+ * returns their number. d3r_selftest_ransac_iters_host: the stopping rule. d3r_selftest_draw_distinct_host: the sample of hypothesis h
+ * that d3r_pnp_ransac (k = 4) and d3r_sim3_ransac (k = 3) draw among n points, into idx_out [k]; returns 1 when 64 draws gave k distinct
+ * indices, 0 when not (idx_out then ends in -1), -1 for another k. */
 int d3r_selftest_p3p_host(const double* uv, const double* X, double fx, double fy, double cx, double cy, double* pose_out);
 int d3r_selftest_p3p_roots_host(const double* f, const double* X, double* R_out, double* t_out);
 int d3r_selftest_ransac_iters_host(double confidence, double ep, int model_points, int max_iters);
+int d3r_selftest_draw_distinct_host(unsigned long long seed, int h, int n, int k, int* idx_out);
 
 /* ---- scene bootstrap: the one-shot initialisation of the aligner (csrc/bootstrap.hip) -----------------------------------------
  * Replaces the per-edge / per-image host loops of dust3r/cloud_opt/init_im_poses.py:67-287 (roma.rigid_points_registration at

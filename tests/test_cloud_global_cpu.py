@@ -2,7 +2,7 @@
 csrc/cloud_features.hip and cloud_metrics.global_registration against, pinned here against the truth on a synthetic scene.
 Every restatement follows the definition of its export in include/dust3r_hip.h, operation for operation:
 - `restated_grid_heads`: the fp32 cell key of d3r_cloud_grid_build, the first index of every key by np.unique.
-- `restated_knn`: an fp32 brute force over all pairs, rows sorted by (d2, index).
+- the k nearest: tests/test_cloud_knn_cpu.py's `brute_force_knn` with exclude_self, the definition of d3r_cloud_knn.
 - `restated_spfh`: float32 numpy, every operation one rounding; only arctan2 is not an IEEE operation, so the function also FLAGS the rows
   with a sample within 1e-4 of a bin width of a bin edge (in fp64), where the device's atan2f may legitimately land on the other side.
 - `restated_fpfh`: fp64, the sums in column and bin order.
@@ -19,6 +19,8 @@ import pytest
 
 from dust3r_amd.cloud_metrics import (FEATURE_CELL, FEATURE_KNN_RADIUS, GlobalRegistration, global_registration, grid_cell, grid_subsample,
                                       match_features, mirror_features, refine_on_inliers, sim3_ransac, similarity_inliers)      # what this file is about
+from test_cloud_knn_cpu import brute_force_knn      # noqa: F401 (tests/test_cloud_global_gpu.py takes it from here too)
+from test_cloud_metrics_cpu import valid_rows
 from test_cloud_icp_cpu import STAGES, pca_normals, restated_register, restated_transform, restated_update, similarity, similarity_distance
 
 F32 = np.float32
@@ -28,14 +30,10 @@ EDGE_MARGIN = 1e-4          # of a bin width: a sample closer than this to a bin
 
 
 # ---- restatements ------------------------------------------------------------------------------------------------------------------------
-def _finite_rows(P):
-    return np.isfinite(P).all(axis=1)
-
-
 def restated_grid_heads(P, cell):
     """indices (M,) int32: the lowest index of every occupied cell, ascending cell key"""
     P = np.asarray(P, F32)
-    ok = _finite_rows(P)
+    ok = valid_rows(P)
     if not ok.any():
         return np.zeros((0,), np.int32)
     lo, hi = P[ok].min(axis=0), P[ok].max(axis=0)
@@ -49,30 +47,6 @@ def restated_grid_heads(P, cell):
     return np.flatnonzero(ok)[first].astype(np.int32)
 
 
-def restated_knn(P, k, max_dist, chunk=512):
-    """(d2 (n, k) float32, idx (n, k) int32) of every point among the others: d3r_cloud_knn with exclude_self, by brute force"""
-    P = np.asarray(P, F32)
-    n = len(P)
-    ok = _finite_rows(P)
-    r2 = F32(max_dist) * F32(max_dist)
-    d2_out, idx_out = np.full((n, k), np.inf, F32), np.full((n, k), -1, np.int32)
-    with np.errstate(invalid='ignore', over='ignore'):
-        for s in range(0, n, chunk):
-            d = P[s:s + chunk, None, :] - P[None, :, :]
-            m = d * d
-            d2 = (m[:, :, 0] + m[:, :, 1]) + m[:, :, 2]
-            assert d2.dtype == F32
-            bad = ~ok[None, :] | ~ok[s:s + chunk, None] | ~(d2 <= r2)
-            bad[np.arange(len(d2)), np.arange(s, s + len(d2))] = True
-            d2 = np.where(bad, F32(np.inf), d2)
-            order = np.argsort(d2, axis=1, kind='stable')[:, :k]              # ties by index
-            got = np.take_along_axis(d2, order, axis=1)
-            cols = min(k, n)
-            d2_out[s:s + chunk, :cols] = got
-            idx_out[s:s + chunk, :cols] = np.where(np.isfinite(got), order, -1)
-    return d2_out, idx_out
-
-
 def _dot(a, b):
     return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
 
@@ -83,7 +57,7 @@ def _cross(a, b):
 
 
 def _normal_ok(N):
-    return _finite_rows(N) & (N != 0).any(axis=1)
+    return valid_rows(N) & (N != 0).any(axis=1)
 
 
 def _bins(x, lo, width):
@@ -101,7 +75,7 @@ def restated_spfh(P, N, idx):
     n, k = idx.shape
     inside = (idx >= 0) & (idx < n)
     g = np.where(inside, idx, 0)
-    point_ok = _finite_rows(P) & _normal_ok(N)
+    point_ok = valid_rows(P) & _normal_ok(N)
     with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
         ok = inside & point_ok[:, None] & point_ok[g]
         u, nq = np.broadcast_to(N[:, None, :], (n, k, 3)), N[g]
@@ -162,8 +136,8 @@ def restated_feature_nearest(A, B):
     """(d2 (na,) float32, idx (na,) int32): a float32 loop over the 33 columns, the lowest index of the minimum"""
     A, B = np.asarray(A, F32), np.asarray(B, F32)
     d2_out, idx_out = np.full(len(A), np.inf, F32), np.full(len(A), -1, np.int32)
-    rows = np.flatnonzero(_finite_rows(A))
-    cand = np.flatnonzero(_finite_rows(B))
+    rows = np.flatnonzero(valid_rows(A))
+    cand = np.flatnonzero(valid_rows(B))
     if len(rows) == 0 or len(cand) == 0:
         return d2_out, idx_out
     a, b = A[rows], B[cand]
@@ -199,23 +173,22 @@ def mix64(x):
 
 
 def draw_index(seed, h, c, n):
-    """visloc_math.hpp's draw_index for an array h of hypotheses"""
+    """ransac.hpp's draw_index for an array h of hypotheses"""
     with np.errstate(over='ignore'):
         r = mix64(mix64(U64(seed) ^ (U64(0xD1B54A32D192ED03) * (h.astype(U64) + U64(1)))) + U64(c))
         return (((r >> U64(32)) * U64(n)) >> U64(32)).astype(np.int64)
 
 
-def restated_samples(seed, n_hyp, n):
-    """(H, 3) int64: the first three distinct draws of every hypothesis, -1 where 64 draws did not give them"""
-    h = np.arange(n_hyp)
-    pick = np.full((n_hyp, 3), -1, np.int64)
+def restated_samples(seed, n_hyp, n, k=3):
+    """(H, k) int64: ransac.hpp's draw_distinct, the first k distinct draws of every hypothesis (of 0 .. n_hyp - 1, or of the hypotheses
+    of an array n_hyp), -1 where 64 draws did not give them"""
+    h = np.arange(n_hyp) if np.ndim(n_hyp) == 0 else np.asarray(n_hyp)
+    pick = np.full((len(h), k), -1, np.int64)
     for c in range(64):
-        k = draw_index(seed, h, c, n)
-        i0, i1, i2 = pick[:, 0].copy(), pick[:, 1].copy(), pick[:, 2].copy()
-        fresh = (k != i0) & (k != i1)
-        pick[:, 0] = np.where(i0 < 0, k, i0)
-        pick[:, 1] = np.where((i0 >= 0) & (i1 < 0) & fresh, k, i1)
-        pick[:, 2] = np.where((i1 >= 0) & (i2 < 0) & fresh, k, i2)
+        d = draw_index(seed, h, c, n)
+        filled = (pick >= 0).sum(axis=1)
+        rows = np.flatnonzero((filled < k) & (pick != d[:, None]).all(axis=1))
+        pick[rows, filled[rows]] = d[rows]
     return pick
 
 
@@ -276,7 +249,7 @@ def restated_ransac(p, q, seed, n_hyp, thr, ratio_min=0.9, with_scale=True):
     nearest correspondence lies to the gate (a count that differed on a device would have to show a row there)"""
     p, q = np.asarray(p, F32), np.asarray(q, F32)
     S, valid = restated_hypotheses(p, q, seed, n_hyp, ratio_min, with_scale)
-    live = _finite_rows(p) & _finite_rows(q)
+    live = valid_rows(p) & valid_rows(q)
     thr2 = F32(thr) * F32(thr)
     counts = np.full(n_hyp, -1, np.int64)
     with np.errstate(invalid='ignore', over='ignore'):
@@ -292,7 +265,7 @@ def restated_ransac(p, q, seed, n_hyp, thr, ratio_min=0.9, with_scale=True):
 
 
 def restated_size(P):
-    V = np.asarray(P, F32)[_finite_rows(P)].astype(np.float64)
+    V = np.asarray(P, F32)[valid_rows(P)].astype(np.float64)
     return math.sqrt(((V - V.mean(axis=0)) ** 2).sum(axis=1).mean())
 
 
@@ -313,7 +286,7 @@ def restated_feature_cloud(P, normals=None, cell=None):
 
 def restated_features(F, N, cell, k=32):
     """(features, d2, idx, counts, flagged) of a feature cloud"""
-    d2, idx = restated_knn(F, k, FEATURE_KNN_RADIUS * cell)
+    d2, idx = brute_force_knn(F, F, k, FEATURE_KNN_RADIUS * cell, exclude_self=True)
     counts, flagged = restated_spfh(F, N, idx)
     return restated_fpfh(idx, d2, counts), d2, idx, counts, flagged
 
@@ -455,6 +428,23 @@ def test_restated_samples_are_distinct_and_reproducible():
     assert (a[:, 0] != a[:, 1]).all() and (a[:, 0] != a[:, 2]).all() and (a[:, 1] != a[:, 2]).all()
     assert not np.array_equal(a, restated_samples(6, 1000, 7))
     assert (restated_samples(0, 50, 3) >= 0).all()                               # three correspondences: every draw set is a permutation
+
+
+@pytest.mark.parametrize('k', [3, 4])
+def test_draw_distinct_is_the_restated_sampler(k):
+    """the sampler of d3r_sim3_ransac (k = 3) and d3r_pnp_ransac (k = 4) on the host build; at n = k every sample is a permutation of all points"""
+    import ctypes as C
+    from dust3r_amd import _lib
+    hyps = np.array([0, 1, 127, 128, 2 ** 23 - 1])
+    for seed in (5, 2 ** 63 + 12345):
+        for n in (4, 5, 7, 1000, 2 ** 31 - 1):
+            want = restated_samples(seed, hyps, n, k)
+            assert (want >= 0).all() and (want < n).all() and all(len(set(row)) == k for row in want.tolist())
+            for h, row in zip(hyps.tolist(), want.tolist()):
+                got = (C.c_int * k)()
+                assert _lib.lib.d3r_selftest_draw_distinct_host(seed, h, n, k, got) == 1
+                assert list(got) == row, (seed, n, h)
+    assert _lib.lib.d3r_selftest_draw_distinct_host(5, 0, 10, 5, (C.c_int * 5)()) == -1
 
 
 def test_restated_ransac_recovers_a_planted_similarity():

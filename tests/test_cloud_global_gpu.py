@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from test_cloud_global_cpu import (DIM, GLOBAL_BAR, KINDS, REFINED_BARS, TRUTH, bumpy, restated_case, restated_feature_nearest, restated_fpfh,
-                                   restated_grid_heads, restated_knn, restated_ransac, restated_spfh, scene)
+                                   restated_grid_heads, brute_force_knn, restated_ransac, restated_spfh, scene)
 from test_cloud_icp_cpu import STAGES, pca_normals, similarity, similarity_distance
 
 pytestmark = pytest.mark.gpu
@@ -63,7 +63,7 @@ def descriptor_inputs(n, k):
             N[9] = 0
             N[11] = (0, 0, 1)
             P[12] = P[11] + np.array([0, 0, 0.25], F32)
-        d2, idx = restated_knn(P, k, 0.5 if n > 100 else 4.0)
+        d2, idx = brute_force_knn(P, P, k, 0.5 if n > 100 else 4.0, exclude_self=True)
         if n > 16:
             idx[11, 0], d2[11, 0] = 12, F32(0.0625)
             idx[13, -1], d2[13, -1] = -1, np.inf

@@ -15,6 +15,7 @@ import pytest
 from scipy.spatial import cKDTree
 
 from dust3r_amd.cloud_metrics import Registration, icp_update, plane_system, register_clouds, similarity_parts      # what this file is about
+from test_cloud_metrics_cpu import valid_rows
 
 F32 = np.float32
 STAGES = (0.3, 0.1, 0.03)
@@ -38,10 +39,6 @@ def restated_transform(P, M, normals=None, R=None):
     return out, rot
 
 
-def _finite_rows(P):
-    return np.isfinite(P).all(axis=1)
-
-
 def restated_used_and_sums(moved, ref, d2, idx, metric, gate, centre, ref_normals=None, moved_normals=None, cos_min=None):
     """(used (n,) bool, count, sums (18 or 36,) float64, terms (count, 18 or 36) float64): the definition of d3r_cloud_icp_sums. sums =
     terms.sum(axis=0) in numpy's order; the kernel adds the same doubles in another order."""
@@ -49,12 +46,12 @@ def restated_used_and_sums(moved, ref, d2, idx, metric, gate, centre, ref_normal
     idx, d2 = np.asarray(idx, np.int64), np.asarray(d2, F32)
     gate = F32(gate)
     with np.errstate(invalid='ignore', over='ignore'):
-        used = (idx >= 0) & (idx < len(ref)) & (d2 <= gate * gate) & _finite_rows(moved)
+        used = (idx >= 0) & (idx < len(ref)) & (d2 <= gate * gate) & valid_rows(moved)
         g = np.where(used, idx, 0)
-        used &= _finite_rows(ref[g])
+        used &= valid_rows(ref[g])
         if metric == 'plane':
             n32 = np.asarray(ref_normals, F32)[g]
-            used &= _finite_rows(n32) & (n32 != 0).any(axis=1)
+            used &= valid_rows(n32) & (n32 != 0).any(axis=1)
         if moved_normals is not None:
             m, n32 = np.asarray(moved_normals, F32), np.asarray(ref_normals, F32)[g]
             cos = (m[:, 0] * n32[:, 0] + m[:, 1] * n32[:, 1]) + m[:, 2] * n32[:, 2]
@@ -105,7 +102,7 @@ def similarity_distance(S, T):
 def nearest_by_tree(tree, ref, moved, gate):
     """(d2 float32, idx) with cKDTree choosing the neighbour and the kernels' fp32 expression giving d2; -1 / inf beyond the gate or for
     a non-finite point"""
-    ok = _finite_rows(moved)
+    ok = valid_rows(moved)
     idx = np.full(len(moved), -1, np.int64)
     d2 = np.full(len(moved), np.inf, F32)
     _, j = tree.query(moved[ok].astype(np.float64), k=1, distance_upper_bound=float(gate) * 1.001)
@@ -138,7 +135,7 @@ def restated_register(src, dst, dst_normals, stages, init=None, with_scale=True,
     """(S, history [(stage, n_pairs, rmse)], converged): the loop of register_clouds"""
     src, dst = np.asarray(src, F32), np.asarray(dst, F32)
     S = np.eye(4) if init is None else np.array(init, np.float64)
-    ok = _finite_rows(dst)
+    ok = valid_rows(dst)
     c = ((dst[ok].min(axis=0).astype(np.float64) + dst[ok].max(axis=0).astype(np.float64)) * 0.5).astype(F32) if centre is None else np.asarray(centre, F32)
     c64 = c.astype(np.float64)
     tree = cKDTree(dst.astype(np.float64))
