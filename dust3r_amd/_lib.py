@@ -5,11 +5,13 @@ and every compute entry point checks for a gfx950 device (`require_device`) befo
 """
 import ctypes as C
 import os
+import re
 
 import torch  # noqa: F401  (loads torch's libamdhip64.so.7 first so that the engine shares its HIP runtime)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libdust3r_hip.so')
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'dust3r_hip.h')
 
 DTYPE_BF16, DTYPE_F16, DTYPE_F32, DTYPE_F16X3, DTYPE_F16F8, DTYPE_F16X2F8 = 0, 1, 2, 3, 4, 5
 DTYPES = {'bf16': DTYPE_BF16, 'bfloat16': DTYPE_BF16, 'f16': DTYPE_F16, 'fp16': DTYPE_F16, 'float16': DTYPE_F16,
@@ -73,148 +75,58 @@ class PnpRansacParams(C.Structure):
     _fields_ = [('max_iters', C.c_int), ('max_points', C.c_int)]
 
 
+_SCALARS = {'void': None, 'int': C.c_int, 'unsigned': C.c_uint, 'long': C.c_long, 'long long': C.c_longlong, 'unsigned long long': C.c_ulonglong,
+            'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t, 'int32_t': C.c_int32, 'uint32_t': C.c_uint32, 'int64_t': C.c_int64,
+            'uint8_t': C.c_uint8}
+# the struct arguments that callers may pass by value (ctypes then takes the address): every other pointer is a plain address
+_STRUCTS = {'d3r_model_config': ModelConfig, 'd3r_view_plan': ViewPlan, 'd3r_criterion_opts': CriterionOpts, 'd3r_pnp_ransac_params': PnpRansacParams}
+
+
+def _ctype(decl, text):
+    """ctypes class of one return or parameter type as the header spells it (`const float* const*`, `int`, ...)."""
+    words = re.sub(r'\bconst\b', ' ', decl)
+    base = ' '.join(words.replace('*', ' ').split())
+    if '*' in words:
+        if base == 'char' and words.count('*') == 1:
+            return C.c_char_p
+        return C.POINTER(_STRUCTS[base]) if base in _STRUCTS and words.count('*') == 1 else C.c_void_p
+    if base not in _SCALARS:
+        raise ImportError(f'include/dust3r_hip.h: unknown type `{decl.strip()}` in `{text}`')
+    return _SCALARS[base]
+
+
+def parse_header(text):
+    """{name: (restype, [argtypes])} of every d3r_* prototype of a C header: the signatures are read, not restated."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#(?:.*\\\n)*.*$', '', text, flags=re.M).replace('extern "C" {', '')
+    text = re.sub(r'\{[^{}]*\}', ' ', text)                  # struct bodies
+    sig = {}
+    for stmt in text.split(';'):
+        if '(' not in stmt:
+            continue                                          # typedefs
+        stmt = ' '.join(stmt.split())
+        m = re.fullmatch(r'([\w\s*]+?)\b(d3r_\w+) ?\(([^()]*)\)', stmt)
+        if not m:
+            raise ImportError(f'include/dust3r_hip.h: cannot parse the declaration `{stmt}`')
+        args = []
+        for a in ([] if m.group(3).strip() == 'void' else m.group(3).split(',')):
+            p = re.fullmatch(r'(.*?)\b\w+ ?(\[\w*\])?', a.strip())      # type, parameter name, array suffix
+            if not p or not p.group(1).strip():
+                raise ImportError(f'include/dust3r_hip.h: cannot parse the parameter `{a.strip()}` of `{stmt}`')
+            args.append(_ctype(p.group(1) + ('*' if p.group(2) else ''), stmt))
+        sig[m.group(2)] = (_ctype(m.group(1), stmt), args)
+    return sig
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                           '(or `python dust3r_amd/build.py`). dust3r_amd has no CPU fallback.')
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError(f'{HEADER_PATH} is missing: the signatures of {os.path.basename(LIB_PATH)} are read from it.')
     lib = C.CDLL(LIB_PATH)
-    vp, i, f, fp, ip = C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p
-    sig = {
-        'd3r_version': (C.c_char_p, []),
-        'd3r_device_check': (i, []),
-        'd3r_rope2d': (i, [vp, vp, i, i, i, i, f, f, i, vp]),
-        'd3r_layernorm': (i, [fp, fp, fp, vp, i, i, f, i, vp]),
-        'd3r_linear': (i, [vp, vp, fp, vp, fp, i, i, i, i, i, vp]),
-        'd3r_linear_x3res': (i, [vp, vp, fp, vp, vp, fp, i, i, i, vp]),
-        'd3r_rope_table': (i, [fp, i, f, f, vp]),
-        'd3r_linear_heads': (i, [vp, vp, fp, i, i, i, i, ip, vp, i, i, i, i, fp, i, fp, fp, fp, fp, f, fp, C.c_size_t, vp, i, i, vp]),
-        'd3r_linear_heads_tile_config': (i, [i, i, i, i, ip, i, i, i, i, i, i]),
-        'd3r_ln_finalize': (i, [fp, i, i, f, fp, fp, vp]),
-        'd3r_ln_fold_pack': (i, [fp, fp, fp, fp, vp, fp, fp, i, i, i, vp]),
-        'd3r_linear_ln': (i, [vp, vp, fp, vp, i, i, i, i, fp, fp, fp, fp, f, vp]),
-        'd3r_layernorm_x3rows': (i, [vp, fp, fp, vp, i, i, f, vp]),
-        'd3r_conv2d_nhwc': (i, [vp, vp, fp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, vp, i, vp]),
-        'd3r_conv_k_slice_major': (i, []),
-        'd3r_pack_conv_weight': (i, [fp, vp, i, i, i, i, i, i, i, vp]),
-        'd3r_pack_convt_bias': (i, [fp, fp, i, i, i, vp]),
-        'd3r_conv2d_nhwc_x': (i, [vp, vp, fp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, i, vp, i, vp]),
-        'd3r_convt_gemm': (i, [vp, vp, fp, vp, i, i, i, i, i, i, i, i, i, vp]),
-        'd3r_conv_head4': (i, [vp, vp, fp, fp, fp, fp, fp, i, i, i, i, i, i, i, i, i, i, i, f, f, vp, i, vp]),
-        'd3r_up2_conv_head4': (i, [vp, vp, vp, fp, fp, fp, fp, fp, i, i, i, i, i, i, i, i, i, i, f, f, vp, i, vp]),
-        'd3r_up2_conv_route': (i, [i, i, i, i, i, i, i, i]),
-        'd3r_up2_conv2d_nhwc_x': (i, [vp, vp, vp, fp, vp, i, i, i, i, i, i, i, i, vp, i, vp]),
-        'd3r_head_final': (i, [vp, i, fp, fp, fp, fp, C.c_size_t, i, i, i, i, f, f, i, vp]),
-        'd3r_linear_head_post': (i, [fp, fp, fp, i, i, i, i, i, i, i, i, f, f, vp]),
-        'd3r_attention': (i, [vp, vp, vp, vp, i, i, i, i, i, f, i, vp]),
-        'd3r_attention_rows': (i, [vp, vp, vp, vp, i, i, i, i, i, f, i, i, vp]),
-        'd3r_upsample2x_nhwc': (i, [vp, vp, i, i, i, i, i, i, i, vp]),
-        'd3r_gemm_set_trace': (i, [vp, C.c_size_t]),
-        'd3r_gemm_tile_config': (i, [i, i, i, i, i, i]),
-        'd3r_build_has_probes': (i, []),
-        'd3r_model_create': (i, [C.POINTER(vp), C.POINTER(ModelConfig)]),
-        'd3r_model_destroy': (i, [vp]),
-        'd3r_model_load_tensor': (i, [vp, C.c_char_p, fp, i, C.POINTER(C.c_int64)]),
-        'd3r_model_load_tensor_device': (i, [vp, C.c_char_p, fp, i, C.POINTER(C.c_int64)]),
-        'd3r_model_missing': (i, [vp]),
-        'd3r_model_forward': (i, [vp, fp, fp, i, i, i, fp, fp, fp, fp, vp]),
-        'd3r_model_forward_mixed': (i, [vp, fp, i, i, fp, i, i, i, fp, fp, fp, fp, vp]),
-        'd3r_model_forward_packed': (i, [vp, fp, fp, i, i, i, fp, vp]),
-        'd3r_model_device_bytes': (C.c_size_t, [vp]),
-        'd3r_model_graph_replays': (C.c_long, [vp]),
-        'd3r_model_feature_bytes': (C.c_size_t, [vp, i, i]),
-        'd3r_model_encode': (i, [vp, fp, i, i, i, vp, vp]),
-        'd3r_model_decode': (i, [vp, vp, i, i, i, fp, fp, fp, fp, vp]),
-        'd3r_model_decode_packed': (i, [vp, vp, i, i, i, fp, vp]),
-        'd3r_model_debug_read': (i, [vp, i, fp, C.c_size_t, vp]),
-        'd3r_model_set_option': (i, [vp, i, i]),
-        'd3r_model_set_postprocess': (i, [vp, i, i, f, f]),
-        'd3r_model_profile_read': (i, [vp, i, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-        'd3r_model_profile_launch': (i, [vp, i] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_double)] * 2),
-        'd3r_aligner_create': (i, [C.POINTER(vp), i, i, ip, ip, ip, ip, i, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, f, f, f,
-                                   i, i, i, i, i, vp]),
-        'd3r_aligner_destroy': (i, [vp]),
-        'd3r_aligner_set_option': (i, [vp, i, i]),
-        'd3r_aligner_set_trainable': (i, [vp, i, C.c_char_p]),
-        'd3r_aligner_run': (i, [vp, i, i, i, f, f, i, fp, vp]),
-        'd3r_aligner_loss_grad': (i, [vp, fp, fp, fp, fp, fp, fp, fp, vp]),
-        'd3r_aligner_set_image_range': (i, [vp, i, i]),
-        'd3r_aligner_step_begin': (i, [vp, i, i, i, f, f, i, vp]),
-        'd3r_aligner_step_end': (i, [vp, i, i, i, f, f, i, vp]),
-        'd3r_aligner_reduced_sums': (i, [vp, C.POINTER(vp), C.POINTER(C.c_longlong)]),
-        'd3r_aligner_read_losses': (i, [vp, i, fp, vp]),
-        'd3r_nearest_neighbors': (i, [fp, i, fp, i, ip, vp]),
-        'd3r_clean_pointcloud': (i, [i, fp, fp, fp, fp, fp, ip, ip, i, f, f, vp]),
-        'd3r_segment_sky_workspace_bytes': (C.c_size_t, [i, i]),
-        'd3r_segment_sky': (i, [i, vp, i, ip, ip, i, vp, vp, vp]),
-        'd3r_sky_color_mask': (i, [i, vp, i, ip, ip, i, vp, vp]),
-        'd3r_scene_mesh_workspace_bytes': (C.c_size_t, [i, i]),
-        'd3r_scene_mesh': (i, [i, vp, vp, vp, i, ip, ip, i, i, vp, vp, vp, vp, vp, vp, vp]),
-        'd3r_fuse_bounds_workspace_bytes': (C.c_size_t, [i, i]),
-        'd3r_fuse_bounds': (i, [i, fp, vp, fp, ip, ip, i, fp, vp, vp, vp]),
-        'd3r_fuse_voxels_workspace_bytes': (C.c_size_t, [i, i, i]),
-        'd3r_fuse_voxels': (i, [i, fp, vp, fp, vp, i, ip, ip, i, C.POINTER(C.c_float), f, C.POINTER(C.c_int), i, fp, vp, fp, ip, vp, vp, vp]),
-        'd3r_cloud_grid_workspace_bytes': (C.c_size_t, [i, i]),
-        'd3r_cloud_grid_build': (i, [i, fp, C.POINTER(C.c_float), f, C.POINTER(C.c_int), vp, vp]),
-        'd3r_cloud_nearest': (i, [i, i, fp, f, C.POINTER(C.c_float), f, C.POINTER(C.c_int), i, fp, ip, ip, vp, vp]),
-        'd3r_cloud_distance_stats_workspace_bytes': (C.c_size_t, [i]),
-        'd3r_cloud_distance_stats': (i, [i, fp, fp, ip, i, C.POINTER(C.c_float), vp, vp, vp, vp]),
-        'd3r_cloud_knn': (i, [i, i, fp, i, f, C.POINTER(C.c_float), f, C.POINTER(C.c_int), i, i, fp, ip, ip, vp, vp]),
-        'd3r_cloud_knn_distances_workspace_bytes': (C.c_size_t, [i]),
-        'd3r_cloud_knn_distances': (i, [i, i, fp, ip, fp, vp, vp, vp, vp]),
-        'd3r_cloud_normals': (i, [i, fp, i, fp, i, ip, i, fp, fp, vp]),
-        'd3r_cloud_orient_normals': (i, [i, fp, fp, ip, i, fp, fp, fp, fp, fp, ip, ip, i, f, vp]),
-        'd3r_cloud_transform': (i, [i, fp, C.POINTER(C.c_float), fp, fp, C.POINTER(C.c_float), fp, vp]),
-        'd3r_cloud_icp_sums_workspace_bytes': (C.c_size_t, [i]),
-        'd3r_cloud_icp_sums': (i, [i, fp, fp, i, fp, fp, fp, ip, i, f, f, C.POINTER(C.c_float), vp, vp, vp, vp, vp]),
-        'd3r_cloud_cluster_workspace_bytes': (C.c_size_t, [i]),
-        'd3r_cloud_cluster': (i, [i, f, i, C.POINTER(C.c_float), f, C.POINTER(C.c_int), ip, ip, ip, ip, vp, ip, C.POINTER(vp), vp, vp, vp]),
-        'd3r_cloud_grid_heads': (i, [i, ip, ip, vp, vp]),
-        'd3r_cloud_spfh': (i, [i, fp, fp, i, ip, vp, vp]),
-        'd3r_cloud_fpfh': (i, [i, i, ip, fp, vp, fp, vp]),
-        'd3r_feature_nearest': (i, [i, fp, i, fp, fp, ip, vp]),
-        'd3r_sim3_ransac_workspace_bytes': (C.c_size_t, [i, i]),
-        'd3r_sim3_ransac': (i, [i, fp, fp, C.c_ulonglong, i, f, C.c_double, i, vp, vp, vp, vp]),
-        'd3r_cloud_tracks_workspace_bytes': (C.c_size_t, [i]),
-        'd3r_cloud_tracks_count': (i, [i, fp, vp, fp, ip, ip, i, i, fp, vp, f, i, C.c_double, ip, vp, vp, vp]),
-        'd3r_cloud_tracks_fill': (i, [i, fp, vp, fp, ip, ip, i, i, fp, vp, f, i, C.c_double, ip, vp, C.c_longlong, i, ip, ip, vp, ip, ip, ip, vp, vp]),
-        'd3r_scene_gallery_workspace_bytes': (C.c_size_t, [i, i]),
-        'd3r_scene_gallery': (i, [i, fp, fp, ip, i, fp, fp, fp, fp, vp, vp]),
-        'd3r_scene_gallery_launch_bound': (None, [C.POINTER(C.c_int)] * 3),
-        'd3r_selftest_gallery_index_host': (i, [fp, i, ip]),
-        'd3r_render_project': (i, [i, fp, i, fp, i, fp, f, ip, vp, vp]),
-        'd3r_render_clear': (i, [i, i, i, vp, vp]),
-        'd3r_render_points': (i, [i, fp, vp, C.c_uint32, i, fp, i, fp, f, i, i, i, vp, vp, vp]),
-        'd3r_render_triangles': (i, [i, vp, i, fp, C.c_uint32, i, fp, i, fp, f, i, i, vp, vp, vp]),
-        'd3r_render_resolve': (i, [i, fp, i, fp, f, i, i, vp, i, C.c_uint32, vp, i, C.c_uint32, vp, i, fp, vp, C.c_uint32, vp, fp, ip, vp]),
-        'd3r_match_pairs_workspace': (C.c_size_t, [i, i]),
-        'd3r_match_pairs': (i, [i, vp, i, vp, ip, ip, vp]),
-        'd3r_pnp_ransac_workspace': (C.c_size_t, [i, i]),
-        'd3r_pnp_ransac': (i, [i, vp, C.POINTER(PnpRansacParams), vp, fp, ip, ip, ip, vp]),
-        'd3r_selftest_p3p_host': (i, [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
-        'd3r_selftest_p3p_roots_host': (i, [vp, vp, vp, vp]),
-        'd3r_selftest_ransac_iters_host': (i, [C.c_double, C.c_double, i, i]),
-        'd3r_selftest_draw_distinct_host': (i, [C.c_ulonglong, i, i, i, ip]),
-        'd3r_row_means': (i, [fp, i, i, i, fp, vp]),
-        'd3r_similarity_moments_workspace': (C.c_size_t, [i, i]),
-        'd3r_similarity_moments': (i, [i, vp, vp, vp, ip, i, vp, vp, vp]),
-        'd3r_weiszfeld_focals': (i, [i, vp, ip, ip, i, fp, vp]),
-        'd3r_anchor_depth': (i, [i, vp, fp, ip, i, i, fp, vp]),
-        'd3r_pnp_job_bytes': (i, []),
-        'd3r_pnp_max_hypotheses': (i, []),
-        'd3r_pnp_sum_count': (i, []),
-        'd3r_pnp_workspace': (C.c_size_t, [i]),
-        'd3r_pnp_score': (i, [i, vp, fp, i, f, ip, vp]),
-        'd3r_pnp_sums': (i, [i, vp, fp, f, vp, vp, vp]),
-        'd3r_pair_criterion_workspace_bytes': (C.c_size_t, [i, i]),
-        'd3r_pair_criterion': (i, [i, i, fp, fp, fp, vp, vp, fp, fp, fp, fp, C.POINTER(CriterionOpts), vp, fp, fp, vp, vp]),
-        'd3r_pair_criterion_passes': (i, [C.POINTER(CriterionOpts)]),
-        'd3r_masked_median': (i, [i, i, fp, fp, vp, vp, vp, vp, vp]),
-        'd3r_view_plan_bytes': (i, []),
-        'd3r_prepare_views': (i, [i, C.POINTER(ViewPlan), vp, i, i, fp, vp, C.c_size_t, fp, fp, fp, vp, vp]),
-        'd3r_selftest_resample_host': (i, [vp, i, i, i, i, i, i, i, i, vp, vp, i, vp, vp, i, vp]),
-        'd3r_selftest_depth_host': (i, [C.POINTER(ViewPlan), i, i, fp, fp, vp]),
-        'd3r_selftest_aligner_math_host': (i, [i, i, ip, ip, i, i, fp, fp, fp, fp, fp, fp, fp, fp, f, f, vp, vp, vp, vp, vp]),
-    }
+    with open(HEADER_PATH) as fh:
+        sig = parse_header(fh.read())
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header / library mismatch
         fn.restype = res

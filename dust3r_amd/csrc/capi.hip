@@ -4,8 +4,6 @@
 
 using namespace d3r;
 
-static inline int rup(int a, int b) { return (a + b - 1) / b * b; }
-
 extern "C" int d3r_rope2d(void* tokens, const int64_t* positions, int B, int N, int H, int D, float base, float F0, int dtype, void* stream) {
     if (!tokens || !positions) return D3R_ERR_INVALID;
     return rc_of(launch_rope2d(dtype, tokens, positions, B, N, H, D, base, F0, (hipStream_t)stream));
@@ -31,7 +29,7 @@ extern "C" int d3r_linear_x3res(const void* act, const void* wgt, const float* b
                                 int K, void* stream) {
     if (!act || !wgt || !out_rows || N % 8 != 0) return D3R_ERR_INVALID;
     GemmParams p = linear_gemm_params(act, K, wgt, bias, M, N, K);
-    p.epi = EPI_F32; p.flags = GF_X3RES; p.res1 = residual_rows; p.ldr = N; p.out2 = out_rows; p.ldo2 = N; p.ln_part = ln_part;
+    epi_typed_residual(p, residual_rows, out_rows, N, ln_part);
     return rc_of(launch_gemm(D3R_F16X3, p, (hipStream_t)stream));
 }
 
@@ -42,16 +40,15 @@ extern "C" int d3r_rope_table(float* table, int max_pos, float base, float F0, v
 
 // The shape half of an EPI_HEADS launch (d3r_linear_heads, d3r_linear_heads_tile_config): the argument checks of the header, then the GemmParams
 // fields the dispatch reads. Weight rows as d3r_linear allocates them.
-static bool heads_shape(GemmParams& p, const void* act, const void* wgt, const float* bias, int dtype, int M, int K, int n_regions, int head_c, const int* kinds, int heads, int ntok, int tok_w, int ldv, int max_pos) {
-    if (dtype != D3R_BF16 && dtype != D3R_F16 && dtype != D3R_F32 && dtype != D3R_F16X3 && dtype != D3R_F16F8 && dtype != D3R_F16X2F8) return false;
+static bool heads_shape(GemmParams& p, const void* act, const void* wgt, const float* bias, int dtype, int M, int K, int n_regions, int head_c, const int* kinds, void* const* dsts, int heads, int ntok, int tok_w, int ldv, const float* rope_table, int max_pos) {
+    if (!gemm_dtype(dtype)) return false;
     if (M <= 0 || K <= 0 || n_regions < 1 || n_regions > 3 || !kinds || heads <= 0 || head_c != heads * 64 || ntok <= 0 || tok_w <= 0) return false;
     if (M % ntok != 0 || ntok % tok_w != 0 || (ntok / tok_w > tok_w ? ntok / tok_w : tok_w) > max_pos) return false;
     if (ldv < rup(ntok, 64) || ldv % 64 != 0) return false;
     for (int r = 0; r < n_regions; ++r)
-        if (kinds[r] != HEAD_ROPE && kinds[r] != HEAD_VT && kinds[r] != HEAD_PLAIN) return false;
+        if ((kinds[r] != HEAD_ROPE && kinds[r] != HEAD_VT && kinds[r] != HEAD_PLAIN) || (dsts && !dsts[r])) return false;
     p = linear_gemm_params(act, K, wgt, bias, M, n_regions * head_c, K);
-    p.epi = EPI_HEADS; p.head_c = head_c; p.heads = heads; p.ntok = ntok; p.tok_w = tok_w; p.ldv = ldv;
-    for (int r = 0; r < n_regions; ++r) p.head_kind[r] = kinds[r];
+    epi_heads(p, head_c, n_regions, kinds, dsts, heads, ntok, tok_w, ldv, rope_table);
     return true;
 }
 
@@ -61,14 +58,9 @@ extern "C" int d3r_linear_heads(const void* act, const void* wgt, const float* b
                                 int sk_cnt_n, int dtype, void* stream) {
     if (!act || !wgt || !dsts || !rope_table) return D3R_ERR_INVALID;
     GemmParams p;
-    if (!heads_shape(p, act, wgt, bias, dtype, M, K, n_regions, head_c, kinds, heads, ntok, tok_w, ldv, max_pos)) return D3R_ERR_INVALID;
-    for (int r = 0; r < n_regions; ++r) {
-        if (!dsts[r]) return D3R_ERR_INVALID;
-        p.head_dst[r] = dsts[r];
-    }
+    if (!heads_shape(p, act, wgt, bias, dtype, M, K, n_regions, head_c, kinds, dsts, heads, ntok, tok_w, ldv, rope_table, max_pos)) return D3R_ERR_INVALID;
     if ((ln_rstd || ln_nmr || ln_colsum || ln_part_in) && (dtype != D3R_F16X3 || !ln_rstd || !ln_nmr || !ln_colsum)) return D3R_ERR_INVALID;
-    p.rope_table = rope_table;
-    if (ln_rstd) { p.ln_rstd = ln_rstd; p.ln_nmr = ln_nmr; p.ln_colsum = ln_colsum; p.ln_part_in = ln_part_in; p.ln_eps = ln_eps; p.ln_inv_c = 1.0f / (float)K; }
+    if (ln_rstd) ln_consumer(p, ln_rstd, ln_nmr, ln_colsum, ln_part_in, ln_eps);
     if (sk_slab && sk_cnt) { p.splitk = 0; p.sk_slab = sk_slab; p.sk_slab_floats = sk_slab_floats; p.sk_cnt = sk_cnt; p.sk_cnt_n = sk_cnt_n; }      // launch_gemm decides whether it splits (engine.hip launch(), lend_sk: gemm_linear)
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
 }
@@ -77,7 +69,7 @@ extern "C" int d3r_linear_heads_tile_config(int M, int K, int n_regions, int hea
                                             int dtype) {
     static const float dummy = 0.f;
     GemmParams p;
-    if (!heads_shape(p, &dummy, &dummy, nullptr, dtype, M, K, n_regions, head_c, kinds, heads, ntok, tok_w, ldv, max_pos)) return D3R_ERR_INVALID;      // (operands never dereferenced)
+    if (!heads_shape(p, &dummy, &dummy, nullptr, dtype, M, K, n_regions, head_c, kinds, nullptr, heads, ntok, tok_w, ldv, nullptr, max_pos)) return D3R_ERR_INVALID;      // (operands never dereferenced)
     const GemmPlan plan = gemm_plan_for(p, dtype);
     return plan.w8 ? D3R_TILE_128W8 : plan.cfg;
 }
@@ -104,7 +96,7 @@ extern "C" int d3r_linear_ln(const void* act_rows, const void* wgt, const float*
     GemmParams p = linear_gemm_params(act_rows, K, wgt, bias_fold, M, N, K);
     p.epi = epilogue == 2 ? EPI_GELU : EPI_T;
     p.out = out; p.ldo = N;
-    p.ln_rstd = ln_rstd; p.ln_nmr = ln_nmr; p.ln_colsum = ln_colsum; p.ln_part_in = ln_part_in; p.ln_eps = ln_eps; p.ln_inv_c = 1.0f / (float)K;
+    ln_consumer(p, ln_rstd, ln_nmr, ln_colsum, ln_part_in, ln_eps);
     return rc_of(launch_gemm(D3R_F16X3, p, (hipStream_t)stream));
 }
 
@@ -121,29 +113,16 @@ extern "C" int d3r_conv2d_nhwc(const void* in, const void* wgt, const float* bia
                                void* stream) {
     if (!in || !wgt || !out || !zero_page || Cout % 4 != 0) return D3R_ERR_INVALID;
     GemmParams p = conv_gemm_params(in, B, Hin, Win, Cin, wgt, bias, Cin, Cout, ksize, stride, pad, zero_page);
-    p.epi = EPI_T; p.flags = relu ? GF_RELU : 0; p.out = out; p.ldo = Cout; p.res1 = res1; p.res2 = res2; p.ldr = Cout;
-    p.out2 = out_relu_copy; p.ldo2 = Cout;
+    epi_typed_store(p, out, Cout, relu ? GF_RELU : 0, res1, res2, out_relu_copy);
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
 // ---- the DPT head's kernels alone (include/dust3r_hip.h): the launches of engine.hip run_dpt (through conv / conv_head4 / launch), for the kernel tests -------------------------------
-static inline bool conv_dtype(int dtype) { return dtype == D3R_BF16 || dtype == D3R_F16 || dtype == D3R_F32 || dtype == D3R_F16X3; }
-static inline bool post_mode(PostMode& pm, int depth_mode, int conf_mode, float vmin, float vmax) {      // d3r_model_set_postprocess's rules
-    if (depth_mode < POST_DEPTH_EXP || depth_mode > POST_DEPTH_SQUARE || conf_mode < POST_CONF_EXP || conf_mode > POST_CONF_SIGMOID) return false;
-    if (!(vmin < vmax) || (conf_mode == POST_CONF_SIGMOID && !(vmax < __builtin_huge_valf() && vmin > -__builtin_huge_valf()))) return false;
-    pm.depth = depth_mode; pm.conf = conf_mode; pm.cmin = vmin; pm.cmax = vmax;
-    return true;
-}
-
 extern "C" int d3r_pack_conv_weight(const float* src, void* dst, int transposed, int Cout, int Cin, int ksize, int cin_pad, int cout_pad, int dtype,
                                     void* stream) {
-    if (!src || !dst || !conv_dtype(dtype) || Cout <= 0 || Cin <= 0 || ksize <= 0) return D3R_ERR_INVALID;
-    if (cin_pad < Cin || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || (transposed && (cout_pad < Cout || cout_pad % 4 != 0))) return D3R_ERR_INVALID;
-    PackParams pp;
-    pp.src = src; pp.dst = dst; pp.numel = (size_t)Cout * Cin * ksize * ksize; pp.ksize = ksize;
-    if (transposed) { pp.kind = PACK_CONVT; pp.cols = Cout; pp.cout_pad = cout_pad; pp.dst_cols = cin_pad; }                 // engine.hip reg_convt / PK_CONVT
-    else { pp.kind = PACK_CONV; pp.cin = Cin; pp.cin_pad = cin_pad; pp.dst_cols = ksize * ksize * cin_pad; }                 // engine.hip reg_conv / PK_CONV
-    return rc_of(launch_pack_weight(dtype, pp, (hipStream_t)stream));
+    if (!src || !dst || Cout <= 0 || Cin <= 0 || ksize <= 0 || !conv_operand_ok(dtype, cin_pad, cin_pad)) return D3R_ERR_INVALID;
+    if (cin_pad < Cin || (transposed && (cout_pad < Cout || cout_pad % 4 != 0))) return D3R_ERR_INVALID;
+    return rc_of(launch_pack_weight(dtype, conv_pack_params(src, dst, transposed != 0, Cout, Cin, ksize, cin_pad, cout_pad), (hipStream_t)stream));      // engine.hip pack_slot's
 }
 
 extern "C" int d3r_pack_convt_bias(const float* src, float* dst, int Cout, int cout_pad, int ksize, void* stream) {
@@ -154,88 +133,78 @@ extern "C" int d3r_pack_convt_bias(const float* src, float* dst, int Cout, int c
 extern "C" int d3r_conv2d_nhwc_x(const void* in, const void* wgt, const float* bias, void* out, const void* res1, const void* res2, void* out_relu_copy,
                                  int B, int Hin, int Win, int cstride, int cin_pad, int Cout, int n_store, int ldo, int ksize, int stride, int pad, int flags,
                                  const void* zero_page, int dtype, void* stream) {
-    if (!in || !wgt || !out || !zero_page || !conv_dtype(dtype) || B <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || ksize <= 0 || stride <= 0 || pad < 0) return D3R_ERR_INVALID;
+    if (!in || !wgt || !out || !zero_page || !conv_operand_ok(dtype, cin_pad, cstride) || B <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || ksize <= 0 || stride <= 0 || pad < 0) return D3R_ERR_INVALID;
     if (n_store < 0) n_store = Cout;
-    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || cstride < cin_pad) return D3R_ERR_INVALID;      // whole K steps per tap, inside a pixel's row
-    if (n_store % 4 != 0 || n_store > rup(Cout, 128) || ldo < n_store || (flags & ~(GF_RELU | GF_NOWIDE))) return D3R_ERR_INVALID;
+    if (n_store % 4 != 0 || n_store > gemm_n_pad(Cout) || ldo < n_store || (flags & ~(GF_RELU | GF_NOWIDE))) return D3R_ERR_INVALID;
     if (Hin + 2 * pad < ksize || Win + 2 * pad < ksize) return D3R_ERR_INVALID;
     GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, wgt, bias, cin_pad, Cout, ksize, stride, pad, zero_page);
     p.n_store = n_store;
-    p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.res1 = res1; p.res2 = res2; p.ldr = ldo; p.out2 = out_relu_copy; p.ldo2 = ldo;      // engine.hip conv()
+    epi_typed_store(p, out, ldo, flags, res1, res2, out_relu_copy);      // engine.hip conv()
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
 extern "C" int d3r_convt_gemm(const void* act, const void* wgt, const float* bias, void* out, int B, int th, int tw, int lda, int cin_pad, int cout_pad,
                               int ksize, int ldo, int dtype, void* stream) {
-    if (!act || !wgt || !out || !conv_dtype(dtype) || B <= 0 || th <= 0 || tw <= 0 || ksize <= 0) return D3R_ERR_INVALID;
-    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || lda < cin_pad || cout_pad <= 0 || cout_pad % 4 != 0 || ldo < cout_pad) return D3R_ERR_INVALID;
+    if (!act || !wgt || !out || !conv_operand_ok(dtype, cin_pad, lda) || B <= 0 || th <= 0 || tw <= 0 || ksize <= 0) return D3R_ERR_INVALID;
+    if (cout_pad <= 0 || cout_pad % 4 != 0 || ldo < cout_pad) return D3R_ERR_INVALID;
     const int N = ksize * ksize * cout_pad;
     GemmParams p = linear_gemm_params(act, lda, wgt, bias, B * th * tw, N, cin_pad);      // engine.hip run_dpt, the EPI_CONVT launch: lin_params on the packed matrix
-    p.epi = EPI_CONVT; p.ksize = ksize; p.ct_cout = cout_pad;
-    p.Hin = th; p.Win = tw; p.out = out; p.ldo = ldo;
+    epi_convt(p, ksize, cout_pad, th, tw, out, ldo);
     return rc_of(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
 extern "C" int d3r_conv_head4(const void* in, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B, int Hin,
                               int Win, int cstride, int cin_pad, int Cout, int ksize, int pstride, int conf_stride, int depth_mode, int conf_mode,
                               float conf_vmin, float conf_vmax, const void* zero_page, int dtype, void* stream) {
-    if (!in || !wgt || !w4 || !b4 || !pts || !conf || !zero_page || !conv_dtype(dtype) || B <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || ksize <= 0) return D3R_ERR_INVALID;
-    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || cstride < cin_pad || pstride < 3 || conf_stride < 1) return D3R_ERR_INVALID;
+    PostMode pm;
+    if (!in || !wgt || !w4 || !b4 || !pts || !conf || !zero_page || !conv_operand_ok(dtype, cin_pad, cstride) || B <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || ksize <= 0) return D3R_ERR_INVALID;
+    if (pstride < 3 || conf_stride < 1 || !post_mode(pm, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
     GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, wgt, bias, cin_pad, Cout, ksize, 1, 1, zero_page);      // engine.hip conv_head4()
-    p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = conf_stride; p.res1 = w4; p.res2 = b4;
-    if (!post_mode(p.post, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
+    epi_head_tail(p, w4, b4, pts, pstride, conf, conf_stride, pm);
     GemmPlan plan;
     if (!head4_tile(p, dtype, plan)) return D3R_DECLINED;
     return rc_of(launch_gemm(dtype, p, plan, (hipStream_t)stream));
 }
 
-// x2 bilinear map of `src` + d3r_conv_head4 on it: ONE launch where the plan has it (engine.hip conv_up2_head4: the map is never stored), else the two launches of
-// today through `map`. Both built by the parameter builders the engine uses (kernels.hpp).
-static GemmParams up2_head4_capi_params(const void* src, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B, int Hi,
-                                        int Wi, int cstride, int cin_pad, int Cout, int pstride, int conf_stride, const void* zero_page) {
-    GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, wgt, bias, cin_pad, Cout, zero_page);
-    p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = conf_stride; p.res1 = w4; p.res2 = b4;
-    return p;
-}
-// the typed-store form (engine.hip conv_up2): d3r_conv2d_nhwc_x's launch without residuals or ReLU copy
-static GemmParams up2_conv_capi_params(const void* src, const void* wgt, const float* bias, void* out, int B, int Hi, int Wi, int cstride, int cin_pad, int Cout, int ldo,
-                                       int flags, const void* zero_page) {
-    GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, wgt, bias, cin_pad, Cout, zero_page);
-    p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.ldr = ldo; p.ldo2 = ldo;
-    return p;
+// x2 bilinear map of `src` + a 3x3 convolution on it: ONE launch where the plan has it (engine.hip conv_up2 / conv_up2_head4: the map is never stored), else the x2 map
+// into `map` and `conv_on_map`, the entry of the convolution alone. `p`: the AMODE_CONV_UP2 launch, built by the parameter builders the engine uses (kernels.hpp).
+template <typename ConvOnMap>
+static int up2_fused_or_two_launches(const GemmParams& p, int dtype, const void* src, void* map, int B, int Hi, int Wi, int cstride, void* stream, ConvOnMap conv_on_map) {
+    const GemmPlan plan = gemm_plan_for(p, dtype);
+    if (plan.up2) return rc_of(launch_gemm(dtype, p, plan, (hipStream_t)stream));
+    if (!map) return D3R_ERR_INVALID;
+    const int rc = rc_of(launch_upsample2x(dtype, src, map, nullptr, B, Hi, Wi, cstride, cstride, 2 * Hi, 2 * Wi, (hipStream_t)stream));
+    return rc != D3R_OK ? rc : conv_on_map();
 }
 extern "C" int d3r_up2_conv_route(int dtype, int B, int Hi, int Wi, int cstride, int cin_pad, int Cout, int head4) {
     if (!conv_dtype(dtype) || B <= 0 || Hi <= 0 || Wi <= 0 || Cout <= 0 || cin_pad <= 0 || cstride < cin_pad) return D3R_ERR_INVALID;
-    const GemmParams p = head4 ? up2_head4_capi_params(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, cstride, cin_pad, Cout, 3, 1, nullptr)
-                               : up2_conv_capi_params(nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, cstride, cin_pad, Cout, rup(Cout, 8), 0, nullptr);
+    GemmParams p = conv_up2_gemm_params(nullptr, B, Hi, Wi, cstride, nullptr, nullptr, cin_pad, Cout, nullptr);
+    if (head4) epi_head_tail(p, nullptr, nullptr, nullptr, 3, nullptr, 1, PostMode());
+    else epi_typed_store(p, nullptr, rup(Cout, 8), 0);
     return gemm_plan_for(p, dtype).up2 ? 1 : 0;
 }
 extern "C" int d3r_up2_conv2d_nhwc_x(const void* src, void* map, const void* wgt, const float* bias, void* out, int B, int Hi, int Wi, int cstride, int cin_pad, int Cout,
                                      int ldo, int flags, const void* zero_page, int dtype, void* stream) {
-    if (!src || !wgt || !out || !zero_page || !conv_dtype(dtype) || B <= 0 || Hi <= 0 || Wi <= 0 || Cout <= 0) return D3R_ERR_INVALID;
-    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || cstride < cin_pad || cstride % 8 != 0 || Cout % 4 != 0 || ldo < Cout || (flags & ~(GF_RELU | GF_NOWIDE))) return D3R_ERR_INVALID;
-    GemmParams p = up2_conv_capi_params(src, wgt, bias, out, B, Hi, Wi, cstride, cin_pad, Cout, ldo, flags, zero_page);
-    const GemmPlan plan = gemm_plan_for(p, dtype);
-    if (plan.up2) return rc_of(launch_gemm(dtype, p, plan, (hipStream_t)stream));
-    if (!map) return D3R_ERR_INVALID;
-    const int rc = rc_of(launch_upsample2x(dtype, src, map, nullptr, B, Hi, Wi, cstride, cstride, 2 * Hi, 2 * Wi, (hipStream_t)stream));
-    if (rc != D3R_OK) return rc;
-    return d3r_conv2d_nhwc_x(map, wgt, bias, out, nullptr, nullptr, nullptr, B, 2 * Hi, 2 * Wi, cstride, cin_pad, Cout, Cout, ldo, 3, 1, 1, flags, zero_page, dtype, stream);
+    if (!src || !wgt || !out || !zero_page || !conv_operand_ok(dtype, cin_pad, cstride) || B <= 0 || Hi <= 0 || Wi <= 0 || Cout <= 0) return D3R_ERR_INVALID;
+    if (cstride % 8 != 0 || Cout % 4 != 0 || ldo < Cout || (flags & ~(GF_RELU | GF_NOWIDE))) return D3R_ERR_INVALID;
+    GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, wgt, bias, cin_pad, Cout, zero_page);
+    epi_typed_store(p, out, ldo, flags);      // engine.hip conv_up2: d3r_conv2d_nhwc_x's launch without residuals or ReLU copy
+    return up2_fused_or_two_launches(p, dtype, src, map, B, Hi, Wi, cstride, stream, [&] {
+        return d3r_conv2d_nhwc_x(map, wgt, bias, out, nullptr, nullptr, nullptr, B, 2 * Hi, 2 * Wi, cstride, cin_pad, Cout, Cout, ldo, 3, 1, 1, flags, zero_page, dtype, stream);
+    });
 }
 extern "C" int d3r_up2_conv_head4(const void* src, void* map, const void* wgt, const float* bias, const float* w4, const float* b4, float* pts, float* conf, int B,
                                   int Hi, int Wi, int cstride, int cin_pad, int Cout, int pstride, int conf_stride, int depth_mode, int conf_mode, float conf_vmin,
                                   float conf_vmax, const void* zero_page, int dtype, void* stream) {
-    if (!src || !wgt || !w4 || !b4 || !pts || !conf || !zero_page || !conv_dtype(dtype) || B <= 0 || Hi <= 0 || Wi <= 0 || Cout <= 0) return D3R_ERR_INVALID;
-    if (cin_pad <= 0 || cin_pad % (128 / (int)dt_bytes(dtype)) != 0 || cstride < cin_pad || cstride % 8 != 0 || pstride < 3 || conf_stride < 1) return D3R_ERR_INVALID;
-    GemmParams p = up2_head4_capi_params(src, wgt, bias, w4, b4, pts, conf, B, Hi, Wi, cstride, cin_pad, Cout, pstride, conf_stride, zero_page);
-    if (!post_mode(p.post, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
-    const GemmPlan plan = gemm_plan_for(p, dtype);
-    if (plan.up2) return rc_of(launch_gemm(dtype, p, plan, (hipStream_t)stream));
-    if (!map) return D3R_ERR_INVALID;
-    const int rc = rc_of(launch_upsample2x(dtype, src, map, nullptr, B, Hi, Wi, cstride, cstride, 2 * Hi, 2 * Wi, (hipStream_t)stream));
-    if (rc != D3R_OK) return rc;
-    return d3r_conv_head4(map, wgt, bias, w4, b4, pts, conf, B, 2 * Hi, 2 * Wi, cstride, cin_pad, Cout, 3, pstride, conf_stride, depth_mode, conf_mode, conf_vmin, conf_vmax,
-                          zero_page, dtype, stream);
+    PostMode pm;
+    if (!src || !wgt || !w4 || !b4 || !pts || !conf || !zero_page || !conv_operand_ok(dtype, cin_pad, cstride) || B <= 0 || Hi <= 0 || Wi <= 0 || Cout <= 0) return D3R_ERR_INVALID;
+    if (cstride % 8 != 0 || pstride < 3 || conf_stride < 1 || !post_mode(pm, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
+    GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, wgt, bias, cin_pad, Cout, zero_page);
+    epi_head_tail(p, w4, b4, pts, pstride, conf, conf_stride, pm);      // engine.hip conv_up2_head4
+    return up2_fused_or_two_launches(p, dtype, src, map, B, Hi, Wi, cstride, stream, [&] {
+        return d3r_conv_head4(map, wgt, bias, w4, b4, pts, conf, B, 2 * Hi, 2 * Wi, cstride, cin_pad, Cout, 3, pstride, conf_stride, depth_mode, conf_mode, conf_vmin, conf_vmax,
+                              zero_page, dtype, stream);
+    });
 }
 
 extern "C" int d3r_head_final(const void* feat, int C, const float* w4, const float* b4, float* pts, float* conf, size_t npix, int pstride, int conf_stride,
@@ -290,7 +259,7 @@ extern "C" int d3r_build_has_probes(void) { return 0; }
 // (same `epilogue` codes as d3r_linear; with_residual: an fp32 residual is added). The dispatch table of DESIGN.md section 4.1 as a function.
 extern "C" int d3r_gemm_tile_config(int dtype, int M, int N, int K, int epilogue, int with_residual) {
     if (M <= 0 || N <= 0 || K <= 0 || N % 4 != 0) return D3R_ERR_INVALID;
-    if (dtype != D3R_BF16 && dtype != D3R_F16 && dtype != D3R_F32 && dtype != D3R_F16X3 && dtype != D3R_F16F8 && dtype != D3R_F16X2F8) return D3R_ERR_INVALID;
+    if (!gemm_dtype(dtype)) return D3R_ERR_INVALID;
     static const float dummy = 0.f;
     GemmParams p = linear_gemm_params(&dummy, K, &dummy, nullptr, M, N, K);      // (never dereferenced: the rules only ask whether the operands exist)
     p.epi = epilogue == 1 ? EPI_F32 : (epilogue == 2 ? EPI_GELU : EPI_T);

@@ -498,6 +498,7 @@ D3R_DEV float rows_sum4(float v) {
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline int rup(int a, int b) { return cdiv(a, b) * b; }
 __host__ __device__ static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline int rc_of(hipError_t e) { return e == hipSuccess ? 0 : 1000 + (int)e; }   // the C ABI's code of a HIP status (include/dust3r_hip.h: D3R_OK = 0, 1000 + hipError_t)
 static inline size_t dt_bytes(int dt) { return (dt == D3R_F32 || dt == D3R_F16X3 || dt == D3R_F16F8 || dt == D3R_F16X2F8) ? 4 : 2; }   // bytes per logical element of an ACTIVATION row

@@ -28,8 +28,6 @@ using namespace d3r;
 
 namespace {
 
-inline int rup(int a, int b) { return (a + b - 1) / b * b; }
-
 enum PackKind { PK_VEC, PK_MAT, PK_CONV, PK_CONVT, PK_CONVT_BIAS, PK_IGNORE };
 
 struct Slot {
@@ -187,7 +185,7 @@ bool reg_vec_at(d3r_model* m, const std::string& key, float* base, int off, int 
     return true;
 }
 bool alloc_lin(d3r_model* m, Lin& L, int N, int K, bool bias = true, int dt = -1) {
-    L.N = N; L.K = K; L.n_pad = rup(N, 128); L.n_rows = rup(N, 256);   // rows up to a 256-wide tile stay zero
+    L.N = N; L.K = K; L.n_pad = gemm_n_pad(N); L.n_rows = gemm_n_rows(N);
     L.dt = dt < 0 ? m->dt : dt;
     L.w = m->dalloc((size_t)L.n_rows * K * wgt_bytes(L.dt));      // 2.5-unit rows: five bytes per element
     L.b = bias ? (float*)m->dalloc((size_t)L.n_rows * sizeof(float)) : nullptr;
@@ -207,7 +205,7 @@ bool reg_ln(d3r_model* m, const std::string& prefix, LNp& p, int C) {
     return reg_vec(m, prefix + ".weight", &p.g, C) && reg_vec(m, prefix + ".bias", &p.b, C);
 }
 bool reg_conv(d3r_model* m, const std::string& prefix, ConvW& c, int Cout, int Cin, int k, bool bias) {
-    c.Cout = Cout; c.Cin = Cin; c.k = k; c.cin_pad = rup(Cin, m->ktile); c.n_pad = rup(Cout, 128); c.n_rows = rup(Cout, 256); c.K = k * k * c.cin_pad;
+    c.Cout = Cout; c.Cin = Cin; c.k = k; c.cin_pad = rup(Cin, m->ktile); c.n_pad = gemm_n_pad(Cout); c.n_rows = gemm_n_rows(Cout); c.K = k * k * c.cin_pad;
     c.w = m->dalloc((size_t)c.n_rows * c.K * dt_bytes(m->dt));
     if (!c.w) return false;
     Slot s; s.kind = PK_CONV; s.dst = c.w; s.rows = Cout; s.cin = Cin; s.cin_pad = c.cin_pad; s.ksize = k; s.dst_cols = c.K;
@@ -220,7 +218,7 @@ bool reg_conv(d3r_model* m, const std::string& prefix, ConvW& c, int Cout, int C
     return true;
 }
 bool reg_convt(d3r_model* m, const std::string& prefix, Lin& L, int Cin, int Cout, int k, int cin_pad, int cout_pad) {
-    L.N = k * k * cout_pad; L.K = cin_pad; L.n_pad = rup(L.N, 128); L.n_rows = rup(L.N, 256); L.dt = m->dt;
+    L.N = k * k * cout_pad; L.K = cin_pad; L.n_pad = gemm_n_pad(L.N); L.n_rows = gemm_n_rows(L.N); L.dt = m->dt;
     L.w = m->dalloc((size_t)L.n_rows * L.K * dt_bytes(m->dt));
     L.b = (float*)m->dalloc((size_t)L.n_rows * sizeof(float));
     if (!L.w || !L.b) return false;
@@ -366,11 +364,11 @@ int pack_slot(d3r_model* m, Slot& s, const float* data, int ndim, const int64_t*
             break;
         case PK_CONV:
             if (ndim != 4 || shape[0] != s.rows || shape[1] != s.cin || shape[2] != s.ksize || shape[3] != s.ksize) return D3R_ERR_SHAPE;
-            pp.kind = PACK_CONV; pp.cin = s.cin; pp.cin_pad = s.cin_pad; pp.ksize = s.ksize;
+            pp = conv_pack_params(data, s.dst, false, s.rows, s.cin, s.ksize, s.cin_pad, 0);
             break;
         case PK_CONVT:
             if (ndim != 4 || shape[0] != s.rows || shape[1] != s.cols || shape[2] != s.ksize || shape[3] != s.ksize) return D3R_ERR_SHAPE;
-            pp.kind = PACK_CONVT; pp.cols = s.cols; pp.ksize = s.ksize; pp.cout_pad = s.cout_pad;
+            pp = conv_pack_params(data, s.dst, true, s.cols, s.rows, s.ksize, s.cin_pad, s.cout_pad);
             break;
         case PK_CONVT_BIAS:
             if (numel != (size_t)s.rows) return D3R_ERR_SHAPE;
@@ -436,7 +434,7 @@ void launch(Ctx& c, int dt, GemmParams& p, int base, int N, int K, bool lend_sk 
 // operands of the nn.Linear `L` on M rows of `act`, with the statistics of a folded LayerNorm in front of it; the caller names epilogue, outputs, residual and flags
 GemmParams lin_params(const Lin& L, const void* act, int lda, int M, const LnStats& stats = LnStats()) {
     GemmParams p = linear_gemm_params(act, lda, L.w, L.b, M, L.N, L.K);
-    if (stats.rstd) { p.ln_rstd = stats.rstd; p.ln_nmr = stats.nmr; p.ln_colsum = L.ln_s; p.bias = L.b_fold; p.ln_part_in = stats.part_in; p.ln_inv_c = 1.0f / (float)L.K; }
+    if (stats.rstd) { p.bias = L.b_fold; ln_consumer(p, stats.rstd, stats.nmr, L.ln_s, stats.part_in, 1e-6f); }
     return p;
 }
 void gemm_linear(Ctx& c, const Lin& L, GemmParams& p) {
@@ -450,10 +448,9 @@ struct NormIn { const void* rows; LnStats stats; };
 struct Region { int kind = 0; void* dst = nullptr; };
 void gemm_heads(Ctx& c, const Lin& L, const NormIn& in, int M, int C, int heads, const SideDim& d, Region r0, Region r1 = Region(), Region r2 = Region()) {
     GemmParams p = lin_params(L, in.rows, C, M, in.stats);
-    p.epi = EPI_HEADS; p.head_c = C;
-    const Region r[3] = {r0, r1, r2};
-    for (int i = 0; i < 3; ++i) { p.head_kind[i] = r[i].kind; p.head_dst[i] = r[i].dst; }
-    p.heads = heads; p.ntok = d.N; p.tok_w = d.tw; p.ldv = d.ldv; p.rope_table = c.m->rope_table;
+    const int kinds[3] = {r0.kind, r1.kind, r2.kind};
+    void* const dsts[3] = {r0.dst, r1.dst, r2.dst};
+    epi_heads(p, C, 3, kinds, dsts, heads, d.N, d.tw, d.ldv, c.m->rope_table);
     // q | k | v whose q | k prefix the plan puts on the persistent kernel (gemm_p4.hip: its drain rotates, it has no V^T): two launches on the same rows and statistics,
     // q | k there and V -- weight rows, bias and column sums from row 2 C on -- where a [vt] launch goes. Every element is computed as in the single launch.
     if (r0.kind == HEAD_ROPE && r1.kind == HEAD_ROPE && r2.kind == HEAD_VT && L.N == 3 * C && L.dt == D3R_F16X3) {
@@ -479,7 +476,7 @@ void gemm_heads(Ctx& c, const Lin& L, const NormIn& in, int M, int C, int heads,
 void conv(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const ConvW& w, int stride, int pad, void* out, int ldo,
           int flags, const void* res1 = nullptr, const void* res2 = nullptr, void* out2 = nullptr) {
     GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, w.w, w.b, w.cin_pad, w.Cout, w.k, stride, pad, c.m->zero_page);   // K, n_pad, n_rows: reg_conv's
-    p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.res1 = res1; p.res2 = res2; p.ldr = ldo; p.out2 = out2; p.ldo2 = ldo;
+    epi_typed_store(p, out, ldo, flags, res1, res2, out2);
     launch(c, c.m->dt, p, PRF_CONV, w.Cout, w.k * w.k * w.Cin);
 }
 
@@ -488,7 +485,7 @@ void conv(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const Co
 bool conv_head4(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, const ConvW& w, const float* w4, const float* b4,
                 float* pts, float* conf, int pstride, int cstride_conf) {
     GemmParams p = conv_gemm_params(in, B, Hin, Win, cstride, w.w, w.b, w.cin_pad, w.Cout, w.k, 1, 1, c.m->zero_page);
-    p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = cstride_conf; p.res1 = w4; p.res2 = b4; p.post = c.m->post;
+    epi_head_tail(p, w4, b4, pts, pstride, conf, cstride_conf, c.m->post);
     GemmPlan plan;
     if (!head4_tile(p, c.m->dt, plan)) return false;      // 512 x 128, else the forced 256 x 128 R (kernels.hpp)
     launch(c, c.m->dt, p, PRF_CONV, w.Cout, w.k * w.k * w.Cin, false, &plan);
@@ -500,24 +497,28 @@ bool conv_head4(Ctx& c, const void* in, int B, int Hin, int Win, int cstride, co
 GemmParams up2_head4_params(const d3r_model* m, const void* src, int B, int Hi, int Wi, int cstride, const ConvW& w, const float* w4, const float* b4,
                             float* pts, float* conf, int pstride, int cstride_conf) {
     GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, w.w, w.b, w.cin_pad, w.Cout, m->zero_page);
-    p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = cstride_conf; p.res1 = w4; p.res2 = b4; p.post = m->post;
+    epi_head_tail(p, w4, b4, pts, pstride, conf, cstride_conf, m->post);
     return p;
 }
 // The typed-store form (head.0 on the x2 map of refinenet-0's output): conv() without residuals
 GemmParams up2_conv_params(const d3r_model* m, const void* src, int B, int Hi, int Wi, int cstride, const ConvW& w, void* out, int ldo, int flags) {
     GemmParams p = conv_up2_gemm_params(src, B, Hi, Wi, cstride, w.w, w.b, w.cin_pad, w.Cout, m->zero_page);
-    p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.ldr = ldo; p.ldo2 = ldo;
+    epi_typed_store(p, out, ldo, flags);
     return p;
 }
+// The head's tail (1x1 convolution + postprocess) runs in the epilogue of the last 3x3 convolution: split-fp16 engines. D3R_HEAD_FUSE=0: the two-kernel route (test A/B)
+bool head_fuse_on(const d3r_model* m) {
+    const char* e = getenv("D3R_HEAD_FUSE");
+    return m->dt == D3R_F16X3 && !(e && e[0] == '0');
+}
 // Which of the head's two x2 maps are interpolated inside the convolution that reads them. D3R_HEAD_UPFUSE=0: neither (the two-kernel routes: test A/B);
-// the last convolution's route also needs its fused tail (D3R_HEAD_FUSE).
+// the last convolution's route also needs its fused tail (head_fuse_on).
 bool up2_switch_on(const d3r_model* m) {
     const char* u = getenv("D3R_HEAD_UPFUSE");
     return m->dt == D3R_F16X3 && !(u && u[0] == '0');
 }
 bool head_upfused(const d3r_model* m, const ConvW& w, int B, int Hi, int Wi, int cstride) {      // head.2 + tail on the x2 map of head.0's output
-    const char* e = getenv("D3R_HEAD_FUSE");
-    if (!up2_switch_on(m) || w.k != 3 || (e && e[0] == '0')) return false;
+    if (!up2_switch_on(m) || w.k != 3 || !head_fuse_on(m)) return false;
     return gemm_plan_for(up2_head4_params(m, nullptr, B, Hi, Wi, cstride, w, nullptr, nullptr, nullptr, nullptr, 3, 1), m->dt).up2;
 }
 bool head0_upfused(const d3r_model* m, const ConvW& w, int B, int Hi, int Wi, int cstride, int ldo) {      // head.0 on the x2 map of refinenet-0's output
@@ -702,11 +703,11 @@ extern "C" int d3r_model_set_option(d3r_model* m, int option, int value) {
 
 // depth_mode / conf_mode of the heads' postprocess (dust3r/heads/postprocess.py:23-58; model.py:58-62 constructor keywords)
 extern "C" int d3r_model_set_postprocess(d3r_model* m, int depth_mode, int conf_mode, float conf_vmin, float conf_vmax) {
-    if (!m || depth_mode < POST_DEPTH_EXP || depth_mode > POST_DEPTH_SQUARE || conf_mode < POST_CONF_EXP || conf_mode > POST_CONF_SIGMOID) return D3R_ERR_INVALID;
-    if (!(conf_vmin < conf_vmax) || (conf_mode == POST_CONF_SIGMOID && !(conf_vmax < __builtin_huge_valf() && conf_vmin > -__builtin_huge_valf()))) return D3R_ERR_INVALID;
+    PostMode pm;
+    if (!m || !post_mode(pm, depth_mode, conf_mode, conf_vmin, conf_vmax)) return D3R_ERR_INVALID;
     hipDeviceSynchronize();     // a captured graph carries the old mode in its kernel arguments
     m->drop_graphs();
-    m->post.depth = depth_mode; m->post.conf = conf_mode; m->post.cmin = conf_vmin; m->post.cmax = conf_vmax;
+    m->post = pm;
     return D3R_OK;
 }
 
@@ -876,10 +877,8 @@ NormIn norm_in(Ctx& c, const Res& r, const LNp& ln, void* scratch, int C) {
 void residual_linear(Ctx& c, const Lin& L, const void* act, int lda, const Res& in, const Res& out, int C, bool typed_copy = false) {
     const bool fold = c.m->ln_fold;
     GemmParams p = lin_params(L, act, lda, out.M);
-    p.epi = EPI_F32; p.ldo = C;
-    if (fold) { p.flags = GF_X3RES; p.res1 = in.raw; p.ln_part = out.part; }
-    else { p.out = out.f32; p.res1 = in.f32; }
-    if (fold || typed_copy) { p.out2 = out.raw; p.ldo2 = C; }
+    if (fold) epi_typed_residual(p, in.raw, out.raw, C, out.part);
+    else { p.epi = EPI_F32; p.ldo = C; p.out = out.f32; p.res1 = in.f32; if (typed_copy) { p.out2 = out.raw; p.ldo2 = C; } }
     gemm_linear(c, L, p);
     if (fold && out.part && !out.inl) D3R_OTHER(launch_ln_finalize(out.part, out.M, C, 1e-6f, out.rs, out.nm, c.st));
 }
@@ -916,7 +915,7 @@ void run_dpt(Ctx& c, const DptHead& D, Arena ar, const Call& k, const void* cons
         if (i < 2) {
             const int ldi[2] = {96, 192}, kk = D.convt_k[i] * D.convt_k[i];
             GemmParams p = lin_params(D.convt[i], b.t1, D.cstride[i], B * th * tw);
-            p.epi = EPI_CONVT; p.ksize = D.convt_k[i]; p.ct_cout = D.convt_coutp[i]; p.Hin = th; p.Win = tw; p.out = b.cmap[i]; p.ldo = D.cstride[i];
+            epi_convt(p, D.convt_k[i], D.convt_coutp[i], th, tw, b.cmap[i], D.cstride[i]);
             launch(c, m->dt, p, PRF_CONV, kk * ldi[i], ldi[i]);
         } else if (i == 3) {
             conv(c, b.t1, B, th, tw, D.cstride[3], D.act3conv, 2, 1, b.cmap[3], D.cstride[3], 0);
@@ -953,9 +952,8 @@ void run_dpt(Ctx& c, const DptHead& D, Arena ar, const Call& k, const void* cons
     D3R_OTHER(launch_upsample2x(m->dt, b.h0, b.h1, nullptr, B, H8, W8, 128, 128, 2 * H8, 2 * W8, c.st));
     // Split-fp16, enough pixels for the 512 x 128 tile (every wave then holds all 128 channels of its 64 pixels): the 1x1 convolution and
     // the postprocess run in the epilogue of the last 3x3 convolution, on its fp32 accumulators -- the 128-channel full-resolution map
-    // (3.2 GB per head at 32 pairs) is neither written nor read back. D3R_HEAD_FUSE=0: the two-kernel route (test A/B).
-    const char* e = m->dt == D3R_F16X3 ? getenv("D3R_HEAD_FUSE") : "0";
-    if (!(e && e[0] == '0') && conv_head4(c, b.h1, B, 2 * H8, 2 * W8, 128, D.head2, D.head4_w, D.head4_b, pts, conf, k.pstride, k.cstride)) return;
+    // (3.2 GB per head at 32 pairs) is neither written nor read back.
+    if (head_fuse_on(m) && conv_head4(c, b.h1, B, 2 * H8, 2 * W8, 128, D.head2, D.head4_w, D.head4_b, pts, conf, k.pstride, k.cstride)) return;
     conv(c, b.h1, B, 2 * H8, 2 * W8, 128, D.head2, 1, 1, b.h2, 128, GF_RELU);
     D3R_OTHER(launch_head_final(m->dt, b.h2, 128, D.head4_w, D.head4_b, pts, conf, (size_t)B * 4 * H8 * W8, k.pstride, k.cstride, m->post, c.st));
 }

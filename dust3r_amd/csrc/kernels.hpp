@@ -86,12 +86,26 @@ hipError_t launch_gemm(int dt, const GemmParams& p, hipStream_t s);
 // the same launch on a plan the caller already took from gemm_plan_for (the engine marks its profile with plan.cfg, then launches)
 hipError_t launch_gemm(int dt, const GemmParams& p, const GemmPlan& plan, hipStream_t s);
 
-// nn.Linear-shaped operands [M][lda] x [N][K]^T: weight rows as the loader allocates them (engine.hip Lin: n_pad = round_up(N, 128), round_up(N, 256) rows).
-// The caller adds the epilogue.
+// The weight rows of an N-column GEMM as the loader allocates them: N rounded up to the 128-column tile is computed, rows up to a 256-wide tile exist and stay zero
+inline int gemm_n_pad(int N) { return rup(N, 128); }
+inline int gemm_n_rows(int N) { return rup(N, 256); }
+// the operand types of the GEMM entries, of the implicit-GEMM convolution entries, and the channel rows a convolution reads: whole K steps per tap, inside a pixel's row
+inline bool gemm_dtype(int dt) { return dt == D3R_BF16 || dt == D3R_F16 || dt == D3R_F32 || dt == D3R_F16X3 || dt == D3R_F16F8 || dt == D3R_F16X2F8; }
+inline bool conv_dtype(int dt) { return dt == D3R_BF16 || dt == D3R_F16 || dt == D3R_F32 || dt == D3R_F16X3; }
+inline bool conv_operand_ok(int dt, int cin_pad, int cstride) { return conv_dtype(dt) && cin_pad > 0 && cin_pad % (128 / (int)dt_bytes(dt)) == 0 && cstride >= cin_pad; }
+// depth_mode / conf_mode of the heads' postprocess as d3r_model_set_postprocess and the kernel entries accept them
+inline bool post_mode(PostMode& pm, int depth_mode, int conf_mode, float vmin, float vmax) {
+    if (depth_mode < POST_DEPTH_EXP || depth_mode > POST_DEPTH_SQUARE || conf_mode < POST_CONF_EXP || conf_mode > POST_CONF_SIGMOID) return false;
+    if (!(vmin < vmax) || (conf_mode == POST_CONF_SIGMOID && !(vmax < __builtin_huge_valf() && vmin > -__builtin_huge_valf()))) return false;
+    pm.depth = depth_mode; pm.conf = conf_mode; pm.cmin = vmin; pm.cmax = vmax;
+    return true;
+}
+
+// nn.Linear-shaped operands [M][lda] x [N][K]^T: weight rows as the loader allocates them (engine.hip Lin). The caller adds the epilogue (the epi_* builders below).
 inline GemmParams linear_gemm_params(const void* act, int lda, const void* wgt, const float* bias, int M, int N, int K) {
     GemmParams p;
     p.act = act; p.lda = lda; p.wgt = wgt; p.bias = bias; p.M = M; p.K = K;
-    p.n_pad = (N + 127) / 128 * 128; p.n_rows = (N + 255) / 256 * 256; p.n_store = N;
+    p.n_pad = gemm_n_pad(N); p.n_rows = gemm_n_rows(N); p.n_store = N;
     return p;
 }
 
@@ -105,7 +119,7 @@ inline GemmParams conv_gemm_params(const void* in, int B, int Hin, int Win, int 
     p.amode = AMODE_CONV; p.act = in; p.wgt = wgt; p.bias = bias;
     p.Hin = Hin; p.Win = Win; p.Cin = cin_pad; p.cstride = cstride; p.ksize = k; p.stride = stride; p.pad = pad;
     p.Hout = (Hin + 2 * pad - k) / stride + 1; p.Wout = (Win + 2 * pad - k) / stride + 1;
-    p.M = B * p.Hout * p.Wout; p.K = k * k * cin_pad; p.n_pad = (Cout + 127) / 128 * 128; p.n_rows = (Cout + 255) / 256 * 256; p.n_store = Cout;
+    p.M = B * p.Hout * p.Wout; p.K = k * k * cin_pad; p.n_pad = gemm_n_pad(Cout); p.n_rows = gemm_n_rows(Cout); p.n_store = Cout;
     p.zero_page = zero_page;
     return p;
 }
@@ -130,6 +144,34 @@ inline bool head4_tile(GemmParams& p, int dt, GemmPlan& plan) {
         plan = gemm_plan_for(p, dt);
     }
     return plan.cfg == GEMM_CFG_512x128 || plan.cfg == GEMM_CFG_256x128R;
+}
+
+// The epilogue half of a launch, one builder per kind, on top of the operand builders above: the ONLY places that know which GemmParams fields an epilogue reads and
+// reuses. The engine (engine.hip) and the kernel-level C ABI (capi.hip) both launch what these fill.
+// typed store (EPI_T): bias, ReLU (flags), up to two residual maps and a ReLU copy, all with the output's row stride
+inline void epi_typed_store(GemmParams& p, void* out, int ldo, int flags, const void* res1 = nullptr, const void* res2 = nullptr, void* relu_copy = nullptr) {
+    p.epi = EPI_T; p.flags = flags; p.out = out; p.ldo = ldo; p.res1 = res1; p.res2 = res2; p.ldr = ldo; p.out2 = relu_copy; p.ldo2 = ldo;
+}
+// the DPT head's tail (EPI_HEAD4, the field reuse stated at the enum): ReLU, the 1x1 convolution w4 / b4, postprocess, pts / conf at their pixel strides
+inline void epi_head_tail(GemmParams& p, const float* w4, const float* b4, float* pts, int pstride, float* conf, int conf_stride, const PostMode& post) {
+    p.epi = EPI_HEAD4; p.flags = GF_RELU; p.out = pts; p.ldo = pstride; p.out2 = conf; p.ldo2 = conf_stride; p.res1 = w4; p.res2 = b4; p.post = post;
+}
+// ConvTranspose2d(k, stride k) as a GEMM over the th x tw token grid (EPI_CONVT): N = k k cout_pad columns scattered to the k k pixels of every token
+inline void epi_convt(GemmParams& p, int k, int cout_pad, int th, int tw, void* out, int ldo) {
+    p.epi = EPI_CONVT; p.ksize = k; p.ct_cout = cout_pad; p.Hin = th; p.Win = tw; p.out = out; p.ldo = ldo;
+}
+// typed residual stream (EPI_F32 with GF_X3RES): out_rows = split-fp16 rows of (acc + bias + res_rows), every row `ld` elements apart; ln_part: GemmParams::ln_part or null
+inline void epi_typed_residual(GemmParams& p, const void* res_rows, void* out_rows, int ld, float* ln_part) {
+    p.epi = EPI_F32; p.flags = GF_X3RES; p.ldo = ld; p.res1 = res_rows; p.ldr = ld; p.out2 = out_rows; p.ldo2 = ld; p.ln_part = ln_part;
+}
+// consumer of a folded LayerNorm over the K columns of its input rows (any epilogue; p.bias is the folded bias): GemmParams::ln_rstd ... ln_part_in
+inline void ln_consumer(GemmParams& p, const float* rstd, const float* nmr, const float* colsum, const float* part_in, float eps) {
+    p.ln_rstd = rstd; p.ln_nmr = nmr; p.ln_colsum = colsum; p.ln_part_in = part_in; p.ln_eps = eps; p.ln_inv_c = 1.0f / (float)p.K;
+}
+// head scatter (EPI_HEADS): n_regions (<= 3) regions of head_c columns, region r stored as kinds[r] at dsts[r] (dsts null: a host query of the plan)
+inline void epi_heads(GemmParams& p, int head_c, int n_regions, const int* kinds, void* const* dsts, int heads, int ntok, int tok_w, int ldv, const float* rope_table) {
+    p.epi = EPI_HEADS; p.head_c = head_c; p.heads = heads; p.ntok = ntok; p.tok_w = tok_w; p.ldv = ldv; p.rope_table = rope_table;
+    for (int r = 0; r < n_regions; ++r) { p.head_kind[r] = kinds[r]; p.head_dst[r] = dsts ? dsts[r] : nullptr; }
 }
 
 // ------------------------------------------------------------------------------ attention
@@ -184,6 +226,15 @@ struct PackParams {
     const float* kscale = nullptr;   // PACK_MAT: multiply column k of the source by kscale[k] before the conversion (LayerNorm gamma folded into the weights)
 };
 hipError_t launch_pack_weight(int dt, const PackParams& p, hipStream_t s);
+// A Conv2d weight [Cout][Cin][k][k] into rows of k k cin_pad (PACK_CONV), or a ConvTranspose2d weight [Cin][Cout][k][k] into the GEMM matrix of cin_pad columns
+// whose N = k k cout_pad rows EPI_CONVT scatters (PACK_CONVT)
+inline PackParams conv_pack_params(const float* src, void* dst, bool transposed, int Cout, int Cin, int k, int cin_pad, int cout_pad) {
+    PackParams pp;
+    pp.src = src; pp.dst = dst; pp.numel = (size_t)Cout * Cin * k * k; pp.ksize = k;
+    if (transposed) { pp.kind = PACK_CONVT; pp.cols = Cout; pp.cout_pad = cout_pad; pp.dst_cols = cin_pad; }
+    else { pp.kind = PACK_CONV; pp.cin = Cin; pp.cin_pad = cin_pad; pp.dst_cols = k * k * cin_pad; }
+    return pp;
+}
 // The load-time fold of ONE nn.Linear behind a LayerNorm, built in one place (engine.hip) for the engine (finalize_fold) and for the kernel-level C ABI
 // (capi.hip d3r_ln_fold_pack): W [N][K] fp32 packed as W diag(gamma) into the rows of `dst` (PACK_MAT with kscale = gamma; K columns per row, padding rows
 // zeroed by the caller), then launch_ln_fold_vectors.

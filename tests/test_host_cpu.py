@@ -21,6 +21,52 @@ def test_library_exports_every_declared_symbol():
     assert b'gfx950' in _lib.lib.d3r_version()
 
 
+def test_ctypes_signatures_are_read_from_the_header():
+    """_lib.parse_header on one of each construct include/dust3r_hip.h uses, and the derived signature of a real entry refusing a wrong scalar kind."""
+    from dust3r_amd import _lib
+    vp, i, f = C.c_void_p, C.c_int, C.c_float
+    sig = _lib.parse_header('''
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define D3R_MULTI 1 /* a comment that runs over
+                               two lines (with a parenthesis; and a semicolon) */
+        typedef struct d3r_model d3r_model;
+        typedef struct d3r_view_plan { const void* rgb; float pose[12]; } d3r_view_plan;
+        /* d3r_commented_out(int a); is no prototype */
+        int d3r_multi_line(const void* act, const float* bias,   // trailing (comment);
+                           int M, float eps,
+                           void* stream);
+        int d3r_no_args(void);
+        int d3r_pointers(const float* const* rows, void* const* dsts, d3r_model** out, const int64_t* shape, int ndim);
+        int d3r_array(const float box[6], int thresholds[], unsigned long long seed, double p);
+        int d3r_struct(int n, const d3r_view_plan* plans, const d3r_model* m);
+        size_t d3r_bytes(int n, long long count, uint32_t colour);
+        const char* d3r_name(void);
+        void d3r_nothing(int* a);
+        #ifdef __cplusplus
+        }
+        #endif
+    ''')
+    assert sig == {'d3r_multi_line': (i, [vp, vp, i, f, vp]),
+                   'd3r_no_args': (i, []),
+                   'd3r_pointers': (i, [vp, vp, vp, vp, i]),
+                   'd3r_array': (i, [vp, vp, C.c_ulonglong, C.c_double]),
+                   'd3r_struct': (i, [i, C.POINTER(_lib.ViewPlan), vp]),
+                   'd3r_bytes': (C.c_size_t, [i, C.c_longlong, C.c_uint32]),
+                   'd3r_name': (C.c_char_p, []),
+                   'd3r_nothing': (None, [vp])}
+    with pytest.raises(ImportError, match='d3r_bad'):
+        _lib.parse_header('int d3r_bad(int a, flaot b);')
+    with pytest.raises(ImportError, match='d3r_worse'):
+        _lib.parse_header('int d3r_worse(int (*callback)(int));')
+    # the library's own table: every export has a signature, and a float where the header says int is an error, not a reinterpreted register
+    assert set(_lib.EXPORTED) == set(_lib.parse_header(open(os.path.join(ROOT, 'include', 'dust3r_hip.h')).read()))
+    assert _lib.lib.d3r_gemm_tile_config(_lib.DTYPE_F16X3, 256, 256, 256, 0, 0) >= 0
+    with pytest.raises(C.ArgumentError):
+        _lib.lib.d3r_gemm_tile_config(_lib.DTYPE_F16X3, 256.0, 256, 256, 0, 0)
+
+
 def test_product_fails_loudly_without_gpu():
     from dust3r_amd import _lib
     if torch.cuda.is_available():
