@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['gemm.hip', 'gemm_p4.hip', 'gemm_p4_heads.hip', 'gemm_up2.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'sky.hip', 'visloc.hip', 'mesh.hip', 'fuse.hip', 'cloud_nn.hip', 'cloud_knn.hip', 'cloud_icp.hip', 'cloud_cluster.hip', 'cloud_features.hip', 'tracks.hip', 'gallery.hip', 'render.hip', 'losses.hip', 'views.hip', 'engine.hip', 'capi.hip']
+SOURCES = ['gemm.hip', 'gemm_p4.hip', 'gemm_p4_heads.hip', 'gemm_up2.hip', 'attention.hip', 'elementwise.hip', 'aligner.hip', 'bootstrap.hip', 'sky.hip', 'visloc.hip', 'mesh.hip', 'fuse.hip', 'cloud_nn.hip', 'cloud_knn.hip', 'cloud_icp.hip', 'cloud_cluster.hip', 'cloud_features.hip', 'cloud_planes.hip', 'tracks.hip', 'gallery.hip', 'render.hip', 'losses.hip', 'views.hip', 'engine.hip', 'capi.hip']
 HEADERS = ['common.hpp', 'reduce.hpp', 'scene_common.hpp', 'kernels.hpp', 'gemm_plan.hpp', 'gemm_p4.hpp', 'gemm_head4.hpp', 'aligner_math.hpp', 'visloc_math.hpp', 'ransac.hpp', 'views_math.hpp', 'gallery_math.hpp', 'fuse_grid.hpp', 'cloud_grid.hpp', os.path.join('..', '..', 'include', 'dust3r_hip.h')]
 LIB = os.path.join(CSRC, 'libdust3r_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-inline-asm']
@@ -27,6 +27,7 @@ EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'gemm_p4.hip': ['-fno-sl
                'cloud_icp.hip': ['-Rpass-analysis=kernel-resource-usage', '-ffp-contract=off'],    # cloud_icp.hip: same for the registration's transform and sums; its fp64 terms round as numpy's do
                'cloud_cluster.hip': ['-Rpass-analysis=kernel-resource-usage', '-ffp-contract=off'],    # cloud_cluster.hip: same for the density clustering's walks and its union-find
                'cloud_features.hip': ['-Rpass-analysis=kernel-resource-usage', '-ffp-contract=off'],   # cloud_features.hip: same for the global registration's descriptors, matching and RANSAC
+               'cloud_planes.hip': ['-Rpass-analysis=kernel-resource-usage', '-ffp-contract=off'],     # cloud_planes.hip: same for the plane RANSAC and the support's moments
                'tracks.hip': ['-Rpass-analysis=kernel-resource-usage', '-ffp-contract=off'],       # tracks.hip: same for the 2-D tracks; its fp64 projection and fp32 distances round as numpy's do
                'gallery.hip': ['-Rpass-analysis=kernel-resource-usage', '-ffp-contract=off'],      # gallery.hip: same for the demo's gallery; its product and sum round separately, as numpy's do
                'render.hip': ['-Rpass-analysis=kernel-resource-usage'],       # render.hip: same for the rasteriser

@@ -35,7 +35,14 @@ order (DESIGN.md, 4.16); viz.FusedCloud.cluster / keep_clusters and scene.fuse(c
 The similarity `register_clouds` starts from, when nobody has one: `grid_subsample` at a cell relative to each cloud's
 own size, FPFH descriptors of the k nearest neighbours (`spfh_counts`, `fpfh_features`), exhaustive mutual matching in 33 dimensions
 (`feature_nearest`, `match_features`) and a Sim(3) RANSAC over the matches (`sim3_ransac`); `register_clouds(..., init='global')` chains
-the two."""
+the two.
+
+    res = detect_planes(cloud, thr)                         # planes, their sizes, a plane label per point: csrc/cloud_planes.hip
+
+Where the floor is, where the walls are, which way is up: a plane RANSAC over ALL points of the cloud (`plane_ransac`),
+refits on the fp64 moments of the inliers (`plane_support`, `plane_from_moments`; together `segment_plane`), sequential extraction
+(`detect_planes`), and on the host the ground among the planes and the motion that stands the scene on it (`ground_plane`,
+`upright_similarity`); viz.FusedCloud.detect_planes / remove_planes / upright and scene.fuse(planes=..., upright=...) are built of it."""
 import collections
 import ctypes as C
 import math
@@ -1036,3 +1043,294 @@ def global_registration(src, dst, src_normals=None, dst_normals=None, cell=None,
 def _as_cloud(cloud, device):
     """a FusedCloud as it is (its normals and positions are read by name), anything else as device points"""
     return cloud if hasattr(cloud, 'positions') else _points(cloud, device, 'cloud')
+
+
+# ---- planes: RANSAC on the whole cloud, refit on the moments of the inliers, sequential extraction (DESIGN.md, 4.18) ------------------------
+MAX_HYPOTHESES_PLANE = MAX_HYPOTHESES       # D3R_SIM3_MAX_HYPOTHESES bounds the plane RANSAC too
+PLANE_MOMENTS = 9
+Plane = collections.namedtuple('Plane', 'model inliers count rms')
+Planes = collections.namedtuple('Planes', 'planes plane_sizes plane_labels')
+
+
+def _plane_args(thr, n_hyp=1, cos_min=None, min_area2=None, min_inliers=3):
+    """(thr, n_hyp, cos_min, min_area2, min_inliers) as the device calls take them; ValueError for what d3r_plane_ransac would refuse.
+    min_area2 = None: (8 thr)^2 -- twice the area of a right triangle with legs of 8 thr: a sample whose points err by thr then tilts its
+    plane by about thr / (8 thr), 7 degrees, at the most, and the refit takes it from there."""
+    if isinstance(n_hyp, bool) or not isinstance(n_hyp, (int, np.integer)) or not 1 <= n_hyp <= MAX_HYPOTHESES_PLANE:
+        raise ValueError(f'n_hyp = {n_hyp!r} must be an int in [1, {MAX_HYPOTHESES_PLANE}]')
+    with np.errstate(over='ignore'):
+        t = np.float32(thr)
+    if not (t > 0 and np.isfinite(t)):
+        raise ValueError(f'thr = {thr!r} must be a positive finite float32')
+    cos_min = 0.0 if cos_min is None else float(np.float32(cos_min))
+    if math.isnan(cos_min):
+        raise ValueError('cos_min is NaN')
+    min_area2 = (8.0 * float(t)) ** 2 if min_area2 is None else float(min_area2)
+    if not min_area2 > 0:
+        raise ValueError(f'min_area2 = {min_area2!r} must be > 0')
+    if isinstance(min_inliers, bool) or not isinstance(min_inliers, (int, np.integer)) or not 3 <= min_inliers < 2 ** 31:
+        raise ValueError(f'min_inliers = {min_inliers!r} must be an int >= 3')
+    return float(t), int(n_hyp), cos_min, min_area2, int(min_inliers)
+
+
+def _plane_cloud(points, normals, device, what):
+    P = _points(points, device, what)
+    N = None if normals is None else _points(normals, device, 'normals')
+    if N is not None and len(N) != len(P):
+        raise ValueError(f'{what}: {len(P)} points, {len(N)} normals')
+    return P, N
+
+
+@torch.no_grad()
+def plane_ransac(points, thr, n_hyp=4096, normals=None, cos_min=None, min_area2=None, min_inliers=3, seed=0):
+    """(best (7,) float64, inliers (n,) uint8) device tensors of d3r_plane_ransac over the points ((n, 3) float32, n >= 3): best = (h or
+    -1, inlier count, valid hypotheses, n_x, n_y, n_z, d). Hypothesis h: three points drawn by (seed, h), the plane through them in fp64,
+    rejected unless twice the triangle's area is >= min_area2 (default (8 thr)^2); scored in fp32 as |n . x + d| <= thr and, with normals
+    (n, 3), |n . normal| >= cos_min (default 0: then the normals only exclude the points that have none); the largest count wins, then
+    the lowest h; -1 unless that count >= min_inliers. n_hyp is fixed (no adaptive stopping); the same seed gives the same bytes. No
+    synchronisation."""
+    thr, n_hyp, cos_min, min_area2, min_inliers = _plane_args(thr, n_hyp, cos_min, min_area2, min_inliers)
+    _lib.require_device()
+    device = _device_of(points)
+    P, N = _plane_cloud(points, normals, device, 'plane_ransac')
+    n = len(P)
+    if n < 3:
+        raise ValueError(f'plane_ransac: {n} points; at least 3')
+    best = torch.zeros((7,), dtype=torch.float64, device=device)
+    inliers = torch.zeros((n,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        work = _lib.workspace(lib.d3r_plane_ransac_workspace_bytes(n, n_hyp), device)
+        check(lib.d3r_plane_ransac(n, ptr(P), ptr(N), int(seed) & (2 ** 64 - 1), n_hyp, thr, cos_min, min_area2, min_inliers, ptr(best), ptr(inliers),
+                                   ptr(work), current_stream()), 'plane_ransac')
+    return best, inliers
+
+
+@torch.no_grad()
+def plane_support(points, plane, thr, centre, normals=None, cos_min=None, want_mask=True):
+    """d3r_plane_support on device tensors: (count (1,) int64, sums (9,) float64, mask (n,) uint8 or None) of the inliers of `plane`
+    (4,), taken as float32: the inlier test of `plane_ransac`, and the fp64 moments of the inliers about `centre` (3,) float32 -- sum a
+    and the upper triangle of sum a a^T, a = p - centre. One launch pair, no synchronisation."""
+    thr, _, cos_min, _, _ = _plane_args(thr, cos_min=cos_min)
+    m = [float(v) for v in np.asarray(plane, np.float64).astype(np.float32).reshape(4)]
+    c = [float(v) for v in np.asarray(centre, np.float64).astype(np.float32).reshape(3)]
+    if not np.isfinite(m + c).all():
+        raise ValueError(f'plane_support: plane {m} and centre {c} must be finite in float32')
+    _lib.require_device()
+    device = _device_of(points)
+    P, N = _plane_cloud(points, normals, device, 'plane_support')
+    n = len(P)
+    count = torch.zeros((1,), dtype=torch.int64, device=device)
+    sums = torch.zeros((PLANE_MOMENTS,), dtype=torch.float64, device=device)
+    mask = torch.zeros((n,), dtype=torch.uint8, device=device) if want_mask else None
+    if n > 0:
+        with torch.cuda.device(device):
+            work = _lib.workspace(lib.d3r_plane_support_workspace_bytes(n), device)
+            check(lib.d3r_plane_support(n, ptr(P), ptr(N), (C.c_float * 4)(*m), thr, cos_min, (C.c_float * 3)(*c), ptr(mask), ptr(count), ptr(sums),
+                                        ptr(work), current_stream()), 'plane_support')
+    return count, sums, mask
+
+
+def moments_covariance(count, sums):
+    """(mean of a (3,), covariance (3, 3)) in fp64 of `count` points from their 9 moments about a centre (`plane_support`)"""
+    s = np.asarray(sums, np.float64)
+    mean = s[:3] / count
+    second = np.array([[s[3], s[4], s[5]], [s[4], s[6], s[7]], [s[5], s[7], s[8]]]) / count
+    return mean, second - np.outer(mean, mean)
+
+
+def plane_from_moments(count, sums, centre):
+    """The least-squares plane (4,) float64 = (n, d) of `count` points given their 9 moments about `centre` (`plane_support`): through the
+    centroid, n the unit eigenvector of the covariance's smallest eigenvalue (np.linalg.eigh), signed so that its component of largest
+    magnitude is positive, d = -n . centroid. None for fewer than 3 points or moments that are not finite. Host fp64."""
+    if count < 3 or not np.isfinite(np.asarray(sums, np.float64)).all():
+        return None
+    mean, cov = moments_covariance(count, sums)
+    _, vec = np.linalg.eigh(cov)
+    n = vec[:, 0] / np.linalg.norm(vec[:, 0])
+    if n[int(np.argmax(np.abs(n)))] < 0:
+        n = -n
+    centroid = np.asarray(centre, np.float64) + mean
+    return np.array([n[0], n[1], n[2], -float(n @ centroid)])
+
+
+def plane_rms(model, count, sums, centre):
+    """sqrt(mean e^2), e = n . p + d, over the `count` points whose 9 moments about `centre` are `sums`: from the moments, no pass over
+    the points. sum e^2 = n^T (sum a a^T) n + 2 k n . (sum a) + count k^2 with k = n . centre + d."""
+    if count <= 0:
+        return float('nan')
+    s = np.asarray(sums, np.float64)
+    n, d = np.asarray(model, np.float64)[:3], float(model[3])
+    A = np.array([[s[3], s[4], s[5]], [s[4], s[6], s[7]], [s[5], s[7], s[8]]])
+    k = float(n @ np.asarray(centre, np.float64)) + d
+    return math.sqrt(max(float(n @ A @ n) + 2.0 * k * float(n @ s[:3]) + count * k * k, 0.0) / count)
+
+
+def plane_centre(model):
+    """(3,) float32: the point of the plane nearest the origin, -d n: the centre the refit's moments are taken about"""
+    m = np.asarray(model, np.float64)
+    return (-m[3] * m[:3]).astype(np.float32)
+
+
+def _segment(P, N, thr, n_hyp, cos_min, min_area2, min_inliers, seed, refine_rounds):
+    """segment_plane on device tensors: (model, mask uint8 device tensor, count, rms) or None"""
+    best, _ = plane_ransac(P, thr, n_hyp, N, cos_min, min_area2, min_inliers, seed)
+    best = best.cpu().numpy()
+    if best[0] < 0:
+        return None
+    model = best[3:7].copy()
+    centre = plane_centre(model)
+    previous = None
+    for r in range(refine_rounds + 1):
+        count_d, sums_d, mask = plane_support(P, model, thr, centre, N, cos_min)
+        packed = torch.cat([count_d.double(), sums_d]).cpu().numpy()      # the round's one read-back: ten numbers
+        count, sums = int(packed[0]), packed[1:]
+        if r == refine_rounds or count == previous:
+            break
+        refit = plane_from_moments(count, sums, centre)
+        if refit is None or not np.isfinite(refit.astype(np.float32)).all():
+            break
+        model, previous = refit, count
+    return model, mask, count, plane_rms(model, count, sums, centre)
+
+
+def _plane_normals(cloud, normals, cos_min, device):
+    """the normals of the inlier test: those given; else, when cos_min is given, the cloud's own"""
+    if normals is not None:
+        return normals
+    if cos_min is None:
+        return None
+    own = _normals_of(cloud, device)
+    if own is None:
+        raise ValueError('cos_min needs normals: give them, or a cloud that has them (estimate_normals)')
+    return own
+
+
+def _rounds(refine_rounds):
+    if isinstance(refine_rounds, bool) or not isinstance(refine_rounds, (int, np.integer)) or refine_rounds < 0:
+        raise ValueError(f'refine_rounds = {refine_rounds!r} must be an int >= 0')
+    return int(refine_rounds)
+
+
+@torch.no_grad()
+def segment_plane(cloud, thr, n_hyp=4096, normals=None, cos_min=None, min_area2=None, min_inliers=3, seed=0, refine_rounds=3, to_host=True):
+    """The dominant plane of a cloud ((N, 3) points or a FusedCloud) on the GPU: a `Plane`(model (4,) float64 = (n, d), inliers (N,) bool,
+    count, rms), or None when no hypothesis has min_inliers inliers. 1. `plane_ransac`. 2. At most refine_rounds refits: `plane_support`
+    of the current model (as float32) gives its mask, count and moments about `plane_centre` of the RANSAC plane in one launch and one
+    read-back of ten numbers; `plane_from_moments` of them is the next model. It stops early when the count equals the previous round's.
+    The model returned is the last one whose mask was taken: inliers, count and rms (`plane_rms`, from the same moments) are its own.
+    normals / cos_min: as `plane_ransac`; with cos_min and no normals the cloud's own are used. The mask comes back on the host unless
+    to_host=False."""
+    args = _plane_args(thr, n_hyp, cos_min, min_area2, min_inliers)
+    refine_rounds = _rounds(refine_rounds)
+    _lib.require_device()
+    device = _device_of(cloud)
+    with torch.cuda.device(device):
+        P, N = _plane_cloud(cloud, _plane_normals(cloud, normals, cos_min, device), device, 'segment_plane')
+        if len(P) < 3:
+            return None
+        res = _segment(P, N, args[0], args[1], None if N is None else args[2], args[3], args[4], seed, refine_rounds)
+    if res is None:
+        return None
+    model, mask, count, rms = res
+    mask = mask.bool()
+    return Plane(model, mask.cpu().numpy() if to_host else mask, count, rms)
+
+
+def default_plane_min_inliers(n):
+    """the support below which `detect_planes` stops: 2 % of the cloud, at least 3 -- a floor or a wall of a scene holds far more, and a
+    plane through fewer points is found in any clutter"""
+    return max(3, int(math.ceil(0.02 * n)))
+
+
+@torch.no_grad()
+def detect_planes(cloud, thr, max_planes=6, min_inliers=None, n_hyp=4096, normals=None, cos_min=None, min_area2=None, seed=0, refine_rounds=3,
+                  to_host=True):
+    """The planes of a cloud by sequential extraction on the GPU: `Planes`(planes (P, 4) float64, plane_sizes (P,) int32, plane_labels (N,)
+    int32, -1 = no plane), in extraction order. Round r runs `segment_plane` with seed + r on the points no earlier plane took -- they are
+    neither sampled nor scored: a boolean compaction on the device keeps the map back to the rows -- and stops at max_planes, when fewer
+    than 3 points are left, or at the first round without a plane of min_inliers points (default `default_plane_min_inliers` of the whole
+    cloud), before or after the refit. Sizes and labels come back on the host unless to_host=False."""
+    if isinstance(max_planes, bool) or not isinstance(max_planes, (int, np.integer)) or max_planes < 0:
+        raise ValueError(f'max_planes = {max_planes!r} must be an int >= 0')
+    refine_rounds = _rounds(refine_rounds)
+    n_all = len(getattr(cloud, 'positions', cloud))
+    args = _plane_args(thr, n_hyp, cos_min, min_area2, default_plane_min_inliers(n_all) if min_inliers is None else min_inliers)
+    _lib.require_device()
+    device = _device_of(cloud)
+    with torch.cuda.device(device):
+        P, N = _plane_cloud(cloud, _plane_normals(cloud, normals, cos_min, device), device, 'detect_planes')
+        labels = torch.full((len(P),), -1, dtype=torch.int32, device=device)
+        rows = torch.arange(len(P), device=device)
+        planes, sizes = [], []
+        for r in range(int(max_planes)):
+            if len(P) < 3:
+                break
+            res = _segment(P, N, args[0], args[1], None if N is None else args[2], args[3], args[4], int(seed) + r, refine_rounds)
+            if res is None or res[2] < args[4]:
+                break
+            model, mask, count, _ = res
+            taken = mask.bool()
+            labels[rows[taken]] = r
+            planes.append(model)
+            sizes.append(count)
+            rows, P = rows[~taken], P[~taken].contiguous()
+            N = None if N is None else N[~taken].contiguous()
+    planes = np.array(planes, np.float64).reshape(-1, 4)
+    sizes = np.array(sizes, np.int32)
+    if to_host:
+        return Planes(planes, sizes, labels.cpu().numpy())
+    return Planes(planes, torch.from_numpy(sizes).to(device), labels)
+
+
+def ground_plane(planes, sizes, cam_centres, thr):
+    """The ground among detected planes: the plane of largest support (the first of equals) that has EVERY camera centre strictly on one
+    side, at more than thr -- cameras stand above a floor, while a wall or a table usually has one behind or below it. Returned (4,)
+    float64 with the sign that puts the cameras on its positive side (n . c + d > thr), or None when there is none. Host fp64."""
+    planes = np.asarray(planes, np.float64).reshape(-1, 4)
+    sizes = np.asarray(sizes).reshape(-1)
+    C3 = np.asarray(cam_centres, np.float64).reshape(-1, 3)
+    if len(planes) != len(sizes):
+        raise ValueError(f'ground_plane: {len(planes)} planes, {len(sizes)} sizes')
+    if len(C3) == 0 or not thr >= 0:
+        raise ValueError('ground_plane: needs camera centres and thr >= 0')
+    for k in np.argsort(-sizes.astype(np.int64), kind='stable'):
+        e = C3 @ planes[k, :3] + planes[k, 3]
+        if (e > thr).all():
+            return planes[k].copy()
+        if (e < -thr).all():
+            return -planes[k]
+    return None
+
+
+def upright_similarity(plane, up=(0.0, 1.0, 0.0)):
+    """The (4, 4) rigid motion of least angle that takes the plane's normal to `up` and the plane to height 0 (up . x' = 0 for x on the
+    plane): R = the rotation about n x up by the angle between them (about any axis perpendicular to n when n = -up), t = d up. Host fp64."""
+    m = np.asarray(plane, np.float64).reshape(4)
+    u = np.asarray(up, np.float64).reshape(3)
+    ln, lu = np.linalg.norm(m[:3]), np.linalg.norm(u)
+    if not (ln > 0 and lu > 0 and np.isfinite(m).all() and np.isfinite(u).all()):
+        raise ValueError(f'upright_similarity: plane {m.tolist()} / up {u.tolist()} have no direction')
+    n, d, u = m[:3] / ln, m[3] / ln, u / lu
+    axis = np.cross(n, u)
+    s, c = np.linalg.norm(axis), float(n @ u)
+    if s > 1e-12:
+        k = axis / s
+    else:                                                               # parallel: nothing to do, or half a turn about any perpendicular axis
+        k = np.cross(n, np.eye(3)[int(np.argmin(np.abs(n)))])
+        k /= np.linalg.norm(k)
+        s, c = 0.0, (1.0 if c > 0 else -1.0)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + s * K + (1.0 - c) * (K @ K)
+    T[:3, 3] = d * u
+    return T
+
+
+def transform_planes(planes, S):
+    """planes (P, 4) mapped by the similarity S = [s R | t]: n' = R n, d' = s d - n' . t, so that n' . (S x) + d' = s (n . x + d)"""
+    planes = np.asarray(planes, np.float64).reshape(-1, 4)
+    _, _, scale = similarity_parts(S)
+    S = np.asarray(S, np.float64)
+    R = S[:3, :3] / scale
+    n = planes[:, :3] @ R.T
+    return np.concatenate([n, (scale * planes[:, 3] - n @ S[:3, 3])[:, None]], axis=1)

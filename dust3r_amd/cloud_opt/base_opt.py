@@ -348,7 +348,7 @@ class BasePCOptimizer(nn.Module):
 
     @torch.no_grad()
     def fuse(self, voxel_size=None, min_count=1, weights='conf', to_host=True, normals=False, outliers=None, k=16, tracks=False, max_reproj_error=None,
-             clusters=None, keep_largest=None):
+             clusters=None, keep_largest=None, planes=None, upright=False):
         """The scene as ONE point cloud (new; the reference exports every masked pixel of every view): the masked points of all views
         (`get_masks()` at the scene's current min_conf_thr, as the GLB export) binned into voxels of `voxel_size` and averaged per voxel,
         weighted by the images' confidences (weights='conf') or equally (weights=None); `viz.fuse_points` on the scene's padded stacks,
@@ -361,7 +361,12 @@ class BasePCOptimizer(nn.Module):
         (`FusedCloud.estimate_normals(scene=self)`; csrc/cloud_knn.hip). tracks=True: last, on the final points, the 2-D tracks -- which
         pixel of which image observes each point, by projection within one voxel_size -- as `cloud.tracks` (`FusedCloud.build_tracks`;
         csrc/tracks.hip), observations landing more than max_reproj_error pixels off dropped; `export.write_colmap` then writes POINTS2D
-        and tracks. Returns a `viz.FusedCloud` (`.save_ply(path)`; `export.write_colmap` takes it)."""
+        and tracks. planes=N, or a dict of the arguments of `FusedCloud.detect_planes`: after the outlier and cluster removal and before
+        the tracks, the N dominant planes (csrc/cloud_planes.hip); the cloud carries `.planes`, `.plane_sizes` and `.plane_labels`.
+        upright=True (implies planes, 6 unless given): last, the cloud is stood on its ground plane (`FusedCloud.upright(scene=self)`: a
+        ValueError when no plane has every camera on one side). The tracks are built BEFORE that motion, in the scene's frame, and the
+        motion then drops them, as `FusedCloud.transform` always does: the scene's cameras do not see the moved points where the tracks
+        say, so tracks=True together with upright=True returns a cloud without tracks. Returns a `viz.FusedCloud` (`.save_ply(path)`; `export.write_colmap` takes it)."""
         if self.imgs is None:
             raise ValueError('fuse needs the scene images: scene.imgs is None (the views given to global_aligner had no "img")')
         if self.device.type != 'cuda':
@@ -370,6 +375,11 @@ class BasePCOptimizer(nn.Module):
             raise ValueError(f"fuse: weights is 'conf' or None, got {weights!r}")
         if keep_largest is not None and not clusters:
             clusters = True
+        if upright and planes is None:
+            planes = 6
+        plane_args = dict(planes) if isinstance(planes, dict) else {} if planes is None else dict(max_planes=planes)
+        if set(plane_args) - {'thr', 'max_planes', 'min_inliers', 'min_area2', 'cos_min', 'n_hyp', 'seed', 'refine_rounds', 'normals'}:
+            raise ValueError(f'fuse: planes is a number of planes or a dict of the arguments of FusedCloud.detect_planes, got {planes!r}')
         cluster_args = dict(clusters) if isinstance(clusters, dict) else {}
         if set(cluster_args) - {'eps', 'min_points'}:
             raise ValueError(f"fuse: clusters is True or a dict of 'eps' / 'min_points', got {clusters!r}")
@@ -387,8 +397,12 @@ class BasePCOptimizer(nn.Module):
                 cloud, _ = cloud.keep_clusters(largest=keep_largest)
         if normals:
             cloud = cloud.estimate_normals(k=k, scene=self)
+        if planes is not None:
+            cloud = cloud.detect_planes(**plane_args)
         if tracks:
             cloud = cloud.build_tracks(self, max_error=max_reproj_error, weights=weights)
+        if upright:
+            cloud, _ = cloud.upright(scene=self)
         return cloud
 
     @torch.no_grad()

@@ -7,8 +7,8 @@
 //   d3r_feature_nearest    feature_nearest_kernel     exhaustive nearest row of b for every row of a in 33 dimensions: THE HOT KERNEL
 //   d3r_sim3_ransac        sim3_hyp_kernel            one thread per hypothesis: counter-based sample of 3 correspondences (ransac.hpp), fp64 similarity
 //                          sim3_score_kernel          grid (correspondence chunk, round of RND hypotheses): ransac.hpp's round scorer
-//                          sim3_select_kernel         one workgroup: the largest count, then the lowest hypothesis
-//                          sim3_mask_kernel           the winner's inlier mask
+//                          sim3_select_kernel         one workgroup: the largest count, then the lowest hypothesis (ransac.hpp's selection)
+//                          sim3_mask_kernel           the winner's inlier mask (ransac.hpp's loop)
 // No floating-point atomics, no kernel waits on another workgroup, no scratch. The only atomics are integer additions of inlier counts
 // (sim3_score_kernel), whose result does not depend on their order: the same bytes on every run. Built without contraction: every
 // product and sum below is one IEEE rounding, which is what the numpy restatements compute; the fp32 3-vector arithmetic is fuse_grid.hpp's.
@@ -379,56 +379,31 @@ __global__ __launch_bounds__(SPT) void sim3_score_kernel(const Sim3Args a, const
     });
 }
 
-// (count, lowest h) as one key: the larger key wins
-D3R_DEV uint64_t sim3_key(int count, int h) { return ((uint64_t)(uint32_t)count << 32) | (uint32_t)(0x7FFFFFFF - h); }
-
 __global__ __launch_bounds__(QT) void sim3_select_kernel(const Sim3Args a, const Sim3Ws w, double* __restrict__ best_out) {
-    __shared__ uint64_t keys[QT];
-    __shared__ int nv[QT];
-    uint64_t key = 0;                                                     // below every valid hypothesis's key (h <= 0x7FFFFFFF - 1 there)
-    int n_valid = 0;
-    for (int h = threadIdx.x; h < a.n_hyp; h += QT) {
-        if (!w.valid[h]) continue;
-        n_valid += 1;
-        const uint64_t kh = sim3_key(w.counts[h], h);
-        key = kh > key ? kh : key;
-    }
-    keys[threadIdx.x] = key;
-    nv[threadIdx.x] = n_valid;
-    __syncthreads();
-    for (int o = QT / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            keys[threadIdx.x] = keys[threadIdx.x + o] > keys[threadIdx.x] ? keys[threadIdx.x + o] : keys[threadIdx.x];
-            nv[threadIdx.x] += nv[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    const ransac::Winner b = ransac::select_winner<QT>(a.n_hyp, w.valid, w.counts, 3);
     if (threadIdx.x != 0) return;
-    const int count = (int)(keys[0] >> 32);
-    const bool found = nv[0] > 0 && count >= 3;
-    const int h = found ? 0x7FFFFFFF - (int)(uint32_t)keys[0] : -1;
-    w.best->h = h;
-    w.best->count = found ? count : 0;
-    w.best->n_valid = nv[0];
-    best_out[0] = (double)h;
-    best_out[1] = (double)(found ? count : 0);
-    best_out[2] = (double)nv[0];
+    const bool found = b.h >= 0;
+    w.best->h = b.h;
+    w.best->count = b.count;
+    w.best->n_valid = b.n_valid;
+    best_out[0] = (double)b.h;
+    best_out[1] = (double)b.count;
+    best_out[2] = (double)b.n_valid;
     for (int c = 0; c < 12; ++c) {
-        best_out[3 + c] = found ? w.S[(size_t)h * 12 + c] : 0.0;
-        w.best->rows[c] = found ? w.rows[(size_t)h * 12 + c] : 0.f;
+        best_out[3 + c] = found ? w.S[(size_t)b.h * 12 + c] : 0.0;
+        w.best->rows[c] = found ? w.rows[(size_t)b.h * 12 + c] : 0.f;
     }
 }
 
 __global__ __launch_bounds__(QT) void sim3_mask_kernel(const Sim3Args a, const Sim3Ws w, uint8_t* __restrict__ inliers_out) {
-    const bool found = w.best->h >= 0;
     float m[12];
 #pragma unroll
     for (int c = 0; c < 12; ++c) m[c] = w.best->rows[c];
-    for (long long i = (long long)blockIdx.x * QT + threadIdx.x; i < a.n; i += (long long)gridDim.x * QT) {
+    ransac::write_mask<QT>(a.n, w.best->h >= 0, inliers_out, [&](long long i) {
         const float* p = a.p + (size_t)i * 3;
         const float* q = a.q + (size_t)i * 3;
-        inliers_out[i] = found && finite3(p) && finite3(q) && sim3_inlier(m, p[0], p[1], p[2], q[0], q[1], q[2], a.thr2);
-    }
+        return finite3(p) && finite3(q) && sim3_inlier(m, p[0], p[1], p[2], q[0], q[1], q[2], a.thr2);
+    });
 }
 
 }  // namespace cloud

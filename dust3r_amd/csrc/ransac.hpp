@@ -1,5 +1,6 @@
-// dust3r_amd -- what the two RANSACs share (PnP in visloc.hip, Sim(3) over correspondences in cloud_features.hip): the counter-based sampler and
-// the scoring of one round of hypotheses. Each file keeps its solver, its inlier test (compiled with its own flags), its loads and its selection.
+// dust3r_amd -- what the three RANSACs share (PnP in visloc.hip, Sim(3) over correspondences in cloud_features.hip, planes of a cloud in
+// cloud_planes.hip): the counter-based sampler and the scoring of one round of hypotheses; the two over clouds also the selection of the winner
+// and the loop that writes its mask. Each file keeps its solver, its inlier test (compiled with its own flags) and its loads.
 #pragma once
 #include "common.hpp"
 
@@ -62,6 +63,51 @@ D3R_DEV void score_round(const float* __restrict__ round_rows, const int* __rest
     __syncthreads();
     for (int t = threadIdx.x; t < RND; t += NT)
         if (cnt[t]) atomicAdd(&counts[t], cnt[t]);
+}
+
+// ---- what the two RANSACs over clouds (Sim(3) in cloud_features.hip, planes in cloud_planes.hip) share behind the scoring -------------------
+// (count, lowest h) as one key: the larger key wins
+D3R_DEV uint64_t winner_key(int count, int h) { return ((uint64_t)(uint32_t)count << 32) | (uint32_t)(0x7FFFFFFF - h); }
+
+struct Winner {
+    int h, count, n_valid;              // h = -1 and count = 0 when no valid hypothesis has min_count inliers
+};
+
+// One workgroup of NT threads (a power of two) selects among n_hyp scored hypotheses: the valid one with the largest count, among equals
+// the lowest h. A maximum over integer keys: the same whatever the order. Every thread gets the result. Once per kernel (it owns its LDS).
+template <int NT> D3R_DEV Winner select_winner(int n_hyp, const int* __restrict__ valid, const int* __restrict__ counts, int min_count) {
+    __shared__ uint64_t keys[NT];
+    __shared__ int nv[NT];
+    uint64_t key = 0;                                                     // below every valid hypothesis's key (h <= 0x7FFFFFFF - 1 there)
+    int n_valid = 0;
+    for (int h = threadIdx.x; h < n_hyp; h += NT) {
+        if (!valid[h]) continue;
+        n_valid += 1;
+        const uint64_t kh = winner_key(counts[h], h);
+        key = kh > key ? kh : key;
+    }
+    keys[threadIdx.x] = key;
+    nv[threadIdx.x] = n_valid;
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) {
+            keys[threadIdx.x] = keys[threadIdx.x + o] > keys[threadIdx.x] ? keys[threadIdx.x + o] : keys[threadIdx.x];
+            nv[threadIdx.x] += nv[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    const int count = (int)(keys[0] >> 32);
+    const bool found = nv[0] > 0 && count >= min_count;
+    Winner w;
+    w.h = found ? 0x7FFFFFFF - (int)(uint32_t)keys[0] : -1;
+    w.count = found ? count : 0;
+    w.n_valid = nv[0];
+    return w;
+}
+
+// the winner's mask over n rows, grid-stride with NT threads: out[i] = found && inlier(i)
+template <int NT, class Inlier> D3R_DEV void write_mask(long long n, bool found, uint8_t* __restrict__ out, Inlier inlier) {
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) out[i] = found && inlier(i);
 }
 
 }  // namespace ransac

@@ -14,7 +14,8 @@ compute_global_alignment -> get_3D_model_from_scene, and the rgb / depth / confi
 for all images, csrc/gallery.hip, no matplotlib). `scenegraph_options` is the rule of set_scenegraph_options as plain data, and
 `python -m dust3r_amd.demo` the command line in place of the gradio page; its --fuse / --ply / --colmap (new) also write the fused cloud of
 `scene.fuse()` as scene.ply and as a COLMAP model (`write_fused`, dust3r_amd/export.py); --fuse_normals / --fuse_outliers add normals and
-statistical outlier removal, --fuse_clusters / --fuse_keep_largest density clustering and the removal of all but the largest clusters."""
+statistical outlier removal, --fuse_clusters / --fuse_keep_largest density clustering and the removal of all but the largest clusters,
+--fuse_planes / --fuse_upright the dominant planes and the cloud stood on its ground."""
 import argparse
 import copy
 import json
@@ -375,13 +376,19 @@ def get_args_parser():
                              'EPS_IN_VOXELS: the neighbourhood radius in voxels (default 2.5) (implies --fuse)')
     parser.add_argument('--fuse_keep_largest', type=int, default=None, metavar='N',
                         help='keep only the N largest clusters of the fused cloud, which drops dense floaters (implies --fuse_clusters and --fuse)')
+    parser.add_argument('--fuse_planes', type=int, nargs='?', const=6, default=None, metavar='N',
+                        help='detect the N dominant planes of the fused cloud (default 6): scene.ply gets an int plane per point, cameras.json the '
+                             'planes and their sizes (implies --fuse)')
+    parser.add_argument('--fuse_upright', action='store_true',
+                        help='stand scene.ply on its ground plane (the largest plane with every camera on one side): y up, ground at height 0; '
+                             'cameras.json gets the 4x4 motion under "upright" (implies --fuse_planes and --fuse)')
     return parser
 
 
 def wants_fuse(args):
-    """--ply, --colmap, --fuse_normals, --fuse_outliers, --fuse_clusters and --fuse_keep_largest imply --fuse"""
+    """--ply, --colmap, --fuse_normals, --fuse_outliers, --fuse_clusters, --fuse_keep_largest, --fuse_planes and --fuse_upright imply --fuse"""
     return (args.fuse is not None or args.ply or args.colmap or args.fuse_normals or args.fuse_outliers is not None or args.fuse_clusters is not None or
-            args.fuse_keep_largest is not None)
+            args.fuse_keep_largest is not None or args.fuse_planes is not None or args.fuse_upright)
 
 
 def clamp_scenegraph(num_files, winsize, refid, scenegraph_type):
@@ -425,14 +432,19 @@ def write_cameras(outdir, scene):
 
 
 def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, ply=True, colmap=False, normals=False, outliers=None, tracks=False,
-                max_reproj_error=None, clusters=None, keep_largest=None):
+                max_reproj_error=None, clusters=None, keep_largest=None, planes=None, upright=False):
     """outdir/scene.ply and / or outdir/colmap of the scene's fused cloud (scene.fuse; export.write_ply / write_colmap), with the mask of
     get_3D_model_from_scene: min_conf_thr through the scene's confidence transform, the sky on request; normals / outliers / tracks /
     max_reproj_error as for scene.fuse. With tracks, their `stats()` are added to outdir/cameras.json (when it is there) under "tracks".
     clusters: None, or the eps of `FusedCloud.cluster` in voxels (0: its default); keep_largest=N keeps the N largest clusters (and implies
     clusters). The cluster count and the ten largest sizes are added to cameras.json under "clusters"; scene.ply gets an `int label`.
+    planes=N: the N dominant planes (`FusedCloud.detect_planes`): scene.ply gets an `int plane`, cameras.json "planes" (the models in the
+    scene's frame and their sizes). upright (implies planes=6): scene.ply is written stood on its ground (`FusedCloud.upright`) and the
+    motion goes to cameras.json under "upright" when a ground was found; the COLMAP model stays in the scene's frame, where its cameras are.
     Returns the file names."""
     from .export import write_colmap
+    if upright and planes is None:
+        planes = 6
     if mask_sky:
         scene = scene.mask_sky()
     scene.min_conf_thr = float(scene.conf_trf(torch.tensor(min_conf_thr)))
@@ -446,14 +458,19 @@ def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, 
             if math.isfinite(voxel_size) and voxel_size > 0:             # else: a scene without a valid point, which scene.fuse handles
                 cluster_args = dict(eps=float(clusters) * voxel_size)
     cloud = scene.fuse(voxel_size=voxel_size, normals=normals, outliers=outliers, tracks=tracks, max_reproj_error=max_reproj_error, clusters=cluster_args,
-                       keep_largest=keep_largest)
-    written = []
+                       keep_largest=keep_largest, planes=planes)
+    written, motion = [], None
+    if upright:
+        try:
+            stood, motion = cloud.upright(scene=scene)
+        except ValueError:                                                # no ground among the planes: the cloud stays as it is
+            stood = cloud
     if ply:
-        written.append(cloud.save_ply(os.path.join(outdir, 'scene.ply')))
+        written.append((stood if upright else cloud).save_ply(os.path.join(outdir, 'scene.ply')))
     if colmap:
         written += write_colmap(os.path.join(outdir, 'colmap'), scene, cloud)
     cameras = os.path.join(outdir, 'cameras.json')
-    if (tracks or cluster_args is not None) and os.path.isfile(cameras):
+    if (tracks or cluster_args is not None or planes is not None) and os.path.isfile(cameras):
         with open(cameras) as f:
             doc = json.load(f)
         if tracks:
@@ -461,6 +478,10 @@ def write_fused(outdir, scene, voxel_size=None, min_conf_thr=3, mask_sky=False, 
         if cluster_args is not None:
             sizes = [int(s) for s in (cloud.cluster_sizes.tolist() if cloud.cluster_sizes is not None else [])]
             doc['clusters'] = dict(count=len(sizes), largest=sizes[:10], kept=None if keep_largest is None else min(int(keep_largest), len(sizes)))
+        if planes is not None:
+            doc['planes'] = dict(models=[[float(v) for v in m] for m in cloud.planes], sizes=[int(v) for v in cloud.plane_sizes])
+            if motion is not None:
+                doc['upright'] = [[float(v) for v in row] for row in motion]
         with open(cameras, 'w') as f:
             json.dump(doc, f, indent=1)
     return written
@@ -491,7 +512,7 @@ def main(argv=None):
         written += write_fused(args.outdir, scene, voxel_size=args.fuse, min_conf_thr=args.min_conf_thr, mask_sky=args.mask_sky,
                                ply=args.ply or not args.colmap, colmap=args.colmap, normals=args.fuse_normals, outliers=args.fuse_outliers,
                                tracks=args.colmap_tracks, max_reproj_error=args.max_reproj_error, clusters=args.fuse_clusters,
-                               keep_largest=args.fuse_keep_largest)
+                               keep_largest=args.fuse_keep_largest, planes=args.fuse_planes, upright=args.fuse_upright)
     if not args.silent:
         print('(wrote', len(written), 'files to', args.outdir, ')')
     return 0

@@ -14,7 +14,7 @@ import numpy as np
 _PLY_VERTEX = [('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
 _PLY_TYPES = {'<f4': 'float', 'u1': 'uchar', '<i4': 'int'}
 _PLY_NORMAL = [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]       # directly after z, where MeshLab, Open3D and Poisson reconstruction expect them
-_PLY_OPTIONAL = {'confidence': '<f4', 'count': '<i4', 'label': '<i4'}
+_PLY_OPTIONAL = {'confidence': '<f4', 'count': '<i4', 'label': '<i4', 'plane': '<i4'}
 
 CAMERA_MODEL_PINHOLE = 1        # COLMAP's model id of PINHOLE (fx, fy, cx, cy)
 
@@ -31,11 +31,12 @@ def _rgb_rows(colors, n):
 
 
 # ---- PLY ------------------------------------------------------------------------------------------------------------------------------
-def write_ply(path, positions, colors, weight=None, count=None, normals=None, labels=None):
+def write_ply(path, positions, colors, weight=None, count=None, normals=None, labels=None, planes=None):
     """Binary little-endian PLY: per vertex `float x y z`, `float nx ny nz` when normals are given, `uchar red green blue`, then
-    `float confidence` (weight), `int count` and `int label` (the cluster of `FusedCloud.cluster`, -1 = noise) when given. positions
-    (M, 3), colors (M, 3) or (M, 4) (alpha dropped), weight (M,), count (M,), normals (M, 3), labels (M,) integers. Without normals and
-    labels the file is the one the four-argument call writes. Returns the path."""
+    `float confidence` (weight), `int count`, `int label` (the cluster of `FusedCloud.cluster`, -1 = noise) and `int plane` (the plane of
+    `FusedCloud.detect_planes`, -1 = none) when given. positions (M, 3), colors (M, 3) or (M, 4) (alpha dropped), weight (M,), count
+    (M,), normals (M, 3), labels and planes (M,) integers. Without normals, labels and planes the file is the one the four-argument call
+    writes. Returns the path."""
     positions = np.asarray(_host(positions), dtype=np.float32).reshape(-1, 3)
     colors = _rgb_rows(colors, len(positions))
     fields = list(_PLY_VERTEX)
@@ -46,11 +47,11 @@ def write_ply(path, positions, colors, weight=None, count=None, normals=None, la
             raise ValueError(f'write_ply: {len(positions)} positions, normals of shape {normals.shape}')
         fields[3:3] = _PLY_NORMAL
         extra.update(nx=normals[:, 0], ny=normals[:, 1], nz=normals[:, 2])
-    for name, arr in (('confidence', weight), ('count', count), ('label', labels)):
+    for name, arr in (('confidence', weight), ('count', count), ('label', labels), ('plane', planes)):
         if arr is not None:
             extra[name] = np.asarray(_host(arr)).reshape(-1)
-            if name == 'label' and extra[name].dtype.kind not in 'iu':
-                raise ValueError(f'write_ply: labels are integers, got {extra[name].dtype}')
+            if name in ('label', 'plane') and extra[name].dtype.kind not in 'iu':
+                raise ValueError(f'write_ply: {name}s are integers, got {extra[name].dtype}')
             if len(extra[name]) != len(positions):
                 raise ValueError(f'write_ply: {len(positions)} positions, {len(extra[name])} values of {name}')
             fields.append((name, _PLY_OPTIONAL[name]))
@@ -69,7 +70,7 @@ def write_ply(path, positions, colors, weight=None, count=None, normals=None, la
 
 def read_ply(path):
     """Reads the dialect `write_ply` writes (binary little-endian, one vertex element, the properties above in that order): a dict of
-    positions (M, 3) float32, colors (M, 3) uint8 and, when present, normals (M, 3) float32, confidence (M,) float32, count (M,) int32 and label (M,) int32."""
+    positions (M, 3) float32, colors (M, 3) uint8 and, when present, normals (M, 3) float32, confidence (M,) float32, count (M,) int32, label (M,) int32 and plane (M,) int32."""
     with open(path, 'rb') as f:
         raw = f.read()
     end = raw.find(b'end_header\n')

@@ -165,7 +165,9 @@ class FusedCloud:
     with to_host=False. voxel_size, origin (3,) float32 (the minimum of the fused points: voxel (i, j, k) starts at origin + voxel_size (i, j,
     k)) and bounds = (min, max) of the fused points, (+inf, -inf) for an empty cloud. After `cluster`: labels (M,) int32, the cluster of every
     point (-1 = noise), and cluster_sizes (C,) int32; they follow the points through estimate_normals, build_tracks, remove_outliers,
-    keep_clusters and transform."""
+    keep_clusters and transform. After `detect_planes`: planes (P, 4) float64 (n, d), plane_sizes (P,) int32 and plane_labels (M,) int32, the
+    plane of every point (-1 = none); they follow the points the same way, and `transform` maps the planes. The three are set by
+    `detect_planes` or `with_planes`, not by the constructor, whose arguments stay the eleven they were."""
 
     def __init__(self, positions, colors, weight, count, voxel_size, bounds, normals=None, curvature=None, tracks=None, labels=None, cluster_sizes=None):
         self.positions, self.colors, self.weight, self.count = positions, colors, weight, count
@@ -175,14 +177,29 @@ class FusedCloud:
         self.normals, self.curvature = normals, curvature      # (M, 3) float32 and (M,) float32 of `estimate_normals`, else None
         self.tracks = tracks                                   # the `CloudTracks` of `build_tracks`, else None
         self.labels, self.cluster_sizes = labels, cluster_sizes    # (M,) int32 (-1 = noise) and (C,) int32 of `cluster`, else None
+        self.planes = self.plane_sizes = self.plane_labels = None  # (P, 4) float64, (P,) int32, (M,) int32 of `detect_planes` / `with_planes`
 
     PER_POINT = ('positions', 'colors', 'weight', 'count', 'normals', 'curvature', 'labels')      # one row per point: what a subset masks
+    PLANE_FIELDS = ('planes', 'plane_sizes', 'plane_labels')   # set after construction; plane_labels is one row per point too (PER_POINT_ROWS)
+    PER_POINT_ROWS = PER_POINT + ('plane_labels',)
 
     def _with(self, **changes):
         """A new cloud with this cloud's fields, the named ones replaced: a deriving method says only what it changes. The attributes ARE the
-        constructor's arguments, plus origin, which follows bounds."""
-        fields = {name: value for name, value in vars(self).items() if name != 'origin'}
-        return FusedCloud(**dict(fields, **changes))
+        constructor's arguments, plus origin, which follows bounds, plus the three plane fields, which are set on the new cloud."""
+        apart = ('origin',) + self.PLANE_FIELDS
+        fields = {name: value for name, value in vars(self).items() if name not in apart}
+        plane_fields = {name: changes.pop(name, getattr(self, name)) for name in self.PLANE_FIELDS}
+        out = FusedCloud(**dict(fields, **changes))
+        for name, value in plane_fields.items():
+            setattr(out, name, value)
+        return out
+
+    def with_planes(self, planes, plane_sizes, plane_labels):
+        """A new cloud carrying these planes (P, 4), their sizes (P,) and the plane of every point (M,), -1 = none: what `detect_planes`
+        attaches, for planes that come from elsewhere (a file, another tool)"""
+        if len(plane_labels) != len(self) or len(planes) != len(plane_sizes):
+            raise ValueError(f'with_planes: {len(self)} points and {len(plane_labels)} labels, {len(planes)} planes and {len(plane_sizes)} sizes')
+        return self._with(planes=np.asarray(planes, np.float64).reshape(-1, 4), plane_sizes=plane_sizes, plane_labels=plane_labels)
 
     def __len__(self):
         return len(self.positions)
@@ -192,7 +209,8 @@ class FusedCloud:
         (export.write_ply)."""
         from .export import write_ply
         return write_ply(path, *(_to_numpy(a) for a in (self.positions, self.colors, self.weight, self.count)),
-                         normals=None if self.normals is None else _to_numpy(self.normals), labels=None if self.labels is None else _to_numpy(self.labels))
+                         normals=None if self.normals is None else _to_numpy(self.normals), labels=None if self.labels is None else _to_numpy(self.labels),
+                         planes=None if self.plane_labels is None else _to_numpy(self.plane_labels))
 
     def _neighbour_radius(self, max_dist):
         """max_dist of the neighbour searches: 8 voxels unless given. A surface sampled at spacing v holds about pi r^2 / v^2 points within
@@ -204,10 +222,11 @@ class FusedCloud:
         return 8.0 * self.voxel_size
 
     def _subset(self, keep):
-        """(cloud, mask) of the points where the device bool tensor `keep` is set: normals, curvature and labels are carried along
-        (cluster_sizes too: they still describe the labels), tracks are not. The mask comes back where this cloud's arrays are."""
+        """(cloud, mask) of the points where the device bool tensor `keep` is set: normals, curvature, labels and plane labels are carried
+        along (cluster_sizes, planes and plane_sizes too: they still describe the labels), tracks are not. The mask comes back where this
+        cloud's arrays are."""
         mask = keep if isinstance(self.positions, torch.Tensor) else keep.cpu().numpy()
-        rows = {name: getattr(self, name) for name in self.PER_POINT}
+        rows = {name: getattr(self, name) for name in self.PER_POINT_ROWS}
         return self._with(tracks=None, **{name: a[mask] for name, a in rows.items() if a is not None}), mask
 
     @torch.no_grad()
@@ -341,7 +360,82 @@ class FusedCloud:
             bounds = (lo, hi) if n_valid > 0 else self.bounds
             if not on_device:
                 positions, normals = positions.cpu().numpy(), None if normals is None else normals.cpu().numpy()
-        return self._with(positions=positions, normals=normals, voxel_size=self.voxel_size * scale, bounds=bounds, tracks=None)
+        from .cloud_metrics import transform_planes
+        planes = None if self.planes is None else transform_planes(self.planes, S)
+        return self._with(positions=positions, normals=normals, voxel_size=self.voxel_size * scale, bounds=bounds, tracks=None, planes=planes)
+
+    @torch.no_grad()
+    def detect_planes(self, thr=None, max_planes=6, min_inliers=None, min_area2=None, cos_min=None, **kw):
+        """A new cloud carrying `.planes` (P, 4) float64, `.plane_sizes` (P,) int32 and `.plane_labels` (M,) int32 (-1 = no plane): the
+        dominant planes in extraction order, on the GPU (cloud_metrics.detect_planes, which has the definition; csrc/cloud_planes.hip).
+        thr: the inlier distance, default 2 voxels: a fused point is the mean of its voxel's samples, so it lies within about half a
+        voxel of the surface plus the depth noise of the views, which the voxel size (the median pixel footprint) is of the order of;
+        2 voxels take both in, and two parallel surfaces closer than that were fused into one layer anyway. min_area2: the least
+        twice-area of a sampled triangle, default (8 thr)^2: points that err by thr over legs of 8 thr tilt the hypothesis by 7 degrees
+        at the most (cloud_metrics._plane_args), and a floor or wall spans hundreds of voxels, so few samples on it are lost.
+        cos_min: with it the cloud's normals must agree with the plane's (|cos| >= cos_min; the cloud needs `estimate_normals`).
+        min_inliers: default 2 % of the cloud. Further arguments (n_hyp, seed, refine_rounds, normals) go to cloud_metrics.detect_planes.
+        ValueError for a cloud without a voxel size when thr is not given, unless it is empty. The points are the same ones: normals,
+        labels and tracks are kept. Arrays come back where this cloud's are."""
+        from .cloud_metrics import detect_planes
+        if thr is None:
+            if not (math.isfinite(self.voxel_size) and self.voxel_size > 0):
+                if len(self) > 0:
+                    raise ValueError(f'the cloud has no voxel size ({self.voxel_size!r}): give thr')
+                thr = 1.0                                                  # an empty cloud: any threshold gives the same nothing
+            else:
+                thr = 2.0 * self.voxel_size
+        res = detect_planes(self, thr, max_planes=max_planes, min_inliers=min_inliers, min_area2=min_area2, cos_min=cos_min,
+                            to_host=not isinstance(self.positions, torch.Tensor), **kw)
+        return self._with(planes=res.planes, plane_sizes=res.plane_sizes, plane_labels=res.plane_labels)
+
+    def _need_planes(self, what):
+        if self.planes is None or self.plane_labels is None:
+            raise ValueError(f'{what}: the cloud has no planes: call detect_planes() first')
+
+    def remove_planes(self, labels=None):
+        """(cloud, keep) of a cloud with planes (`detect_planes`), like `remove_outliers`: the points that lie on none of the planes
+        `labels` (default: on no plane at all), keep (M,) bool. planes, plane_sizes and the remaining plane_labels stay as they are
+        (nothing is renumbered). Tracks are DROPPED, as in `remove_outliers`."""
+        self._need_planes('remove_planes')
+        n_planes = len(self.planes)
+        gone = np.ones(n_planes, bool)
+        if labels is not None:
+            wanted = np.asarray(list(labels))
+            if wanted.size and (wanted.dtype.kind not in 'iu' or wanted.min() < 0 or wanted.max() >= n_planes):
+                raise ValueError(f'remove_planes: labels {list(labels)!r} are not planes 0 .. {n_planes - 1}')
+            gone = np.zeros(n_planes, bool)
+            gone[wanted.astype(np.int64)] = True
+        own = self.plane_labels if isinstance(self.plane_labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(self.plane_labels))
+        table = torch.from_numpy(np.concatenate([~gone, [True]])).to(own.device)             # the last entry answers label -1
+        return self._subset(table[own.long()])
+
+    def upright(self, scene=None, cam_centres=None, thr=None):
+        """(cloud, T): the cloud moved by the (4, 4) rigid motion T that stands it on its ground: `cloud_metrics.ground_plane` of the
+        detected planes -- the largest that has every camera centre (cam_centres (V, 3), or those of `scene`) on one side at more than thr
+        (default 2 voxels) -- then `cloud_metrics.upright_similarity`: the ground's normal goes to (0, 1, 0) by the least rotation, the
+        ground to height 0, the cameras to positive heights. ValueError when no plane qualifies. As `transform`, the result has no tracks."""
+        from .cloud_metrics import ground_plane, upright_similarity
+        self._need_planes('upright')
+        if (scene is None) == (cam_centres is None):
+            raise ValueError('upright: give exactly one of scene, cam_centres')
+        if cam_centres is None:
+            cam_centres = _to_numpy(scene.get_im_poses().detach())[:, :3, 3]
+        if thr is None:
+            thr = 2.0 * self.voxel_size if math.isfinite(self.voxel_size) and self.voxel_size > 0 else 0.0
+        ground = ground_plane(self.planes, _to_numpy(self.plane_sizes), cam_centres, thr)
+        if ground is None:
+            raise ValueError(f'upright: none of the {len(self.planes)} planes has every camera on one side at more than {thr!r}')
+        T = upright_similarity(ground)
+        return self.transform(T), T
+
+    def colored_by_plane(self):
+        """A new cloud whose colours are `label_colors` of its plane labels: grey where there is no plane"""
+        self._need_planes('colored_by_plane')
+        colors = label_colors(self.plane_labels)
+        if isinstance(self.colors, torch.Tensor):
+            colors = torch.from_numpy(colors).to(self.colors.device)
+        return self._with(colors=colors)
 
     @torch.no_grad()
     def feature_cloud(self, cell=None):

@@ -701,6 +701,43 @@ size_t d3r_sim3_ransac_workspace_bytes(int n_corr, int n_hyp);
 int d3r_sim3_ransac(int n_corr, const float* p, const float* q, unsigned long long seed, int n_hyp, float thr, double ratio_min, int with_scale,
                     double* best_out, uint8_t* inliers_out, void* workspace, void* stream);
 
+/* Plane detection on a cloud (new; csrc/cloud_planes.hip): a RANSAC over the points of ONE cloud and the support of a given plane
+ * (dust3r_amd/cloud_metrics.py, plane_ransac / segment_plane / detect_planes). points [n][3] DEVICE fp32, normals [n][3] DEVICE fp32 or
+ * NULL; validity as in the cloud metrics above; every fp32 and fp64 operation below is rounded on its own (no contraction), in the order
+ * written. A plane is (n_x, n_y, n_z, d): the points with n . x + d = 0.
+ * THE INLIER TEST of a plane row m = (n_x, n_y, n_z, d) fp32: point i is an INLIER when it is valid and, in fp32,
+ *   e = ((n_x x + n_y y) + n_z z) + d has |e| <= thr; with normals also: its normal u is finite, is not (0, 0, 0), and
+ *   |((n_x u_x + n_y u_y) + n_z u_z)| >= cos_min. The test does not see the sign of a normal: fused normals may point either way.
+ * d3r_plane_ransac: n >= 3, 1 <= n_hyp <= D3R_SIM3_MAX_HYPOTHESES, thr > 0 and finite, cos_min not NaN (used only with normals),
+ *   min_area2 > 0, min_inliers >= 3. HYPOTHESIS h: the three points p0, p1, p2 of the sampler of d3r_sim3_ransac among n (the first three
+ *   distinct draws; fewer: invalid). In fp64 from the fp32 points: u = p1 - p0, v = p2 - p0, c = u x v (a component is one difference
+ *   of two products: c_x = u_y v_z - u_z v_y, c_y = u_z v_x - u_x v_z, c_z = u_x v_y - u_y v_x), l = sqrt((c_x c_x + c_y c_y) + c_z c_z),
+ *   n = c / l, d = -((n_x p0_x + n_y p0_y) + n_z p0_z). INVALID when a sampled point is not valid, when l >= min_area2 does not hold
+ *   (l is twice the triangle's area: one number rejects tiny and near-collinear triangles), or when an entry of (n, d) is not finite;
+ *   decided before any scoring. SCORE: the inlier test of the row float32(n, d) over all points. THE WINNER: the valid hypothesis with
+ *   the largest inlier count, among equals the lowest h. best_out [7] fp64 = { h, or -1 when no valid hypothesis has min_inliers
+ *   inliers; its count (0 with -1); the number of valid hypotheses; n_x, n_y, n_z, d in fp64 (0 with -1) }; inliers_out [n] uint8 =
+ *   the winner's mask (0 with -1). n_hyp is fixed: no adaptive stopping. One thread per hypothesis; a scoring kernel with the rows of
+ *   256 hypotheses in LDS and 8 points (and normals) per lane in registers, which skips invalid hypotheses and rounds without a valid
+ *   one; one workgroup selects. Integer atomic additions of counts only: the same seed gives the same bytes. workspace:
+ *   d3r_plane_ransac_workspace_bytes(n, n_hyp) bytes (0 for invalid sizes).
+ * d3r_plane_support: n >= 1; plane [4] HOST fp32 and centre [3] HOST fp32, finite (read during the call); thr, cos_min as above.
+ *   mask_out [n] DEVICE uint8 (optional) = the inlier test of `plane`; count_out [1] DEVICE int64 = the inliers; sums_out [9] DEVICE
+ *   fp64 = the moments of the inliers about centre: with a = p - centre in fp64 from the fp32 values,
+ *   { sum a_x, sum a_y, sum a_z, sum a_x a_x, sum a_x a_y, sum a_x a_z, sum a_y a_y, sum a_y a_z, sum a_z a_z }.
+ *   Each sum is the fp64 sum of the stated terms over the inliers in a fixed order: the same bytes on every run, within
+ *   2 (n - 1) 2^-53 sum |term| of any other order. One launch pair, no second pass over the points. workspace:
+ *   d3r_plane_support_workspace_bytes(n) bytes of DEVICE memory (0 for n <= 0).
+ * No floating-point atomics, no waiting between workgroups, no scratch. D3R_ERR_INVALID on NULL (normals and mask_out may be NULL), sizes,
+ * thr, cos_min, min_area2 or min_inliers out of range, a non-finite plane or centre; nothing is launched then. No allocation, no
+ * synchronisation. */
+size_t d3r_plane_ransac_workspace_bytes(int n, int n_hyp);
+int d3r_plane_ransac(int n, const float* points, const float* normals, unsigned long long seed, int n_hyp, float thr, float cos_min,
+                     double min_area2, int min_inliers, double* best_out, uint8_t* inliers_out, void* workspace, void* stream);
+size_t d3r_plane_support_workspace_bytes(int n);
+int d3r_plane_support(int n, const float* points, const float* normals, const float* plane, float thr, float cos_min, const float* centre,
+                      uint8_t* mask_out, long long* count_out, double* sums_out, void* workspace, void* stream);
+
 /* 2-D tracks of a cloud in the views of a scene (new; csrc/tracks.hip): which pixel of which view observes each point, by projection.
  * pts [n][row][3], mask [n][row], weight [n][row] or NULL, img_h / img_w [n]: the scene's stacks as for d3r_fuse_bounds (n * row <= 2^31 - 1,
  * 1 <= n <= 65535; what lies behind a view's h w elements is never read; a view whose h w exceeds row is empty). positions [M][3] DEVICE
@@ -879,7 +916,7 @@ int d3r_pnp_ransac(int n_jobs, const d3r_pnp_ransac_job* jobs, const d3r_pnp_ran
  * world correspondences, the 4th picking the root; pose_out [12] world -> camera; returns 1 when a pose was found.
  * d3r_selftest_p3p_roots_host: every P3P solution for 3 unit bearings f [3][3] and world points X [3][3] (R_out [4][9], t_out [4][3]);
  * returns their number. d3r_selftest_ransac_iters_host: the stopping rule. d3r_selftest_draw_distinct_host: the sample of hypothesis h
- * that d3r_pnp_ransac (k = 4) and d3r_sim3_ransac (k = 3) draw among n points, into idx_out [k]; returns 1 when 64 draws gave k distinct
+ * that d3r_pnp_ransac (k = 4), d3r_sim3_ransac and d3r_plane_ransac (k = 3) draw among n points, into idx_out [k]; returns 1 when 64 draws gave k distinct
  * indices, 0 when not (idx_out then ends in -1), -1 for another k. */
 int d3r_selftest_p3p_host(const double* uv, const double* X, double fx, double fy, double cx, double cy, double* pose_out);
 int d3r_selftest_p3p_roots_host(const double* f, const double* X, double* R_out, double* t_out);
