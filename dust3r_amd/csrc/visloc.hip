@@ -219,13 +219,17 @@ D3R_DEV void scaled_rows(const double* pose, const d3r_pnp_ransac_job& J, float*
     }
 }
 
-// the inlier test of every RANSAC stage: in front of the camera and squared pixel error <= thr^2, multiplied through by z^2
+// the inlier test of every RANSAC stage: in front of the camera and squared pixel error <= thr^2, multiplied through by z^2. The right side
+// must be finite: a world point with an infinite coordinate can give z = +inf, and inf <= inf would make it an inlier (of the LM set too,
+// where its NaN residual freezes the polish). A NaN or infinity anywhere else already fails one of the comparisons, so with this term a row
+// with a non-finite coordinate is never an inlier; for finite rows the term is true and the rest is the expression it always was.
 D3R_DEV bool is_inlier(const float* rows, float X, float Y, float Z, float a, float b, float thr2) {
     const float x = rows[0] * X + rows[1] * Y + rows[2] * Z + rows[3];
     const float y = rows[4] * X + rows[5] * Y + rows[6] * Z + rows[7];
     const float z = rows[8] * X + rows[9] * Y + rows[10] * Z + rows[11];
     const float ex = x - a * z, ey = y - b * z;
-    return z > 0.f && ex * ex + ey * ey <= thr2 * (z * z);
+    const float lim = thr2 * (z * z);
+    return z > 0.f && lim < INFINITY && ex * ex + ey * ey <= lim;
 }
 
 __global__ __launch_bounds__(64) void pnp_init_kernel(const d3r_pnp_ransac_job* __restrict__ jobs, int max_points, void* workspace) {

@@ -884,7 +884,8 @@ int d3r_match_pairs(int n_pairs, const d3r_match_job* jobs, int max_pixels, void
 /* One PnP-RANSAC problem of d3r_pnp_ransac: n correspondences, pixels pts2d [n][2] (undistorted) and world points pts3d [n][3], DEVICE
  * fp32. Pinhole fx, fy, cx, cy; reprojection threshold thr in pixels; at most max_iters hypotheses, stopped early by OpenCV's
  * RANSACUpdateNumIters at `confidence`; sampling keyed by `seed` and the hypothesis index only. inlier_mask: DEVICE uint8 [n] output
- * (inliers of the returned pose), or NULL. */
+ * (inliers of the returned pose), or NULL. Rows may hold NaN or infinities: such a row is never an inlier, of no hypothesis, of the set
+ * the polish runs over, or of the returned pose (a sample that draws one gives no hypothesis); rows are not filtered beforehand. */
 typedef struct {
     const float* pts2d;
     const float* pts3d;

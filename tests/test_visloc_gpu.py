@@ -5,11 +5,9 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from test_visloc_cpu import CX, CY, FX, FY, IMG_H, IMG_W, K, pnp_abi
 
-FX, FY, CX, CY = 520.0, 480.0, 300.5, 210.25
-K = np.array([[FX, 0, CX], [0, FY, CY], [0, 0, 1.0]])
-IMG_W, IMG_H = 640, 480
+pytestmark = pytest.mark.gpu
 
 
 def _problem(n, outliers, noise, seed):
@@ -298,24 +296,9 @@ def test_localize_equals_visloc_loop_on_the_engine(gpu):
 
 # ---- kernel-level failure paths, stopping and tie rules, call splitting, padding ---------------------------------------------------------
 def _pnp_abi(jobs, gpu, max_iters=10_000):
-    """d3r_pnp_ransac straight through the C ABI (no Python-side n <= 4 shortcut): [(status, inliers, drawn, best index)]"""
-    import ctypes as C
-    from dust3r_amd._lib import PnpRansacJob, PnpRansacParams, check, current_stream, lib, ptr
-    from dust3r_amd.visloc.localization import _records
-    keep, recs = [], []
-    for uv, X in jobs:
-        p2 = torch.as_tensor(uv, dtype=torch.float32, device=gpu).reshape(-1, 2).contiguous()
-        p3 = torch.as_tensor(X, dtype=torch.float32, device=gpu).reshape(-1, 3).contiguous()
-        keep += [p2, p3]
-        recs.append(PnpRansacJob(p2.data_ptr(), p3.data_ptr(), None, len(p2), max_iters, FX, FY, CX, CY, 5.0, 0.9999, 0))
-    m = len(recs)
-    params = PnpRansacParams(max_iters, max(max(r.n for r in recs), 1))
-    rec = _records(recs, PnpRansacJob, gpu)
-    work = torch.empty(int(lib.d3r_pnp_ransac_workspace(m, params.max_points)), dtype=torch.uint8, device=gpu)
-    poses = torch.empty((m, 12), dtype=torch.float64, device=gpu)
-    inl, status, stats = (torch.empty(s, dtype=torch.int32, device=gpu) for s in (m, m, (m, 2)))
-    check(lib.d3r_pnp_ransac(m, ptr(rec), C.byref(params), ptr(work), ptr(poses), ptr(inl), ptr(status), ptr(stats), current_stream()), 'pnp')
-    return [(int(a), int(b), int(c), int(d)) for a, b, (c, d) in zip(status.cpu(), inl.cpu(), stats.cpu().tolist())]
+    """d3r_pnp_ransac straight through the C ABI (test_visloc_cpu.pnp_abi, shared with test_visloc_ransac_gpu.py):
+    [(status, inliers, drawn, best index)]"""
+    return pnp_abi(jobs, gpu, max_iters)[0]
 
 
 def test_pnp_kernel_failures_stopping_and_ties(gpu):
